@@ -2,14 +2,26 @@
 """Benchmark of the hot path on MI355X (contract: see the round prompt / DESIGN.md section 7).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3p|c2|c1|c5|c3se|c2t|c3t] [--dtype mixed|bf16|f16]
-                    [--streams S]
+                    [--streams S] [--full] [--dump-outputs DIR]
 
 A step = one forward pass of the north-star path (PerceptionAgent -> pool -> CPEA -> STFT -> MaskSynthesisAgent ->
 apply_mask -> iSTFT) over one batch of synthetic 16 kHz utterances that is already resident in HBM.  Default workload = the
 shape BASELINE.json's metric is quoted on ("512-frame utts", target shape "batch 256 x 512-frame utterances"): c3p = batch
 256 x 512 STFT frames (L = 40 880), forward, 16-bit MFMA operands (default policy "mixed": fp16 GEMM operands, bf16
 attention core) with fp32 accumulation.  value = STFT frames/s over all ranks (utterances shard over ranks: no data-path
-collective).  The default N = 1 line also carries, as sub-records measured after the timed region:
+collective).
+
+A plain run does only what that figure needs: set-up, warm-up (with the calibration of the passes in flight), the K timed steps,
+the outputs of the last step if --dump-outputs DIR is given, the result line.  --dump-outputs writes what the last timed step
+returned (forward: every array of the path's output dict; training: the loss and the trained flat fp32 parameters) as
+DIR/<name>.npy in float32 (float64 for float64 and integer results), at most 64 MB in all: an array larger than its share is
+replaced by a fixed seeded sample of its flattened elements.  Inputs and weights are seeded, so two builds run with the same
+arguments can be compared output for output.
+
+Everything else is measured only with --full: the instrumented pass (`breakdown_ms_per_step`, the dominant family and its
+`roofline`, event-timed per launch inside the timed region), three sequential passes (`single_pass_ms_per_step`,
+`roofline.exclusive_*`), the `attention` figure inside the pass, and for the default N = 1 line the sub-records measured after
+the timed region:
   `configs1`  BASELINE configs[1] (B 64 x 4 s, T 801) through the same path: ms per step, frames/s, dominant kernel + roofline,
               the attention kernel inside that pass
   `train`     BASELINE configs[2] on the north-star composition (c3t: B 256 x 4 s, forward + objective + backward through
@@ -17,6 +29,8 @@ collective).  The default N = 1 line also carries, as sub-records measured after
               dominant family + roofline, final loss, skipped steps (0 in the timed steps)
   `headline`  the attention kernel ALONE at B 256 x T 512 x 4 heads x 64, bf16 (north_star's >= 30 % of bf16 MFMA peak)
   `sustained`, `mask_rmse`, `cpu_baseline` (the oracle on the host cores, bounded sample, N = 1 only).
+With --gpus N > 1 the default --full line carries `dp_train` instead of `train`; the training workloads' --full lines carry the
+roofline, the per-family breakdown and `cpu_baseline`.
 
 Launching: `python bench.py --gpus N` with no torchrun environment starts the N ranks itself (child processes, before this
 process touches the GPU); under `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N` the ranks are the
@@ -198,6 +212,46 @@ def cpu_baseline_path_train(weights, L, iters=3, batch=4):
     return {"value": batch * T / dt, "unit": "STFT frames/s", "cores": cores, "kind": "port",
             "sample": "oracle (torch fp32 autograd restatement) forward+backward of the same step, batch %d x %d samples, %d "
                       "iterations, %.1f s each; no optimiser step" % (batch, L, iters, dt)}
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# --dump-outputs: what the last timed step returned
+# ---------------------------------------------------------------------------------------------------------------
+DUMP_BUDGET = 60 << 20                  # bytes of .npy payload in all (under 64 MB with the headers)
+
+
+def collect_outputs(named, budget=DUMP_BUDGET):
+    """{name: tensor} -> {name: numpy array}: floating results in float32 (float64 stays float64), integer / bool results in
+    float64.  Arrays are taken smallest first; one that fits in its even share of what is left of the budget is kept whole with
+    its shape, a larger one becomes a 1-D sample of its flattened elements at sorted indices drawn from a generator seeded by
+    its name (the same positions in every run and every build for the same shapes).  Reads device tensors: call it after the
+    device has finished the step."""
+    import zlib
+    import numpy as np
+    import torch
+    items = sorted(((k, v.detach()) for k, v in named.items() if torch.is_tensor(v)), key=lambda kv: (kv[1].numel(), kv[0]))
+    out, left = {}, budget
+    for i, (k, v) in enumerate(items):
+        dt = torch.float32 if v.is_floating_point() and v.dtype != torch.float64 else torch.float64
+        share = left // (len(items) - i) // (4 if dt == torch.float32 else 8)
+        if v.numel() <= share:
+            a = v.to(dt).cpu().numpy()
+        else:
+            idx = np.unique(np.random.default_rng(zlib.crc32(k.encode())).integers(0, v.numel(), share))
+            a = v.reshape(-1)[torch.from_numpy(idx).to(v.device)].to(dt).cpu().numpy()
+        out[k] = a
+        left -= a.nbytes
+    return out
+
+
+def write_outputs(dirname, arrays):
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+    print("[bench] outputs of the last timed step -> %s: %s" % (dirname, ", ".join("%s %s %s" % (k, a.dtype, a.shape)
+                                                                              for k, a in sorted(arrays.items()))),
+          file=sys.stderr, flush=True)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -387,9 +441,11 @@ def settle_loss_scale(step, opt, scaler, min_steps, barrier=None):
     return n
 
 
-def train_leg(args, workload, rank, world, steps, warmup, batch=0, profile=True):
-    """warm-up (incl. settling the loss scale), one instrumented step alone on the device (per-family breakdown), then `steps`
-    timed steps between barriers with the dominant family event-timed per launch.  Every rank calls it; returns a dict."""
+def train_leg(args, workload, rank, world, steps, warmup, batch=0, profile=True, keep_outputs=False):
+    """warm-up (incl. settling the loss scale), one instrumented step alone on the device (per-family breakdown; profile only),
+    then `steps` timed steps between barriers (profile: with the dominant family event-timed per launch).  keep_outputs: the
+    record's `outputs` = collect_outputs of the last timed step's loss and the trained flat fp32 parameters.  Every rank calls
+    it; returns a dict."""
     import torch
     import torch.distributed as dist
     from sincformer_metacog_speech_enhancement_amd import ops
@@ -428,6 +484,7 @@ def train_leg(args, workload, rank, world, steps, warmup, batch=0, profile=True)
     if profile:
         launches = ops.profiler.launches(dominant)
         ops.profiler.disable()
+    outputs = collect_outputs({"loss": loss.detach().reshape(1), "params": opt.flat_p}) if keep_outputs else None
     tmax = torch.tensor([elapsed], device="cuda", dtype=torch.float64)
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -440,7 +497,7 @@ def train_leg(args, workload, rank, world, steps, warmup, batch=0, profile=True)
            "allreduce_bytes_per_step": opt.sync.bytes_per_step() if world > 1 else 0,
            "allreduce_buckets": len(opt.sync.buckets), "overlap": bool(opt.sync.overlap),
            "exposed_allreduce_ms_per_step": opt.sync.exposed_ms() if world > 1 else None,
-           "breakdown": breakdown, "dominant": dominant, "launches": launches}
+           "breakdown": breakdown, "dominant": dominant, "launches": launches, "outputs": outputs}
     if scaler is not None:
         s1 = scaler.stats()
         rec["loss_scale"] = {"scale": s1["scale"], "init_scale": 65536.0,
@@ -495,9 +552,9 @@ def main_train(args):
     SpeechEnhancer; c2t / c3t: the north-star SincNet + Conformer composition at B 64 / B 256)."""
     import torch.distributed as dist
     rank, world = init_ranks(args)
-    r = train_leg(args, args.workload, rank, world, args.steps, args.warmup, batch=args.batch)
+    r = train_leg(args, args.workload, rank, world, args.steps, args.warmup, batch=args.batch, profile=args.full,
+                  keep_outputs=bool(args.dump_outputs) and rank == 0)
     if rank == 0:
-        sub = train_subrecord(r, args.workload)
         line = {
             "metric": METRIC,
             "value": r["frames_per_s"], "unit": "STFT frames/s trained (whole job)", "n_gpus": world, "steps": args.steps,
@@ -508,20 +565,24 @@ def main_train(args):
                        "sharding": "utterances over ranks; one bucketed all-reduce (RCCL) of the flat fp32 gradient per step, "
                                    "overlapped with backward", "optimizer": "AdamW lr 5e-4 betas (0.9, 0.98) wd 0.01, clip 5.0",
                        "dropout": "module defaults (0.1 / 0.15)" if r["whole_path"] else 0.15},
-            "roofline": sub["roofline"],
             "frames_per_s_per_gpu": r["frames_per_s"] / world,
             "final_loss": r["final_loss"], "optimizer_state": r["optimizer_state"],
             "applied_steps_in_timed_region": r["applied_steps_in_timed_region"],
             "allreduce_bytes_per_step": r["allreduce_bytes_per_step"],
             "exposed_allreduce_ms_per_step": r["exposed_allreduce_ms_per_step"],
             "rccl_ranks": world,
-            "breakdown_ms_per_step": sub["breakdown_ms_per_step"],
         }
+        if args.full:
+            sub = train_subrecord(r, args.workload)
+            line["roofline"] = sub["roofline"]
+            line["breakdown_ms_per_step"] = sub["breakdown_ms_per_step"]
         if "loss_scale" in r:
             line["loss_scale"] = r["loss_scale"]
-        print("[bench] gpu leg done: %.1f ms/step, %.3e frames/s; dominant kernel %s" %
-              (line["ms_per_step"], line["value"], r["dominant"]), file=sys.stderr, flush=True)
-        if world == 1 and not args.no_cpu_baseline:
+        print("[bench] gpu leg done: %.1f ms/step, %.3e frames/s%s" % (line["ms_per_step"], line["value"],
+              "; dominant kernel %s" % r["dominant"] if r["dominant"] else ""), file=sys.stderr, flush=True)
+        if r["outputs"] is not None:
+            write_outputs(args.dump_outputs, r["outputs"])
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline_path_train(r["sd"], r["samples"]) if r["whole_path"] else \
                 cpu_baseline_train(r["sd"], r["samples"])
         if args.breakdown:
@@ -612,10 +673,12 @@ def headline_attention():
 # ---------------------------------------------------------------------------------------------------------------
 # forward workloads
 # ---------------------------------------------------------------------------------------------------------------
-def forward_leg(args, workload, rank, world, steps, warmup, streams_req, batch=0, sustained=True, graph=False, tags=False):
-    """one forward workload: calibration of the passes in flight, warm-up, one instrumented pass alone on the device, `steps`
-    timed steps between barriers with the dominant family event-timed per launch, three strictly sequential passes (exclusive
-    launch durations, single-pass step), optionally the >= 2 s sustained loop.  Every rank calls it; returns a dict."""
+def forward_leg(args, workload, rank, world, steps, warmup, streams_req, batch=0, sustained=True, graph=False, tags=False,
+                profile=True, keep_outputs=False):
+    """one forward workload: calibration of the passes in flight, warm-up, one instrumented pass alone on the device (profile),
+    `steps` timed steps between barriers (profile: with the dominant family event-timed per launch), three strictly sequential
+    passes (profile: exclusive launch durations, single-pass step), optionally the >= 2 s sustained loop.  keep_outputs: the
+    record's `outputs` = collect_outputs of what the last timed step returned.  Every rank calls it; returns a dict."""
     import torch
     import torch.distributed as dist
     from sincformer_metacog_speech_enhancement_amd import ops, synthetic as syn
@@ -693,30 +756,40 @@ def forward_leg(args, workload, rank, world, steps, warmup, streams_req, batch=0
         for i in range(max(warmup, 1)):
             step()
         torch.cuda.synchronize()
-        ops.profiler.enable(None, tags=tags)
-        out_one = path(wave)                              # eager, so the per-launch events exist even with --graph
-        breakdown = ops.profiler.summary()
-        launches_one = {k: ops.profiler.launches(k) for k in breakdown if "[" not in k}
-        ops.profiler.disable()
-        gpu_masks = (out_one["mask_real"][:1].cpu(), out_one["mask_imag"][:1].cpu()) if rank == 0 else None
-        del out_one
-        dominant = max((k for k in breakdown if "[" not in k), key=lambda k: breakdown[k]["ms_total"])
+        breakdown, launches_one, dominant, launches, gpu_masks = {}, {}, None, None, None
+        if profile:
+            ops.profiler.enable(None, tags=tags)
+            out_one = path(wave)                          # eager, so the per-launch events exist even with --graph
+            breakdown = ops.profiler.summary()
+            launches_one = {k: ops.profiler.launches(k) for k in breakdown if "[" not in k}
+            ops.profiler.disable()
+            gpu_masks = (out_one["mask_real"][:1].cpu(), out_one["mask_imag"][:1].cpu()) if rank == 0 else None
+            del out_one
+            dominant = max((k for k in breakdown if "[" not in k), key=lambda k: breakdown[k]["ms_total"])
         refuse_variant_overrides()
-        if not graph:
+        if profile and not graph:
             ops.profiler.enable({dominant})
         barrier()
         t0 = time.perf_counter()
-        for _ in range(steps):
-            step()
+        for i in range(steps):
+            if keep_outputs and i == steps - 1:
+                last = step()
+            else:
+                step()
         barrier()
         elapsed = time.perf_counter() - t0
-        launches = launches_one[dominant] if graph else ops.profiler.launches(dominant)
-        ops.profiler.disable()
+        if profile:
+            launches = launches_one[dominant] if graph else ops.profiler.launches(dominant)
+            ops.profiler.disable()
+        outputs = None
+        if keep_outputs:                                  # before anything else runs: a graph replay reuses its output buffers
+            outputs = collect_outputs(last)
+            del last
         # with several passes in flight the live per-launch durations include the time a kernel shares the chip with the
         # other stream's kernels; strictly sequential passes AFTER the timed region give the exclusive durations and the
         # single-pass step time
         launches_excl, single_ms = None, None
-        if not graph:
+        if profile and not graph:
             torch.cuda.synchronize()
             ops.profiler.enable({dominant})
             t1 = time.perf_counter()
@@ -730,7 +803,7 @@ def forward_leg(args, workload, rank, world, steps, warmup, streams_req, batch=0
         # as the contract says - a burst of a fraction of a second at the default K), dominant family timed live
         sus = None
         if sustained:
-            if not graph:
+            if profile and not graph:
                 ops.profiler.enable({dominant})
             barrier()
             t2 = time.perf_counter()
@@ -749,7 +822,7 @@ def forward_leg(args, workload, rank, world, steps, warmup, streams_req, batch=0
             barrier()
             dt_s = time.perf_counter() - t2
             sus = {"steps": n_s, "seconds": dt_s, "ms_per_step": dt_s / n_s * 1e3, "frames_per_s": world * B * T * n_s / dt_s}
-            if not graph:
+            if profile and not graph:
                 ds = ops.profiler.summary()[dominant]
                 sus.update({"dominant_kernel": dominant, "dominant_avg_ms": ds["ms_avg"], "dominant_launches": ds["n"]})
                 ops.profiler.disable()
@@ -762,7 +835,7 @@ def forward_leg(args, workload, rank, world, steps, warmup, streams_req, batch=0
     return {"workload": workload, "desc": desc, "B": B, "L": L, "T": T, "elapsed": elapsed, "steps": steps, "streams": n_streams,
             "calib": calib, "breakdown": breakdown, "launches_one": launches_one, "dominant": dominant, "launches": launches,
             "launches_excl": launches_excl, "single_ms": single_ms, "sustained": sus, "gpu_masks": gpu_masks, "weights": weights,
-            "noisy": noisy, "use_memory": use_memory, "policy": ops.policy_name()}
+            "noisy": noisy, "use_memory": use_memory, "policy": ops.policy_name(), "outputs": outputs}
 
 
 def forward_roofline(r, passes_in_flight):
@@ -793,13 +866,20 @@ def breakdown_of(r):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline figure: the instrumented pass (breakdown, roofline), sequential "
+                         "passes, the sustained loop, the sub-records of the default line and the CPU baseline with mask_rmse "
+                         "(the --no-* / --train-* / --configs1-* / --dp-* options shape these)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float32 / float64, at most "
+                         "64 MB in all: larger arrays as a fixed seeded sample of their elements)")
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS),
-                    help="default: c3p = the shape BASELINE's metric names (B 256 x 512-frame utterances); the default line also "
-                         "carries `configs1` (BASELINE configs[1], B 64 x 4 s) and `train` (configs[2] on the north-star composition) "
-                         "at N = 1, and with --gpus N > 1 a `dp_train` sub-record: the c3se training step with the RCCL gradient "
-                         "all-reduce (BASELINE configs[3])")
+                    help="default: c3p = the shape BASELINE's metric names (B 256 x 512-frame utterances); with --full the "
+                         "default line also carries `configs1` (BASELINE configs[1], B 64 x 4 s) and `train` (configs[2] on the "
+                         "north-star composition) at N = 1, and with --gpus N > 1 a `dp_train` sub-record: the c3se training step "
+                         "with the RCCL gradient all-reduce (BASELINE configs[3])")
     ap.add_argument("--dp-batch", type=int, default=0, help="per-GPU batch of the dp_train sub-record (default: the workload's 256)")
     ap.add_argument("--dp-steps", type=int, default=5)
     ap.add_argument("--dp-warmup", type=int, default=2)
@@ -816,7 +896,7 @@ def main():
                          "dynamic loss scale)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-headline", action="store_true", help="skip the attention-kernel-alone measurement at B256 x T512")
-    ap.add_argument("--breakdown", default=None, help="write the per-kernel-family breakdown JSON here")
+    ap.add_argument("--breakdown", default=None, help="write the per-kernel-family breakdown JSON here (needs --full)")
     ap.add_argument("--batch", type=int, default=0, help="override the per-GPU batch of the workload")
     ap.add_argument("--graph", action="store_true", help="replay the forward as one hipGraph (launch-bound small batches)")
     ap.add_argument("--streams", type=int, default=0, help="forward passes in flight: consecutive steps alternate over this many "
@@ -825,6 +905,10 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
+    if args.breakdown and not args.full:
+        raise SystemExit("bench.py: --breakdown comes from the instrumented pass of --full")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))                          # before anything in this process touches the GPU
     default_line = args.workload is None
@@ -836,16 +920,21 @@ def main():
     import torch
     import torch.distributed as dist
     rank, world = init_ranks(args)
-    dp_sub = default_line and world > 1 and not args.no_dp_train
-    train_sub = default_line and world == 1 and not args.no_train
-    c1_sub = default_line and not args.no_configs1
+    full = args.full
+    dp_sub = full and default_line and world > 1 and not args.no_dp_train
+    train_sub = full and default_line and world == 1 and not args.no_train
+    c1_sub = full and default_line and not args.no_configs1
 
     r = forward_leg(args, args.workload, rank, world, args.steps, args.warmup, args.streams, batch=args.batch,
-                    sustained=not args.no_sustained, graph=args.graph, tags=bool(args.breakdown))
+                    sustained=full and not args.no_sustained, graph=args.graph, tags=bool(args.breakdown), profile=full,
+                    keep_outputs=bool(args.dump_outputs) and rank == 0)
+    if rank == 0 and r["outputs"] is not None:
+        write_outputs(args.dump_outputs, r["outputs"])
+        r["outputs"] = None
     # the attention kernel alone comes right after the primary workload: it is specified like the timed region - the kernel on
     # a chip that has just run the K steps - and the other ranks simply wait at the next barrier
     headline = None
-    if rank == 0 and not args.no_headline and default_line:
+    if full and rank == 0 and not args.no_headline and default_line:
         headline = headline_attention()
     c1 = None
     if c1_sub:
@@ -867,13 +956,14 @@ def main():
                        "sharding": "utterances over ranks, no data-path collective",
                        "launch": "one hipGraph replay per step" if args.graph else "eager launches",
                        "streams": r["streams"], "precision_policy": r["policy"]},
-            "roofline": forward_roofline(r, r["streams"]),
             "frames_per_s_per_gpu": frames / elapsed / world,
         }
+        if full:
+            line["roofline"] = forward_roofline(r, r["streams"])
         if default_line:
             line["config"]["why_this_workload"] = ("the shape BASELINE.json's metric and north_star target are quoted on (batch 256 x "
                                                    "512-frame utterances); BASELINE configs[1] (B 64 x 4 s) is the `configs1` sub-record, "
-                                                   "configs[2] the `train` sub-record")
+                                                   "configs[2] the `train` sub-record (both with --full)")
         if r["calib"]:
             line["config"]["calibration_ms_per_pass"] = r["calib"]
         if r["single_ms"] is not None:
@@ -881,8 +971,9 @@ def main():
         att = attention_in_pass(r)
         if att:
             line["attention"] = att
-        line["breakdown_ms_per_step"] = breakdown_of(r)
-        line["breakdown_note"] = "one instrumented pass alone on the device (HIP events per launch); sums to the single-pass step"
+        if full:
+            line["breakdown_ms_per_step"] = breakdown_of(r)
+            line["breakdown_note"] = "one instrumented pass alone on the device (HIP events per launch); sums to the single-pass step"
         if r["sustained"]:
             sus = r["sustained"]
             sus["vs_timed_region"] = sus["ms_per_step"] / line["ms_per_step"]
@@ -904,9 +995,9 @@ def main():
             line["train"] = train_subrecord(tr, "c3t")
         if dp_rec:
             line["dp_train"] = dp_rec
-        print("[bench] gpu leg done: %.1f ms/step, %.3e frames/s; dominant kernel %s" %
-              (line["ms_per_step"], line["value"], r["dominant"]), file=sys.stderr, flush=True)
-        if world == 1 and not args.no_cpu_baseline:
+        print("[bench] gpu leg done: %.1f ms/step, %.3e frames/s%s" % (line["ms_per_step"], line["value"],
+              "; dominant kernel %s" % r["dominant"] if r["dominant"] else ""), file=sys.stderr, flush=True)
+        if full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"], rm = cpu_baseline(r["weights"], r["L"], r["noisy"], gpu_masks=r["gpu_masks"],
                                                     use_memory=r["use_memory"])
             line["mask_rmse"] = {"value": rm, "bound": 1e-3, "what": "RMSE of (mask_real | mask_imag) of utterance 0 of the bench "

@@ -8,6 +8,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -31,7 +32,7 @@ def _run(cmd, env=None):
 
 
 def test_bench_single_gpu_line():
-    d = _json_line(_run([sys.executable, "bench.py", "--workload", "c1", "--steps", "6", "--warmup", "2"]))
+    d = _json_line(_run([sys.executable, "bench.py", "--full", "--workload", "c1", "--steps", "6", "--warmup", "2"]))
     assert d["sustained"]["steps"] >= 250 and d["sustained"]["seconds"] >= 2.0 and 0.5 < d["sustained"]["vs_timed_region"] < 2.0
     assert all(k in d for k in REQUIRED + ["cpu_baseline"])
     assert d["n_gpus"] == 1 and d["steps"] == 6 and d["warmup"] == 2 and d["scaling"] == "weak" and d["vs_baseline"] is None
@@ -47,12 +48,12 @@ def test_bench_single_gpu_line():
 
 
 def test_bench_default_line_is_on_the_metrics_shape_and_carries_configs1_and_train():
-    """the driver's one command: primary workload = the shape BASELINE's metric names (B 256 x 512-frame utterances), with
+    """the driver's command with --full: primary workload = the shape BASELINE's metric names (B 256 x 512-frame utterances), with
     BASELINE configs[1] (`configs1`), configs[2] on the north-star composition (`train`: fp16 operands under the device-side
     dynamic loss scale, no skipped step inside its timed steps) and the attention kernel alone (`headline`) as sub-records;
     the roof of the dominant family is chosen per launch"""
-    d = _json_line(_run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--train-batch", "16",
-                         "--train-steps", "2", "--train-warmup", "1"]))
+    d = _json_line(_run([sys.executable, "bench.py", "--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+                         "--train-batch", "16", "--train-steps", "2", "--train-warmup", "1"]))
     assert "B256 x 512-frame" in d["config"]["workload"] and d["config"]["frames_per_utt"] == 512
     assert abs(d["value"] - 256 * 512 / (d["ms_per_step"] * 1e-3)) < 1e-3 * d["value"]
     assert d["roofline"]["traffic"] is None or "NOT measured" in d["roofline"]["traffic_source"]
@@ -90,7 +91,8 @@ def test_bench_gpus_flag_starts_the_ranks_itself():
     env = {"SFM_SINGLE_DEVICE": "1", "SFM_DIST_BACKEND": "gloo"}
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         os.environ.pop(k, None)
-    d = _json_line(_run([sys.executable, "bench.py", "--gpus", "2", "--workload", "c1", "--steps", "3", "--warmup", "1"], env))
+    d = _json_line(_run([sys.executable, "bench.py", "--full", "--gpus", "2", "--workload", "c1", "--steps", "3", "--warmup", "1"],
+                        env))
     assert d["n_gpus"] == 2 and abs(d["value"] - 2 * 201 / (d["ms_per_step"] * 1e-3)) < 1e-3 * d["value"]
     assert "cpu_baseline" not in d
 
@@ -108,7 +110,8 @@ def test_bench_two_ranks_rehearsal(workload, extra):
     env = {"SFM_SINGLE_DEVICE": "1", "SFM_DIST_BACKEND": "gloo"}
     port = "29531" if workload == "c1" else "29532"
     out = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                "--master-port", port, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", workload] + extra, env)
+                "--master-port", port, "bench.py", "--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", workload]
+               + extra, env)
     d = _json_line(out)
     assert all(k in d for k in REQUIRED)
     assert d["n_gpus"] == 2 and d["steps"] == 3 and d["scaling"] == "weak"
@@ -123,8 +126,8 @@ def test_bench_default_two_ranks_carry_the_dp_train_record():
     (north_star: "RCCL all-reduce of gradients"; here over gloo, two ranks on the one card) - and the sustained figure"""
     env = {"SFM_SINGLE_DEVICE": "1", "SFM_DIST_BACKEND": "gloo"}
     out = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                "--master-port", "29533", "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2", "--no-headline",
-                "--configs1-batch", "2", "--dp-batch", "4", "--dp-steps", "2", "--dp-warmup", "1"], env)
+                "--master-port", "29533", "bench.py", "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2",
+                "--no-headline", "--configs1-batch", "2", "--dp-batch", "4", "--dp-steps", "2", "--dp-warmup", "1"], env)
     d = _json_line(out)
     assert all(k in d for k in REQUIRED) and d["n_gpus"] == 2 and "B256 x 512-frame" in d["config"]["workload"]
     assert "train" not in d and "B64 x 4 s" in d["configs1"]["workload"]
@@ -139,3 +142,53 @@ def test_bench_default_two_ranks_carry_the_dp_train_record():
     assert t["exposed_allreduce_ms_per_step"] is not None and 0 <= t["exposed_allreduce_ms_per_step"] <= t["ms_per_step"]
     assert t["applied_steps_in_timed_region"] == 2 and not t["optimizer_state"]["skipped"]
     assert t["loss_scale"]["skipped_in_timed_region"] == 0
+
+
+# what only --full measures: none of it belongs in a plain line
+FULL_ONLY = ["roofline", "breakdown_ms_per_step", "single_pass_ms_per_step", "attention", "sustained", "headline", "configs1",
+             "train", "dp_train", "cpu_baseline", "mask_rmse"]
+PLAIN = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+         "dtype", "data", "config"]
+
+
+def _dumped(d):
+    files = sorted(f for f in os.listdir(d) if f.endswith(".npy"))
+    assert sum(os.path.getsize(os.path.join(d, f)) for f in files) <= 64e6
+    out = {f[:-4]: np.load(os.path.join(d, f)) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    return out
+
+
+def test_bench_plain_default_line_is_lean_and_dumps_a_bounded_sample(tmp_path):
+    """the plain driver's command: the headline figure and nothing else; --dump-outputs writes the last timed step's arrays
+    (c3p returns far more than 64 MB: the large ones are a seeded sample)"""
+    d = _json_line(_run([sys.executable, "bench.py", "--steps", "4", "--warmup", "1", "--dump-outputs", str(tmp_path)]))
+    assert all(k in d for k in PLAIN) and not any(k in d for k in FULL_ONLY)
+    assert "B256 x 512-frame" in d["config"]["workload"] and d["steps"] == 4 and d["warmup"] == 1 and d["higher_is_better"] is True
+    assert d["metric"].startswith("audio frames/sec/GPU") and "bf16 attention" in d["dtype"]
+    assert abs(d["value"] - 256 * 512 / (d["ms_per_step"] * 1e-3)) < 1e-3 * d["value"]
+    out = _dumped(tmp_path)
+    assert {"mask_real", "mask_imag", "enhanced"} <= set(out)
+    assert out["mask_real"].ndim == 1 and 0 < out["mask_real"].size < 256 * 512 * 129
+    assert all(bool(np.isfinite(a).all()) for a in out.values())
+
+
+@pytest.mark.parametrize("workload,extra,names", [("c1", [], {"mask_real", "mask_imag", "enhanced"}),
+                                                 ("c3se", ["--batch", "2"], {"loss", "params"})])
+def test_bench_dump_outputs_are_reproducible(tmp_path, workload, extra, names):
+    """same arguments -> same seeded inputs and weights -> the same outputs, run after run (what lets two builds be compared);
+    --steps sets the timed steps"""
+    dumps = []
+    for run in ("a", "b"):
+        d = _json_line(_run([sys.executable, "bench.py", "--workload", workload, "--steps", "2", "--warmup", "1", "--dump-outputs",
+                             str(tmp_path / run)] + extra))
+        assert d["steps"] == 2 and d["ms_per_step"] > 0 and not any(k in d for k in FULL_ONLY)
+        dumps.append(_dumped(tmp_path / run))
+    a, b = dumps
+    assert names <= set(a) and set(a) == set(b)
+    if workload == "c1":
+        assert a["mask_real"].shape == (1, 201, 129) and a["enhanced"].shape == (1, 16000)     # small: whole, with its shape
+    else:
+        assert a["loss"].shape == (1,) and np.isfinite(a["loss"]).all() and a["params"].dtype == np.float32
+    for k in a:
+        np.testing.assert_allclose(a[k], b[k], rtol=1e-5, atol=1e-6, err_msg=k)
