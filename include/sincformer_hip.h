@@ -129,7 +129,8 @@ int sfm_attention_fwd_ex(const void* qkv, void* out, int B, int T, int H, int hd
                          float scale, int dtype, int out_dtype, int variant, void* stream);
 
 /* nn.LayerNorm (+ optional erf GELU when act==1): models/conformer.py:43,68,107,150;
- * agents/msa.py:44-47; training/conformer_pipeline.py:274,282. */
+ * agents/msa.py:44-47; training/conformer_pipeline.py:274,282.  D <= 512; ldx, and ld16 / ld32 of the outputs that are
+ * written, >= D (else SFM_ERR_SHAPE); dtype SFM_DT_BF16 or SFM_DT_F16 (else SFM_ERR_ARG). */
 int sfm_layernorm(const float* x, const float* w, const float* b, void* out16, float* out32, int M, int D,
                   int ldx, int ld16, int ld32, float eps, int act, int dtype, void* stream);
 
@@ -147,7 +148,7 @@ int sfm_dwconv_bn_swish(const void* x, const float* wdw, const float* bdw, const
                         int C, int KS, float eps, int dtype, void* stream);
 
 /* same operation with host-folded operands (wT [KS][C], BatchNorm+bias folded into sc/sh), register-resident
- * taps; KS in {7, 31}, C in {64, 128, 256, 512} */
+ * taps for KS in {7, 31} and C in {32, 64, 128, 256, 512}; any other C > 0 and odd KS on a generic kernel */
 int sfm_dwconv_folded(const void* x, const float* wT, const float* sc, const float* sh, void* out, int B, int T,
                       int C, int KS, int act, int out_f32, int dtype, void* stream);
 
@@ -358,7 +359,8 @@ int sfm_conv_wgrad16(const void* G, const void* x, float* dW, float* db, int B, 
                      void* stream);                       /* ws: sfm_tn_ws_floats(B * Lout, N, ksize * Cin) */
 long long sfm_colsum_ws_floats(int M, int N);
 int sfm_colsum(const void* G, float* out, int M, int N, int ldg, int g_f32, int dtype, float* ws, void* stream);
-/* LayerNorm backward; ws (optional, sfm_layernorm_bwd_ws_floats(M, D) floats): ordered dgamma / dbeta */
+/* LayerNorm backward; ws (optional, sfm_layernorm_bwd_ws_floats(M, D) floats): ordered dgamma / dbeta.  D <= 512 and every
+ * row stride (ldx, ldy, ld) >= D, else SFM_ERR_SHAPE */
 long long sfm_layernorm_bwd_ws_floats(int M, int D);
 int sfm_layernorm_bwd(const float* x, const float* gamma, const float* dy, const float* dres, float* dx,
                       float* dgamma, float* dbeta, int M, int D, int ldx, int ld, float eps, float* ws, void* stream);

@@ -178,7 +178,9 @@ static int layernorm_bwd_go(const float* x, const float* gamma, const void* dy, 
   if (!x || !gamma || !dy || !dx || !dgamma || !dbeta) return SFM_ERR_ARG;
   if (ws && (((uintptr_t)ws) % 16) != 0) return SFM_ERR_ARG;
   if (M <= 0 || D <= 0 || D > 512) return SFM_ERR_SHAPE;
+  if (ldx < D || ldy < D || ld < D) return SFM_ERR_SHAPE;                 // rows of x, dy, dres / dx must not overlap
   if (next16 && (next_p < 0.f || next_p >= 1.f || ((uintptr_t)next16 % 8) != 0)) return SFM_ERR_SHAPE;
+  if (dtype != SFM_DT_BF16 && dtype != SFM_DT_F16) return SFM_ERR_ARG;
   u16* nxt = (u16*)next16;
   const int nfmt = dtype == SFM_DT_F16 ? 2 : 1;
   constexpr int LNB_R = 2;

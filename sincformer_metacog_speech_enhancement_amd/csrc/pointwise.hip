@@ -89,6 +89,9 @@ extern "C" int sfm_layernorm(const float* x, const float* w, const float* b, voi
                              int ldx, int ld16, int ld32, float eps, int act, int dtype, void* stream) {
   if (!x || !w || !b || (!out16 && !out32)) return SFM_ERR_ARG;
   if (M <= 0 || D <= 0 || D > 512) return SFM_ERR_SHAPE;
+  // every row stride must cover the D normalised columns, or rows would overlap (and the last one run past its buffer)
+  if (ldx < D || (out16 && ld16 < D) || (out32 && ld32 < D)) return SFM_ERR_SHAPE;
+  if (dtype != SFM_DT_BF16 && dtype != SFM_DT_F16) return SFM_ERR_ARG;
   const bool vec = D == 256 && (ldx % 4 == 0) && (((uintptr_t)x | (uintptr_t)w | (uintptr_t)b) % 16 == 0) &&
                    (!out16 || ((ld16 % 4 == 0) && ((uintptr_t)out16 % 8 == 0))) &&
                    (!out32 || ((ld32 % 4 == 0) && ((uintptr_t)out32 % 16 == 0)));
@@ -584,22 +587,60 @@ static int launch_dwconv_reg(const void* x, const float* wT, const float* sc, co
   return SFM_OK;
 }
 
+// Any channel count and any odd KS (the shapes the register-resident kernels do not take, e.g. the training-mode
+// ConvolutionModule at C 192 / 384): one output element per thread, taps and scale / shift read from global memory.
+template <class T>
+__global__ __launch_bounds__(256) void dwconv_generic_kernel(const u16* __restrict__ x, const float* __restrict__ wT,
+                                                             const float* __restrict__ sc, const float* __restrict__ sh,
+                                                             void* __restrict__ out, int Tlen, int C, int KS, long long total,
+                                                             int act, int out_f32) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int c = (int)(i % C);
+  const long long bt = i / C;                                            // b * Tlen + t
+  const int t = (int)(bt % Tlen);
+  const u16* xc = x + (bt - t) * C + c;                                  // (b, 0, c)
+  const int padl = (KS - 1) / 2;
+  float acc = 0.f;
+  for (int k = 0; k < KS; ++k) {
+    const int tt = t + k - padl;
+    if (tt >= 0 && tt < Tlen) acc += wT[(long long)k * C + c] * T::to_f32(xc[(long long)tt * C]);
+  }
+  float y = acc * sc[c] + sh[c];
+  if (act) y = swish_f(y);
+  if (out_f32) reinterpret_cast<float*>(out)[i] = y;
+  else reinterpret_cast<u16*>(out)[i] = T::from_f32(y);
+}
+
 // wT [KS][C] fp32 (transposed depthwise weights), sc/sh [C] = BatchNorm(eval) folded with the conv bias:
-// y = act ? swish(conv(x) * sc + sh) : conv(x) * sc + sh ; 16-bit or fp32 output
+// y = act ? swish(conv(x) * sc + sh) : conv(x) * sc + sh ; 16-bit or fp32 output.  KS odd; KS 7 / 31 with C in
+// {32, 64, 128, 256, 512} on the register-resident kernels, everything else on the generic one.
 extern "C" int sfm_dwconv_folded(const void* x, const float* wT, const float* sc, const float* sh, void* out, int B, int T,
                                  int C, int KS, int act, int out_f32, int dtype, void* stream) {
   if (!x || !wT || !sc || !sh || !out) return SFM_ERR_ARG;
-  if (B <= 0 || T <= 0 || C % 8 != 0 || C > 512 || (256 % (C / 2)) != 0 || (DW_TT / (256 / (C / 2))) % 4 != 0)
-    return SFM_ERR_SHAPE;
+  if (B <= 0 || T <= 0 || C <= 0 || KS < 1 || (KS & 1) == 0) return SFM_ERR_SHAPE;
+  if (dtype != SFM_DT_BF16 && dtype != SFM_DT_F16) return SFM_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
+  const bool reg = (KS == 7 || KS == 31) && C % 8 == 0 && C <= 512 && (256 % (C / 2)) == 0 && (DW_TT / (256 / (C / 2))) % 4 == 0;
+  if (!reg) {
+    const long long total = (long long)B * T * C;
+    const long long nb = (total + 255) / 256;
+    if (nb > 0x7fffffffLL) return SFM_ERR_SHAPE;
+    if (dtype == SFM_DT_F16)
+      SFM_LAUNCH((dwconv_generic_kernel<F16>), dim3((unsigned)nb), dim3(256), 0, st, (const u16*)x, wT, sc, sh, out, T, C, KS, total,
+                 act, out_f32);
+    else
+      SFM_LAUNCH((dwconv_generic_kernel<BF16>), dim3((unsigned)nb), dim3(256), 0, st, (const u16*)x, wT, sc, sh, out, T, C, KS, total,
+                 act, out_f32);
+    return SFM_OK;
+  }
   // fp16: the dot-product form (SFM_DWCONV_DOT=0 keeps the multiply-add kernel: the A/B knob)
   static const int dot_on = getenv("SFM_DWCONV_DOT") ? atoi(getenv("SFM_DWCONV_DOT")) : 1;
   if (KS == 31 && dtype == SFM_DT_F16 && dot_on) return launch_dwconv_dot<31>(x, wT, sc, sh, out, B, T, C, act, out_f32, st);
   if (KS == 31) return dtype == SFM_DT_F16 ? launch_dwconv_reg<F16, 31>(x, wT, sc, sh, out, B, T, C, act, out_f32, st)
                                            : launch_dwconv_reg<BF16, 31>(x, wT, sc, sh, out, B, T, C, act, out_f32, st);
-  if (KS == 7) return dtype == SFM_DT_F16 ? launch_dwconv_reg<F16, 7>(x, wT, sc, sh, out, B, T, C, act, out_f32, st)
-                                          : launch_dwconv_reg<BF16, 7>(x, wT, sc, sh, out, B, T, C, act, out_f32, st);
-  return SFM_ERR_SHAPE;
+  return dtype == SFM_DT_F16 ? launch_dwconv_reg<F16, 7>(x, wT, sc, sh, out, B, T, C, act, out_f32, st)
+                             : launch_dwconv_reg<BF16, 7>(x, wT, sc, sh, out, B, T, C, act, out_f32, st);
 }
 
 extern "C" int sfm_dwconv_bn_swish(const void* x, const float* wdw, const float* bdw, const float* bnw,

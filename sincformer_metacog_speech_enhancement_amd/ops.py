@@ -495,9 +495,9 @@ def headpool(xd16, pw, pooled16, part, B, Tin, Tout, gcols=16):
 
 
 def ln_linear16(x32, ln_w, ln_b, pw, epi=EPI_NONE, out_dtype=None, eps=1e-5):
-    """linear16(LayerNorm(x32[:, :256]), pw, epi) with a 16-bit result.  On the shapes sfm_lin256 takes (K = 256, plain or GLU epilogue,
-    M >= 4096) the LayerNorm is the GEMM kernel's prologue (sfm_ln_lin256): one launch, the normalised 16-bit rows never reach HBM;
-    otherwise sfm_layernorm + linear16.  The two routes give the same bits."""
+    """linear16(LayerNorm(x32[:, :D]), pw, epi) with a 16-bit result, D = ln_w.numel().  On the shapes sfm_lin256 takes (D = K = 256,
+    plain or GLU epilogue, M >= 4096) the LayerNorm is the GEMM kernel's prologue (sfm_ln_lin256): one launch, the normalised 16-bit rows
+    never reach HBM; otherwise sfm_layernorm + linear16.  The two routes give the same bits."""
     M = x32.shape[0]
     out = torch.empty(M, pw.N, device=x32.device, dtype=out_dtype or _state["dtype"])
     fused = (_LIN256["on"] and _state["gemm_variant"] == 0 and epi in (EPI_NONE, EPI_GLU) and (epi == EPI_GLU) == bool(pw.glu) and
@@ -514,7 +514,7 @@ def ln_linear16(x32, ln_w, ln_b, pw, epi=EPI_NONE, out_dtype=None, eps=1e-5):
               2.0 * M * pw.Npad * 256, M * 256 * 4.0 + pw.Npad * 512.0 + M * pw.N * 2.0,
               tag="M%d N%d K256 ln+lin256%s" % (M, pw.Npad, " glu" if pw.glu else ""))
         return out
-    h16 = torch.empty(M, 256, device=x32.device, dtype=_state["dtype"])
+    h16 = torch.empty(M, ln_w.numel(), device=x32.device, dtype=_state["dtype"])
     layernorm(x32, ln_w, ln_b, out16=h16, eps=eps)
     return linear16(h16, pw, epi=epi, out=out)
 
@@ -655,11 +655,16 @@ def attention(qkv16, B, T, H, hd, out=None, prescaled=False, out_dtype=None):
     return out
 
 
+LAYERNORM_MAX_D = 512      # sfm_layernorm / sfm_layernorm_bwd_*: the widest row they normalise (and so the widest Conformer d_model)
+
+
 def layernorm(x32, w, b, out16=None, out32=None, act=0, eps=1e-5):
     """rows of x32 [M, >=D] are normalised over their first D = w.numel() columns."""
     _need_dev(x32)
     L = _lib.load()
     M, D = x32.shape[0], w.numel()
+    if D > LAYERNORM_MAX_D:
+        raise RuntimeError("layernorm: width %d is not supported (the LayerNorm kernels take D <= %d)" % (D, LAYERNORM_MAX_D))
     _call("layernorm", L.sfm_layernorm, (_p(x32), _p(w), _p(b), _p(out16), _p(out32), M, D, x32.stride(0),
                          out16.stride(0) if out16 is not None else 0, out32.stride(0) if out32 is not None else 0,
                          eps, act, _dt(), _stream()),
@@ -1131,6 +1136,8 @@ def layernorm_bwd(x32, gamma, dy, dres32, dgamma, dbeta, eps=1e-5, next_drop=Non
     next backward node of the residual chain starts from (same counters as ew_train(EW_SCALE_DROP)) -> (dx, next16)."""
     L = _lib.load()
     M, D = dy.shape
+    if D > LAYERNORM_MAX_D:
+        raise RuntimeError("layernorm_bwd: width %d is not supported (the LayerNorm kernels take D <= %d)" % (D, LAYERNORM_MAX_D))
     dx = torch.empty(M, D, device=dy.device, dtype=torch.float32)
     ws = _ws(int(L.sfm_layernorm_bwd_ws_floats(M, D)), dy.device) if _DET["on"] else None
     dy16 = 0 if dy.dtype == torch.float32 else 1

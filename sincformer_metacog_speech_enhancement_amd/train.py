@@ -168,7 +168,15 @@ def _mhsa_bwd(dy, c, G, do=None, nxt=None):
 # ---------------------------------------------------------------------------
 # ConvolutionModule (models/conformer.py:101-128), BatchNorm1d in training mode
 # ---------------------------------------------------------------------------
+TRAIN_DWCONV_KS = (7, 31)      # depthwise kernel sizes whose weight gradient sfm_dwconv_wgrad computes
+
+
 def _conv_fwd(x, P, B, T, p, seeds, bn_buffers, momentum=0.1, eps=1e-5, bn_eval=False):
+    KS = P["conv.depthwise.weight"].shape[-1]
+    if KS not in TRAIN_DWCONV_KS:
+        # refused here, before any launch and before the BatchNorm running statistics move, not in the backward
+        raise NotImplementedError("ConvolutionModule training: depthwise kernel_size %d is not supported (the weight-gradient "
+                                  "kernel takes kernel_size 7 or 31; eval() takes any odd kernel_size)" % KS)
     dt = ops.compute_dtype()
     M, D = x.shape
     lw, lb = _f32(P["conv.layer_norm.weight"]), _f32(P["conv.layer_norm.bias"])

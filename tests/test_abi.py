@@ -61,3 +61,42 @@ def test_null_pointers_are_rejected_without_a_gpu(built):
                         0, 0, 0, None) == -2       # Cin not a multiple of 8
     assert L.sfm_bilstm_layer(one, one, one, 2, 5, 100, 0, None) == -2   # unsupported hidden size
     assert L.sfm_bilstm_layer_ex(one, one, one, 2, 5, 100, 1, None) == -2
+
+
+def test_layernorm_row_strides_narrower_than_the_row_are_rejected_without_a_gpu(built):
+    """sfm_layernorm / sfm_layernorm_bwd_ex / sfm_layernorm_bwd_next refuse (SFM_ERR_SHAPE) a row stride below D: rows would
+    overlap and the last one would run past its buffer.  Every call carries an invalid dtype, checked after the shapes: the
+    controls pass every stride check and are then refused for it (SFM_ERR_ARG), and no call here can reach a launch."""
+    L = built.load()
+    one = ctypes.c_void_p(16)
+    M, D, BAD_DT = 4, 384, 7
+    # forward: x, out16, out32 strides
+    assert L.sfm_layernorm(one, one, one, one, None, M, D, D, D, 0, 1e-5, 0, BAD_DT, None) == -1           # control
+    assert L.sfm_layernorm(one, one, one, one, one, M, D, D + 8, D, D + 4, 1e-5, 0, BAD_DT, None) == -1   # control, wide strides
+    assert L.sfm_layernorm(one, one, one, None, one, M, D, 512, 0, 512, 1e-5, 0, BAD_DT, None) == -1      # control: no out16
+    assert L.sfm_layernorm(one, one, one, one, None, M, D, 256, D, 0, 1e-5, 0, BAD_DT, None) == -2        # ldx < D
+    assert L.sfm_layernorm(one, one, one, one, None, M, D, D, 256, 0, 1e-5, 0, BAD_DT, None) == -2        # ld16 < D
+    assert L.sfm_layernorm(one, one, one, None, one, M, D, D, 0, 256, 1e-5, 0, BAD_DT, None) == -2        # ld32 < D
+    assert L.sfm_layernorm(one, one, one, one, one, M, D, D, D, D - 1, 1e-5, 0, BAD_DT, None) == -2
+    assert L.sfm_layernorm(one, one, one, one, None, M, 513, 513, 513, 0, 1e-5, 0, BAD_DT, None) == -2    # D > 512
+    # backward: ldx, ldy, ld (dres / dx)
+    for fn, tail in ((L.sfm_layernorm_bwd_ex, ()), (L.sfm_layernorm_bwd_next, (one, 1.0, 0.0, 0))):
+        def call(ldx, ldy, ld, dt):
+            args = (one, one, one, 0, one, one, one, one, M, D, ldx, ldy, ld, 1e-5, dt) + tail + (None, None)
+            return fn(*args)
+        assert call(D, D, D, BAD_DT) == -1                                                                   # control
+        assert call(D + 16, D + 8, D + 4, BAD_DT) == -1                                                      # control
+        assert call(256, D, D, BAD_DT) == -2
+        assert call(D, 256, D, BAD_DT) == -2
+        assert call(D, D, 256, BAD_DT) == -2
+
+
+def test_depthwise_conv_shape_checks_without_a_gpu(built):
+    """sfm_dwconv_folded takes any C > 0 and odd KS (generic kernel beside the register-resident ones); C <= 0 and even KS are
+    refused before any launch (C = 0 used to divide by zero in the check itself)"""
+    L = built.load()
+    one = ctypes.c_void_p(16)
+    assert L.sfm_dwconv_folded(one, one, one, one, one, 2, 10, 0, 7, 1, 0, 7, None) == -2
+    assert L.sfm_dwconv_folded(one, one, one, one, one, 2, 10, 192, 8, 1, 0, 7, None) == -2
+    assert L.sfm_dwconv_folded(one, one, one, one, one, 2, 10, 192, 15, 1, 0, 7, None) == -1     # control: shape accepted
+    assert L.sfm_dwconv_folded(one, one, one, one, one, 2, 10, 256, 31, 1, 0, 7, None) == -1

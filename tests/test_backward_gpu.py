@@ -52,7 +52,7 @@ def test_gemm16_tn_and_colsum(ops, dt, M, N, K):
     report("colsum 16", db.cpu(), q16(g, dt).sum(0), 1e-3)
 
 
-@pytest.mark.parametrize("M,D", [(300, 256), (77, 64), (50, 258)])
+@pytest.mark.parametrize("M,D", [(300, 256), (77, 64), (50, 258), (90, 384), (61, 512)])
 def test_layernorm_bwd(ops, M, D):
     x = (arr("lx", (M, D), 3, 2.0) + 0.3).requires_grad_(True)
     w = (arr("lw", (D,), 4) * 0.1 + 1).requires_grad_(True)
@@ -68,7 +68,7 @@ def test_layernorm_bwd(ops, M, D):
 
 
 @pytest.mark.parametrize("dt", DTYPES)
-@pytest.mark.parametrize("M,D,p", [(203, 256, 0.1), (64, 256, 0.0), (77, 144, 0.15), (50, 130, 0.1)])
+@pytest.mark.parametrize("M,D,p", [(203, 256, 0.1), (64, 256, 0.0), (77, 144, 0.15), (50, 130, 0.1), (90, 384, 0.1), (61, 512, 0.0)])
 def test_layernorm_bwd_also_writes_the_next_nodes_operand(ops, dt, M, D, p):
     """next_drop = (alpha, p, seed): the second output equals ew_train(EW_SCALE_DROP) of the returned dx BIT FOR BIT (same
     counters m * D + d, same order of the two multiplications) on the vector paths (D 256; D 144 with a ragged second half), to a
@@ -207,7 +207,8 @@ def _keep_mask(seed, B, H, T, p):
 
 @pytest.mark.parametrize("dt", DTYPES)
 @pytest.mark.parametrize("B,T,H,p,hd", [(2, 200, 4, 0.0, 64), (1, 64, 2, 0.0, 64), (2, 129, 1, 0.0, 64), (1, 150, 2, 0.15, 64),
-                                        (2, 37, 4, 0.0, 16), (1, 50, 2, 0.2, 32)])       # hd != 64: generic kernels
+                                        (2, 37, 4, 0.0, 16), (1, 50, 2, 0.2, 32),        # hd != 64: generic kernels
+                                        (2, 200, 8, 0.0, 64), (1, 100, 2, 0.1, 128), (2, 64, 4, 0.0, 48)])
 def test_attention_train_fwd_bwd(ops, dt, B, T, H, p, hd):
     ops.set_compute_dtype(dt)
     seed = 77

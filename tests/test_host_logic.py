@@ -256,3 +256,65 @@ def test_lin256_routing_rule():
     finally:
         ops.set_lin256(True)
         ops.reset_precision() if hasattr(ops, "reset_precision") else None
+
+
+def test_width_bounds_separate_plausible_wrong_answers():
+    """For every row of tests/test_widths_gpu.py, in float64: plausible subtly-wrong kernels (LayerNorm statistics over the
+    first 256 columns, softmax scale 1/sqrt(64) for every head_dim, head h reading head h+1's V, depthwise padding off by one)
+    move the output of the module they sit in by at least 5x the row's GPU bound in every precision."""
+    from helpers import WIDTH_ROWS, WIDTH_EVAL_TOL, width_block_state, width_input, rel_rmse
+    torch.manual_seed(0)
+
+    def ln_first256(x, w, b, eps=1e-5):
+        mu = x[..., :256].mean(dim=-1, keepdim=True)
+        var = ((x[..., :256] - mu) ** 2).mean(dim=-1, keepdim=True)
+        return (x - mu) / torch.sqrt(var + eps) * w + b
+
+    def mhsa(x, sd, H, scale_hd=None, v_next_head=False):
+        B, T, D = x.shape
+        hd = D // H
+        h = orc.layer_norm(x, sd["layer_norm.weight"], sd["layer_norm.bias"])
+        q, k, v = [t.reshape(B, T, H, hd).transpose(1, 2)
+                   for t in orc.linear(h, sd["attention.in_proj_weight"], sd["attention.in_proj_bias"]).split(D, dim=-1)]
+        if v_next_head:
+            v = torch.roll(v, -1, dims=1)
+        p = torch.softmax((q @ k.transpose(-1, -2)) / math.sqrt(scale_hd or hd), dim=-1)
+        o = (p @ v).transpose(1, 2).reshape(B, T, D)
+        return x + orc.linear(o, sd["attention.out_proj.weight"], sd["attention.out_proj.bias"])
+
+    def conv_pad_off_by_one(x, sd):
+        B, T, D = x.shape
+        h = orc.layer_norm(x, sd["layer_norm.weight"], sd["layer_norm.bias"]).transpose(1, 2)
+        a, g = F.conv1d(h, sd["pointwise1.weight"], sd["pointwise1.bias"]).split(D, dim=1)
+        h = a * torch.sigmoid(g)
+        pad = (sd["depthwise.weight"].shape[-1] - 1) // 2
+        h = F.conv1d(F.pad(h, (pad + 1, pad - 1)), sd["depthwise.weight"], sd["depthwise.bias"], groups=D)
+        h = orc.swish(orc.batch_norm_eval(h, sd["batch_norm.weight"], sd["batch_norm.bias"], sd["batch_norm.running_mean"],
+                                          sd["batch_norm.running_var"]))
+        return x + F.conv1d(h, sd["pointwise2.weight"], sd["pointwise2.bias"]).transpose(1, 2)
+
+    need = 5 * max(WIDTH_EVAL_TOL.values())
+    for r in WIDTH_ROWS:
+        D, H = r["D"], r["H"]
+        B, T = r["BT"]
+        B = min(B, 2)                                   # the figures are per element: fewer utterances suffice on CPU
+        sd = {k: (v.double() if v.dtype.is_floating_point else v) for k, v in width_block_state(D, H, r["FF"], r["KS"]).items()}
+        x = width_input(B, T, D).double()
+        ff, att, cv = orc.sub(sd, "ff1"), orc.sub(sd, "mhsa"), orc.sub(sd, "conv")
+        ref_att = orc.mhsa(x, att, H)
+        assert rel_rmse(mhsa(x, att, H), ref_att) < 1e-12                     # the local copy is the oracle
+        errs = {"head h reads V of head h+1": rel_rmse(mhsa(x, att, H, v_next_head=True), ref_att),
+                "depthwise padding off by one": rel_rmse(conv_pad_off_by_one(x, cv), orc.conv_module(x, cv))}
+        if D // H != 64:
+            errs["softmax scale 1/sqrt(64)"] = rel_rmse(mhsa(x, att, H, scale_hd=64), ref_att)
+        if D > 256:
+            ref_ff = orc.ffn(x, ff)
+            ln = orc.layer_norm
+            orc.layer_norm = ln_first256
+            try:
+                errs["LayerNorm statistics over 256 columns"] = rel_rmse(orc.ffn(x, ff), ref_ff)
+            finally:
+                orc.layer_norm = ln
+        for what, e in errs.items():
+            print("%-7s %-40s rel rmse %.3e (needs > %.2e)" % (r["id"], what, e, need))
+            assert e > need, (r["id"], what, e)

@@ -503,7 +503,8 @@ def _attn_ref(qkv, B, T, H, hd):
 @pytest.mark.parametrize("variant", [1, 3, 4, 5, 6])    # the head_dim-64 kernels: 32 query rows per wave / persistent ring / pipelined persistent (8 x 64, 4 x 64, 4 x 128 rows)
 @pytest.mark.parametrize("dt", DTYPES)
 @pytest.mark.parametrize("B,T,H,hd", [(2, 200, 4, 64), (1, 64, 4, 64), (3, 1, 2, 64), (1, 801, 4, 64), (2, 129, 1, 64),
-                                      (1, 1100, 2, 64), (2, 20, 4, 16), (1, 37, 2, 32)])
+                                      (1, 1100, 2, 64), (2, 20, 4, 16), (1, 37, 2, 32),
+                                      (2, 512, 8, 64), (3, 256, 6, 64), (2, 150, 2, 128), (1, 77, 4, 48), (2, 64, 1, 96)])
 def test_attention(ops, dt, B, T, H, hd, variant):
     ops.set_compute_dtype(dt)
     ops.set_attention_variant(variant)
@@ -569,7 +570,7 @@ def test_attention_online_softmax_rescale(ops, variant):
 
 # ---------------------------------------------------------------------------
 @pytest.mark.parametrize("dt", DTYPES)
-@pytest.mark.parametrize("M,D", [(100, 256), (101, 256), (7, 256), (33, 64), (17, 258)])   # D 256: the two-rows-per-wave kernel, odd M = its tail
+@pytest.mark.parametrize("M,D", [(100, 256), (101, 256), (7, 256), (33, 64), (17, 258), (45, 384), (29, 512)])   # D 256: the two-rows-per-wave kernel, odd M = its tail
 def test_layernorm(ops, dt, M, D):
     ops.set_compute_dtype(dt)
     x, w, b = arr("lx", (M, D), 50, 2.0) + 0.3, arr("lw", (D,), 51) * 0.1 + 1, arr("lb", (D,), 52) * 0.1
@@ -584,7 +585,25 @@ def test_layernorm(ops, dt, M, D):
 
 
 @pytest.mark.parametrize("dt", DTYPES)
-@pytest.mark.parametrize("C,KS,T", [(256, 31, 200), (64, 7, 20), (256, 31, 64), (256, 31, 7)])
+@pytest.mark.parametrize("M,D,ldx,ld16,ld32", [(37, 384, 392, 400, 388), (21, 256, 258, 262, 266), (19, 256, 264, 264, 272)])
+def test_layernorm_row_strides_leave_padding_columns_untouched(ops, dt, M, D, ldx, ld16, ld32):
+    """x32 row stride > D and out16 / out32 strides > D: the D columns of every row are normalised, the padding columns of
+    both outputs keep their sentinel (D 256 with row strides that are / are not multiples of 4: both kernels)"""
+    ops.set_compute_dtype(dt)
+    xw = arr("lsx", (M, ldx), 53, 2.0) + 0.3
+    w, b = arr("lsw", (D,), 54) * 0.1 + 1, arr("lsb", (D,), 55) * 0.1
+    o16 = torch.full((M, ld16), 7.0, device="cuda", dtype=dt)
+    o32 = torch.full((M, ld32), -3.0, device="cuda")
+    ops.layernorm(dev(xw)[:, :ldx], dev(w), dev(b), out16=o16[:, :D], out32=o32[:, :D])
+    ref = orc.layer_norm(xw[:, :D], w, b)
+    report("layernorm strided fp32 D%d" % D, o32[:, :D].cpu(), ref, 2e-5)
+    report("layernorm strided 16b D%d" % D, o16[:, :D].float().cpu(), ref, 8 * EPS[dt])
+    assert bool((o16[:, D:] == 7.0).all()) and bool((o32[:, D:] == -3.0).all())
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("C,KS,T", [(256, 31, 200), (64, 7, 20), (256, 31, 64), (256, 31, 7), (384, 31, 200), (192, 15, 150),
+                                    (512, 3, 33)])
 def test_dwconv_bn_swish(ops, dt, C, KS, T):
     ops.set_compute_dtype(dt)
     B = 2
