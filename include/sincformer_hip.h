@@ -168,7 +168,7 @@ int sfm_pool_time_affine(const float* src, const float* scale, const float* shif
 int sfm_pool_time_affine16(const void* src16, int src_dtype, const float* scale, const float* shift, void* dst16, float* dst32,
                            int B, int Tin, int Tout, int C, long long ld_src, long long ld_dst, int dtype, void* stream);
 /* mean over time (glue G2: episodic-memory key), src fp32 [B, T, ld_src] cols [0, C) -> dst fp32 [B, C]; deterministic
- * two-pass sum, scratch: sfm_mean_time_scratch_floats floats */
+ * two-pass sum, scratch: sfm_mean_time_scratch_floats floats; ld_src < C is SFM_ERR_SHAPE (sfm_sum_time too) */
 long long sfm_mean_time_scratch_floats(int B, int T, int C);
 int sfm_mean_time(const float* src, float* dst, float* scratch, int B, int T, int C, long long ld_src, void* stream);
 /* the same reduction without the 1/T (training: gradient of a per-utterance bias broadcast over the frames) */

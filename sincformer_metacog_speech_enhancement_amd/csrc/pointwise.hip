@@ -1028,7 +1028,7 @@ extern "C" long long sfm_mean_time_scratch_floats(int B, int T, int C) { return 
 
 extern "C" int sfm_mean_time(const float* src, float* dst, float* scratch, int B, int T, int C, long long ld_src, void* stream) {
   if (!src || !dst || !scratch) return SFM_ERR_ARG;
-  if (B <= 0 || T <= 0 || C <= 0 || B > 65535) return SFM_ERR_SHAPE;
+  if (B <= 0 || T <= 0 || C <= 0 || B > 65535 || ld_src < C) return SFM_ERR_SHAPE;
   const int nchunk = (T + 63) / 64;
   SFM_LAUNCH(mean_time_partial_kernel, dim3((C + 255) / 256, nchunk, B), dim3(256), 0, (hipStream_t)stream, src, scratch, T, C, ld_src,
              nchunk);
@@ -1040,7 +1040,7 @@ extern "C" int sfm_mean_time(const float* src, float* dst, float* scratch, int B
 // sum over time with the same two passes (training: gradient of a per-utterance bias broadcast over the frames, glue G3)
 extern "C" int sfm_sum_time(const float* src, float* dst, float* scratch, int B, int T, int C, long long ld_src, void* stream) {
   if (!src || !dst || !scratch) return SFM_ERR_ARG;
-  if (B <= 0 || T <= 0 || C <= 0 || B > 65535) return SFM_ERR_SHAPE;
+  if (B <= 0 || T <= 0 || C <= 0 || B > 65535 || ld_src < C) return SFM_ERR_SHAPE;
   const int nchunk = (T + 63) / 64;
   SFM_LAUNCH(mean_time_partial_kernel, dim3((C + 255) / 256, nchunk, B), dim3(256), 0, (hipStream_t)stream, src, scratch, T, C, ld_src,
              nchunk);

@@ -100,3 +100,15 @@ def test_depthwise_conv_shape_checks_without_a_gpu(built):
     assert L.sfm_dwconv_folded(one, one, one, one, one, 2, 10, 192, 8, 1, 0, 7, None) == -2
     assert L.sfm_dwconv_folded(one, one, one, one, one, 2, 10, 192, 15, 1, 0, 7, None) == -1     # control: shape accepted
     assert L.sfm_dwconv_folded(one, one, one, one, one, 2, 10, 256, 31, 1, 0, 7, None) == -1
+
+
+def test_time_reductions_refuse_a_row_stride_below_the_row_without_a_gpu(built):
+    """sfm_sum_time / sfm_mean_time read C columns of rows ld_src apart: ld_src < C (rows overlap, the last one runs past its
+    buffer) is SFM_ERR_SHAPE, returned before any launch"""
+    L = built.load()
+    one = ctypes.c_void_p(16)
+    assert L.sfm_sum_time(one, one, one, 2, 5, 129, 128, None) == -2
+    assert L.sfm_mean_time(one, one, one, 2, 5, 129, 128, None) == -2
+    assert L.sfm_sum_time(one, one, one, 2, 5, 129, 0, None) == -2
+    assert L.sfm_mean_time(one, one, None, 2, 5, 129, 136, None) == -1      # (a null pointer is refused first, as everywhere)
+    assert L.sfm_sum_time(one, one, None, 2, 5, 129, 129, None) == -1

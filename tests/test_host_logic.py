@@ -318,3 +318,147 @@ def test_width_bounds_separate_plausible_wrong_answers():
         for what, e in errs.items():
             print("%-7s %-40s rel rmse %.3e (needs > %.2e)" % (r["id"], what, e, need))
             assert e > need, (r["id"], what, e)
+
+
+# ---------------------------------------------------------------------------
+# CPU companion of tests/test_train_nodes_gpu.py: the float64 restatements in helpers.py are the oracle's formulas (the oracle
+# itself is pinned to the reference by tests/test_oracle_golden.py), and the bounds derived from them separate wrong kernels
+# ---------------------------------------------------------------------------
+FP32_PIN = 2e-5          # float64 restatement against the oracle's own fp32 evaluation, relative to the largest value
+
+
+def _pin(name, got64, oracle32):
+    import helpers as hp
+    e = hp.figs(oracle32, got64)
+    print("%-40s restatement vs oracle: rel rmse %.2e max/max %.2e" % (name, e[0], e[1]))
+    assert e[0] < FP32_PIN and e[1] < FP32_PIN, (name, e)
+
+
+def test_float64_restatements_are_the_oracle():
+    import helpers as hp
+    # BiLSTM recurrence and its saved state, on the golden module's weights
+    sd = orc.sub(synth_sd("CorrelationPhaseEstimationAgent", 61), "lstm")
+    x = arr("lsx", (2, 21, 256), 90)
+    for sfx, rev in (("", False), ("_reverse", True)):
+        w = [sd[k + sfx] for k in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")]
+        xg = x.double() @ w[0].double().t() + w[2].double() + w[3].double()
+        out, save = hp.lstm_dir64(xg, w[1].double(), rev)
+        _pin("lstm_dir64 reverse=%s" % rev, out, orc._lstm_dir(x, *w, rev))
+        _pin("saved state reproduces the output", save[:, :, 3] * torch.tanh(save[:, :, 4]), orc._lstm_dir(x, *w, rev))
+    # framing + DFT = orc.stft at the four resolutions; istft64 = orc.istft; the three terms = orc.spectrum_objective
+    wave = arr("cw", (2, 1637), 70, 0.1)
+    for nf, hop, win in ((256, 80, 160), (256, 64, 256), (512, 128, 512), (1024, 256, 1024)):
+        re, im = hp.dft64(hp.frame64(wave.double(), nf, hop, win), nf, win)
+        o_re, o_im = orc.stft(wave, nf, hop, win)
+        _pin("frame64 + DFT %d/%d/%d" % (nf, hop, win), torch.stack([re, im]), torch.stack([o_re, o_im]))
+    clean = arr("cw", (2, 1637), 70, 0.1)
+    cr, ci = orc.stft(clean)
+    er, ei = 0.8 * cr + 0.05 * arr("pe", tuple(cr.shape), 72), 0.8 * ci + 0.05 * arr("pf", tuple(cr.shape), 73)
+    enh = hp.istft64(er.double(), ei.double(), 1637, 256, 80, 160)
+    _pin("istft64", enh, orc.istft(er, ei, 1637))
+    _pin("sisnr64", hp.sisnr64(enh, clean.double()), orc.si_snr_loss(orc.istft(er, ei, 1637), clean))
+    mr = 0.0
+    for nf, hop, win in ((256, 64, 256), (512, 128, 512), (1024, 256, 1024)):
+        p = hp.dft64(hp.frame64(enh, nf, hop, win), nf, win)
+        t = hp.dft64(hp.frame64(clean.double(), nf, hop, win), nf, win)
+        mr = mr + hp.spec_terms64(p[0], p[1], t[0], t[1], 0) / 3.0
+    _pin("spec_terms64 mode 0 (three resolutions)", mr, orc.mr_stft_loss(orc.istft(er, ei, 1637), clean))
+    l1 = hp.spec_terms64(er.double(), ei.double(), cr.double(), ci.double(), 1)
+    total, l_si, _ = orc.spectrum_objective(er, ei, clean, cr, ci)
+    _pin("the objective from the restatements", hp.sisnr64(enh, clean.double()) + 0.5 * l1 + mr, total)
+    _pin("spec_terms64 mode 1", l1, (total - l_si - orc.mr_stft_loss(orc.istft(er, ei, 1637), clean)) * 2.0)
+    # finalize64 from float64 sums of the same signals = the same three terms
+    e32, c64 = enh.float().double(), clean.double()
+    Sw = torch.stack([e32.sum(1), c64.sum(1), (e32 * e32).sum(1), (c64 * c64).sum(1), (e32 * c64).sum(1)], dim=1)
+    mag = lambda a, b: torch.sqrt(a.double() ** 2 + b.double() ** 2 + 1e-8)
+    Sm = torch.stack([torch.zeros(()).double()] * 3 + [(mag(er, ei) - mag(cr, ci)).abs().sum()])
+    fin = hp.finalize64(Sw, Sm, torch.zeros(1, 4), [1], 2, 1637, er.numel(), 0)
+    _pin("finalize64: SI-SNR and L1 magnitude", fin[1:3], torch.stack([l_si, (total - l_si - orc.mr_stft_loss(enh.float(), clean)) * 2]))
+    # polar mask and complex product on the golden MaskSynthesisAgent's logits
+    msd = synth_sd("MaskSynthesisAgent", 51)
+    zr, zi = arr("g5_zr", (2, 256, 21), 52), arr("g5_zi", (2, 256, 21), 52)
+    nr, ni = arr("g5_nr", (2, 21, 129), 52, 0.5), arr("g5_ni", (2, 21, 129), 52, 0.5)
+    cpea = orc.cpea_forward(synth_sd("CorrelationPhaseEstimationAgent", 61), zr)
+    bias = arr("g5_bias", (2, 129), 53)
+    mr0, mi0, lm, lp = orc.msa_forward(msd, zr, zi, cpea, nr, ni, return_logits=True)
+    mr1, mi1, _, _ = orc.msa_forward(msd, zr, zi, cpea, nr, ni, mag_logit_bias=bias, return_logits=True)
+    _pin("polar64", torch.stack(hp.polar64(lm.double(), lp.double(), None, None, None, hp.PHASE_SCALE)), torch.stack([mr0, mi0]))
+    _pin("polar64 with bias", torch.stack(hp.polar64(lm.double(), lp.double(), bias.double(), None, None, hp.PHASE_SCALE)),
+         torch.stack([mr1, mi1]))
+    _pin("polar64 x noisy", torch.stack(hp.polar64(lm.double(), lp.double(), bias.double(), nr.double(), ni.double(), hp.PHASE_SCALE)),
+         torch.stack(orc.apply_mask(nr, ni, mr1, mi1)))
+
+
+def test_hand_written_adjoints_equal_autograd():
+    """bptt64 (used for the arm B bound and the BPTT mutants) and adjoint_ola64 (the mutants' host) against torch autograd of
+    lstm_dir64 / frame64 in float64"""
+    import helpers as hp
+    for row in ((3, 40, 64), (2, 17, 32), (1, 1, 128), (4, 9, 128)):
+        c = hp.bptt_case(row)
+        e = hp.figs(hp.bptt_from_save(c["save64"], c["whh"].double(), c["dout"].double()), c["ref64"])
+        assert max(e) < 1e-12, (row, e)
+    for row in hp.ola_rows():
+        c = hp.ola_case(row)
+        e = hp.figs(c["ev"](torch.float64), c["ref64"])
+        assert max(e) < 1e-13, (row, e)
+
+
+def test_train_node_bounds_separate_plausible_wrong_answers():
+    """every row of tests/test_train_nodes_gpu.py, on the row's own inputs: each wrong form moves the float64 reference by at
+    least 5 x the row's bound (on one of the slices the row checks).  Bitwise rows have no bound: the wrong form must differ."""
+    import helpers as hp
+    f64 = torch.float64
+    for row in hp.ola_rows():
+        c = hp.ola_case(row)
+        for m in hp.OLA_MUTANTS:
+            if (m == "window offset ignored" and row[4] == row[2]) or (m == hp.OLA_MUTANTS[4] and not (row[5] and row[6])):
+                continue                                         # no window offset / nothing to reorder at this row
+            if m == hp.OLA_MUTANTS[2] and row[4] < row[2]:
+                continue                                         # sample n_fft/2 mirrors padded position 0, which no short window covers
+            hp.separates("stft_adjoint_ola %s" % (row,), m, c["ev"](f64, m), c["ref64"], c["ref32"], hp.K_SUM, c["sum_bound"], c["slices"])
+    for row in hp.SISNR_ROWS:
+        c = hp.sisnr_case(row)
+        for m in hp.SISNR_MUTANTS:
+            if m == "1/B missing" and row[0] == 1:
+                continue
+            hp.separates("sisnr_bwd %s" % (row,), m, c["ev"](f64, m), c["ref64"], c["ref32"], hp.K_TRANS)
+    for row in hp.SPEC_ROWS:
+        c = hp.spec_case(row)
+        for m in hp.SPEC_MUTANTS[row[2]]:
+            hp.separates("spec_loss_bwd %s" % (row,), m, c["ev"](f64, m), c["ref64"], c["ref32"], hp.K_TRANS, None, c["slices"])
+    for row in hp.POLAR_ROWS:
+        c = hp.polar_case(row)
+        for m in hp.POLAR_MUTANTS:
+            if (m == hp.POLAR_MUTANTS[0] and not row[4]) or (m == hp.POLAR_MUTANTS[2] and not row[3]):
+                continue
+            hp.separates("polar_mask_bwd %s" % (row,), m, c["ev"](f64, m)[0], c["ref64"], c["ref32"], hp.K_TRANS)
+    for row in hp.BPTT_ROWS:
+        if row[1] == 1:
+            continue                                             # one step: no recurrence to get wrong
+        c = hp.bptt_case(row)
+        for m in hp.BPTT_MUTANTS:
+            wrong = hp.bptt_from_save(c["save64"], c["whh"].double(), c["dout"].double(), m)
+            hp.separates("bilstm_layer_bwd %s" % (row,), m, wrong, c["ref64"], c["ref32"], hp.K_SUM, None, c["slices"])
+        for amp in (2e-5, 4e-3):                                 # arm B: 2 x the effect of the forward's allowed error
+            moved = hp.bptt_forward_error_bound(c, amp)
+            for m in hp.BPTT_MUTANTS:
+                wrong = hp.bptt_from_save(c["save64"], c["whh"].double(), c["dout"].double(), m)
+                hp.separates("bilstm_layer_bwd arm B %g %s" % (amp, row), m, wrong, c["ref64"], moved, 2.0, None, c["slices"])
+    for row in hp.TIME_ROWS:
+        B, T, C, ld = row
+        x = hp.time_case(row)[..., :C]
+        for mean in (False, True):
+            for m in hp.TIME_MUTANTS:
+                if T % 64 == 0 or (m == hp.TIME_MUTANTS[1] and not mean):
+                    continue                                     # whole chunks only: the wrong form is the right one
+                hp.separates("%s %s" % ("mean_time" if mean else "sum_time", row), m, hp.time_reduce(x.double(), mean, m),
+                             hp.time_reduce(x.double(), mean), hp.time_reduce(x, mean), hp.K_SUM, hp.time_sum_bound(x.double(), mean))
+    for row in hp.HPREV_ROWS:
+        B, T, H = row
+        h = hp.hprev_case(row)
+        for dt in (torch.float16, torch.bfloat16):
+            ref = hp.hprev_ref(h, B, T, H, dt)
+            for m in hp.HPREV_MUTANTS:
+                if T == 1 and m == hp.HPREV_MUTANTS[0]:
+                    continue                                     # one step: both halves are all zero either way
+                assert not torch.equal(hp.hprev_ref(h, B, T, H, dt, m), ref), (row, dt, m)

@@ -1,0 +1,405 @@
+"""Each fp32 streaming / reduction / recurrence node of the training path (objective, mask heads, glue, BiLSTM) called
+directly and compared, element by element, with a float64 restatement of the same operation (helpers.py; pinned to the oracle
+and shown to separate wrong kernels by tests/test_host_logic.py).
+
+Bounds come from the reference alone: e32 = error of the same restatement evaluated in float32 on the CPU; bound = 4 x e32
+for rows that only add and multiply, 16 x e32 behind the hardware's exp / rcp / sin / cos / log / sqrt, or the elementwise
+n 2^-24 sum|terms| bound of an fp32 sum where that is larger; bitwise rows have none.  Every row prints
+`ROW | name | slice | e32 | bound | observed` as (relative RMSE, max|err| / max|ref|); profiles/README.md keeps the table."""
+import os
+import subprocess
+import sys
+
+import pytest
+import torch
+
+import helpers as hp
+from helpers import arr
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DTYPES = [torch.bfloat16, torch.float16]
+NAN = float("nan")
+SENTINEL = 7.0                                              # what the padding columns hold before a kernel runs
+
+
+@pytest.fixture(scope="module")
+def ops():
+    assert torch.cuda.is_available()
+    from sincformer_metacog_speech_enhancement_amd import ops as _ops
+    return _ops
+
+
+@pytest.fixture(scope="module")
+def train():
+    assert torch.cuda.is_available()
+    from sincformer_metacog_speech_enhancement_amd import train as _train
+    return _train
+
+
+def dev(t):
+    return None if t is None else t.cuda().contiguous()
+
+
+def _id(row):
+    return "-".join(str(v) for v in row)
+
+
+# ---------------------------------------------------------------------------
+# objective
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("row", hp.ola_rows(), ids=_id)
+def test_stft_adjoint_ola(ops, row):
+    """against torch autograd of "reflect-pad, then cut frames"; the first / last n_fft/2 samples (where the reflected images
+    land) are reported and bounded apart from the interior"""
+    B, L, nf, hop, wn, acc, post = row
+    c = hp.ola_case(row)
+    dwave = dev(c["prev"]) if acc else torch.full((B, L), NAN, device="cuda")
+    ops.stft_adjoint_ola(dev(c["frames"]), dwave, B, c["T"], L, nf, hop, wn, accumulate=acc, post=dev(c["post"]))
+    hp.check_row("stft_adjoint_ola %s" % _id(row), dwave.cpu(), c["ref64"], c["ref32"], hp.K_SUM, c["sum_bound"], c["slices"])
+
+
+@pytest.mark.parametrize("row", hp.SISNR_ROWS, ids=_id)
+def test_sisnr_bwd(ops, row):
+    """wave_moments -> sisnr_bwd on signals with (different) DC offsets; L 70001 walks the grid-stride loop"""
+    B, L, scale = row
+    c = hp.sisnr_case(row)
+    Sw = ops.wave_moments(dev(c["est"]), dev(c["tgt"]))
+    e, t = c["est"].double(), c["tgt"].double()
+    ref = torch.stack([e.sum(1), t.sum(1), (e * e).sum(1), (t * t).sum(1), (e * t).sum(1)], dim=1)
+    mag = torch.stack([e.abs().sum(1), t.abs().sum(1), (e * e).sum(1), (t * t).sum(1), (e * t).abs().sum(1)], dim=1)
+    # float64 accumulation of L exactly representable terms, in any order (the float64 reference sum included)
+    assert bool(((Sw.cpu() - ref).abs() <= 2 * L * 2.0 ** -53 * mag).all()), (Sw.cpu() - ref).abs().max()
+    dwave = torch.full((B, L), NAN, device="cuda")
+    ops.sisnr_bwd(dev(c["est"]), dev(c["tgt"]), Sw, dwave, scale=scale)
+    hp.check_row("sisnr_bwd %s" % _id(row), dwave.cpu(), c["ref64"], c["ref32"], hp.K_TRANS)
+
+
+def _spec_run(ops, row, c):
+    M, F, mode, padded, acc, scale = row
+    pr, pi, tr, ti = (dev(c[k]) for k in ("pr", "pi", "tr", "ti"))
+    S = ops.spec_sums(pr, pi, tr, ti)
+    if padded:
+        ld = ops.round_up(2 * F, 8)
+        g = torch.full((M, ld), SENTINEL, device="cuda")
+        g[:, :2 * F] = torch.cat([dev(c["prev"][0]), dev(c["prev"][1])], dim=1) if acc else NAN
+        dr, di = g, g[:, F:]
+    else:
+        ld = F
+        dr, di = (dev(c["prev"][0]), dev(c["prev"][1])) if acc else (torch.full((M, F), NAN, device="cuda") for _ in range(2))
+    ops.spec_loss_bwd(pr, pi, tr, ti, S, dr, di, F, ld, mode, accumulate=acc, scale=scale)
+    if padded:
+        assert bool((g[:, 2 * F:] == SENTINEL).all()), "padding columns written"
+        return torch.stack([g[:, :F], g[:, F:2 * F]]).cpu(), S
+    return torch.stack([dr, di]).cpu(), S
+
+
+@pytest.mark.parametrize("row", hp.SPEC_ROWS, ids=_id)
+def test_spec_loss_bwd(ops, row):
+    """spec_sums -> spec_loss_bwd: every bin, the bins of ordinary size apart from the ~5 % small ones that dominate the RMS;
+    row 0 is P = 0 + 0j and row 1 is P = T exactly (zero gradient of the sign terms in the reference's convention)"""
+    c = hp.spec_case(row)
+    got, _ = _spec_run(ops, row, c)
+    hp.check_row("spec_loss_bwd %s" % _id(row), got, c["ref64"], c["ref32"], hp.K_TRANS, None, c["slices"])
+    if not row[4]:
+        assert bool((got[:, 0] == 0).all()), "gradient at P = 0 + 0j"
+        assert bool((got[:, 1] == 0).all()), "gradient at P = T"
+
+
+@pytest.mark.parametrize("R", [0, 1, 3])
+def test_enhancer_loss_finalize(ops, R):
+    """the four terms from the kernels' own reductions against float64 arithmetic on the same sums; the three resolutions
+    have unequal element counts"""
+    B, L = 3, 4321
+    w = hp.sisnr_case((B, L, 1.0))
+    Sw = ops.wave_moments(dev(w["est"]), dev(w["tgt"]))
+    rows = [hp.SPEC_ROWS[0], hp.SPEC_ROWS[4], hp.SPEC_ROWS[2]]
+    sums, counts = [], []
+    for r in rows:
+        c = hp.spec_case(r)
+        sums.append(ops.spec_sums(*(dev(c[k]) for k in ("pr", "pi", "tr", "ti"))))
+        counts.append(c["pr"].numel())
+    assert len(set(counts)) > 1
+    Sr, Sm = torch.stack(sums), sums[2]
+    nr = torch.tensor(counts, device="cuda", dtype=torch.int64)
+    out = ops.enhancer_loss_finalize(Sw, Sm, Sr, nr, B, L, counts[2], R=(None if R == 3 else R))
+    ref64 = hp.finalize64(Sw.cpu(), Sm.cpu(), Sr.cpu(), counts, B, L, counts[2], R)
+    ref32 = hp.finalize64(Sw.cpu(), Sm.cpu(), Sr.cpu(), counts, B, L, counts[2], R, dtype=torch.float32)
+    terms = {name: (lambda t, i=i: t[i:i + 1]) for i, name in enumerate(("total", "neg SI-SNR", "L1 magnitude", "MR-STFT"))}
+    hp.check_row("enhancer_loss_finalize R=%d" % R, out.cpu(), ref64, ref32, hp.K_TRANS, None, terms)
+    assert (float(out[3]) == 0.0) == (R == 0)
+
+
+# ---------------------------------------------------------------------------
+# mask heads
+# ---------------------------------------------------------------------------
+def _logit_layout(layout, c, M, F):
+    lm, lp = c["lm"].reshape(M, F), c["lp"].reshape(M, F)
+    if layout == "split":
+        return dev(lm), dev(lp), F
+    ld = 2 * F if layout == "merged" else 2 * F + 6
+    buf = torch.full((M, ld), NAN, device="cuda")
+    buf[:, :F], buf[:, F:2 * F] = lm.cuda(), lp.cuda()
+    return buf, buf[:, F:], ld
+
+
+@pytest.mark.parametrize("row", hp.POLAR_ROWS, ids=_id)
+def test_polar_mask_bwd(ops, row):
+    B, T, F, noisy, bias, layout = row
+    M = B * T
+    c = hp.polar_case(row)
+    a, b_, ld = _logit_layout(layout, c, M, F)
+    ldd = ops.round_up(2 * F, 8)
+    dlog = torch.full((M, ldd), SENTINEL, device="cuda")
+    dlog[:, :2 * F] = NAN
+    flat = lambda t: None if t is None else dev(t.reshape(M, F))
+    ops.polar_mask_bwd(a, b_, flat(c["nr"]), flat(c["ni"]), flat(c["gr"]), flat(c["gi"]), dlog, M, F, hp.PHASE_SCALE, ld,
+                       mag_bias=dev(c["bias"]), rows_per_batch=T)
+    assert bool((dlog[:, 2 * F:] == SENTINEL).all()), "padding columns written"
+    got = torch.stack([dlog[:, :F].reshape(B, T, F), dlog[:, F:2 * F].reshape(B, T, F)]).cpu()
+    hp.check_row("polar_mask_bwd %s" % _id(row), got, c["ref64"], c["ref32"], hp.K_TRANS)
+    if bias:                                                 # d bias = sum over the frames of d magnitude logit
+        db = ops.sum_time(dlog, B, T, F, ldd)
+        hp.check_row("polar_mask_bwd %s d bias (sum_time)" % _id(row), db.cpu(), c["db64"], c["db32"], hp.K_TRANS,
+                     hp.time_sum_bound(c["ref64"][0], False))
+
+
+def test_polar_mask_function(train):
+    row = hp.POLAR_ROWS[0]
+    B, T, F = row[:3]
+    c = hp.polar_case(row)
+    lg = torch.cat([c["lm"], c["lp"]], dim=-1).reshape(B * T, 2 * F).cuda().requires_grad_(True)
+    er, ei, mm = train.PolarMaskFunction.apply(lg, dev(c["nr"]), dev(c["ni"]), hp.PHASE_SCALE)
+    hp.check_row("PolarMaskFunction forward", torch.stack([er, ei]).detach().cpu(), c["fwd64"], c["fwd32"], hp.K_TRANS)
+    hp.check_row("PolarMaskFunction mask magnitude", mm.cpu(), torch.sigmoid(c["lm"].double()), torch.sigmoid(c["lm"]), hp.K_TRANS)
+    ((er * dev(c["gr"])).sum() + (ei * dev(c["gi"])).sum()).backward()
+    got = torch.stack([lg.grad[:, :F].reshape(B, T, F), lg.grad[:, F:].reshape(B, T, F)]).cpu()
+    hp.check_row("PolarMaskFunction backward", got, c["ref64"], c["ref32"], hp.K_TRANS)
+
+
+@pytest.mark.parametrize("layout", ["merged", "strided", "split"])
+@pytest.mark.parametrize("bias", [False, True])
+def test_mask_head_function(train, layout, bias):
+    """the mask itself (no noisy spectrum), B = 3 distinct bias rows, d bias through sum_time"""
+    B, T, F = 3, 50, 129
+    M = B * T
+    c = hp.polar_case((B, T, F, False, bias, layout))
+    bs = dev(c["bias"]).requires_grad_(True) if bias else None
+    if layout == "split":
+        lm, lp = dev(c["lm"].reshape(M, F)).requires_grad_(True), dev(c["lp"].reshape(M, F)).requires_grad_(True)
+        mr, mi = train.MaskHeadFunction.apply(lm, lp, bs, B, T, hp.PHASE_SCALE)
+    else:
+        buf = torch.zeros(M, 2 * F + (6 if layout == "strided" else 0), device="cuda")
+        buf[:, :F], buf[:, F:2 * F] = c["lm"].reshape(M, F).cuda(), c["lp"].reshape(M, F).cuda()
+        buf.requires_grad_(True)
+        mr, mi = train.MaskHeadFunction.apply(buf[:, :2 * F], None, bs, B, T, hp.PHASE_SCALE)
+    name = "MaskHeadFunction %s%s" % (layout, " + bias" if bias else "")
+    hp.check_row(name + " forward", torch.stack([mr, mi]).detach().cpu(), c["fwd64"], c["fwd32"], hp.K_TRANS)
+    ((mr * dev(c["gr"])).sum() + (mi * dev(c["gi"])).sum()).backward()
+    if layout == "split":
+        got = torch.stack([lm.grad.reshape(B, T, F), lp.grad.reshape(B, T, F)]).cpu()
+    else:
+        got = torch.stack([buf.grad[:, :F].reshape(B, T, F), buf.grad[:, F:2 * F].reshape(B, T, F)]).cpu()
+        assert bool((buf.grad[:, 2 * F:] == 0).all())
+    hp.check_row(name + " backward", got, c["ref64"], c["ref32"], hp.K_TRANS)
+    if bias:
+        hp.check_row(name + " d bias", bs.grad.cpu(), c["db64"], c["db32"], hp.K_TRANS, hp.time_sum_bound(c["ref64"][0], False))
+
+
+# ---------------------------------------------------------------------------
+# glue
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("row", hp.TIME_ROWS, ids=_id)
+def test_sum_time_and_mean_time(ops, train, row):
+    B, T, C, ld = row
+    x = hp.time_case(row)
+    x64 = x[..., :C].double()
+    for mean in (False, True):
+        got = ops.mean_time(dev(x), B, T, C, ld) if mean else ops.sum_time(dev(x), B, T, C, ld)
+        hp.check_row("%s %s" % ("mean_time" if mean else "sum_time", _id(row)), got.cpu(), hp.time_reduce(x64, mean),
+                     hp.time_reduce(x[..., :C], mean), hp.K_SUM, hp.time_sum_bound(x64, mean))
+    xg = dev(x).requires_grad_(True)
+    out = train.MeanTimeFunction.apply(xg[..., :C])                    # a column slice of wider rows is read in place
+    hp.check_row("MeanTimeFunction forward %s" % _id(row), out.detach().cpu(), hp.time_reduce(x64, True),
+                 hp.time_reduce(x[..., :C], True), hp.K_SUM, hp.time_sum_bound(x64, True))
+    g = arr("tm_g", (B, C), T + C + 1)
+    out.backward(dev(g))
+    ref = lambda dt: (g.to(dt) / T).unsqueeze(1).expand(B, T, C)
+    hp.check_row("MeanTimeFunction backward %s" % _id(row), xg.grad[..., :C].cpu(), ref(torch.float64), ref(torch.float32), hp.K_SUM,
+                 2 * hp.U32 * ref(torch.float64).abs())
+    assert bool((xg.grad[..., C:] == 0).all())
+
+
+# (M, C, Cb, lda, ldb): Cb = 0, C/2, C; row-strided a and b; 70000 x 256 / 4 > 16384 x 256
+ADD_ROWS = [(1000, 256, 128, 264, 132), (1000, 256, 0, 256, 4), (1000, 256, 256, 260, 256), (333, 264, 132, 272, 136),
+            (333, 264, 264, 264, 268), (70000, 256, 128, 256, 128)]
+
+
+@pytest.mark.parametrize("row", ADD_ROWS, ids=_id)
+def test_add_cols_bitwise(ops, row):
+    M, C, Cb, lda, ldb = row
+    a, b_ = arr("ac_a", (M, lda), C + Cb), arr("ac_b", (M, ldb), C + Cb + 1)
+    out = ops.add_cols(a.cuda()[:, :C], b_.cuda()[:, :max(Cb, 1)], M, C, Cb)
+    ref = a[:, :C].clone()
+    ref[:, :Cb] += b_[:, :Cb]
+    assert torch.equal(out.cpu().view(torch.int32), ref.view(torch.int32))
+
+
+def test_latent_fanout_function_bitwise(train):
+    """both consumers' gradients arrive as row-strided views: folded by ONE sfm_add_cols, equal to the fp32 add bit for bit"""
+    B, T, D = 3, 77, 128
+    zp = arr("lf_z", (B, T, 2 * D), 1).cuda().requires_grad_(True)
+    whole, half = train.LatentFanoutFunction.apply(zp, D)
+    assert torch.equal(whole, zp) and torch.equal(half, zp[..., :D])
+    ga, gh = arr("lf_ga", (B, T, 2 * D + 8), 2), arr("lf_gh", (B, T, D + 4), 3)
+    torch.autograd.backward([whole, half], [ga.cuda()[..., :2 * D], gh.cuda()[..., :D]])
+    ref = ga[..., :2 * D].clone()
+    ref[..., :D] += gh[..., :D]
+    assert torch.equal(zp.grad.cpu().view(torch.int32), ref.view(torch.int32))
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("row", hp.HPREV_ROWS, ids=_id)
+def test_lstm_hprev16_bitwise(ops, row, dt):
+    B, T, H = row
+    ops.set_compute_dtype(dt)
+    h = hp.hprev_case(row)
+    out = ops.lstm_hprev16(h.cuda(), B, T, H)
+    assert out.dtype is dt
+    assert torch.equal(out.cpu().view(torch.int16), hp.hprev_ref(h, B, T, H, dt).view(torch.int16))
+
+
+# ---------------------------------------------------------------------------
+# iSTFT and complex product under autograd
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("L", [1600, 1637, 479])
+def test_istft_function(train, L):
+    B, nf, hop, wn = 2, 256, 80, 160
+    T, F = 1 + L // hop, nf // 2 + 1
+    re, im, g = arr("is_r", (B, T, F), L) * 0.1, arr("is_i", (B, T, F), L + 1) * 0.1, arr("is_g", (B, L), L + 2)
+
+    def ev(dt, absolute=False):
+        r, i = [(t.abs() if absolute else t).to(dt).clone().requires_grad_(True) for t in (re, im)]
+        w = hp.istft64(r, i, L, nf, hop, wn, absolute)
+        (w * (g.abs() if absolute else g).to(dt)).sum().backward()
+        return w.detach(), torch.stack([r.grad, i.grad])
+    w64, g64 = ev(torch.float64)
+    w32, g32 = ev(torch.float32)
+    # a matrix product's rounding depends on the order of its sum (and e32 on the host's BLAS): where it is larger, the
+    # n 2^-24 sum|terms| bound of the sum itself.  Forward: 2F products per frame, ceil(win / hop) frames per sample, their
+    # overlap-add and the division by the envelope; backward: win products, the division and the product with the window
+    wabs, gabs = ev(torch.float64, absolute=True)
+    fr = -(-wn // hop)
+    n_fwd, n_bwd = 2 * F * fr + fr + 1, wn + 2
+    r, i = re.cuda().requires_grad_(True), im.cuda().requires_grad_(True)
+    w = train.IstftFunction.apply(r, i, L, nf, hop, wn)
+    hp.check_row("IstftFunction forward L=%d" % L, w.detach().cpu(), w64, w32, hp.K_SUM, n_fwd * hp.U32 * wabs)
+    w.backward(g.cuda())
+    hp.check_row("IstftFunction backward L=%d" % L, torch.stack([r.grad, i.grad]).cpu(), g64, g32, hp.K_SUM, n_bwd * hp.U32 * gabs)
+
+
+def test_complex_mul_function(train):
+    shape = (2, 50, 129)
+    x = [arr("cm%d" % i, shape, 40 + i) for i in range(4)]
+    cot = [arr("cmg%d" % i, shape, 50 + i) for i in range(2)]
+
+    def ev(dt):
+        v = [t.to(dt).clone().requires_grad_(True) for t in x]
+        er, ei = v[2] * v[0] - v[3] * v[1], v[2] * v[1] + v[3] * v[0]
+        ((er * cot[0].to(dt)).sum() + (ei * cot[1].to(dt)).sum()).backward()
+        return torch.stack([er.detach(), ei.detach()]), torch.stack([t.grad for t in v])
+    f64, g64 = ev(torch.float64)
+    f32, g32 = ev(torch.float32)
+    v = [t.cuda().requires_grad_(True) for t in x]
+    er, ei = train.ComplexMulFunction.apply(*v)
+    # two products and one add per element: 3 roundings (a fused multiply-add has fewer)
+    two = lambda a, b, c, d: 3 * hp.U32 * ((a * b).abs() + (c * d).abs())
+    d = [t.double() for t in x]
+    hp.check_row("ComplexMulFunction forward", torch.stack([er, ei]).detach().cpu(), f64, f32, hp.K_SUM,
+                 torch.stack([two(d[2], d[0], d[3], d[1]), two(d[2], d[1], d[3], d[0])]))
+    ((er * cot[0].cuda()).sum() + (ei * cot[1].cuda()).sum()).backward()
+    hp.check_row("ComplexMulFunction backward", torch.stack([t.grad for t in v]).cpu(), g64, g32, hp.K_SUM)
+
+
+# ---------------------------------------------------------------------------
+# BiLSTM: BPTT
+# ---------------------------------------------------------------------------
+def _arm_a(ops, row, tag=""):
+    """the kernel walks the REFERENCE's saved state (rounded to fp32): only the BPTT itself is under test"""
+    B, T, H = row
+    c = hp.bptt_case(row)
+    dxg = ops.bilstm_layer_bwd(dev(c["save64"].float()), dev(c["whh"]), dev(c["dout"]), B, T, H)
+    hp.check_row("bilstm_layer_bwd arm A%s %s" % (tag, _id(row)), dxg.cpu(), c["ref64"], c["ref32"], hp.K_SUM, None, c["slices"])
+
+
+@pytest.mark.parametrize("row", hp.BPTT_ROWS, ids=_id)
+def test_bilstm_layer_bwd_arm_a(ops, row):
+    _arm_a(ops, row)
+
+
+def test_bilstm_layer_bwd_arm_a_eight_lanes_per_unit():
+    """bilstm_layer_bwd_kernel<128, 8>: SFM_LSTM_BWD_LPU is read once per process, so the hidden-128 rows run in a child"""
+    env = dict(os.environ, SFM_LSTM_BWD_LPU="8", PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    cmd = [sys.executable] + (["-s"] if sys.flags.no_user_site else []) + [os.path.abspath(__file__), "lpu8"]
+    r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    print(r.stdout)
+    assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])
+    assert r.stdout.count("ROW | bilstm_layer_bwd arm A <128, 8>") == 3 * 5
+
+
+@pytest.mark.parametrize("w16", [False, True])
+@pytest.mark.parametrize("row", hp.BPTT_ROWS, ids=_id)
+def test_bilstm_layer_train_then_bwd_arm_b(ops, row, w16):
+    """the kernel's own forward feeds its BPTT.  The bound is the reference's: perturb the float64 saved state by uniform
+    noise of the amplitude the suite allows the forward (2e-5 fp32 recurrence, test_bilstm_layer; 4e-3 fp16 recurrence,
+    test_bilstm_layer_train_fp16_recurrence_saves_consistent_state; hidden 32 keeps the fp32 kernel) and take twice the distance
+    the float64 gradient moves.  The forward is held to those amplitudes here as well."""
+    B, T, H = row
+    c = hp.bptt_case(row)
+    half = w16 and H != 32
+    amp, out_tol = (4e-3, 2e-3) if half else (2e-5, 2e-5)
+    out, save = ops.bilstm_layer_train(dev(c["xg"]), dev(c["whh"]), B, T, H, w16=w16)
+    e_out, e_save = hp.maxerr(out.cpu(), c["out64"]), hp.maxerr(save.cpu(), c["save64"])
+    print("bilstm_layer_train %s w16=%s: max|err| out %.2e (<= %.0e) saved state %.2e (<= %.0e)" % (_id(row), w16, e_out, out_tol,
+                                                                                               e_save, amp))
+    assert e_out <= out_tol and e_save <= amp
+    dxg = ops.bilstm_layer_bwd(save, dev(c["whh"]), dev(c["dout"]), B, T, H)
+    moved = hp.bptt_forward_error_bound(c, amp)
+    hp.check_row("bilstm_layer_train -> bwd arm B w16=%s %s" % (w16, _id(row)), dxg.cpu(), c["ref64"], moved, 2.0, None, c["slices"],
+                 unit="moved by the forward's allowed error")
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+def test_bilstm_layer_function_hidden_64(ops, train, dt):
+    """BiLSTMLayerFunction at hidden 64 (bilstm_layer_bwd_kernel<64, 8> and the saving forward at hidden 64), every returned
+    gradient against autograd of the float64 layer, with the 16-bit bounds of test_cpea_train_mode_bptt"""
+    ops.set_compute_dtype(dt)
+    B, T, Din, H = 3, 40, 256, 64
+    names = ("x", "wif", "whf", "bif", "bhf", "wir", "whr", "bir", "bhr")
+    shapes = ((B, T, Din), (4 * H, Din), (4 * H, H), (4 * H,), (4 * H,), (4 * H, Din), (4 * H, H), (4 * H,), (4 * H,))
+    scales = (1.0, Din ** -0.5, H ** -0.5, 0.1, 0.1, Din ** -0.5, H ** -0.5, 0.1, 0.1)
+    v = [arr("bl_" + n, s, 80 + i) * sc for i, (n, s, sc) in enumerate(zip(names, shapes, scales))]
+    cot = arr("bl_cot", (B, T, 2 * H), 99)
+    r = [t.double().requires_grad_(True) for t in v]
+    xg = torch.stack([r[0] @ r[1].t() + r[3] + r[4], r[0] @ r[5].t() + r[7] + r[8]], dim=2)
+    ref_out, _ = hp.bilstm64(xg, torch.stack([r[2], r[6]]))
+    (ref_out * cot.double()).sum().backward()
+    g = [t.cuda().requires_grad_(True) for t in v]
+    out = train.BiLSTMLayerFunction.apply(*g)
+    (out * cot.cuda()).sum().backward()
+    tol = 2e-3 if dt is torch.float16 else 1.5e-2
+    e = hp.rmse(out.detach().cpu(), ref_out.detach())
+    print("BiLSTMLayerFunction H 64 %s: output rmse %.2e (tol %.1e)" % (dt, e, tol))
+    assert e < tol
+    for n, got, ref in zip(names, g, r):
+        rel = hp.rel_rmse(got.grad.cpu(), ref.grad)
+        print("BiLSTMLayerFunction H 64 %s: d %-4s rel rmse %.2e (tol %.1e)" % (dt, n, rel, tol))
+        assert rel < tol, (n, rel)
+
+
+if __name__ == "__main__":                                   # child of test_bilstm_layer_bwd_arm_a_eight_lanes_per_unit
+    assert sys.argv[1:] == ["lpu8"] and os.environ.get("SFM_LSTM_BWD_LPU") == "8"
+    from sincformer_metacog_speech_enhancement_amd import ops as _ops
+    for _row in hp.BPTT_ROWS:
+        if _row[2] == 128:
+            _arm_a(_ops, _row, " <128, 8>")
