@@ -152,6 +152,39 @@ int sfm_dwconv_bn_swish(const void* x, const float* wdw, const float* bdw, const
 int sfm_dwconv_folded(const void* x, const float* wT, const float* sc, const float* sh, void* out, int B, int T,
                       int C, int KS, int act, int out_f32, int dtype, void* stream);
 
+/* ---- packed (variable-length) batches: B utterances of different lengths back to back, no padding ----------------------
+ * Row matrices hold the frames of all utterances concatenated: utterance u owns rows [frame_off[u], frame_off[u + 1]),
+ * frame_off = int32[B + 1] on the device, ascending from 0, frame_off[B] = sum_T; waveforms likewise with samp_off.  The offsets
+ * are read on the device; the host passes B, the longest utterance max_T and sum_T, which it knows from the lengths.  Each
+ * utterance's result is what the dense entry point gives for it alone.  Null pointers -> SFM_ERR_ARG, B <= 0 and the shape
+ * rules of the dense twin -> SFM_ERR_SHAPE, before any HIP call. */
+/* sfm_framed_gemm_f32 on packed signals: frame t of utterance u = its samples t * hop + k - padl, zero (mode 0) or reflected
+ * at its own first / last sample (mode 1; every signal longer than padl).  A 128-row tile covers packed rows of any number of
+ * utterances.  out / out2 rows at stride ldm, columns at stride ldn, columns >= nsplit go to out2 when given. */
+int sfm_framed_gemm_f32_varlen(const float* sig, const float* Wt, void* out, void* out2, const int* samp_off,
+                               const int* frame_off, int B, int sum_T, int hop, int padl, int K, int Kpad, int N, int Npad,
+                               int nsplit, long long ldm, long long ldn, int mode, int out_f32, int dtype, void* stream);
+/* sfm_framed_gemm_split16 on packed signals (same layout, fp32 result) */
+int sfm_framed_gemm_split16_varlen(const float* sig, const void* Whi, const void* Wlo, float* out, float* out2,
+                                   const int* samp_off, const int* frame_off, int B, int sum_T, int hop, int padl, int K,
+                                   int Kpad, int N, int Npad, int nsplit, int col2_off, long long ldm, int mode, void* stream);
+/* sfm_attention_fwd_ex on packed rows: every utterance attends to its own rows.  head_dim 64: the 4-wave MFMA kernel, one
+ * workgroup per entry of items = int32[n_items][4] (utterance, head, 128-row query tile, 0), every existing tile exactly once;
+ * other head_dim <= 256: one wave per row, items unused, operands' format only (SFM_ERR_SHAPE otherwise).  scale <= 0: Q
+ * already carries softmax_scale * log2(e). */
+int sfm_attention_fwd_varlen(const void* qkv, void* out, const int* frame_off, const int* items, int n_items, int B, int max_T,
+                             int sum_T, int H, int hd, int ldqkv, int ldo, int koff, int voff, float scale, int dtype,
+                             int out_dtype, void* stream);
+/* sfm_dwconv_folded on packed rows [sum_T, C]: zero edge at every utterance's own first and last frame.  KS 7 / 31 with C in
+ * {32, 64, 128, 256, 512}: one workgroup per entry of tiles = int32[n_tiles][2] (utterance, 64-frame tile of it); any other
+ * C > 0 and odd KS: generic kernel, tiles unused. */
+int sfm_dwconv_folded_varlen(const void* x, const float* wT, const float* sc, const float* sh, void* out, const int* frame_off,
+                             const int* tiles, int n_tiles, int B, int max_T, int sum_T, int C, int KS, int act, int out_f32,
+                             int dtype, void* stream);
+/* sfm_istft_ola on packed frames [sum_T, ld_frames] -> packed samples [sum_L]: per-utterance frame range, envelope, length */
+int sfm_istft_ola_varlen(const float* frames, const float* win2, float* out, const int* frame_off, const int* samp_off, int B,
+                         int sum_L, int n_fft, int hop, int win, long long ld_frames, void* stream);
+
 /* layout / packing */
 int sfm_convert_rows(const float* src, void* dst, long long M, int C, int Cz, long long ld_src,
                      long long ld_dst, int dtype, void* stream);

@@ -55,13 +55,18 @@ __device__ __forceinline__ uint32_t pack2_o(float lo, float hi, bool other) {
   return other ? BF16::pack(lo, hi) : F16::pack(lo, hi);
 }
 
-template <class T, bool DROP>
+// VARLEN: the packed form.  qkv / out hold the rows of all utterances back to back (utterance u = rows [frame_off[u],
+// frame_off[u + 1])); a workgroup is one entry (utterance, head, query tile) of the item table the host built from the lengths
+// (ops.attention_items: only the tiles that exist, longest key range first).  Query tiles start at the utterance's first row and
+// keys run over that utterance alone, so an utterance's result is the dense kernel's on that utterance by itself.
+template <class T, bool DROP, bool VARLEN = false>
 __global__ __launch_bounds__(256) void attn_fwd_hd64_kernel(const u16* __restrict__ qkv, u16* __restrict__ out,
                                                             int Tlen, int ldqkv, int ldo, int koff, int voff,
                                                             long long qkv_batch_stride, long long o_batch_stride,
                                                             float scale_log2e, int nqt, int nheads,
                                                             float* __restrict__ lse_out, float p_drop, uint32_t seed,
-                                                            int out_other) {
+                                                            int out_other, const int* __restrict__ frame_off = nullptr,
+                                                            const int* __restrict__ items = nullptr) {
   constexpr int KV_BUF = 64 * KS_ROW + 64 * VS_ROW;
   __shared__ __attribute__((aligned(16))) u16 smem[2 * KV_BUF];
 
@@ -69,12 +74,24 @@ __global__ __launch_bounds__(256) void attn_fwd_hd64_kernel(const u16* __restric
   // XCD-aware order: workgroups are dealt round-robin over the 8 XCDs, so give each XCD a contiguous
   // run of (batch, head, q-tile) ids: the q-tiles that share one (batch, head)'s K/V then share an L2.
   int id = blockIdx.x;
-  {
+  int qt, h, b;
+  if (VARLEN) {
+    // (the host has dealt the table over the XCDs already: ops.attention_items)
+    const int u = __builtin_amdgcn_readfirstlane(items[4 * id]);
+    h = __builtin_amdgcn_readfirstlane(items[4 * id + 1]);
+    qt = __builtin_amdgcn_readfirstlane(items[4 * id + 2]);
+    const int row0 = __builtin_amdgcn_readfirstlane(frame_off[u]);
+    Tlen = __builtin_amdgcn_readfirstlane(frame_off[u + 1]) - row0;
+    b = 0;
+    qkv += (long long)row0 * ldqkv;
+    out += (long long)row0 * ldo;
+  } else {
     const int total = gridDim.x, q = total >> 3, r = total & 7, xcd = id & 7, slot = id >> 3;
     id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
+    qt = id % nqt;
+    h = (id / nqt) % nheads;
+    b = id / (nqt * nheads);
   }
-  const int qt = id % nqt;
-  const int h = (id / nqt) % nheads, b = id / (nqt * nheads);
   const int q0 = qt * 128 + wave * 32;
   const int hl = lane >> 5, l31 = lane & 31;
   const u16* base = qkv + (long long)b * qkv_batch_stride + h * 64;
@@ -702,17 +719,28 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_hd64r_kernel(const u16* __res
 // generic small-shape attention: one wave per query row, lanes over head_dim
 // (<= 256 => up to 4 elements per lane), two passes over the keys in fp32.
 // ---------------------------------------------------------------------------
-template <class T>
+// VARLEN: the packed form (see attn_fwd_hd64_kernel): the grid runs over the packed rows, `Tlen` is their number sum(T_i), and
+// each wave finds the utterance of its row by a binary search in frame_off [nutt + 1]; keys are that utterance's rows.
+template <class T, bool VARLEN = false>
 __global__ __launch_bounds__(256) void attn_fwd_generic_kernel(const u16* __restrict__ qkv, u16* __restrict__ out,
                                                                int Tlen, int hd, int ldqkv, int ldo, int koff,
                                                                int voff, long long qkv_batch_stride,
                                                                long long o_batch_stride, float scale,
-                                                               float* __restrict__ lse_out, float p_drop, uint32_t seed) {
+                                                               float* __restrict__ lse_out, float p_drop, uint32_t seed,
+                                                               const int* __restrict__ frame_off = nullptr, int nutt = 0) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int q = blockIdx.x * 4 + wave;
+  int q = blockIdx.x * 4 + wave;
   const int h = blockIdx.y, b = blockIdx.z;
   const int nheads = gridDim.y;
   if (q >= Tlen) return;
+  if (VARLEN) {
+    const int u = sfm_seg_find(frame_off, nutt, q);
+    const int row0 = frame_off[u];
+    Tlen = frame_off[u + 1] - row0;
+    q -= row0;
+    qkv += (long long)row0 * ldqkv;
+    out += (long long)row0 * ldo;
+  }
   const float inv_keep = (p_drop > 0.f) ? 1.0f / (1.0f - p_drop) : 1.0f;
   const uint32_t drop_rowh = attn_row_hash(seed, ((unsigned long long)b * nheads + h) * Tlen + q);
   const uint32_t drop_thr = attn_keep_threshold(p_drop);
@@ -860,6 +888,46 @@ extern "C" int sfm_attention_fwd_ex(const void* qkv, void* out, int B, int T, in
                                     float scale, int dtype, int out_dtype, int variant, void* stream) {
   return attention_fwd_impl(qkv, out, nullptr, B, T, H, hd, ldqkv, ldo, koff, voff, qkv_batch_stride, o_batch_stride,
                             scale, 0.f, 0u, dtype, out_dtype, variant, stream);
+}
+
+// Packed (variable-length) form of sfm_attention_fwd_ex: qkv [sum_T, ldqkv] / out [sum_T, ldo] hold B utterances back to back,
+// utterance u = rows [frame_off[u], frame_off[u + 1]) (int32[B + 1] on the device, frame_off[B] = sum_T, no length above max_T),
+// and attends to its own rows only.  head_dim 64 runs the 4-wave MFMA kernel, one workgroup per entry of `items`
+// (int32[n_items][4] = utterance, head, 128-row query tile, 0: every tile of every (utterance, head) exactly once, in any
+// order); any other head_dim <= 256 the one-wave-per-row kernel (items unused, operands' format only).
+extern "C" int sfm_attention_fwd_varlen(const void* qkv, void* out, const int* frame_off, const int* items, int n_items, int B,
+                                        int max_T, int sum_T, int H, int hd, int ldqkv, int ldo, int koff, int voff, float scale,
+                                        int dtype, int out_dtype, void* stream) {
+  if (!qkv || !out || !frame_off) return SFM_ERR_ARG;
+  if (B <= 0 || max_T <= 0 || sum_T < max_T || H <= 0 || hd <= 0 || hd > 256) return SFM_ERR_SHAPE;
+  if (ldqkv < H * hd || ldo < H * hd) return SFM_ERR_SHAPE;
+  if ((dtype != SFM_DT_BF16 && dtype != SFM_DT_F16) || (out_dtype != SFM_DT_BF16 && out_dtype != SFM_DT_F16)) return SFM_ERR_ARG;
+  const int out_other = (out_dtype != dtype) ? 1 : 0;
+  hipStream_t st = (hipStream_t)stream;
+  if (hd == 64 && (ldqkv % 8) == 0 && (ldo % 8) == 0 && (koff % 8) == 0 && (voff % 8) == 0) {
+    if (!items) return SFM_ERR_ARG;
+    // every (utterance, head) has between 1 and ceil(max_T / 128) tiles
+    if (n_items < B * H || (long long)n_items > (long long)B * H * ((max_T + 127) / 128)) return SFM_ERR_SHAPE;
+    const float sl2 = (scale > 0.f) ? scale * 1.44269504088896340736f : 1.0f;
+    dim3 grid(n_items), block(256);
+    if (dtype == SFM_DT_F16)
+      SFM_LAUNCH((attn_fwd_hd64_kernel<F16, false, true>), grid, block, 0, st, (const u16*)qkv, (u16*)out, 0, ldqkv, ldo, koff, voff,
+                 0LL, 0LL, sl2, 1, H, (float*)nullptr, 0.f, 0u, out_other, frame_off, items);
+    else
+      SFM_LAUNCH((attn_fwd_hd64_kernel<BF16, false, true>), grid, block, 0, st, (const u16*)qkv, (u16*)out, 0, ldqkv, ldo, koff, voff,
+                 0LL, 0LL, sl2, 1, H, (float*)nullptr, 0.f, 0u, out_other, frame_off, items);
+    return SFM_OK;
+  }
+  if (out_other) return SFM_ERR_SHAPE;                    // the small-shape kernel writes the operands' format only
+  dim3 grid((sum_T + 3) / 4, H, 1), block(256);
+  if (scale <= 0.f) scale = 0.69314718055994530942f;        // pre-scaled Q carries log2(e): exp(x ln2) = 2^x
+  if (dtype == SFM_DT_F16)
+    SFM_LAUNCH((attn_fwd_generic_kernel<F16, true>), grid, block, 0, st, (const u16*)qkv, (u16*)out, sum_T, hd, ldqkv, ldo, koff,
+               voff, 0LL, 0LL, scale, (float*)nullptr, 0.f, 0u, frame_off, B);
+  else
+    SFM_LAUNCH((attn_fwd_generic_kernel<BF16, true>), grid, block, 0, st, (const u16*)qkv, (u16*)out, sum_T, hd, ldqkv, ldo, koff,
+               voff, 0LL, 0LL, scale, (float*)nullptr, 0.f, 0u, frame_off, B);
+  return SFM_OK;
 }
 
 // training-mode forward: also writes lse [B,H,T] (log2 domain) and applies attention dropout

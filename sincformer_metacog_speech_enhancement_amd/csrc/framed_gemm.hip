@@ -21,6 +21,8 @@ struct FramedParams {
   long long sig_batch_stride, o_batch_stride, ldm, ldn;
   int B, M, Ls, hop, padl, K, Kpad, N, Npad, nsplit;
   int mode, out_f32, gn_group;
+  const int* samp_off;     // packed form only: int32[B + 1] first sample / first output row of each utterance
+  const int* frame_off;
 };
 
 #define FBM 128
@@ -28,15 +30,36 @@ struct FramedParams {
 #define FKC 32
 #define FAS 33
 
-template <class T>
+// VARLEN: the packed form.  sig is the concatenation of B signals, the M = sum(T_i) output rows are the concatenation of
+// their frames; a row tile covers 128 packed rows whatever utterances they belong to, and each row looks its utterance up
+// (first sample, length, frame index: a table in LDS filled by a binary search per row), so the edge handling is the
+// utterance's own.  A row's result depends on that row's samples only, not on the tile it falls into.
+template <class T, bool VARLEN>
 __global__ __launch_bounds__(256) void framed_gemm_kernel(FramedParams p) {
   __shared__ float As[FBM * FAS];
   __shared__ float Bs[FKC * FBN];
+  __shared__ int rowtab[VARLEN ? 3 * FBM : 1];             // [first sample | length | frame index] of the tile's rows
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int n0 = blockIdx.x * FBN;
   const int m0 = blockIdx.y * FBM;
   const int b = blockIdx.z;
   const float* sg = p.sig + (long long)b * p.sig_batch_stride;
+  if (VARLEN) {
+    if (tid < FBM) {
+      const int m = m0 + tid;
+      int s0 = 0, len = 0, t = 0;
+      if (m < p.M) {
+        const int u = sfm_seg_find(p.frame_off, p.B, m);
+        s0 = p.samp_off[u];
+        len = p.samp_off[u + 1] - s0;
+        t = m - p.frame_off[u];
+      }
+      rowtab[tid] = s0;
+      rowtab[FBM + tid] = len;
+      rowtab[2 * FBM + tid] = t;
+    }
+    __syncthreads();
+  }
 
   f32x16 acc[2];
 #pragma unroll
@@ -55,7 +78,17 @@ __global__ __launch_bounds__(256) void framed_gemm_kernel(FramedParams p) {
       int m = m0 + row;
       int k = kc * FKC + kk;
       float v = 0.f;
-      if (m < p.M && k < p.K) {
+      if (VARLEN) {
+        if (m < p.M && k < p.K) {
+          const int len = rowtab[FBM + row];
+          long long s = (long long)rowtab[2 * FBM + row] * p.hop + k - p.padl;
+          if (p.mode == 1) {
+            if (s < 0) s = -s;
+            if (s >= len) s = 2LL * (len - 1) - s;
+          }
+          if (s >= 0 && s < len) v = p.sig[rowtab[row] + s];
+        }
+      } else if (m < p.M && k < p.K) {
         long long s = (long long)m * p.hop + k - p.padl;
         if (p.mode == 1) {
           if (s < 0) s = -s;
@@ -151,10 +184,35 @@ extern "C" int sfm_framed_gemm_f32(const float* sig, const float* Wt, const floa
   p.sig_batch_stride = sig_batch_stride; p.o_batch_stride = o_batch_stride; p.ldm = ldm; p.ldn = ldn;
   p.B = B; p.M = M; p.Ls = Ls; p.hop = hop; p.padl = padl; p.K = K; p.Kpad = Kpad; p.N = N; p.Npad = Npad;
   p.nsplit = nsplit; p.mode = mode; p.out_f32 = out_f32; p.gn_group = gn_group;
+  p.samp_off = nullptr; p.frame_off = nullptr;
   dim3 grid((N + FBN - 1) / FBN, (M + FBM - 1) / FBM, B), block(256);
-  if (dtype == SFM_DT_F16) SFM_LAUNCH((framed_gemm_kernel<F16>), grid, block, 0, (hipStream_t)stream, p);
-  else SFM_LAUNCH((framed_gemm_kernel<BF16>), grid, block, 0, (hipStream_t)stream, p);
+  if (dtype == SFM_DT_F16) SFM_LAUNCH((framed_gemm_kernel<F16, false>), grid, block, 0, (hipStream_t)stream, p);
+  else SFM_LAUNCH((framed_gemm_kernel<BF16, false>), grid, block, 0, (hipStream_t)stream, p);
   SFM_CHECK_LAUNCH();
+  return SFM_OK;
+}
+
+// Packed form: sig = B signals back to back (signal i = samples [samp_off[i], samp_off[i + 1])), out rows = their frames back
+// to back (utterance i = rows [frame_off[i], frame_off[i + 1]), row stride ldm, column stride ldn); sum_T = frame_off[B].  Frame
+// t of utterance i reads its samples t * hop + k - padl, zero (mode 0) or reflected at its own first / last sample (mode 1:
+// every signal must be longer than padl, which the host checks - functional.packed_segments).  No bias, no GroupNorm partials.
+extern "C" int sfm_framed_gemm_f32_varlen(const float* sig, const float* Wt, void* out, void* out2, const int* samp_off,
+                                          const int* frame_off, int B, int sum_T, int hop, int padl, int K, int Kpad, int N,
+                                          int Npad, int nsplit, long long ldm, long long ldn, int mode, int out_f32, int dtype,
+                                          void* stream) {
+  if (!sig || !Wt || !out || !samp_off || !frame_off) return SFM_ERR_ARG;
+  if (B <= 0 || sum_T <= 0 || N <= 0 || K <= 0 || hop <= 0) return SFM_ERR_SHAPE;
+  if (Kpad % FKC != 0 || Npad % FBN != 0 || K > Kpad || N > Npad) return SFM_ERR_SHAPE;
+  if (dtype != SFM_DT_BF16 && dtype != SFM_DT_F16) return SFM_ERR_ARG;
+  FramedParams p;
+  p.sig = sig; p.Wt = Wt; p.bias = nullptr; p.out = out; p.out2 = out2; p.gn_partial = nullptr;
+  p.sig_batch_stride = 0; p.o_batch_stride = 0; p.ldm = ldm; p.ldn = ldn;
+  p.B = B; p.M = sum_T; p.Ls = 0; p.hop = hop; p.padl = padl; p.K = K; p.Kpad = Kpad; p.N = N; p.Npad = Npad;
+  p.nsplit = nsplit; p.mode = mode; p.out_f32 = out_f32; p.gn_group = 0;
+  p.samp_off = samp_off; p.frame_off = frame_off;
+  dim3 grid((N + FBN - 1) / FBN, (sum_T + FBM - 1) / FBM, 1), block(256);
+  if (dtype == SFM_DT_F16) SFM_LAUNCH((framed_gemm_kernel<F16, true>), grid, block, 0, (hipStream_t)stream, p);
+  else SFM_LAUNCH((framed_gemm_kernel<BF16, true>), grid, block, 0, (hipStream_t)stream, p);
   return SFM_OK;
 }
 
@@ -182,15 +240,36 @@ struct Split16Params {
   float* out2;
   long long sig_batch_stride, o_batch_stride, ldm;
   int B, M, Ls, hop, padl, K, Kpad, N, Npad, nsplit, col2_off, mode;
+  const int* samp_off;     // packed form only, as in FramedParams
+  const int* frame_off;
 };
 
+// VARLEN: the packed form, as in framed_gemm_kernel (per-row utterance table in LDS)
+template <bool VARLEN>
 __global__ __launch_bounds__(256, 2) void framed_gemm_split16_kernel(Split16Params p) {
   __shared__ __attribute__((aligned(16))) u16 Ah[SBM * SSTR], Al[SBM * SSTR];
   __shared__ __attribute__((aligned(16))) u16 Bh[SBN * SSTR], Bl[SBN * SSTR];
+  __shared__ int rowtab[VARLEN ? 3 * SBM : 1];             // [first sample | length | frame index] of the tile's rows
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int hl = lane >> 5, l31 = lane & 31;
   const int n0 = blockIdx.x * SBN, m0 = blockIdx.y * SBM, b = blockIdx.z;
   const float* sg = p.sig + (long long)b * p.sig_batch_stride;
+  if (VARLEN) {
+    if (tid < SBM) {
+      const int m = m0 + tid;
+      int s0 = 0, len = 0, t = 0;
+      if (m < p.M) {
+        const int u = sfm_seg_find(p.frame_off, p.B, m);
+        s0 = p.samp_off[u];
+        len = p.samp_off[u + 1] - s0;
+        t = m - p.frame_off[u];
+      }
+      rowtab[tid] = s0;
+      rowtab[SBM + tid] = len;
+      rowtab[2 * SBM + tid] = t;
+    }
+    __syncthreads();
+  }
 
   f32x16 acc[8];
 #pragma unroll
@@ -209,6 +288,14 @@ __global__ __launch_bounds__(256, 2) void framed_gemm_split16_kernel(Split16Para
     }
     return (s >= 0 && s < p.Ls) ? sg[s] : 0.f;
   };
+  auto fetch_row = [&](int row, long long s) -> float {       // packed form: sample s of the utterance of tile row `row`
+    const int len = rowtab[SBM + row];
+    if (p.mode == 1) {
+      if (s < 0) s = -s;
+      if (s >= len) s = 2LL * (len - 1) - s;
+    }
+    return (s >= 0 && s < len) ? p.sig[rowtab[row] + s] : 0.f;
+  };
   auto load_chunk = [&](int kc) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -216,7 +303,13 @@ __global__ __launch_bounds__(256, 2) void framed_gemm_split16_kernel(Split16Para
       const int row = idx >> 4, kp = idx & 15;
       const int m = m0 + row, k = kc * SKC + 2 * kp;
       float v0 = 0.f, v1 = 0.f;
-      if (m < p.M) {
+      if (VARLEN) {
+        if (m < p.M) {
+          const long long s = (long long)rowtab[2 * SBM + row] * p.hop + k - p.padl;
+          if (k < p.K) v0 = fetch_row(row, s);
+          if (k + 1 < p.K) v1 = fetch_row(row, s + 1);
+        }
+      } else if (m < p.M) {
         const long long s = (long long)m * p.hop + k - p.padl;
         if (k < p.K) v0 = fetch(s);
         if (k + 1 < p.K) v1 = fetch(s + 1);
@@ -303,7 +396,27 @@ extern "C" int sfm_framed_gemm_split16(const float* sig, const void* Whi, const 
   p.sig_batch_stride = sig_batch_stride; p.o_batch_stride = o_batch_stride; p.ldm = ldm;
   p.B = B; p.M = M; p.Ls = Ls; p.hop = hop; p.padl = padl; p.K = K; p.Kpad = Kpad; p.N = N; p.Npad = Npad;
   p.nsplit = nsplit; p.col2_off = col2_off; p.mode = mode;
+  p.samp_off = nullptr; p.frame_off = nullptr;
   dim3 grid((N + SBN - 1) / SBN, (M + SBM - 1) / SBM, B), block(256);
-  SFM_LAUNCH(framed_gemm_split16_kernel, grid, block, 0, (hipStream_t)stream, p);
+  SFM_LAUNCH(framed_gemm_split16_kernel<false>, grid, block, 0, (hipStream_t)stream, p);
+  return SFM_OK;
+}
+
+// Packed form of sfm_framed_gemm_split16: operands and layout as sfm_framed_gemm_f32_varlen, fp32 result.
+extern "C" int sfm_framed_gemm_split16_varlen(const float* sig, const void* Whi, const void* Wlo, float* out, float* out2,
+                                              const int* samp_off, const int* frame_off, int B, int sum_T, int hop, int padl,
+                                              int K, int Kpad, int N, int Npad, int nsplit, int col2_off, long long ldm,
+                                              int mode, void* stream) {
+  if (!sig || !Whi || !Wlo || !out || !samp_off || !frame_off) return SFM_ERR_ARG;
+  if (B <= 0 || sum_T <= 0 || N <= 0 || K <= 0 || hop <= 0) return SFM_ERR_SHAPE;
+  if (Kpad % SKC != 0 || Npad % SBN != 0 || K > Kpad || N > Npad) return SFM_ERR_SHAPE;
+  Split16Params p;
+  p.sig = sig; p.Whi = (const u16*)Whi; p.Wlo = (const u16*)Wlo; p.out = out; p.out2 = out2;
+  p.sig_batch_stride = 0; p.o_batch_stride = 0; p.ldm = ldm;
+  p.B = B; p.M = sum_T; p.Ls = 0; p.hop = hop; p.padl = padl; p.K = K; p.Kpad = Kpad; p.N = N; p.Npad = Npad;
+  p.nsplit = nsplit; p.col2_off = col2_off; p.mode = mode;
+  p.samp_off = samp_off; p.frame_off = frame_off;
+  dim3 grid((N + SBN - 1) / SBN, (sum_T + SBM - 1) / SBM, 1), block(256);
+  SFM_LAUNCH(framed_gemm_split16_kernel<true>, grid, block, 0, (hipStream_t)stream, p);
   return SFM_OK;
 }

@@ -397,16 +397,28 @@ __global__ __launch_bounds__(256) void dwconv_bn_swish_kernel(const u16* __restr
 // Register-weight variant for the shapes of the path (KS = 31 or 7, C/2 | 256): the 2*KS taps of a
 // thread's channel pair live in registers, LDS holds only the 16-bit input tile (3 workgroups per CU),
 // weights arrive pre-transposed [KS][C] with BatchNorm folded into per-channel scale/shift.
-template <class T, int KS>
+// VARLEN: the packed form.  x / out hold the rows of all utterances back to back (utterance u = rows [frame_off[u],
+// frame_off[u + 1])); workgroup i takes entry i of the tile table (utterance, 64-frame tile of that utterance) the host built
+// from the lengths (ops.dwconv_tiles), so tiles start at the utterance's first frame and the zero edge is the utterance's own.
+template <class T, int KS, bool VARLEN = false>
 __global__ __launch_bounds__(256) void dwconv_reg_kernel(const u16* __restrict__ x, const float* __restrict__ wT,
                                                          const float* __restrict__ sc, const float* __restrict__ sh,
-                                                         void* __restrict__ out, int Tlen, int C, int act, int out_f32) {
+                                                         void* __restrict__ out, int Tlen, int C, int act, int out_f32,
+                                                         const int* __restrict__ frame_off = nullptr,
+                                                         const int* __restrict__ tiles = nullptr) {
   extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];
   u16* xs = reinterpret_cast<u16*>(dsm);                                 // [DW_TT + KS - 1][C]
   constexpr int padl = (KS - 1) / 2, rows = DW_TT + KS - 1;
   const int tid = threadIdx.x;
-  const int t0 = blockIdx.x * DW_TT, b = blockIdx.y;
-  const u16* xb = x + (long long)b * Tlen * C;
+  int t0 = blockIdx.x * DW_TT;
+  long long row0 = (long long)blockIdx.y * Tlen;                         // first row of the utterance
+  if (VARLEN) {
+    const int u = tiles[2 * blockIdx.x];
+    t0 = tiles[2 * blockIdx.x + 1] * DW_TT;
+    row0 = frame_off[u];
+    Tlen = frame_off[u + 1] - (int)row0;
+  }
+  const u16* xb = x + row0 * C;
   const int cpr = C >> 3;
   for (int e = tid; e < rows * cpr; e += 256) {
     const int r = e / cpr, c8 = (e - r * cpr) * 8;
@@ -427,7 +439,7 @@ __global__ __launch_bounds__(256) void dwconv_reg_kernel(const u16* __restrict__
   }
   const float s0 = sc[c], s1 = sc[c + 1], h0 = sh[c], h1 = sh[c + 1];
   __syncthreads();
-  const long long obase = (long long)b * Tlen * C;
+  const long long obase = row0 * C;
   const int per = DW_TT / ngrp;                                          // frames per thread (multiple of 4)
   for (int tl = grp * per; tl < (grp + 1) * per; tl += 4) {
     float a0[4] = {0.f, 0.f, 0.f, 0.f}, a1[4] = {0.f, 0.f, 0.f, 0.f};
@@ -468,18 +480,27 @@ __global__ __launch_bounds__(256) void dwconv_reg_kernel(const u16* __restrict__
 // even outputs of a step, odd pairs for the odd ones): per 4 outputs x 2 channels 128 dot products + 68 permutes against 248
 // multiply-adds + 68 converts.  New rounding: the taps, once, to fp16 (the operand format of every MFMA of the path).
 typedef _Float16 dw_h2 __attribute__((ext_vector_type(2)));
-template <int KS>
+template <int KS, bool VARLEN = false>                                   // VARLEN: the packed form, as in dwconv_reg_kernel
 __global__ __launch_bounds__(256) void dwconv_dot_kernel(const u16* __restrict__ x, const float* __restrict__ wT,
                                                          const float* __restrict__ sc, const float* __restrict__ sh,
-                                                         void* __restrict__ out, int Tlen, int C, int act, int out_f32) {
+                                                         void* __restrict__ out, int Tlen, int C, int act, int out_f32,
+                                                         const int* __restrict__ frame_off = nullptr,
+                                                         const int* __restrict__ tiles = nullptr) {
   extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];
   u16* xs = reinterpret_cast<u16*>(dsm);                                 // [DW_TT + KS - 1][C]
   constexpr int padl = (KS - 1) / 2, rows = DW_TT + KS - 1;
   constexpr int NP = (KS + 1) / 2;                                       // tap pairs (the last one = (w[KS-1], 0))
   constexpr int NR = KS + 3;                                             // staged rows a step of 4 outputs reads
   const int tid = threadIdx.x;
-  const int t0 = blockIdx.x * DW_TT, b = blockIdx.y;
-  const u16* xb = x + (long long)b * Tlen * C;
+  int t0 = blockIdx.x * DW_TT;
+  long long row0 = (long long)blockIdx.y * Tlen;                         // first row of the utterance
+  if (VARLEN) {
+    const int u = tiles[2 * blockIdx.x];
+    t0 = tiles[2 * blockIdx.x + 1] * DW_TT;
+    row0 = frame_off[u];
+    Tlen = frame_off[u + 1] - (int)row0;
+  }
+  const u16* xb = x + row0 * C;
   const int cpr = C >> 3;
   // staging in batches of 12 chunks per thread with ALL of a batch's loads issued before its first LDS write (the rolled
   // load -> write loop of the kernel above pays one memory round trip per 16 bytes: 12 in a row at C = 256, and that latency
@@ -515,7 +536,7 @@ __global__ __launch_bounds__(256) void dwconv_dot_kernel(const u16* __restrict__
   }
   const float s0 = sc[c], s1 = sc[c + 1], h0 = sh[c], h1 = sh[c + 1];
   __syncthreads();
-  const long long obase = (long long)b * Tlen * C;
+  const long long obase = row0 * C;
   const int per = DW_TT / ngrp;                                          // frames per thread (multiple of 4)
   for (int tl = grp * per; tl < (grp + 1) * per; tl += 4) {
     uint32_t d[NR + 1];                                                  // row k of the step: (x[k][c], x[k][c + 1])
@@ -552,53 +573,67 @@ __global__ __launch_bounds__(256) void dwconv_dot_kernel(const u16* __restrict__
   }
 }
 
-template <int KS>
+// (the launchers' VARLEN form: B = 0 rows of the grid's second dimension are replaced by the n_tiles entries of `tiles`)
+template <int KS, bool VARLEN = false>
 static int launch_dwconv_dot(const void* x, const float* wT, const float* sc, const float* sh, void* out, int B, int Tn,
-                             int C, int act, int out_f32, hipStream_t st) {
+                             int C, int act, int out_f32, hipStream_t st, const int* frame_off = nullptr,
+                             const int* tiles = nullptr, int n_tiles = 0) {
   const int lds = (DW_TT + KS - 1) * C * 2;
   static bool attr_dev[64] = {false};
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return SFM_ERR_LAUNCH;
   if (!attr_dev[dev]) {
-    if (hipFuncSetAttribute((const void*)dwconv_dot_kernel<KS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
+    if (hipFuncSetAttribute((const void*)dwconv_dot_kernel<KS, VARLEN>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
       return SFM_ERR_LAUNCH;
     attr_dev[dev] = true;
   }
-  SFM_LAUNCH((dwconv_dot_kernel<KS>), dim3((Tn + DW_TT - 1) / DW_TT, B), dim3(256), lds, st, (const u16*)x, wT, sc, sh, out, Tn,
-             C, act, out_f32);
+  const dim3 grid = VARLEN ? dim3(n_tiles, 1) : dim3((Tn + DW_TT - 1) / DW_TT, B);
+  SFM_LAUNCH((dwconv_dot_kernel<KS, VARLEN>), grid, dim3(256), lds, st, (const u16*)x, wT, sc, sh, out, Tn, C, act, out_f32,
+             frame_off, tiles);
   return SFM_OK;
 }
 
-template <class T, int KS>
+template <class T, int KS, bool VARLEN = false>
 static int launch_dwconv_reg(const void* x, const float* wT, const float* sc, const float* sh, void* out, int B, int Tn,
-                             int C, int act, int out_f32, hipStream_t st) {
+                             int C, int act, int out_f32, hipStream_t st, const int* frame_off = nullptr,
+                             const int* tiles = nullptr, int n_tiles = 0) {
   const int lds = (DW_TT + KS - 1) * C * 2;
   static bool attr_dev[64] = {false};                        // hipFuncSetAttribute is per device
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return SFM_ERR_LAUNCH;
   bool& attr = attr_dev[dev];
   if (!attr) {
-    if (hipFuncSetAttribute((const void*)dwconv_reg_kernel<T, KS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
+    if (hipFuncSetAttribute((const void*)dwconv_reg_kernel<T, KS, VARLEN>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
       return SFM_ERR_LAUNCH;
     attr = true;
   }
-  SFM_LAUNCH((dwconv_reg_kernel<T, KS>), dim3((Tn + DW_TT - 1) / DW_TT, B), dim3(256), lds, st, (const u16*)x, wT, sc, sh,
-             out, Tn, C, act, out_f32);
+  const dim3 grid = VARLEN ? dim3(n_tiles, 1) : dim3((Tn + DW_TT - 1) / DW_TT, B);
+  SFM_LAUNCH((dwconv_reg_kernel<T, KS, VARLEN>), grid, dim3(256), lds, st, (const u16*)x, wT, sc, sh, out, Tn, C, act, out_f32,
+             frame_off, tiles);
   return SFM_OK;
 }
 
 // Any channel count and any odd KS (the shapes the register-resident kernels do not take, e.g. the training-mode
 // ConvolutionModule at C 192 / 384): one output element per thread, taps and scale / shift read from global memory.
-template <class T>
+// VARLEN: the packed form; each element finds its utterance by a binary search in frame_off [nutt + 1].
+template <class T, bool VARLEN = false>
 __global__ __launch_bounds__(256) void dwconv_generic_kernel(const u16* __restrict__ x, const float* __restrict__ wT,
                                                              const float* __restrict__ sc, const float* __restrict__ sh,
                                                              void* __restrict__ out, int Tlen, int C, int KS, long long total,
-                                                             int act, int out_f32) {
+                                                             int act, int out_f32, const int* __restrict__ frame_off = nullptr,
+                                                             int nutt = 0) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
   const int c = (int)(i % C);
-  const long long bt = i / C;                                            // b * Tlen + t
-  const int t = (int)(bt % Tlen);
+  const long long bt = i / C;                                            // b * Tlen + t (packed form: the packed row)
+  int t;
+  if (VARLEN) {
+    const int u = sfm_seg_find(frame_off, nutt, (int)bt);
+    t = (int)bt - frame_off[u];
+    Tlen = frame_off[u + 1] - frame_off[u];
+  } else {
+    t = (int)(bt % Tlen);
+  }
   const u16* xc = x + (bt - t) * C + c;                                  // (b, 0, c)
   const int padl = (KS - 1) / 2;
   float acc = 0.f;
@@ -641,6 +676,42 @@ extern "C" int sfm_dwconv_folded(const void* x, const float* wT, const float* sc
                                            : launch_dwconv_reg<BF16, 31>(x, wT, sc, sh, out, B, T, C, act, out_f32, st);
   return dtype == SFM_DT_F16 ? launch_dwconv_reg<F16, 7>(x, wT, sc, sh, out, B, T, C, act, out_f32, st)
                              : launch_dwconv_reg<BF16, 7>(x, wT, sc, sh, out, B, T, C, act, out_f32, st);
+}
+
+// Packed (variable-length) form of sfm_dwconv_folded: x / out [sum_T, C] hold B utterances back to back, utterance u = rows
+// [frame_off[u], frame_off[u + 1]) (int32[B + 1] on the device), each convolved with a zero edge at its own first and last frame.
+// The register-resident kernels take one workgroup per entry of `tiles` (int32[n_tiles][2] = utterance, 64-frame tile of that
+// utterance: every tile of every utterance once), the generic kernel does not read the table.
+extern "C" int sfm_dwconv_folded_varlen(const void* x, const float* wT, const float* sc, const float* sh, void* out,
+                                        const int* frame_off, const int* tiles, int n_tiles, int B, int max_T, int sum_T, int C,
+                                        int KS, int act, int out_f32, int dtype, void* stream) {
+  if (!x || !wT || !sc || !sh || !out || !frame_off) return SFM_ERR_ARG;
+  if (B <= 0 || max_T <= 0 || sum_T < max_T || C <= 0 || KS < 1 || (KS & 1) == 0) return SFM_ERR_SHAPE;
+  if (dtype != SFM_DT_BF16 && dtype != SFM_DT_F16) return SFM_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const bool reg = (KS == 7 || KS == 31) && C % 8 == 0 && C <= 512 && (256 % (C / 2)) == 0 && (DW_TT / (256 / (C / 2))) % 4 == 0;
+  if (!reg) {
+    const long long total = (long long)sum_T * C;
+    const long long nb = (total + 255) / 256;
+    if (nb > 0x7fffffffLL) return SFM_ERR_SHAPE;
+    if (dtype == SFM_DT_F16)
+      SFM_LAUNCH((dwconv_generic_kernel<F16, true>), dim3((unsigned)nb), dim3(256), 0, st, (const u16*)x, wT, sc, sh, out, 0, C, KS,
+                 total, act, out_f32, frame_off, B);
+    else
+      SFM_LAUNCH((dwconv_generic_kernel<BF16, true>), dim3((unsigned)nb), dim3(256), 0, st, (const u16*)x, wT, sc, sh, out, 0, C, KS,
+                 total, act, out_f32, frame_off, B);
+    return SFM_OK;
+  }
+  if (!tiles) return SFM_ERR_ARG;
+  if (n_tiles < B || (long long)n_tiles > (long long)B * ((max_T + DW_TT - 1) / DW_TT)) return SFM_ERR_SHAPE;
+  static const int dot_on = getenv("SFM_DWCONV_DOT") ? atoi(getenv("SFM_DWCONV_DOT")) : 1;      // as sfm_dwconv_folded
+  if (KS == 31 && dtype == SFM_DT_F16 && dot_on)
+    return launch_dwconv_dot<31, true>(x, wT, sc, sh, out, 0, 0, C, act, out_f32, st, frame_off, tiles, n_tiles);
+  if (KS == 31)
+    return dtype == SFM_DT_F16 ? launch_dwconv_reg<F16, 31, true>(x, wT, sc, sh, out, 0, 0, C, act, out_f32, st, frame_off, tiles, n_tiles)
+                               : launch_dwconv_reg<BF16, 31, true>(x, wT, sc, sh, out, 0, 0, C, act, out_f32, st, frame_off, tiles, n_tiles);
+  return dtype == SFM_DT_F16 ? launch_dwconv_reg<F16, 7, true>(x, wT, sc, sh, out, 0, 0, C, act, out_f32, st, frame_off, tiles, n_tiles)
+                             : launch_dwconv_reg<BF16, 7, true>(x, wT, sc, sh, out, 0, 0, C, act, out_f32, st, frame_off, tiles, n_tiles);
 }
 
 extern "C" int sfm_dwconv_bn_swish(const void* x, const float* wdw, const float* bdw, const float* bnw,
@@ -1214,6 +1285,42 @@ __global__ __launch_bounds__(256) void istft_ola_kernel(const float* __restrict_
     }
   }
   out[(long long)b * L + s] = (env > 1e-11f) ? acc / env : 0.f;
+}
+
+// Packed form: frames [sum_T, ld_frames] and out [sum_L] hold B utterances back to back (frames of utterance u = rows
+// [frame_off[u], frame_off[u + 1]), its samples = out[samp_off[u] .. samp_off[u + 1])); each sample finds its utterance by a
+// binary search and sums that utterance's frames only, in the dense kernel's order.
+__global__ __launch_bounds__(256) void istft_ola_varlen_kernel(const float* __restrict__ frames, const float* __restrict__ win2,
+                                                               float* __restrict__ out, const int* __restrict__ frame_off,
+                                                               const int* __restrict__ samp_off, int nutt, int sum_L, int n_fft,
+                                                               int hop, int win, long long ld_frames) {
+  const int g = blockIdx.x * 256 + threadIdx.x;
+  if (g >= sum_L) return;
+  const int u = sfm_seg_find(samp_off, nutt, g);
+  const int s = g - samp_off[u];
+  const int row0 = frame_off[u], Tn = frame_off[u + 1] - row0;
+  const int p = s + n_fft / 2 - (n_fft - win) / 2;     // position relative to window support start
+  int t = p / hop;
+  if (t > Tn - 1) t = Tn - 1;
+  float acc = 0.f, env = 0.f;
+  for (; t >= 0; --t) {
+    int n = p - t * hop;
+    if (n >= win) break;
+    if (n >= 0) {
+      acc += frames[((long long)row0 + t) * ld_frames + n];
+      env += win2[n];
+    }
+  }
+  out[g] = (env > 1e-11f) ? acc / env : 0.f;
+}
+
+extern "C" int sfm_istft_ola_varlen(const float* frames, const float* win2, float* out, const int* frame_off, const int* samp_off,
+                                    int B, int sum_L, int n_fft, int hop, int win, long long ld_frames, void* stream) {
+  if (!frames || !win2 || !out || !frame_off || !samp_off) return SFM_ERR_ARG;
+  if (B <= 0 || sum_L <= 0 || hop <= 0 || win <= 0 || win > n_fft || ld_frames < win) return SFM_ERR_SHAPE;
+  SFM_LAUNCH(istft_ola_varlen_kernel, dim3((sum_L + 255) / 256), dim3(256), 0, (hipStream_t)stream, frames, win2, out, frame_off,
+             samp_off, B, sum_L, n_fft, hop, win, ld_frames);
+  return SFM_OK;
 }
 
 extern "C" int sfm_istft_ola(const float* frames, const float* win2, float* out, int B, int T, int L, int n_fft, int hop,

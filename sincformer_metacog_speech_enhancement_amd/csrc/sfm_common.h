@@ -195,6 +195,18 @@ __device__ __forceinline__ float wave_sum16_transpose(const float (&v)[16], int 
   return a + c;
 }
 
+// Packed (variable-length) batches: utterance b owns rows [off[b], off[b + 1]) of a concatenated matrix, off = int32[n + 1]
+// ascending from 0, read on the device.  Returns the utterance of row r: the largest b < n with off[b] <= r.
+__device__ __forceinline__ int sfm_seg_find(const int* __restrict__ off, int n, int r) {
+  int lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (off[mid] <= r) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
 // hipGetLastError() is sticky on ROCm 7 (it reports the last *error* of any earlier runtime call
 // in this thread, e.g. a benign hipErrorNotReady from an event query made by the caller's
 // framework), so the state is cleared right before the launch and read right after it.

@@ -9,6 +9,7 @@ All functions take/return device tensors and only enqueue kernels on the
 current stream; there is no CPU code path.
 """
 import math
+import numpy as np
 import torch
 
 from . import ops
@@ -154,6 +155,117 @@ def istft(real, imag, length, n_fft=N_FFT, hop=HOP, win=WIN):
 
 
 # ---------------------------------------------------------------------------
+# Packed (variable-length) batches: utterances of different lengths back to back, no padding (DESIGN.md "Packed batches")
+# ---------------------------------------------------------------------------
+class PackedSegments:
+    """Host description of one packed pass: `frame_counts` T_i, `frame_offsets` [B + 1], `max_T`, `sum_T`, and - when built from
+    signal lengths - `lengths` L_i, `sample_offsets` [B + 1], `sum_L`; `start` / `stop`: the pass's slice of the caller's list.
+    Pure host data (numpy); tables(device, H) uploads the offsets and the kernels' work tables once per pass and caches them."""
+
+    def __init__(self, frame_counts, lengths=None, start=0):
+        self.frame_counts = np.asarray(frame_counts, dtype=np.int64).reshape(-1)
+        self.B = int(self.frame_counts.size)
+        if self.B == 0 or int(self.frame_counts.min()) < 1:
+            raise ValueError("a packed pass needs at least one utterance and at least one frame per utterance")
+        self.frame_offsets = np.concatenate([[0], np.cumsum(self.frame_counts)])
+        self.max_T, self.sum_T = int(self.frame_counts.max()), int(self.frame_offsets[-1])
+        self.sum_T2 = float((self.frame_counts.astype(np.float64) ** 2).sum())
+        self.lengths = None if lengths is None else np.asarray(lengths, dtype=np.int64).reshape(-1)
+        self.sample_offsets = None if lengths is None else np.concatenate([[0], np.cumsum(self.lengths)])
+        self.sum_L = None if lengths is None else int(self.sample_offsets[-1])
+        if max(self.sum_T, self.sum_L or 0) >= 2 ** 31:
+            raise ValueError("a packed pass is indexed with int32: %d rows / %s samples" % (self.sum_T, self.sum_L))
+        self.start, self.stop = start, start + self.B
+        self._tables = {}
+
+    def tables(self, device, H=None):
+        """device int32 tensors: frame_off [B + 1], samp_off [B + 1] (None without lengths), conv_tiles [n, 2] - one upload - and,
+        when H is given, attn_items [n, 4] for H heads (a second one, the first time that H is asked for)"""
+        t = self._tables.get(str(device))
+        if t is None:
+            parts = [self.frame_offsets.astype(np.int32), ops.dwconv_tiles(self.frame_counts).reshape(-1)]
+            if self.sample_offsets is not None:
+                parts.append(self.sample_offsets.astype(np.int32))
+            flat = torch.from_numpy(np.concatenate(parts)).to(device)
+            n0, n1 = parts[0].size, parts[1].size
+            t = self._tables[str(device)] = {"frame_off": flat[:n0], "conv_tiles": flat[n0:n0 + n1].view(-1, 2),
+                                             "samp_off": flat[n0 + n1:] if self.sample_offsets is not None else None}
+        if H is not None and ("attn_items", H) not in t:
+            t["attn_items", H] = torch.from_numpy(ops.attention_items(self.frame_counts, H)).to(device)
+        return t
+
+
+def packed_segments(lengths, n_fft=N_FFT, hop=HOP, max_frames=None):
+    """Signal lengths -> list of PackedSegments, one per pass (no GPU needed).  T_i = 1 + L_i // hop.  A length the dense stft()
+    refuses (L <= n_fft // 2: shorter than the reflect padding) raises, naming the signal's index.  max_frames: the list is cut
+    greedily, in the given order, into passes of at most that many frames; an utterance longer than max_frames is a pass of its
+    own.  Default: one pass."""
+    L = [int(x) for x in lengths]
+    for i, n in enumerate(L):
+        if n <= n_fft // 2:
+            raise ValueError("packed_segments: signal %d is shorter than the reflect padding (L=%d <= n_fft/2=%d)" % (i, n, n_fft // 2))
+    if max_frames is not None and max_frames < 1:
+        raise ValueError("packed_segments: max_frames must be positive")
+    T = [1 + n // hop for n in L]
+    passes, first, frames = [], 0, 0
+    for i, t in enumerate(T):
+        if max_frames is not None and i > first and frames + t > max_frames:
+            passes.append(PackedSegments(T[first:i], L[first:i], first))
+            first, frames = i, 0
+        frames += t
+    if len(L) > first:
+        passes.append(PackedSegments(T[first:], L[first:], first))
+    return passes
+
+
+def stft_packed(wave, seg, n_fft=N_FFT, hop=HOP, win=WIN, split16=False):
+    """wave [sum_L] fp32 (the signals of `seg` back to back) -> real, imag [sum_T, n_fft/2+1] fp32: the frames of every signal
+    with the reflect padding taken at its own ends.  split16: the split-bf16 form (stft_split16) instead of the exact fp32 one."""
+    wave = wave.contiguous()
+    if seg.sample_offsets is None or wave.numel() != seg.sum_L:
+        raise RuntimeError("stft_packed: %d samples, the segments describe %s" % (wave.numel(), seg.sum_L))
+    if int(seg.lengths.min()) <= n_fft // 2 or not np.array_equal(seg.frame_counts, 1 + seg.lengths // hop):
+        raise RuntimeError("stft_packed: the segments were not built for n_fft %d / hop %d" % (n_fft, hop))
+    F = n_fft // 2 + 1
+    c = _stft_consts(n_fft, win, wave.device)
+    tb = seg.tables(wave.device)
+    re = torch.empty(seg.sum_T, F, device=wave.device, dtype=torch.float32)
+    im = torch.empty(seg.sum_T, F, device=wave.device, dtype=torch.float32)
+    padl = n_fft // 2 - (n_fft - win) // 2
+    if not split16:
+        ops.framed_gemm_varlen(wave, c["fwd"], re, tb["samp_off"], tb["frame_off"], B=seg.B, sum_T=seg.sum_T, hop=hop, padl=padl,
+                               K=win, N=2 * F, ldm=F, mode=1, out2=im, nsplit=F)
+        return re, im
+    if "fwd16" not in c:
+        base = c["fwd"][:win, :2 * F]
+        c["fwd16"] = ops.pack_split16_matrix(torch.cat([base[:, :F], base[:, F + 1:2 * F - 1]], dim=1).contiguous())
+    ops.framed_gemm_split16_varlen(wave, c["fwd16"], re, tb["samp_off"], tb["frame_off"], B=seg.B, sum_T=seg.sum_T, hop=hop,
+                                   padl=padl, ldm=F, mode=1, out2=im, nsplit=F, col2_off=1)
+    im[..., 0] = 0.0
+    im[..., F - 1] = 0.0
+    return re, im
+
+
+def istft_packed(real, imag, seg, n_fft=N_FFT, hop=HOP, win=WIN):
+    """real, imag [sum_T, n_fft/2+1] -> waveform [sum_L]: every utterance overlap-added over its own frames, to its own length"""
+    real, imag = real.contiguous(), imag.contiguous()
+    M, F = real.shape
+    if seg.sample_offsets is None or M != seg.sum_T:
+        raise RuntimeError("istft_packed: %d rows, the segments describe %d (and need the signal lengths)" % (M, seg.sum_T))
+    c = _stft_consts(n_fft, win, real.device)
+    tb = seg.tables(real.device)
+    ld = ops.round_up(2 * F, 8)
+    spec = torch.empty(M, ld, device=real.device, dtype=torch.float32)
+    ops.pack_spec(real, imag, spec, M, F, ld, F)
+    frames = torch.empty(M, win, device=real.device, dtype=torch.float32)
+    ops.framed_gemm(spec, c["inv"], frames, B=1, M=M, Ls=M * ld, sig_batch_stride=0, hop=ld, padl=0, K=2 * F, N=win,
+                    o_batch_stride=0, ldm=win, ldn=1, mode=0)                  # row-wise: one irfft x window per frame
+    out = torch.empty(seg.sum_L, device=real.device, dtype=torch.float32)
+    ops.istft_ola_varlen(frames, c["win2"], out, tb["frame_off"], tb["samp_off"], seg.B, n_fft, hop, win, win)
+    return out
+
+
+# ---------------------------------------------------------------------------
 # Conformer (models/conformer.py)
 # ---------------------------------------------------------------------------
 FUSED_FFN = True      # False: LayerNorm + two gemm16 launches
@@ -234,8 +346,9 @@ def ffn_forward(x32, pk):
     return ops.linear16(u, pk["w2"], epi=ops.EPI_RESID, resid=x32, alpha=0.5)
 
 
-def mhsa_forward(x32, pk, B, T, H, h=None, index=None):
+def mhsa_forward(x32, pk, B, T, H, h=None, index=None, seg=None):
     """h: LN(x32) in 16-bit when the producer already normalised (fused into the preceding FFN's epilogue).
+    seg: a PackedSegments - x32 holds its utterances back to back ([sum_T, D]; B, T unused) and each attends to its own rows.
     The projections run in the caller's ("block") operand format, the Q | K | V buffer and the attention core in the
     "attn" stage's format: the in-projection's epilogue writes that format, the attention epilogue writes the block's."""
     D = x32.shape[1]
@@ -247,7 +360,15 @@ def mhsa_forward(x32, pk, B, T, H, h=None, index=None):
         qkv = ops.ln_linear16(x32, pk["ln_w"], pk["ln_b"], pk["win"], out_dtype=adt)
     else:
         qkv = ops.linear16(h, pk["win"], out_dtype=adt)
-    if adt is bdt:
+    if seg is not None:
+        tb = seg.tables(x32.device, H if D // H == 64 else None)
+        args = (qkv, tb["frame_off"], tb["attn_items", H] if D // H == 64 else None, seg.B, seg.max_T, seg.sum_T, H, D // H)
+        if adt is bdt:
+            o = ops.attention_varlen(*args, prescaled=True, sum_T2=seg.sum_T2)
+        else:
+            with ops.stage("attn", index):
+                o = ops.attention_varlen(*args, prescaled=True, out_dtype=bdt, sum_T2=seg.sum_T2)
+    elif adt is bdt:
         o = ops.attention(qkv, B, T, H, D // H, prescaled=True)
     else:
         with ops.stage("attn", index):
@@ -255,35 +376,52 @@ def mhsa_forward(x32, pk, B, T, H, h=None, index=None):
     return ops.linear16(o, pk["wout"], epi=ops.EPI_RESID, resid=x32, alpha=1.0)
 
 
-def convmod_forward(x32, pk, B, T):
+def _dw_folded_any(pk):
+    """BatchNorm(eval) + depthwise bias folded for ANY width / kernel size (pack_convmod folds the register-resident shapes only):
+    operands of the packed depthwise kernel, which has no un-folded form.  Cached in the pack."""
+    f = pk["dw_folded"] or pk.get("dw_folded_any")
+    if f is None:
+        bsc = pk["bn_w"] * torch.rsqrt(pk["bn_v"] + 1e-5)
+        bsh = pk["bn_b"] - pk["bn_m"] * bsc + pk["dw_b"] * bsc
+        f = pk["dw_folded_any"] = (pk["dw_w"].t().contiguous(), bsc.contiguous(), bsh.contiguous())
+    return f
+
+
+def convmod_forward(x32, pk, B, T, seg=None):
+    """seg: a PackedSegments - packed rows, the depthwise convolution sees a zero edge at each utterance's own ends"""
     D = x32.shape[1]
     g = ops.ln_linear16(x32, pk["ln_w"], pk["ln_b"], pk["pw1"], epi=ops.EPI_GLU)      # LayerNorm = the GEMM kernel's prologue
-    if pk["dw_folded"] is not None:
+    if seg is not None:
+        tb = seg.tables(x32.device)
+        wT, sc, sh = _dw_folded_any(pk)
+        d = ops.dwconv_folded_varlen(g, wT, sc, sh, tb["frame_off"], tb["conv_tiles"], seg.B, seg.max_T, seg.sum_T, D)
+    elif pk["dw_folded"] is not None:
         d = ops.dwconv_folded(g, pk["dw_folded"][0], pk["dw_folded"][1], pk["dw_folded"][2], B, T, D)
     else:
         d = ops.dwconv_bn_swish(g, pk["dw_w"], pk["dw_b"], pk["bn_w"], pk["bn_b"], pk["bn_m"], pk["bn_v"], B, T, D)
     return ops.linear16(d, pk["pw2"], epi=ops.EPI_RESID, resid=x32, alpha=1.0)
 
 
-def block_forward(x32, pk, B, T, H, want16=False):
-    """ConformerBlock.forward (eval) on the flattened [B*T, D] fp32 stream."""
+def block_forward(x32, pk, B, T, H, want16=False, seg=None):
+    """ConformerBlock.forward (eval) on the flattened [B*T, D] fp32 stream; seg: a PackedSegments - the stream is its
+    utterances back to back ([sum_T, D]; B, T unused), each treated as if it were alone."""
     with ops.stage("block", pk.get("index")):
-        return _block_forward(x32, pk, B, T, H, want16)
+        return _block_forward(x32, pk, B, T, H, want16, seg)
 
 
-def _block_forward(x32, pk, B, T, H, want16):
+def _block_forward(x32, pk, B, T, H, want16, seg=None):
     if _ffn_fusable(x32, pk["ff1"]) and x32.shape[1] == 256:
         # ff1 and mhsa.layer_norm in one launch; likewise ff2 and final_norm below (the sum ff2 produces is not kept)
         x, h = ffn_forward_ln(x32, pk["ff1"], pk["mhsa"]["ln_w"], pk["mhsa"]["ln_b"], False, True)
-        x = mhsa_forward(x, pk["mhsa"], B, T, H, h=h, index=pk.get("index"))
-        x = convmod_forward(x, pk["conv"], B, T)
+        x = mhsa_forward(x, pk["mhsa"], B, T, H, h=h, index=pk.get("index"), seg=seg)
+        x = convmod_forward(x, pk["conv"], B, T, seg=seg)
         if not want16 and _ffn_fusable(x, pk["ff2"]):
             return ffn_forward_ln(x, pk["ff2"], pk["fn_w"], pk["fn_b"], True, False)[1]
         x = ffn_forward(x, pk["ff2"])
     else:
         x = ffn_forward(x32, pk["ff1"])
-        x = mhsa_forward(x, pk["mhsa"], B, T, H, index=pk.get("index"))
-        x = convmod_forward(x, pk["conv"], B, T)
+        x = mhsa_forward(x, pk["mhsa"], B, T, H, index=pk.get("index"), seg=seg)
+        x = convmod_forward(x, pk["conv"], B, T, seg=seg)
         x = ffn_forward(x, pk["ff2"])
     out = torch.empty_like(x)
     out16 = torch.empty(x.shape, device=x.device, dtype=ops.compute_dtype()) if want16 else None

@@ -133,6 +133,14 @@ SIGNATURES = {
     "sfm_memory_fwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_f, c_vp],
     "sfm_memory_bwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_f, c_vp, c_vp],
     "sfm_memory_param_floats": [c_i, c_i, c_i],
+    # packed (variable-length) batches
+    "sfm_framed_gemm_f32_varlen": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_ll, c_ll,
+                                   c_i, c_i, c_i, c_vp],
+    "sfm_framed_gemm_split16_varlen": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i,
+                                       c_ll, c_i, c_vp],
+    "sfm_attention_fwd_varlen": [c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_vp],
+    "sfm_dwconv_folded_varlen": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_vp],
+    "sfm_istft_ola_varlen": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_ll, c_vp],
 }
 
 _lib = None

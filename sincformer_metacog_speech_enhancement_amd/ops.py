@@ -790,6 +790,123 @@ def istft_ola(frames, win2, out, B, T, Ln, n_fft, hop, win, ld_frames):
           *_cost_of("istft_ola", locals()))
 
 
+# ---------------------------------------------------------------------------
+# packed (variable-length) batches: B utterances back to back, no padding.  Rows of utterance u = [frame_off[u], frame_off[u + 1])
+# of every [sum_T, ...] matrix, its samples = [samp_off[u], samp_off[u + 1]) of the packed waveform; the offsets are int32 device
+# tensors (functional.PackedSegments uploads them with the two work tables below in one copy).
+# ---------------------------------------------------------------------------
+ATTN_QTILE = 128      # query rows of a workgroup of attn_fwd_hd64_kernel
+DWCONV_TILE = 64      # frames of a workgroup of the register-resident depthwise kernels (DW_TT)
+_XCDS, _XCD_RUN = 8, 8
+
+
+def attention_items(frame_counts, H):
+    """work table of sfm_attention_fwd_varlen at head_dim 64: int32 [n, 4] = (utterance, head, query tile, 0), one row per
+    workgroup, only the tiles that exist.  Logical order: longest key range first (the long items start first, the short ones
+    fill the tail), the tiles of one (utterance, head) adjacent.  Workgroups are dealt round-robin over the 8 XCDs, so within
+    every run of 64 the table is dealt the way the dense kernel maps its block ids: XCD x takes 8 consecutive logical items,
+    and the tiles that share one (utterance, head)'s K / V share an L2."""
+    T = np.asarray(frame_counts, dtype=np.int64)
+    order = np.argsort(-T, kind="stable")
+    nt = (T[order] + ATTN_QTILE - 1) // ATTN_QTILE                   # tiles per (utterance, head), in logical order
+    per = np.repeat(nt, H)                                           # ... per (utterance, head) pair
+    n = int(per.sum())
+    utt = np.repeat(np.repeat(order, H), per)
+    head = np.repeat(np.tile(np.arange(H), len(T)), per)
+    first = np.repeat(np.cumsum(per) - per, per)
+    tile = np.arange(n) - first
+    logical = np.stack([utt, head, tile, np.zeros(n, dtype=np.int64)], axis=1)
+    run = _XCDS * _XCD_RUN
+    pos = np.arange(n)
+    base = pos // run * run
+    total = np.minimum(run, n - base)                                # items of the position's run (the last one may be short)
+    p = pos - base
+    q, r, xcd, slot = total // _XCDS, total % _XCDS, p % _XCDS, p // _XCDS
+    src = base + np.where(xcd < r, xcd * (q + 1), r * (q + 1) + (xcd - r) * q) + slot
+    return np.ascontiguousarray(logical[src], dtype=np.int32)
+
+
+def dwconv_tiles(frame_counts):
+    """work table of sfm_dwconv_folded_varlen: int32 [n, 2] = (utterance, 64-frame tile of that utterance)"""
+    T = np.asarray(frame_counts, dtype=np.int64)
+    nt = (T + DWCONV_TILE - 1) // DWCONV_TILE
+    n = int(nt.sum())
+    utt = np.repeat(np.arange(len(T)), nt)
+    tile = np.arange(n) - np.repeat(np.cumsum(nt) - nt, nt)
+    return np.ascontiguousarray(np.stack([utt, tile], axis=1), dtype=np.int32)
+
+
+def framed_gemm_varlen(sig, Wt, out, samp_off, frame_off, *, B, sum_T, hop, padl, K, N, ldm, ldn=1, mode=0, out2=None, nsplit=0):
+    """framed_gemm on packed signals sig [sum_L] -> packed rows out [sum_T, ldm]"""
+    _need_dev(sig, Wt, out, samp_off, frame_off)
+    L = _lib.load()
+    Kpad, Npad = Wt.shape
+    _call("framed_gemm_f32_varlen", L.sfm_framed_gemm_f32_varlen,
+          (_p(sig), _p(Wt), _p(out), _p(out2), _p(samp_off), _p(frame_off), B, sum_T, hop, padl, K, Kpad, N, Npad, nsplit, ldm, ldn,
+           mode, 1 if out.dtype == torch.float32 else 0, _dt(), _stream()),
+          2.0 * sum_T * N * K, 4.0 * (sig.numel() + sum_T * N))
+    return out
+
+
+def framed_gemm_split16_varlen(sig, W, out, samp_off, frame_off, *, B, sum_T, hop, padl, ldm, mode=0, out2=None, nsplit=0,
+                               col2_off=0):
+    """framed_gemm_split16 on packed signals; W = pack_split16_matrix(...)"""
+    _need_dev(sig, out, samp_off, frame_off)
+    L = _lib.load()
+    hi, lo, K, N = W
+    Npad, Kpad = hi.shape
+    _call("framed_gemm_split16_varlen", L.sfm_framed_gemm_split16_varlen,
+          (_p(sig), _p(hi), _p(lo), _p(out), _p(out2), _p(samp_off), _p(frame_off), B, sum_T, hop, padl, K, Kpad, N, Npad, nsplit,
+           col2_off, ldm, mode, _stream()),
+          2.0 * sum_T * K * N, 4.0 * (sig.numel() + sum_T * N))
+    return out
+
+
+def attention_varlen(qkv16, frame_off, items, B, max_T, sum_T, H, hd, out=None, prescaled=False, out_dtype=None, sum_T2=None):
+    """attention() on packed rows: qkv16 [sum_T, 3*H*hd] (q | k | v) -> [sum_T, H*hd], every utterance over its own rows.
+    items: device copy of attention_items(frame_counts, H) (head_dim 64; None otherwise).  sum_T2 = sum of T_i^2, for the
+    profiler's FLOP count only."""
+    _need_dev(qkv16, frame_off, items)
+    L = _lib.load()
+    D = H * hd
+    ld = qkv16.stride(0)
+    if qkv16.dtype != _state["dtype"]:
+        raise RuntimeError("attention: Q | K | V are %s, the stage's format is %s" % (qkv16.dtype, _state["dtype"]))
+    if out is None:
+        out = torch.empty(sum_T, D, device=qkv16.device, dtype=out_dtype or qkv16.dtype)
+    n_items = 0 if items is None else items.shape[0]
+    _call("attention_fwd_varlen", L.sfm_attention_fwd_varlen,
+          (_p(qkv16), _p(out), _p(frame_off), _p(items), n_items, B, max_T, sum_T, H, hd, ld, out.stride(0), D, 2 * D,
+           (-1.0 if prescaled else 1.0 / math.sqrt(hd)), _dt(), _DT_ID[out.dtype], _stream()),
+          4.0 * H * hd * float(sum_T2 if sum_T2 is not None else 0), 4.0 * sum_T * D * 2)
+    return out
+
+
+def dwconv_folded_varlen(x16, wT, sc, sh, frame_off, tiles, B, max_T, sum_T, C, out=None, act=1):
+    """dwconv_folded() on packed rows [sum_T, C]: zero edge at each utterance's own first and last frame.
+    tiles: device copy of dwconv_tiles(frame_counts)."""
+    _need_dev(x16, frame_off, tiles)
+    L = _lib.load()
+    KS = wT.shape[0]
+    if out is None:
+        out = torch.empty_like(x16)
+    _call("dwconv_varlen", L.sfm_dwconv_folded_varlen,
+          (_p(x16), _p(wT), _p(sc), _p(sh), _p(out), _p(frame_off), _p(tiles), 0 if tiles is None else tiles.shape[0], B, max_T,
+           sum_T, C, KS, int(act), 1 if out.dtype == torch.float32 else 0, _dt(), _stream()),
+          2.0 * sum_T * C * KS, sum_T * C * 4.0)
+    return out
+
+
+def istft_ola_varlen(frames, win2, out, frame_off, samp_off, B, n_fft, hop, win, ld_frames):
+    """istft_ola() on packed frames [sum_T, ld_frames] -> packed samples out [sum_L]"""
+    _need_dev(frames, out, frame_off, samp_off)
+    L = _lib.load()
+    _call("istft_ola_varlen", L.sfm_istft_ola_varlen,
+          (_p(frames), _p(win2), _p(out), _p(frame_off), _p(samp_off), B, out.numel(), n_fft, hop, win, ld_frames, _stream()),
+          0.0, out.numel() * 12.0)
+    return out
+
+
 def pack_spec(re, im, dst, M, F, ld, ld_src):
     L = _lib.load()
     _call("pack_spec", L.sfm_pack_spec, (_p(re), _p(im), _p(dst), M, F, ld, ld_src, _stream()),

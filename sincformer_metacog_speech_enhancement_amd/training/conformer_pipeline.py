@@ -151,6 +151,45 @@ class SpeechEnhancer(HipModule):
                        mmag=mm, ld_enh=F)
         return er, ei, mm
 
+    def forward_packed(self, noisy_real, noisy_imag, frame_counts):
+        """forward() on a packed batch: noisy_real / noisy_imag [sum_T, F] hold the spectra of utterances of different lengths
+        back to back, `frame_counts` their frame counts (a sequence, or the functional.PackedSegments of the pass).  Returns
+        (enh_real, enh_imag, mask_mag), each [sum_T, F]; every utterance gets what forward() gives it alone.  eval() only."""
+        self._require_device(noisy_real, noisy_imag)
+        if self.training or self._wants_autograd(noisy_real, noisy_imag):
+            raise RuntimeError("SpeechEnhancer.forward_packed is an inference path: call eval() and pass tensors that do not "
+                               "require grad (training takes rectangular batches through forward())")
+        seg = frame_counts if isinstance(frame_counts, Fn.PackedSegments) else Fn.PackedSegments(frame_counts)
+        nr, ni = noisy_real.float().contiguous(), noisy_imag.float().contiguous()
+        if nr.dim() != 2 or nr.shape != ni.shape or nr.shape[0] != seg.sum_T or nr.shape[1] != self.n_freq:
+            raise RuntimeError("forward_packed: spectra %s / %s, expected [%d, %d] (sum of the frame counts x n_freq)" % (
+                tuple(nr.shape), tuple(ni.shape), seg.sum_T, self.n_freq))
+        d_model, H = self.input_proj.out_features, self.num_heads
+        if d_model % H != 0 or d_model // H > 256:
+            raise NotImplementedError("forward_packed: d_model %d with %d heads (head_dim %s): the packed attention kernels take "
+                                      "head_dim <= 256" % (d_model, H, d_model / H))
+        pk = self._packed(self._pack)
+        M, F = nr.shape
+        dev = nr.device
+        ldc = ops.round_up(2 * F, 8)
+        cat = torch.empty(M, ldc, device=dev, dtype=torch.float32)
+        ops.pack_spec(nr, ni, cat, M, F, ldc, F)
+        ld16 = pk["proj"].Kpad
+        with ops.stage("front"):
+            x16 = torch.zeros(M, ld16, device=dev, dtype=ops.compute_dtype())
+            ops.layernorm(cat, pk["in_w"], pk["in_b"], out16=x16)
+            x = ops.linear16(x16, pk["proj"], out_dtype=torch.float32)
+        for bp in pk["blocks"]:
+            x = Fn.block_forward(x, bp, None, None, H, seg=seg)
+        with ops.stage("tail"):
+            h16 = Fn._ln16(x, pk["on_w"], pk["on_b"])
+            logits = ops.linear16(h16, pk["heads"], out_dtype=torch.float32)   # [M, 2F] = mag | phase
+        er = torch.empty(M, F, device=dev, dtype=torch.float32)
+        ei = torch.empty(M, F, device=dev, dtype=torch.float32)
+        mm = torch.empty(M, F, device=dev, dtype=torch.float32)
+        ops.polar_mask(logits, logits[:, F:], 1, M, F, math.pi / 6, logits.stride(0), nr=nr, ni=ni, er=er, ei=ei, mmag=mm, ld_enh=F)
+        return er, ei, mm
+
     # LayerNorm over 2F needs D passed explicitly: ops.layernorm infers D from x32.shape[1]
     # (cat has ldc >= 2F columns), so view the valid columns.
 
@@ -399,6 +438,31 @@ class ConformerPipeline:
         else:
             y = self._enhance_device(x)
         return y.squeeze(0).cpu().numpy()
+
+    @torch.no_grad()
+    def enhance_batch(self, noisy_signals, max_frames=None):
+        """enhance_signal for a list of signals of different lengths (1-D numpy arrays or tensors) in packed passes: no padding,
+        every result equal to what enhance_signal gives that signal alone; returns a list of numpy arrays of the same lengths.
+        Per pass: one host-to-device copy of the concatenated samples, one forward over all frames, one copy back.
+        max_frames: upper bound on the frames of a pass (functional.packed_segments); default: one pass."""
+        if self.model is None:
+            raise RuntimeError("No model loaded.")
+        sigs = [np.ascontiguousarray(s.detach().cpu().numpy() if torch.is_tensor(s) else s, dtype=np.float32).reshape(-1)
+                for s in noisy_signals]
+        if not sigs:
+            return []
+        self.model.eval()
+        out = []
+        for seg in Fn.packed_segments([s.size for s in sigs], self.fft_size, self.hop_size, max_frames):
+            # the samples are concatenated straight into a page-locked staging buffer: one asynchronous copy to the device
+            stage = torch.empty(seg.sum_L, dtype=torch.float32, pin_memory=True)
+            np.concatenate(sigs[seg.start:seg.stop], out=stage.numpy())
+            x = stage.to(self.device, non_blocking=True)
+            nr, ni = Fn.stft_packed(x, seg, self.fft_size, self.hop_size, self.frame_size)
+            er, ei, _ = self.model.forward_packed(nr, ni, seg)
+            y = Fn.istft_packed(er, ei, seg, self.fft_size, self.hop_size, self.frame_size).cpu().numpy()
+            out.extend(np.split(y, seg.sample_offsets[1:-1]))             # views of the pass's result, no second copy
+        return out
 
     def _enhance_device(self, x):
         nr, ni = batch_stft(x, self.fft_size, self.hop_size, self.frame_size)
