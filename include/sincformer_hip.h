@@ -268,6 +268,10 @@ int sfm_framed_gemm_split16(const float* sig, const void* Whi, const void* Wlo, 
  * atomics.  Sizes: sfm_*_ws_floats, or as stated; ws contents are scratch (destroyed), 16-byte aligned.
  * here: ws >= 64 * B * 5 doubles (wave_moments), >= 2048 * 4 doubles (spec_sums). */
 int sfm_wave_moments(const float* est, const float* tgt, double* S, int B, int L, double* ws, void* stream);
+/* packed form of sfm_wave_moments (atomics only): est / tgt = B signals back to back, signal b = samples
+ * [samp_off[b], samp_off[b + 1]) (int32 [B + 1] on the device; an empty signal leaves its row zero); max_L = the longest.
+ * The grid is min(ceil(max_L / 256), 64) x B workgroups along x: SFM_ERR_SHAPE when that exceeds 2^31 - 1. */
+int sfm_wave_moments_varlen(const float* est, const float* tgt, double* S, const int* samp_off, int B, int max_L, void* stream);
 int sfm_spec_sums(const float* pr, const float* pi, const float* tr, const float* ti, double* S, long long n, double* ws,
                   void* stream);
 int sfm_enhancer_loss_finalize(const double* Sw, const double* Sm, const double* Sr, const long long* nr, int B,
@@ -303,6 +307,21 @@ int sfm_ssnr_frames(const float* clean, const float* enh, double* acc, int B, in
                     float lower, void* stream);
 int sfm_stoi_frames(const float* cr, const float* ci, const float* er, const float* ei, const double* sc, const double* se,
                     double* acc, int B, int nframes, int F, void* stream);
+/* lsd_frames: the reference's PESQ fallback (evaluation/pesq_eval.py:66-78) per frame, from the two spectra [B, nframes, F] of
+ *   a rectangular-window DFT: acc [B] fp64 (zero-filled) += sqrt(mean_f (log(|C_f| + 1e-10) - log(|E_f| + 1e-10))^2). */
+int sfm_lsd_frames(const float* cr, const float* ci, const float* er, const float* ei, double* acc, int B, int nframes, int F,
+                   void* stream);
+/* Packed forms for utterances of different lengths (layout as sfm_framed_gemm_f32_varlen): samples of utterance u =
+ * [samp_off[u], samp_off[u + 1]); its frames in the METRIC's framing (n_u = (L_u - frame) / hop + 1, or 0 when L_u < frame)
+ * = packed frames / spectrum rows [frame_off[u], frame_off[u + 1]), both int32 [B + 1] on the device; an utterance may own
+ * no frame (its acc entries stay zero).  sum_frames = frame_off[B]; 0 launches nothing.  One wave per packed frame; the
+ * per-utterance sums are fp64 atomics as in the dense forms.  acc / sc / se indexed by utterance as above. */
+int sfm_ssnr_frames_varlen(const float* clean, const float* enh, double* acc, const int* samp_off, const int* frame_off, int B,
+                           int sum_frames, int frame, int hop, float upper, float lower, void* stream);
+int sfm_stoi_frames_varlen(const float* cr, const float* ci, const float* er, const float* ei, const double* sc,
+                           const double* se, double* acc, const int* frame_off, int B, int sum_frames, int F, void* stream);
+int sfm_lsd_frames_varlen(const float* cr, const float* ci, const float* er, const float* ei, double* acc, const int* frame_off,
+                          int B, int sum_frames, int F, void* stream);
 /* Gradient of the SincConv1d FIR bank w.r.t. its taps (training of agents/perception.py:79-118):
  * dfilt [C, K] += sum_{b,l} dy[b, l, c] x[b, l + k - K/2]; x [B, L] fp32, dy [B, L, C] 16-bit or fp32; scratch:
  * sfm_sinc_wgrad_scratch_floats floats (need not be zeroed).  K <= 256. */

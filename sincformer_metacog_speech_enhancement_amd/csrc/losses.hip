@@ -36,6 +36,37 @@ __global__ __launch_bounds__(256) void wave_moments_kernel(const float* __restri
   }
 }
 
+// Packed form: est / tgt hold B signals back to back, signal b = samples [samp_off[b], samp_off[b + 1]).  The grid is
+// B x nbx workgroups along x (no limit on B from the grid's y dimension); workgroup (b, x) strides over signal b with the grid
+// its dense launch would use (min(ceil(L_b / 256), 64) workgroups; the others leave at once), so every partial is the dense
+// kernel's and only the order of the fp64 atomics differs.  Atomics only.
+__global__ __launch_bounds__(256) void wave_moments_varlen_kernel(const float* __restrict__ est, const float* __restrict__ tgt,
+                                                                  double* __restrict__ S, const int* __restrict__ samp_off,
+                                                                  int nbx) {
+  __shared__ double red[4][5];
+  const int b = blockIdx.x / nbx, bx = blockIdx.x - b * nbx;
+  const int s0 = samp_off[b], L = samp_off[b + 1] - s0;
+  int nb = (L + 255) / 256;
+  if (nb > nbx) nb = nbx;                                        // 64 at most (the launch's cap); fewer if max_L understates
+  if (bx >= nb) return;
+  const float* e = est + s0;
+  const float* t = tgt + s0;
+  double s[5] = {0, 0, 0, 0, 0};
+  for (int i = bx * 256 + threadIdx.x; i < L; i += nb * 256) {
+    const double a = e[i], c = t[i];
+    s[0] += a; s[1] += c; s[2] += a * a; s[3] += c * c; s[4] += a * c;
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    s[k] = wave_sum_d(s[k]);
+    if (lane == 0) red[wave][k] = s[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < 5)
+    atomicAdd(&S[b * 5 + threadIdx.x], red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x]);
+}
+
 // spectra of prediction (pr, pi) and target (tr, ti), n bins each:
 // S = { sum (|T|-|P|)^2, sum |T|^2, sum |log(|P|+1e-8) - log(|T|+1e-8)|, sum |sqrt(P^2+1e-8) - sqrt(T^2+1e-8)| }
 __global__ __launch_bounds__(256) void spec_sums_kernel(const float* __restrict__ pr, const float* __restrict__ pi,
@@ -111,6 +142,18 @@ extern "C" int sfm_wave_moments(const float* est, const float* tgt, double* S, i
   if (nb > 64) nb = 64;
   SFM_LAUNCH(wave_moments_kernel, dim3(nb, B), dim3(256), 0, (hipStream_t)stream, est, tgt, S, L, ws);
   return ws ? sfm_fold_partials_f64(ws, S, B, 5, 5, nb, 1, stream) : SFM_OK;
+}
+
+// max_L: the longest signal of the pack (sizes the grid; a signal longer than 64 x 256 samples is strided over anyway)
+extern "C" int sfm_wave_moments_varlen(const float* est, const float* tgt, double* S, const int* samp_off, int B, int max_L,
+                                       void* stream) {
+  if (!est || !tgt || !S || !samp_off) return SFM_ERR_ARG;
+  if (B <= 0 || max_L <= 0) return SFM_ERR_SHAPE;
+  int nb = (max_L + 255) / 256;
+  if (nb > 64) nb = 64;
+  if ((long long)nb * B > 0x7fffffffLL) return SFM_ERR_SHAPE;    // grid x
+  SFM_LAUNCH(wave_moments_varlen_kernel, dim3((unsigned)(nb * B)), dim3(256), 0, (hipStream_t)stream, est, tgt, S, samp_off, nb);
+  return SFM_OK;
 }
 
 extern "C" int sfm_spec_sums(const float* pr, const float* pi, const float* tr, const float* ti, double* S, long long n,

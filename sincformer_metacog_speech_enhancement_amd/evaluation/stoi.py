@@ -11,13 +11,14 @@ from ._common import to_device_batch
 _mat = {}
 
 
-def _dft_operand(frame_len, dev):
-    """[frame_len, 2F] windowed rfft as a real matrix: np.hanning (symmetric) window, F = frame_len // 2 + 1."""
-    key = (frame_len, str(dev))
+def _dft_operand(frame_len, dev, window="hann"):
+    """[frame_len, 2F] windowed rfft as a real matrix: np.hanning (symmetric) window - or none ("rect", the PESQ fallback's
+    frames) - F = frame_len // 2 + 1."""
+    key = (frame_len, str(dev)) if window == "hann" else (frame_len, str(dev), window)
     m = _mat.get(key)
     if m is None:
         F = frame_len // 2 + 1
-        w = np.hanning(frame_len)
+        w = np.hanning(frame_len) if window == "hann" else np.ones(frame_len)
         n = np.arange(frame_len, dtype=np.float64)[:, None]
         f = np.arange(F, dtype=np.float64)[None, :]
         ang = 2.0 * np.pi * ((n * f) % frame_len) / frame_len

@@ -194,6 +194,35 @@ class PackedSegments:
             t["attn_items", H] = torch.from_numpy(ops.attention_items(self.frame_counts, H)).to(device)
         return t
 
+    def metric_tables(self, device, framings):
+        """frame offsets of the quality metrics' own framings (evaluation/packed.py): framings = ((frame, hop), ...), no padding,
+        n_i = (L_i - frame) // hop + 1 frames where L_i >= frame, else none.  Returns {(frame, hop): {"frame_off": device int32
+        [B + 1], "counts": device int32 [B], "n": the host counts, "sum": their sum}}; the framings not yet on the device go
+        up in ONE copy and are cached like tables()."""
+        if self.lengths is None:
+            raise ValueError("metric_tables: the segments were built without signal lengths")
+        cache = self._tables.setdefault(("metrics", str(device)), {})
+        missing = [fh for fh in dict.fromkeys(framings) if fh not in cache]
+        if missing:
+            host = [metric_frame_counts(self.lengths, *fh) for fh in missing]
+            flat = torch.from_numpy(np.concatenate([np.concatenate([[0], np.cumsum(n), n]) for n in host]).astype(np.int32)).to(device)
+            w = 2 * self.B + 1
+            for i, (fh, n) in enumerate(zip(missing, host)):
+                cache[fh] = {"frame_off": flat[i * w:i * w + self.B + 1], "counts": flat[i * w + self.B + 1:(i + 1) * w], "n": n,
+                             "sum": int(n.sum())}
+        return {fh: cache[fh] for fh in framings}
+
+
+def metric_frame_counts(lengths, frame, hop):
+    """frames of a metric's framing per utterance (evaluation/ssnr.py:57, stoi.py:71, pesq_eval.py:61): int64 [B]"""
+    if frame <= 0 or hop <= 0:
+        raise ValueError("metric_frame_counts: frame %d / hop %d" % (frame, hop))
+    L = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    n = np.where(L >= frame, (L - frame) // hop + 1, 0)
+    if int(n.sum()) >= 2 ** 31:
+        raise ValueError("a packed pass is indexed with int32: %d metric frames" % int(n.sum()))
+    return n
+
 
 def packed_segments(lengths, n_fft=N_FFT, hop=HOP, max_frames=None):
     """Signal lengths -> list of PackedSegments, one per pass (no GPU needed).  T_i = 1 + L_i // hop.  A length the dense stft()

@@ -76,6 +76,11 @@ SIGNATURES = {
                                   c_vp],
     "sfm_ssnr_frames": [c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_f, c_f, c_vp],
     "sfm_stoi_frames": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_vp],
+    "sfm_lsd_frames": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_vp],
+    "sfm_ssnr_frames_varlen": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_f, c_f, c_vp],
+    "sfm_stoi_frames_varlen": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_vp],
+    "sfm_lsd_frames_varlen": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_vp],
+    "sfm_wave_moments_varlen": [c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_vp],
     "sfm_sinc_wgrad_scratch_floats": [c_i, c_i, c_i, c_i],
     "sfm_sinc_wgrad": [c_vp, c_vp, c_i, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_vp],
     "sfm_sinc_shift_len": [c_i],

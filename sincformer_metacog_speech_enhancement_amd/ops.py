@@ -977,6 +977,59 @@ def wave_moments(est, tgt):
     return S
 
 
+def wave_moments_varlen(est, tgt, samp_off, B, max_L):
+    """wave_moments of packed signals est, tgt [sum_L] -> S [B, 5] fp64 (the fp64-atomics form)"""
+    _need_dev(est, tgt, samp_off)
+    L = _lib.load()
+    S = torch.zeros(B, 5, device=est.device, dtype=torch.float64)
+    _call("loss_reduce", L.sfm_wave_moments_varlen, (_p(est), _p(tgt), _p(S), _p(samp_off), B, int(max_L), _stream()), 0.0,
+          8.0 * est.numel())
+    return S
+
+
+def ssnr_frames_varlen(clean, enh, samp_off, frame_off, B, sum_frames, frame, hop, upper=35.0, lower=-10.0):
+    """packed clean / enh [sum_L] -> acc [B, 2] fp64 = {sum of the clipped SNRs of the non-silent frames, their count}"""
+    _need_dev(clean, enh, samp_off, frame_off)
+    L = _lib.load()
+    acc = torch.zeros(B, 2, device=clean.device, dtype=torch.float64)
+    _call("metrics", L.sfm_ssnr_frames_varlen, (_p(clean), _p(enh), _p(acc), _p(samp_off), _p(frame_off), B, int(sum_frames),
+                                                int(frame), int(hop), float(upper), float(lower), _stream()), 0.0,
+          8.0 * clean.numel() * frame / hop)
+    return acc
+
+
+def stoi_frames_varlen(cr, ci, er, ei, sc, se, frame_off, B):
+    """packed spectra rows [sum_frames, F], sc / se [B] fp64 -> acc [B] fp64 = sum of the clipped frame correlations"""
+    _need_dev(cr, ci, er, ei, sc, se, frame_off)
+    L = _lib.load()
+    n, F = cr.shape
+    acc = torch.zeros(B, device=cr.device, dtype=torch.float64)
+    _call("metrics", L.sfm_stoi_frames_varlen, (_p(cr), _p(ci), _p(er), _p(ei), _p(sc), _p(se), _p(acc), _p(frame_off), B, n, F,
+                                                _stream()), 0.0, 16.0 * n * F)
+    return acc
+
+
+def lsd_frames(cr, ci, er, ei):
+    """spectra [B, nframes, F] -> acc [B] fp64 = sum over the frames of the log-spectral distortion"""
+    _need_dev(cr, ci, er, ei)
+    L = _lib.load()
+    B, n, F = cr.shape
+    acc = torch.zeros(B, device=cr.device, dtype=torch.float64)
+    _call("metrics", L.sfm_lsd_frames, (_p(cr), _p(ci), _p(er), _p(ei), _p(acc), B, n, F, _stream()), 0.0, 16.0 * B * n * F)
+    return acc
+
+
+def lsd_frames_varlen(cr, ci, er, ei, frame_off, B):
+    """packed spectra rows [sum_frames, F] -> acc [B] fp64"""
+    _need_dev(cr, ci, er, ei, frame_off)
+    L = _lib.load()
+    n, F = cr.shape
+    acc = torch.zeros(B, device=cr.device, dtype=torch.float64)
+    _call("metrics", L.sfm_lsd_frames_varlen, (_p(cr), _p(ci), _p(er), _p(ei), _p(acc), _p(frame_off), B, n, F, _stream()), 0.0,
+          16.0 * n * F)
+    return acc
+
+
 def spec_sums(pr, pi, tr, ti, out=None):
     L = _lib.load()
     S = torch.zeros(4, device=pr.device, dtype=torch.float64) if out is None else out

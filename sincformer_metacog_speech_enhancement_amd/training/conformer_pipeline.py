@@ -458,11 +458,54 @@ class ConformerPipeline:
             stage = torch.empty(seg.sum_L, dtype=torch.float32, pin_memory=True)
             np.concatenate(sigs[seg.start:seg.stop], out=stage.numpy())
             x = stage.to(self.device, non_blocking=True)
-            nr, ni = Fn.stft_packed(x, seg, self.fft_size, self.hop_size, self.frame_size)
-            er, ei, _ = self.model.forward_packed(nr, ni, seg)
-            y = Fn.istft_packed(er, ei, seg, self.fft_size, self.hop_size, self.frame_size).cpu().numpy()
+            y = self._enhance_packed_device(x, seg).cpu().numpy()
             out.extend(np.split(y, seg.sample_offsets[1:-1]))             # views of the pass's result, no second copy
         return out
+
+    def _enhance_packed_device(self, x, seg):
+        """the device part of a packed pass: samples [sum_L] of the pass's signals back to back -> enhanced samples [sum_L]"""
+        nr, ni = Fn.stft_packed(x, seg, self.fft_size, self.hop_size, self.frame_size)
+        er, ei, _ = self.model.forward_packed(nr, ni, seg)
+        return Fn.istft_packed(er, ei, seg, self.fft_size, self.hop_size, self.frame_size)
+
+    @torch.no_grad()
+    def evaluate_batch(self, clean_signals, noisy_signals, fs=None, max_frames=None, metrics=("stoi", "pesq", "ssnr"),
+                       return_enhanced=False):
+        """The inner loop of the reference's evaluate (main.py:315-359) for one list of test files: enhance every noisy signal
+        and score the noisy and the enhanced signal against the clean one (compute_stoi, compute_pesq, compute_ssnr on
+        clean[:ml], x[:ml]), in packed passes.  Two lists of 1-D signals of any lengths; every pair is cut to its shorter member.
+        Returns {"noisy": {metric: float64 numpy [N]}, "enhanced": {...}} in the caller's order, and with return_enhanced
+        "signals": the list enhance_batch returns.  Per pass: one host-to-device copy (noisy and clean samples), STFT, forward
+        and iSTFT as enhance_batch, evaluation.compute_metrics_packed twice, ONE copy back of the [2, metrics, B] scores; the
+        enhanced samples leave the device only with return_enhanced.  max_frames: as enhance_batch."""
+        from ..evaluation import packed as pk
+        if self.model is None:
+            raise RuntimeError("No model loaded.")
+        metrics = pk._check_metrics(metrics)
+        clean, noisy, passes = pk.plan_evaluation(clean_signals, noisy_signals, self.fft_size, self.hop_size, max_frames)
+        N = len(noisy)
+        res = {k: {m: np.zeros(N, dtype=np.float64) for m in metrics} for k in ("noisy", "enhanced")}
+        if return_enhanced:
+            res["signals"] = []
+        self.model.eval()
+        fs = fs or self.fs
+        for seg in passes:
+            stage = torch.empty(2, seg.sum_L, dtype=torch.float32, pin_memory=True)
+            np.concatenate(noisy[seg.start:seg.stop], out=stage.numpy()[0])
+            np.concatenate(clean[seg.start:seg.stop], out=stage.numpy()[1])
+            both = stage.to(self.device, non_blocking=True)
+            x, c = both[0], both[1]
+            y = self._enhance_packed_device(x, seg)
+            shared = {}                                                    # the clean spectra serve both comparisons
+            sn = pk.compute_metrics_packed(c, x, seg, fs, metrics, clean_spectra=shared)
+            se = pk.compute_metrics_packed(c, y, seg, fs, metrics, clean_spectra=shared)
+            scores = torch.stack([torch.stack([d[m] for m in metrics]) for d in (sn, se)]).cpu().numpy()
+            for k, side in enumerate(("noisy", "enhanced")):
+                for j, m in enumerate(metrics):
+                    res[side][m][seg.start:seg.stop] = scores[k, j]
+            if return_enhanced:
+                res["signals"].extend(np.split(y.cpu().numpy(), seg.sample_offsets[1:-1]))
+        return res
 
     def _enhance_device(self, x):
         nr, ni = batch_stft(x, self.fft_size, self.hop_size, self.frame_size)
