@@ -824,31 +824,16 @@ static int attention_fwd_impl(const void* qkv, void* out, float* lse, int B, int
                                   out_other, sfm_attn_variant == 6 ? 44 : ((sfm_attn_variant == 5 || (sfm_attn_variant == 0 && pipe4_auto)) ? 4 : 8), st);
     if (p_drop == 0.f && bytes_q < (1LL << 31) && bytes_o < (1LL << 31) && sfm_attn_variant == 3) {
       const int n_items = nqt5 * H * B;
-      // (CU count and the dynamic-LDS attribute are per device: caches keyed by hipGetDevice())
-      int dev = 0;
-      if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return SFM_ERR_LAUNCH;
-      static int ncus[64] = {0};
-      if (ncus[dev] == 0) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return SFM_ERR_LAUNCH;
-        ncus[dev] = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-      }
-      const int ncu = ncus[dev];
+      const int ncu = sfm_cu_count();
+      if (ncu <= 0) return SFM_ERR_LAUNCH;
       constexpr int lds = 6 * 16384 + 65536;                        // K/V ring + Q prefetch region = 160 KB
-      static bool attr_set[64][2] = {{false, false}};
-      const int ti = dtype == SFM_DT_F16 ? 1 : 0;
-      if (!attr_set[dev][ti]) {
-        const void* fn = ti ? (const void*)attn_fwd_hd64r_kernel<F16> : (const void*)attn_fwd_hd64r_kernel<BF16>;
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return SFM_ERR_LAUNCH;
-        attr_set[dev][ti] = true;
-      }
       dim3 gridr(n_items < ncu ? n_items : ncu), blockr(512);
       if (dtype == SFM_DT_F16)
-        SFM_LAUNCH((attn_fwd_hd64r_kernel<F16>), gridr, blockr, lds, st, (const u16*)qkv, (u16*)out, T, ldqkv, ldo, koff, voff,
-                   qkv_batch_stride, o_batch_stride, sl2, nqt5, H, n_items, lse, out_other);
+        SFM_LAUNCH_LDS((attn_fwd_hd64r_kernel<F16>), gridr, blockr, lds, st, (const u16*)qkv, (u16*)out, T, ldqkv, ldo, koff, voff,
+                       qkv_batch_stride, o_batch_stride, sl2, nqt5, H, n_items, lse, out_other);
       else
-        SFM_LAUNCH((attn_fwd_hd64r_kernel<BF16>), gridr, blockr, lds, st, (const u16*)qkv, (u16*)out, T, ldqkv, ldo, koff, voff,
-                   qkv_batch_stride, o_batch_stride, sl2, nqt5, H, n_items, lse, out_other);
+        SFM_LAUNCH_LDS((attn_fwd_hd64r_kernel<BF16>), gridr, blockr, lds, st, (const u16*)qkv, (u16*)out, T, ldqkv, ldo, koff, voff,
+                       qkv_batch_stride, o_batch_stride, sl2, nqt5, H, n_items, lse, out_other);
       return SFM_OK;
     }
     const int nqt = (T + 127) / 128;
@@ -870,7 +855,6 @@ static int attention_fwd_impl(const void* qkv, void* out, float* lse, int B, int
       SFM_LAUNCH((attn_fwd_generic_kernel<BF16>), grid, block, 0, st, (const u16*)qkv, (u16*)out, T, hd,
                          ldqkv, ldo, koff, voff, qkv_batch_stride, o_batch_stride, scale, lse, p_drop, seed);
   }
-  SFM_CHECK_LAUNCH();
   return SFM_OK;
 }
 

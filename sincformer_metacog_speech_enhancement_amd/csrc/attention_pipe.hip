@@ -726,29 +726,16 @@ static int attnp_launch(const void* qkv, void* out, float* lse, int B, int Tlen,
   constexpr int QROWS = 32 * SB * NW;
   const int nqt = (Tlen + QROWS - 1) / QROWS;
   const int n_items = nqt * H * B;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return SFM_ERR_LAUNCH;
-  static int ncu[64] = {0};
-  static bool attr_set[64] = {false};
-  if (ncu[dev] == 0) {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return SFM_ERR_LAUNCH;
-    ncu[dev] = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
+  const int ncu = sfm_cu_count();
+  if (ncu <= 0) return SFM_ERR_LAUNCH;
   constexpr int lds = 3 * (NW * SB / 8) * 16384 + NW * SB * 4096;   // K/V ring + Q prefetch region: 160 KB (8, 2) / 80 KB (4, 2) / 160 KB (4, 4)
-  const void* fn = SB == 4 ? (const void*)attn_fwd_hd64q4_kernel<T>
-                           : (NW == 8 ? (const void*)attn_fwd_hd64p8_kernel<T> : (const void*)attn_fwd_hd64p4_kernel<T>);
-  if (!attr_set[dev]) {
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return SFM_ERR_LAUNCH;
-    attr_set[dev] = true;
-  }
   constexpr int wgs_per_cu = (SB == 4) ? 1 : 8 / NW;
   // (diagnostic: SFM_ATTNP_WGS_PER_CU=1 with the (4, 2) form = one wave per SIMD, what a lone wave's step loop sustains)
   static const int wgs_env = getenv("SFM_ATTNP_WGS_PER_CU") ? atoi(getenv("SFM_ATTNP_WGS_PER_CU")) : 0;
-  const int resident = ncu[dev] * ((wgs_env > 0 && wgs_env <= wgs_per_cu) ? wgs_env : wgs_per_cu);
+  const int resident = ncu * ((wgs_env > 0 && wgs_env <= wgs_per_cu) ? wgs_env : wgs_per_cu);
   dim3 gridr(n_items < resident ? n_items : resident), blockr(64 * NW);
-#define ATTNP_LAUNCH(K) SFM_LAUNCH((K<T>), gridr, blockr, lds, st, (const u16*)qkv, (u16*)out, Tlen, ldqkv, ldo, koff, voff,          \
-                                   qkv_batch_stride, o_batch_stride, sl2, nqt, H, n_items, lse, out_other)
+#define ATTNP_LAUNCH(K) SFM_LAUNCH_LDS((K<T>), gridr, blockr, lds, st, (const u16*)qkv, (u16*)out, Tlen, ldqkv, ldo, koff, voff,      \
+                                       qkv_batch_stride, o_batch_stride, sl2, nqt, H, n_items, lse, out_other)
   if (SB == 4) ATTNP_LAUNCH(attn_fwd_hd64q4_kernel);
   else if (NW == 8) ATTNP_LAUNCH(attn_fwd_hd64p8_kernel);
   else ATTNP_LAUNCH(attn_fwd_hd64p4_kernel);

@@ -188,7 +188,6 @@ extern "C" int sfm_framed_gemm_f32(const float* sig, const float* Wt, const floa
   dim3 grid((N + FBN - 1) / FBN, (M + FBM - 1) / FBM, B), block(256);
   if (dtype == SFM_DT_F16) SFM_LAUNCH((framed_gemm_kernel<F16, false>), grid, block, 0, (hipStream_t)stream, p);
   else SFM_LAUNCH((framed_gemm_kernel<BF16, false>), grid, block, 0, (hipStream_t)stream, p);
-  SFM_CHECK_LAUNCH();
   return SFM_OK;
 }
 

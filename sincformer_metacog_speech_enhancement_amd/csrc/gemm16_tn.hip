@@ -422,23 +422,13 @@ static int gemm16_tn_launch(const void* G, const void* X, float* dW, float* db, 
     splits = (M + rows - 1) / rows;
     if (ws && (long long)splits * ((long long)N * K + N) > ws_floats) return SFM_ERR_ARG;
     dim3 grid(N / 256, K / 256, splits), block(1024);
-    const size_t lds = 4 * 64 * TN_ROW * sizeof(u16);
-    static bool attr_set_dev[64] = {false};        // hipFuncSetAttribute is per device
-  int attr_dev_ = 0;
-  if (hipGetDevice(&attr_dev_) != hipSuccess || attr_dev_ < 0 || attr_dev_ >= 64) return SFM_ERR_LAUNCH;
-  bool& attr_set = attr_set_dev[attr_dev_];
-    if (!attr_set) {
-      if (hipFuncSetAttribute((const void*)gemm16_tn_wide_kernel<F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-          hipFuncSetAttribute((const void*)gemm16_tn_wide_kernel<BF16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return SFM_ERR_LAUNCH;
-      attr_set = true;
-    }
+    constexpr int lds = 4 * 64 * TN_ROW * (int)sizeof(u16);
     if (dtype == SFM_DT_F16)
-      SFM_LAUNCH((gemm16_tn_wide_kernel<F16>), grid, block, lds, (hipStream_t)stream, (const u16*)G, (const u16*)X, dW, db, M, N, K,
-                 ldg, ldx, ldw, rows, ws);
+      SFM_LAUNCH_LDS((gemm16_tn_wide_kernel<F16>), grid, block, lds, (hipStream_t)stream, (const u16*)G, (const u16*)X, dW, db, M, N, K,
+                     ldg, ldx, ldw, rows, ws);
     else
-      SFM_LAUNCH((gemm16_tn_wide_kernel<BF16>), grid, block, lds, (hipStream_t)stream, (const u16*)G, (const u16*)X, dW, db, M, N, K,
-                 ldg, ldx, ldw, rows, ws);
+      SFM_LAUNCH_LDS((gemm16_tn_wide_kernel<BF16>), grid, block, lds, (hipStream_t)stream, (const u16*)G, (const u16*)X, dW, db, M, N, K,
+                     ldg, ldx, ldw, rows, ws);
     return ws ? tn_fold(ws, dW, db, N, K, ldw, splits, 1, stream) : SFM_OK;
   }
   const int tiles = ((N + 127) / 128) * ((K + 127) / 128);

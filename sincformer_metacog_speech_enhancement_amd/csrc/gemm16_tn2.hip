@@ -249,15 +249,6 @@ static int tn2_go(const void* G, const void* X, float* dW, float* db, int M, int
                   unsigned x_rec, hipStream_t st, const TnConv& cv, int n_cu, float* ws, long long ws_floats) {
   constexpr int TNc = 64 * WNW, TKc = 64 * WKW;
   constexpr int lds = STAGES * 64 * (TNc + TKc) * 2;
-  static bool attr_set_dev[64] = {false};                      // hipFuncSetAttribute is per device
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return SFM_ERR_LAUNCH;
-  if (!attr_set_dev[dev]) {
-    if (hipFuncSetAttribute((const void*)gemm16_tn2_kernel<T, WNW, WKW, STAGES>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) !=
-        hipSuccess)
-      return SFM_ERR_LAUNCH;
-    attr_set_dev[dev] = true;
-  }
   const int tiles = ((N + TNc - 1) / TNc) * ((K + TKc - 1) / TKc);
   // one workgroup per CU (the ring takes most of the LDS): ONE round of n_cu workgroups
   int splits = n_cu / tiles;
@@ -269,8 +260,8 @@ static int tn2_go(const void* G, const void* X, float* dW, float* db, int M, int
   splits = (M + rows - 1) / rows;
   dim3 grid((N + TNc - 1) / TNc, (K + TKc - 1) / TKc, splits), block(WNW * WKW * 64);
   if (ws && (long long)splits * ((long long)N * K + (long long)WKW * N) > ws_floats) return SFM_ERR_ARG;
-  SFM_LAUNCH((gemm16_tn2_kernel<T, WNW, WKW, STAGES>), grid, block, lds, st, (const u16*)G, (const u16*)X, dW, db, M, N, K, ldg, ldx,
-             ldw, rows, g_rec, x_rec, cv, ws);
+  SFM_LAUNCH_LDS((gemm16_tn2_kernel<T, WNW, WKW, STAGES>), grid, block, lds, st, (const u16*)G, (const u16*)X, dW, db, M, N, K, ldg,
+                 ldx, ldw, rows, g_rec, x_rec, cv, ws);
   return ws ? tn_fold(ws, dW, db, N, K, ldw, splits, WKW, (void*)st) : SFM_OK;
 }
 

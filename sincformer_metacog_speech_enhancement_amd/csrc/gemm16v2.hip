@@ -604,19 +604,10 @@ __global__ __launch_bounds__(256) void gemm16p_kernel(Gemm2Params p, int total_t
 template <class T, int BN>
 static int launch_p(const Gemm2Params& p, hipStream_t stream) {
   constexpr int lds = 2 * (128 + BN) * 128 + 4 * 8 * (BN / 2 + 4) * 4;
-  static bool attr_set_dev[64] = {false};        // hipFuncSetAttribute is per device
-  int attr_dev_ = 0;
-  if (hipGetDevice(&attr_dev_) != hipSuccess || attr_dev_ < 0 || attr_dev_ >= 64) return SFM_ERR_LAUNCH;
-  bool& attr_set = attr_set_dev[attr_dev_];
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)gemm16p_kernel<T, BN>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-      return SFM_ERR_LAUNCH;
-    attr_set = true;
-  }
   const int total = p.nMt * p.nNt * p.B;
   int nblk = 512;                                      // 2 workgroups on each of the 256 CUs
   if (total < nblk) nblk = (total + 7) / 8 * 8;
-  SFM_LAUNCH((gemm16p_kernel<T, BN>), dim3(nblk), dim3(256), lds, stream, p, total);
+  SFM_LAUNCH_LDS((gemm16p_kernel<T, BN>), dim3(nblk), dim3(256), lds, stream, p, total);
   return SFM_OK;
 }
 
@@ -742,17 +733,8 @@ __global__ __launch_bounds__(NW * 64) void gemm16w_kernel(Gemm2Params p) {
 template <class T, int BM, int BN, int NW>
 static int launch_w(const Gemm2Params& p, hipStream_t stream) {
   constexpr int lds = 2 * (BM + BN) * 128;
-  static bool attr_set_dev[64] = {false};        // hipFuncSetAttribute is per device
-  int attr_dev_ = 0;
-  if (hipGetDevice(&attr_dev_) != hipSuccess || attr_dev_ < 0 || attr_dev_ >= 64) return SFM_ERR_LAUNCH;
-  bool& attr_set = attr_set_dev[attr_dev_];
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)gemm16w_kernel<T, BM, BN, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-      return SFM_ERR_LAUNCH;
-    attr_set = true;
-  }
   dim3 grid(p.nMt * p.nNt * p.B), block(NW * 64);
-  SFM_LAUNCH((gemm16w_kernel<T, BM, BN, NW>), grid, block, lds, stream, p);
+  SFM_LAUNCH_LDS((gemm16w_kernel<T, BM, BN, NW>), grid, block, lds, stream, p);
   return SFM_OK;
 }
 
@@ -760,17 +742,8 @@ template <class T, int BN, int STAGES, int BM>
 static int launch_v2(const Gemm2Params& p, hipStream_t stream) {
   constexpr int ring = STAGES * (BM + BN) * 128, image = 4 * 64 * (BN / 2 + 4) * 4;
   constexpr int lds = ring > image ? ring : image;
-  static bool attr_set_dev[64] = {false};        // hipFuncSetAttribute is per device
-  int attr_dev_ = 0;
-  if (hipGetDevice(&attr_dev_) != hipSuccess || attr_dev_ < 0 || attr_dev_ >= 64) return SFM_ERR_LAUNCH;
-  bool& attr_set = attr_set_dev[attr_dev_];
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)gemm16v2_kernel<T, BN, STAGES, BM>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-      return SFM_ERR_LAUNCH;
-    attr_set = true;
-  }
   dim3 grid(p.nMt * p.nNt * p.B), block(256);
-  SFM_LAUNCH((gemm16v2_kernel<T, BN, STAGES, BM>), grid, block, lds, stream, p);
+  SFM_LAUNCH_LDS((gemm16v2_kernel<T, BN, STAGES, BM>), grid, block, lds, stream, p);
   return SFM_OK;
 }
 

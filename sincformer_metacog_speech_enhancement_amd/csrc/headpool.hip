@@ -263,20 +263,10 @@ extern "C" int sfm_headpool(const void* xd, const void* W, const float* bias, vo
   const int w_bytes = NW * HP_K * 2;
   dim3 grid(B * P), block(512);
   hipStream_t st = (hipStream_t)stream;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return SFM_ERR_LAUNCH;
-  static bool attr_set[64][2] = {{false}};
-  const int ki = dtype == SFM_DT_F16 ? 1 : 0;
-  const void* fn = ki ? (const void*)headpool_kernel<F16> : (const void*)headpool_kernel<BF16>;
-  if (!attr_set[dev][ki]) {
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return SFM_ERR_LAUNCH;
-    attr_set[dev][ki] = true;
-  }
-  if (ki)
-    SFM_LAUNCH((headpool_kernel<F16>), grid, block, lds, st, (const u16*)xd, (const u16*)W, bias, (u16*)pooled, gn_partial, Tin, Tout, NW,
-               lda, ldp, fpt, P, gcols, w_bytes, (int)p_bytes);
-  else
-    SFM_LAUNCH((headpool_kernel<BF16>), grid, block, lds, st, (const u16*)xd, (const u16*)W, bias, (u16*)pooled, gn_partial, Tin, Tout, NW,
-               lda, ldp, fpt, P, gcols, w_bytes, (int)p_bytes);
+#define HP_GO(TT) SFM_LAUNCH_LDS((headpool_kernel<TT>), grid, block, lds, st, (const u16*)xd, (const u16*)W, bias, (u16*)pooled, gn_partial, \
+                                 Tin, Tout, NW, lda, ldp, fpt, P, gcols, w_bytes, (int)p_bytes)
+  if (dtype == SFM_DT_F16) HP_GO(F16);
+  else HP_GO(BF16);
+#undef HP_GO
   return SFM_OK;
 }

@@ -325,24 +325,11 @@ static int lin256_launch(const void* A, const float* X32, int ldx, const float* 
   const int other = f32o ? 2 : (out_dtype != dtype ? 1 : 0);
   dim3 grid((M + L2_BM - 1) / L2_BM), block(512);
   hipStream_t st = (hipStream_t)stream;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return SFM_ERR_LAUNCH;
-  static bool attr_set[64][24] = {{false}};
+  // (no kernel for an fp32 result with GLU or with the LayerNorm prologue: rejected above, and by the default below)
   const int ki = (has_ln ? 12 : 0) + (dtype == SFM_DT_F16 ? 6 : 0) + (glu ? 3 : 0) + other;
-#define L2_FN(TT, G, O, N) (const void*)lin256_kernel<TT, G, O, N>
-  const void* fns[24] = {L2_FN(BF16, 0, 0, 0), L2_FN(BF16, 0, 1, 0), L2_FN(BF16, 0, 2, 0), L2_FN(BF16, 1, 0, 0), L2_FN(BF16, 1, 1, 0), nullptr,
-                         L2_FN(F16, 0, 0, 0),  L2_FN(F16, 0, 1, 0),  L2_FN(F16, 0, 2, 0),  L2_FN(F16, 1, 0, 0),  L2_FN(F16, 1, 1, 0),  nullptr,
-                         L2_FN(BF16, 0, 0, 1), L2_FN(BF16, 0, 1, 1), nullptr, L2_FN(BF16, 1, 0, 1), L2_FN(BF16, 1, 1, 1), nullptr,
-                         L2_FN(F16, 0, 0, 1),  L2_FN(F16, 0, 1, 1),  nullptr, L2_FN(F16, 1, 0, 1),  L2_FN(F16, 1, 1, 1),  nullptr};
-#undef L2_FN
-  if (!fns[ki]) return SFM_ERR_SHAPE;
-  if (!attr_set[dev][ki]) {
-    if (hipFuncSetAttribute(fns[ki], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return SFM_ERR_LAUNCH;
-    attr_set[dev][ki] = true;
-  }
   const L2Ln ln = {X32, lnw, lnb, ldx, eps};
-#define L2_GO(TT, G, O, N) SFM_LAUNCH((lin256_kernel<TT, G, O, N>), grid, block, lds, st, (const u16*)A, (const u16*)W, bias, (u16*)out, \
-                                      M, NW, lda, ldo, (int)a_bytes, w_bytes, (int)o_bytes, ln)
+#define L2_GO(TT, G, O, N) SFM_LAUNCH_LDS((lin256_kernel<TT, G, O, N>), grid, block, lds, st, (const u16*)A, (const u16*)W, bias, (u16*)out, \
+                                          M, NW, lda, ldo, (int)a_bytes, w_bytes, (int)o_bytes, ln)
   switch (ki) {
     case 0: L2_GO(BF16, 0, 0, 0); break;
     case 1: L2_GO(BF16, 0, 1, 0); break;
@@ -361,7 +348,8 @@ static int lin256_launch(const void* A, const float* X32, int ldx, const float* 
     case 18: L2_GO(F16, 0, 0, 1); break;
     case 19: L2_GO(F16, 0, 1, 1); break;
     case 21: L2_GO(F16, 1, 0, 1); break;
-    default: L2_GO(F16, 1, 1, 1); break;
+    case 22: L2_GO(F16, 1, 1, 1); break;
+    default: return SFM_ERR_SHAPE;
   }
 #undef L2_GO
   return SFM_OK;

@@ -126,7 +126,6 @@ extern "C" int sfm_memory_fwd(const float* emb, const float* params, float* bias
     return SFM_ERR_SHAPE;
   SFM_LAUNCH(memory_fwd_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, emb, params, bias_out, gate_out,
                      top_idx, sim_out, key_dim, value_dim, slots, temperature);
-  SFM_CHECK_LAUNCH();
   return SFM_OK;
 }
 

@@ -112,7 +112,6 @@ extern "C" int sfm_layernorm(const float* x, const float* w, const float* b, voi
   else
     SFM_LAUNCH((layernorm_kernel<BF16>), grid, block, 0, (hipStream_t)stream, x, w, b, (u16*)out16, out32, M,
                        D, ldx, ld16, ld32, eps, act);
-  SFM_CHECK_LAUNCH();
   return SFM_OK;
 }
 
@@ -168,7 +167,6 @@ extern "C" int sfm_gn_finalize(const float* partial, const float* w, const float
   double count = (double)rows * (double)(C / G);
   SFM_LAUNCH(gn_finalize_kernel, dim3(G, B), dim3(64), 0, (hipStream_t)stream, partial, w, b, scale, shift, P,
                      G, C, count, eps);
-  SFM_CHECK_LAUNCH();
   return SFM_OK;
 }
 
@@ -309,7 +307,6 @@ extern "C" int sfm_gn_apply(const void* x1, const float* sc1, const float* sh1, 
   else
     SFM_LAUNCH((gn_apply_kernel<BF16>), dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, x1, sc1, sh1,
                        x2, sc2, sh2, out, rows_per_batch, C, total8, in_f32, out_f32, act);
-  SFM_CHECK_LAUNCH();
   return SFM_OK;
 }
 
@@ -578,18 +575,10 @@ template <int KS, bool VARLEN = false>
 static int launch_dwconv_dot(const void* x, const float* wT, const float* sc, const float* sh, void* out, int B, int Tn,
                              int C, int act, int out_f32, hipStream_t st, const int* frame_off = nullptr,
                              const int* tiles = nullptr, int n_tiles = 0) {
-  const int lds = (DW_TT + KS - 1) * C * 2;
-  static bool attr_dev[64] = {false};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return SFM_ERR_LAUNCH;
-  if (!attr_dev[dev]) {
-    if (hipFuncSetAttribute((const void*)dwconv_dot_kernel<KS, VARLEN>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-      return SFM_ERR_LAUNCH;
-    attr_dev[dev] = true;
-  }
+  const int lds = (DW_TT + KS - 1) * C * 2;                  // grows with C: the grant follows the widest launch so far
   const dim3 grid = VARLEN ? dim3(n_tiles, 1) : dim3((Tn + DW_TT - 1) / DW_TT, B);
-  SFM_LAUNCH((dwconv_dot_kernel<KS, VARLEN>), grid, dim3(256), lds, st, (const u16*)x, wT, sc, sh, out, Tn, C, act, out_f32,
-             frame_off, tiles);
+  SFM_LAUNCH_LDS((dwconv_dot_kernel<KS, VARLEN>), grid, dim3(256), lds, st, (const u16*)x, wT, sc, sh, out, Tn, C, act, out_f32,
+                 frame_off, tiles);
   return SFM_OK;
 }
 
@@ -597,19 +586,10 @@ template <class T, int KS, bool VARLEN = false>
 static int launch_dwconv_reg(const void* x, const float* wT, const float* sc, const float* sh, void* out, int B, int Tn,
                              int C, int act, int out_f32, hipStream_t st, const int* frame_off = nullptr,
                              const int* tiles = nullptr, int n_tiles = 0) {
-  const int lds = (DW_TT + KS - 1) * C * 2;
-  static bool attr_dev[64] = {false};                        // hipFuncSetAttribute is per device
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return SFM_ERR_LAUNCH;
-  bool& attr = attr_dev[dev];
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)dwconv_reg_kernel<T, KS, VARLEN>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-      return SFM_ERR_LAUNCH;
-    attr = true;
-  }
+  const int lds = (DW_TT + KS - 1) * C * 2;                  // as above
   const dim3 grid = VARLEN ? dim3(n_tiles, 1) : dim3((Tn + DW_TT - 1) / DW_TT, B);
-  SFM_LAUNCH((dwconv_reg_kernel<T, KS, VARLEN>), grid, dim3(256), lds, st, (const u16*)x, wT, sc, sh, out, Tn, C, act, out_f32,
-             frame_off, tiles);
+  SFM_LAUNCH_LDS((dwconv_reg_kernel<T, KS, VARLEN>), grid, dim3(256), lds, st, (const u16*)x, wT, sc, sh, out, Tn, C, act, out_f32,
+                 frame_off, tiles);
   return SFM_OK;
 }
 
@@ -647,6 +627,39 @@ __global__ __launch_bounds__(256) void dwconv_generic_kernel(const u16* __restri
   else reinterpret_cast<u16*>(out)[i] = T::from_f32(y);
 }
 
+// KS 7 / 31 with C in {32, 64, 128, 256, 512}: the shapes of the register-resident kernels
+static bool dwconv_reg_shape(int C, int KS) {
+  return (KS == 7 || KS == 31) && C % 8 == 0 && C <= 512 && (256 % (C / 2)) == 0 && (DW_TT / (256 / (C / 2))) % 4 == 0;
+}
+
+// The routing of sfm_dwconv_folded and of its packed form (VARLEN: Tn = 0, rows = sum_T, B utterances in frame_off): the
+// register-resident kernels on their shapes, the generic kernel on everything else.
+template <bool VARLEN>
+static int dwconv_folded_route(const void* x, const float* wT, const float* sc, const float* sh, void* out, int B, int Tn,
+                               long long rows, int C, int KS, int act, int out_f32, int dtype, hipStream_t st,
+                               const int* frame_off, const int* tiles, int n_tiles) {
+  if (!dwconv_reg_shape(C, KS)) {
+    const long long total = rows * C;
+    const long long nb = (total + 255) / 256;
+    if (nb > 0x7fffffffLL) return SFM_ERR_SHAPE;
+    if (dtype == SFM_DT_F16)
+      SFM_LAUNCH((dwconv_generic_kernel<F16, VARLEN>), dim3((unsigned)nb), dim3(256), 0, st, (const u16*)x, wT, sc, sh, out, Tn, C, KS,
+                 total, act, out_f32, frame_off, VARLEN ? B : 0);
+    else
+      SFM_LAUNCH((dwconv_generic_kernel<BF16, VARLEN>), dim3((unsigned)nb), dim3(256), 0, st, (const u16*)x, wT, sc, sh, out, Tn, C, KS,
+                 total, act, out_f32, frame_off, VARLEN ? B : 0);
+    return SFM_OK;
+  }
+  // fp16: the dot-product form (SFM_DWCONV_DOT=0 keeps the multiply-add kernel: the A/B knob)
+  static const int dot_on = getenv("SFM_DWCONV_DOT") ? atoi(getenv("SFM_DWCONV_DOT")) : 1;
+#define DW_GO(L) return L(x, wT, sc, sh, out, B, Tn, C, act, out_f32, st, frame_off, tiles, n_tiles)
+  if (KS == 31 && dtype == SFM_DT_F16 && dot_on) DW_GO((launch_dwconv_dot<31, VARLEN>));
+  if (KS == 31) { if (dtype == SFM_DT_F16) DW_GO((launch_dwconv_reg<F16, 31, VARLEN>)); else DW_GO((launch_dwconv_reg<BF16, 31, VARLEN>)); }
+  if (dtype == SFM_DT_F16) DW_GO((launch_dwconv_reg<F16, 7, VARLEN>));
+  DW_GO((launch_dwconv_reg<BF16, 7, VARLEN>));
+#undef DW_GO
+}
+
 // wT [KS][C] fp32 (transposed depthwise weights), sc/sh [C] = BatchNorm(eval) folded with the conv bias:
 // y = act ? swish(conv(x) * sc + sh) : conv(x) * sc + sh ; 16-bit or fp32 output.  KS odd; KS 7 / 31 with C in
 // {32, 64, 128, 256, 512} on the register-resident kernels, everything else on the generic one.
@@ -655,27 +668,8 @@ extern "C" int sfm_dwconv_folded(const void* x, const float* wT, const float* sc
   if (!x || !wT || !sc || !sh || !out) return SFM_ERR_ARG;
   if (B <= 0 || T <= 0 || C <= 0 || KS < 1 || (KS & 1) == 0) return SFM_ERR_SHAPE;
   if (dtype != SFM_DT_BF16 && dtype != SFM_DT_F16) return SFM_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  const bool reg = (KS == 7 || KS == 31) && C % 8 == 0 && C <= 512 && (256 % (C / 2)) == 0 && (DW_TT / (256 / (C / 2))) % 4 == 0;
-  if (!reg) {
-    const long long total = (long long)B * T * C;
-    const long long nb = (total + 255) / 256;
-    if (nb > 0x7fffffffLL) return SFM_ERR_SHAPE;
-    if (dtype == SFM_DT_F16)
-      SFM_LAUNCH((dwconv_generic_kernel<F16>), dim3((unsigned)nb), dim3(256), 0, st, (const u16*)x, wT, sc, sh, out, T, C, KS, total,
-                 act, out_f32);
-    else
-      SFM_LAUNCH((dwconv_generic_kernel<BF16>), dim3((unsigned)nb), dim3(256), 0, st, (const u16*)x, wT, sc, sh, out, T, C, KS, total,
-                 act, out_f32);
-    return SFM_OK;
-  }
-  // fp16: the dot-product form (SFM_DWCONV_DOT=0 keeps the multiply-add kernel: the A/B knob)
-  static const int dot_on = getenv("SFM_DWCONV_DOT") ? atoi(getenv("SFM_DWCONV_DOT")) : 1;
-  if (KS == 31 && dtype == SFM_DT_F16 && dot_on) return launch_dwconv_dot<31>(x, wT, sc, sh, out, B, T, C, act, out_f32, st);
-  if (KS == 31) return dtype == SFM_DT_F16 ? launch_dwconv_reg<F16, 31>(x, wT, sc, sh, out, B, T, C, act, out_f32, st)
-                                           : launch_dwconv_reg<BF16, 31>(x, wT, sc, sh, out, B, T, C, act, out_f32, st);
-  return dtype == SFM_DT_F16 ? launch_dwconv_reg<F16, 7>(x, wT, sc, sh, out, B, T, C, act, out_f32, st)
-                             : launch_dwconv_reg<BF16, 7>(x, wT, sc, sh, out, B, T, C, act, out_f32, st);
+  return dwconv_folded_route<false>(x, wT, sc, sh, out, B, T, (long long)B * T, C, KS, act, out_f32, dtype, (hipStream_t)stream,
+                                    nullptr, nullptr, 0);
 }
 
 // Packed (variable-length) form of sfm_dwconv_folded: x / out [sum_T, C] hold B utterances back to back, utterance u = rows
@@ -688,30 +682,12 @@ extern "C" int sfm_dwconv_folded_varlen(const void* x, const float* wT, const fl
   if (!x || !wT || !sc || !sh || !out || !frame_off) return SFM_ERR_ARG;
   if (B <= 0 || max_T <= 0 || sum_T < max_T || C <= 0 || KS < 1 || (KS & 1) == 0) return SFM_ERR_SHAPE;
   if (dtype != SFM_DT_BF16 && dtype != SFM_DT_F16) return SFM_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  const bool reg = (KS == 7 || KS == 31) && C % 8 == 0 && C <= 512 && (256 % (C / 2)) == 0 && (DW_TT / (256 / (C / 2))) % 4 == 0;
-  if (!reg) {
-    const long long total = (long long)sum_T * C;
-    const long long nb = (total + 255) / 256;
-    if (nb > 0x7fffffffLL) return SFM_ERR_SHAPE;
-    if (dtype == SFM_DT_F16)
-      SFM_LAUNCH((dwconv_generic_kernel<F16, true>), dim3((unsigned)nb), dim3(256), 0, st, (const u16*)x, wT, sc, sh, out, 0, C, KS,
-                 total, act, out_f32, frame_off, B);
-    else
-      SFM_LAUNCH((dwconv_generic_kernel<BF16, true>), dim3((unsigned)nb), dim3(256), 0, st, (const u16*)x, wT, sc, sh, out, 0, C, KS,
-                 total, act, out_f32, frame_off, B);
-    return SFM_OK;
+  if (dwconv_reg_shape(C, KS)) {                               // (only these kernels read the tile table)
+    if (!tiles) return SFM_ERR_ARG;
+    if (n_tiles < B || (long long)n_tiles > (long long)B * ((max_T + DW_TT - 1) / DW_TT)) return SFM_ERR_SHAPE;
   }
-  if (!tiles) return SFM_ERR_ARG;
-  if (n_tiles < B || (long long)n_tiles > (long long)B * ((max_T + DW_TT - 1) / DW_TT)) return SFM_ERR_SHAPE;
-  static const int dot_on = getenv("SFM_DWCONV_DOT") ? atoi(getenv("SFM_DWCONV_DOT")) : 1;      // as sfm_dwconv_folded
-  if (KS == 31 && dtype == SFM_DT_F16 && dot_on)
-    return launch_dwconv_dot<31, true>(x, wT, sc, sh, out, 0, 0, C, act, out_f32, st, frame_off, tiles, n_tiles);
-  if (KS == 31)
-    return dtype == SFM_DT_F16 ? launch_dwconv_reg<F16, 31, true>(x, wT, sc, sh, out, 0, 0, C, act, out_f32, st, frame_off, tiles, n_tiles)
-                               : launch_dwconv_reg<BF16, 31, true>(x, wT, sc, sh, out, 0, 0, C, act, out_f32, st, frame_off, tiles, n_tiles);
-  return dtype == SFM_DT_F16 ? launch_dwconv_reg<F16, 7, true>(x, wT, sc, sh, out, 0, 0, C, act, out_f32, st, frame_off, tiles, n_tiles)
-                             : launch_dwconv_reg<BF16, 7, true>(x, wT, sc, sh, out, 0, 0, C, act, out_f32, st, frame_off, tiles, n_tiles);
+  return dwconv_folded_route<true>(x, wT, sc, sh, out, B, 0, sum_T, C, KS, act, out_f32, dtype, (hipStream_t)stream, frame_off,
+                                   tiles, n_tiles);
 }
 
 extern "C" int sfm_dwconv_bn_swish(const void* x, const float* wdw, const float* bdw, const float* bnw,
@@ -720,22 +696,16 @@ extern "C" int sfm_dwconv_bn_swish(const void* x, const float* wdw, const float*
   if (!x || !wdw || !bdw || !bnw || !bnb || !bnm || !bnv || !out) return SFM_ERR_ARG;
   if (C % 8 != 0 || KS < 1 || (KS & 1) == 0 || B <= 0 || T <= 0) return SFM_ERR_SHAPE;
   size_t rows = DW_TT + KS - 1;
-  size_t lds = ((rows * C * 2 + 15) & ~(size_t)15) + ((size_t)KS * C + 2 * (size_t)C) * 4;
-  if (lds > 160 * 1024) return SFM_ERR_SHAPE;
+  size_t lds_sz = ((rows * C * 2 + 15) & ~(size_t)15) + ((size_t)KS * C + 2 * (size_t)C) * 4;
+  if (lds_sz > 160 * 1024) return SFM_ERR_SHAPE;
+  const int lds = (int)lds_sz;
   dim3 grid((T + DW_TT - 1) / DW_TT, B), block(256);
-  hipError_t e;
-  if (dtype == SFM_DT_F16) {
-    e = hipFuncSetAttribute((const void*)dwconv_bn_swish_kernel<F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return SFM_ERR_LAUNCH;
-    SFM_LAUNCH((dwconv_bn_swish_kernel<F16>), grid, block, lds, (hipStream_t)stream, (const u16*)x, wdw, bdw,
-                       bnw, bnb, bnm, bnv, (u16*)out, T, C, KS, eps);
-  } else {
-    e = hipFuncSetAttribute((const void*)dwconv_bn_swish_kernel<BF16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return SFM_ERR_LAUNCH;
-    SFM_LAUNCH((dwconv_bn_swish_kernel<BF16>), grid, block, lds, (hipStream_t)stream, (const u16*)x, wdw, bdw,
-                       bnw, bnb, bnm, bnv, (u16*)out, T, C, KS, eps);
-  }
-  SFM_CHECK_LAUNCH();
+  if (dtype == SFM_DT_F16)
+    SFM_LAUNCH_LDS((dwconv_bn_swish_kernel<F16>), grid, block, lds, (hipStream_t)stream, (const u16*)x, wdw, bdw,
+                   bnw, bnb, bnm, bnv, (u16*)out, T, C, KS, eps);
+  else
+    SFM_LAUNCH_LDS((dwconv_bn_swish_kernel<BF16>), grid, block, lds, (hipStream_t)stream, (const u16*)x, wdw, bdw,
+                   bnw, bnb, bnm, bnv, (u16*)out, T, C, KS, eps);
   return SFM_OK;
 }
 
@@ -798,7 +768,6 @@ extern "C" int sfm_convert_rows(const float* src, void* dst, long long M, int C,
   else
     SFM_LAUNCH((convert_rows_kernel<BF16>), dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, src,
                        (u16*)dst, M, C, Cz, ld_src, ld_dst);
-  SFM_CHECK_LAUNCH();
   return SFM_OK;
 }
 
@@ -845,7 +814,6 @@ extern "C" int sfm_transpose(const void* src, void* dst, int B, int R, int C, lo
   else
     SFM_LAUNCH((transpose_kernel<BF16>), grid, block, 0, (hipStream_t)stream, src, dst, R, C, src_batch,
                        src_row, dst_batch, dst_row, src_f32, dst_f32);
-  SFM_CHECK_LAUNCH();
   return SFM_OK;
 }
 
@@ -989,7 +957,6 @@ static int pool_time_go(const void* src, int srcfmt, const float* scale, const f
   if (dtype == SFM_DT_F16) POOL_SRC(F16) else POOL_SRC(BF16)
 #undef POOL_SRC
 #undef POOL_GO
-  SFM_CHECK_LAUNCH();
   return SFM_OK;
 }
 
@@ -1067,7 +1034,6 @@ extern "C" int sfm_pool_time_bwd(const float* dout, float* dsrc, int B, int Tin,
   dim3 grid(nv >= 256 ? (nv + 255) / 256 : 1, (unsigned)row_blocks, B), block(256);
   if (vec) SFM_LAUNCH((pool_time_bwd_kernel<4>), grid, block, 0, (hipStream_t)stream, dout, dsrc, Tin, Tout, C, ld_dout, ld_dsrc);
   else SFM_LAUNCH((pool_time_bwd_kernel<1>), grid, block, 0, (hipStream_t)stream, dout, dsrc, Tin, Tout, C, ld_dout, ld_dsrc);
-  SFM_CHECK_LAUNCH();
   return SFM_OK;
 }
 
@@ -1186,7 +1152,6 @@ extern "C" int sfm_stft_lognorm_bwd(const float* re, const float* im, const floa
   long long nb = (M * F + 255) / 256;
   if (nb > 16384) nb = 16384;
   SFM_LAUNCH(stft_lognorm_bwd_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, re, im, g, dre, dim_, M, F, ld_g);
-  SFM_CHECK_LAUNCH();
   return SFM_OK;
 }
 
@@ -1233,7 +1198,6 @@ extern "C" int sfm_polar_mask(const float* lm, const float* lp, const float* mag
   if (nb > 16384) nb = 16384;
   SFM_LAUNCH(polar_mask_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, lm, lp, mag_bias, nr, ni,
                      mr, mi, er, ei, mmag, rows_per_batch, F, total, phase_scale, ld_logits, ld_enh);
-  SFM_CHECK_LAUNCH();
   return SFM_OK;
 }
 
@@ -1256,7 +1220,6 @@ extern "C" int sfm_complex_mul(const float* sr, const float* si, const float* mr
   if (nb > 16384) nb = 16384;
   SFM_LAUNCH(complex_mul_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, sr, si, mr, mi, er, ei,
                      total);
-  SFM_CHECK_LAUNCH();
   return SFM_OK;
 }
 
@@ -1329,7 +1292,6 @@ extern "C" int sfm_istft_ola(const float* frames, const float* win2, float* out,
   if (B <= 0 || T <= 0 || L <= 0 || hop <= 0 || win <= 0 || win > n_fft) return SFM_ERR_SHAPE;
   SFM_LAUNCH(istft_ola_kernel, dim3((L + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, frames, win2, out,
                      T, L, n_fft, hop, win, ld_frames);
-  SFM_CHECK_LAUNCH();
   return SFM_OK;
 }
 
@@ -1356,7 +1318,6 @@ extern "C" int sfm_pack_spec(const float* re, const float* im, float* dst, long 
   if (nb > 16384) nb = 16384;
   SFM_LAUNCH(pack_spec_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, re, im, dst, M, F, ld,
                      ld_src);
-  SFM_CHECK_LAUNCH();
   return SFM_OK;
 }
 
@@ -1413,6 +1374,5 @@ extern "C" int sfm_sinc_filters(const float* low_hz, const float* band_hz, const
   if (C <= 0 || K <= 0 || K > 512 || (K & 1) == 0 || (Wt && Npad < C)) return SFM_ERR_SHAPE;
   SFM_LAUNCH(sinc_filters_kernel, dim3(C), dim3(256), 0, (hipStream_t)stream, low_hz, band_hz, window, n_, filt,
                      Wt, C, K, Npad, sample_rate, min_low_hz, min_band_hz);
-  SFM_CHECK_LAUNCH();
   return SFM_OK;
 }

@@ -7,6 +7,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
+#include <mutex>
 
 #define SFM_OK 0
 #define SFM_ERR_ARG -1
@@ -216,7 +218,50 @@ __device__ __forceinline__ int sfm_seg_find(const int* __restrict__ off, int n, 
     hipLaunchKernelGGL(kernel, grid, block, shmem, stream, __VA_ARGS__);       \
     if (hipGetLastError() != hipSuccess) return SFM_ERR_LAUNCH;                \
   } while (0)
-#define SFM_CHECK_LAUNCH() do { } while (0)
+
+// ---- dynamic LDS above the default has to be granted per (kernel, device) before the launch -----------------------------------
+// sfm_grant_lds<kernel>(bytes): the current device's grant for this kernel instantiation is at least `bytes` on return.
+// granted[] is the largest size set so far, so a launcher whose size depends on a run-time argument (FF, C) grows the grant
+// when a later call needs more; the steady state costs one hipGetDevice and one load.  Launchers run on the caller's thread
+// and on autograd's: the record is atomic and the grant is only ever raised, under the lock.
+static inline int sfm_device(int* dev) {
+  return (hipGetDevice(dev) == hipSuccess && *dev >= 0 && *dev < 64) ? SFM_OK : SFM_ERR_LAUNCH;
+}
+template <auto Kernel>
+static int sfm_grant_lds(int bytes) {
+  static std::atomic<int> granted[64];
+  static std::mutex raise;
+  int dev = 0;
+  if (sfm_device(&dev) != SFM_OK) return SFM_ERR_LAUNCH;
+  if (bytes <= granted[dev].load(std::memory_order_acquire)) return SFM_OK;
+  std::lock_guard<std::mutex> lock(raise);
+  if (bytes <= granted[dev].load(std::memory_order_relaxed)) return SFM_OK;
+  if (hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess)
+    return SFM_ERR_LAUNCH;
+  granted[dev].store(bytes, std::memory_order_release);
+  return SFM_OK;
+}
+#define SFM_LAUNCH_LDS(kernel, grid, block, shmem, stream, ...)                \
+  do {                                                                         \
+    if (sfm_grant_lds<kernel>(shmem) != SFM_OK) return SFM_ERR_LAUNCH;         \
+    SFM_LAUNCH(kernel, grid, block, shmem, stream, __VA_ARGS__);               \
+  } while (0)
+
+// CUs of the current device (the persistent kernels size their grids by it); 256 if the runtime reports none, 0 on error.
+// (inline, not static: one cache for the whole library)
+inline int sfm_cu_count() {
+  static std::atomic<int> ncu[64];
+  int dev = 0;
+  if (sfm_device(&dev) != SFM_OK) return 0;
+  int n = ncu[dev].load(std::memory_order_relaxed);
+  if (n == 0) {
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
+    n = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    ncu[dev].store(n, std::memory_order_relaxed);
+  }
+  return n;
+}
 
 // reduce.hip: the ordered second pass of the split reductions (deterministic training step).  ws [S][rows][cols] compact.
 // (ws is used as scratch by the multi-level fold: its contents are destroyed)

@@ -179,17 +179,9 @@ extern "C" int sfm_sinc_fir16_tiles(int L) {
 template <class T, int PASSES>
 static int sinc_fir16_go(const float* wave, const float* filt, void* wsh, void* out, float* gn_partial, int L, int K, int out_f32,
                          dim3 grid, int lds, int tpb, hipStream_t st) {
-  static bool attr_set_dev[64] = {false};              // hipFuncSetAttribute is per device
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return SFM_ERR_LAUNCH;
-  if (!attr_set_dev[dev]) {
-    if (hipFuncSetAttribute((const void*)sinc_fir16_kernel<T, PASSES>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-      return SFM_ERR_LAUNCH;
-    attr_set_dev[dev] = true;
-  }
   SFM_LAUNCH((sinc_fir16_prep_kernel<T>), dim3(8, FIR_C), dim3(256), 0, st, filt, (u16*)wsh, K);
-  SFM_LAUNCH((sinc_fir16_kernel<T, PASSES>), grid, dim3(FIR_WAVES * 64), lds, st, wave, (const u16*)wsh, out, gn_partial, L, K / 2,
-             out_f32, tpb);
+  SFM_LAUNCH_LDS((sinc_fir16_kernel<T, PASSES>), grid, dim3(FIR_WAVES * 64), lds, st, wave, (const u16*)wsh, out, gn_partial, L,
+                 K / 2, out_f32, tpb);
   return SFM_OK;
 }
 
