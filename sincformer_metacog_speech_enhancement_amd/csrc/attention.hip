@@ -334,49 +334,13 @@ __device__ __forceinline__ float xhalf_sum(float v) {
   return lo + hi;
 }
 
-// ---- ablation hooks of the ring kernel (diagnostic builds only: -DSFM_ABL=n; results are then WRONG on purpose) ----
-#ifndef SFM_ABL
-#define SFM_ABL 0
-#endif
-#if SFM_ABL == 1
-#define SFM_ABL_EXP(x) (x)
-#else
-#define SFM_ABL_EXP(x) __builtin_amdgcn_exp2f(x)
-#endif
-#if SFM_ABL == 13
-#define SFM_ABL_ROWMAX(sn) ([&]() { float m_ = fmaxf(sn[0], sn[1]); _Pragma("unroll") for (int r = 2; r < 16; ++r) m_ = fmaxf(m_, sn[r]); return m_; }())
-#else
-#define SFM_ABL_ROWMAX(sn) ([&]() { float m_ = sfm_max2_raw(sn[0], sn[1]); _Pragma("unroll") for (int r = 2; r < 16; r += 2) m_ = sfm_max3_raw(m_, sn[r], sn[r + 1]); return m_; }())
-#endif
-#if SFM_ABL == 5
-#define SFM_ABL_LACC(x)
-#else
-#define SFM_ABL_LACC(x) x
-#endif
-#if SFM_ABL == 4
-#define SFM_ABL_SCHED
-#else
-#define SFM_ABL_SCHED                                                                                                  \
-  _Pragma("unroll") for (int g_ = 0; g_ < 11; ++g_) {                                                                  \
-    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                                                 \
-    __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);                                                                 \
-  }
-#endif
-#if SFM_ABL == 10
-#define SFM_ABL_STORE_AUX 17
-#else
-#define SFM_ABL_STORE_AUX 0
-#endif
-#if SFM_ABL == 11
-#define SFM_ABL_STAGGER() do { if (wave >= 4) __builtin_amdgcn_s_sleep(6); } while (0)
-#else
-#define SFM_ABL_STAGGER() do { } while (0)
-#endif
-#if SFM_ABL == 3
-#define SFM_ABL_SYNC()
-#else
-#define SFM_ABL_SYNC() do { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); } while (0)
-#endif
+// maximum of a lane's 16 accumulator values: one v_max_f32, then seven v_max3_f32
+__device__ __forceinline__ float attn_row_max16(const f32x16& sn) {
+  float m = sfm_max2_raw(sn[0], sn[1]);
+#pragma unroll
+  for (int r = 2; r < 16; r += 2) m = sfm_max3_raw(m, sn[r], sn[r + 1]);
+  return m;
+}
 
 typedef __attribute__((address_space(3))) void* attn_lds_ptr_t;
 
@@ -501,21 +465,24 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_hd64r_kernel(const u16* __res
       u32x4 pf[2];                                                                                                    \
       _Pragma("unroll") for (int s2 = 0; s2 < 2; ++s2) {                                                              \
         float e_[8];                                                                                                  \
-        _Pragma("unroll") for (int r = 0; r < 8; ++r) e_[r] = SFM_ABL_EXP(s[V_][8 * s2 + r]);                         \
+        _Pragma("unroll") for (int r = 0; r < 8; ++r) e_[r] = __builtin_amdgcn_exp2f(s[V_][8 * s2 + r]);              \
         pf[s2][0] = pack2<T>(e_[0], e_[1]);                                                                           \
         pf[s2][1] = pack2<T>(e_[2], e_[3]);                                                                           \
         pf[s2][2] = pack2<T>(e_[4], e_[5]);                                                                           \
         pf[s2][3] = pack2<T>(e_[6], e_[7]);                                                                           \
       }                                                                                                               \
       _Pragma("unroll") for (int s2 = 0; s2 < 2; ++s2) {                                                              \
-        SFM_ABL_LACC(lacc[V_] = T::mfma(vones, pf[s2], lacc[V_]);)                                                    \
+        lacc[V_] = T::mfma(vones, pf[s2], lacc[V_]);                                                                  \
         o[V_][0] = T::mfma(SFM_VF(s2, 0), pf[s2], o[V_][0]);                                                              \
         o[V_][1] = T::mfma(SFM_VF(s2, 1), pf[s2], o[V_][1]);                                                              \
       }                                                                                                               \
     }                                                                                                                 \
-    float mx = SFM_ABL_ROWMAX(sn);                                                                                    \
+    float mx = attn_row_max16(sn);                                                                                    \
     mx = xhalf_max(mx);                                                                                               \
-    SFM_ABL_SCHED                                                                                                     \
+    _Pragma("unroll") for (int g_ = 0; g_ < 11; ++g_) {                                                               \
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                                              \
+      __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);                                                              \
+    }                                                                                                                 \
     if ((FIRST) || __any(mx > DEFER_THR)) {                                                                           \
       const float want = m_run[U] + mx;                                                                               \
       const float hi = T::to_f32(T::from_f32(want));                                                                  \
@@ -572,23 +539,14 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_hd64r_kernel(const u16* __res
       const int c = ln + 64 * i;
       const int row = c >> 3, ch = c & 7;
       const u32x4 v = *reinterpret_cast<const u32x4*>(ob + row * 128 + ((ch ^ ((row >> 1) & 7)) << 4));
-      __builtin_amdgcn_raw_buffer_store_b128(v, ors, (qbase + row) * ldo * 2 + h * 128 + ch * 16, 0, SFM_ABL_STORE_AUX);
+      __builtin_amdgcn_raw_buffer_store_b128(v, ors, (qbase + row) * ldo * 2 + h * 128 + ch * 16, 0, 0);
     }
     st_item = -1;
   };
 
-#if SFM_ABL == 9
-  // diagnostic build: lse_out is a stamp buffer, 8 x uint64 per workgroup: start, end, end of items 0..5 (100 MHz ticks)
-  unsigned long long* dbg = reinterpret_cast<unsigned long long*>(lse_out) + (size_t)blockIdx.x * 8;
-  if (tid == 0) dbg[0] = __builtin_amdgcn_s_memrealtime();
-  int dbg_k = 0;
-  lse_out = nullptr;
-#endif
-#if SFM_ABL != 12
   // the second-dispatched half of the workgroup loses the VALU arbitration against its SIMD partner on every segment
   // (priority, then age): one static s_setprio for that half (+1.5 %; `wave` is wave-uniform by readfirstlane)
   if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-#endif
   int gcount = 0;                                                   // groups consumed so far by this workgroup (ring parity)
   if ((int)blockIdx.x < n_items) {
     issue_q(blockIdx.x);
@@ -601,8 +559,8 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_hd64r_kernel(const u16* __res
     for (int g = 0; g < ngrp; ++g) {
       // ---- group boundary: this wave's pieces of group g have landed (vmcnt), everyone's have and everyone is done with
       //      group g-1 (barrier): refill that half with the next group of this item or group 0 of the next item ----
-      SFM_ABL_SYNC();
-      SFM_ABL_STAGGER();
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
       const int half = gcount & 1;
       if (g + 1 < ngrp) issue_group(item, g + 1, half ^ 1);
       else if (item + (int)gridDim.x < n_items) issue_group(item + gridDim.x, 0, half ^ 1);
@@ -702,17 +660,10 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_hd64r_kernel(const u16* __res
         }
     }
     st_item = item;
-#if SFM_ABL == 9
-    if (tid == 0 && dbg_k < 6) dbg[2 + dbg_k] = __builtin_amdgcn_s_memrealtime();
-    ++dbg_k;
-#endif
   }
 #undef SFM_ATTN_RITEM
 #undef SFM_VF
   store_o();
-#if SFM_ABL == 9
-  if (tid == 0) dbg[1] = __builtin_amdgcn_s_memrealtime();
-#endif
 }
 
 // ---------------------------------------------------------------------------

@@ -27,20 +27,8 @@
 //   * K fragments of step s+1 and V^T fragments of step s are read from LDS under the second ritem of step s (inline asm,
 //     counted lgkmcnt): no LDS latency in front of an MFMA chain.
 #include "sfm_common.h"
-#include <stdlib.h>
 
-#ifndef SFM_ATTNP_ABL
-#define SFM_ATTNP_ABL 0
-#endif
 typedef __attribute__((address_space(3))) void* attnp_lds_ptr_t;
-
-// timing experiments (results wrong): SFM_ATTNP_ABL 9 = the 16 exponentials of a ritem replaced by plain VALU adds (what do the
-// quarter-rate transcendentals cost?), 10 = no LDS fragment reads inside the step loop (stale K / V^T fragments), 11 = both
-#if SFM_ATTNP_ABL == 9 || SFM_ATTNP_ABL == 11
-#define ATTNP_EXP2(x) __builtin_amdgcn_fmed3f((x), 0.0f, 0.25f)      /* one plain VALU op, values stay below the rescale threshold */
-#else
-#define ATTNP_EXP2(x) __builtin_amdgcn_exp2f(x)
-#endif
 
 __device__ __forceinline__ float attnp_xhalf_max(float v) {
   // v_permlane32_swap exchanges lanes 32-63 of its first operand with lanes 0-31 of the second (s_nop: VALU write -> swap)
@@ -56,22 +44,6 @@ __device__ __forceinline__ uint32_t attnp_pack2_o(float lo, float hi, bool other
 }
 
 #define ATTNP_HEADROOM 3.0f
-
-// diagnostic build (-DSFM_ATTNP_STAMPS, tools/attnp_stamps.py): lse_out becomes a stamp buffer, 8 x uint64 per wave:
-// kernel start, kernel end, and the sums of s_memtime differences over [wait + barrier], [group-0 prologue], [step loops],
-// [drain + normalise].  No stamp executes in the real kernel.
-#ifdef SFM_ATTNP_STAMPS
-__device__ __forceinline__ unsigned long long attnp_stamp() {
-  unsigned long long t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : : "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-#define ATTNP_T(...) __VA_ARGS__
-#else
-#define ATTNP_T(...)
-#endif
 
 // NW = waves per workgroup (8: one workgroup per CU, items of 512 query rows, ring of 3 x 2 key tiles; 4: TWO workgroups per
 // CU, items of 256 query rows, ring of 3 x 1 key tile, 80 KB of LDS each - the two waves of a SIMD then belong to different
@@ -98,12 +70,6 @@ __device__ __forceinline__ void attnp_body(const u16* __restrict__ qkv, u16* __r
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-#if defined(SFM_ATTNP_STAGGER)
-  // timing experiment: the second resident workgroup of a CU starts SFM_ATTNP_STAGGER x 1024 cycles late, so that the two
-  // workgroups' item epilogues do not coincide
-  if (NW == 4 && blockIdx.x >= gridDim.x / 2)
-    for (int i = 0; i < SFM_ATTNP_STAGGER; ++i) __builtin_amdgcn_s_sleep(16);
-#endif
   const int hl = lane >> 5, l31 = lane & 31;
   const int nkt = (Tlen + 63) >> 6, ngrp = (nkt + GT - 1) / GT, nsteps = (Tlen + 31) >> 5;
   const int rec_bytes = Tlen * ldqkv * 2;                          // keys / queries >= Tlen are out of range: read as zero
@@ -221,7 +187,7 @@ __device__ __forceinline__ void attnp_body(const u16* __restrict__ qkv, u16* __r
   {                                                                                                                    \
     _Pragma("unroll") for (int s2 = 0; s2 < 2; ++s2) {                                                                 \
       float e_[8];                                                                                                     \
-      _Pragma("unroll") for (int r = 0; r < 8; ++r) e_[r] = ATTNP_EXP2(s[X][8 * s2 + r]);                              \
+      _Pragma("unroll") for (int r = 0; r < 8; ++r) e_[r] = __builtin_amdgcn_exp2f(s[X][8 * s2 + r]);                  \
       pf[X][s2][0] = pack2<T>(e_[0], e_[1]);                                                                           \
       pf[X][s2][1] = pack2<T>(e_[2], e_[3]);                                                                           \
       pf[X][s2][2] = pack2<T>(e_[4], e_[5]);                                                                           \
@@ -319,52 +285,41 @@ __device__ __forceinline__ void attnp_body(const u16* __restrict__ qkv, u16* __r
   asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(vt[1][0][0]), "+v"(vt[1][0][1]), "+v"(vt[1][1][0]), "+v"(vt[1][1][1]) : : "memory")
 #define ATTNP_SB() __builtin_amdgcn_sched_barrier(0);
 #define ATTNP_SG(mask, n) __builtin_amdgcn_sched_group_barrier(mask, n, 0);
-#if SFM_ATTNP_ABL == 8
-#define ATTNP_AUG(U) zero
-#else
-#define ATTNP_AUG(U) T::mfma(ka, qa[U], zero)
-#endif
-#if SFM_ATTNP_ABL == 10 || SFM_ATTNP_ABL == 11
-#define ATTNP_IFRD(C) false
-#else
-#define ATTNP_IFRD(C) (C)
-#endif
 #define ATTNP_RITEM(U, STEP, AFIRST, KPRE, KSB, VLO, VSB, VHSB, FORCE)                                                 \
   {                                                                                                                    \
     constexpr int V_ = ((U) + SB - 1) % SB;                                                                            \
     const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};              \
     float e_[16];                                                                                                      \
-    ATTNP_PRIO(U)                                                                                                      \
     ATTNP_SB()                                                                                                         \
     /* ---- the S chain: augmented k-step, then the four d-slices; 12 exponentials and 4 converts beside it ---- */    \
-    f32x16 sn = ATTNP_AUG(U);                                                                                          \
-    _Pragma("unroll") for (int r = 0; r < 3; ++r) e_[r] = ATTNP_EXP2(s[V_][r]);                                        \
+    f32x16 sn = T::mfma(ka, qa[U], zero);                                                                              \
+    _Pragma("unroll") for (int r = 0; r < 3; ++r) e_[r] = __builtin_amdgcn_exp2f(s[V_][r]);                            \
     ATTNP_SG(0x008, 1) ATTNP_SG(0x400, 3)                                                                              \
     ATTNP_SB()                                                                                                         \
     if (AFIRST) ATTNP_KF_WAIT(4);                                                                                      \
     sn = T::mfma(kf[0], qf[U][0], sn);                                                                                 \
-    if (ATTNP_IFRD(KPRE)) ATTNP_RD_K(0, KSB, sn);                                                                          \
-    if (ATTNP_IFRD(AFIRST)) ATTNP_RD_V(1, 0, 0, VHSB, sn);                                                                 \
-    _Pragma("unroll") for (int r = 3; r < 6; ++r) e_[r] = ATTNP_EXP2(s[V_][r]);                                        \
+    if (KPRE) ATTNP_RD_K(0, KSB, sn);                                                                                  \
+    if (AFIRST) ATTNP_RD_V(1, 0, 0, VHSB, sn);                                                                         \
+    _Pragma("unroll") for (int r = 3; r < 6; ++r) e_[r] = __builtin_amdgcn_exp2f(s[V_][r]);                            \
     ATTNP_SG(0x008, 1) ATTNP_SG(0x400, 3)                                                                              \
     ATTNP_SB()                                                                                                         \
-    if (SFM_ATTNP_ABL != 13) sn = T::mfma(kf[1], qf[U][1], sn);                                                        \
-    if (ATTNP_IFRD(KPRE)) ATTNP_RD_K(1, KSB, sn);                                                                          \
-    if (ATTNP_IFRD(AFIRST)) ATTNP_RD_V(1, 0, 1, VHSB, sn);                                                                 \
-    _Pragma("unroll") for (int r = 6; r < 9; ++r) e_[r] = ATTNP_EXP2(s[V_][r]);                                        \
+    sn = T::mfma(kf[1], qf[U][1], sn);                                                                                 \
+    if (KPRE) ATTNP_RD_K(1, KSB, sn);                                                                                  \
+    if (AFIRST) ATTNP_RD_V(1, 0, 1, VHSB, sn);                                                                         \
+    _Pragma("unroll") for (int r = 6; r < 9; ++r) e_[r] = __builtin_amdgcn_exp2f(s[V_][r]);                            \
     ATTNP_SG(0x008, 1) ATTNP_SG(0x400, 3)                                                                              \
     ATTNP_SB()                                                                                                         \
-    if (SFM_ATTNP_ABL != 13) sn = T::mfma(kf[2], qf[U][2], sn);                                                        \
-    if (ATTNP_IFRD(KPRE)) ATTNP_RD_K(2, KSB, sn);                                                                          \
-    if (ATTNP_IFRD(AFIRST)) ATTNP_RD_V(1, 1, 0, VHSB, sn);                                                                 \
-    _Pragma("unroll") for (int r = 9; r < 12; ++r) e_[r] = ATTNP_EXP2(s[V_][r]);                                       \
+    sn = T::mfma(kf[2], qf[U][2], sn);                                                                                 \
+    if (KPRE) ATTNP_RD_K(2, KSB, sn);                                                                                  \
+    if (AFIRST) ATTNP_RD_V(1, 1, 0, VHSB, sn);                                                                         \
+    _Pragma("unroll") for (int r = 9; r < 12; ++r) e_[r] = __builtin_amdgcn_exp2f(s[V_][r]);                           \
     pf[V_][0][0] = pack2<T>(e_[0], e_[1]);                                                                             \
     pf[V_][0][1] = pack2<T>(e_[2], e_[3]);                                                                             \
     ATTNP_SG(0x008, 1) ATTNP_SG(0x400, 3) ATTNP_SG(0x002, 2)                                                           \
     ATTNP_SB()                                                                                                         \
-    if (SFM_ATTNP_ABL != 13) sn = T::mfma(kf[3], qf[U][3], sn);                                                        \
-    if (ATTNP_IFRD(KPRE)) ATTNP_RD_K(3, KSB, sn);                                                                          \
-    if (ATTNP_IFRD(AFIRST)) ATTNP_RD_V(1, 1, 1, VHSB, sn);                                                                 \
+    sn = T::mfma(kf[3], qf[U][3], sn);                                                                                 \
+    if (KPRE) ATTNP_RD_K(3, KSB, sn);                                                                                  \
+    if (AFIRST) ATTNP_RD_V(1, 1, 1, VHSB, sn);                                                                         \
     pf[V_][0][2] = pack2<T>(e_[4], e_[5]);                                                                             \
     pf[V_][0][3] = pack2<T>(e_[6], e_[7]);                                                                             \
     ATTNP_SG(0x008, 1) ATTNP_SG(0x002, 2)                                                                              \
@@ -375,11 +330,11 @@ __device__ __forceinline__ void attnp_body(const u16* __restrict__ qkv, u16* __r
     /* ---- PV of the pending block, the remaining exponentials, the overflow test ---- */                             \
     if (AFIRST) ATTNP_VT_WAIT_LO();                                                                                    \
     ATTNP_MFMA_L(lacc[U], pf[U][0])                                                                                    \
-    e_[12] = ATTNP_EXP2(s[V_][12]);                                                                                    \
+    e_[12] = __builtin_amdgcn_exp2f(s[V_][12]);                                                                        \
     ATTNP_SG(0x008, 1) ATTNP_SG(0x400, 1)                                                                              \
     ATTNP_SB()                                                                                                         \
     ATTNP_MFMA_O(o[U][0], ATTNP_VF(0, 0), pf[U][0])                                                                    \
-    _Pragma("unroll") for (int r = 13; r < 16; ++r) e_[r] = ATTNP_EXP2(s[V_][r]);                                      \
+    _Pragma("unroll") for (int r = 13; r < 16; ++r) e_[r] = __builtin_amdgcn_exp2f(s[V_][r]);                          \
     ATTNP_SG(0x008, 1) ATTNP_SG(0x400, 3)                                                                              \
     ATTNP_SB()                                                                                                         \
     ATTNP_MFMA_O(o[U][1], ATTNP_VF(0, 1), pf[U][0])                                                                    \
@@ -391,12 +346,12 @@ __device__ __forceinline__ void attnp_body(const u16* __restrict__ qkv, u16* __r
     ATTNP_SB()                                                                                                         \
     if (AFIRST) ATTNP_VT_WAIT_HI();                                                                                    \
     ATTNP_MFMA_L(lacc[U], pf[U][1])                                                                                    \
-    if (ATTNP_IFRD(VLO)) { ATTNP_RD_V_O(0, 0, 0, VSB, lacc[U]) ATTNP_RD_V_O(0, 0, 1, VSB, lacc[U]) }                                       \
+    if (VLO) { ATTNP_RD_V_O(0, 0, 0, VSB, lacc[U]) ATTNP_RD_V_O(0, 0, 1, VSB, lacc[U]) }                               \
     uint32_t flag_ = (pf[V_][0][0] | pf[V_][0][1] | pf[V_][0][2]) | (pf[V_][0][3] | pf[V_][1][0] | pf[V_][1][1]);      \
     ATTNP_SG(0x008, 1) ATTNP_SG(0x002, 2)                                                                              \
     ATTNP_SB()                                                                                                         \
     ATTNP_MFMA_O(o[U][0], ATTNP_VF(1, 0), pf[U][1])                                                                    \
-    if (ATTNP_IFRD(VLO)) { ATTNP_RD_V_O(0, 1, 0, VSB, o[U][0]) ATTNP_RD_V_O(0, 1, 1, VSB, o[U][0]) }                                       \
+    if (VLO) { ATTNP_RD_V_O(0, 1, 0, VSB, o[U][0]) ATTNP_RD_V_O(0, 1, 1, VSB, o[U][0]) }                               \
     flag_ |= pf[V_][1][2] | pf[V_][1][3];                                                                              \
     ATTNP_SG(0x008, 1) ATTNP_SG(0x002, 1)                                                                              \
     ATTNP_SB()                                                                                                         \
@@ -405,16 +360,9 @@ __device__ __forceinline__ void attnp_body(const u16* __restrict__ qkv, u16* __r
     s[U] = sn;                                                                                                         \
     /* the forced case enters through the same data-dependent test (a short-circuit on FORCE lets the compiler sink the   \
        exponentials out of this block, behind the branch) */                                                           \
-    if (__any((((SFM_ATTNP_ABL == 8) ? (flag_ & 0u) : flag_) | ((FORCE) ? 0x4000u : 0u)) & 0x40004000u) != 0u)          \
+    if (__any((flag_ | ((FORCE) ? 0x4000u : 0u)) & 0x40004000u) != 0u)                                                 \
       ATTNP_RESCALE(V_, FORCE)                                                                                         \
   }
-
-#if SFM_ATTNP_ABL == 2
-  // experiment: the two waves of a SIMD take turns at priority 1, one ritem each
-#define ATTNP_PRIO(U) if ((wave >= 4) == ((U) == 1)) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);
-#else
-#define ATTNP_PRIO(U)
-#endif
 
   // ---- O of the finished item: transposed through the wave's own 8 KB of the Q region (the next item's Q fragments have
   //      been read out of it) so that every store instruction writes 8 whole 128-byte rows ----
@@ -508,9 +456,7 @@ __device__ __forceinline__ void attnp_body(const u16* __restrict__ qkv, u16* __r
   };
 
   // the second-dispatched half of the workgroup loses the VALU arbitration against its SIMD partner (priority, then age)
-#if SFM_ATTNP_ABL != 1 && SFM_ATTNP_ABL != 2
   if (NW == 8 && wave >= 4) __builtin_amdgcn_s_setprio(1);
-#endif
   // ring bookkeeping: `cslot` = slot of the group being consumed; the prefetch cursor (p_item, p_g, pslot) names the next
   // group to fetch; it runs two groups ahead of the consumer
   // XCD-aware item order: workgroups are dealt round-robin over the 8 XCDs; give each XCD a contiguous run of virtual ids so
@@ -540,15 +486,12 @@ __device__ __forceinline__ void attnp_body(const u16* __restrict__ qkv, u16* __r
   }
   const int pad_step = (Tlen & 31) ? nsteps - 1 : -1;               // the only step that can contain padding keys
   ka = u32x4{hl == 0 ? ones2k : 0u, 0u, 0u, 0u};
-  ATTNP_T(unsigned long long t_bar = 0, t_pre = 0, t_steps = 0, t_post = 0, t_last = 0, t_q = 0, t_so = 0, t_dr = 0; const unsigned long long t_start = attnp_stamp();
-          unsigned long long* dbg = reinterpret_cast<unsigned long long*>(lse_out) + ((size_t)blockIdx.x * NW + wave) * 8; lse_out = nullptr;)
 
   // ---- group boundary: this wave's pieces of the group to consume have landed - counted vmcnt: the `inflight` youngest
   //      operations (this wave's refill of another slot, Q prefetch, O stores; all issued after those pieces) may stay in
   //      flight - then everyone's have (barrier; its lgkmcnt(0) also covers the V^T reads of the last step, issued before).
   //      Then the K fragments of the group's first step. ----
 #define ATTNP_BOUNDARY()                                                                                               \
-  ATTNP_T(const unsigned long long tb0_ = attnp_stamp();)                                                              \
   if (inflight >= 32) asm volatile("s_waitcnt vmcnt(32) lgkmcnt(0)" ::: "memory");                                     \
   else if (inflight >= 24) asm volatile("s_waitcnt vmcnt(24) lgkmcnt(0)" ::: "memory");                                \
   else if (inflight >= 16) asm volatile("s_waitcnt vmcnt(16) lgkmcnt(0)" ::: "memory");                                \
@@ -559,13 +502,11 @@ __device__ __forceinline__ void attnp_body(const u16* __restrict__ qkv, u16* __r
   __builtin_amdgcn_s_barrier();            /* raw: __syncthreads() would drain vmcnt to 0 (refill and O stores in flight) */ \
   asm volatile("" ::: "memory");                                                                                       \
   inflight = 0;                                                                                                        \
-  ATTNP_T(const unsigned long long tb1_ = attnp_stamp(); t_bar += tb1_ - tb0_;)                                        \
   load_kf(cslot * GT * SLOT);
   // the steps of group `g` (the K prefetch of a step beyond the group reads stale ring / Q-region bytes that are never
   // used: the next group's first fragments are read after its barrier)
 #define ATTNP_STEPS()                                                                                                  \
   ATTNP_KF_WAIT(0);                                                                                                    \
-  ATTNP_T(const unsigned long long ts0_ = attnp_stamp();)                                                              \
   {                                                                                                                    \
     const int step_end = min(nsteps, (g + 1) * 2 * GT);                                                                \
     for (int step = g * 2 * GT; step < step_end; ++step) {                                                             \
@@ -589,7 +530,6 @@ __device__ __forceinline__ void attnp_body(const u16* __restrict__ qkv, u16* __r
       vprev = sbk;                                                                                                     \
     }                                                                                                                  \
   }                                                                                                                    \
-  ATTNP_T(t_last = attnp_stamp(); t_steps += t_last - ts0_;)
 
   for (int item = vid; item < n_items; item += gridDim.x) {
     const int qt = item % nqt, bh = item / nqt;
@@ -635,9 +575,8 @@ __device__ __forceinline__ void attnp_body(const u16* __restrict__ qkv, u16* __r
       ATTNP_EXP_PACK(SB - 1, flag_)
       const bool force1 = nsteps == 1;
       if (__any(((flag_ | (force1 ? 0x4000u : 0u)) & 0x40004000u) != 0u)) ATTNP_RESCALE(SB - 1, force1)
-      if (ATTNP_IFRD(true)) {                                       // second half of the last step's V^T
-        ATTNP_RD_V_O(1, 0, 0, vprev, lacc[0]) ATTNP_RD_V_O(1, 0, 1, vprev, lacc[0]) ATTNP_RD_V_O(1, 1, 0, vprev, lacc[0]) ATTNP_RD_V_O(1, 1, 1, vprev, lacc[0])
-      }
+      // second half of the last step's V^T
+      ATTNP_RD_V_O(1, 0, 0, vprev, lacc[0]) ATTNP_RD_V_O(1, 0, 1, vprev, lacc[0]) ATTNP_RD_V_O(1, 1, 0, vprev, lacc[0]) ATTNP_RD_V_O(1, 1, 1, vprev, lacc[0])
       ATTNP_VT_WAIT();
       ATTNP_PV(0)
       ATTNP_PV(1)
@@ -646,7 +585,6 @@ __device__ __forceinline__ void attnp_body(const u16* __restrict__ qkv, u16* __r
         ATTNP_PV(3)
       }
     }
-    ATTNP_T(t_dr += attnp_stamp() - t_last;)
     // ---- normalise and pack; the stores themselves are issued after the next barrier (store_o) ----
 #pragma unroll
     for (int u = 0; u < SB; ++u) {
@@ -669,7 +607,6 @@ __device__ __forceinline__ void attnp_body(const u16* __restrict__ qkv, u16* __r
     ow[u][dj][rq][1] = PK(o[u][dj][4 * rq + 2], o[u][dj][4 * rq + 3]);                                                 \
   }
     if ((out_other != 0) == (T::id == SFM_DT_BF16)) { ATTNP_PACK_O(F16::pack) } else { ATTNP_PACK_O(BF16::pack) }
-    ATTNP_T(const unsigned long long tso_ = attnp_stamp();)
     if (qf_ready) {
       if (scale_log2e != 1.0f) {
 #pragma unroll
@@ -687,7 +624,6 @@ __device__ __forceinline__ void attnp_body(const u16* __restrict__ qkv, u16* __r
     }
     store_o(item);                                                  // RW / 8 stores, left in flight across the next barrier
     inflight += RW / 8;
-    ATTNP_T(t_so += attnp_stamp() - tso_;)
     if (has_next) {
       if (ngrp == 1) {                                              // single-group items: no room for the Q prefetch earlier
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -700,9 +636,7 @@ __device__ __forceinline__ void attnp_body(const u16* __restrict__ qkv, u16* __r
       const int np = issue_next_group();                            // the refill that belongs to the item's last group
       inflight = (ngrp == 1) ? 0 : inflight + np;
     }
-    ATTNP_T(t_post += attnp_stamp() - t_last;)
   }
-  ATTNP_T(if (lane == 0) { dbg[0] = t_start; dbg[1] = attnp_stamp(); dbg[2] = t_bar; dbg[3] = t_pre; dbg[4] = t_steps; dbg[5] = t_post; dbg[6] = (t_q << 32) | t_so; dbg[7] = t_dr; })
 }
 
 // (the launch bounds cannot depend on a template parameter with this hipcc: thin kernels around the body)
@@ -730,9 +664,7 @@ static int attnp_launch(const void* qkv, void* out, float* lse, int B, int Tlen,
   if (ncu <= 0) return SFM_ERR_LAUNCH;
   constexpr int lds = 3 * (NW * SB / 8) * 16384 + NW * SB * 4096;   // K/V ring + Q prefetch region: 160 KB (8, 2) / 80 KB (4, 2) / 160 KB (4, 4)
   constexpr int wgs_per_cu = (SB == 4) ? 1 : 8 / NW;
-  // (diagnostic: SFM_ATTNP_WGS_PER_CU=1 with the (4, 2) form = one wave per SIMD, what a lone wave's step loop sustains)
-  static const int wgs_env = getenv("SFM_ATTNP_WGS_PER_CU") ? atoi(getenv("SFM_ATTNP_WGS_PER_CU")) : 0;
-  const int resident = ncu * ((wgs_env > 0 && wgs_env <= wgs_per_cu) ? wgs_env : wgs_per_cu);
+  const int resident = ncu * wgs_per_cu;
   dim3 gridr(n_items < resident ? n_items : resident), blockr(64 * NW);
 #define ATTNP_LAUNCH(K) SFM_LAUNCH_LDS((K<T>), gridr, blockr, lds, st, (const u16*)qkv, (u16*)out, Tlen, ldqkv, ldo, koff, voff,      \
                                        qkv_batch_stride, o_batch_stride, sl2, nqt, H, n_items, lse, out_other)

@@ -1,12 +1,5 @@
 #include "gemm16_epi.h"
 
-#ifndef SFM_CONVP_GELU_H2
-#define SFM_CONVP_GELU_H2 1
-#endif
-#ifndef SFM_CONVP_MIX
-#define SFM_CONVP_MIX 1                 // fp16 operands: GroupNorm affine by v_fma_mix* on the packed inputs (A/B: -DSFM_CONVP_MIX=0)
-#endif
-
 // ---------------------------------------------------------------------------------------------------------------
 // conv16p: the PerceptionAgent's Conv1d layers (agents/perception.py:192-206, 167-171) with the GroupNorm + GELU of their
 // INPUT applied while the operand is staged, so the normalised activation never exists in HBM:
@@ -51,11 +44,6 @@ __device__ __forceinline__ float gelu_as(float z) {    // z Phi(z), erf by A&S 7
 // 1 - poly * ex cancels).  z itself (scale / shift of the GroupNorm) is still formed in fp32 from the fp16 inputs: a packed
 // x * a + d would cancel |mean / std| ulps.
 typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t gelu_as_h2p(uint32_t zb);
-__device__ __forceinline__ uint32_t gelu_as_h2(float z0, float z1) {
-  const h2_t z = {(_Float16)z0, (_Float16)z1};
-  return gelu_as_h2p(__builtin_bit_cast(uint32_t, z));
-}
 // z pair already packed (the GroupNorm affine of the fp16 inputs formed by v_fma_mixlo / mixhi_f16: fp32 arithmetic, ONE rounding
 // to fp16, no unpack / pack instructions)
 __device__ __forceinline__ uint32_t gelu_as_h2p(uint32_t zb) {
@@ -208,17 +196,6 @@ __device__ __forceinline__ void convp_epilogue(const Gemm2Params& g, f32x16 (&ac
   else convp_epilogue_impl<T, false>(g, acc, img, bias_s, lane, b, colb, row_base);
 }
 
-#ifdef SFM_CONVP_STAMPS
-// diagnostic build only: s_memtime stamps per workgroup (start, patch staged, k-loop done, end) -> sfm_conv16p_read_stamps
-__device__ unsigned long long sfm_convp_stamps[8 * 32768];
-#define SFM_STAMP(i) do { if (tid == 0 && blockIdx.x < 32768) sfm_convp_stamps[blockIdx.x * 8 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-extern "C" int sfm_conv16p_read_stamps(void* host, int nblocks) {
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(sfm_convp_stamps), (size_t)nblocks * 64, 0, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -3;
-}
-#else
-#define SFM_STAMP(i) do { } while (0)
-#endif
-
 template <class T, int KS, int STRIDE, int NPASS, bool SKIP, bool TWO_IN>
 __global__ __launch_bounds__(256, 2) void conv16p_kernel(ConvPParams p) {
   constexpr int R = 127 * STRIDE + KS;                 // input rows of a 128-row output tile
@@ -353,10 +330,8 @@ __global__ __launch_bounds__(256, 2) void conv16p_kernel(ConvPParams p) {
         for (int e = 0; e < 4; ++e) { a2[e] = t0[e]; a2[4 + e] = t1[e]; d1[e] += g0[e]; d1[4 + e] += g1[e]; }
       }
     }
-    if (slab == 0) SFM_STAMP(4);
     wait_vmcnt<0>();                                   // this wave's pieces have landed ...
     __syncthreads();                                   // ... everyone's have
-    if (slab == 0) SFM_STAMP(5);
 #pragma unroll 2
     for (int lr = srow; lr < LROWS; lr += 32) {
       if (row_pos(lr) < 0) continue;                   // zero-filled row: stays the conv's zero padding
@@ -367,7 +342,6 @@ __global__ __launch_bounds__(256, 2) void conv16p_kernel(ConvPParams p) {
       u32x4 o;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-#if SFM_CONVP_GELU_H2 && SFM_CONVP_MIX
         if (T::id == SFM_DT_F16) {
           // z = x1 * a1 [+ x2 * a2] + d straight from the packed fp16 inputs (mixed-precision FMA: fp16 source halves, fp32
           // coefficients and arithmetic) into a packed fp16 pair: 2 (4) instructions per pair instead of 4 (7)
@@ -383,18 +357,14 @@ __global__ __launch_bounds__(256, 2) void conv16p_kernel(ConvPParams p) {
           o[e] = gelu_as_h2p(zpk);
           continue;
         }
-#endif
+        // bf16: unpack, fp32 affine and GELU, pack
         float z0 = T::to_f32((u16)(v1[e] & 0xffffu)) * a1[2 * e] + d1[2 * e];
         float z1 = T::to_f32((u16)(v1[e] >> 16)) * a1[2 * e + 1] + d1[2 * e + 1];
         if (TWO_IN) {
           z0 += T::to_f32((u16)(v2[e] & 0xffffu)) * a2[2 * e];
           z1 += T::to_f32((u16)(v2[e] >> 16)) * a2[2 * e + 1];
         }
-#if SFM_CONVP_GELU_H2
-        if (T::id == SFM_DT_F16) o[e] = gelu_as_h2(z0, z1);
-        else
-#endif
-          o[e] = pack2<T>(gelu_as(z0), gelu_as(z1));
+        o[e] = pack2<T>(gelu_as(z0), gelu_as(z1));
       }
       *reinterpret_cast<u32x4*>(q1) = o;
     }
@@ -424,18 +394,11 @@ __global__ __launch_bounds__(256, 2) void conv16p_kernel(ConvPParams p) {
     }
   };
 
-  SFM_STAMP(0);
-#ifdef SFM_CONVP_STAMPS
-  if (tid == 0 && blockIdx.x < 32768)                  // which CU / thread-group slot this workgroup ran on (HW_ID, XCC_ID)
-    sfm_convp_stamps[blockIdx.x * 8 + 6] = (unsigned long long)(unsigned)__builtin_amdgcn_s_getreg(4 | (31 << 11)) |
-                                           ((unsigned long long)(unsigned)__builtin_amdgcn_s_getreg(20 | (31 << 11)) << 32);
-#endif
   if (!TWO_IN) issue_w(0);
   for (int slab = 0; slab < nslab; ++slab) {
     if (slab > 0) __syncthreads();                     // every wave is done reading the previous slab's patch (and weight tiles)
     stage_patch(slab);
     __syncthreads();                                   // patch complete
-    if (slab == 0) SFM_STAMP(1);
     const int q0 = slab * TPS;
     if (TWO_IN) issue_w(q0);                           // the ring held the second raw input until now
 #pragma unroll
@@ -460,12 +423,10 @@ __global__ __launch_bounds__(256, 2) void conv16p_kernel(ConvPParams p) {
     }
   }
   __syncthreads();                                     // the ring becomes the epilogue strips
-  SFM_STAMP(2);
   unsigned char* img = smem + wave * 9216;             // 64 x 144 B per wave, in the (now free) patch + ring area
 #pragma unroll
   for (int n = 0; n < NPASS; ++n) convp_epilogue<T>(p.g, acc[n], img, bias_s, lane, b, n * 128 + wn * 64, l0 + wm * 64);
   if (SKIP) convp_epilogue<T>(p.gs, accs, img, bias_s + 256, lane, b, wn * 64, l0 + wm * 64);
-  SFM_STAMP(3);
 }
 
 template <class T, int KS, int STRIDE, int NPASS, bool SKIP, bool TWO_IN>

@@ -13,9 +13,6 @@
 // ~8 KB/row for LN + two GEMM launches.
 #include "sfm_common.h"
 
-#ifndef SFM_FFN_ABL
-#define SFM_FFN_ABL 0                   // diagnostic builds only (tools/variant_lib.sh): 1 no weight refills, 2 no Swish (results wrong)
-#endif
 #define FF_D 256
 #define FF_BM 128
 #define FF_CH 64                        // hidden units per chunk
@@ -44,16 +41,6 @@ __device__ __forceinline__ void ff_barrier() {
   asm volatile("" ::: "memory");
 }
 
-#ifdef SFM_FFN_STAMPS
-// diagnostic build only (tools/variant_lib.sh): s_memtime stamps per workgroup -> sfm_ffn_read_stamps
-__device__ unsigned long long sfm_ffn_stamps[8 * 4096];
-#define FF_STAMP(i) do { if (threadIdx.x == 0 && blockIdx.x < 4096) sfm_ffn_stamps[blockIdx.x * 8 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-extern "C" int sfm_ffn_read_stamps(void* host, int nblocks) {
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(sfm_ffn_stamps), (size_t)nblocks * 64, 0, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -3;
-}
-#else
-#define FF_STAMP(i) do { } while (0)
-#endif
 
 template <class T>
 __global__ __launch_bounds__(512) void ffn_fused_kernel(const float* __restrict__ x, const float* __restrict__ lnw,
@@ -75,7 +62,6 @@ __global__ __launch_bounds__(512) void ffn_fused_kernel(const float* __restrict_
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, hl = lane >> 5;
   const int m0 = blockIdx.x * FF_BM;
-  FF_STAMP(0);
   auto w1_rs = __builtin_amdgcn_make_buffer_rsrc((void*)W1, 0, w1_bytes, 0x00020000);
   auto w2_rs = __builtin_amdgcn_make_buffer_rsrc((void*)W2, 0, w2_bytes, 0x00020000);
 
@@ -116,7 +102,6 @@ __global__ __launch_bounds__(512) void ffn_fused_kernel(const float* __restrict_
   for (int s = 0; s < 16; ++s)
     hf[s] = *reinterpret_cast<const u32x4*>(Hs + r1 * 512 + (((2 * s + hl) ^ (r1 & 15)) << 4));
   __syncthreads();                                         // LN image consumed: the weight ring may overwrite it
-  FF_STAMP(1);
   const int nch = FF / FF_CH;
   // Weight pieces: a wave moves 4 x 1 KB of every W1 chunk and 4 x 1 KB of every W2 chunk (ring stage c & 1).  A chunk index
   // past the end is issued all the same: the buffer range check turns it into zeros written to ring bytes nobody reads
@@ -186,11 +171,7 @@ __global__ __launch_bounds__(512) void ffn_fused_kernel(const float* __restrict_
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const float z = s1[4 * q + e];
-#if SFM_FFN_ABL == 2
-      y[e] = z;
-#else
       y[e] = z * __builtin_amdgcn_rcpf(1.0f + __expf(-z));
-#endif
     }
     u32x2 pk;
     pk[0] = pack2<T>(y[0], y[1]);
@@ -224,16 +205,13 @@ __global__ __launch_bounds__(512) void ffn_fused_kernel(const float* __restrict_
         for (int j = 0; j < 2; ++j) {
           acc2[i][j] = T::mfma(fa[k][i], fb[k][j], acc2[i][j]);
           const int m = k * 4 + i * 2 + j;
-#if SFM_FFN_ABL != 1
           if (refill && (m & 3) == 1) w1_piece(c + 3, m >> 2);
-#endif
         }
   };
 
   f32x16 s1;                                                // GEMM1 accumulator of the chunk whose Swish comes next
   ff_wait_vmcnt<8>();                                       // W1(0) is in
   ff_barrier();
-  FF_STAMP(2);
   s1_init(0, s1);
   {
     u32x4 fw[4];
@@ -270,9 +248,7 @@ __global__ __launch_bounds__(512) void ffn_fused_kernel(const float* __restrict_
         s1n = T::mfma(fw[k & 3], hf[k], s1n);
         if (k + 4 < 16) ff_frag_read(fw[k & 3], fbase + (uint32_t)(hx4 ^ ((k + 4) << 5)));
         if ((k & 3) == 1) swish_quad(s1, k >> 2);
-#if SFM_FFN_ABL != 1
         if ((k & 3) == 3) w2_piece(c + 1, k >> 2);
-#endif
       }
       s1 = s1n;
     }
@@ -302,7 +278,6 @@ __global__ __launch_bounds__(512) void ffn_fused_kernel(const float* __restrict_
   ff_wait_vmcnt<0>();                                       // the refills past the last chunk (zeros) have landed in the
   ff_barrier();                                             // ring bytes the epilogue image is about to take
 
-  FF_STAMP(3);
   // ---- epilogue in the prologue's row layout: acc2 -> fp32 image [128][260] -> wave w takes rows 16w..16w+15, a lane 4
   //      consecutive columns: out = x + alpha * (acc2 + b2) leaves as 1-KB row stores, and the LayerNorm of the NEXT sub-layer
   //      (mhsa.layer_norm after ff1, final_norm after ff2; models/conformer.py:66, 151) is a per-wave DPP reduction ----
@@ -316,7 +291,6 @@ __global__ __launch_bounds__(512) void ffn_fused_kernel(const float* __restrict_
       for (int r = 0; r < 16; ++r)
         img[(wm2 * 64 + i * 32 + mfma_row(r, lane)) * IW + wn2 * 64 + j * 32 + l31] = acc2[i][j][r];
   ff_barrier();
-  FF_STAMP(4);
   const f32x4 bb = *reinterpret_cast<const f32x4*>(b2 + ln * 4);
   f32x4 g2 = {0.f, 0.f, 0.f, 0.f}, h2 = {0.f, 0.f, 0.f, 0.f};
   if (ln2w != nullptr) {
@@ -365,7 +339,6 @@ __global__ __launch_bounds__(512) void ffn_fused_kernel(const float* __restrict_
       }
     }
   }
-  FF_STAMP(5);
 }
 
 // x, out [M, 256] fp32 contiguous rows; W1 [FF, 256], W2 [256, FF] 16-bit row-major (nn.Linear layout); fp32 biases.

@@ -7,7 +7,6 @@
 // M is split over gridDim.z; partial tiles are accumulated into the fp32 dW with float atomics
 // (128-byte contiguous per wave-instruction).  sfm_colsum gives the bias gradient.
 #include "sfm_common.h"
-#include <cstdlib>
 
 #define TN_ROW 160      // u16 elements per LDS row (128 + 32 pad) = 320 B
 
@@ -374,7 +373,7 @@ __global__ __launch_bounds__(256) void colsum_vec_kernel(const void* __restrict_
 
 // gemm16_tn2.hip: the LDS-DMA ring form (SFM_ERR_SHAPE = not a shape it takes)
 int sfm_tn2_launch(const void* G, const void* X, float* dW, float* db, int M, int N, int K, int ldg, int ldx, int ldw, int dtype,
-                   void* stream, const TnConv& cv, long long x_elems, int variant, float* ws, long long ws_floats);
+                   void* stream, const TnConv& cv, long long x_elems, float* ws, long long ws_floats);
 
 // deterministic mode (ws != NULL): every M-split writes its partial dW [N][K] (+ db [N]) into ws and sfm_fold_partials adds the
 // partials to dW / db in split order.  An upper bound of the floats any of the kernels below needs for (M, N, K):
@@ -403,15 +402,11 @@ static int gemm16_tn_launch(const void* G, const void* X, float* dW, float* db, 
   if (M <= 0 || N <= 0 || K <= 0 || (ldg % 8) != 0 || (cv.Lout == 0 && (ldx % 8) != 0)) return SFM_ERR_SHAPE;
   // The LDS-DMA ring kernel (gemm16_tn2.hip) takes the Conv1d / sinc-FIR weight gradients (M = 1 .. 16 M im2col rows: 1.3-1.4x the first
   // kernel, profiles/README.md round 3); on the plain K = 256 / 1024 linears the 256 x 256-tile kernel below stays ahead.
-  // A/B knob (tools/gemm_tn_bench.py): SFM_TN2 = 0 first kernels only, 1 / 2 = ring kernel everywhere, 128 x 128 / 128 x 256 tiles
-  static const int tn2 = getenv("SFM_TN2") ? atoi(getenv("SFM_TN2")) : -1;
-  const bool tn2_auto = (tn2 < 0) && cv.Lout > 0;              // conv and the sinc bank's Toeplitz form (2.6 -> 1.8 ms at B 256 x 4 s)
-  if ((tn2 > 0 || tn2_auto) && M >= 4096) {
-    const int rc = sfm_tn2_launch(G, X, dW, db, M, N, K, ldg, ldx, ldw, dtype, stream, cv, x_elems, tn2 > 0 ? tn2 : 2, ws, ws_floats);
+  if (cv.Lout > 0 && M >= 4096) {                              // conv and the sinc bank's Toeplitz form (2.6 -> 1.8 ms at B 256 x 4 s)
+    const int rc = sfm_tn2_launch(G, X, dW, db, M, N, K, ldg, ldx, ldw, dtype, stream, cv, x_elems, ws, ws_floats);
     if (rc != SFM_ERR_SHAPE) return rc;
   }
-  static const int wide_on = getenv("SFM_TN_WIDE") ? atoi(getenv("SFM_TN_WIDE")) : 1;          // A/B knob
-  if (wide_on && cv.Lout == 0 && cv.toeplitz == 0 && (N % 256) == 0 && (K % 256) == 0 && M >= 8192) {
+  if (cv.Lout == 0 && cv.toeplitz == 0 && (N % 256) == 0 && (K % 256) == 0 && M >= 8192) {
     const int tiles_w = (N / 256) * (K / 256);
     int splits = 256 / tiles_w;                                // one 16-wave workgroup per CU: one full round
     if (splits < 1) splits = 1;
@@ -434,8 +429,7 @@ static int gemm16_tn_launch(const void* G, const void* X, float* dW, float* db, 
   const int tiles = ((N + 127) / 128) * ((K + 127) / 128);
   // 142 registers -> 3 workgroups per CU: aim at ONE full round of 768 resident workgroups (1024 was 1.3 rounds: the
   // second round ran on a third of the chip)
-  static const int target = getenv("SFM_TN_TARGET") ? atoi(getenv("SFM_TN_TARGET")) : 768;   // A/B knob (tools/gemm_tn_bench.py)
-  int splits = target / tiles;
+  int splits = 768 / tiles;
   const int max_splits = (M + 255) / 256;
   if (splits > max_splits) splits = max_splits;
   if (splits < 1) splits = 1;

@@ -10,7 +10,7 @@
 //     conflict-free like the 320-byte rows of the first kernel;
 //   * out-of-range rows / columns / conv padding are fetched with an out-of-range buffer offset (hardware returns 0);
 //   * the im2col coordinates of a conv's X rows advance incrementally (no division in the loop).
-// Tiles: (WNW x WKW) waves of 64 x 64; 2 x 2 (128 x 128, 4 stages) and 2 x 4 (128 n x 256 k, 3 stages), one workgroup per CU.
+// Tiles: (WNW x WKW) waves of 64 x 64; instantiated as 2 x 4 (128 n x 256 k, 3 stages), one workgroup per CU.
 #include "sfm_common.h"
 
 struct TnConv {            // = gemm16_tn.hip
@@ -266,9 +266,9 @@ static int tn2_go(const void* G, const void* X, float* dW, float* db, int M, int
 }
 
 // called by gemm16_tn.hip's launcher; returns SFM_ERR_SHAPE when the shape is not one this kernel takes (the caller then
-// uses the first kernel).  variant: 1 = 128 x 128 tiles, 2 = 128 (n) x 256 (k) tiles.
+// uses the first kernel).  128 (n) x 256 (k) tiles.
 int sfm_tn2_launch(const void* G, const void* X, float* dW, float* db, int M, int N, int K, int ldg, int ldx, int ldw, int dtype,
-                   void* stream, const TnConv& cv, long long x_elems, int variant, float* ws, long long ws_floats) {
+                   void* stream, const TnConv& cv, long long x_elems, float* ws, long long ws_floats) {
   if ((N % 8) != 0 || (K % 8) != 0 || (ldg % 8) != 0) return SFM_ERR_SHAPE;
   if (cv.Lout == 0 && (ldx % 8) != 0) return SFM_ERR_SHAPE;
   if (cv.Lout > 0 && !cv.toeplitz && (cv.Cin % 8) != 0) return SFM_ERR_SHAPE;
@@ -287,10 +287,6 @@ int sfm_tn2_launch(const void* G, const void* X, float* dW, float* db, int M, in
   const int n_cu = n_cu_dev[dev];
   hipStream_t st = (hipStream_t)stream;
   const unsigned gr = (unsigned)g_bytes, xr = (unsigned)x_bytes;
-  if (variant == 2) {
-    if (dtype == SFM_DT_F16) return tn2_go<F16, 2, 4, 3>(G, X, dW, db, M, N, K, ldg, ldx, ldw, gr, xr, st, cv, n_cu, ws, ws_floats);
-    return tn2_go<BF16, 2, 4, 3>(G, X, dW, db, M, N, K, ldg, ldx, ldw, gr, xr, st, cv, n_cu, ws, ws_floats);
-  }
-  if (dtype == SFM_DT_F16) return tn2_go<F16, 2, 2, 4>(G, X, dW, db, M, N, K, ldg, ldx, ldw, gr, xr, st, cv, n_cu, ws, ws_floats);
-  return tn2_go<BF16, 2, 2, 4>(G, X, dW, db, M, N, K, ldg, ldx, ldw, gr, xr, st, cv, n_cu, ws, ws_floats);
+  if (dtype == SFM_DT_F16) return tn2_go<F16, 2, 4, 3>(G, X, dW, db, M, N, K, ldg, ldx, ldw, gr, xr, st, cv, n_cu, ws, ws_floats);
+  return tn2_go<BF16, 2, 4, 3>(G, X, dW, db, M, N, K, ldg, ldx, ldw, gr, xr, st, cv, n_cu, ws, ws_floats);
 }

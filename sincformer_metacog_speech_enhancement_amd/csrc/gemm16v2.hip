@@ -11,7 +11,6 @@
 //     bias / activation / GLU / residual / GroupNorm partials, then 16-byte row stores;
 //   * XCD-aware block order: the N-tiles of one M-tile (same A rows) run on one XCD (L2 reuse).
 #include "sfm_common.h"
-#include <cstdlib>
 
 #include "gemm16_epi.h"
 
@@ -768,7 +767,6 @@ static int gemm16_impl(const void* A, const void* W, const float* bias, void* ou
     if (out_f32 != 0 || (N % 8) != 0 || (ldo % 8) != 0 || (o_batch_stride % 8) != 0 || gn_partial) return SFM_ERR_SHAPE;
     if ((((uintptr_t)out) % 16) != 0 || (out2 && (((uintptr_t)out2) % 16) != 0) || (aux && (((uintptr_t)aux) % 16) != 0))
       return SFM_ERR_SHAPE;
-    if (variant != 2 && variant != 6 && variant != 9 && variant != 10) variant = 0;
   }
   if (B <= 0 || Lout <= 0 || N <= 0 || out_f32 < 0 || out_f32 > 2) return SFM_ERR_SHAPE;
   const long long a_rec = ((long long)(Lin - 1) * lda + Cin) * 2;
@@ -821,13 +819,9 @@ static int gemm16_impl(const void* A, const void* W, const float* bias, void* ou
   // 256-row tiles on 8 or 16 waves (variant 9) and 512 x 128 tiles on 16 waves (variant 10) stay selectable, but auto no longer
   // picks them for the inference GEMMs: since the PerceptionAgent convs left for conv16p the shapes that remain are K = 256 /
   // 1024 linears, and there the 128 x 128 kernel wins on every one (tools/gemm_bench.py, round 2: M 51264, K 256, N 768:
-  // 49 us against 75 us wide, 108 us wide inside the pass; bench c2 8.00 -> 7.83 ms per step).  The fused-Swish epilogues of the
-  // training step still run best on the wide tiles (52.3 ms per step against 55.4 ms on the persistent 128 x 128 kernel).
-  const long long tiles256 = (long long)((Lout + 255) / 256) * (Npad / 256) * B;
-  const bool auto_wide = (variant == 0) && swish && (Npad % 256 == 0) && tiles256 >= 512;
-  const bool auto_tall = false;
-  const bool tall = ((variant == 10) && bn128) || auto_tall;
-  const bool wide = ((variant == 9) && bn128) || auto_wide;
+  // 49 us against 75 us wide, 108 us wide inside the pass; bench c2 8.00 -> 7.83 ms per step).
+  const bool tall = (variant == 10) && bn128;
+  const bool wide = (variant == 9) && bn128;
   const bool wide256 = wide && (Npad % 256 == 0);
   const int BMv = tall ? 512 : (wide ? 256 : 128);
   p.nMt = (Lout + BMv - 1) / BMv;
@@ -836,7 +830,7 @@ static int gemm16_impl(const void* A, const void* W, const float* bias, void* ou
   hipStream_t st = (hipStream_t)stream;
   // the persistent kernel is 5-20 % faster than variant 2 on isolated launches of the path's skinny GEMMs
   // (tools/gemm_bench.py) but 2 % slower inside the forward pass (bench.py, same box, A/B/A/B): not the default
-  const bool persistent = (variant == 6) || (swish && !wide && !tall && variant != 2);
+  const bool persistent = (variant == 6);
 #define GO(TT)                                                                                            \
   if (tall) return launch_w<TT, 512, 128, 16>(p, st);                                                   \
   if (wide) return wide256 ? launch_w<TT, 256, 256, 16>(p, st) : launch_w<TT, 256, 128, 8>(p, st);      \
@@ -868,10 +862,9 @@ extern "C" int sfm_gemm16_swish(const void* A, const void* W, const float* bias,
                                 unsigned int seed, int dtype, void* stream) {
   // 128 x 128 tiles with the whole-tile epilogue (variant 2): 0.34 / 0.29 ms per launch at M 205 056, N 1024, K 256 against 0.47 /
   // 0.39 ms on the 256-row tiles with the strip epilogue and 0.46 / 0.49 ms on the persistent kernel (tools/gemm_train_bench.py,
-  // round 3).  A/B knob: SFM_SWISH_VARIANT = 0 (256-row tiles when they fill the chip), 6, 9, 10.
-  const int sv = getenv("SFM_SWISH_VARIANT") ? atoi(getenv("SFM_SWISH_VARIANT")) : 2;   // (read per call: tools/swish_sensitivity.py toggles it)
+  // round 3).
   return gemm16_impl(A, W, bias, out, nullptr, nullptr, 1, M, M, Cin, lda, 1, 1, 0, 0, Kpad, N, Npad, ldo, 0, 0, 0, 1.0f,
-                     backward ? EPI_SWISH_BWD : EPI_SWISH_DUAL, 0, 0, 0, dtype, sv, p_drop, seed, aux, out2, stream);
+                     backward ? EPI_SWISH_BWD : EPI_SWISH_DUAL, 0, 0, 0, dtype, 2, p_drop, seed, aux, out2, stream);
 }
 
 extern "C" int sfm_gemm16_ex(const void* A, const void* W, const float* bias, void* out, const float* resid,

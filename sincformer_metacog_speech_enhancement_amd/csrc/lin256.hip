@@ -12,9 +12,6 @@
 #include "sfm_common.h"
 #include "gemm16_epi.h"
 
-#ifndef SFM_L2_ABL
-#define SFM_L2_ABL 0                      // timing experiments (results wrong): 1 no row stores, 2 no W refills, 3 no image writes, 4 no MFMAs
-#endif
 #define L2_BM 128
 #define L2_K 256
 #define L2_STAGE 32768                    // one W chunk: 64 rows x 512 B
@@ -248,7 +245,7 @@ __global__ __launch_bounds__(512) void lin256_kernel(const u16* __restrict__ A, 
         l2_barrier();
       }
     }
-    if (SFM_L2_ABL != 1 && OTHER != 2 && c >= CPG && (c % CPG) == 0) {   // group c / CPG - 1 was completed in X(c - 1)
+    if (OTHER != 2 && c >= CPG && (c % CPG) == 0) {   // group c / CPG - 1 was completed in X(c - 1)
       store_group(stored);
       ++stored;
       did_store = true;
@@ -265,11 +262,10 @@ __global__ __launch_bounds__(512) void lin256_kernel(const u16* __restrict__ A, 
       else if (k == 13) l2_frag_wait<2>(fw[k & 3]);
       else if (k == 14) l2_frag_wait<1>(fw[k & 3]);
       else l2_frag_wait<0>(fw[k & 3]);
-      if (SFM_L2_ABL != 4) s1n = T::mfma(fw[k & 3], hf[k], s1n);
-      else asm volatile("" : "+v"(s1n), "+v"(fw[k & 3]));
+      s1n = T::mfma(fw[k & 3], hf[k], s1n);
       if (k + 4 < 16) l2_frag_read(fw[k & 3], fbase + (uint32_t)(hx4 ^ ((k + 4) << 5)));
-      if (SFM_L2_ABL != 3 && (k & 3) == 1) epi_quad(s1, c, k >> 2);
-      if (SFM_L2_ABL != 2 && (k & 3) == 3) w_piece(c + 3, stage_free, k >> 2);
+      if ((k & 3) == 1) epi_quad(s1, c, k >> 2);
+      if ((k & 3) == 3) w_piece(c + 3, stage_free, k >> 2);
     }
     s1 = s1n;
     // W(c + 2) has landed: behind it in this wave's queue are the 4 pieces of W(c + 3) and this period's row stores

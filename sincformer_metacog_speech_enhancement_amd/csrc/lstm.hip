@@ -12,9 +12,7 @@
 // workgroup barrier per time step.
 #include "sfm_common.h"
 
-#ifndef SFM_LSTM_LPU
-#define SFM_LSTM_LPU 4                       // lanes per hidden unit of the forward recurrence (8 = round 1's mapping)
-#endif
+constexpr int LSTM_FWD_LPU = 4;              // lanes per hidden unit of the forward recurrence (8 = round 1's mapping)
 
 template <int CTRL>
 __device__ __forceinline__ float dpp_add(float v) {          // v + v[permuted lane] (within a row of 16 lanes)
@@ -296,7 +294,7 @@ __global__ __launch_bounds__(LPU * H) void bilstm_layer_bwd_kernel(const float* 
 
 template <int H>
 static int bilstm_fwd_go(const float* xg, const float* whh, float* out, float* save, int B, int T, hipStream_t st, bool w16 = false) {
-  constexpr int LPU = H >= 64 ? SFM_LSTM_LPU : 8;           // H 32: 4 x H / 4 = 8-float slices, too short for the float4 reads
+  constexpr int LPU = H >= 64 ? LSTM_FWD_LPU : 8;           // H 32: 4 x H / 4 = 8-float slices, too short for the float4 reads
   if constexpr (H >= 64 && (H / LPU) % 8 == 0) {
     if (w16) {
       if (save) SFM_LAUNCH((bilstm_layer16_kernel<H, LPU, true>), dim3(2, B), dim3(LPU * H), 0, st, xg, whh, out, T, save);
@@ -356,7 +354,9 @@ extern "C" int sfm_bilstm_layer_bwd(const float* save, const float* whh, const f
   if (!save || !whh || !dout || !dxg) return SFM_ERR_ARG;
   if (B <= 0 || T <= 0) return SFM_ERR_SHAPE;
   hipStream_t st = (hipStream_t)stream;
-  static const int lpu = getenv("SFM_LSTM_BWD_LPU") ? atoi(getenv("SFM_LSTM_BWD_LPU")) : 4;    // A/B knob (tools/lstm_bench.py)
+  // The library's only environment read.  It stays because tests/test_train_nodes_gpu.py pins bilstm_layer_bwd_kernel<128, 8>
+  // through it in a child process; ops.variant_overrides() reports it, so nothing is timed with it set.
+  static const int lpu = getenv("SFM_LSTM_BWD_LPU") ? atoi(getenv("SFM_LSTM_BWD_LPU")) : 4;
   if (H == 128 && lpu == 4) SFM_LAUNCH((bilstm_layer_bwd_kernel<128, 4>), dim3(2, B), dim3(512), 0, st, save, whh, dout, dxg, T);
   else if (H == 128) SFM_LAUNCH((bilstm_layer_bwd_kernel<128, 8>), dim3(2, B), dim3(1024), 0, st, save, whh, dout, dxg, T);
   else if (H == 64) SFM_LAUNCH((bilstm_layer_bwd_kernel<64, 8>), dim3(2, B), dim3(512), 0, st, save, whh, dout, dxg, T);

@@ -2,7 +2,6 @@
 // mask epilogue, overlap-add, sinc filter synthesis.  All are coalesced
 // streaming kernels (wave = 64 lanes, shuffles for row statistics, LDS halos).
 #include "sfm_common.h"
-#include <stdlib.h>
 
 // ---------------------------------------------------------------------------
 // LayerNorm over the last dim (nn.LayerNorm; models/conformer.py:43,68,107,150,
@@ -650,11 +649,9 @@ static int dwconv_folded_route(const void* x, const float* wT, const float* sc, 
                  total, act, out_f32, frame_off, VARLEN ? B : 0);
     return SFM_OK;
   }
-  // fp16: the dot-product form (SFM_DWCONV_DOT=0 keeps the multiply-add kernel: the A/B knob)
-  static const int dot_on = getenv("SFM_DWCONV_DOT") ? atoi(getenv("SFM_DWCONV_DOT")) : 1;
+  // KS 31: fp16 on the dot-product form, bf16 on the multiply-add kernel
 #define DW_GO(L) return L(x, wT, sc, sh, out, B, Tn, C, act, out_f32, st, frame_off, tiles, n_tiles)
-  if (KS == 31 && dtype == SFM_DT_F16 && dot_on) DW_GO((launch_dwconv_dot<31, VARLEN>));
-  if (KS == 31) { if (dtype == SFM_DT_F16) DW_GO((launch_dwconv_reg<F16, 31, VARLEN>)); else DW_GO((launch_dwconv_reg<BF16, 31, VARLEN>)); }
+  if (KS == 31) { if (dtype == SFM_DT_F16) DW_GO((launch_dwconv_dot<31, VARLEN>)); else DW_GO((launch_dwconv_reg<BF16, 31, VARLEN>)); }
   if (dtype == SFM_DT_F16) DW_GO((launch_dwconv_reg<F16, 7, VARLEN>));
   DW_GO((launch_dwconv_reg<BF16, 7, VARLEN>));
 #undef DW_GO

@@ -13,13 +13,43 @@ EPI_NONE, EPI_SWISH, EPI_GELU, EPI_RESID, EPI_GLU, EPI_SIGMOID, EPI_TANH_SCALE, 
 _DT_ID = {torch.bfloat16: 0, torch.float16: 1}
 import os as _os
 TRAIN_DTYPE = torch.float16         # base (training) operand format: the reference's own AMP recipe, see reset_precision
-_state = {"dtype": TRAIN_DTYPE, "gemm_variant": int(_os.environ.get("SFM_GEMM_VARIANT", "0"))}
+_state = {"dtype": TRAIN_DTYPE}
+
+# Every kernel-selection switch of the package: name -> [environment variable or None, default, current value].  The environment
+# is read here, once, at import; the set_* functions below write the current value.  bench.py times nothing while
+# variant_overrides() reports an entry away from its default.  The precision policy is no switch
+# (bench.py sets it itself), nor is SFM_LIB_PATH (lib.py: the documented way to time another build).
+_SWITCHES = {
+    "gemm_variant": ["SFM_GEMM_VARIANT", 0, 0],             # set_gemm_variant
+    "attention_variant": [None, 0, 0],                      # set_attention_variant
+    "lin256": ["SFM_LIN256", True, True],                   # set_lin256
+    "headpool": ["SFM_HEADPOOL", True, True],               # set_headpool
+    "lstm_w16": ["SFM_LSTM_W16", True, True],               # set_lstm_w16
+    "deterministic": ["SFM_DETERMINISTIC", True, True],     # set_deterministic
+    "wgrad_stream": ["SFM_WGRAD_STREAM", True, True],       # wgrad_side_stream: weight-gradient GEMMs on a second stream
+    "fuse_ffn_swish": ["SFM_FUSE_FFN_SWISH", True, True],   # train.py: Swish (+ hidden dropout) of the FFN in its GEMMs' epilogues
+    "fuse_next_drop": ["SFM_FUSE_NEXT_DROP", True, True],   # train.py: the LayerNorm backward also writes the next node's operand
+    "steal_grads": ["SFM_STEAL_GRADS", False, False],       # optim.FlatAdamW's default for steal_grads=None
+    # read by the library itself (csrc/lstm.hip), never by the package: listed so that it is reported
+    "lstm_bwd_lpu": ["SFM_LSTM_BWD_LPU", 4, 4],
+}
+for _sw in _SWITCHES.values():
+    if _sw[0] is not None and _sw[0] in _os.environ:
+        _sw[2] = (_os.environ[_sw[0]] != "0") if isinstance(_sw[1], bool) else int(_os.environ[_sw[0]])
+
+
+def switch(name):
+    return _SWITCHES[name][2]
+
+
+def variant_overrides():
+    """the switches that are NOT at their default, by name: bench.py refuses to time anything while one is active"""
+    return {name: cur for name, (_, default, cur) in _SWITCHES.items() if cur != default}
 
 
 def set_gemm_variant(v):
     """0 auto, 2 = 128-row tiles, 6 = persistent, 9 = 256-row wide tiles, 10 = 512 x 128 tiles (A/B testing)."""
-    _state["gemm_variant"] = int(v)
-
+    _SWITCHES["gemm_variant"][2] = int(v)
 
 
 _DT_NAMES = {"bf16": torch.bfloat16, "bfloat16": torch.bfloat16, "f16": torch.float16, "fp16": torch.float16,
@@ -210,15 +240,15 @@ profiler = KernelProfiler()
 # BatchNorm statistics, the objective's moments, ||g||^2) writes its per-workgroup partials into a workspace and folds them in a
 # fixed order (csrc/reduce.hip) instead of issuing atomics: a step is then bit-reproducible, like the reference's CPU step.
 # SFM_DETERMINISTIC=0 / set_deterministic(False) passes NULL workspaces = the fp32-atomics form (A/B of the cost).
-_DET = {"on": _os.environ.get("SFM_DETERMINISTIC", "1") != "0", "bufs": {}}
+_WS_BUFS = {}
 
 
 def set_deterministic(flag):
-    _DET["on"] = bool(flag)
+    _SWITCHES["deterministic"][2] = bool(flag)
 
 
 def is_deterministic():
-    return _DET["on"]
+    return switch("deterministic")
 
 
 def _ws(n, device, dtype=torch.float32):
@@ -226,12 +256,12 @@ def _ws(n, device, dtype=torch.float32):
     stream and dtype: launches of one stream run in order, so the fold of one launch has read the partials before the next
     launch overwrites them; a replaced buffer goes back to the caching allocator, which hands memory freed on a stream only
     to later work of that stream).  None when the atomics form is selected."""
-    if not _DET["on"]:
+    if not switch("deterministic"):
         return None
     key = (device.index, torch.cuda.current_stream(device).cuda_stream, dtype)
-    t = _DET["bufs"].get(key)
+    t = _WS_BUFS.get(key)
     if t is None or t.numel() < n:
-        t = _DET["bufs"][key] = torch.empty(max(int(n), 1 << 18), device=device, dtype=dtype)
+        t = _WS_BUFS[key] = torch.empty(max(int(n), 1 << 18), device=device, dtype=dtype)
     return t
 
 
@@ -383,12 +413,12 @@ def gemm16(A, pw, out, *, B, Lout, Lin, a_batch_stride, ldo, o_batch_stride, lda
         _call("gemm16", L.sfm_gemm16_train, (_p(A), _p(pw.w), _p(pw.bias), _p(out), _p(resid), _p(gn_partial), B, Lout, Lin, cin,
                                              lda, pw.ksize, stride, pad, a_batch_stride, pw.Kpad, pw.N, pw.Npad, ldo,
                                              o_batch_stride, ldr, r_batch_stride, float(alpha), epi, out_f32, gn_group, nsplit,
-                                             _dt(), _state["gemm_variant"], float(p_drop), int(seed) & 0xffffffff, _stream()),
+                                             _dt(), switch("gemm_variant"), float(p_drop), int(seed) & 0xffffffff, _stream()),
               *_cost_of("gemm16", locals()))
         return out
     _call("gemm16", L.sfm_gemm16_ex, (_p(A), _p(pw.w), _p(pw.bias), _p(out), _p(resid), _p(gn_partial), B, Lout, Lin, cin, lda,
                       pw.ksize, stride, pad, a_batch_stride, pw.Kpad, pw.N, pw.Npad, ldo, o_batch_stride, ldr, r_batch_stride,
-                      float(alpha), epi, out_f32, gn_group, nsplit, _dt(), _state["gemm_variant"], _stream()),
+                      float(alpha), epi, out_f32, gn_group, nsplit, _dt(), switch("gemm_variant"), _stream()),
           *_cost_of("gemm16", locals()))
     return out
 
@@ -430,24 +460,27 @@ def conv16p(x1, sc1, sh1, pw, out, *, B, Lin, stride, pad, x2=None, sc2=None, sh
     return out
 
 
-_LIN256 = {"on": _os.environ.get("SFM_LIN256", "1") != "0"}
-
-
 def set_lin256(flag):
     """K = 256 linears with a plain / GLU epilogue and a 16-bit result on the resident-operand kernel (csrc/lin256.hip; default on,
     SFM_LIN256=0 / False = sfm_gemm16 for every shape: the A/B)"""
-    _LIN256["on"] = bool(flag)
+    _SWITCHES["lin256"][2] = bool(flag)
+
+
+def _lin256_weight_ok(pw, epi):
+    """the half of the lin256 routing that the switches, the packed weight and the epilogue decide: shared by linear16
+    (_lin256_ok) and ln_linear16, whose operand checks differ"""
+    return (switch("lin256") and switch("gemm_variant") == 0 and epi in (EPI_NONE, EPI_GLU) and (epi == EPI_GLU) == bool(pw.glu) and
+            pw.K == 256 and pw.Kpad == 256 and pw.ksize == 1 and pw.Npad % (128 if pw.glu else 64) == 0 and
+            pw.Npad == (2 * pw.N if pw.glu else pw.N) and pw.Npad <= 2048 and pw.w.dtype == _state["dtype"])
 
 
 def _lin256_ok(x16, pw, epi, out, resid, nsplit, p_drop):
-    return (_LIN256["on"] and _state["gemm_variant"] == 0 and epi in (EPI_NONE, EPI_GLU) and (epi == EPI_GLU) == bool(pw.glu) and
-            pw.K == 256 and pw.Kpad == 256 and pw.ksize == 1 and pw.Npad % (128 if pw.glu else 64) == 0 and
-            (pw.Npad == (2 * pw.N if pw.glu else pw.N)) and pw.Npad <= 2048 and
+    return (_lin256_weight_ok(pw, epi) and
             resid is None and nsplit == 0 and p_drop == 0.0 and
             (out.dtype in (torch.float16, torch.bfloat16) or (out.dtype == torch.float32 and not pw.glu and out.stride(0) % 4 == 0)) and
             x16.shape[0] >= 4096 and x16.stride(1) == 1 and out.stride(1) == 1 and x16.stride(0) % 8 == 0 and
             (out.stride(0) % 8 == 0 or out.dtype == torch.float32) and
-            x16.dtype == _state["dtype"] and pw.w.dtype == _state["dtype"])
+            x16.dtype == _state["dtype"])
 
 
 def lin256(x16, pw, out):
@@ -465,17 +498,14 @@ def lin256(x16, pw, out):
     return out
 
 
-_HEADPOOL = {"on": _os.environ.get("SFM_HEADPOOL", "1") != "0"}
-
-
 def set_headpool(flag):
     """latent heads + time pooling in one launch (sfm_headpool) in the fused path; False / SFM_HEADPOOL=0 = heads GEMM, then pool_time"""
-    _HEADPOOL["on"] = bool(flag)
+    _SWITCHES["headpool"][2] = bool(flag)
 
 
 def headpool_tiles(Tin, Tout):
     """(frames per tile, tiles per utterance) of sfm_headpool, or None when the pair is not supported / the fusion is switched off"""
-    if not _HEADPOOL["on"] or _state["gemm_variant"] != 0:
+    if not switch("headpool") or switch("gemm_variant") != 0:
         return None
     fpt = int(_lib.load().sfm_headpool_frames_per_tile(int(Tin), int(Tout)))
     return (fpt, (Tout + fpt - 1) // fpt) if fpt > 0 else None
@@ -494,18 +524,19 @@ def headpool(xd16, pw, pooled16, part, B, Tin, Tout, gcols=16):
           tag="M%d N%d K256 headpool->T%d" % (B * Tin, pw.Npad, Tout))
 
 
+def _ln_lin256_ok(x32, ln_w, pw, epi, out):
+    return (_lin256_weight_ok(pw, epi) and out.dtype in (torch.float16, torch.bfloat16) and
+            x32.shape[0] >= 4096 and x32.dtype == torch.float32 and x32.stride(1) == 1 and x32.stride(0) % 4 == 0 and
+            x32.data_ptr() % 16 == 0 and ln_w.numel() == 256)
+
+
 def ln_linear16(x32, ln_w, ln_b, pw, epi=EPI_NONE, out_dtype=None, eps=1e-5):
     """linear16(LayerNorm(x32[:, :D]), pw, epi) with a 16-bit result, D = ln_w.numel().  On the shapes sfm_lin256 takes (D = K = 256,
     plain or GLU epilogue, M >= 4096) the LayerNorm is the GEMM kernel's prologue (sfm_ln_lin256): one launch, the normalised 16-bit rows
     never reach HBM; otherwise sfm_layernorm + linear16.  The two routes give the same bits."""
     M = x32.shape[0]
     out = torch.empty(M, pw.N, device=x32.device, dtype=out_dtype or _state["dtype"])
-    fused = (_LIN256["on"] and _state["gemm_variant"] == 0 and epi in (EPI_NONE, EPI_GLU) and (epi == EPI_GLU) == bool(pw.glu) and
-             pw.K == 256 and pw.Kpad == 256 and pw.ksize == 1 and pw.Npad % (128 if pw.glu else 64) == 0 and
-             pw.Npad == (2 * pw.N if pw.glu else pw.N) and pw.Npad <= 2048 and out.dtype in (torch.float16, torch.bfloat16) and
-             M >= 4096 and x32.dtype == torch.float32 and x32.stride(1) == 1 and x32.stride(0) % 4 == 0 and
-             x32.data_ptr() % 16 == 0 and ln_w.numel() == 256 and pw.w.dtype == _state["dtype"])
-    if fused:
+    if _ln_lin256_ok(x32, ln_w, pw, epi, out):
         _need_dev(x32, out)
         L = _lib.load()
         lw, lb = ln_w.detach().float().contiguous(), ln_b.detach().float().contiguous()
@@ -599,7 +630,7 @@ ATTN_QSCALE_LOG2E = 1.4426950408889634
 
 def attention_kernel_name(B, T, H, variant=None):
     """name of the forward kernel sfm_attention_fwd_ex picks for head_dim 64 (mirrors the rule in csrc/attention.hip)"""
-    v = _ATTN_VARIANT[0] if variant is None else variant
+    v = switch("attention_variant") if variant is None else variant
     nqt5 = (T + 511) // 512
     enough = B * H * nqt5 >= 128
     if v == 0:
@@ -620,21 +651,7 @@ def set_attention_variant(v):
     v = int(v)
     if not 0 <= v <= 6:
         raise ValueError("attention variant %d" % v)
-    _ATTN_VARIANT[0] = v
-
-
-_ATTN_VARIANT = [0]
-
-
-def variant_overrides():
-    """the kernel-selection test knobs that are NOT at their default (set_gemm_variant, set_attention_variant, SFM_GEMM_VARIANT):
-    bench.py refuses to time anything while one is active"""
-    out = {}
-    if _state["gemm_variant"] != 0:
-        out["gemm_variant"] = _state["gemm_variant"]
-    if _ATTN_VARIANT[0] != 0:
-        out["attention_variant"] = _ATTN_VARIANT[0]
-    return out
+    _SWITCHES["attention_variant"][2] = v
 
 
 def attention(qkv16, B, T, H, hd, out=None, prescaled=False, out_dtype=None):
@@ -650,7 +667,7 @@ def attention(qkv16, B, T, H, hd, out=None, prescaled=False, out_dtype=None):
         out = torch.empty(B * T, D, device=qkv16.device, dtype=out_dtype or qkv16.dtype)
     _call("attention_fwd", L.sfm_attention_fwd_ex, (_p(qkv16), _p(out), B, T, H, hd, ld, out.stride(0), D, 2 * D, T * ld,
                                                     T * out.stride(0), (-1.0 if prescaled else 1.0 / math.sqrt(hd)), _dt(),
-                                                    _DT_ID[out.dtype], _ATTN_VARIANT[0], _stream()),
+                                                    _DT_ID[out.dtype], switch("attention_variant"), _stream()),
           *_cost_of("attention_fwd", locals()))
     return out
 
@@ -1082,7 +1099,7 @@ def sum_time(src32, B, T, C, ld_src):
 
 def _tn_ws(L_, M, N, K, device):
     """(workspace, its size in floats) of the ordered M-split fold of the TN GEMMs, or (None, 0) in the atomics form"""
-    if not _DET["on"]:
+    if not switch("deterministic"):
         return None, 0
     n = int(L_.sfm_tn_ws_floats(M, N, K))
     return _ws(n, device), n
@@ -1137,7 +1154,7 @@ def gn_act_backward(dout, act, G, x1, sc1, sh1, mean1, rstd1, gamma1, x2=None, s
     work = torch.zeros(3 * B * C + 3 * C, device=dev, dtype=torch.float32)       # S [B][3][C] | dparam [3][C]
     S, dparam = work[:3 * B * C], work[3 * B * C:].view(3, C)
     nbytes = float(B * L * C) * ((4 if f32(dout) else 2) + (1 + two) * (4 if f32(x1) else 2))
-    ws = _ws(int(L_.sfm_gn_bwd_reduce_ws_floats(B, L, C)), dev) if _DET["on"] else None
+    ws = _ws(int(L_.sfm_gn_bwd_reduce_ws_floats(B, L, C)), dev) if switch("deterministic") else None
     _call("gn_bwd_reduce", L_.sfm_gn_bwd_reduce, (_p(dout), f32(dout), _p(x1), f32(x1), _p(sc1), _p(sh1), _p(mean1), _p(rstd1), _p(x2),
                                            f32(x2) if two else 0, _p(sc2), _p(sh2), _p(mean2), _p(rstd2), _p(S), B, L, C, G,
                                            int(act), _dt(), _p(ws), _stream()), 0.0, nbytes)
@@ -1168,7 +1185,7 @@ class wgrad_side_stream:
     exit the current stream waits for them."""
 
     def __init__(self, enabled=True):
-        self.enabled = enabled and _os.environ.get("SFM_WGRAD_STREAM", "1") != "0"
+        self.enabled = enabled and switch("wgrad_stream")
 
     def __enter__(self):
         if self.enabled:
@@ -1296,7 +1313,7 @@ def conv_dgrad16(dy16, weight, B, Lout, Lin, stride, pad, accumulate_into=None, 
 def colsum(G, out):
     L = _lib.load()
     M, N = G.shape
-    ws = _ws(int(L.sfm_colsum_ws_floats(M, N)), G.device) if _DET["on"] else None
+    ws = _ws(int(L.sfm_colsum_ws_floats(M, N)), G.device) if switch("deterministic") else None
     _call("colsum", L.sfm_colsum, (_p(G), _p(out), M, N, G.stride(0), 1 if G.dtype == torch.float32 else 0, _dt(), _p(ws), _stream()))
 
 
@@ -1309,7 +1326,7 @@ def layernorm_bwd(x32, gamma, dy, dres32, dgamma, dbeta, eps=1e-5, next_drop=Non
     if D > LAYERNORM_MAX_D:
         raise RuntimeError("layernorm_bwd: width %d is not supported (the LayerNorm kernels take D <= %d)" % (D, LAYERNORM_MAX_D))
     dx = torch.empty(M, D, device=dy.device, dtype=torch.float32)
-    ws = _ws(int(L.sfm_layernorm_bwd_ws_floats(M, D)), dy.device) if _DET["on"] else None
+    ws = _ws(int(L.sfm_layernorm_bwd_ws_floats(M, D)), dy.device) if switch("deterministic") else None
     dy16 = 0 if dy.dtype == torch.float32 else 1
     if dy16 and dy.dtype != _state["dtype"]:
         raise RuntimeError("layernorm_bwd: a 16-bit dy must be in the compute format")
@@ -1342,7 +1359,7 @@ def col_stats(y32, aux=None, mean=None, rstd=None):
     L = _lib.load()
     M, C = y32.shape
     S = torch.zeros(C, 2, device=y32.device, dtype=torch.float32)
-    ws = _ws(int(L.sfm_col_stats_ws_floats(M, C)), y32.device) if _DET["on"] else None
+    ws = _ws(int(L.sfm_col_stats_ws_floats(M, C)), y32.device) if switch("deterministic") else None
     _call("col_stats", L.sfm_col_stats, (_p(y32), _p(aux), _p(mean), _p(rstd), _p(S), M, C, _p(ws), _stream()))
     return S
 
@@ -1380,7 +1397,7 @@ def bn_swish_bwd(g, y32, mean, rstd, gamma, beta, eval_mode=False):
     S = torch.zeros(C, 2, device=y32.device, dtype=torch.float32)
     dy = torch.empty_like(y32)
     gf = 1 if g.dtype == torch.float32 else 0
-    ws = _ws(int(L.sfm_col_stats_ws_floats(M, C)), y32.device) if _DET["on"] else None
+    ws = _ws(int(L.sfm_col_stats_ws_floats(M, C)), y32.device) if switch("deterministic") else None
     for ps in (0, 1):
         Sx = torch.zeros_like(S) if (eval_mode and ps == 1) else S
         _call("bn_swish_bwd", L.sfm_bn_swish_bwd, (_p(g), _p(y32), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(Sx), _p(dy), M, C, gf,
@@ -1428,16 +1445,13 @@ def attention_bwd(qkv16, O16, dO16, lse, B, T, H, hd, p_drop=0.0, seed=0):
     return dqkv
 
 
-_LSTM = {"w16": _os.environ.get("SFM_LSTM_W16", "1") != "0"}
-
-
 def set_lstm_w16(flag):
     """inference BiLSTM recurrence on fp16 operands (sfm_bilstm_layer_ex, default on; SFM_LSTM_W16=0 / False = fp32 W_hh and h)"""
-    _LSTM["w16"] = bool(flag)
+    _SWITCHES["lstm_w16"][2] = bool(flag)
 
 
 def lstm_w16():
-    return _LSTM["w16"]
+    return switch("lstm_w16")
 
 
 def bilstm_layer(xg, whh, B, T, H, w16=False):
@@ -1461,7 +1475,7 @@ def bilstm_layer_train(xg, whh, B, T, H, w16=None):
     out = torch.empty(B, T, 2 * H, device=xg.device, dtype=torch.float32)
     save = torch.empty(B, T, 2, 5, H, device=xg.device, dtype=torch.float32)
     if w16 is None:
-        w16 = _LSTM["w16"] and _state["dtype"] == torch.float16
+        w16 = switch("lstm_w16") and _state["dtype"] == torch.float16
     if w16:
         _call("bilstm_layer", L.sfm_bilstm_layer_train_ex, (_p(xg), _p(whh), _p(out), _p(save), B, T, H, 1, _stream()))
     else:
@@ -1491,7 +1505,7 @@ def memory_bwd(emb, params, d_out, d_gate, key_dim, value_dim, slots, temperatur
     d_emb = torch.empty(Bn, key_dim, device=emb.device, dtype=torch.float32) if want_d_emb else None
     dparams = torch.zeros_like(params)
     ws = None
-    if _DET["on"]:
+    if switch("deterministic"):
         npar = int(L.sfm_memory_param_floats(key_dim, value_dim, slots))
         if npar != params.numel():
             raise RuntimeError("memory_bwd: the parameter blob has %d floats, the kernel's layout %d" % (params.numel(), npar))

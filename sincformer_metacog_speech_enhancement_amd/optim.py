@@ -4,7 +4,6 @@ with no host synchronisation: the clip coefficient, the skip decision and the bi
 on the device.  Data parallel: pass a dp.FlatGradSynchronizer; its buffer holds the SUM over ranks and 1/world
 is folded into the unscale factor.  DynamicLossScale = torch.amp.GradScaler of the reference's AMP branch
 (:442, 504, 512-517) with the scale, its growth / backoff and the Inf check kept on the device."""
-import os
 import torch
 
 from . import ops, dp as _dp
@@ -77,7 +76,7 @@ class FlatAdamW:
             raise RuntimeError("FlatAdamW: parameters must live on the MI355X (no CPU fallback)")
         self.lr, self.betas, self.eps, self.weight_decay, self.max_norm = lr, betas, eps, weight_decay, max_norm
         if steal_grads is None:
-            steal_grads = os.environ.get("SFM_STEAL_GRADS", "0") != "0"          # A/B knob
+            steal_grads = ops.switch("steal_grads")
         # steal_grads (opt-in: its A/B, profiles/r03/steal_grads_ab.txt, is inside the run-to-run noise, and it changes what
         # `p.grad` is between backward and step): autograd keeps the gradient tensors of the backward nodes and the synchronizer
         # gathers them into the flat buffer with a few cat launches (dp.FlatGradSynchronizer) instead of one aten add per

@@ -9,7 +9,6 @@ bit-identical: SURVEY H5); with p = 0 the gradients match torch autograd of the 
 compute dtype where they feed the matrix cores.
 """
 import math
-import os
 import torch
 
 from . import ops
@@ -62,9 +61,6 @@ class _Seeds:
 # ---------------------------------------------------------------------------
 # FeedForwardModule (models/conformer.py:41-49)
 # ---------------------------------------------------------------------------
-FUSE_FFN_SWISH = os.environ.get("SFM_FUSE_FFN_SWISH", "1") != "0"     # Swish (+ hidden dropout) of the FFN in the epilogues of its GEMMs (forward: dual output; backward)
-
-
 def _ffn_fwd(x, P, pre, p, seeds):
     dt = ops.compute_dtype()
     M, D = x.shape
@@ -73,7 +69,7 @@ def _ffn_fwd(x, P, pre, p, seeds):
     f2, b2 = _lin_pack(_f32(P[pre + "linear2.weight"]), _f32(P[pre + "linear2.bias"]))
     h16 = _ln16(x, lw, lb)
     s1, s2 = seeds.next(), seeds.next()
-    if FUSE_FFN_SWISH and f1.N % 8 == 0:
+    if ops.switch("fuse_ffn_swish") and f1.N % 8 == 0:
         # one epilogue writes u = dropout(swish(z)) and, in the slot of the pre-activation, the derivative factor
         # d = keep * swish'(z): the backward's epilogue is then a single multiply
         z1, u = ops.linear16_swish(h16, f1, p_drop=p, seed=s1)
@@ -83,9 +79,6 @@ def _ffn_fwd(x, P, pre, p, seeds):
         ops.ew_train(ops.EW_SWISH_FWD, u, z=z1, p=p, seed=s1)
     y = _resid_gemm(u, f2, x, 0.5, p, s2)                                 # x + 0.5 * dropout(linear2(u)), one launch
     return y, dict(x=x, lw=lw, h16=h16, z1=z1, u=u, b1=b1, b2=b2, s1=s1, s2=s2, p=p)
-
-
-FUSE_NEXT_DROP = os.environ.get("SFM_FUSE_NEXT_DROP", "1") != "0"     # A/B knob: the LayerNorm backward also writes the next node's 16-bit operand
 
 
 def _branch_grad(dy, do, alpha, p, seed):
@@ -99,7 +92,7 @@ def _branch_grad(dy, do, alpha, p, seed):
 
 def _ln_bwd_chain(x, lw, dh, dy, gw, gb, nxt):
     """LayerNorm backward at the end of a module's backward; nxt = (alpha, p, seed) of the NEXT node's branch dropout -> (dx, do16)"""
-    if nxt is not None and FUSE_NEXT_DROP:
+    if nxt is not None and ops.switch("fuse_next_drop"):
         return ops.layernorm_bwd(x, lw, dh, dy, gw, gb, next_drop=nxt)
     return ops.layernorm_bwd(x, lw, dh, dy, gw, gb), None
 
@@ -111,7 +104,7 @@ def _ffn_bwd(dy, c, G, pre, do=None, nxt=None):
     do = _branch_grad(dy, do, 0.5, c["p"], c["s2"])
     # input gradient first, weight gradient second: the K = 1024 weight-gradient GEMM launched right behind the streaming
     # ew_train ran 0.28 ms against 0.21 ms behind a GEMM (tools/ffn_bwd_probe.py --variant late; profiles/README.md, round 3)
-    if FUSE_FFN_SWISH and FF % 8 == 0:
+    if ops.switch("fuse_ffn_swish") and FF % 8 == 0:
         dz = ops.linear16_swish(do, c["b2"], p_drop=c["p"], seed=c["s1"], aux=c["z1"])   # (do W2) * d, d saved by the forward
     else:
         du = ops.linear16(do, c["b2"], out_dtype=torch.float32)             # [M, FF]

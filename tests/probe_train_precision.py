@@ -9,7 +9,7 @@ relative RMSE of every parameter gradient, for
   fp16            uniform fp16 operands, no loss scale
   fp16+S=2^k      fp16 operands, the loss multiplied by a static S  (what the dynamic scale settles at, swept)
   amp16           fp16 operands + optim.DynamicLossScale through FlatAdamW (lr 0): THE training format (bench.py, smoke())
-Also a 1-ulp sensitivity draw: the bf16 step twice with the Swish epilogue perturbed is NOT repeated here (tools/swish_sensitivity.py).
+Also a 1-ulp sensitivity draw: the bf16 step twice with the Swish epilogue perturbed is NOT repeated here (profiles/README.md, round 3).
 Lives under tests/ because it uses the oracle (test infrastructure)."""
 import json
 import math

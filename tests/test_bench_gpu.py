@@ -77,9 +77,10 @@ def test_bench_default_line_is_on_the_metrics_shape_and_carries_configs1_and_tra
     assert not t["optimizer_state"]["skipped"]
 
 
-def test_bench_refuses_to_time_with_a_variant_override():
+@pytest.mark.parametrize("var,value", [("SFM_GEMM_VARIANT", "9"), ("SFM_LIN256", "0"), ("SFM_LSTM_BWD_LPU", "8")])
+def test_bench_refuses_to_time_with_a_variant_override(var, value):
     e = dict(os.environ)
-    e["SFM_GEMM_VARIANT"] = "9"
+    e[var] = value
     r = subprocess.run([sys.executable, "bench.py", "--workload", "c1", "--steps", "1", "--warmup", "1", "--no-cpu-baseline",
                         "--no-sustained"], cwd=ROOT, env=e, capture_output=True, text=True, timeout=300)
     assert r.returncode != 0 and "variant override" in (r.stderr + r.stdout)

@@ -1,6 +1,10 @@
 """CPU-only checks of the host side: interface mirrors (names, ctor semantics, state_dict
 contract), weight packing, DFT operands, synthetic data determinism, no-CPU-fallback rule."""
+import json
 import math
+import os
+import subprocess
+import sys
 import numpy as np
 import pytest
 import torch
@@ -256,6 +260,88 @@ def test_lin256_routing_rule():
     finally:
         ops.set_lin256(True)
         ops.reset_precision() if hasattr(ops, "reset_precision") else None
+
+
+def test_lin256_routing_callers_agree():
+    """linear16 (ops._lin256_ok) and ln_linear16 (ops._ln_lin256_ok) share the switch / weight / epilogue half of the rule
+    (ops._lin256_weight_ok): on the (pack, epilogue) cases of test_lin256_routing_rule, each with operands its own half accepts,
+    the two give the same answer; a LayerNorm wider than 256 stays off the fused kernel.  (Host logic only: no launch.)"""
+    ops.set_compute_dtype(torch.float16)
+    try:
+        pw = ops.pack_linear(torch.randn(768, 256), torch.randn(768))
+        pg = ops.pack_linear(torch.randn(512, 256), torch.randn(512), glu=True)
+        p1024 = ops.pack_linear(torch.randn(256, 1024), torch.randn(256))
+        pbf = ops.pack_linear(torch.randn(768, 256), torch.randn(768))
+        pbf.w = pbf.w.to(torch.bfloat16)                                       # weight not in the stage's format
+        x16, x32, ln_w = torch.empty(8192, 256, dtype=torch.float16), torch.empty(8192, 256), torch.ones(256)
+        cases = [(pw, ops.EPI_NONE, True), (pg, ops.EPI_GLU, True), (pg, ops.EPI_NONE, False), (pw, ops.EPI_GLU, False),
+                 (pw, ops.EPI_RESID, False), (pw, ops.EPI_SWISH, False), (p1024, ops.EPI_NONE, False), (pbf, ops.EPI_NONE, False)]
+
+        def both(p, epi):
+            out = torch.empty(8192, p.N, dtype=torch.float16)
+            xk = x16 if p.K == 256 else torch.empty(8192, p.K, dtype=torch.float16)
+            return ops._lin256_ok(xk, p, epi, out, None, 0, 0.0), ops._ln_lin256_ok(x32, ln_w, p, epi, out)
+
+        for p, epi, want in cases:
+            assert both(p, epi) == (want, want), (p.N, p.K, epi)
+        try:
+            for setter, off in ((ops.set_lin256, False), (ops.set_gemm_variant, 2)):
+                setter(off)
+                assert both(pw, ops.EPI_NONE) == (False, False) and both(pg, ops.EPI_GLU) == (False, False)
+                ops.set_lin256(True), ops.set_gemm_variant(0)
+        finally:
+            ops.set_lin256(True), ops.set_gemm_variant(0)
+        o16 = torch.empty(8192, 768, dtype=torch.float16)
+        assert not ops._ln_lin256_ok(torch.empty(8192, 512), torch.ones(512), pw, ops.EPI_NONE, o16)   # D > 256: two launches
+    finally:
+        ops.reset_precision()
+
+
+_SWITCH_SETTERS = [("gemm_variant", ops.set_gemm_variant, 9, 0), ("attention_variant", ops.set_attention_variant, 3, 0),
+                   ("lin256", ops.set_lin256, False, True), ("headpool", ops.set_headpool, False, True),
+                   ("lstm_w16", ops.set_lstm_w16, False, True), ("deterministic", ops.set_deterministic, False, True)]
+_SWITCH_ENV = [("SFM_GEMM_VARIANT", "9", "gemm_variant", 9), ("SFM_LIN256", "0", "lin256", False),
+               ("SFM_HEADPOOL", "0", "headpool", False), ("SFM_LSTM_W16", "0", "lstm_w16", False),
+               ("SFM_DETERMINISTIC", "0", "deterministic", False), ("SFM_WGRAD_STREAM", "0", "wgrad_stream", False),
+               ("SFM_FUSE_FFN_SWISH", "0", "fuse_ffn_swish", False), ("SFM_FUSE_NEXT_DROP", "0", "fuse_next_drop", False),
+               ("SFM_STEAL_GRADS", "1", "steal_grads", True), ("SFM_LSTM_BWD_LPU", "8", "lstm_bwd_lpu", 8)]
+
+
+def _overrides_in_child(env):
+    e = {k: v for k, v in os.environ.items() if not k.startswith("SFM_")}
+    e.update(env)
+    code = "import json; from sincformer_metacog_speech_enhancement_amd import ops; print(json.dumps(ops.variant_overrides()))"
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "-c", code], cwd=root, env=e, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    return json.loads(r.stdout.strip().splitlines()[-1])
+
+
+def test_variant_overrides_is_empty_in_a_clean_environment():
+    assert _overrides_in_child({}) == {}
+    assert {sw[0] for sw in ops._SWITCHES.values()} - {None} == {e[0] for e in _SWITCH_ENV}   # the child cases below cover the table
+
+
+@pytest.mark.parametrize("name,setter,off,default", _SWITCH_SETTERS, ids=[s[0] for s in _SWITCH_SETTERS])
+def test_variant_overrides_reports_a_setter_off_its_default(name, setter, off, default):
+    before = ops.variant_overrides()
+    assert name not in before
+    try:
+        setter(off)
+        assert ops.variant_overrides() == dict(before, **{name: off})
+    finally:
+        setter(default)
+    assert ops.variant_overrides() == before
+
+
+@pytest.mark.parametrize("var,value,name,want", _SWITCH_ENV, ids=[e[0] for e in _SWITCH_ENV])
+def test_variant_overrides_reports_an_environment_variable(var, value, name, want):
+    assert _overrides_in_child({var: value}) == {name: want}
+
+
+def test_variant_overrides_ignores_the_library_path():
+    """SFM_LIB_PATH is the documented way to time another build with bench.py: not a switch"""
+    assert _overrides_in_child({"SFM_LIB_PATH": "/nonexistent/libsincformer_hip.so"}) == {}
 
 
 def test_width_bounds_separate_plausible_wrong_answers():

@@ -1,6 +1,5 @@
 """Forward-type GEMMs of the training step at M = B x T rows (fused-Swish FFN Linear forward / backward, residual and plain epilogues):
-    python tools/gemm_train_bench.py [--rows 205056] [--iters 10]
-A/B knobs are process-wide environment variables (SFM_SWISH_VARIANT), so run the tool once per setting."""
+    python tools/gemm_train_bench.py [--rows 205056] [--iters 10]"""
 import argparse
 import os
 import sys

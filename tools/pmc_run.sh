@@ -1,6 +1,6 @@
 #!/bin/bash
 # rocprofv3 PMC passes (two counter sets, counters only - no trace domains) over one python tool, summed per kernel whose
-# name contains SUBSTR.    usage (on the GPU box): tools/pmc_run.sh <tag> <SUBSTR> tools/ffn_stamps.py f16
+# name contains SUBSTR.    usage (on the GPU box): tools/pmc_run.sh <tag> <SUBSTR> tools/ffn_bench.py
 cd /tmp && export TMPDIR=/tmp
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 tag=$1; sub=$2; shift 2
