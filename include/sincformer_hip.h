@@ -512,6 +512,23 @@ long long sfm_memory_param_floats(int key_dim, int value_dim, int slots);
 int sfm_memory_bwd(const float* emb, const float* params, const float* d_out, const float* d_gate, float* d_emb,
                    float* dparams, int B, int key_dim, int value_dim, int slots, float temperature, float* ws, void* stream);
 
+/* Stage objectives of the curriculum (training/losses.py:22-143; curriculum_losses.hip).  Both write the scalar loss to loss[0]
+ * and, when a gradient pointer is given, EVERY element of the gradient (callers need not zero it) in the same launch.  Sums over
+ * workgroups go through `ws` (required; scratch, destroyed) and the ordered fold: no atomics, bit-reproducible.
+ * sfm_pstoi_loss: loss = -mean over (B, NB, S = T / frame_len) of the correlation of the mean-removed, clipped band envelopes.
+ *   layout 0: e0 / c0 = enhanced / clean magnitudes [B, F, T]; e1 = c1 = g1 = NULL; g0 (or NULL) [B, F, T].
+ *   layout 1: (e0, e1) / (c0, c1) = (real, imag) of enhanced / clean, channels-last [B, T, F]; the magnitude is
+ *     sqrt(re^2 + im^2 + 1e-8); (g0, g1) both or neither, [B, T, F].
+ *   band_w [NB, F] dense (rows may overlap); beta_db = the clip level in dB (10^(beta / 20) x the clean energy).
+ *   The clean side gets no gradient.  Frames t >= S * frame_len are unused and get gradient 0.
+ *   ws >= B * S + 1 doubles.  SFM_ERR_SHAPE: NB > 32, F > 257, frame_len outside 2..32, T < frame_len, B * S > 2^31 - 1.
+ * sfm_mse_loss: loss = mean (pred - target)^2 over n elements, summed in double; grad (or NULL) = 2 (pred - target) / n.
+ *   ws >= 1025 doubles. */
+int sfm_pstoi_loss(const float* e0, const float* e1, const float* c0, const float* c1, const float* band_w, float* loss,
+                   float* g0, float* g1, double* ws, int B, int T, int F, int NB, int frame_len, float beta_db, int layout,
+                   void* stream);
+int sfm_mse_loss(const float* pred, const float* target, float* loss, float* grad, double* ws, long long n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,3 +26,8 @@ PA_ENCODER_CHANNELS = 256
 VQ_NUM_CENTROIDS = 3
 VQ_COMMITMENT_WEIGHT = 0.25
 MAA_THRESHOLD_INIT = 0.5
+
+# curriculum stages in epochs (config.py:120-122 of the reference)
+CURRICULUM_STAGE1_EPOCHS = 15
+CURRICULUM_STAGE2_EPOCHS = 20
+CURRICULUM_STAGE3_EPOCHS = 15

@@ -146,6 +146,9 @@ SIGNATURES = {
     "sfm_attention_fwd_varlen": [c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_vp],
     "sfm_dwconv_folded_varlen": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_vp],
     "sfm_istft_ola_varlen": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_ll, c_vp],
+    # stage objectives of the curriculum
+    "sfm_pstoi_loss": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_vp],
+    "sfm_mse_loss": [c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, c_vp],
 }
 
 _lib = None

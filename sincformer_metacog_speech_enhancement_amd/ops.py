@@ -1047,6 +1047,65 @@ def lsd_frames_varlen(cr, ci, er, ei, frame_off, B):
     return acc
 
 
+def _ws64(n, device):
+    """float64 scratch of >= n elements for an entry point that has no atomics form (the ordered fold is its only path)"""
+    t = _ws(n, device, torch.float64)
+    return t if t is not None else torch.empty(int(n), device=device, dtype=torch.float64)
+
+
+def pstoi_loss(enh, clean, band_w, need_grad=False, frame_len=30, beta=15.0):
+    """PerceptualSTOILoss (training/losses.py:89-143) in one launch.  enh / clean: fp32 contiguous magnitudes [B, F, T], or
+    (real, imag) pairs of channels-last [B, T, F] tensors; band_w [NB, F].  -> (loss [1] fp32, gradient to enh or None: one
+    tensor or a (real, imag) pair, every element written)."""
+    pair = isinstance(enh, (tuple, list))
+    e0, e1 = enh if pair else (enh, None)
+    c0, c1 = clean if pair else (clean, None)
+    _need_dev(e0, e1, c0, c1, band_w)
+    L = _lib.load()
+    if pair:
+        B, T, F = e0.shape
+    else:
+        B, F, T = e0.shape
+    NB = band_w.shape[0]
+    FL = int(frame_len)
+    if band_w.shape[1] != F or c0.shape != e0.shape or NB > 32 or F > 257 or not 2 <= FL <= 32 or T < FL:
+        _lib.check(-2, "pstoi_loss")
+    loss = torch.empty(1, device=e0.device, dtype=torch.float32)
+    g0 = torch.empty_like(e0) if need_grad else None
+    g1 = torch.empty_like(e0) if need_grad and pair else None
+    S = T // FL
+    n = e0.numel()
+    _call("pstoi_loss", L.sfm_pstoi_loss, (_p(e0), _p(e1), _p(c0), _p(c1), _p(band_w), _p(loss), _p(g0), _p(g1),
+                                           _p(_ws64(B * S + 1, e0.device)), B, T, F, NB, FL, float(beta), 1 if pair else 0,
+                                           _stream()),
+          (6.0 if need_grad else 4.0) * NB * F * B * S * FL,
+          pstoi_bytes(B, T, F, FL, pair, need_grad))
+    return loss, ((g0, g1) if pair else g0) if need_grad else None
+
+
+def pstoi_bytes(B, T, F, frame_len, pair, need_grad):
+    """bytes one sfm_pstoi_loss launch has to move: each used input element read once (the pair form reads re, im of the
+    enhanced side again for the gradient), each gradient element written once"""
+    used, every = 4.0 * B * (T // frame_len) * frame_len * F, 4.0 * B * T * F
+    if pair:
+        return 4 * used + ((2 * used + 2 * every) if need_grad else 0.0)
+    return 2 * used + (every if need_grad else 0.0)
+
+
+def mse_loss(pred, target, need_grad=False):
+    """nn.MSELoss() of two fp32 contiguous tensors of one shape -> (loss [1] fp32, 2 (pred - target) / n or None)"""
+    _need_dev(pred, target)
+    L = _lib.load()
+    if pred.shape != target.shape or pred.numel() == 0:
+        _lib.check(-2, "mse_loss")
+    loss = torch.empty(1, device=pred.device, dtype=torch.float32)
+    grad = torch.empty_like(pred) if need_grad else None
+    n = pred.numel()
+    _call("mse_loss", L.sfm_mse_loss, (_p(pred), _p(target), _p(loss), _p(grad), _p(_ws64(1025, pred.device)), n, _stream()),
+          3.0 * n, (12.0 if need_grad else 8.0) * n)
+    return loss, grad
+
+
 def spec_sums(pr, pi, tr, ti, out=None):
     L = _lib.load()
     S = torch.zeros(4, device=pr.device, dtype=torch.float64) if out is None else out

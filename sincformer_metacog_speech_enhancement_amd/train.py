@@ -615,6 +615,51 @@ class L1MagnitudeFunction(torch.autograd.Function):
         return (d_er * g.float()).to(ctx.dtypes[0]), (d_ei * g.float()).to(ctx.dtypes[1]), None, None
 
 
+class PerceptualStoiFunction(torch.autograd.Function):
+    """PerceptualSTOILoss.forward (training/losses.py:89-143) in one launch.  layout 0: enh / clean are magnitudes
+    [B, F, T] (enh_im = clean_im = None); layout 1: (enh, enh_im) / (clean, clean_im) are (real, imag) of channels-last
+    [B, T, F] spectra.  The gradient goes to the enhanced side only (the clean side is a target and gets None), and is
+    produced by the forward launch when an enhanced input requires it."""
+
+    @staticmethod
+    def forward(ctx, enh, enh_im, clean, clean_im, band_w, frame_len, beta):
+        pair = enh_im is not None
+        f32 = lambda t: t.detach().float().contiguous()
+        e = (f32(enh), f32(enh_im)) if pair else f32(enh)
+        c = (f32(clean), f32(clean_im)) if pair else f32(clean)
+        need = enh.requires_grad or (pair and enh_im.requires_grad)
+        loss, grad = ops.pstoi_loss(e, c, f32(band_w), need_grad=need, frame_len=frame_len, beta=beta)
+        ctx.grads = grad if (grad is None or pair) else (grad, None)
+        ctx.dtypes = (enh.dtype, enh_im.dtype if pair else None)
+        return loss[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.grads is None:
+            return (None,) * 7
+        d0, d1 = ctx.grads
+        ctx.grads = None
+        g = g.float()
+        return ((d0 * g).to(ctx.dtypes[0]), None if d1 is None else (d1 * g).to(ctx.dtypes[1]), None, None, None, None, None)
+
+
+class MseFunction(torch.autograd.Function):
+    """nn.MSELoss() (MSEMaskLoss, training/losses.py:22-30): mean squared difference, summed in double in a fixed order.
+    The gradient goes to `predicted` only; `target` gets None."""
+
+    @staticmethod
+    def forward(ctx, predicted, target):
+        p, t = predicted.detach().float().contiguous(), target.detach().float().contiguous()
+        loss, grad = ops.mse_loss(p, t, need_grad=predicted.requires_grad)
+        ctx.grad, ctx.dtype = grad, predicted.dtype
+        return loss[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        d, ctx.grad = ctx.grad, None
+        return (None if d is None else (d * g.float()).to(ctx.dtype)), None
+
+
 class ComplexMulFunction(torch.autograd.Function):
     """ComplexConformer.apply_mask (models/conformer.py:230-245) with its backward: the gradient of a complex product
     is the incoming gradient times the conjugate of the other factor — the same HIP kernel."""

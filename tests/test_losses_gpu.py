@@ -1,0 +1,319 @@
+"""The curriculum objectives on the device (curriculum_losses.hip through training.PerceptualSTOILoss / MSEMaskLoss) against
+the float64 restatement of tests/loss_cases.py, on every case and in both input forms: [B, F, T] magnitudes (form 0) and
+channels-last (real, imag) pairs (form 1; the restatement takes the magnitudes of the pairs and autograd carries the gradient
+to real and imag).
+
+Bounds come from the restatement alone, by the rule of tests/test_train_nodes_gpu.py: e32 = the float32 evaluation of the
+restatement on the CPU against the float64 one; the gradient (relative RMSE, max|err| / max|ref|) within 16 x e32 - the
+formula sits behind sqrt and a reciprocal -, the loss within max(16 x e32, 16 x 2^-24): a correlation is at most 1 in
+magnitude, so that is the same factor on one ulp of 1.0, and a lucky e32 must not set a bound below rounding.  MSEMaskLoss
+only adds and multiplies: 4 x e32 (the loss: or one rounding of the fp32 result, 2^-24 |loss|, where that is larger).
+Every row prints `ROW | name | e32 | bound | observed`; profiles/README.md keeps the table.
+
+c6 (all zero): in form 0 the loss is exactly 0; in form 1 the magnitudes are sqrt(1e-8), constant, and what the mean removal
+leaves of a constant in fp32 (a few 1e-12) decides the loss: there the row's bound applies.  The gradient is exactly 0 in both."""
+import math
+
+import pytest
+import torch
+
+import helpers as hp
+import loss_cases as lc
+
+pytestmark = pytest.mark.gpu
+NAN = float("nan")
+FORMS = (0, 1)
+
+
+@pytest.fixture(scope="module")
+def mods():
+    assert torch.cuda.is_available()
+    from sincformer_metacog_speech_enhancement_amd import ops, train
+    from sincformer_metacog_speech_enhancement_amd.training import MSEMaskLoss, PerceptualSTOILoss
+    return {"ops": ops, "train": train, "pstoi": PerceptualSTOILoss, "mse": MSEMaskLoss}
+
+
+def _module(mods, name):
+    m = mods["pstoi"]().cuda()
+    m.band_weights = lc.weights(name).cuda()
+    return m
+
+
+def _inputs(name, form, dtype=torch.float32):
+    """device leaves (enhanced side requiring grad) and the clean side of a case"""
+    c = lc.case(name)
+    if form == 0:
+        return [c["enh"].cuda().to(dtype).requires_grad_(True)], [c["clean"].cuda().to(dtype)]
+    er, ei, cr, ci = (t.cuda().to(dtype) for t in lc.pairs(c))
+    return [er.requires_grad_(True), ei.requires_grad_(True)], [cr, ci]
+
+
+def _run(mods, name, form, scale=None, dtype=torch.float32):
+    """(loss, gradient as the restatement stacks it) through the module and autograd"""
+    enh, clean = _inputs(name, form, dtype)
+    m = _module(mods, name)
+    loss = m(enh[0], clean[0]) if form == 0 else m.forward_cl(enh[0], enh[1], clean[0], clean[1])
+    (loss if scale is None else scale * loss).backward()
+    return loss.detach(), (enh[0].grad if form == 0 else torch.stack([enh[0].grad, enh[1].grad]))
+
+
+def _loss_bound(l32, l64):
+    e32 = abs(float(l32) - float(l64))
+    return e32, max(hp.K_TRANS * e32, hp.K_TRANS * hp.U32)
+
+
+@pytest.mark.parametrize("form", FORMS)
+@pytest.mark.parametrize("name", list(lc.CASES))
+def test_parity(mods, name, form):
+    l64, g64 = lc.reference(name, form, torch.float64)
+    l32, g32 = lc.reference(name, form, torch.float32)
+    loss, grad = _run(mods, name, form)
+    e32, bound = _loss_bound(l32, l64)
+    obs = abs(float(loss) - float(l64))
+    print("ROW | pstoi loss %s form %d | e32 %.2e | bound %.2e | observed %.2e" % (name, form, e32, bound, obs))
+    assert math.isfinite(float(loss)) and obs <= bound
+    assert bool(torch.isfinite(grad).all())
+    hp.check_row("pstoi grad %s form %d" % (name, form), grad.cpu(), g64, g32, hp.K_TRANS)
+    if name == "c6_all_zero":
+        assert bool((grad == 0).all())
+        if form == 0:
+            assert float(loss) == 0.0
+
+
+@pytest.mark.parametrize("form", FORMS)
+@pytest.mark.parametrize("name", ["c2_tail_loud_flat", "c3_five_tail_frames"])
+def test_every_gradient_element_is_written(mods, name, form):
+    """the kernel's own output buffers, pre-filled with NaN: none is left, and the frames no segment uses are exactly 0"""
+    ops = mods["ops"]
+    c = lc.case(name)
+    w = c["w"].cuda()
+    T = lc.CASES[name][1]
+    used = T // lc.FRAME_LEN * lc.FRAME_LEN
+    if form == 0:
+        e0, c0 = c["enh"].cuda(), c["clean"].cuda()
+        g0 = torch.full_like(e0, NAN)
+        args = (e0, None, c0, None, g0, None)
+    else:
+        er, ei, cr, ci = (t.cuda() for t in lc.pairs(c))
+        g0, g1 = torch.full_like(er, NAN), torch.full_like(er, NAN)
+        args = (er, ei, cr, ci, g0, g1)
+    B, F = c["enh"].shape[:2]
+    L = ops._lib.load()
+    loss = torch.full((1,), NAN, device="cuda")
+    ws = torch.empty(B * (T // lc.FRAME_LEN) + 1, device="cuda", dtype=torch.float64)
+    p = ops._p
+    rc = L.sfm_pstoi_loss(p(args[0]), p(args[1]), p(args[2]), p(args[3]), p(w), p(loss), p(args[4]), p(args[5]), p(ws), B, T, F,
+                          w.shape[0], lc.FRAME_LEN, lc.BETA_DB, form, ops._stream())
+    assert rc == 0
+    torch.cuda.synchronize()
+    assert math.isfinite(float(loss))
+    for g in args[4:]:
+        if g is None:
+            continue
+        assert not bool(torch.isnan(g).any())
+        tail = g[:, :, used:] if form == 0 else g[:, used:, :]
+        assert tail.numel() > 0 and bool((tail == 0).all())
+        assert bool((g != 0).any())
+
+
+@pytest.mark.parametrize("form", FORMS)
+def test_bins_of_no_band_get_exactly_zero(mods, form):
+    """c4 (16 kHz): band 0 is empty, and the bins outside every band have gradient exactly 0"""
+    name = "c4_empty_band_16k"
+    w = lc.weights(name)
+    assert not w[0].any()
+    free = ~(w > 0).any(dim=0)
+    assert int(free.sum()) > 0
+    _, grad = _run(mods, name, form)
+    g = grad[:, free, :] if form == 0 else grad[..., free]
+    assert bool((g == 0).all())
+    covered = grad[:, ~free, :] if form == 0 else grad[..., ~free]
+    assert bool((covered != 0).any())
+
+
+@pytest.mark.parametrize("form", FORMS)
+def test_batch_independence(mods, form):
+    """utterance 0 of c3 inside its batch and scored alone.  A workgroup sees one utterance, so d corr / d x is the same bits
+    either way and only the factor -1 / (B NB S) differs.  Inside a batch of 4 (utterances 0, 1, 2, 1) that factor is the
+    lone one's times 2^-2, exactly: 4 x the batch's gradient is bitwise the lone gradient.  Inside the case's own batch of 3
+    the factors 1 / 126 and 1 / 42 are each rounded to fp32 and no fp32 evaluation can make 3 x fl(x / 126) the bits of
+    fl(x / 42) for every x: there the two sides differ by the roundings alone, each at most 2^-24 relative - the two
+    factors, the two products with them and the test's own multiplication by 3 (five; form 1 divides re * d by the magnitude
+    on either side, four more) -, so the bound is 6 x 2^-24 |g| for form 0 and 10 x 2^-24 |g| for form 1."""
+    name = "c3_five_tail_frames"
+    m = _module(mods, name)
+    enh, clean = _inputs(name, form)
+
+    def run(rows):
+        e = [t.detach()[rows].contiguous().requires_grad_(True) for t in enh]
+        c = [t[rows].contiguous() for t in clean]
+        (m(e[0], c[0]) if form == 0 else m.forward_cl(e[0], e[1], c[0], c[1])).backward()
+        return [t.grad for t in e]
+    alone, four, three = run([0]), run([0, 1, 2, 1]), run([0, 1, 2])
+    k = (6 if form == 0 else 10) * 2.0 ** -24
+    for a, f, t in zip(alone, four, three):
+        assert bool((a[0] != 0).any())
+        assert torch.equal(f[0] * 4, a[0])
+        assert bool(((t[0] * 3 - a[0]).abs() <= k * a[0].abs()).all())
+
+
+@pytest.mark.parametrize("form", FORMS)
+def test_two_runs_are_bitwise_equal(mods, form):
+    name = "c7_many_partials"
+    l1, g1 = _run(mods, name, form)
+    l2, g2 = _run(mods, name, form)
+    assert torch.equal(l1, l2) and torch.equal(g1, g2)
+
+
+@pytest.mark.parametrize("form", FORMS)
+def test_backward_scales_by_the_incoming_gradient(mods, form):
+    name = "c2_tail_loud_flat"
+    _, g1 = _run(mods, name, form)
+    _, g3 = _run(mods, name, form, scale=3.0)
+    assert torch.equal(g3, g1 * 3.0)
+
+
+@pytest.mark.parametrize("form", FORMS)
+def test_non_contiguous_and_fp16_inputs(mods, form):
+    """a transposed view and an fp16 tensor are accepted; the gradient comes back in the input's dtype and equals the
+    gradient of the contiguous fp32 copy of the same values"""
+    name = "c2_tail_loud_flat"
+    m = _module(mods, name)
+    enh, clean = _inputs(name, form)
+    base = [t.detach().transpose(1, 2).contiguous().requires_grad_(True) for t in enh]        # leaves in the other layout
+    views = [t.transpose(1, 2) for t in base]
+    assert not views[0].is_contiguous()
+    (m(views[0], clean[0]) if form == 0 else m.forward_cl(views[0], views[1], clean[0], clean[1])).backward()
+    _, ref = _run(mods, name, form)
+    got = base[0].grad.transpose(1, 2) if form == 0 else torch.stack([t.grad.transpose(1, 2) for t in base])
+    assert torch.equal(got, ref)
+    half = [t.detach().half().requires_grad_(True) for t in enh]
+    loss = m(half[0], clean[0]) if form == 0 else m.forward_cl(half[0], half[1], clean[0], clean[1])
+    loss.backward()
+    assert all(t.grad is not None and t.grad.dtype == torch.float16 and bool(torch.isfinite(t.grad).all()) for t in half)
+    back = [t.detach().float().requires_grad_(True) for t in half]
+    (m(back[0], clean[0]) if form == 0 else m.forward_cl(back[0], back[1], clean[0], clean[1])).backward()
+    assert all(torch.equal(h.grad, b.grad.half()) for h, b in zip(half, back))
+
+
+def test_clean_side_gets_no_gradient(mods):
+    name = "c1_one_segment"
+    m = _module(mods, name)
+    c = lc.case(name)
+    e, cl = c["enh"].cuda().requires_grad_(True), c["clean"].cuda().requires_grad_(True)
+    m(e, cl).backward()
+    assert e.grad is not None and cl.grad is None
+    with torch.no_grad():
+        assert not m(e, cl).requires_grad
+
+
+@pytest.mark.parametrize("shape", [(2, 61, 129), (70001,)], ids=str)
+def test_mse_mask_loss(mods, shape):
+    """value and gradient against float64; n = 70001 walks the grid-stride loop (69 workgroups of 256 threads)"""
+    p, t = lc.mse_case(shape, 161)
+    p64 = p.double().requires_grad_(True)
+    l64 = lc.mse(p64, t.double())
+    l64.backward()
+    p32 = p.clone().requires_grad_(True)
+    l32 = lc.mse(p32, t)
+    l32.backward()
+    pd = p.cuda().requires_grad_(True)
+    loss = mods["mse"]()(pd, t.cuda())
+    loss.backward()
+    e32 = abs(float(l32) - float(l64))
+    bound = max(hp.K_SUM * e32, hp.U32 * abs(float(l64)))
+    obs = abs(float(loss) - float(l64))
+    print("ROW | mse loss %s | e32 %.2e | bound %.2e | observed %.2e" % (shape, e32, bound, obs))
+    assert obs <= bound
+    hp.check_row("mse grad %s" % (shape,), pd.grad.cpu(), p64.grad, p32.grad, hp.K_SUM)
+    g = torch.full_like(pd, NAN)
+    _, g2 = mods["ops"].mse_loss(pd.detach(), t.cuda(), need_grad=True)
+    assert torch.equal(g2, pd.grad) and not bool(torch.isnan(g2).any()) and g.shape == g2.shape
+    pd2 = p.cuda().requires_grad_(True)
+    (mods["mse"]()(pd2, t.cuda()) * 3.0).backward()
+    assert torch.equal(pd2.grad, pd.grad * 3.0)
+    ph = p.cuda().half().requires_grad_(True)
+    mods["mse"]()(ph, t.cuda().half()).backward()
+    assert ph.grad.dtype == torch.float16
+
+
+def test_guards_raise_before_any_launch(mods):
+    m = mods["pstoi"]().cuda()
+    x29 = torch.rand(1, 129, 29, device="cuda")
+    with pytest.raises(ValueError, match="30-frame segment"):
+        m(x29, x29)
+    with pytest.raises(ValueError, match="30-frame segment"):
+        m.forward_cl(*([x29.transpose(1, 2).contiguous()] * 4))
+    wide = mods["pstoi"]().cuda()
+    wide.band_weights = torch.rand(14, 258, device="cuda")
+    x = torch.rand(1, 258, 30, device="cuda")
+    with pytest.raises(ValueError):
+        wide(x, x)
+    many = mods["pstoi"]().cuda()
+    many.band_weights = torch.rand(33, 129, device="cuda")
+    x = torch.rand(1, 129, 30, device="cuda")
+    with pytest.raises(ValueError):
+        many(x, x)
+    with pytest.raises(RuntimeError):                              # the wrapper refuses as well, before the call
+        mods["ops"].pstoi_loss(x, x, many.band_weights)
+    with pytest.raises(RuntimeError, match="CPU"):
+        m(x.cpu(), x.cpu())
+    with pytest.raises(RuntimeError, match="CPU"):
+        mods["mse"]()(x.cpu(), x.cpu())
+    other = mods["pstoi"]().cuda()
+    other.frame_len = 33
+    with pytest.raises(NotImplementedError):
+        other(x, x)
+
+
+def test_frame_len_and_beta_reach_the_kernel(mods):
+    """frame_len 20 and beta 3 dB (everything loud clips harder) against the restatement with the same two scalars"""
+    name = "c3_five_tail_frames"
+    c = lc.case(name)
+    m = _module(mods, name)
+    m.frame_len, m.beta = 20, 3.0
+    e = c["enh"].cuda().requires_grad_(True)
+    loss = m(e, c["clean"].cuda())
+    loss.backward()
+    refs = []
+    for dt in (torch.float64, torch.float32):
+        x = c["enh"].to(dt).clone().requires_grad_(True)
+        l = lc.pstoi(x, c["clean"].to(dt), c["w"].to(dt), frame_len=20, beta=3.0)
+        l.backward()
+        refs.append((l.detach(), x.grad))
+    e32, bound = _loss_bound(refs[1][0], refs[0][0])
+    assert abs(float(loss) - float(refs[0][0])) <= bound
+    hp.check_row("pstoi grad frame_len 20 beta 3", e.grad.cpu(), refs[0][1], refs[1][1], hp.K_TRANS)
+
+
+def test_composition_with_the_enhancer(mods):
+    """a tiny SpeechEnhancer in train() mode, B 2 x T 61: forward_cl on its outputs plus MSEMaskLoss on mask_mag, one
+    backward: finite gradients on every parameter, and the gradient reaching enh_real / enh_imag is the restatement's"""
+    from sincformer_metacog_speech_enhancement_amd import synthetic as syn
+    from sincformer_metacog_speech_enhancement_amd.training.conformer_pipeline import SpeechEnhancer
+    name = "c2_tail_loud_flat"
+    torch.manual_seed(5)
+    model = SpeechEnhancer(n_freq=129, d_model=64, num_blocks=1, num_heads=2, d_ff=128, dropout=0.0)
+    shapes = {k: tuple(v.shape) for k, v in model.state_dict().items()}
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in syn.synth_state_dict(shapes, 99).items()})
+    model.cuda().train()
+    c = lc.case(name)
+    nr, ni, cr, ci = (t.cuda() for t in lc.pairs(c))
+    er, ei, mask_mag = model(nr, ni)
+    er.retain_grad(), ei.retain_grad()
+    crit, mse = _module(mods, name), mods["mse"]().cuda()
+    oracle_mask = torch.rand_like(mask_mag)
+    total = crit.forward_cl(er, ei, cr, ci) + mse(mask_mag, oracle_mask)
+    assert math.isfinite(float(total))
+    total.backward()
+    for k, p in model.named_parameters():
+        assert p.grad is not None and bool(torch.isfinite(p.grad).all()), k
+    assert any(bool((p.grad != 0).any()) for p in model.parameters())
+    refs = []
+    for dt in (torch.float64, torch.float32):
+        a, b = er.detach().cpu().to(dt).requires_grad_(True), ei.detach().cpu().to(dt).requires_grad_(True)
+        l = lc.pstoi(lc.magnitude(a, b).transpose(1, 2), lc.magnitude(cr.cpu().to(dt), ci.cpu().to(dt)).transpose(1, 2),
+                     c["w"].to(dt))
+        l.backward()
+        refs.append(torch.stack([a.grad, b.grad]))
+    hp.check_row("pstoi grad behind the enhancer", torch.stack([er.grad, ei.grad]).cpu(), refs[0], refs[1], hp.K_TRANS)
