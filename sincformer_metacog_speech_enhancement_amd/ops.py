@@ -629,7 +629,8 @@ ATTN_QSCALE_LOG2E = 1.4426950408889634
 
 
 def attention_kernel_name(B, T, H, variant=None):
-    """name of the forward kernel sfm_attention_fwd_ex picks for head_dim 64 (mirrors the rule in csrc/attention.hip)"""
+    """name of the forward kernel sfm_attention_fwd_ex / sfm_attention_fwd_train (no dropout) pick for head_dim 64: the rule of
+    attention_fwd_impl in csrc/attention.hip, restated (tests/test_attention_rule_gpu.py holds the two together bit by bit)"""
     v = switch("attention_variant") if variant is None else variant
     nqt5 = (T + 511) // 512
     enough = B * H * nqt5 >= 128
@@ -639,15 +640,16 @@ def attention_kernel_name(B, T, H, variant=None):
         elif enough and T <= 256 and 100 * T >= 90 * 256:
             v = 5
         else:
-            v = 2 if T >= 1024 else 1
-    return {1: "attn_fwd_hd64_kernel", 2: "attn_fwd_hd64x2_kernel", 3: "attn_fwd_hd64r_kernel", 4: "attn_fwd_hd64p8_kernel",
+            v = 1                                   # short launches and every T outside the windows, T >= 1024 included
+    return {1: "attn_fwd_hd64_kernel", 2: "attn_fwd_hd64r_kernel", 3: "attn_fwd_hd64r_kernel", 4: "attn_fwd_hd64p8_kernel",
             5: "attn_fwd_hd64p4_kernel", 6: "attn_fwd_hd64q4_kernel"}[v]
 
 
 def set_attention_variant(v):
-    """0: chosen by shape (default), 1: 32 query rows per wave, 3: persistent ring kernel, 4 / 5: pipelined persistent kernel
-    with one 8-wave / two 4-wave workgroups per CU (A/B measurements).  Host-side state only: the value is passed to
-    sfm_attention_fwd_ex with every call (the library keeps no selection state)."""
+    """0: chosen by shape (default), 1: 32 query rows per wave, 3: persistent ring kernel (2 is accepted as 3), 4 / 5:
+    pipelined persistent kernel with one 8-wave / two 4-wave workgroups per CU and 64 query rows per wave, 6: the same with
+    four waves of 128 rows (A/B measurements).  Host-side state only: the value is passed to sfm_attention_fwd_ex with every
+    call (the library keeps no selection state)."""
     v = int(v)
     if not 0 <= v <= 6:
         raise ValueError("attention variant %d" % v)

@@ -50,6 +50,68 @@ def rmse(a, b):
     return float(((a - b) ** 2).mean().sqrt())
 
 
+# ---------------------------------------------------------------------------
+# Attention: the default kernel-selection rule (tests/test_attention_rule_gpu.py on the GPU, tests/test_host_logic.py for
+# ops.attention_kernel_name without one).  (B, H, T, kernel) rows at head_dim 64, worked out by hand from the integer rule of
+# attention_fwd_impl (csrc/attention.hip): nq = ceil(T / 512); enough = B * H * nq >= 128; the 8-wave pipelined kernel when
+# enough and (T >= 1024 or 100 T >= 78 * 512 nq): T 400..512 (39936 <= 100 T), T 799..1023 (79872 <= 100 T); else the 4-wave
+# one when enough and T <= 256 and 100 T >= 23040: T 231..256; the 32-rows-per-wave kernel otherwise.  Each row stands on one
+# side of one edge of that rule (a T window's end, or 127 / 128 and 88 / 132 items).
+# ---------------------------------------------------------------------------
+ATTN_KERNELS = {"hd64": "attn_fwd_hd64_kernel", "ring": "attn_fwd_hd64r_kernel", "p8": "attn_fwd_hd64p8_kernel",
+                "p4": "attn_fwd_hd64p4_kernel", "q4": "attn_fwd_hd64q4_kernel"}
+ATTN_FORCED = {1: "hd64", 2: "ring", 3: "ring", 4: "p8", 5: "p4", 6: "q4"}          # ops.set_attention_variant(v) -> kernel
+ATTN_VARIANT_OF = {ATTN_KERNELS[k]: v for v, k in ATTN_FORCED.items() if v != 2}     # kernel name -> the variant that forces it
+ATTN_RULE_ROWS = [(32, 4, 230, "hd64"), (32, 4, 231, "p4"), (32, 4, 256, "p4"), (32, 4, 257, "hd64"), (32, 4, 399, "hd64"),
+                  (32, 4, 400, "p8"), (32, 4, 512, "p8"), (16, 4, 513, "hd64"), (16, 4, 798, "hd64"), (16, 4, 799, "p8"),
+                  (11, 4, 1024, "hd64"), (16, 4, 1024, "p8"), (11, 4, 1025, "p8"), (127, 1, 256, "hd64"), (128, 1, 256, "p4")]
+
+
+def attn_ref64(qkv, B, T, H, hd, prescaled=False, dO=None, keep=None):
+    """float64 attention of qkv [B*T, 3*H*hd] (q | k | v), one utterance at a time (a [H, T, T] score block at most is alive).
+    prescaled: q carries log2(e) / sqrt(hd), P = softmax(ln2 * q.k); otherwise P = softmax(q.k / sqrt(hd)).  keep [B, H, T, T]:
+    the dropout factor on P.  -> O [B*T, H*hd], log2-domain log-sum-exp of the scaled scores [B, H, T], and - with a cotangent
+    dO [B*T, H*hd] - the float64 autograd gradient w.r.t. qkv (else None)"""
+    D = H * hd
+    x = qkv.double().reshape(B, T, 3 * D)
+    scale = math.log(2.0) if prescaled else 1.0 / math.sqrt(hd)
+    outs, lses, grads = [], [], []
+    for b in range(B):
+        xb = x[b].clone().requires_grad_(dO is not None)
+        q, k, v = [t.reshape(T, H, hd).transpose(0, 1) for t in xb.split(D, dim=-1)]
+        s = (q @ k.transpose(-1, -2)) * scale
+        p = torch.softmax(s, dim=-1)
+        lses.append((torch.logsumexp(s, dim=-1) / math.log(2.0)).detach())
+        if keep is not None:
+            p = p * keep[b].double()
+        o = (p @ v).transpose(0, 1).reshape(T, D)
+        if dO is not None:
+            o.backward(dO.double().reshape(B, T, D)[b])
+            grads.append(xb.grad)
+        outs.append(o.detach())
+    return torch.cat(outs), torch.stack(lses), (torch.cat(grads) if dO is not None else None)
+
+
+def keep_mask(seed, B, H, T, p):
+    """numpy replica of the counter-based keep function (attention.hip / attention_bwd.hip): full hash of the probability row
+    (b, h, q), then one multiply-add + xorshift-multiply round per key"""
+    M32 = np.uint64(0xFFFFFFFF)
+    row = np.arange(B * H * T, dtype=np.uint64)
+    x = ((row & M32) * np.uint64(0x9E3779B1)) & M32
+    x ^= ((row >> np.uint64(32)) * np.uint64(0x85EBCA77)) & M32
+    x ^= np.uint64(seed)
+    x ^= x >> np.uint64(16); x = (x * np.uint64(0x7FEB352D)) & M32
+    x ^= x >> np.uint64(15); x = (x * np.uint64(0x846CA68B)) & M32
+    x ^= x >> np.uint64(16)
+    key = np.arange(T, dtype=np.uint64)
+    y = (x[:, None] + ((key * np.uint64(0x9E3779B1)) & M32)[None, :]) & M32
+    y ^= y >> np.uint64(15); y = (y * np.uint64(0x846CA68B)) & M32
+    y ^= y >> np.uint64(16)
+    thr = np.uint64(math.ceil(float(np.float32(p)) * 16777216.0))
+    keep = ((y >> np.uint64(8)) >= thr).astype(np.float32) / (1.0 - p)
+    return torch.from_numpy(keep.reshape(B, H, T, T))
+
+
 def metric_cases():
     """(name, fs, clean, enhanced) pairs shared by the generator and the tests: plain noisy pairs at both sample rates,
     a silent stretch (skipped frames), identical signals (upper bound), ragged length, shorter-than-a-frame."""

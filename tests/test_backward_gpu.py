@@ -5,7 +5,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from helpers import arr, maxerr, rmse
+from helpers import arr, maxerr, rmse, keep_mask as _keep_mask
 from oracle import sfm_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -183,26 +183,6 @@ def _attn_ref(qkv, B, T, H, hd, keep=None):
     if keep is not None:
         p = p * keep
     return (p @ v).transpose(1, 2).reshape(B * T, D), lse2
-
-
-def _keep_mask(seed, B, H, T, p):
-    """numpy replica of the counter-based keep function (attention.hip / attention_bwd.hip): full hash of the probability row
-    (b, h, q), then one multiply-add + xorshift-multiply round per key"""
-    M32 = np.uint64(0xFFFFFFFF)
-    row = np.arange(B * H * T, dtype=np.uint64)
-    x = ((row & M32) * np.uint64(0x9E3779B1)) & M32
-    x ^= ((row >> np.uint64(32)) * np.uint64(0x85EBCA77)) & M32
-    x ^= np.uint64(seed)
-    x ^= x >> np.uint64(16); x = (x * np.uint64(0x7FEB352D)) & M32
-    x ^= x >> np.uint64(15); x = (x * np.uint64(0x846CA68B)) & M32
-    x ^= x >> np.uint64(16)
-    key = np.arange(T, dtype=np.uint64)
-    y = (x[:, None] + ((key * np.uint64(0x9E3779B1)) & M32)[None, :]) & M32
-    y ^= y >> np.uint64(15); y = (y * np.uint64(0x846CA68B)) & M32
-    y ^= y >> np.uint64(16)
-    thr = np.uint64(math.ceil(float(np.float32(p)) * 16777216.0))
-    keep = ((y >> np.uint64(8)) >= thr).astype(np.float32) / (1.0 - p)
-    return torch.from_numpy(keep.reshape(B, H, T, T))
 
 
 @pytest.mark.parametrize("dt", DTYPES)

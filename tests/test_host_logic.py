@@ -3,6 +3,7 @@ contract), weight packing, DFT operands, synthetic data determinism, no-CPU-fall
 import json
 import math
 import os
+import re
 import subprocess
 import sys
 import numpy as np
@@ -342,6 +343,32 @@ def test_variant_overrides_reports_an_environment_variable(var, value, name, wan
 def test_variant_overrides_ignores_the_library_path():
     """SFM_LIB_PATH is the documented way to time another build with bench.py: not a switch"""
     assert _overrides_in_child({"SFM_LIB_PATH": "/nonexistent/libsincformer_hip.so"}) == {}
+
+
+def test_attention_kernel_name_follows_the_rule_of_attention_fwd_impl():
+    """ops.attention_kernel_name restates the selection rule of csrc/attention.hip: at every edge row of helpers.ATTN_RULE_ROWS
+    it names the kernel worked out by hand from the C rule (tests/test_attention_rule_gpu.py checks on the GPU that this is the
+    kernel the library launches), short launches fall back to the 32-rows-per-wave kernel at ANY T, a forced variant names
+    its own kernel at every row, and every name it can return is a kernel that exists in csrc/"""
+    from helpers import ATTN_KERNELS, ATTN_FORCED, ATTN_RULE_ROWS
+    assert ops.switch("attention_variant") == 0
+    for B, H, T, kern in ATTN_RULE_ROWS:
+        assert ops.attention_kernel_name(B, T, H) == ATTN_KERNELS[kern], (B, H, T)
+        assert ops.attention_kernel_name(B, T, H, variant=0) == ATTN_KERNELS[kern], (B, H, T)
+        for v, forced in ATTN_FORCED.items():
+            assert ops.attention_kernel_name(B, T, H, variant=v) == ATTN_KERNELS[forced], (B, H, T, v)
+    for T in (1024, 1025, 2048, 6001):                  # few items: no window applies, whatever the length
+        assert ops.attention_kernel_name(1, T, 4) == ATTN_KERNELS["hd64"], T
+    try:                                                # variant=None reads the switch
+        for v, forced in ATTN_FORCED.items():
+            ops.set_attention_variant(v)
+            assert ops.attention_kernel_name(32, 230, 4) == ATTN_KERNELS[forced], v
+    finally:
+        ops.set_attention_variant(0)
+    csrc = os.path.join(os.path.dirname(os.path.abspath(ops.__file__)), "csrc")
+    text = "".join(open(os.path.join(csrc, f)).read() for f in ("attention.hip", "attention_pipe.hip"))
+    for name in ATTN_KERNELS.values():
+        assert re.search(r"__global__[^;{]*\b%s\(" % name, text), name
 
 
 def test_width_bounds_separate_plausible_wrong_answers():
