@@ -14,9 +14,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libsincformer_hip.so")
+INCLUDE = os.path.join(os.path.dirname(HERE), "include")     # sincformer_hip.h: every definition is compiled against its declaration
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
-         "-I", CSRC]
+         "-I", CSRC, "-I", INCLUDE]
 # per-source extras: keep the attention accumulators in VGPRs (the softmax works on them with
 # VALU instructions; the default AGPR placement costs ~220 v_accvgpr moves per key tile)
 # -fno-honor-nans: row maxima of the online softmax compile to bare v_max3_f32 (see attention.hip)
@@ -34,7 +35,7 @@ def _newer(src, dst, deps):
 def build(force=False, verbose=True):
     os.makedirs(OBJ, exist_ok=True)
     srcs = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
-    hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [os.path.join(INCLUDE, "sincformer_hip.h")]
     jobs = []
     for s in srcs:
         src = os.path.join(CSRC, s)

@@ -25,20 +25,9 @@
 #define OS_ROW 72
 #define DEFER_THR 4.0f
 
-// Attention dropout: keep(row, key) = finalise(rowhash(row) + key * golden), rowhash = the full counter hash of the probability
-// row (b, h, q), computed once per row; per score one multiply-add, one xorshift-multiply round and an integer compare
-// (~9 VALU instructions instead of ~16).  The same function in attention.hip (forward) and attention_bwd.hip.
-__device__ __forceinline__ uint32_t attn_row_hash(uint32_t seed, unsigned long long row) {
-  uint32_t x = (uint32_t)row * 0x9E3779B1u ^ (uint32_t)(row >> 32) * 0x85EBCA77u ^ seed;
-  x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
-  return x;
-}
-__device__ __forceinline__ uint32_t attn_keep_threshold(float p) { return (uint32_t)ceilf(p * 16777216.0f); }
-__device__ __forceinline__ float attn_keep_rk(uint32_t rowh, int key, uint32_t thr24, float inv_keep) {
-  uint32_t x = rowh + (uint32_t)key * 0x9E3779B1u;
-  x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
-  return ((x >> 8) >= thr24) ? inv_keep : 0.f;
-}
+// Attention dropout: keep(row, key) = sfm_keep_from_group(sfm_hash(seed, row), key, ...): the full counter hash of the
+// probability row (b, h, q) once per row; per score one multiply-add, one xorshift-multiply round and an integer compare
+// (~9 VALU instructions instead of ~16).  Forward (attention.hip) and backward (attention_bwd.hip) call the same functions.
 
 // Row maxima: this file is compiled with -fno-honor-nans (build.py), so fmaxf() on MFMA results is a plain v_max_f32 /
 // v_max3_f32; with NaNs honoured hipcc canonicalises every operand first (one extra v_max_f32 x, x per score pair, +3 %
@@ -46,14 +35,6 @@ __device__ __forceinline__ float attn_keep_rk(uint32_t rowh, int key, uint32_t t
 // avoid the canonicalisation but hides the MFMA-result hazard from the compiler's nop insertion: wrong values now and then.)
 __device__ __forceinline__ float sfm_max2_raw(float a, float b) { return fmaxf(a, b); }
 __device__ __forceinline__ float sfm_max3_raw(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
-
-// O is written in the operands' format T, or (out_other) in the other 16-bit format: the attention core may run in bf16 behind
-// fp16 projections (precision policy, ops.STAGES)
-template <class T>
-__device__ __forceinline__ uint32_t pack2_o(float lo, float hi, bool other) {
-  if (T::id == SFM_DT_BF16) return other ? F16::pack(lo, hi) : BF16::pack(lo, hi);
-  return other ? BF16::pack(lo, hi) : F16::pack(lo, hi);
-}
 
 // VARLEN: the packed form.  qkv / out hold the rows of all utterances back to back (utterance u = rows [frame_off[u],
 // frame_off[u + 1])); a workgroup is one entry (utterance, head, query tile) of the item table the host built from the lengths
@@ -135,8 +116,8 @@ __global__ __launch_bounds__(256) void attn_fwd_hd64_kernel(const u16* __restric
   for (int r = 0; r < 16; ++r) lacc[r] = 0.f;
   float m_run = 0.f;                                                // value currently subtracted by the MFMA
   // attention dropout (training): the lane's probability row is fixed, so its row hash is computed once
-  const uint32_t drop_rowh = DROP ? attn_row_hash(seed, ((unsigned long long)b * nheads + h) * Tlen + (q0 + l31 < Tlen ? q0 + l31 : 0)) : 0u;
-  const uint32_t drop_thr = DROP ? attn_keep_threshold(p_drop) : 0u;
+  const uint32_t drop_rowh = DROP ? sfm_hash(seed, ((unsigned long long)b * nheads + h) * Tlen + (q0 + l31 < Tlen ? q0 + l31 : 0)) : 0u;
+  const uint32_t drop_thr = DROP ? sfm_keep_threshold(p_drop) : 0u;
   const float drop_ik = DROP ? 1.0f / (1.0f - p_drop) : 1.0f;
 
   // staging coordinates: 64 rows x 8 chunks(16 B) for K and for V; 2 chunks each per thread
@@ -254,7 +235,7 @@ __global__ __launch_bounds__(256) void attn_fwd_hd64_kernel(const u16* __restric
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
             const int key = kbase + kj * 32 + mfma_row(8 * s2 + e, lane);
-            pd[e] = s[kj][8 * s2 + e] * attn_keep_rk(drop_rowh, key, drop_thr, drop_ik);
+            pd[e] = s[kj][8 * s2 + e] * sfm_keep_from_group(drop_rowh, (uint32_t)key, drop_thr, drop_ik);
           }
           pf[0] = pack2<T>(pd[0], pd[1]);
           pf[1] = pack2<T>(pd[2], pd[3]);
@@ -295,8 +276,8 @@ __global__ __launch_bounds__(256) void attn_fwd_hd64_kernel(const u16* __restric
     for (int rq = 0; rq < 4; ++rq) {
       int d0 = dj * 32 + 8 * rq + 4 * hl;
       u32x2 w;
-      w[0] = pack2_o<T>(o[dj][4 * rq + 0] * inv, o[dj][4 * rq + 1] * inv, out_other != 0);
-      w[1] = pack2_o<T>(o[dj][4 * rq + 2] * inv, o[dj][4 * rq + 3] * inv, out_other != 0);
+      w[0] = pack2_out<T>(o[dj][4 * rq + 0] * inv, o[dj][4 * rq + 1] * inv, out_other != 0);
+      w[1] = pack2_out<T>(o[dj][4 * rq + 2] * inv, o[dj][4 * rq + 3] * inv, out_other != 0);
       *reinterpret_cast<u32x2*>(&Os[l31 * OS_ROW + d0]) = w;
     }
   __syncthreads();
@@ -314,26 +295,6 @@ __global__ __launch_bounds__(256) void attn_fwd_hd64_kernel(const u16* __restric
 }
 
 // ---------------------------------------------------------------------------
-// v_permlane32_swap exchanges lanes 32-63 of its first operand with lanes 0-31 of the second: fed two copies of x it
-// leaves [x.lo, x.lo] and [x.hi, x.hi].  The s_nop covers the 2 wait states a VALU write of an operand needs before
-// the swap reads it.  (Scalars in and out: this compiler reads element 0 for __builtin_bit_cast(float, vec[i]).)
-__device__ __forceinline__ void xhalf_swap(float v, float& lo, float& hi) {
-  uint32_t a = __builtin_bit_cast(uint32_t, v), c = a;
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(c));
-  lo = __builtin_bit_cast(float, a);
-  hi = __builtin_bit_cast(float, c);
-}
-__device__ __forceinline__ float xhalf_max(float v) {
-  float lo, hi;
-  xhalf_swap(v, lo, hi);
-  return fmaxf(lo, hi);
-}
-__device__ __forceinline__ float xhalf_sum(float v) {
-  float lo, hi;
-  xhalf_swap(v, lo, hi);
-  return lo + hi;
-}
-
 // maximum of a lane's 16 accumulator values: one v_max_f32, then seven v_max3_f32
 __device__ __forceinline__ float attn_row_max16(const f32x16& sn) {
   float m = sfm_max2_raw(sn[0], sn[1]);
@@ -341,8 +302,6 @@ __device__ __forceinline__ float attn_row_max16(const f32x16& sn) {
   for (int r = 2; r < 16; r += 2) m = sfm_max3_raw(m, sn[r], sn[r + 1]);
   return m;
 }
-
-typedef __attribute__((address_space(3))) void* attn_lds_ptr_t;
 
 template <class T>
 __global__ __launch_bounds__(512, 2) void attn_fwd_hd64r_kernel(const u16* __restrict__ qkv, u16* __restrict__ out, int Tlen,
@@ -376,8 +335,8 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_hd64r_kernel(const u16* __res
       if (kt < nkt) {
         const int off = kt * 64 * ldqkv * 2 + h * 128;
         unsigned char* dst = rsm + (half * GT + tl) * SLOT + wave * 1024;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (attn_lds_ptr_t)dst, 16, kconst + off, 0, 0, 0);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (attn_lds_ptr_t)(dst + 8192), 16, vconst + off, 0, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)dst, 16, kconst + off, 0, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)(dst + 8192), 16, vconst + off, 0, 0, 0);
       }
     }
   };
@@ -393,7 +352,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_hd64r_kernel(const u16* __res
       // LDS chunk position lane&7 of row 8j + lane/8 holds logical chunk (lane&7) ^ ((4j + lane/16) & 7)
       const int c = ((lane & 7) ^ ((4 * j + (lane >> 4)) & 7)) << 4;
       const int voff = off + (8 * j + (lane >> 3)) * ldqkv * 2 + c;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (attn_lds_ptr_t)(rsm + QBASE + wave * 8192 + j * 1024), 16, voff, 0, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)(rsm + QBASE + wave * 8192 + j * 1024), 16, voff, 0, 0, 0);
     }
   };
 
@@ -426,7 +385,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_hd64r_kernel(const u16* __res
   // wait for the next group's K/V prefetch and for the previous item's O stores.  The ring protocol (vmcnt + barrier at the
   // group boundary) is what orders reads against fills; `vt_wait` is the lgkmcnt wait the compiler no longer inserts, tied
   // to the fragment registers so that their consumers stay behind it.
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(attn_lds_ptr_t)rsm;
+  const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_ptr_t)rsm;
   auto load_vf = [&](int sbase) {
 #pragma unroll
     for (int dj = 0; dj < 2; ++dj) {
@@ -559,7 +518,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_hd64r_kernel(const u16* __res
     for (int g = 0; g < ngrp; ++g) {
       // ---- group boundary: this wave's pieces of group g have landed (vmcnt), everyone's have and everyone is done with
       //      group g-1 (barrier): refill that half with the next group of this item or group 0 of the next item ----
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wait_vmcnt<0>();
       __syncthreads();
       const int half = gcount & 1;
       if (g + 1 < ngrp) issue_group(item, g + 1, half ^ 1);
@@ -655,8 +614,8 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_hd64r_kernel(const u16* __res
       for (int dj = 0; dj < 2; ++dj)
 #pragma unroll
         for (int rq = 0; rq < 4; ++rq) {
-          ow[u][dj][rq][0] = pack2_o<T>(o[u][dj][4 * rq + 0] * inv, o[u][dj][4 * rq + 1] * inv, out_other != 0);
-          ow[u][dj][rq][1] = pack2_o<T>(o[u][dj][4 * rq + 2] * inv, o[u][dj][4 * rq + 3] * inv, out_other != 0);
+          ow[u][dj][rq][0] = pack2_out<T>(o[u][dj][4 * rq + 0] * inv, o[u][dj][4 * rq + 1] * inv, out_other != 0);
+          ow[u][dj][rq][1] = pack2_out<T>(o[u][dj][4 * rq + 2] * inv, o[u][dj][4 * rq + 3] * inv, out_other != 0);
         }
     }
     st_item = item;
@@ -693,8 +652,8 @@ __global__ __launch_bounds__(256) void attn_fwd_generic_kernel(const u16* __rest
     out += (long long)row0 * ldo;
   }
   const float inv_keep = (p_drop > 0.f) ? 1.0f / (1.0f - p_drop) : 1.0f;
-  const uint32_t drop_rowh = attn_row_hash(seed, ((unsigned long long)b * nheads + h) * Tlen + q);
-  const uint32_t drop_thr = attn_keep_threshold(p_drop);
+  const uint32_t drop_rowh = sfm_hash(seed, ((unsigned long long)b * nheads + h) * Tlen + q);
+  const uint32_t drop_thr = sfm_keep_threshold(p_drop);
   const u16* base = qkv + (long long)b * qkv_batch_stride + h * hd;
   float qv[4], acc[4];
 #pragma unroll
@@ -717,7 +676,7 @@ __global__ __launch_bounds__(256) void attn_fwd_generic_kernel(const u16* __rest
     float al = expf(m - mn), pv = expf(sc - mn);
     l = l * al + pv;
     m = mn;
-    const float pd = (p_drop > 0.f) ? pv * attn_keep_rk(drop_rowh, key, drop_thr, inv_keep) : pv;   // O only, not l
+    const float pd = (p_drop > 0.f) ? pv * sfm_keep_from_group(drop_rowh, (uint32_t)key, drop_thr, inv_keep) : pv;   // O only, not l
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       int d = lane + 64 * i;

@@ -28,21 +28,6 @@
 //     counted lgkmcnt): no LDS latency in front of an MFMA chain.
 #include "sfm_common.h"
 
-typedef __attribute__((address_space(3))) void* attnp_lds_ptr_t;
-
-__device__ __forceinline__ float attnp_xhalf_max(float v) {
-  // v_permlane32_swap exchanges lanes 32-63 of its first operand with lanes 0-31 of the second (s_nop: VALU write -> swap)
-  uint32_t a = __builtin_bit_cast(uint32_t, v), c = a;
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(c));
-  return fmaxf(__builtin_bit_cast(float, a), __builtin_bit_cast(float, c));
-}
-
-template <class T>
-__device__ __forceinline__ uint32_t attnp_pack2_o(float lo, float hi, bool other) {
-  if (T::id == SFM_DT_BF16) return other ? F16::pack(lo, hi) : BF16::pack(lo, hi);
-  return other ? BF16::pack(lo, hi) : F16::pack(lo, hi);
-}
-
 #define ATTNP_HEADROOM 3.0f
 
 // NW = waves per workgroup (8: one workgroup per CU, items of 512 query rows, ring of 3 x 2 key tiles; 4: TWO workgroups per
@@ -99,8 +84,8 @@ __device__ __forceinline__ void attnp_body(const u16* __restrict__ qkv, u16* __r
         unsigned char* dst = rsm + (half * GT + tl) * SLOT + wave * (RPW * 128);
 #pragma unroll
         for (int pc = 0; pc < RPW / 8; ++pc) {
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (attnp_lds_ptr_t)(dst + pc * 1024), 16, kconst[pc] + off, 0, 0, 0);
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (attnp_lds_ptr_t)(dst + pc * 1024 + 8192), 16, vconst + off + pc * 8 * ldqkv * 2, 0, 0, 0);
+          __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)(dst + pc * 1024), 16, kconst[pc] + off, 0, 0, 0);
+          __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)(dst + pc * 1024 + 8192), 16, vconst + off + pc * 8 * ldqkv * 2, 0, 0, 0);
         }
         np += 2 * (RPW / 8);
       }
@@ -117,12 +102,12 @@ __device__ __forceinline__ void attnp_body(const u16* __restrict__ qkv, u16* __r
     for (int j = 0; j < RW / 8; ++j) {
       const int c = ((lane & 7) ^ ((4 * j + (lane >> 4)) & 7)) << 4;
       const int vo = off + (8 * j + (lane >> 3)) * ldqkv * 2 + c;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (attnp_lds_ptr_t)(rsm + QBASE + wave * QWB + j * 1024), 16, vo, 0, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)(rsm + QBASE + wave * QWB + j * 1024), 16, vo, 0, 0, 0);
     }
   };
 
   // ---- fragment read lane constants (byte offsets inside a 32-key step: K rows at +0, V rows at +8192) ----
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(attnp_lds_ptr_t)rsm;
+  const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_ptr_t)rsm;
   uint32_t klane[4];
 #pragma unroll
   for (int ks = 0; ks < 4; ++ks) klane[ks] = lds0 + l31 * 128 + (((2 * ks + hl) ^ ((l31 >> 1) & 7)) << 4);
@@ -236,7 +221,7 @@ __device__ __forceinline__ void attnp_body(const u16* __restrict__ qkv, u16* __r
   {                                                                                                                    \
     float mx = fmaxf(s[X][0], s[X][1]);                                                                                \
     _Pragma("unroll") for (int r = 2; r < 16; r += 2) mx = fmaxf(fmaxf(mx, s[X][r]), s[X][r + 1]);                     \
-    mx = attnp_xhalf_max(mx);                                                                                          \
+    mx = xhalf_max(mx);                                                                                                \
     /* new subtracted value, split in two 16-bit terms so that the MFMA subtracts it to ~2^-17 */                      \
     const float want_ = m_run[X] + ((FORCE) ? mx + ATTNP_HEADROOM : fmaxf(mx + ATTNP_HEADROOM, 0.f));                  \
     const float hi_ = T::to_f32(T::from_f32(want_));                                                                   \
@@ -492,13 +477,13 @@ __device__ __forceinline__ void attnp_body(const u16* __restrict__ qkv, u16* __r
   //      flight - then everyone's have (barrier; its lgkmcnt(0) also covers the V^T reads of the last step, issued before).
   //      Then the K fragments of the group's first step. ----
 #define ATTNP_BOUNDARY()                                                                                               \
-  if (inflight >= 32) asm volatile("s_waitcnt vmcnt(32) lgkmcnt(0)" ::: "memory");                                     \
-  else if (inflight >= 24) asm volatile("s_waitcnt vmcnt(24) lgkmcnt(0)" ::: "memory");                                \
-  else if (inflight >= 16) asm volatile("s_waitcnt vmcnt(16) lgkmcnt(0)" ::: "memory");                                \
-  else if (inflight >= 12) asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)" ::: "memory");                                \
-  else if (inflight >= 8) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");                                  \
-  else if (inflight >= 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");                                  \
-  else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                                                     \
+  if (inflight >= 32) wait_ring<32>();                                                                                 \
+  else if (inflight >= 24) wait_ring<24>();                                                                            \
+  else if (inflight >= 16) wait_ring<16>();                                                                            \
+  else if (inflight >= 12) wait_ring<12>();                                                                            \
+  else if (inflight >= 8) wait_ring<8>();                                                                              \
+  else if (inflight >= 4) wait_ring<4>();                                                                              \
+  else wait_ring<0>();                                                                                                 \
   __builtin_amdgcn_s_barrier();            /* raw: __syncthreads() would drain vmcnt to 0 (refill and O stores in flight) */ \
   asm volatile("" ::: "memory");                                                                                       \
   inflight = 0;                                                                                                        \
@@ -538,8 +523,8 @@ __device__ __forceinline__ void attnp_body(const u16* __restrict__ qkv, u16* __r
     const bool has_next = item + (int)gridDim.x < n_items;
     if (!qf_ready) {
       // first item of the workgroup (or single-group items, below): this wave's own Q pieces have landed -> fragments
-      if (first_q_pending) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PPG) : "memory");      // the youngest = the two K/V groups
-      else { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); inflight = 0; }
+      if (first_q_pending) wait_vmcnt<2 * PPG>();      // the youngest = the two K/V groups
+      else { wait_vmcnt<0>(); inflight = 0; }
       first_q_pending = false;
       load_qf();
       init_state();
@@ -561,7 +546,7 @@ __device__ __forceinline__ void attnp_body(const u16* __restrict__ qkv, u16* __r
     qf_ready = false;
     if (ngrp > 1 && has_next) {
       // the next item's Q fragments: its rows were fetched a group or more ago (operations issued after them: >= one refill)
-      asm volatile("s_waitcnt vmcnt(2)" ::: "memory");             // (a refill is 2 or 4 pieces)
+      wait_vmcnt<2>();             // (a refill is 2 or 4 pieces)
 #pragma unroll
       for (int u = 0; u < SB; ++u)
 #pragma unroll

@@ -20,11 +20,6 @@
 #define PST_MAX_F 257
 #define PST_MAX_FL 32
 
-static __device__ __forceinline__ double cl_wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 // sum over the 32 lanes of a half-wave, the same value (bit for bit) in each of them
 static __device__ __forceinline__ float half_sum(float v) {
 #pragma unroll
@@ -260,7 +255,7 @@ __global__ __launch_bounds__(256) void mse_kernel(const float* __restrict__ p, c
     acc += d * d;
     if (grad) grad[i] = (float)(d * gs);
   }
-  acc = cl_wave_sum_d(acc);
+  acc = wave_sum_d(acc);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   __syncthreads();
   if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);

@@ -17,28 +17,8 @@
 #define FF_BM 128
 #define FF_CH 64                        // hidden units per chunk
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-template <int N>
-__device__ __forceinline__ void ff_wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ void ff_frag_read(u32x4& dst, uint32_t lds_addr) {
-  asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(lds_addr) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void ff_frag_wait(u32x4& frag) {
-  asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(frag) : "n"(N) : "memory");
-}
 __device__ __forceinline__ float ff_lane_bcast(float v, int r) {       // lane r's value in every lane (r static: v_readlane)
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), r));
-}
-__device__ __forceinline__ void ff_barrier() {
-  // LDS writes of this wave must have completed before other waves pass the barrier; the LDS-DMA
-  // queue (vmcnt) is deliberately NOT drained here - that is what the counted waits are for.
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
 }
 
 
@@ -210,8 +190,8 @@ __global__ __launch_bounds__(512) void ffn_fused_kernel(const float* __restrict_
   };
 
   f32x16 s1;                                                // GEMM1 accumulator of the chunk whose Swish comes next
-  ff_wait_vmcnt<8>();                                       // W1(0) is in
-  ff_barrier();
+  wait_vmcnt<8>();                                          // W1(0) is in
+  ring_barrier();
   s1_init(0, s1);
   {
     u32x4 fw[4];
@@ -223,8 +203,8 @@ __global__ __launch_bounds__(512) void ffn_fused_kernel(const float* __restrict_
       if (k + 4 < 16) fw[k & 3] = w1_frag(0, k + 4);
     }
   }
-  ff_wait_vmcnt<0>();                                       // W2(0), W1(1) are in
-  ff_barrier();                                             // W1(0) has been read by everyone
+  wait_vmcnt<0>();                                          // W2(0), W1(1) are in
+  ring_barrier();                                           // W1(0) has been read by everyone
 #pragma unroll
   for (int i = 0; i < 4; ++i) w1_piece(2, i);
   for (int c = 0; c + 1 < nch; ++c) {
@@ -233,31 +213,31 @@ __global__ __launch_bounds__(512) void ffn_fused_kernel(const float* __restrict_
       f32x16 s1n;
       s1_init(c + 1, s1n);
       // W1 fragments by inline-asm reads kept FOUR MFMAs ahead of their use (left to the compiler the reads sink to one
-      // MFMA ahead to save registers).  ff_frag_wait is the lgkmcnt wait the compiler no longer inserts (N = this wave's
+      // MFMA ahead to save registers).  frag_wait is the lgkmcnt wait the compiler no longer inserts (N = this wave's
       // younger fragment reads), tied to the registers.
       const uint32_t fbase = w1_lane + (uint32_t)(((c + 1) & 1) * STG);
       u32x4 fw[4];
 #pragma unroll
-      for (int k = 0; k < 4; ++k) ff_frag_read(fw[k], fbase + (uint32_t)(hx4 ^ (k << 5)));
+      for (int k = 0; k < 4; ++k) frag_read(fw[k], fbase + (uint32_t)(hx4 ^ (k << 5)));
 #pragma unroll
       for (int k = 0; k < 16; ++k) {
-        if (k <= 12) ff_frag_wait<3>(fw[k & 3]);
-        else if (k == 13) ff_frag_wait<2>(fw[k & 3]);
-        else if (k == 14) ff_frag_wait<1>(fw[k & 3]);
-        else ff_frag_wait<0>(fw[k & 3]);
+        if (k <= 12) frag_wait<3>(fw[k & 3]);
+        else if (k == 13) frag_wait<2>(fw[k & 3]);
+        else if (k == 14) frag_wait<1>(fw[k & 3]);
+        else frag_wait<0>(fw[k & 3]);
         s1n = T::mfma(fw[k & 3], hf[k], s1n);
-        if (k + 4 < 16) ff_frag_read(fw[k & 3], fbase + (uint32_t)(hx4 ^ ((k + 4) << 5)));
+        if (k + 4 < 16) frag_read(fw[k & 3], fbase + (uint32_t)(hx4 ^ ((k + 4) << 5)));
         if ((k & 3) == 1) swish_quad(s1, k >> 2);
         if ((k & 3) == 3) w2_piece(c + 1, k >> 2);
       }
       s1 = s1n;
     }
-    ff_wait_vmcnt<8>();                                     // W2(c) is in
-    ff_barrier();                                           // U(c) complete; W1(c+1) and W2(c-1) have been read
+    wait_vmcnt<8>();                                        // W2(c) is in
+    ring_barrier();                                         // U(c) complete; W1(c+1) and W2(c-1) have been read
     // ---- Y(c): acc2[64 x 64] += U[64 rows x 64] * W2c[64 out cols x 64]^T ----
     gemm2(c, true);
-    ff_wait_vmcnt<8>();                                     // W1(c+2) is in
-    ff_barrier();                                           // U(c) and W2(c) have been read
+    wait_vmcnt<8>();                                        // W1(c+2) is in
+    ring_barrier();                                         // U(c) and W2(c) have been read
   }
   // ---- last chunk: no GEMM1 left, so H's registers take the residual rows of x now (prologue layout: wave w rows 16w..+15,
   //      4 consecutive columns per lane) and the loads fly under the last Swish and GEMM2; no refills either ----
@@ -272,11 +252,11 @@ __global__ __launch_bounds__(512) void ffn_fused_kernel(const float* __restrict_
   }
 #pragma unroll
   for (int q = 0; q < 4; ++q) swish_quad(s1, q);
-  ff_wait_vmcnt<20>();                                      // W2(nch-1) is in (behind it: the zeros of W1(nch+1), the 16 rows)
-  ff_barrier();
+  wait_vmcnt<20>();                                         // W2(nch-1) is in (behind it: the zeros of W1(nch+1), the 16 rows)
+  ring_barrier();
   gemm2(nch - 1, false);
-  ff_wait_vmcnt<0>();                                       // the refills past the last chunk (zeros) have landed in the
-  ff_barrier();                                             // ring bytes the epilogue image is about to take
+  wait_vmcnt<0>();                                          // the refills past the last chunk (zeros) have landed in the
+  ring_barrier();                                           // ring bytes the epilogue image is about to take
 
   // ---- epilogue in the prologue's row layout: acc2 -> fp32 image [128][260] -> wave w takes rows 16w..16w+15, a lane 4
   //      consecutive columns: out = x + alpha * (acc2 + b2) leaves as 1-KB row stores, and the LayerNorm of the NEXT sub-layer
@@ -290,7 +270,7 @@ __global__ __launch_bounds__(512) void ffn_fused_kernel(const float* __restrict_
 #pragma unroll
       for (int r = 0; r < 16; ++r)
         img[(wm2 * 64 + i * 32 + mfma_row(r, lane)) * IW + wn2 * 64 + j * 32 + l31] = acc2[i][j][r];
-  ff_barrier();
+  ring_barrier();
   const f32x4 bb = *reinterpret_cast<const f32x4*>(b2 + ln * 4);
   f32x4 g2 = {0.f, 0.f, 0.f, 0.f}, h2 = {0.f, 0.f, 0.f, 0.f};
   if (ln2w != nullptr) {

@@ -3,15 +3,15 @@
 #pragma once
 #include "sfm_common.h"
 
-#define EPI_NONE 0
-#define EPI_SWISH 1
-#define EPI_GELU 2
-#define EPI_RESID 3
-#define EPI_GLU 4
-#define EPI_SIGMOID 5
-#define EPI_TANH_SCALE 6
-#define EPI_SIGMA 7
-#define EPI_CPEA 8
+#define EPI_NONE SFM_EPI_NONE                 // 0..8: the public codes (include/sincformer_hip.h)
+#define EPI_SWISH SFM_EPI_SWISH
+#define EPI_GELU SFM_EPI_GELU
+#define EPI_RESID SFM_EPI_RESID
+#define EPI_GLU SFM_EPI_GLU
+#define EPI_SIGMOID SFM_EPI_SIGMOID
+#define EPI_TANH_SCALE SFM_EPI_TANH_SCALE
+#define EPI_SIGMA SFM_EPI_SIGMA
+#define EPI_CPEA SFM_EPI_CPEA
 #define EPI_SWISH_DUAL 9     // training forward of an FFN's first Linear: out = keep * swish(z), out2 = d = keep * swish'(z) (16-bit)
 #define EPI_SWISH_BWD 10     // training backward: out = v * aux, aux = the saved derivative factor d
 
@@ -34,37 +34,13 @@ struct Gemm2Params {
   u16* out2;                                      // EPI_SWISH_DUAL: second output (that derivative factor), layout of `out`
 };
 
-// 16-bit results are written in the operands' format T (out_f32 == 0) or in the OTHER 16-bit format (out_f32 == 2: a stage
-// boundary of the precision policy, e.g. fp16 projections feeding a bf16 attention core); out_f32 == 1 is fp32.
-template <class T>
-__device__ __forceinline__ uint32_t pack2_out(float lo, float hi, bool other) {
-  if (T::id == SFM_DT_BF16) return other ? F16::pack(lo, hi) : BF16::pack(lo, hi);
-  return other ? BF16::pack(lo, hi) : F16::pack(lo, hi);
-}
+// 16-bit results are written in the operands' format T (out_f32 == 0) or in the OTHER 16-bit format (out_f32 == 2: pack2_out,
+// sfm_common.h); out_f32 == 1 is fp32.
 template <class T>
 __device__ __forceinline__ u16 from_f32_out(float v, bool other) {
   if (T::id == SFM_DT_BF16) return other ? F16::from_f32(v) : BF16::from_f32(v);
   return other ? BF16::from_f32(v) : F16::from_f32(v);
 }
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-// The wait in front of a ring barrier: this wave's LDS-DMA pieces of the stage to consume have landed (counted vmcnt) AND its
-// own ds_reads of the stage it read last have RETURNED (lgkmcnt(0)).  The second half is what makes the refill right after the
-// barrier safe (WAR): the compiler sinks the last MFMAs of a k-tile below the next barrier and leaves their operand reads in
-// flight across it; without the lgkmcnt a fast wave's refill of that slot (L2-hit latency: a few hundred cycles) could land
-// before a slow wave's reads were served - rare wrong 64 x 32 accumulator blocks (found in round 3 by
-// tools/pa_determinism_probe.py: 3-7 passes of 300 at B 64 in conv16p; cdna guide: "restage ... 1 phase after when an lgkmcnt
-// before the reading phase's first barrier retired those reads").
-template <int N>
-__device__ __forceinline__ void wait_ring() {
-  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
-}
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
 
 // Epilogue of one wave tile (64 rows x WN columns, accumulators acc[2][NJ]) in 8 passes of 8 rows through the wave's private
 // LDS strip `img` (8 x (WN + 4) floats): bias / activation / GLU / residual / dropout / GroupNorm partials, 16-byte row stores.

@@ -19,14 +19,6 @@ struct TnConv {            // = gemm16_tn.hip
   int toeplitz;
 };
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-template <int N>
-__device__ __forceinline__ void tn2_wait_vmcnt() {
-  // + lgkmcnt(0): this wave's transposed reads of the slot refilled after the barrier have returned (WAR, see gemm16_epi.h wait_ring)
-  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
-}
-
 template <class T, int WNW, int WKW, int STAGES>
 __global__ __launch_bounds__(WNW * WKW * 64) void gemm16_tn2_kernel(const u16* __restrict__ G, const u16* __restrict__ X,
                                                                     float* __restrict__ dW, float* __restrict__ db, int M, int N,
@@ -173,9 +165,9 @@ __global__ __launch_bounds__(WNW * WKW * 64) void gemm16_tn2_kernel(const u16* _
   for (int t = 0; t < nsteps; ++t) {
     // step t must have landed; up to D - 1 younger steps may stay in flight
     const int younger = (nsteps - 1 - t) < (D - 1) ? (nsteps - 1 - t) : (D - 1);
-    if (younger >= 2) tn2_wait_vmcnt<2 * NLD>();
-    else if (younger == 1) tn2_wait_vmcnt<NLD>();
-    else tn2_wait_vmcnt<0>();
+    if (younger >= 2) wait_ring<2 * NLD>();                    // (+ lgkmcnt(0): the transposed reads of the slot refilled below have returned)
+    else if (younger == 1) wait_ring<NLD>();
+    else wait_ring<0>();
     __builtin_amdgcn_s_barrier();                              // ... for every wave; and the slot refilled below is no longer read
     if (t + D < nsteps) {
       int st = stage + D;

@@ -20,24 +20,6 @@
 #define HP_NSTAGE 3
 #define HP_IMG 16384
 
-typedef __attribute__((address_space(3))) void* hp_lds_ptr_t;
-
-template <int N>
-__device__ __forceinline__ void hp_wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ void hp_frag_read(u32x4& dst, uint32_t lds_addr) {
-  asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(lds_addr) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void hp_frag_wait(u32x4& frag) {
-  asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(frag) : "n"(N) : "memory");
-}
-__device__ __forceinline__ void hp_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 
 template <class T>
 __global__ __launch_bounds__(512) void headpool_kernel(const u16* __restrict__ A, const u16* __restrict__ W,
@@ -69,11 +51,11 @@ __global__ __launch_bounds__(512) void headpool_kernel(const u16* __restrict__ A
     const int row = inst * 2 + (lane >> 5);
     const int lc = (lane & 31) ^ (row & 15);
     const int r = r_lo + row;
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rs, (hp_lds_ptr_t)(smem + inst * 1024), 16,
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rs, (lds_ptr_t)(smem + inst * 1024), 16,
                                              r < Tin ? (r * lda + lc * 8) * 2 : Tin * lda * 2, 0, 0, 0);
   }
   for (int i = tid; i < NW; i += 512) bs[i] = bias ? bias[i] : 0.f;
-  hp_wait_vmcnt<0>();
+  wait_vmcnt<0>();
   __syncthreads();
   const int r1 = (wave >> 1) * 32 + l31;                            // this lane's row of the tile
   u32x4 hf[16];
@@ -86,7 +68,7 @@ __global__ __launch_bounds__(512) void headpool_kernel(const u16* __restrict__ A
     const int row = inst * 2 + (lane >> 5);
     const int lc = (lane & 31) ^ (row & 15);
     const int voff = c < nch ? ((c * 64 + row) * HP_K + lc * 8) * 2 : w_bytes;
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rs, (hp_lds_ptr_t)(smem + stage * HP_STAGE + inst * 1024), 16, voff, 0, 0, 0);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rs, (lds_ptr_t)(smem + stage * HP_STAGE + inst * 1024), 16, voff, 0, 0, 0);
   };
 #pragma unroll
   for (int c = 0; c < 3; ++c)
@@ -95,7 +77,7 @@ __global__ __launch_bounds__(512) void headpool_kernel(const u16* __restrict__ A
 
   const int half = wave & 1;
   const int n1 = half * 32 + l31;
-  const uint32_t w_lane = (uint32_t)(uintptr_t)(hp_lds_ptr_t)smem + (uint32_t)(n1 * 512);
+  const uint32_t w_lane = (uint32_t)(uintptr_t)(lds_ptr_t)smem + (uint32_t)(n1 * 512);
   const int hx4 = (hl ^ (n1 & 15)) << 4;
   const bool own = (r_lo + r1) < own_end;                           // this lane's row counts in this tile's statistics
   float gs[2] = {0.f, 0.f}, gq[2] = {0.f, 0.f};                     // per-lane sums of the chunk in flight: the wave's two groups
@@ -166,8 +148,8 @@ __global__ __launch_bounds__(512) void headpool_kernel(const u16* __restrict__ A
   };
 
   // ---- chunk 0 alone ----
-  hp_wait_vmcnt<8>();
-  hp_barrier();
+  wait_vmcnt<8>();
+  ring_barrier();
   f32x16 s1;
 #pragma unroll
   for (int r = 0; r < 16; ++r) s1[r] = 0.f;
@@ -181,8 +163,8 @@ __global__ __launch_bounds__(512) void headpool_kernel(const u16* __restrict__ A
       if (k + 4 < 16) fw[k & 3] = *reinterpret_cast<const u32x4*>(smem + n1 * 512 + (((2 * (k + 4) + hl) ^ (n1 & 15)) << 4));
     }
   }
-  hp_wait_vmcnt<4>();
-  hp_barrier();
+  wait_vmcnt<4>();
+  ring_barrier();
 
   int stage_next = 1, stage_free = 0;
   for (int c = 0; c + 1 < nch; ++c) {
@@ -193,24 +175,24 @@ __global__ __launch_bounds__(512) void headpool_kernel(const u16* __restrict__ A
     const uint32_t fbase = w_lane + (uint32_t)(stage_next * HP_STAGE);
     u32x4 fw[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) hp_frag_read(fw[k], fbase + (uint32_t)(hx4 ^ (k << 5)));
+    for (int k = 0; k < 4; ++k) frag_read(fw[k], fbase + (uint32_t)(hx4 ^ (k << 5)));
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
-      if (k <= 12) hp_frag_wait<3>(fw[k & 3]);
-      else if (k == 13) hp_frag_wait<2>(fw[k & 3]);
-      else if (k == 14) hp_frag_wait<1>(fw[k & 3]);
-      else hp_frag_wait<0>(fw[k & 3]);
+      if (k <= 12) frag_wait<3>(fw[k & 3]);
+      else if (k == 13) frag_wait<2>(fw[k & 3]);
+      else if (k == 14) frag_wait<1>(fw[k & 3]);
+      else frag_wait<0>(fw[k & 3]);
       s1n = T::mfma(fw[k & 3], hf[k], s1n);
-      if (k + 4 < 16) hp_frag_read(fw[k & 3], fbase + (uint32_t)(hx4 ^ ((k + 4) << 5)));
+      if (k + 4 < 16) frag_read(fw[k & 3], fbase + (uint32_t)(hx4 ^ ((k + 4) << 5)));
       if ((k & 3) == 1) epi_quad(s1, c, k >> 2);
       if ((k & 3) == 3) w_piece(c + 3, stage_free, k >> 2);
     }
     stats_out(c);
     s1 = s1n;
     // W(c + 2) has landed: behind it are the 4 pieces of W(c + 3) and (c >= 1) this period's pooled store
-    if (c >= 1) hp_wait_vmcnt<5>();
-    else hp_wait_vmcnt<4>();
-    hp_barrier();
+    if (c >= 1) wait_vmcnt<5>();
+    else wait_vmcnt<4>();
+    ring_barrier();
     stage_free = stage_next;
     stage_next = (stage_next == HP_NSTAGE - 1) ? 0 : stage_next + 1;
   }
@@ -218,8 +200,8 @@ __global__ __launch_bounds__(512) void headpool_kernel(const u16* __restrict__ A
 #pragma unroll
   for (int q = 0; q < 4; ++q) epi_quad(s1, nch - 1, q);
   stats_out(nch - 1);
-  hp_wait_vmcnt<0>();
-  hp_barrier();
+  wait_vmcnt<0>();
+  ring_barrier();
   pool_chunk(nch - 1);
   // statistics of the tile: the four row groups in order
   if (tid < ngr * 2) {

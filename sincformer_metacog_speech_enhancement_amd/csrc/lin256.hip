@@ -18,25 +18,6 @@
 #define L2_NSTAGE 3
 #define L2_IMG 16384                      // one result image: 128 rows x 128 B (64 columns of 16 bits)
 
-typedef __attribute__((address_space(3))) void* l2_lds_ptr_t;
-
-template <int N>
-__device__ __forceinline__ void l2_wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ void l2_frag_read(u32x4& dst, uint32_t lds_addr) {
-  asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(lds_addr) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void l2_frag_wait(u32x4& frag) {
-  asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(frag) : "n"(N) : "memory");
-}
-__device__ __forceinline__ void l2_barrier() {
-  // this wave's LDS writes / reads have completed; the LDS-DMA queue (vmcnt) is NOT drained: counted waits do that
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 
 // GLU: 0 = plain (64 output columns per chunk), 1 = GLU (a chunk's 64 W rows = 32 values | 32 gates -> 32 output columns)
 // OTHER: 1 = the result is written in the other 16-bit format (a run-time flag here is a branch per convert inside the MFMA
@@ -106,12 +87,12 @@ __global__ __launch_bounds__(512) void lin256_kernel(const u16* __restrict__ A, 
       const int row = inst * 2 + (lane >> 5);
       const int lc = (lane & 31) ^ (row & 15);
       const long long voff = ((long long)(m0 + row) * lda + lc * 8) * 2;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rs, (l2_lds_ptr_t)(smem + inst * 1024), 16,
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rs, (lds_ptr_t)(smem + inst * 1024), 16,
                                                voff < a_bytes ? (int)voff : a_bytes, 0, 0, 0);
     }
   }
   for (int i = tid; i < NW; i += 512) bs[i] = bias ? bias[i] : 0.f;
-  l2_wait_vmcnt<0>();
+  wait_vmcnt<0>();
   __syncthreads();
   const int r1 = (wave >> 1) * 32 + l31;                            // this lane's row of the tile
   u32x4 hf[16];                                                     // the wave's 32 rows x 256 k as MFMA B-operand fragments
@@ -127,7 +108,7 @@ __global__ __launch_bounds__(512) void lin256_kernel(const u16* __restrict__ A, 
     const int row = inst * 2 + (lane >> 5);
     const int lc = (lane & 31) ^ (row & 15);
     const int voff = c < nch ? ((c * 64 + row) * L2_K + lc * 8) * 2 : w_bytes;
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rs, (l2_lds_ptr_t)(smem + stage * L2_STAGE + inst * 1024), 16, voff, 0, 0, 0);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rs, (lds_ptr_t)(smem + stage * L2_STAGE + inst * 1024), 16, voff, 0, 0, 0);
   };
 #pragma unroll
   for (int c = 0; c < 3; ++c)
@@ -137,7 +118,7 @@ __global__ __launch_bounds__(512) void lin256_kernel(const u16* __restrict__ A, 
   // this lane's W row inside a chunk (= MFMA A-operand row l31 of the wave's 32 units)
   const int half = wave & 1;
   const int n1 = GLU ? (half * 16 + l31 + ((l31 >= 16) ? 16 : 0)) : (half * 32 + l31);
-  const uint32_t w_lane = (uint32_t)(uintptr_t)(l2_lds_ptr_t)smem + (uint32_t)(n1 * 512);
+  const uint32_t w_lane = (uint32_t)(uintptr_t)(lds_ptr_t)smem + (uint32_t)(n1 * 512);
   const int hx4 = (hl ^ (n1 & 15)) << 4;                            // fragment k at w_lane + stage + (hx4 ^ (k << 5))
   // accumulator register 4q + e of this lane = unit 8q + 4hl + e of the wave = chunk row:
   auto unit_row = [&](int q) { return GLU ? (half * 16 + 8 * (q & 1) + 4 * hl + ((q >= 2) ? 32 : 0)) : (half * 32 + 8 * q + 4 * hl); };
@@ -215,8 +196,8 @@ __global__ __launch_bounds__(512) void lin256_kernel(const u16* __restrict__ A, 
   };
 
   // ---- chunk 0 alone ----
-  l2_wait_vmcnt<8>();                                               // W(0) has landed (W(1), W(2) behind it)
-  l2_barrier();
+  wait_vmcnt<8>();                                                  // W(0) has landed (W(1), W(2) behind it)
+  ring_barrier();
   f32x16 s1;
   s_init(0, s1);
   {
@@ -229,8 +210,8 @@ __global__ __launch_bounds__(512) void lin256_kernel(const u16* __restrict__ A, 
       if (k + 4 < 16) fw[k & 3] = *reinterpret_cast<const u32x4*>(smem + n1 * 512 + (((2 * (k + 4) + hl) ^ (n1 & 15)) << 4));
     }
   }
-  l2_wait_vmcnt<4>();                                               // W(1) has landed
-  l2_barrier();                                                     // ... for everyone; W(0) has been read by everyone
+  wait_vmcnt<4>();                                                  // W(1) has landed
+  ring_barrier();                                                   // ... for everyone; W(0) has been read by everyone
 
   // ---- X(c), c = 0 .. nch - 2: MFMAs of chunk c + 1 | epilogue of chunk c | refill W(c + 3) -> the stage W(c) left |
   //      row stores of the image completed one barrier ago ----
@@ -242,7 +223,7 @@ __global__ __launch_bounds__(512) void lin256_kernel(const u16* __restrict__ A, 
     if constexpr (OTHER == 2) {
       if (c >= 1) {                                                 // chunk c - 1: out of the images, then they may be rewritten
         store_chunk32(c - 1);
-        l2_barrier();
+        ring_barrier();
       }
     }
     if (OTHER != 2 && c >= CPG && (c % CPG) == 0) {   // group c / CPG - 1 was completed in X(c - 1)
@@ -255,25 +236,25 @@ __global__ __launch_bounds__(512) void lin256_kernel(const u16* __restrict__ A, 
     const uint32_t fbase = w_lane + (uint32_t)(stage_next * L2_STAGE);
     u32x4 fw[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) l2_frag_read(fw[k], fbase + (uint32_t)(hx4 ^ (k << 5)));
+    for (int k = 0; k < 4; ++k) frag_read(fw[k], fbase + (uint32_t)(hx4 ^ (k << 5)));
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
-      if (k <= 12) l2_frag_wait<3>(fw[k & 3]);
-      else if (k == 13) l2_frag_wait<2>(fw[k & 3]);
-      else if (k == 14) l2_frag_wait<1>(fw[k & 3]);
-      else l2_frag_wait<0>(fw[k & 3]);
+      if (k <= 12) frag_wait<3>(fw[k & 3]);
+      else if (k == 13) frag_wait<2>(fw[k & 3]);
+      else if (k == 14) frag_wait<1>(fw[k & 3]);
+      else frag_wait<0>(fw[k & 3]);
       s1n = T::mfma(fw[k & 3], hf[k], s1n);
-      if (k + 4 < 16) l2_frag_read(fw[k & 3], fbase + (uint32_t)(hx4 ^ ((k + 4) << 5)));
+      if (k + 4 < 16) frag_read(fw[k & 3], fbase + (uint32_t)(hx4 ^ ((k + 4) << 5)));
       if ((k & 3) == 1) epi_quad(s1, c, k >> 2);
       if ((k & 3) == 3) w_piece(c + 3, stage_free, k >> 2);
     }
     s1 = s1n;
     // W(c + 2) has landed: behind it in this wave's queue are the 4 pieces of W(c + 3) and this period's row stores
-    if (OTHER == 2) l2_wait_vmcnt<8>();                             // (fp32: 4 row stores per period; none in X(0), where 8 is lenient
+    if (OTHER == 2) wait_vmcnt<8>();                                // (fp32: 4 row stores per period; none in X(0), where 8 is lenient
                                                                     //  by nothing: W(2) then has only the 4 pieces of W(3) behind it)
-    else if (did_store) l2_wait_vmcnt<6>();
-    else l2_wait_vmcnt<4>();
-    l2_barrier();                                                   // image of chunk c complete; W(c + 1) read by everyone
+    else if (did_store) wait_vmcnt<6>();
+    else wait_vmcnt<4>();
+    ring_barrier();                                                 // image of chunk c complete; W(c + 1) read by everyone
     stage_free = stage_next;
     stage_next = (stage_next == L2_NSTAGE - 1) ? 0 : stage_next + 1;
   }
@@ -281,13 +262,13 @@ __global__ __launch_bounds__(512) void lin256_kernel(const u16* __restrict__ A, 
   if constexpr (OTHER == 2) {
     if (nch >= 2) {                                                 // the images still hold chunk nch - 2
       store_chunk32(nch - 2);
-      l2_barrier();
+      ring_barrier();
     }
   }
 #pragma unroll
   for (int q = 0; q < 4; ++q) epi_quad(s1, nch - 1, q);
-  l2_wait_vmcnt<0>();                                               // (the zero refills past the last chunk have landed)
-  l2_barrier();
+  wait_vmcnt<0>();                                                  // (the zero refills past the last chunk have landed)
+  ring_barrier();
   if constexpr (OTHER == 2) {
     store_chunk32(nch - 1);
   } else {

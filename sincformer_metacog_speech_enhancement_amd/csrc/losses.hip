@@ -4,12 +4,6 @@
 // wave shuffles + one f64 atomic per workgroup) and the scalar finalisation on device.
 #include "sfm_common.h"
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // per utterance b: S[b] = { sum e, sum t, sum e^2, sum t^2, sum e*t }   (accumulated with atomics: zero S first)
 __global__ __launch_bounds__(256) void wave_moments_kernel(const float* __restrict__ est, const float* __restrict__ tgt,
                                                            double* __restrict__ S, int L, double* __restrict__ ws) {

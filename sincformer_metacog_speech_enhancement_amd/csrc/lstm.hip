@@ -14,17 +14,7 @@
 
 constexpr int LSTM_FWD_LPU = 4;              // lanes per hidden unit of the forward recurrence (8 = round 1's mapping)
 
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float v) {          // v + v[permuted lane] (within a row of 16 lanes)
-  const int x = __builtin_bit_cast(int, v);
-  const int y = __builtin_amdgcn_update_dpp(0, x, CTRL, 0xF, 0xF, false);
-  return v + __builtin_bit_cast(float, y);
-}
-template <int CTRL>
-__device__ __forceinline__ float dpp_get(float v) {
-  const int y = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, false);
-  return __builtin_bit_cast(float, y);
-}
+// DPP controls for dpp_perm / dpp_perm_add (sfm_common.h)
 #define DPP_XOR1 0xB1        // quad_perm [1,0,3,2]
 #define DPP_XOR2 0x4E        // quad_perm [2,3,0,1]
 #define DPP_HALF_MIRROR 0x141  // lane i <-> 7-i inside each group of 8
@@ -88,15 +78,15 @@ __global__ __launch_bounds__(LPU * H) void bilstm_layer_kernel(const float* __re
     }
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-      a[g] = dpp_add<DPP_XOR1>(a[g]);
-      a[g] = dpp_add<DPP_XOR2>(a[g]);
-      if (LPU == 8) a[g] = dpp_add<DPP_HALF_MIRROR>(a[g]);
+      a[g] = dpp_perm_add<DPP_XOR1>(a[g]);
+      a[g] = dpp_perm_add<DPP_XOR2>(a[g]);
+      if (LPU == 8) a[g] = dpp_perm_add<DPP_HALF_MIRROR>(a[g]);
     }
     // every lane now holds the 4 complete pre-activations of its unit; lane q of each quad activates gate q
     const float pre = ((mygate == 0) ? a[0] : (mygate == 1) ? a[1] : (mygate == 2) ? a[2] : a[3]) + xcur;
     const float act = gsc * fast_sigmoid(gsc * pre) + gof;
-    const float ig = dpp_get<DPP_Q0>(act), fg = dpp_get<DPP_Q1>(act);
-    const float cg = dpp_get<DPP_Q2>(act), og = dpp_get<DPP_Q3>(act);
+    const float ig = dpp_perm<DPP_Q0>(act), fg = dpp_perm<DPP_Q1>(act);
+    const float cg = dpp_perm<DPP_Q2>(act), og = dpp_perm<DPP_Q3>(act);
     c = fg * c + ig * cg;
     const float h = og * (2.0f * fast_sigmoid(2.0f * c) - 1.0f);
     if (ks == 0) {
@@ -149,7 +139,7 @@ __global__ __launch_bounds__(LPU * H, 4) void bilstm_layer16_kernel(const float*
   const float gsc = (mygate == 2) ? 2.0f : 1.0f, gof = (mygate == 2) ? -1.0f : 0.0f;
   // unit j's h as a byte address in LDS.  The 16-bit store is an asm statement: a C++ store through a _Float16 lvalue into the
   // uint32_t array is an aliasing violation, and the compiler then reads ONE dword per 16-byte group and reuses it
-  const uint32_t hbase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)&hs[0][0];
+  const uint32_t hbase = (uint32_t)(uintptr_t)(lds_ptr_t)&hs[0][0];
   const uint32_t hslot = hbase + ((j / KS) * SLW * 2 + (j % KS)) * 2;
   const uint32_t hread = hbase + ks * SLW * 4;                // this lane's slice (the reads are asm too: 16-byte, counted waits)
   float xnext = xb[(long long)t * (8 * H)];
@@ -181,14 +171,14 @@ __global__ __launch_bounds__(LPU * H, 4) void bilstm_layer16_kernel(const float*
     }
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-      a[g] = dpp_add<DPP_XOR1>(a[g]);
-      a[g] = dpp_add<DPP_XOR2>(a[g]);
-      if (LPU == 8) a[g] = dpp_add<DPP_HALF_MIRROR>(a[g]);
+      a[g] = dpp_perm_add<DPP_XOR1>(a[g]);
+      a[g] = dpp_perm_add<DPP_XOR2>(a[g]);
+      if (LPU == 8) a[g] = dpp_perm_add<DPP_HALF_MIRROR>(a[g]);
     }
     const float pre = ((mygate == 0) ? a[0] : (mygate == 1) ? a[1] : (mygate == 2) ? a[2] : a[3]) + xcur;
     const float act = gsc * fast_sigmoid(gsc * pre) + gof;
-    const float ig = dpp_get<DPP_Q0>(act), fg = dpp_get<DPP_Q1>(act);
-    const float cg = dpp_get<DPP_Q2>(act), og = dpp_get<DPP_Q3>(act);
+    const float ig = dpp_perm<DPP_Q0>(act), fg = dpp_perm<DPP_Q1>(act);
+    const float cg = dpp_perm<DPP_Q2>(act), og = dpp_perm<DPP_Q3>(act);
     c = fg * c + ig * cg;
     const float h = og * (2.0f * fast_sigmoid(2.0f * c) - 1.0f);
     if (ks == 0) {
@@ -285,9 +275,9 @@ __global__ __launch_bounds__(LPU * H) void bilstm_layer_bwd_kernel(const float* 
       a2 += w[i + 7] * u[3];
     }
     a += a2;
-    a = dpp_add<DPP_XOR1>(a);
-    a = dpp_add<DPP_XOR2>(a);
-    if (LPU == 8) a = dpp_add<DPP_HALF_MIRROR>(a);
+    a = dpp_perm_add<DPP_XOR1>(a);
+    a = dpp_perm_add<DPP_XOR2>(a);
+    if (LPU == 8) a = dpp_perm_add<DPP_HALF_MIRROR>(a);
     dh_rec = a;                                                // every lane of the unit holds it; lane 0 uses it
   }
 }

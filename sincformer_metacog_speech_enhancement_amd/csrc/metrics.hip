@@ -10,12 +10,6 @@
 // frames / spectrum rows [frame_off[u], frame_off[u + 1]) - the metric's OWN framing, an utterance may own no frame at all.
 #include "sfm_common.h"
 
-__device__ __forceinline__ double wsum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // acc[b] = { sum of kept frame SNRs, number of kept frames }
 __global__ __launch_bounds__(256) void ssnr_frames_kernel(const float* __restrict__ clean, const float* __restrict__ enh,
                                                           double* __restrict__ acc, int L, int nframes, int frame, int hop,
@@ -33,8 +27,8 @@ __global__ __launch_bounds__(256) void ssnr_frames_kernel(const float* __restric
       sp += cv * cv;
       ep += d * d;
     }
-    sp = wsum_d(sp);
-    ep = wsum_d(ep);
+    sp = wave_sum_d(sp);
+    ep = wave_sum_d(ep);
     if (sp < 1e-10) continue;                                  // silence frame: skipped (evaluation/ssnr.py:72)
     double snr = (ep < 1e-10) ? (double)upper : 10.0 * log10(sp / ep);
     snr = fmin(fmax(snr, (double)lower), (double)upper);
@@ -85,8 +79,8 @@ __global__ __launch_bounds__(256) void ssnr_frames_varlen_kernel(const float* __
       sp += cv * cv;
       ep += d * d;
     }
-    sp = wsum_d(sp);
-    ep = wsum_d(ep);
+    sp = wave_sum_d(sp);
+    ep = wave_sum_d(ep);
     if (sp < 1e-10) continue;
     double snr = (ep < 1e-10) ? (double)upper : 10.0 * log10(sp / ep);
     snr = fmin(fmax(snr, (double)lower), (double)upper);
@@ -122,9 +116,9 @@ __device__ __forceinline__ double spec_frame_value(const float* __restrict__ cr,
       Bq += em * em;
       C += cm * em;
     }
-    A = wsum_d(A);
-    Bq = wsum_d(Bq);
-    C = wsum_d(C);
+    A = wave_sum_d(A);
+    Bq = wave_sum_d(Bq);
+    C = wave_sum_d(C);
     const double clean_energy = sqrt(A + 1e-10);
     const double k = clean_energy / (sqrt(Bq) + 1e-10);        // enh_norm = enh_spec * k
     const double corr = (k * C) / (sqrt(A * (k * k * Bq)) + 1e-10);
@@ -136,7 +130,7 @@ __device__ __forceinline__ double spec_frame_value(const float* __restrict__ cr,
       const double d = log(sqrt(a0 * a0 + a1 * a1) + 1e-10) - log(sqrt(b0 * b0 + b1 * b1) + 1e-10);
       D += d * d;
     }
-    return sqrt(wsum_d(D) / (double)F);
+    return sqrt(wave_sum_d(D) / (double)F);
   }
 }
 

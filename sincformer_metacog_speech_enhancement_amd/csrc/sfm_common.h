@@ -9,14 +9,7 @@
 #include <stdint.h>
 #include <atomic>
 #include <mutex>
-
-#define SFM_OK 0
-#define SFM_ERR_ARG -1
-#define SFM_ERR_SHAPE -2
-#define SFM_ERR_LAUNCH -3
-
-#define SFM_DT_BF16 0
-#define SFM_DT_F16 1
+#include "sincformer_hip.h"     // the public ABI: status, dtype and epilogue codes, and the declaration every entry point is checked against
 
 typedef uint16_t u16;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -80,6 +73,13 @@ struct F16 {
 template <class T>
 __device__ __forceinline__ uint32_t pack2(float lo, float hi) {
   return T::pack(lo, hi);
+}
+// 16-bit results are written in the operands' format T or (other) in the OTHER 16-bit format: a stage boundary of the precision
+// policy (ops.STAGES), e.g. fp16 projections feeding a bf16 attention core
+template <class T>
+__device__ __forceinline__ uint32_t pack2_out(float lo, float hi, bool other) {
+  if (T::id == SFM_DT_BF16) return other ? F16::pack(lo, hi) : BF16::pack(lo, hi);
+  return other ? BF16::pack(lo, hi) : F16::pack(lo, hi);
 }
 
 // ---- counter-based dropout: keep(seed, idx) is a pure function, so forward and backward agree and no
@@ -146,14 +146,23 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+__device__ __forceinline__ double wave_sum_d(double v) {       // the fp64 accumulators of the losses and metrics
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
 
+// DPP lane permutations (CTRL: a dpp_ctrl code)
+template <int CTRL>
+__device__ __forceinline__ float dpp_perm(float v) {           // v of the lane that DPP control CTRL selects (within a row of 16 lanes)
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, false));
+}
+template <int CTRL>
+__device__ __forceinline__ float dpp_perm_add(float v) {       // v + v[permuted lane]
+  return v + dpp_perm<CTRL>(v);
+}
 // wave-wide sum without LDS traffic: 4 DPP steps leave every 16-lane row's total in all of its lanes,
 // then the four row totals are combined through scalar registers (v_readlane)
-template <int CTRL>
-__device__ __forceinline__ float dpp_perm_add(float v) {
-  const int y = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, false);
-  return v + __builtin_bit_cast(float, y);
-}
 __device__ __forceinline__ float wave_sum_dpp(float v) {
   v = dpp_perm_add<0xB1>(v);     // quad_perm [1,0,3,2]
   v = dpp_perm_add<0x4E>(v);     // quad_perm [2,3,0,1]
@@ -167,16 +176,32 @@ __device__ __forceinline__ float wave_sum_dpp(float v) {
   return (r0 + r1) + (r2 + r3);
 }
 
+// v_permlane32_swap exchanges lanes 32-63 of its first operand with lanes 0-31 of the second: fed two copies of x it
+// leaves [x.lo, x.lo] and [x.hi, x.hi].  The s_nop covers the 2 wait states a VALU write of an operand needs before
+// the swap reads it.  (Scalars in and out: this compiler reads element 0 for __builtin_bit_cast(float, vec[i]).)
+__device__ __forceinline__ void xhalf_swap(float v, float& lo, float& hi) {
+  uint32_t a = __builtin_bit_cast(uint32_t, v), c = a;
+  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(c));
+  lo = __builtin_bit_cast(float, a);
+  hi = __builtin_bit_cast(float, c);
+}
+__device__ __forceinline__ float xhalf_max(float v) {
+  float lo, hi;
+  xhalf_swap(v, lo, hi);
+  return fmaxf(lo, hi);
+}
+__device__ __forceinline__ float xhalf_sum(float v) {
+  float lo, hi;
+  xhalf_swap(v, lo, hi);
+  return lo + hi;
+}
+
 // Sixteen wave-wide sums at once: lane l returns the sum over all 64 lanes of v[l & 15].  A transposing butterfly: at each
 // of the four in-row stages a lane keeps half of its values and hands the other half to a partner lane that keeps those, so
 // the work halves per stage (8 + 4 + 2 + 1 DPP adds instead of 16 x 4).  gfx9 DPP has no xor-4 / xor-8 lane permutation; the
 // mirrors (xor 15, xor 7) do, provided they come FIRST - a partner must agree with the lane on every bit already used for
 // selecting (row_mirror flips bits 3..0: used when none is; row_half_mirror flips 2..0: after bit 3 only; then xor 2, xor 1).
 // The four 16-lane rows are then added by the gfx950 lane swaps.  ~55 VALU instructions against ~190 for 16 wave_sum_dpp.
-template <int CTRL>
-__device__ __forceinline__ float dpp_perm(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, false));
-}
 __device__ __forceinline__ float wave_sum16_transpose(const float (&v)[16], int lane) {
   const bool b3 = lane & 8, b2 = lane & 4, b1 = lane & 2, b0 = lane & 1;
   float w[8], x[4], y[2];
@@ -191,10 +216,42 @@ __device__ __forceinline__ float wave_sum16_transpose(const float (&v)[16], int 
   //  inputs are the same value; s_nop 1 = the VALU-write -> permlane-swap hazard the compiler would have covered)
   float a = z, c = z;
   asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(c));     // a: rows (0,0,2,2), c: rows (1,1,3,3)
-  z = a + c;
-  a = z, c = z;
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(c));     // a: halves (lo,lo), c: (hi,hi)
-  return a + c;
+  return xhalf_sum(a + c);                                                        // halves (lo,lo) + (hi,hi)
+}
+
+// ---- LDS-DMA rings: buffer_load ... lds fills a stage (counted by vmcnt), ds_reads drain it (lgkmcnt), raw barriers between ----
+typedef __attribute__((address_space(3))) void* lds_ptr_t;
+
+template <int N>
+__device__ __forceinline__ void wait_vmcnt() {
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+// The wait in front of a ring barrier: this wave's LDS-DMA pieces of the stage to consume have landed (counted vmcnt) AND its
+// own ds_reads of the stage it read last have RETURNED (lgkmcnt(0)).  The second half is what makes the refill right after the
+// barrier safe (WAR): the compiler sinks the last MFMAs of a k-tile below the next barrier and leaves their operand reads in
+// flight across it; without the lgkmcnt a fast wave's refill of that slot (L2-hit latency: a few hundred cycles) could land
+// before a slow wave's reads were served - rare wrong 64 x 32 accumulator blocks (found in round 3 by
+// tools/pa_determinism_probe.py: 3-7 passes of 300 at B 64 in conv16p; cdna guide: "restage ... 1 phase after when an lgkmcnt
+// before the reading phase's first barrier retired those reads").
+template <int N>
+__device__ __forceinline__ void wait_ring() {
+  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
+}
+// Workgroup barrier of a ring: this wave's LDS writes / reads must have completed before other waves pass it; the LDS-DMA
+// queue (vmcnt) is deliberately NOT drained here - that is what the counted waits are for.
+__device__ __forceinline__ void ring_barrier() {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+}
+// MFMA operand fragment straight from an LDS byte address, and the lgkmcnt wait the compiler does not insert for it
+// (N = this wave's LDS reads issued after the one that filled `frag`)
+__device__ __forceinline__ void frag_read(u32x4& dst, uint32_t lds_addr) {
+  asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(lds_addr) : "memory");
+}
+template <int N>
+__device__ __forceinline__ void frag_wait(u32x4& frag) {
+  asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(frag) : "n"(N) : "memory");
 }
 
 // Packed (variable-length) batches: utterance b owns rows [off[b], off[b + 1]) of a concatenated matrix, off = int32[n + 1]

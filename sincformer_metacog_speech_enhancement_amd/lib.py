@@ -151,6 +151,13 @@ SIGNATURES = {
     "sfm_mse_loss": [c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, c_vp],
 }
 
+# the entry points that return a size (long long); every other one returns an int status
+RETURNS_LONG_LONG = {
+    "sfm_mean_time_scratch_floats", "sfm_sinc_wgrad_scratch_floats", "sfm_sinc_shift_len", "sfm_gn_bwd_reduce_ws_floats",
+    "sfm_tn_ws_floats", "sfm_colsum_ws_floats", "sfm_layernorm_bwd_ws_floats", "sfm_col_stats_ws_floats",
+    "sfm_dwconv_wgrad_scratch_floats", "sfm_memory_param_floats",
+}
+
 _lib = None
 
 
@@ -174,7 +181,7 @@ def load():
         except AttributeError as e:
             raise HipExtensionMissing("symbol %s missing from %s" % (name, LIB_PATH)) from e
         fn.argtypes = args
-        fn.restype = c_ll if name.endswith("_scratch_floats") or name.endswith("_ws_floats") or name in ("sfm_sinc_shift_len", "sfm_memory_param_floats") else c_i
+        fn.restype = c_ll if name in RETURNS_LONG_LONG else c_i
     _lib = lib
     return lib
 

@@ -1,5 +1,5 @@
 """The C-ABI library loads on a machine without a GPU and exports every symbol that
-include/sincformer_hip.h declares, with the arity the ctypes binding assumes."""
+include/sincformer_hip.h declares, with the parameter and return types the ctypes binding assumes."""
 import ctypes
 import os
 import re
@@ -10,14 +10,30 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "sincformer_hip.h")
 
 
+_CTYPES = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "float": ctypes.c_float, "unsigned int": ctypes.c_uint}
+
+
+def _ctype(decl):
+    """ctypes type of one C parameter or return type, e.g. "const float* x", "unsigned int seed", "long long" """
+    decl = " ".join(decl.replace("*", " * ").split())
+    if "*" in decl:
+        return ctypes.c_void_p
+    words = [w for w in decl.split() if w != "const"]
+    for n in (len(words), len(words) - 1):                  # with or without a parameter name behind the type
+        if " ".join(words[:n]) in _CTYPES:
+            return _CTYPES[" ".join(words[:n])]
+    raise ValueError("no ctypes mapping for %r" % decl)
+
+
 def _header_decls():
+    """name -> (return type, [parameter types]) as ctypes types, for every function the header declares"""
     src = open(HEADER).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     decls = {}
-    for m in re.finditer(r"\b(?:long long|int)\s+(sfm_\w+)\s*\(([^;]*?)\)\s*;", src, flags=re.S):
-        args = m.group(2).strip()
-        n = 0 if args in ("", "void") else len([a for a in args.split(",") if a.strip()])
-        decls[m.group(1)] = n
+    for m in re.finditer(r"\b(long long|int)\s+(sfm_\w+)\s*\(([^;]*?)\)\s*;", src, flags=re.S):
+        args = m.group(3).strip()
+        params = [] if args in ("", "void") else [_ctype(a) for a in args.split(",")]
+        decls[m.group(2)] = (_ctype(m.group(1)), params)
     return decls
 
 
@@ -30,10 +46,13 @@ def built():
 
 def test_header_declares_the_bound_symbols(built):
     decls = _header_decls()
-    assert len(decls) >= 18
+    assert len(decls) >= 108                                # (the pattern has not lost a declaration)
     assert set(decls) == set(built.SIGNATURES), set(decls) ^ set(built.SIGNATURES)
-    for name, n in decls.items():
-        assert n == len(built.SIGNATURES[name]), (name, n, len(built.SIGNATURES[name]))
+    L = built.load()
+    for name, (ret, params) in decls.items():
+        assert built.SIGNATURES[name] == params, (name, params, built.SIGNATURES[name])
+        assert getattr(L, name).restype is ret, (name, ret, getattr(L, name).restype)
+    assert built.RETURNS_LONG_LONG == {name for name, (ret, _) in decls.items() if ret is ctypes.c_longlong}
 
 
 def test_library_exports_every_symbol(built):

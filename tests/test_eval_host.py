@@ -173,7 +173,7 @@ def test_header_binding_and_library_agree_on_the_new_entry_points(L):
     decls = test_abi._header_decls()
     raw = ctypes.CDLL(lib.LIB_PATH)
     for n in ("sfm_ssnr_frames_varlen", "sfm_stoi_frames_varlen", "sfm_lsd_frames", "sfm_lsd_frames_varlen", "sfm_wave_moments_varlen"):
-        assert decls[n] == len(lib.SIGNATURES[n]) and hasattr(raw, n), n
+        assert decls[n][1] == lib.SIGNATURES[n] and decls[n][0] is getattr(L, n).restype and hasattr(raw, n), n
 
 
 # ---------------------------------------------------------------------------

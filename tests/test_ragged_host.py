@@ -180,7 +180,7 @@ def test_header_binding_and_library_agree_on_the_new_entry_points(L):
              "sfm_istft_ola_varlen")
     raw = ctypes.CDLL(lib.LIB_PATH)
     for n in names:
-        assert decls[n] == len(lib.SIGNATURES[n]) and hasattr(raw, n), n
+        assert decls[n][1] == lib.SIGNATURES[n] and decls[n][0] is getattr(L, n).restype and hasattr(raw, n), n
 
 
 # ---------------------------------------------------------------------------
