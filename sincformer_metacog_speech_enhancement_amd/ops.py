@@ -3,6 +3,7 @@ host-side weight packing the kernels expect.  Tensors must live on the HIP
 device; there is no CPU fallback (lib.load() raises if the .so is missing)."""
 import ctypes
 import math
+import re as _re
 import numpy as np
 import torch
 
@@ -266,69 +267,29 @@ def _ws(n, device, dtype=torch.float32):
 
 
 def _call(name, fn, args, flops=0.0, nbytes=0.0, tag=None):
-    if profiler.active(name):
-        e0 = torch.cuda.Event(enable_timing=True)
-        e1 = torch.cuda.Event(enable_timing=True)
-        e0.record()
-        rc = fn(*args)
-        e1.record()
-        profiler.records.append((name, e0, e1, float(flops), float(nbytes)))
-        if tag is not None and profiler.tags:
-            profiler.records.append(("%s[%s]" % (name, tag), e0, e1, float(flops), float(nbytes)))
-    else:
-        rc = fn(*args)
-    _lib.check(rc, name)
-
-
-
-def _cost_of(name, v):
-    """algorithmic (flops, bytes) of one launch, from the wrapper's local variables
-    (bytes = each operand read once + each result written once)."""
+    """enqueue one entry point; flops / nbytes = the launch's algorithmic cost, stated by the wrapper (each operand read once,
+    each result written once: DESIGN.md section 4), tag = its shape for the profiler's per-shape records"""
+    if len(args) != len(fn.argtypes):                   # ctypes itself lets surplus arguments of a cdecl function through
+        raise TypeError("%s takes %d arguments (include/sincformer_hip.h), %d given" % (fn.__name__, len(fn.argtypes), len(args)))
     try:
-        if name == "gemm16":
-            pw = v["pw"]
-            ncols = pw.Npad if pw.glu else pw.N
-            rows = v["B"] * v["Lout"]
-            fl = 2.0 * rows * ncols * pw.K
-            osz = 4 if v["out"].dtype == torch.float32 else 2
-            by = v["B"] * v["Lin"] * pw.cin * 2 + pw.Npad * pw.Kpad * 2 + rows * pw.N * osz
-            if v.get("resid") is not None:
-                by += rows * pw.N * 4
-            return fl, by, "M%d N%d K%d k%d s%d epi%d o%d" % (rows, ncols, pw.K, pw.ksize, v["stride"], v["epi"], osz)
-        if name == "framed_gemm_f32":
-            rows = v["B"] * v["M"]
-            osz = 4 if v["out"].dtype == torch.float32 else 2
-            return (2.0 * rows * v["N"] * v["K"], v["B"] * v["Ls"] * 4 + rows * v["N"] * osz,
-                    "M%d N%d K%d hop%d" % (rows, v["N"], v["K"], v["hop"]))
-        if name == "attention_fwd":
-            B, T, H, hd = v["B"], v["T"], v["H"], v["hd"]
-            return 4.0 * B * H * T * T * hd, 4.0 * B * T * H * hd * 2
-        if name == "layernorm":
-            M, D = v["M"], v["D"]
-            return 8.0 * M * D, M * D * (4 + (2 if v["out16"] is not None else 0) + (4 if v["out32"] is not None else 0))
-        if name == "gn_apply":
-            n = v["Bn"] * v["rows"] * v["C"]
-            isz = 4 if v["in_f32"] else 2
-            osz = 4 if v["out_f32"] else 2
-            return 10.0 * n, n * (isz * (2 if v["x2"] is not None else 1) + osz)
-        if name == "dwconv_bn_swish":
-            n = v["B"] * v["T"] * v["C"]
-            return 2.0 * n * v["KS"], n * 4
-        if name == "bilstm_layer":
-            B, T, H = v["B"], v["T"], v["H"]
-            return 2.0 * B * T * 2 * 4 * H * H, B * T * (8 * H + 2 * H) * 4
-        if name == "pool_time":
-            return 0.0, v["B"] * (v["Tin"] * v["src_bytes"] + v["Tout"] * 4) * v["C"]
-        if name == "polar_mask":
-            n = v["B"] * v["rows"] * v["F"]
-            return 20.0 * n, n * 4 * 8
-        if name == "stft_lognorm_pack":
-            return 0.0, v["M"] * v["F"] * (8 + 4)
-        if name == "istft_ola":
-            return 0.0, v["B"] * v["Ln"] * 12
-    except Exception:
-        pass
-    return 0.0, 0.0
+        if profiler.active(name):
+            e0 = torch.cuda.Event(enable_timing=True)
+            e1 = torch.cuda.Event(enable_timing=True)
+            e0.record()
+            rc = fn(*args)
+            e1.record()
+            profiler.records.append((name, e0, e1, float(flops), float(nbytes)))
+            if tag is not None and profiler.tags:
+                profiler.records.append(("%s[%s]" % (name, tag), e0, e1, float(flops), float(nbytes)))
+        else:
+            rc = fn(*args)
+    except ctypes.ArgumentError as e:                   # "argument 7: ... wrong type": say which parameter of the header that is
+        m = _re.match(r"argument (\d+):", str(e))
+        names = _lib.ABI[fn.__name__][2]
+        if m is None or not 1 <= int(m.group(1)) <= len(names):
+            raise
+        raise ctypes.ArgumentError("%s, parameter `%s`: %s" % (fn.__name__, names[int(m.group(1)) - 1], e)) from None
+    _lib.check(rc, name)
 
 
 # ---------------------------------------------------------------------------
@@ -395,6 +356,14 @@ def pack_linear(weight, bias=None, glu=False, k_pad_to=None, dtype=None):
     return PackedWeight(W.contiguous(), Bp, (N // 2) if glu else N, K, ksize, cin, glu)
 
 
+def gemm16_cost(pw, B, Lout, Lin, stride, epi, osz, has_resid):
+    """(flops, bytes, tag) of one sfm_gemm16 launch with osz-byte results.  A GLU pack multiplies its Npad columns; the bytes count
+    pw.N result columns for every pack."""
+    rows, ncols = B * Lout, pw.Npad if pw.glu else pw.N
+    nbytes = B * Lin * pw.cin * 2 + pw.Npad * pw.Kpad * 2 + rows * pw.N * osz + (rows * pw.N * 4 if has_resid else 0)
+    return 2.0 * rows * ncols * pw.K, nbytes, "M%d N%d K%d k%d s%d epi%d o%d" % (rows, ncols, pw.K, pw.ksize, stride, epi, osz)
+
+
 def gemm16(A, pw, out, *, B, Lout, Lin, a_batch_stride, ldo, o_batch_stride, lda=None, stride=1, pad=0,
            epi=EPI_NONE, resid=None, ldr=0, r_batch_stride=0, alpha=1.0, gn_partial=None, gn_group=0, nsplit=0,
            p_drop=0.0, seed=0):
@@ -409,17 +378,16 @@ def gemm16(A, pw, out, *, B, Lout, Lin, a_batch_stride, ldo, o_batch_stride, lda
     if A.dtype != _state["dtype"] or pw.w.dtype != _state["dtype"]:
         raise RuntimeError("gemm16: operand formats %s / %s do not match the stage's %s (precision policy)" %
                            (A.dtype, pw.w.dtype, _state["dtype"]))
+    cost = gemm16_cost(pw, B, Lout, Lin, stride, epi, 4 if out_f32 == 1 else 2, resid is not None)
     if p_drop > 0.0:                                   # training forward: residual-branch dropout in the epilogue
         _call("gemm16", L.sfm_gemm16_train, (_p(A), _p(pw.w), _p(pw.bias), _p(out), _p(resid), _p(gn_partial), B, Lout, Lin, cin,
                                              lda, pw.ksize, stride, pad, a_batch_stride, pw.Kpad, pw.N, pw.Npad, ldo,
                                              o_batch_stride, ldr, r_batch_stride, float(alpha), epi, out_f32, gn_group, nsplit,
-                                             _dt(), switch("gemm_variant"), float(p_drop), int(seed) & 0xffffffff, _stream()),
-              *_cost_of("gemm16", locals()))
+                                             _dt(), switch("gemm_variant"), float(p_drop), int(seed) & 0xffffffff, _stream()), *cost)
         return out
     _call("gemm16", L.sfm_gemm16_ex, (_p(A), _p(pw.w), _p(pw.bias), _p(out), _p(resid), _p(gn_partial), B, Lout, Lin, cin, lda,
                       pw.ksize, stride, pad, a_batch_stride, pw.Kpad, pw.N, pw.Npad, ldo, o_batch_stride, ldr, r_batch_stride,
-                      float(alpha), epi, out_f32, gn_group, nsplit, _dt(), switch("gemm_variant"), _stream()),
-          *_cost_of("gemm16", locals()))
+                      float(alpha), epi, out_f32, gn_group, nsplit, _dt(), switch("gemm_variant"), _stream()), *cost)
     return out
 
 
@@ -580,6 +548,12 @@ def linear16_swish(x16, pw, p_drop=0.0, seed=0, aux=None):
     return (out2, out) if aux is None else out
 
 
+def framed_gemm_cost(B, M, Ls, K, N, hop, osz):
+    """(flops, bytes, tag) of one sfm_framed_gemm_f32 launch with osz-byte results: the signal is read once, not once per frame"""
+    rows = B * M
+    return 2.0 * rows * N * K, B * Ls * 4 + rows * N * osz, "M%d N%d K%d hop%d" % (rows, N, K, hop)
+
+
 def framed_gemm(sig, Wt, out, *, B, M, Ls, sig_batch_stride, hop, padl, K, N, o_batch_stride, ldm, ldn, mode=0,
                 bias=None, out2=None, nsplit=0, gn_partial=None, gn_group=0):
     _need_dev(sig, Wt, out)
@@ -589,7 +563,7 @@ def framed_gemm(sig, Wt, out, *, B, M, Ls, sig_batch_stride, hop, padl, K, N, o_
     _call("framed_gemm_f32", L.sfm_framed_gemm_f32, (_p(sig), _p(Wt), _p(bias), _p(out), _p(out2), _p(gn_partial), B, M, Ls,
                                sig_batch_stride, hop, padl, K, Kpad, N, Npad, nsplit, o_batch_stride, ldm, ldn, mode,
                                out_f32, gn_group, _dt(), _stream()),
-          *_cost_of("framed_gemm_f32", locals()))
+          *framed_gemm_cost(B, M, Ls, K, N, hop, 4 if out_f32 else 2))
     return out
 
 
@@ -670,11 +644,16 @@ def attention(qkv16, B, T, H, hd, out=None, prescaled=False, out_dtype=None):
     _call("attention_fwd", L.sfm_attention_fwd_ex, (_p(qkv16), _p(out), B, T, H, hd, ld, out.stride(0), D, 2 * D, T * ld,
                                                     T * out.stride(0), (-1.0 if prescaled else 1.0 / math.sqrt(hd)), _dt(),
                                                     _DT_ID[out.dtype], switch("attention_variant"), _stream()),
-          *_cost_of("attention_fwd", locals()))
+          4.0 * B * H * T * T * hd, 4.0 * B * T * H * hd * 2)
     return out
 
 
 LAYERNORM_MAX_D = 512      # sfm_layernorm / sfm_layernorm_bwd_*: the widest row they normalise (and so the widest Conformer d_model)
+
+
+def layernorm_bytes(M, D, has_out16, has_out32):
+    """fp32 rows in, a 16-bit and / or an fp32 copy of the normalised rows out"""
+    return M * D * (4 + (2 if has_out16 else 0) + (4 if has_out32 else 0))
 
 
 def layernorm(x32, w, b, out16=None, out32=None, act=0, eps=1e-5):
@@ -687,16 +666,20 @@ def layernorm(x32, w, b, out16=None, out32=None, act=0, eps=1e-5):
     _call("layernorm", L.sfm_layernorm, (_p(x32), _p(w), _p(b), _p(out16), _p(out32), M, D, x32.stride(0),
                          out16.stride(0) if out16 is not None else 0, out32.stride(0) if out32 is not None else 0,
                          eps, act, _dt(), _stream()),
-          *_cost_of("layernorm", locals()))
+          8.0 * M * D, layernorm_bytes(M, D, out16 is not None, out32 is not None))
 
 
 def gn_finalize(partial, w, b, Bn, P, G, C, rows, eps=1e-5):
     L = _lib.load()
     scale = torch.empty(Bn, C, device=w.device, dtype=torch.float32)
     shift = torch.empty(Bn, C, device=w.device, dtype=torch.float32)
-    _call("gn_finalize", L.sfm_gn_finalize, (_p(partial), _p(w), _p(b), _p(scale), _p(shift), Bn, P, G, C, rows, eps, _stream()),
-          *_cost_of("gn_finalize", locals()))
+    _call("gn_finalize", L.sfm_gn_finalize, (_p(partial), _p(w), _p(b), _p(scale), _p(shift), Bn, P, G, C, rows, eps, _stream()))
     return scale, shift
+
+
+def gn_apply_bytes(n, in_f32, out_f32, two_inputs):
+    """n elements of one or two inputs in, n out, each fp32 or 16-bit"""
+    return n * ((4 if in_f32 else 2) * (2 if two_inputs else 1) + (4 if out_f32 else 2))
 
 
 def gn_apply(x1, sc1, sh1, out, Bn, rows, C, act=0, x2=None, sc2=None, sh2=None):
@@ -705,7 +688,7 @@ def gn_apply(x1, sc1, sh1, out, Bn, rows, C, act=0, x2=None, sc2=None, sh2=None)
     out_f32 = 1 if out.dtype == torch.float32 else 0
     _call("gn_apply", L.sfm_gn_apply, (_p(x1), _p(sc1), _p(sh1), _p(x2), _p(sc2), _p(sh2), _p(out), Bn, rows, C, in_f32, out_f32, act,
                         _dt(), _stream()),
-          *_cost_of("gn_apply", locals()))
+          10.0 * Bn * rows * C, gn_apply_bytes(Bn * rows * C, in_f32, out_f32, x2 is not None))
     return out
 
 
@@ -716,7 +699,7 @@ def dwconv_bn_swish(x16, wdw, bdw, bnw, bnb, bnm, bnv, B, T, C, out=None, eps=1e
         out = torch.empty_like(x16)
     _call("dwconv_bn_swish", L.sfm_dwconv_bn_swish, (_p(x16), _p(wdw), _p(bdw), _p(bnw), _p(bnb), _p(bnm), _p(bnv), _p(out), B, T, C, KS,
                                eps, _dt(), _stream()),
-          *_cost_of("dwconv_bn_swish", locals()))
+          2.0 * B * T * C * KS, B * T * C * 4)
     return out
 
 
@@ -736,15 +719,14 @@ def dwconv_folded(x16, wT, sc, sh, B, T, C, out=None, act=1):
 def convert_rows(src32, dst16, M, C, Cz, ld_src, ld_dst):
     L = _lib.load()
     _call("convert_rows", L.sfm_convert_rows, (_p(src32), _p(dst16), M, C, Cz, ld_src, ld_dst, _dt(), _stream()),
-          *_cost_of("convert_rows", locals()), tag="M%d C%d" % (M, C))
+          tag="M%d C%d" % (M, C))
 
 
 def transpose(src, dst, B, R, C, src_batch, src_row, dst_batch, dst_row):
     L = _lib.load()
     _call("transpose", L.sfm_transpose, (_p(src), _p(dst), B, R, C, src_batch, src_row, dst_batch, dst_row,
                          1 if src.dtype == torch.float32 else 0, 1 if dst.dtype == torch.float32 else 0, _dt(),
-                         _stream()),
-          *_cost_of("transpose", locals()))
+                         _stream()))
 
 
 def mean_time(src32, B, T, C, ld_src):
@@ -766,6 +748,11 @@ def pool_time_bwd(dout32, B, Tin, Tout, C):
     return dsrc
 
 
+def pool_time_bytes(B, Tin, Tout, C, src_bytes):
+    """Tin rows of src_bytes-wide elements in, Tout rows out, counted as fp32"""
+    return B * (Tin * src_bytes + Tout * 4) * C
+
+
 def pool_time(src32, dst16, dst32, B, Tin, Tout, C, ld_src, ld_dst, scale=None, shift=None):
     """adaptive average pooling over time; scale / shift [B, C]: out = scale * avg + shift (pooled GroupNorm output).
     src32: fp32, or 16-bit in the current operand format (the fused path's raw latent heads)."""
@@ -778,13 +765,13 @@ def pool_time(src32, dst16, dst32, B, Tin, Tout, C, ld_src, ld_dst, scale=None, 
         args = (_p(src32), _DT_ID[src32.dtype], _p(scale), _p(shift), _p(dst16), _p(dst32), B, Tin, Tout, C, ld_src, ld_dst,
                 _dt(), _stream())
         fn = L.sfm_pool_time_affine16
-    _call("pool_time", fn, args, *_cost_of("pool_time", locals()))
+    _call("pool_time", fn, args, 0.0, pool_time_bytes(B, Tin, Tout, C, src_bytes))
 
 
 def stft_lognorm_pack(re, im, dst16, M, F, zpad, ld_dst):
     L = _lib.load()
     _call("stft_lognorm_pack", L.sfm_stft_lognorm_pack, (_p(re), _p(im), _p(dst16), M, F, zpad, ld_dst, _dt(), _stream()),
-          *_cost_of("stft_lognorm_pack", locals()))
+          0.0, M * F * (8 + 4))
 
 
 def polar_mask(lm, lp, B, rows, F, phase_scale, ld_logits, mag_bias=None, nr=None, ni=None, mr=None, mi=None, er=None,
@@ -792,21 +779,20 @@ def polar_mask(lm, lp, B, rows, F, phase_scale, ld_logits, mag_bias=None, nr=Non
     L = _lib.load()
     _call("polar_mask", L.sfm_polar_mask, (_p(lm), _p(lp), _p(mag_bias), _p(nr), _p(ni), _p(mr), _p(mi), _p(er), _p(ei), _p(mmag), B,
                           rows, F, float(phase_scale), ld_logits, ld_enh, _stream()),
-          *_cost_of("polar_mask", locals()))
+          20.0 * B * rows * F, B * rows * F * 4 * 8)
 
 
 def complex_mul(sr, si, mr, mi):
     L = _lib.load()
     er, ei = torch.empty_like(sr), torch.empty_like(sr)
-    _call("complex_mul", L.sfm_complex_mul, (_p(sr), _p(si), _p(mr), _p(mi), _p(er), _p(ei), sr.numel(), _stream()),
-          *_cost_of("complex_mul", locals()))
+    _call("complex_mul", L.sfm_complex_mul, (_p(sr), _p(si), _p(mr), _p(mi), _p(er), _p(ei), sr.numel(), _stream()))
     return er, ei
 
 
 def istft_ola(frames, win2, out, B, T, Ln, n_fft, hop, win, ld_frames):
     L = _lib.load()
     _call("istft_ola", L.sfm_istft_ola, (_p(frames), _p(win2), _p(out), B, T, Ln, n_fft, hop, win, ld_frames, _stream()),
-          *_cost_of("istft_ola", locals()))
+          0.0, B * Ln * 12)
 
 
 # ---------------------------------------------------------------------------
@@ -928,8 +914,7 @@ def istft_ola_varlen(frames, win2, out, frame_off, samp_off, B, n_fft, hop, win,
 
 def pack_spec(re, im, dst, M, F, ld, ld_src):
     L = _lib.load()
-    _call("pack_spec", L.sfm_pack_spec, (_p(re), _p(im), _p(dst), M, F, ld, ld_src, _stream()),
-          *_cost_of("pack_spec", locals()))
+    _call("pack_spec", L.sfm_pack_spec, (_p(re), _p(im), _p(dst), M, F, ld, ld_src, _stream()))
 
 
 def sinc_filters(low_hz, band_hz, window, n_, C, K, sample_rate, min_low_hz, min_band_hz, want_filt=True):
@@ -939,8 +924,7 @@ def sinc_filters(low_hz, band_hz, window, n_, C, K, sample_rate, min_low_hz, min
     Wt = torch.zeros(round_up(K, 32), Npad, device=dev, dtype=torch.float32)
     filt = torch.empty(C, K, device=dev, dtype=torch.float32) if want_filt else None
     _call("sinc_filters", L.sfm_sinc_filters, (_p(low_hz), _p(band_hz), _p(window), _p(n_), _p(filt), _p(Wt), C, K, Npad,
-                            float(sample_rate), float(min_low_hz), float(min_band_hz), _stream()),
-          *_cost_of("sinc_filters", locals()))
+                            float(sample_rate), float(min_low_hz), float(min_band_hz), _stream()))
     return filt, Wt
 
 
@@ -1519,12 +1503,11 @@ def bilstm_layer(xg, whh, B, T, H, w16=False):
     """one BiLSTM layer's recurrence (inference).  w16: recurrent product on fp16 operands (the fused path passes lstm_w16())"""
     L = _lib.load()
     out = torch.empty(B, T, 2 * H, device=xg.device, dtype=torch.float32)
+    flops, nbytes = 2.0 * B * T * 2 * 4 * H * H, B * T * (8 * H + 2 * H) * 4
     if w16:
-        _call("bilstm_layer", L.sfm_bilstm_layer_ex, (_p(xg), _p(whh), _p(out), B, T, H, 1, _stream()),
-              *_cost_of("bilstm_layer", locals()))
+        _call("bilstm_layer", L.sfm_bilstm_layer_ex, (_p(xg), _p(whh), _p(out), B, T, H, 1, _stream()), flops, nbytes)
     else:
-        _call("bilstm_layer", L.sfm_bilstm_layer, (_p(xg), _p(whh), _p(out), B, T, H, _dt(), _stream()),
-              *_cost_of("bilstm_layer", locals()))
+        _call("bilstm_layer", L.sfm_bilstm_layer, (_p(xg), _p(whh), _p(out), B, T, H, _dt(), _stream()), flops, nbytes)
     return out
 
 
@@ -1585,8 +1568,7 @@ def memory_fwd(emb, params, key_dim, value_dim, slots, temperature):
     top = torch.empty(Bn, device=dev, dtype=torch.int32)
     sim = torch.empty(Bn, device=dev, dtype=torch.float32)
     _call("memory_fwd", L.sfm_memory_fwd, (_p(emb), _p(params), _p(bias), _p(gate), _p(top), _p(sim), Bn, key_dim, value_dim, slots,
-                          float(temperature), _stream()),
-          *_cost_of("memory_fwd", locals()))
+                          float(temperature), _stream()))
     return bias, gate, top, sim
 
 

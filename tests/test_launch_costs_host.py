@@ -1,0 +1,148 @@
+"""The algorithmic cost (family, flops, bytes, tag) that each ops wrapper states for its launch: what bench.py's per-family
+breakdown adds up.  The wrappers run on CPU tensors against a stub library and a recording _call, so no launch happens and no
+library is needed; the expected figures are literals (each operand read once, each result written once)."""
+import torch
+import pytest
+
+from sincformer_metacog_speech_enhancement_amd import lib, ops
+
+F16, F32 = torch.float16, torch.float32
+
+
+class _StubLib:
+    """every entry point returns 0; the size helpers (*_floats, *_tiles) return a small positive count"""
+
+    def __getattr__(self, symbol):
+        if not symbol.startswith("sfm_"):
+            raise AttributeError(symbol)
+        rc = 4 if symbol.endswith(("_floats", "_tiles")) else 0
+        fn = lambda *args: rc
+        fn.__name__ = symbol
+        return fn
+
+
+@pytest.fixture
+def launches(monkeypatch):
+    """[(symbol, family, flops, bytes, tag)] of every launch the wrappers under test enqueue"""
+    rec = []
+
+    def record(name, fn, args, flops=0.0, nbytes=0.0, tag=None):
+        assert len(args) == len(lib.SIGNATURES[fn.__name__]), fn.__name__       # the tuple has the header's length
+        rec.append((fn.__name__, name, flops, nbytes, tag))
+
+    monkeypatch.setattr(ops._lib, "load", lambda: _StubLib())
+    monkeypatch.setattr(ops, "_stream", lambda: None)
+    monkeypatch.setattr(ops, "_need_dev", lambda *ts: None)
+    monkeypatch.setattr(ops, "_call", record)
+    return rec
+
+
+def _pack(N, K, Npad, Kpad, ksize, cin, glu=False):
+    return ops.PackedWeight(torch.zeros(Npad, Kpad, dtype=F16), torch.zeros(Npad), N, K, ksize, cin, glu)
+
+
+def test_gemm16_costs(launches):
+    x = torch.zeros(4000, 256, dtype=F16)                    # below the 4096 rows at which linear16 routes to sfm_lin256
+    pw = _pack(512, 256, 512, 256, 1, 256)
+    resid = torch.zeros(4000, 512, dtype=F32)
+    ops.linear16(x, pw)
+    ops.linear16(x, pw, epi=ops.EPI_RESID, resid=resid)
+    ops.linear16(x, pw, epi=ops.EPI_RESID, resid=resid, p_drop=0.1, seed=7)              # training: dropout in the epilogue
+    ops.linear16(x, _pack(256, 256, 512, 256, 1, 256, glu=True), epi=ops.EPI_GLU)        # flops over Npad, bytes over pw.N
+    ops.gemm16(torch.zeros(3, 1000, 64, dtype=F16), _pack(128, 448, 128, 448, 7, 64), torch.zeros(3, 500, 128, dtype=F16),
+               B=3, Lout=500, Lin=1000, a_batch_stride=64000, ldo=128, o_batch_stride=64000, stride=2, pad=3)
+    assert launches == [
+        ("sfm_gemm16_ex", "gemm16", 1048576000.0, 6406144, "M4000 N512 K256 k1 s1 epi0 o2"),
+        ("sfm_gemm16_ex", "gemm16", 1048576000.0, 18694144, "M4000 N512 K256 k1 s1 epi3 o4"),
+        ("sfm_gemm16_train", "gemm16", 1048576000.0, 18694144, "M4000 N512 K256 k1 s1 epi3 o4"),
+        ("sfm_gemm16_ex", "gemm16", 1048576000.0, 4358144, "M4000 N512 K256 k1 s1 epi4 o2"),
+        ("sfm_gemm16_ex", "gemm16", 172032000.0, 882688, "M1500 N128 K448 k7 s2 epi0 o2"),
+    ]
+
+
+def test_framed_gemm_and_attention_costs(launches):
+    B, M, N, K, Ls, hop = 2, 101, 514, 400, 16000, 160
+    for odt in (F32, F16):
+        ops.framed_gemm(torch.zeros(B, Ls), torch.zeros(416, 576), torch.zeros(B, M, N, dtype=odt), B=B, M=M, Ls=Ls,
+                        sig_batch_stride=Ls, hop=hop, padl=200, K=K, N=N, o_batch_stride=M * N, ldm=N, ldn=1)
+    ops.attention(torch.zeros(600, 768, dtype=F16), 2, 300, 4, 64)
+    assert launches == [
+        ("sfm_framed_gemm_f32", "framed_gemm_f32", 83062400.0, 543312, "M202 N514 K400 hop160"),
+        ("sfm_framed_gemm_f32", "framed_gemm_f32", 83062400.0, 335656, "M202 N514 K400 hop160"),
+        ("sfm_attention_fwd_ex", "attention_fwd", 184320000.0, 1228800.0, None),
+    ]
+
+
+def test_normalisation_costs(launches):
+    M, D = 600, 256
+    x, w = torch.zeros(M, D), torch.ones(D)
+    o16, o32 = torch.zeros(M, D, dtype=F16), torch.zeros(M, D)
+    ops.layernorm(x, w, w, out16=o16)
+    ops.layernorm(x, w, w, out16=o16, out32=o32)
+    ops.layernorm(x, w, w, out32=o32)
+    Bn, rows, C = 2, 1000, 128
+    sc = torch.zeros(Bn, C)
+    ops.gn_finalize(torch.zeros(Bn, 8, 8, 2), torch.ones(C), torch.zeros(C), Bn, 8, 8, C, rows)
+    ops.gn_apply(torch.zeros(Bn, rows, C, dtype=F16), sc, sc, torch.zeros(Bn, rows, C), Bn, rows, C)
+    ops.gn_apply(torch.zeros(Bn, rows, C), sc, sc, torch.zeros(Bn, rows, C, dtype=F16), Bn, rows, C, act=1,
+                 x2=torch.zeros(Bn, rows, C), sc2=sc, sh2=sc)
+    assert launches == [
+        ("sfm_layernorm", "layernorm", 1228800.0, 921600, None),
+        ("sfm_layernorm", "layernorm", 1228800.0, 1536000, None),
+        ("sfm_layernorm", "layernorm", 1228800.0, 1228800, None),
+        ("sfm_gn_finalize", "gn_finalize", 0.0, 0.0, None),
+        ("sfm_gn_apply", "gn_apply", 2560000.0, 1536000, None),
+        ("sfm_gn_apply", "gn_apply", 2560000.0, 2560000, None),
+    ]
+
+
+def test_conformer_pointwise_and_recurrent_costs(launches):
+    B, T, C = 2, 300, 256
+    v = torch.zeros(C)
+    ops.dwconv_bn_swish(torch.zeros(B, T, C, dtype=F16), torch.zeros(C, 1, 31), v, v, v, v, v, B, T, C)
+    ops.convert_rows(torch.zeros(600, 260), torch.zeros(600, 264, dtype=F16), 600, 257, 264, 260, 264)
+    ops.transpose(torch.zeros(B, T, C), torch.zeros(B, C, T, dtype=F16), B, T, C, T * C, C, T * C, T)
+    H = 128
+    xg, whh = torch.zeros(B, T, 2, 4 * H), torch.zeros(2, 4 * H, H)
+    ops.bilstm_layer(xg, whh, B, T, H)
+    ops.bilstm_layer(xg, whh, B, T, H, w16=True)
+    ops.memory_fwd(torch.zeros(B, 64), torch.zeros(4096), 64, 32, 16, 0.5)
+    assert launches == [
+        ("sfm_dwconv_bn_swish", "dwconv_bn_swish", 9523200.0, 614400, None),
+        ("sfm_convert_rows", "convert_rows", 0.0, 0.0, "M600 C257"),
+        ("sfm_transpose", "transpose", 0.0, 0.0, None),
+        ("sfm_bilstm_layer", "bilstm_layer", 157286400.0, 3072000, None),
+        ("sfm_bilstm_layer_ex", "bilstm_layer", 157286400.0, 3072000, None),
+        ("sfm_memory_fwd", "memory_fwd", 0.0, 0.0, None),
+    ]
+
+
+def test_pool_time_costs_by_source_width(launches):
+    B, Tin, Tout, C = 2, 1000, 101, 256
+    dst = torch.zeros(B, Tout, C)
+    ops.pool_time(torch.zeros(B, Tin, C, dtype=F16), None, dst, B, Tin, Tout, C, C, C)
+    ops.pool_time(torch.zeros(B, Tin, C), None, dst, B, Tin, Tout, C, C, C)
+    assert launches == [
+        ("sfm_pool_time_affine16", "pool_time", 0.0, 1230848, None),
+        ("sfm_pool_time_affine", "pool_time", 0.0, 2254848, None),
+    ]
+
+
+def test_spectral_costs(launches):
+    B, rows, F, Ln = 2, 101, 257, 16000
+    M = B * rows
+    s = torch.zeros(M, F)
+    ops.stft_lognorm_pack(s, s, torch.zeros(M, 264, dtype=F16), M, F, 264, 264)
+    ops.polar_mask(torch.zeros(M, 2 * F), torch.zeros(M, 2 * F), B, rows, F, 3.14, 2 * F, nr=s, ni=s, er=s, ei=s)
+    ops.complex_mul(s, s, s, s)
+    ops.istft_ola(torch.zeros(M, 400), torch.zeros(Ln), torch.zeros(B, Ln), B, rows, Ln, 400, 160, 400, 400)
+    ops.pack_spec(s, s, torch.zeros(M, 520), M, F, 520, F)
+    ops.sinc_filters(torch.zeros(64, 1), torch.zeros(64, 1), torch.zeros(125), torch.zeros(1, 125), 64, 251, 16000, 50, 50)
+    assert launches == [
+        ("sfm_stft_lognorm_pack", "stft_lognorm_pack", 0.0, 622968, None),
+        ("sfm_polar_mask", "polar_mask", 1038280.0, 1661248, None),
+        ("sfm_complex_mul", "complex_mul", 0.0, 0.0, None),
+        ("sfm_istft_ola", "istft_ola", 0.0, 384000, None),
+        ("sfm_pack_spec", "pack_spec", 0.0, 0.0, None),
+        ("sfm_sinc_filters", "sinc_filters", 0.0, 0.0, None),
+    ]
