@@ -529,6 +529,61 @@ int sfm_pstoi_loss(const float* e0, const float* e1, const float* c0, const floa
                    void* stream);
 int sfm_mse_loss(const float* pred, const float* target, float* loss, float* grad, double* ws, long long n, void* stream);
 
+/* AdversarialLoss (training/losses.py:150-289; adversarial.hip): what a discriminator call needs around the convs, which run on
+ * sfm_gemm16 / sfm_conv_wgrad16.  Activations are channels-last 16-bit rows; sums are ordered (no atomics).  `loss` is ONE double
+ * that the forward entry points ADD their scaled term to, in stream order: the caller zeroes it once per objective.
+ * Forward operands are PAIRS of 16-bit words, v = hi + lo / 2048 (hi = v rounded to `dtype`, lo = the rounding error x 2048, also
+ *   rounded): the `*lo` / `packed_lo` arguments, laid out like their hi twins.  The caller runs hi x hi + (lo x hi + hi x lo) / 2048
+ *   (three sfm_gemm16 launches, the last two accumulating with alpha = 1 / 2048), so a pre-activation carries ~2^-20 and the
+ *   kinks of LeakyReLU and of the L1 term are decided as in fp32; the backward uses the hi words alone.
+ * sfm_adv_sn_fwd: legacy torch.nn.utils.spectral_norm (one power iteration, dim 0) of the n_layers convs of a discriminator, one
+ *   workgroup per row of `table` (device, 16 int64 words per layer): {weight_orig [N][Cin][k] fp32, bias [N], weight_u [N],
+ *   weight_v [Cin k], N, Cin, k, Cp, Npad, Kpad, off16, off32}.  training != 0: v <- normalize(W^T u), u <- normalize(W v),
+ *   both written back; else the buffers are only read.  sigma = u^T W v.  packed + off16 receives W / sigma as [Npad][Kpad]
+ *   16-bit in sfm_gemm16's layout (column tap * Cp + ci, zero elsewhere); saved + off32 receives bias [Npad] | u [N] | v [Cin k]
+ *   | W v [N] | sigma [1] of THIS call (its backward needs them; off16 % 8 == 0).
+ * The backward entry points share (g, cnorm): g = the objective's incoming gradient (one float, on the device), cnorm = its
+ *   largest static coefficient.  Each derives the same power of two S = 2^k, |g cnorm| S in [32, 64), and everything the pass
+ *   rounds to 16 bits carries S (so fp16 dY tensors stay in the normal range whatever g is); S is divided out, exactly, where a
+ *   gradient leaves in fp32.  g == NULL: S = 1.
+ * sfm_adv_sn_bwd: d weight_orig [N][Cin][k] (= or +=) (G - <G, W / sigma> u v^T) / sigma / S for G = S dL/d(W / sigma)
+ *   [N][k][Cp] tap-major as sfm_conv_wgrad16 leaves it; db (= or +=) db_in / S (both or neither); u, v, sigma from the forward
+ *   call's `saved`.
+ * sfm_adv_stage: pair == 0: x [B, F, T] fp32 magnitudes; pair != 0: (x, im) = (real, imag) [B, T, F], magnitude
+ *   sqrt(re^2 + im^2 + 1e-8).  -> x16 [B, T, Cp] 16-bit, columns >= F zero, and x32 [B, T, F] fp32 (or NULL).
+ * sfm_adv_stage_bwd: the adjoint: d [B, T, Cp] fp32 (carrying S) -> dx [B, F, T], or (dx, dx_im) [B, T, F]; every element written.
+ * sfm_adv_leaky: a16 = LeakyReLU_0.2(z) for n fp32 pre-activations (n % 4 == 0); with z_real (the real pass's pre-activation
+ *   of the same layer) also loss += scale * sum |leaky(z) - leaky(z_real)|; ws >= 2048 doubles.
+ * sfm_adv_leaky_bwd: dz16 = (incoming + S * w_fm * g[0] * sign(leaky(z) - leaky(z_real))) * (z > 0 ? 1 : 0.2): the 16-bit dY of the
+ *   two gradient GEMMs; incoming or z_real may be NULL (not both).  g = the objective's incoming gradient, on the device.
+ * sfm_adv_pool: AvgPool1d(4, 2, 1), padding counted: in32 [B, Tin, F] -> out32 [B, Tin / 2, F] (or NULL), out16 [B, Tin / 2, Cp].
+ * sfm_adv_pool_bwd: dx [B, Tin, Cp] += its adjoint of dnext [B, Tin / 2, Cp].
+ * sfm_adv_head: out [B, T] = Conv1d(C, 1, 3, pad 1) of a16 [B, T, C] with w16 [3][C] tap-major 16-bit and bias[0];
+ *   loss += scale * sum (out - target)^2; ws >= ceil(B T / 4) doubles.
+ * sfm_adv_head_bwd: dout = g[0] * coef * (out - target); da [B, T, C] fp32 = S x its adjoint; dwb (or NULL) = dw [3][C] tap-major | db
+ *   (not scaled), through
+ *   ws >= ceil(B T / 64) * (3 C + 1) floats. */
+int sfm_adv_sn_fwd(const long long* table, int n_layers, void* packed, void* packed_lo, float* saved, int training, float eps,
+                   int dtype, void* stream);
+int sfm_adv_sn_bwd(const float* G, const float* W, const float* u, const float* v, const float* sigma, float* dW,
+                   const float* db_in, float* db, const float* g, float cnorm, int N, int Cin, int ksize, int Cp, int accumulate,
+                   void* stream);
+int sfm_adv_stage(const float* x, const float* im, void* x16, void* x16lo, float* x32, int B, int F, int T, int Cp, int pair,
+                  int dtype, void* stream);
+int sfm_adv_stage_bwd(const float* d, const float* re, const float* im, float* dx, float* dx_im, const float* g, float cnorm, int B,
+                      int F, int T, int Cp, int pair, void* stream);
+int sfm_adv_leaky(const float* z, const float* z_real, void* a16, void* a16lo, double* ws, double* loss, float scale, long long n,
+                  int dtype, void* stream);
+int sfm_adv_leaky_bwd(const float* incoming, const float* z, const float* z_real, const float* g, float w_fm, float cnorm,
+                      void* dz16, long long n, int dtype, void* stream);
+int sfm_adv_pool(const float* in32, float* out32, void* out16, void* out16lo, int B, int Tin, int F, int Cp, int dtype,
+                 void* stream);
+int sfm_adv_pool_bwd(const float* dnext, float* dx, int B, int Tin, int Cp, void* stream);
+int sfm_adv_head(const void* a16, const void* a16lo, const void* w16, const void* w16lo, const float* bias, float* out, double* ws,
+                 double* loss, float target, float scale, int B, int T, int C, int dtype, void* stream);
+int sfm_adv_head_bwd(const void* a16, const void* w16, const float* out, const float* g, float coef, float cnorm, float target,
+                     float* da, float* dwb, float* ws, int B, int T, int C, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1290,14 +1290,15 @@ def gemm16_tn(G16, X16, dW, db=None):
           tag="M%d N%d K%d" % (M, N, K))
 
 
-def conv_wgrad16(dy16, x16, B, Lout, Lin, Cin, N, ksize, stride, pad):
+def conv_wgrad16(dy16, x16, B, Lout, Lin, Cin, N, ksize, stride, pad, tap_major=False):
     """Conv1d weight / bias gradient from dY [B*Lout, N] and the channels-last input x [B, Lin, Cin] (both 16-bit):
-    returns dW in torch's Conv1d layout [N, Cin, ksize] and db [N] (fp32)."""
+    returns dW in torch's Conv1d layout [N, Cin, ksize] and db [N] (fp32).  tap_major: dW as the GEMM leaves it,
+    [N, ksize, Cin] (no permuting copy; adv_sn_bwd reads that layout)."""
     ws = _WGRAD["stream"]
     if ws is not None and torch.cuda.current_stream() != ws:   # off the critical path: see wgrad_side_stream
         ws.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(ws):
-            out = conv_wgrad16(dy16, x16, B, Lout, Lin, Cin, N, ksize, stride, pad)
+            out = conv_wgrad16(dy16, x16, B, Lout, Lin, Cin, N, ksize, stride, pad, tap_major)
         _WGRAD["keep"].extend((dy16, x16))
         return out
     L = _lib.load()
@@ -1308,6 +1309,8 @@ def conv_wgrad16(dy16, x16, B, Lout, Lin, Cin, N, ksize, stride, pad):
                                             Lin * Cin, dy16.stride(0), dW.stride(0), _dt(), _p(ws), wsn, _stream()),
           2.0 * B * Lout * N * ksize * Cin, (B * Lout * N + B * Lin * Cin) * 2.0,
           tag="conv M%d N%d K%d s%d" % (B * Lout, N, ksize * Cin, stride))
+    if tap_major:
+        return dW.reshape(N, ksize, Cin), db
     return dW.reshape(N, ksize, Cin).permute(0, 2, 1).contiguous(), db
 
 
@@ -1684,3 +1687,211 @@ def vq_backward(x, idx, centroids, g_q, g_loss, beta):
     _call("vq", L.sfm_vq_backward, (_p(x), _p(idx), _p(centroids), centroids.numel(), _p(g_q), _p(g_loss), float(beta), _p(dx),
                                      _p(dcent), x.numel(), _stream()), 0.0, 20.0 * x.numel())
     return dx, dcent
+
+
+# ---------------------------------------------------------------------------
+# AdversarialLoss (training/losses.py:150-289): csrc/adversarial.hip around gemm16 / conv_wgrad16 / conv_dgrad16
+# ---------------------------------------------------------------------------
+ADV_MAX_WIDTH = 512                     # first-layer Cin after zero padding (257 bins -> 512)
+
+
+def adv_plan(n_freq, channels):
+    """the convs of SubDiscriminator(n_freq, channels) as the kernels see them: one dict per conv (the C -> 1 head last) with
+    N, Cin, ksize, stride, pad, Cp (Cin zero-padded: a power of two >= 8 for sfm_gemm16's taps), Npad / Kpad of the packed
+    weight, and its offsets in the call's two buffers (off16: W / sigma, 16-bit elements; off32: bias | u | v | W v | sigma)"""
+    plan, cin, off16, off32 = [], int(n_freq), 0, 0
+    specs = [(c, 5, 2 if i < len(channels) - 1 else 1, 2) for i, c in enumerate(channels)] + [(1, 3, 1, 1)]
+    for n, k, stride, pad in specs:
+        cp = 8
+        while cp < cin:
+            cp *= 2
+        head = n == 1
+        npad = 1 if head else (round_up(n, 128) if n > 64 and round_up(n, 128) - n < 64 else round_up(n, 64))
+        kpad = k * cp if head else round_up(k * cp, 64)
+        plan.append(dict(N=n, Cin=cin, ksize=k, stride=stride, pad=pad, Cp=cp, Npad=npad, Kpad=kpad, off16=off16, off32=off32))
+        off16 += round_up(npad * kpad, 8)
+        off32 += round_up(npad + 2 * n + cin * k + 1, 4)
+        cin = n
+    return plan, off16, off32
+
+
+def adv_sn_table(plan, convs, device):
+    """the device table sfm_adv_sn_fwd walks: 16 int64 words per conv (pointers of weight_orig, bias, weight_u, weight_v, then
+    the plan's sizes and offsets)"""
+    rows = []
+    for L_, m in zip(plan, convs):
+        rows.append([m.weight_orig.data_ptr(), m.bias.data_ptr(), m.weight_u.data_ptr(), m.weight_v.data_ptr(), L_["N"], L_["Cin"],
+                     L_["ksize"], L_["Cp"], L_["Npad"], L_["Kpad"], L_["off16"], L_["off32"], 0, 0, 0, 0])
+    return torch.tensor(rows, dtype=torch.int64).to(device)
+
+
+ADV_LO_SCALE = 2048.0               # adversarial.hip: a forward operand is hi + lo / 2048
+
+
+def adv_sn_views(L_, packed, saved, packed_lo=None):
+    """(PackedWeight or the head's [3 C] row, bias, u, v, sigma) of one conv inside the buffers sfm_adv_sn_fwd filled; with
+    packed_lo the same view of the lo words (zero bias: the correction GEMMs add to a result that has its bias)"""
+    if packed_lo is not None:
+        w = packed_lo[L_["off16"]:L_["off16"] + L_["Npad"] * L_["Kpad"]].view(L_["Npad"], L_["Kpad"])
+        if L_["N"] == 1:
+            return w
+        return PackedWeight(w, _zero_bias(L_["Npad"], w.device), L_["N"], L_["ksize"] * L_["Cp"], L_["ksize"], L_["Cp"])
+    n, k, cin = L_["N"], L_["ksize"], L_["Cin"]
+    w = packed[L_["off16"]:L_["off16"] + L_["Npad"] * L_["Kpad"]].view(L_["Npad"], L_["Kpad"])
+    o = L_["off32"]
+    bias = saved[o:o + L_["Npad"]]
+    u = saved[o + L_["Npad"]:o + L_["Npad"] + n]
+    v = saved[o + L_["Npad"] + n:o + L_["Npad"] + n + cin * k]
+    sigma = saved[o + L_["Npad"] + 2 * n + cin * k:o + L_["Npad"] + 2 * n + cin * k + 1]
+    pw = w if n == 1 else PackedWeight(w, bias, n, k * L_["Cp"], k, L_["Cp"])
+    return pw, bias, u, v, sigma
+
+
+def adv_sn_fwd(table, plan, n16, n32, training, eps=1e-12):
+    """spectral norm of every conv of one discriminator in ONE launch (a workgroup per conv): power iteration when `training`
+    (weight_u / weight_v updated in place), sigma, W / sigma packed for gemm16 as hi / lo words
+    -> (packed 16-bit [n16], packed_lo [n16], saved fp32 [n32])"""
+    _need_dev(table)
+    L = _lib.load()
+    packed = torch.empty(n16, device=table.device, dtype=_state["dtype"])
+    packed_lo = torch.empty(n16, device=table.device, dtype=_state["dtype"])
+    saved = torch.empty(n32, device=table.device, dtype=torch.float32)
+    nk = sum(p["N"] * p["Cin"] * p["ksize"] for p in plan)
+    _call("adv_sn", L.sfm_adv_sn_fwd, (_p(table), len(plan), _p(packed), _p(packed_lo), _p(saved), 1 if training else 0,
+                                       float(eps), _dt(), _stream()),
+          (6.0 if training else 4.0) * nk, ((3 if training else 2) * 4.0 + 4.0) * nk + 4.0 * n16)
+    return packed, packed_lo, saved
+
+
+def adv_sn_bwd(G, weight_orig, u, v, sigma, dW, Cp, accumulate, db_in=None, db=None, g=None, cnorm=0.0):
+    """dW [N, Cin, k] (= or +=) (G - <G, W / sigma> u v^T) / sigma / S, G [N, k, Cp] tap-major; db (= or +=) db_in / S.
+    S = the power of two the pass's 16-bit tensors carry, derived from (g, cnorm) as in every backward kernel (g None: 1)"""
+    _need_dev(G, weight_orig, dW, db_in, db, g)
+    L = _lib.load()
+    N, Cin, k = weight_orig.shape
+    nk = N * Cin * k
+    _call("adv_sn", L.sfm_adv_sn_bwd, (_p(G), _p(weight_orig), _p(u), _p(v), _p(sigma), _p(dW), _p(db_in), _p(db), _p(g),
+                                       float(cnorm), N, Cin, k, Cp, 1 if accumulate else 0, _stream()), 6.0 * nk, (24.0 if accumulate else 20.0) * nk)
+    return dW
+
+
+def adv_stage(x, im, Cp, want32):
+    """magnitudes [B, F, T] fp32 (im None), or (real, imag) [B, T, F] -> ((x16, x16lo) [B, T, Cp] zero-padded hi / lo words,
+    x32 [B, T, F] or None)"""
+    _need_dev(x, im)
+    L = _lib.load()
+    pair = im is not None
+    if pair:
+        B, T, F = x.shape
+    else:
+        B, F, T = x.shape
+    x16 = torch.empty(B, T, Cp, device=x.device, dtype=_state["dtype"])
+    lo = torch.empty_like(x16)
+    x32 = torch.empty(B, T, F, device=x.device, dtype=torch.float32) if want32 else None
+    n = B * T * F
+    _call("adv_stage", L.sfm_adv_stage, (_p(x), _p(im), _p(x16), _p(lo), _p(x32), B, F, T, Cp, 1 if pair else 0, _dt(), _stream()),
+          4.0 * n if pair else 0.0, (8.0 if pair else 4.0) * n + 4.0 * B * T * Cp + (4.0 * n if want32 else 0.0))
+    return (x16, lo), x32
+
+
+def adv_stage_bwd(d, re, im, B, F, T, g=None, cnorm=0.0):
+    """adjoint of adv_stage: d [B, T, Cp] fp32 (carrying the pass's scale) -> d x [B, F, T], or (d re, d im) [B, T, F]; every
+    element written"""
+    _need_dev(d, re, im, g)
+    L = _lib.load()
+    pair = re is not None
+    Cp = d.shape[-1]
+    if pair:
+        dx, dxi = torch.empty_like(re), torch.empty_like(im)
+    else:
+        dx, dxi = torch.empty(B, F, T, device=d.device, dtype=torch.float32), None
+    n = B * T * F
+    _call("adv_stage", L.sfm_adv_stage_bwd, (_p(d), _p(re), _p(im), _p(dx), _p(dxi), _p(g), float(cnorm), B, F, T, Cp,
+                                             1 if pair else 0, _stream()),
+          6.0 * n if pair else 0.0, (20.0 if pair else 8.0) * n)
+    return dx, dxi
+
+
+def adv_leaky(z, z_real=None, loss=None, scale=0.0):
+    """(a16, a16lo) = LeakyReLU(0.2)(z) as hi / lo words; with z_real also loss[0] += scale * sum |leaky(z) - leaky(z_real)|,
+    summed in order"""
+    _need_dev(z, z_real, loss)
+    L = _lib.load()
+    n = z.numel()
+    a16 = torch.empty(z.shape, device=z.device, dtype=_state["dtype"])
+    lo = torch.empty_like(a16)
+    ws = _ws64(2048, z.device) if z_real is not None else None
+    _call("adv_leaky", L.sfm_adv_leaky, (_p(z), _p(z_real), _p(a16), _p(lo), _p(ws), _p(loss), float(scale), n, _dt(), _stream()),
+          (4.0 if z_real is not None else 1.0) * n, (12.0 if z_real is not None else 8.0) * n)
+    return a16, lo
+
+
+def adv_leaky_bwd(incoming, z, z_real, g, w_fm, cnorm):
+    """dz16 = (incoming + S * w_fm * g * sign(leaky(z) - leaky(z_real))) * leaky'(z): the 16-bit dY of the gradient GEMMs"""
+    _need_dev(incoming, z, z_real, g)
+    L = _lib.load()
+    n = z.numel()
+    dz16 = torch.empty(z.shape, device=z.device, dtype=_state["dtype"])
+    terms = (incoming is not None) + (z_real is not None)
+    _call("adv_leaky", L.sfm_adv_leaky_bwd, (_p(incoming), _p(z), _p(z_real), _p(g), float(w_fm), float(cnorm), _p(dz16), n, _dt(),
+                                             _stream()),
+          (1.0 + 2.0 * terms) * n, (6.0 + 4.0 * terms) * n)
+    return dz16
+
+
+def adv_pool(in32, Cp, want32):
+    """AvgPool1d(4, 2, 1) on channels-last rows: in32 [B, Tin, F] -> ((out16, out16lo) [B, Tin // 2, Cp] zero-padded hi / lo
+    words, out32 or None)"""
+    _need_dev(in32)
+    L = _lib.load()
+    B, Tin, F = in32.shape
+    Tout = Tin // 2
+    out16 = torch.empty(B, Tout, Cp, device=in32.device, dtype=_state["dtype"])
+    lo = torch.empty_like(out16)
+    out32 = torch.empty(B, Tout, F, device=in32.device, dtype=torch.float32) if want32 else None
+    _call("adv_pool", L.sfm_adv_pool, (_p(in32), _p(out32), _p(out16), _p(lo), B, Tin, F, Cp, _dt(), _stream()),
+          4.0 * B * Tout * F, 4.0 * B * Tin * F + 4.0 * B * Tout * Cp + (4.0 * B * Tout * F if want32 else 0.0))
+    return (out16, lo), out32
+
+
+def adv_pool_bwd(dnext, dx):
+    """dx [B, Tin, Cp] += adjoint of AvgPool1d(4, 2, 1) applied to dnext [B, Tin // 2, Cp]"""
+    _need_dev(dnext, dx)
+    L = _lib.load()
+    B, Tin, Cp = dx.shape
+    _call("adv_pool", L.sfm_adv_pool_bwd, (_p(dnext), _p(dx), B, Tin, Cp, _stream()),
+          3.0 * B * Tin * Cp, 8.0 * B * Tin * Cp + 4.0 * B * (Tin // 2) * Cp)
+    return dx
+
+
+def adv_head(a16, a16lo, w16, w16lo, bias, loss, target, scale):
+    """Conv1d(C, 1, 3, pad 1) of a [B, T, C] (hi / lo words, as the weight) as a dot product per row -> out [B, T] fp32;
+    loss[0] += scale * sum (out - target)^2"""
+    _need_dev(a16, a16lo, w16, w16lo, bias, loss)
+    L = _lib.load()
+    B, T, C = a16.shape
+    out = torch.empty(B, T, device=a16.device, dtype=torch.float32)
+    ws = _ws64((B * T + 3) // 4, a16.device)
+    _call("adv_head", L.sfm_adv_head, (_p(a16), _p(a16lo), _p(w16), _p(w16lo), _p(bias), _p(out), _p(ws), _p(loss), float(target),
+                                       float(scale), B, T, C, _dt(), _stream()),
+          6.0 * B * T * C, 4.0 * B * T * C + 12.0 * C + 4.0 * B * T)
+    return out
+
+
+def adv_head_bwd(a16, w16, out, g, coef, cnorm, target, want_dw):
+    """dout = g * coef * (out - target) -> (da [B, T, C] fp32 carrying the pass's scale, dwb = dw [3, C] tap-major | db or None)"""
+    _need_dev(a16, w16, out, g)
+    L = _lib.load()
+    B, T, C = a16.shape
+    da = torch.empty(B, T, C, device=a16.device, dtype=torch.float32)
+    dwb = torch.empty(3 * C + 1, device=a16.device, dtype=torch.float32) if want_dw else None
+    ws = None
+    if want_dw:
+        n = (B * T + 63) // 64 * (3 * C + 1)
+        ws = _ws(n, a16.device)
+        ws = ws if ws is not None else torch.empty(n, device=a16.device, dtype=torch.float32)
+    _call("adv_head", L.sfm_adv_head_bwd, (_p(a16), _p(w16), _p(out), _p(g), float(coef), float(cnorm), float(target), _p(da), _p(dwb),
+                                           _p(ws),
+                                           B, T, C, _dt(), _stream()),
+          (12.0 if want_dw else 6.0) * B * T * C, (4.0 + (2.0 if want_dw else 0.0)) * B * T * C + 4.0 * B * T + 6.0 * C)
+    return da, dwb

@@ -1551,3 +1551,218 @@ class VQFunction(torch.autograd.Function):
         gl = None if g_loss is None else g_loss.detach().float().reshape(1).contiguous()
         dx, dcent = ops.vq_backward(xf, idx, cf, gq, gl, beta)
         return dx.to(xdt), dcent.to(cdt), None
+
+
+# ---------------------------------------------------------------------------
+# AdversarialLoss (training/losses.py:150-289): three spectrally normalised conv stacks on channels-last 16-bit rows
+# ---------------------------------------------------------------------------
+def _adv_convs(disc):
+    return [m for m in disc.layers if isinstance(m, torch.nn.Conv1d)]
+
+
+def _adv_setup(disc, device):
+    """(plan, n16, n32, sn table) of one SubDiscriminator; the table holds parameter addresses, so it is rebuilt when one moves
+    (an optimiser that re-homes the parameters in a flat buffer) or the operand format changes"""
+    convs = _adv_convs(disc)
+    key = (ops.policy_key(), str(device)) + tuple(t.data_ptr() for m in convs for t in (m.weight_orig, m.bias, m.weight_u, m.weight_v))
+    cache = disc.__dict__.get("_sfm_adv")
+    if cache is None or cache[0] != key:
+        plan, n16, n32 = ops.adv_plan(convs[0].weight_orig.shape[1], [m.weight_orig.shape[0] for m in convs[:-1]])
+        cache = (key, (plan, n16, n32, ops.adv_sn_table(plan, convs, device)))
+        disc.__dict__["_sfm_adv"] = cache
+    return cache[1]
+
+
+def adv_disc_pass(disc, x16, B, T, loss=None, head=None, fm_real=None, fm_scale=None, keep=True):
+    """one call `disc(x)`, x16 = the (hi, lo) words of the input rows: spectral norm (one launch; iterates weight_u / weight_v
+    when disc.training), then per layer the implicit-GEMM conv to fp32 - hi x hi, then lo x hi and hi x lo added at 1 / 2048, so
+    the kinks that follow are decided as in fp32 - and the LeakyReLU pass.  head = (target, scale): loss += scale * sum (out - target)^2.
+    fm_real = the real pass's record: each layer adds its L1 term, fm_scale[l] * sum |a - a_real|.  -> the record the backward
+    and the callers read: plan, packed, saved, xs (layer inputs, 16-bit), zs (fp32 pre-activations), Ts, out"""
+    plan, n16, n32, table = _adv_setup(disc, x16[0].device)
+    packed, packed_lo, saved = ops.adv_sn_fwd(table, plan, n16, n32, disc.training)
+    rec = dict(plan=plan, packed=packed, saved=saved, xs=[], zs=[], Ts=[T], out=None)
+    (x, xlo), Lin = x16, T
+    for l, L_ in enumerate(plan[:-1]):
+        pw, pw_lo = ops.adv_sn_views(L_, packed, saved)[0], ops.adv_sn_views(L_, packed, saved, packed_lo)
+        Lout = (Lin + 2 * L_["pad"] - L_["ksize"]) // L_["stride"] + 1
+        z = torch.empty(B, Lout, L_["N"], device=x.device, dtype=torch.float32)
+        kw = dict(B=B, Lout=Lout, Lin=Lin, a_batch_stride=Lin * L_["Cp"], ldo=L_["N"], o_batch_stride=Lout * L_["N"],
+                  stride=L_["stride"], pad=L_["pad"])
+        ops.gemm16(x, pw, z, **kw)
+        corr = dict(epi=ops.EPI_RESID, resid=z, ldr=L_["N"], r_batch_stride=Lout * L_["N"], alpha=1.0 / ops.ADV_LO_SCALE)
+        pw0 = ops.PackedWeight(pw.w, pw_lo.bias, pw.N, pw.K, pw.ksize, pw.cin)          # the hi words without the bias
+        ops.gemm16(xlo, pw0, z, **kw, **corr)
+        ops.gemm16(x, pw_lo, z, **kw, **corr)
+        if fm_real is not None:
+            a, alo = ops.adv_leaky(z, z_real=fm_real["zs"][l], loss=loss, scale=fm_scale[l])
+        else:
+            a, alo = ops.adv_leaky(z)
+        rec["xs"].append(x)
+        rec["zs"].append(z)
+        rec["Ts"].append(Lout)
+        x, xlo, Lin = a, alo, Lout
+    rec["xs"].append(x)
+    if head is not None:
+        w16, bias = ops.adv_sn_views(plan[-1], packed, saved)[:2]
+        rec["out"] = ops.adv_head(x, xlo, w16, ops.adv_sn_views(plan[-1], packed, saved, packed_lo), bias, loss, head[0], head[1])
+        rec["head"] = head
+    if not keep:
+        rec["xs"] = rec["xs"][-1:]
+    return rec
+
+
+def adv_disc_backward(disc, rec, B, g, cnorm, grads, need_p, need_x, head_coef=None, fm_real=None, fm_w=None):
+    """backward of one adv_disc_pass: -> d x16 [B, T, Cp] fp32 (or None); parameter gradients are added into grads[id(p)]
+    (the real and the fake pass of one objective share the parameters; the sums run in launch order).  (g, cnorm): every 16-bit
+    tensor of the pass, and d x16, carry the power of two the kernels derive from them (adversarial.hip, adv_scale)"""
+    plan, packed, saved = rec["plan"], rec["packed"], rec["saved"]
+    convs = _adv_convs(disc)
+
+    def give(p, val):
+        if id(p) in grads:
+            grads[id(p)] += val.reshape(p.shape)
+        else:
+            grads[id(p)] = val.reshape(p.shape).clone()
+
+    inc = None
+    if head_coef is not None:
+        L_, m = plan[-1], convs[-1]
+        w16, _, u, v, sigma = ops.adv_sn_views(L_, packed, saved)
+        inc, dwb = ops.adv_head_bwd(rec["xs"][-1], w16, rec["out"], g, head_coef, cnorm, rec["head"][0], need_p)
+        if need_p:
+            C = L_["Cin"]
+            acc = id(m.weight_orig) in grads
+            if not acc:
+                grads[id(m.weight_orig)] = torch.empty_like(m.weight_orig, dtype=torch.float32)
+            ops.adv_sn_bwd(dwb[:3 * C], m.weight_orig.detach(), u, v, sigma, grads[id(m.weight_orig)], C, acc)
+            give(m.bias, dwb[3 * C:])
+    for l in range(len(plan) - 2, -1, -1):
+        L_, m = plan[l], convs[l]
+        pw, _, u, v, sigma = ops.adv_sn_views(L_, packed, saved)
+        Lin, Lout, N, Cp = rec["Ts"][l], rec["Ts"][l + 1], L_["N"], L_["Cp"]
+        dz16 = ops.adv_leaky_bwd(inc, rec["zs"][l], None if fm_real is None else fm_real["zs"][l], g,
+                                 0.0 if fm_w is None else fm_w[l], cnorm)
+        if need_p:
+            G, db = ops.conv_wgrad16(dz16.view(B * Lout, N), rec["xs"][l], B, Lout, Lin, Cp, N, L_["ksize"], L_["stride"],
+                                     L_["pad"], tap_major=True)
+            with ops.after_wgrad(G, db, u, v, sigma):
+                acc = id(m.weight_orig) in grads
+                if not acc:
+                    grads[id(m.weight_orig)] = torch.empty_like(m.weight_orig, dtype=torch.float32)
+                    grads[id(m.bias)] = torch.empty_like(m.bias, dtype=torch.float32)
+                ops.adv_sn_bwd(G, m.weight_orig.detach(), u, v, sigma, grads[id(m.weight_orig)], Cp, acc, db_in=db,
+                               db=grads[id(m.bias)], g=g, cnorm=cnorm)
+        if l > 0 or need_x:
+            w = pw.w[:N, :L_["ksize"] * Cp].view(N, L_["ksize"], Cp).permute(0, 2, 1)       # W / sigma as [N, Cp, k]
+            inc = ops.conv_dgrad16(dz16, w, B, Lout, Lin, L_["stride"], L_["pad"])
+        else:
+            inc = None
+    return inc
+
+
+class AdversarialFunction(torch.autograd.Function):
+    """AdversarialLoss.discriminator_loss ("d"), .generator_loss ("g") and .feature_matching_loss ("fm"): every discriminator is
+    called as the reference calls it (real first, then fake, never batched: each call advances the spectral-norm vectors and
+    its backward uses its own u, v, sigma).  clean / enh are magnitudes [B, F, T] (the *_im arguments None) or the (real, imag)
+    pairs of channels-last [B, T, F] spectra.  Gradients: "d" to the parameters only; "g" and "fm" to enh and, where they
+    require it, to the parameters through the fake pass.  clean gets none."""
+
+    @staticmethod
+    def forward(ctx, adv, mode, clean, clean_im, enh, enh_im, *params):
+        pair = enh_im is not None
+        f32 = lambda t: None if t is None else t.detach().float().contiguous()
+        e, ei, c, ci = f32(enh), f32(enh_im), f32(clean), f32(clean_im)
+        if pair:
+            B, T, F = e.shape
+        else:
+            B, F, T = e.shape
+        discs = list(adv.discriminators)
+        nd = len(discs)
+        need_x = mode != "d" and (enh.requires_grad or (pair and enh_im.requires_grad))
+        need_p = any(p.requires_grad for p in params)
+        Cp0 = ops.adv_plan(F, [1])[0][0]["Cp"]
+        loss = torch.zeros(1, device=e.device, dtype=torch.float64)
+
+        def scales(x, xi):
+            """the input of every scale as 16-bit rows: the staging pass, then the pools on the fp32 rows"""
+            x16, x32 = ops.adv_stage(x, xi, Cp0, nd > 1)
+            out, Ts = [x16], [T]
+            for s in range(1, nd):
+                x16, x32 = ops.adv_pool(x32, Cp0, s < nd - 1)
+                out.append(x16)
+                Ts.append(Ts[-1] // 2)
+            return out, Ts
+
+        fake, Ts = scales(e, ei)
+        real = scales(c, ci)[0] if mode != "g" else None
+        recs = []
+        for i, disc in enumerate(discs):
+            mean = 1.0 / (nd * B * _adv_tout(disc, Ts[i]))           # mse_loss's mean over [B, 1, T'], and the / 3 of the sum
+            if mode == "d":
+                r = adv_disc_pass(disc, real[i], B, Ts[i], loss, head=(1.0, mean), keep=need_p)
+                f = adv_disc_pass(disc, fake[i], B, Ts[i], loss, head=(0.0, mean), keep=need_p)
+            elif mode == "g":
+                r = None
+                f = adv_disc_pass(disc, fake[i], B, Ts[i], loss, head=(1.0, mean), keep=need_p or need_x)
+            else:
+                r = adv_disc_pass(disc, real[i], B, Ts[i], keep=False)
+                w = [1.0 / (nd * z.numel()) for z in r["zs"]]
+                f = adv_disc_pass(disc, fake[i], B, Ts[i], loss, fm_real=r, fm_scale=w, keep=need_p or need_x)
+                f["fm_w"] = w
+                r = dict(zs=r["zs"])
+            recs.append((r, f))
+        if need_x or need_p:
+            ctx.recs, ctx.Ts = recs, Ts
+        ctx.meta = (adv, mode, pair, B, F, T, need_x, need_p)
+        ctx.inputs = (e, ei) if need_x else None
+        ctx.params = params
+        ctx.dtypes = (enh.dtype, enh_im.dtype if pair else None)
+        return loss[0].float()
+
+    @staticmethod
+    def backward(ctx, g):
+        adv, mode, pair, B, F, T, need_x, need_p = ctx.meta
+        none = (None,) * 6
+        if not (need_x or need_p):
+            return none + (None,) * len(ctx.params)
+        discs = list(adv.discriminators)
+        nd = len(discs)
+        g = g.detach().float().reshape(1).contiguous()
+        grads, dxs = {}, []
+        if mode == "fm":                # the objective's largest static coefficient: what the pass's power-of-two scale is set by
+            cnorm = max(w for _, f in ctx.recs for w in f["fm_w"])
+        else:
+            cnorm = max(2.0 / (nd * B * _adv_tout(disc, ctx.Ts[i])) for i, disc in enumerate(discs))
+        with ops.wgrad_side_stream(enabled=need_p and B * T >= 100000):
+            for i, disc in enumerate(discs):
+                r, f = ctx.recs[i]
+                coef = 2.0 / (nd * B * _adv_tout(disc, ctx.Ts[i]))
+                if mode == "d":
+                    adv_disc_backward(disc, r, B, g, cnorm, grads, True, False, head_coef=coef)
+                    adv_disc_backward(disc, f, B, g, cnorm, grads, True, False, head_coef=coef)
+                elif mode == "g":
+                    dxs.append(adv_disc_backward(disc, f, B, g, cnorm, grads, need_p, need_x, head_coef=coef))
+                else:
+                    dxs.append(adv_disc_backward(disc, f, B, g, cnorm, grads, need_p, need_x, fm_real=r, fm_w=f["fm_w"]))
+        dx = dxi = None
+        if need_x:
+            for s in range(nd - 1, 0, -1):
+                ops.adv_pool_bwd(dxs[s], dxs[s - 1])
+            e, ei = ctx.inputs
+            dx, dxi = ops.adv_stage_bwd(dxs[0], e if pair else None, ei, B, F, T, g=g, cnorm=cnorm)
+            dx = dx.to(ctx.dtypes[0])
+            dxi = None if dxi is None else dxi.to(ctx.dtypes[1])
+        out = []
+        for p in ctx.params:
+            gp = grads.get(id(p)) if p.requires_grad else None
+            out.append(None if gp is None else gp.to(p.dtype))
+        ctx.recs = ctx.inputs = None
+        return (None, None, None, None, dx, dxi) + tuple(out)
+
+
+def _adv_tout(disc, T):
+    """frames the discriminator's output has for T input frames (every stride-2 conv: k 5, pad 2 -> ceil(T / 2))"""
+    for m in _adv_convs(disc)[:-1]:
+        T = (T + 2 * m.padding[0] - m.kernel_size[0]) // m.stride[0] + 1
+    return T

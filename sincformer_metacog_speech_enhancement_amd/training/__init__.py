@@ -1,4 +1,4 @@
 from .curriculum import CurriculumScheduler
-from .losses import MSEMaskLoss, PerceptualSTOILoss
+from .losses import AdversarialLoss, MSEMaskLoss, PerceptualSTOILoss, SubDiscriminator
 
-__all__ = ["CurriculumScheduler", "MSEMaskLoss", "PerceptualSTOILoss"]
+__all__ = ["AdversarialLoss", "CurriculumScheduler", "MSEMaskLoss", "PerceptualSTOILoss", "SubDiscriminator"]

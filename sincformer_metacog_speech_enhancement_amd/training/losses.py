@@ -1,9 +1,11 @@
 """Host-side mirrors of training/losses.py: MSEMaskLoss (:22-30) and PerceptualSTOILoss (:37-143), the objectives of the
-curriculum's stages 1 and 2, each one launch of curriculum_losses.hip (forward and, when the input requires it, the gradient).
-The adversarial part of stage 3 (SubDiscriminator, AdversarialLoss) is not built.  How the terms are weighted and combined
-is the caller's: the reference combines them nowhere."""
+curriculum's stages 1 and 2, each one launch of curriculum_losses.hip (forward and, when the input requires it, the gradient);
+SubDiscriminator and AdversarialLoss (:150-289), the third term of stage 3: spectrally normalised Conv1d stacks at three time
+scales, run as implicit GEMMs on channels-last 16-bit rows with csrc/adversarial.hip around them (train.AdversarialFunction).
+How the terms are weighted and combined is the caller's: the reference combines them nowhere."""
 import numpy as np
 import torch
+from torch import nn
 
 from .. import config
 from .._hostmod import HipModule
@@ -85,3 +87,98 @@ class PerceptualSTOILoss(HipModule):
         self._check(B, T, F)
         return train.PerceptualStoiFunction.apply(enh_real, enh_imag, clean_real, clean_imag, self.band_weights,
                                                   int(self.frame_len), float(self.beta))
+
+
+ADV_MIN_FRAMES = 4                  # 4 -> 2 -> 1 through the two pools; at 3 the second pool has no output
+ADV_MAX_WIDTH = 512                 # first-layer Cin after zero padding (ops.ADV_MAX_WIDTH)
+ADV_CHANNELS = ((64, 128, 256, 512), (64, 128, 256), (32, 64, 128))
+
+
+class SubDiscriminator(HipModule):
+    """One scale: Conv1d(k 5, pad 2) per entry of `channels` (stride 2 on all but the last) + LeakyReLU(0.2) each, then
+    Conv1d(C, 1, k 3, pad 1); every conv under the legacy torch.nn.utils.spectral_norm.  The convs live in `layers` at the
+    reference's indices (0, 2, ..) so keys, shapes and the seeded init are its own; they are never called."""
+
+    def __init__(self, n_freq, channels=None):
+        super().__init__()
+        mods, cin = [], n_freq
+        channels = list(channels or ADV_CHANNELS[0])
+        for i, c in enumerate(channels):
+            mods += [nn.utils.spectral_norm(nn.Conv1d(cin, c, 5, stride=1 if i == len(channels) - 1 else 2, padding=2)),
+                     nn.LeakyReLU(0.2, inplace=True)]
+            cin = c
+        mods.append(nn.utils.spectral_norm(nn.Conv1d(cin, 1, 3, padding=1)))
+        self.layers = nn.Sequential(*mods)
+        self.n_freq = n_freq
+
+    def forward(self, x):
+        """x [B, F, T] magnitudes -> (out [B, 1, T'], [the post-LeakyReLU features [B, C, T']]) in fp32.  A call iterates the
+        spectral-norm vectors in train() like any call of the reference's; the results carry no autograd graph (the three
+        objectives of AdversarialLoss are the differentiable entry points)."""
+        from .. import ops, train
+        self._require_device(x)
+        _adv_check(self.n_freq, x, name="SubDiscriminator")
+        B, F, T = x.shape
+        x16, _ = ops.adv_stage(x.detach().float().contiguous(), None, ops.adv_plan(F, [1])[0][0]["Cp"], False)
+        loss = torch.zeros(1, device=x.device, dtype=torch.float64)
+        rec = train.adv_disc_pass(self, x16, B, T, loss, head=(0.0, 0.0))
+        feats = [a.float().transpose(1, 2) for a in rec["xs"][1:]]
+        return rec["out"].unsqueeze(1), feats
+
+
+def _adv_check(n_freq, x, name="AdversarialLoss", cl=False):
+    if n_freq > ADV_MAX_WIDTH:
+        raise NotImplementedError("%s (HIP build): at most %d frequency bins; got %d" % (name, ADV_MAX_WIDTH, n_freq))
+    if x.dim() != 3:
+        raise ValueError("%s: a rank-3 spectrogram is needed; got shape %s" % (name, tuple(x.shape)))
+    frames_dim, bins_dim = (1, 2) if cl else (2, 1)
+    if x.shape[bins_dim] != n_freq:
+        raise ValueError("%s: %d frequency bins, the discriminators take %d" % (name, x.shape[bins_dim], n_freq))
+    if x.shape[frames_dim] < ADV_MIN_FRAMES or x.shape[0] < 1:
+        raise ValueError("%s: at least one utterance of %d frames is needed; got shape %s" % (name, ADV_MIN_FRAMES, tuple(x.shape)))
+
+
+class AdversarialLoss(HipModule):
+    """Three SubDiscriminators on the input, its AvgPool1d(4, 2, 1) and the pool of that.  The three objectives take magnitudes
+    [B, F, T]; the *_cl forms take channels-last spectra [B, T, F] as (real, imag) pairs, as SpeechEnhancer / EnhancementPath
+    produce them (magnitude sqrt(re^2 + im^2 + 1e-8), taken in the staging kernel).  Every call of a discriminator advances its
+    spectral-norm vectors in train(), so results depend on the call sequence exactly as the reference's do."""
+
+    def __init__(self, input_dim=None):
+        super().__init__()
+        n_freq = input_dim or (config.FFT_SIZE // 2 + 1)
+        self.discriminators = nn.ModuleList([SubDiscriminator(n_freq, list(c)) for c in ADV_CHANNELS])
+        self.downsample = nn.AvgPool1d(kernel_size=4, stride=2, padding=1)     # never called: adversarial.hip's pool
+        self.discriminator = self.discriminators[0]
+        self.n_freq = n_freq
+
+    def _run(self, mode, clean, clean_im, enh, enh_im, cl):
+        from .. import train
+        given = [t for t in (clean, clean_im, enh, enh_im) if t is not None]
+        self._require_device(*given)
+        for t in given[1:]:
+            if t.shape != given[0].shape:
+                raise ValueError("AdversarialLoss: shapes differ: %s and %s" % (tuple(given[0].shape), tuple(t.shape)))
+        _adv_check(self.n_freq, enh, cl=cl)
+        params = list(self.parameters())
+        if any(p.dtype != torch.float32 for p in params):
+            raise NotImplementedError("AdversarialLoss (HIP build): the discriminators' parameters are kept in fp32")
+        return train.AdversarialFunction.apply(self, mode, clean, clean_im, enh, enh_im, *params)
+
+    def discriminator_loss(self, clean_spec, enhanced_spec):
+        return self._run("d", clean_spec, None, enhanced_spec, None, False)
+
+    def generator_loss(self, enhanced_spec):
+        return self._run("g", None, None, enhanced_spec, None, False)
+
+    def feature_matching_loss(self, clean_spec, enhanced_spec):
+        return self._run("fm", clean_spec, None, enhanced_spec, None, False)
+
+    def discriminator_loss_cl(self, clean_real, clean_imag, enh_real, enh_imag):
+        return self._run("d", clean_real, clean_imag, enh_real, enh_imag, True)
+
+    def generator_loss_cl(self, enh_real, enh_imag):
+        return self._run("g", None, None, enh_real, enh_imag, True)
+
+    def feature_matching_loss_cl(self, clean_real, clean_imag, enh_real, enh_imag):
+        return self._run("fm", clean_real, clean_imag, enh_real, enh_imag, True)
