@@ -584,6 +584,45 @@ int sfm_adv_head(const void* a16, const void* a16lo, const void* w16, const void
 int sfm_adv_head_bwd(const void* a16, const void* w16, const float* out, const float* g, float coef, float cnorm, float target,
                      float* da, float* dwb, float* ws, int B, int T, int C, int dtype, void* stream);
 
+/* Curriculum batches (masks.hip): the mask targets of masks/{irm,pcirm,opt_pcirm}.py on n contiguous fp32 elements per plane, the
+ * SNR mix of training/conformer_pipeline.py:142-150 (the rule of training/pipeline.py:71-94) over a batch, and the two fused.
+ * All planes fp32; 16-byte accesses where every plane is 16-byte aligned, scalar ones otherwise.  n, B * L and B * T * F are at
+ * most 2^31 - 1 (SFM_ERR_SHAPE beyond).  No atomics anywhere: results are the same bits from run to run.
+ * sfm_mask_irm: out = clip((c^2 / (c^2 + n^2 + eps))^p, 0, 1) of the magnitudes c, n; p = 0.5 takes a square root, any other
+ *   p > 0 powf (p <= 0: SFM_ERR_ARG).
+ * sfm_mask_corr: rho_s = clip(|y c| / (sqrt(y^2 + eps) sqrt(c^2 + eps)), 0, 1) of noisy y and clean c, rho_n likewise of y and
+ *   the noise: the per-T-F-unit rule (masks/pcirm.py:49-57) at every element, whatever the rank of the caller's tensors.
+ * sfm_mask_pcirm: out = clip(S / (S + N + eps), 0, 1), S = rho_s (c |cos phi1|)^2, N = rho_n (n |cos phi2|)^2.
+ * sfm_mask_quantize: table = M + 1 ascending boundaries [0, s_2 .. s_M, 1] then the M assigned values, doubles on the device;
+ *   out = the value of the step m with boundary[m] <= x < boundary[m + 1], the last value for x >= boundary[M], compared in
+ *   double; 0 where no step holds x (a NaN, a negative value).  M in 2..16 (SFM_ERR_SHAPE outside).
+ * sfm_mix_scale: clean [B, L]; bank = every noise signal back to back, bank_off int32 [n_noise + 1] ascending from 0;
+ *   noise_ids int32 [B] (clamped to the bank); snr_db [B]; lengths int32 [B] or NULL (= L; clamped to 0..L).  Utterance b is
+ *   mixed with noise[j mod Ln] at sample j (a shorter noise tiled, a longer one cut).  Two launches: fp64 sums of clean^2 and
+ *   noise^2 over the first lengths[b] samples, one partial pair per workgroup of 4096 samples; then ONE workgroup adds each
+ *   utterance's partials in index order and writes scale[b] = sqrt(Pc / (Pn 10^(snr_db / 10))), P = mean + 1e-10.
+ *   ws >= 2 * B * ceil(L / 4096) doubles.  B <= 65535.
+ * sfm_mix_apply: noisy[b, j] = clean[b, j] + scale[b] * noise[j mod Ln] for j < lengths[b], 0 from there on; noise_rows
+ *   (or NULL) [B, L] receives the unscaled noise[j mod Ln], 0 from lengths[b] on.  Every element is written.
+ * sfm_curriculum_mask: (cr, ci), (nr, ni) = spectra [B, T, F] of the clean utterances and of sfm_mix_apply's noise rows.
+ *   (yr, yi) = C + scale[b] N, the spectrum of the mix (the STFT is linear).  kind 0: no mask (mask may be NULL); 1: the IRM
+ *   of |C| and |s N| with exponent p; 2: the PCIRM of |C|, |s N|, |Y| with rho_s, rho_n as sfm_mask_corr gives them for
+ *   those magnitudes and phi1 = arg C - arg Y, phi2 = arg N - arg Y, whose cosines are taken as Re(C conj Y) / (|C| |Y|) (a zero
+ *   counts as phase 0); 3: that PCIRM quantised by `table` (sfm_mask_quantize's, M steps). */
+int sfm_mask_irm(const float* clean_mag, const float* noise_mag, float* out, long long n, float p, float eps, void* stream);
+int sfm_mask_corr(const float* noisy, const float* clean, const float* noise, float* rho_s, float* rho_n, long long n, float eps,
+                  void* stream);
+int sfm_mask_pcirm(const float* clean_mag, const float* noise_mag, const float* rho_s, const float* rho_n, const float* phi1,
+                   const float* phi2, float* out, long long n, float eps, void* stream);
+int sfm_mask_quantize(const float* pcirm, const double* table, float* out, long long n, int M, void* stream);
+int sfm_mix_scale(const float* clean, const float* bank, const int* bank_off, const int* noise_ids, const float* snr_db,
+                  const int* lengths, double* ws, float* scale, int B, int L, int n_noise, void* stream);
+int sfm_mix_apply(const float* clean, const float* bank, const int* bank_off, const int* noise_ids, const int* lengths,
+                  const float* scale, float* noisy, float* noise_rows, int B, int L, int n_noise, void* stream);
+int sfm_curriculum_mask(const float* cr, const float* ci, const float* nr, const float* ni, const float* scale,
+                        const double* table, float* yr, float* yi, float* mask, int B, int T, int F, int kind, float p, float eps,
+                        int M, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,10 @@ VQ_NUM_CENTROIDS = 3
 VQ_COMMITMENT_WEIGHT = 0.25
 MAA_THRESHOLD_INIT = 0.5
 
+# OPT-PCIRM quantiser (config.py:89-90 of the reference): M = 3 attenuation steps, local criterion -15 dB
+OPT_NUM_STEPS = 3
+LOCAL_CRITERION_DB = -15
+
 # curriculum stages in epochs (config.py:120-122 of the reference)
 CURRICULUM_STAGE1_EPOCHS = 15
 CURRICULUM_STAGE2_EPOCHS = 20

@@ -1092,6 +1092,125 @@ def mse_loss(pred, target, need_grad=False):
     return loss, grad
 
 
+# ---------------------------------------------------------------------------
+# curriculum batches: mask targets and the SNR mix (csrc/masks.hip)
+# ---------------------------------------------------------------------------
+MIX_CHUNK = 4096                    # samples per workgroup of sfm_mix_scale / sfm_mix_apply
+QUANT_MAX_STEPS = 16                # sfm_mask_quantize
+MASK_KINDS = {None: 0, "irm": 1, "pcirm": 2, "opt_pcirm": 3}
+
+
+def _same_planes(name, *ts):
+    """the element count of fp32 contiguous tensors of one shape: anything else is refused (-2) before the call"""
+    if any(t.shape != ts[0].shape or t.dtype != torch.float32 or not t.is_contiguous() for t in ts) or ts[0].numel() == 0:
+        _lib.check(-2, name)
+    return ts[0].numel()
+
+
+def mask_irm(clean_mag, noise_mag, p=0.5, eps=1e-10):
+    """masks/irm.py:17-39 on two fp32 contiguous tensors of one shape -> fp32 tensor of that shape"""
+    _need_dev(clean_mag, noise_mag)
+    L = _lib.load()
+    n = _same_planes("mask_irm", clean_mag, noise_mag)
+    out = torch.empty_like(clean_mag)
+    _call("mask_irm", L.sfm_mask_irm, (_p(clean_mag), _p(noise_mag), _p(out), n, float(p), float(eps), _stream()),
+          6.0 * n, 12.0 * n)
+    return out
+
+
+def mask_corr(noisy, clean, noise, eps=1e-10):
+    """masks/pcirm.py:49-57, 70-72 per element -> (rho_s, rho_n)"""
+    _need_dev(noisy, clean, noise)
+    L = _lib.load()
+    n = _same_planes("mask_corr", noisy, clean, noise)
+    rho_s, rho_n = torch.empty_like(noisy), torch.empty_like(noisy)
+    _call("mask_corr", L.sfm_mask_corr, (_p(noisy), _p(clean), _p(noise), _p(rho_s), _p(rho_n), n, float(eps), _stream()),
+          14.0 * n, 20.0 * n)
+    return rho_s, rho_n
+
+
+def mask_pcirm(clean_mag, noise_mag, rho_s, rho_n, phi1, phi2, eps=1e-10):
+    """masks/pcirm.py:122-131 per element"""
+    _need_dev(clean_mag, noise_mag, rho_s, rho_n, phi1, phi2)
+    L = _lib.load()
+    n = _same_planes("mask_pcirm", clean_mag, noise_mag, rho_s, rho_n, phi1, phi2)
+    out = torch.empty_like(clean_mag)
+    _call("mask_pcirm", L.sfm_mask_pcirm, (_p(clean_mag), _p(noise_mag), _p(rho_s), _p(rho_n), _p(phi1), _p(phi2), _p(out), n,
+                                           float(eps), _stream()), 12.0 * n, 28.0 * n)
+    return out
+
+
+def mask_quantize(pcirm, table, M):
+    """masks/opt_pcirm.py:79-101; table: float64 device tensor, M + 1 boundaries then M values (masks.opt_pcirm.quantizer_table)"""
+    _need_dev(pcirm, table)
+    L = _lib.load()
+    n = _same_planes("mask_quantize", pcirm)
+    if table.dtype != torch.float64 or table.numel() != 2 * M + 1 or not 2 <= M <= QUANT_MAX_STEPS:
+        _lib.check(-2, "mask_quantize")
+    out = torch.empty_like(pcirm)
+    _call("mask_quantize", L.sfm_mask_quantize, (_p(pcirm), _p(table), _p(out), n, int(M), _stream()), 0.0, 8.0 * n)
+    return out
+
+
+def _mix_columns(name, clean, bank, bank_off, noise_ids, lengths, *per_utterance):
+    """what the mix kernels index with has the size and type they assume: refused (-2) before the call otherwise"""
+    B = clean.shape[0]
+    ok = clean.dim() == 2 and clean.dtype == torch.float32 and bank.dtype == torch.float32 and bank_off.dtype == torch.int32
+    ok = ok and bank_off.numel() >= 2 and noise_ids.dtype == torch.int32 and noise_ids.numel() == B
+    ok = ok and (lengths is None or (lengths.dtype == torch.int32 and lengths.numel() == B))
+    ok = ok and all(t.dtype == torch.float32 and t.numel() == B for t in per_utterance)
+    if not ok:
+        _lib.check(-2, name)
+
+
+def mix_scale(clean, bank, bank_off, noise_ids, snr_db, lengths=None):
+    """clean [B, L] fp32 contiguous; bank fp32, bank_off int32 [n_noise + 1]; noise_ids int32 [B]; snr_db fp32 [B]; lengths int32
+    [B] or None -> scale [B] fp32 (two launches: fp64 chunk sums, then the ordered fold)"""
+    _need_dev(clean, bank, bank_off, noise_ids, snr_db, lengths)
+    L = _lib.load()
+    _mix_columns("mix_scale", clean, bank, bank_off, noise_ids, lengths, snr_db)
+    B, Ln = clean.shape
+    n_noise = bank_off.numel() - 1
+    scale = torch.empty(B, device=clean.device, dtype=torch.float32)
+    ws = _ws64(2 * B * ((Ln + MIX_CHUNK - 1) // MIX_CHUNK), clean.device)
+    _call("mix", L.sfm_mix_scale, (_p(clean), _p(bank), _p(bank_off), _p(noise_ids), _p(snr_db), _p(lengths), _p(ws), _p(scale), B,
+                                   Ln, n_noise, _stream()), 4.0 * B * Ln, 8.0 * B * Ln, "scale B%d L%d" % (B, Ln))
+    return scale
+
+
+def mix_apply(clean, bank, bank_off, noise_ids, scale, lengths=None, want_rows=False):
+    """-> (noisy [B, L], the unscaled noise rows [B, L] or None); every element written"""
+    _need_dev(clean, bank, bank_off, noise_ids, scale, lengths)
+    L = _lib.load()
+    _mix_columns("mix_apply", clean, bank, bank_off, noise_ids, lengths, scale)
+    B, Ln = clean.shape
+    noisy = torch.empty_like(clean)
+    rows = torch.empty_like(clean) if want_rows else None
+    _call("mix", L.sfm_mix_apply, (_p(clean), _p(bank), _p(bank_off), _p(noise_ids), _p(lengths), _p(scale), _p(noisy), _p(rows), B,
+                                   Ln, bank_off.numel() - 1, _stream()), 2.0 * B * Ln, (16.0 if want_rows else 12.0) * B * Ln,
+          "apply B%d L%d rows%d" % (B, Ln, 1 if want_rows else 0))
+    return noisy, rows
+
+
+def curriculum_mask(cr, ci, nr, ni, scale, kind=None, p=0.5, eps=1e-10, table=None, M=0):
+    """spectra [B, T, F] of the clean utterances and of the noise rows, scale [B] -> (yr, yi, mask or None): the spectrum of
+    the mix and the mask target `kind` (MASK_KINDS), one launch"""
+    _need_dev(cr, ci, nr, ni, scale, table)
+    L = _lib.load()
+    B, T, F = cr.shape
+    _same_planes("curriculum_mask", cr, ci, nr, ni)
+    k = MASK_KINDS[kind]
+    if scale.numel() != B or scale.dtype != torch.float32 or (k == 3 and (table is None or table.numel() != 2 * M + 1)):
+        _lib.check(-2, "curriculum_mask")
+    yr, yi = torch.empty_like(cr), torch.empty_like(cr)
+    mask = torch.empty_like(cr) if k else None
+    n = B * T * F
+    _call("curriculum_mask", L.sfm_curriculum_mask, (_p(cr), _p(ci), _p(nr), _p(ni), _p(scale), _p(table), _p(yr), _p(yi), _p(mask),
+                                                     B, T, F, k, float(p), float(eps), int(M), _stream()),
+          (8.0, 16.0, 32.0, 32.0)[k] * n, (28.0 if k else 24.0) * n, "B%d T%d F%d kind%d" % (B, T, F, k))
+    return yr, yi, mask
+
+
 def spec_sums(pr, pi, tr, ti, out=None):
     L = _lib.load()
     S = torch.zeros(4, device=pr.device, dtype=torch.float64) if out is None else out

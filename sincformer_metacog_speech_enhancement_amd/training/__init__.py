@@ -1,4 +1,6 @@
+from .conformer_pipeline import CurriculumBatch, NoiseBank, curriculum_batch, mix_at_snr, mix_batch
 from .curriculum import CurriculumScheduler
 from .losses import AdversarialLoss, MSEMaskLoss, PerceptualSTOILoss, SubDiscriminator
 
-__all__ = ["AdversarialLoss", "CurriculumScheduler", "MSEMaskLoss", "PerceptualSTOILoss", "SubDiscriminator"]
+__all__ = ["AdversarialLoss", "CurriculumBatch", "CurriculumScheduler", "MSEMaskLoss", "NoiseBank", "PerceptualSTOILoss",
+           "SubDiscriminator", "curriculum_batch", "mix_at_snr", "mix_batch"]

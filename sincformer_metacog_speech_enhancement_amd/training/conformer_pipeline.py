@@ -1,11 +1,15 @@
 """Host-side mirror of the model / STFT / objective part of training/conformer_pipeline.py
 (si_snr_loss :52, MultiResolutionSTFTLoss :74, batch_stft :196, batch_istft :205, SpeechEnhancer :218-301,
 ConformerPipeline._compute_loss :539, _save_best :611, save_model :618, load_model :628, enhance_signal :653) and the
-north-star agent composition (EnhancementPath; SURVEY.md §3.3 with the glue of DESIGN.md).
+north-star agent composition (EnhancementPath; SURVEY.md §3.3 with the glue of DESIGN.md), and of what its data set does
+to a batch (_add_noise_at_snr :142, the assignment of WaveformDataset :162-171) as device passes: mix_at_snr, mix_batch,
+curriculum_batch.
 The data loaders / optimiser loop of the reference are out of scope.
 """
 import math
 import os
+from typing import NamedTuple, Optional
+
 import numpy as np
 import torch
 from torch import nn
@@ -32,6 +36,151 @@ def batch_istft(stft_real, stft_imag, fft_size, hop_size, frame_size, length):
     if not stft_real.is_cuda:
         raise RuntimeError("batch_istft: HIP path needs a device tensor (no CPU fallback)")
     return Fn.istft(stft_real.float(), stft_imag.float(), length, fft_size, hop_size, frame_size)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Curriculum batches: the SNR mix (:142-150, assigned as WaveformDataset does :162-171) and the oracle mask targets of masks/,
+# made where the batch is consumed (csrc/masks.hip).  Clean utterances and the noise bank go to the device once.
+# ---------------------------------------------------------------------------------------------------------------------------
+class NoiseBank:
+    """A list of 1-D fp32 device tensors as ONE concatenated buffer plus an int32 offset table [count + 1]"""
+
+    def __init__(self, signals):
+        signals = list(signals)
+        if not signals:
+            raise ValueError("noise bank: at least one noise signal is needed")
+        for s in signals:
+            if not torch.is_tensor(s) or not s.is_cuda:
+                raise RuntimeError("noise bank: the HIP path needs device tensors (no CPU fallback); got a CPU tensor")
+            if s.dim() != 1 or s.numel() == 0:
+                raise ValueError("noise bank: 1-D non-empty signals are needed; got shape %s" % (tuple(s.shape),))
+        sizes = [s.numel() for s in signals]
+        if sum(sizes) > 2 ** 31 - 1:
+            raise ValueError("noise bank: %d samples; the offset table is int32" % sum(sizes))
+        self.count = len(signals)
+        self.buffer = torch.cat([s.detach().float() for s in signals]).contiguous()
+        self.offsets = torch.tensor(np.concatenate([[0], np.cumsum(sizes)]), dtype=torch.int32, device=self.buffer.device)
+
+
+_banks = {}
+
+
+def noise_bank(signals):
+    """the NoiseBank of a list of device tensors, built once per list content (storage, length and version of every entry)"""
+    if isinstance(signals, NoiseBank):
+        return signals
+    signals = list(signals)
+    key = tuple((s.data_ptr(), s.numel(), s._version, str(s.device)) if torch.is_tensor(s) else id(s) for s in signals)
+    hit = _banks.get(key)
+    if hit is None:
+        if len(_banks) >= 8:
+            _banks.clear()
+        hit = _banks[key] = (NoiseBank(signals), signals)        # (the list is kept: a freed entry's address cannot come back)
+    return hit[0]
+
+
+def _mix_args(name, clean, bank, noise_ids, snr_db, lengths):
+    if not torch.is_tensor(clean) or not clean.is_cuda:
+        raise RuntimeError("%s: the HIP path needs device tensors (no CPU fallback); got a CPU tensor" % name)
+    if clean.dim() != 2 or clean.numel() == 0:
+        raise ValueError("%s: clean [B, L] is needed; got shape %s" % (name, tuple(clean.shape)))
+    clean = clean.detach().float().contiguous()
+    B, L = clean.shape
+    dev = clean.device
+
+    def column(v, dtype, what, lo=None, hi=None):
+        if torch.is_tensor(v) and v.is_cuda:
+            t = v.detach().to(dtype).contiguous()                # (a device column is trusted: the kernels clamp what they index with)
+        else:
+            a = np.asarray(v.cpu() if torch.is_tensor(v) else v).reshape(-1)
+            if lo is not None and a.size and (a.min() < lo or a.max() > hi):
+                raise ValueError("%s: %s outside %d..%d" % (name, what, lo, hi))
+            t = torch.as_tensor(a).to(dtype).to(dev)
+        if t.shape != (B,):
+            raise ValueError("%s: %s must have one entry per utterance (%d); got shape %s" % (name, what, B, tuple(t.shape)))
+        return t
+    ids = column(noise_ids, torch.int32, "noise_ids", 0, bank.count - 1)
+    snr = column(snr_db, torch.float32, "snr_db")
+    lens = None if lengths is None else column(lengths, torch.int32, "lengths", 1, L)
+    return clean, ids, snr, lens
+
+
+def mix_at_snr(clean, noise_bank_, noise_ids, snr_db, lengths=None):
+    """_add_noise_at_snr (:142-150) over a batch.  clean [B, L] (zero from lengths[i] on, as the reference pads), noise_bank_ a
+    list of 1-D device tensors (or a NoiseBank), noise_ids [B], snr_db [B], lengths [B] or None (= L) -> (noisy [B, L], scale [B]).
+    Per utterance: the noise is tiled when shorter (sample j reads noise[j mod Ln]) and cut when longer; the powers are means
+    over the utterance's own lengths[i] samples plus 1e-10 each, summed in fp64 in a fixed order (no atomics: the same bits
+    from run to run); scale = sqrt(Pc / (Pn 10^(snr / 10))); noisy = clean + scale * noise, 0 at and beyond lengths[i]."""
+    bank = noise_bank(noise_bank_)
+    clean, ids, snr, lens = _mix_args("mix_at_snr", clean, bank, noise_ids, snr_db, lengths)
+    scale = ops.mix_scale(clean, bank.buffer, bank.offsets, ids, snr, lens)
+    noisy, _ = ops.mix_apply(clean, bank.buffer, bank.offsets, ids, scale, lens)
+    return noisy, scale
+
+
+def _add_noise_at_snr(clean, noise, snr_db):
+    """training/conformer_pipeline.py:142-150 for one utterance: 1-D device tensors -> the noisy utterance (mix_at_snr)"""
+    return mix_at_snr(clean.reshape(1, -1), [noise.reshape(-1)], [0], [float(snr_db)])[0][0]
+
+
+def mix_assignment(count, n_noise, snr_levels, first_index=0):
+    """WaveformDataset's rule (:162-171) for the utterances first_index .. first_index + count - 1 of the data set:
+    utterance i gets noise i % n_noise and snr_levels[i % len(snr_levels)] -> (noise ids, SNRs in dB), two lists"""
+    snr_levels = list(snr_levels)
+    if not snr_levels or n_noise < 1:
+        raise ValueError("mix_assignment: at least one SNR level and one noise signal are needed")
+    idx = range(first_index, first_index + count)
+    return [i % n_noise for i in idx], [float(snr_levels[i % len(snr_levels)]) for i in idx]
+
+
+def mix_batch(clean, noise_bank_, snr_levels, first_index=0, lengths=None):
+    """mix_at_snr with WaveformDataset's assignment: utterance first_index + i of the data set gets
+    snr_levels[(first_index + i) % len(snr_levels)] and noise (first_index + i) % len(noise_bank_) -> (noisy, scale)"""
+    bank = noise_bank(noise_bank_)
+    ids, snr = mix_assignment(clean.shape[0], bank.count, snr_levels, first_index)
+    return mix_at_snr(clean, bank, ids, snr, lengths)
+
+
+class CurriculumBatch(NamedTuple):
+    """what curriculum_batch returns: the mix, the channels-last spectra the models consume, the mask target, the mix scales"""
+    noisy: torch.Tensor
+    noisy_real: torch.Tensor
+    noisy_imag: torch.Tensor
+    clean_real: torch.Tensor
+    clean_imag: torch.Tensor
+    mask: Optional[torch.Tensor]
+    scale: torch.Tensor
+
+
+@torch.no_grad()
+def curriculum_batch(clean, noise_bank_, snr_levels, mask_type, first_index=0, lengths=None, p=0.5, middle_value=None):
+    """One training batch of a curriculum stage, made on the device: the mix of mix_batch, the spectra of the mix and of the
+    clean utterances [B, T, F], and the oracle mask [B, T, F] of `mask_type` ('irm', 'pcirm', 'opt_pcirm' or None) - directly the
+    `oracle_mask` of MSEMaskLoss for a [B, T, F] prediction.  Nothing carries autograd history.
+      'irm'       masks.compute_irm(|C|, |sN|, p)
+      'pcirm'     masks.compute_pcirm of |C|, |sN|, the correlation coefficients of (|Y|, |C|, |sN|) and the phase differences
+                  arg C - arg Y, arg N - arg Y (a zero bin counts as phase 0)
+      'opt_pcirm' that PCIRM through masks.quantize_pcirm(., compute_snr_boundaries()[0], middle_value)
+    The STFT is linear: it is taken of `clean` and of the unscaled noise rows (functional.stft, exact fp32), and one
+    memory-bound kernel forms Y = C + scale N and the mask from them.  `clean` must be zero from lengths[i] on.
+    get_stage(epoch)['snr_levels'] is a value for `snr_levels`; the mask kind is the caller's choice."""
+    from ..masks.opt_pcirm import compute_snr_boundaries, quantizer_table
+    if mask_type not in ops.MASK_KINDS:
+        raise ValueError("curriculum_batch: mask_type must be 'irm', 'pcirm', 'opt_pcirm' or None; got %r" % (mask_type,))
+    if mask_type == "irm" and not p > 0:
+        raise ValueError("curriculum_batch: p must be positive; got %r" % (p,))
+    bank = noise_bank(noise_bank_)
+    ids, snr = mix_assignment(clean.shape[0], bank.count, snr_levels, first_index)
+    clean, ids, snr, lens = _mix_args("curriculum_batch", clean, bank, ids, snr, lengths)
+    scale = ops.mix_scale(clean, bank.buffer, bank.offsets, ids, snr, lens)
+    noisy, rows = ops.mix_apply(clean, bank.buffer, bank.offsets, ids, scale, lens, want_rows=True)
+    fft, hop, win = config.FFT_SIZE, config.HOP_SIZE, config.FRAME_SIZE
+    cr, ci = Fn.stft(clean, fft, hop, win)
+    nr, ni = Fn.stft(rows, fft, hop, win)
+    table, M = (quantizer_table(compute_snr_boundaries()[0], middle_value, clean.device) if mask_type == "opt_pcirm"
+                else (None, 0))
+    yr, yi, mask = ops.curriculum_mask(cr, ci, nr, ni, scale, mask_type, p=p, table=table, M=M)
+    return CurriculumBatch(noisy, yr, yi, cr, ci, mask, scale)
 
 
 def si_snr_loss(estimated, target):
