@@ -1,5 +1,6 @@
 """Training-mode ConformerBlock on the HIP path (forward with batch statistics + backward) against torch
-autograd of the CPU oracle (dropout p = 0), plus statistical checks of the dropout path."""
+autograd of the CPU oracle (dropout p = 0), plus statistical checks of the dropout path.  The p > 0 step itself - every mask
+rebuilt on the host, forward and gradients against float64 at the bounds used here - is in tests/test_dropout_gpu.py."""
 import math
 import numpy as np
 import pytest
