@@ -428,20 +428,27 @@ int sfm_layernorm_bwd_next(const float* x, const float* gamma, const void* dy, i
 /* mode 0 swish fwd, 1 swish bwd, 2 GLU fwd, 3 GLU bwd, 4 alpha*g*dropout; counter-based dropout (p, seed) */
 int sfm_ew_train(const void* z, const void* g, void* out, long long M, int N, int mode, int g_f32, int out_f32,
                  float alpha, float p, unsigned int seed, int dtype, void* stream);
-/* BatchNorm1d training statistics / backward (through the following Swish); ws (optional): sfm_col_stats_ws_floats(M, C) floats */
+/* BatchNorm1d training statistics / backward (through the following Swish); ws (optional): sfm_col_stats_ws_floats(M, C) floats.
+ * sfm_col_stats without aux gives the raw moments { sum y, sum y^2 }: kept for callers that want them; the training step forms
+ * its statistics from sfm_col_stats_shifted */
 long long sfm_col_stats_ws_floats(int M, int C);
 int sfm_col_stats(const float* y, const float* aux, const float* mean, const float* rstd, float* S, int M, int C, float* ws,
                   void* stream);
+/* the sums of the BatchNorm statistics, shifted: K[c] = mean of min(M, 128) rows of y spread evenly over the M; S[c] =
+ * { sum (y - K[c]), sum (y - K[c])^2 } (S zero-filled; ws as above) */
+int sfm_col_pilot(const float* y, float* K, int M, int C, void* stream);
+int sfm_col_stats_shifted(const float* y, const float* K, float* S, int M, int C, float* ws, void* stream);
 /* gradient fan-in: out[m, c] = a[m, c] + (c < Cb ? b[m, c] : 0), fp32 rows with strides lda / ldb / ldo (C, Cb multiples of 4) */
 int sfm_add_cols(const float* a, const float* b, float* out, long long M, int C, int Cb, long long lda, long long ldb, long long ldo,
                  void* stream);
 /* BiLSTM dW_hh operand: previous output of each chain, h fp32 [B, T, 2H] -> out 16-bit [B*T, 2H]
  * (out[b,t,:H] = h[b,t-1,:H], out[b,t,H:] = h[b,t+1,H:], zero at the chain's first step) */
 int sfm_lstm_hprev16(const float* h, void* out, int B, int T, int H, int dtype, void* stream);
-/* nn.BatchNorm1d training statistics from sfm_col_stats' sums: mean, rstd, folded affine (sc, sh) and the in-place update of the
- * running statistics (unbiased variance; run_* may be NULL); eval_mode: statistics = run_mean / run_var, nothing updated */
-int sfm_bn_finalize(const float* S, const float* gamma, const float* beta, float* run_mean, float* run_var, float* mean,
-                    float* rstd, float* sc, float* sh, int C, long long M, float eps, float momentum, int eval_mode,
+/* nn.BatchNorm1d training statistics from the shifted sums S of sfm_col_stats_shifted and their shift K (sfm_col_pilot):
+ * mean = K + S0 / M, var = S1 / M - (S0 / M)^2, rstd, folded affine (sc, sh) and the in-place update of the running statistics
+ * (unbiased variance; run_* may be NULL); eval_mode: statistics = run_mean / run_var, nothing updated (S, K may be NULL) */
+int sfm_bn_finalize(const float* S, const float* K, const float* gamma, const float* beta, float* run_mean, float* run_var,
+                    float* mean, float* rstd, float* sc, float* sh, int C, long long M, float eps, float momentum, int eval_mode,
                     void* stream);
 int sfm_bn_swish_bwd(const void* g, const float* y, const float* mean, const float* rstd, const float* gamma,
                      const float* beta, float* S, float* dy, int M, int C, int g_f32, int pass, int dtype,

@@ -434,18 +434,23 @@ extern "C" int sfm_ew_train(const void* z, const void* g, void* out, long long M
 // BatchNorm1d training (models/conformer.py:95,118): statistics over all B*T rows per channel.
 //   col_stats: S[c] = { sum y, sum y^2 }  or, with aux (backward), { sum dy, sum dy * xhat }
 //   (accumulated with atomics; S must be zero-filled; y fp32 [M, C])
+//   col_stats_shifted (shift = K[c] from col_pilot, the mean of up to 128 rows spread evenly over the M): S[c] = { sum (y - K),
+//   sum (y - K)^2 }.  The BatchNorm statistics are formed from these: sum y^2 / M - mean^2 cancels in fp32 once |mean| is a few
+//   standard deviations (its relative error grows with (mean / std)^2, as nn.BatchNorm1d's two-pass form does not); with the
+//   shift, |mean - K| / std takes the place of |mean| / std, and K is a sample mean: a fraction of a standard deviation away.
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void col_stats_kernel(const float* __restrict__ y, const float* __restrict__ aux,
                                                         const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                        float* __restrict__ S, int M, int C, int rows_per_block,
-                                                        float* __restrict__ ws) {
+                                                        const float* __restrict__ shift, float* __restrict__ S, int M, int C,
+                                                        int rows_per_block, float* __restrict__ ws) {
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c >= C) return;
   const int m0 = blockIdx.y * rows_per_block, m1 = min(M, m0 + rows_per_block);
   float s0 = 0.f, s1 = 0.f;
   if (!aux) {
+    const float sh = shift ? shift[c] : 0.f;                // (no shift: sfm_col_stats' raw moments; y - 0 is y, bit for bit)
     for (int m = m0; m < m1; ++m) {
-      const float v = y[(long long)m * C + c];
+      const float v = y[(long long)m * C + c] - sh;
       s0 += v;
       s1 += v * v;
     }
@@ -471,19 +476,26 @@ __global__ __launch_bounds__(256) void col_stats_kernel(const float* __restrict_
 // 4-byte loads, 256 dependent trips: 1.5 TB/s on [205 056, 256].)
 __global__ __launch_bounds__(256) void col_stats_vec_kernel(const float* __restrict__ y, const float* __restrict__ aux,
                                                             const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                            float* __restrict__ S, int M, int C, int rows_per_block,
-                                                            float* __restrict__ ws) {
+                                                            const float* __restrict__ shift, float* __restrict__ S, int M, int C,
+                                                            int rows_per_block, float* __restrict__ ws) {
   __shared__ float red[2048];                            // [row lane][2][C]
   const int nv = C >> 2, rl = 256 / nv;
   const int tv = threadIdx.x % nv, tr = threadIdx.x / nv, c0 = tv * 4;
   const int m0 = blockIdx.x * rows_per_block, m1 = min(M, m0 + rows_per_block);
   float s0[4] = {0.f, 0.f, 0.f, 0.f}, s1[4] = {0.f, 0.f, 0.f, 0.f};
   if (!aux) {
+    float sh[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) sh[j] = shift ? shift[c0 + j] : 0.f;
 #pragma unroll 4
     for (int m = m0 + tr; m < m1; m += rl) {
       const f32x4 v = *reinterpret_cast<const f32x4*>(y + (long long)m * C + c0);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) { s0[j] += v[j]; s1[j] = fmaf(v[j], v[j], s1[j]); }
+      for (int j = 0; j < 4; ++j) {
+        const float d = v[j] - sh[j];
+        s0[j] += d;
+        s1[j] = fmaf(d, d, s1[j]);
+      }
     }
   } else {
     const f32x4 mu = *reinterpret_cast<const f32x4*>(mean + c0);
@@ -517,22 +529,55 @@ __global__ __launch_bounds__(256) void col_stats_vec_kernel(const float* __restr
 // folded in block order: bit-reproducible statistics; NULL = fp32 atomics)
 extern "C" long long sfm_col_stats_ws_floats(int M, int C) { return (long long)((M + 127) / 128 + 1) * 2 * (C > 0 ? C : 0); }
 
-extern "C" int sfm_col_stats(const float* y, const float* aux, const float* mean, const float* rstd, float* S, int M, int C,
-                             float* ws, void* stream) {
-  if (!y || !S || (aux && (!mean || !rstd))) return SFM_ERR_ARG;
+static int col_stats_go(const float* y, const float* aux, const float* mean, const float* rstd, const float* shift, float* S, int M,
+                        int C, float* ws, void* stream) {
   if (M <= 0 || C <= 0) return SFM_ERR_SHAPE;
   if (ws && (((uintptr_t)ws) % 16) != 0) return SFM_ERR_ARG;
   if (C % 4 == 0 && C <= 1024 && 256 % (C / 4) == 0 &&
       (((uintptr_t)y | (uintptr_t)aux | (uintptr_t)mean | (uintptr_t)rstd) % 16) == 0) {
     const int rpbv = 128;
-    SFM_LAUNCH(col_stats_vec_kernel, dim3((M + rpbv - 1) / rpbv), dim3(256), 0, (hipStream_t)stream, y, aux, mean, rstd, S, M, C, rpbv,
-               ws);
+    SFM_LAUNCH(col_stats_vec_kernel, dim3((M + rpbv - 1) / rpbv), dim3(256), 0, (hipStream_t)stream, y, aux, mean, rstd, shift, S, M, C,
+               rpbv, ws);
     return ws ? sfm_fold_partials(ws, S, 1, 2 * C, 2 * C, (M + rpbv - 1) / rpbv, 1, stream) : SFM_OK;
   }
   const int rpb = 256;
   SFM_LAUNCH(col_stats_kernel, dim3((C + 255) / 256, (M + rpb - 1) / rpb), dim3(256), 0, (hipStream_t)stream, y, aux, mean,
-             rstd, S, M, C, rpb, ws);
+             rstd, shift, S, M, C, rpb, ws);
   return ws ? sfm_fold_partials(ws, S, 1, 2 * C, 2 * C, (M + rpb - 1) / rpb, 1, stream) : SFM_OK;
+}
+
+extern "C" int sfm_col_stats(const float* y, const float* aux, const float* mean, const float* rstd, float* S, int M, int C,
+                             float* ws, void* stream) {
+  if (!y || !S || (aux && (!mean || !rstd))) return SFM_ERR_ARG;
+  return col_stats_go(y, aux, mean, rstd, nullptr, S, M, C, ws, stream);
+}
+
+// K[c] = mean of ns = min(M, 128) rows of y spread evenly over the M (row i * M / ns): the shift of sfm_col_stats_shifted.  A
+// thread owns one column and one of 4 row lanes; the lanes meet in LDS in a fixed order (the same bits on every run).
+__global__ __launch_bounds__(256) void col_pilot_kernel(const float* __restrict__ y, float* __restrict__ K, int M, int C) {
+  __shared__ float red[4][64];
+  const int tc = threadIdx.x & 63, tr = threadIdx.x >> 6, c = blockIdx.x * 64 + tc;
+  const int ns = min(M, 128);
+  float s = 0.f;
+  if (c < C)
+    for (int i = tr; i < ns; i += 4) s += y[((long long)i * M / ns) * C + c];
+  red[tr][tc] = s;
+  __syncthreads();
+  if (tr == 0 && c < C) K[c] = (((red[0][tc] + red[1][tc]) + red[2][tc]) + red[3][tc]) / (float)ns;
+}
+
+extern "C" int sfm_col_pilot(const float* y, float* K, int M, int C, void* stream) {
+  if (!y || !K) return SFM_ERR_ARG;
+  if (M <= 0 || C <= 0) return SFM_ERR_SHAPE;
+  SFM_LAUNCH(col_pilot_kernel, dim3((C + 63) / 64), dim3(256), 0, (hipStream_t)stream, y, K, M, C);
+  return SFM_OK;
+}
+
+// the sums of the BatchNorm statistics: S[c] = { sum (y - K[c]), sum (y - K[c])^2 } (S zero-filled; same kernels, workspace and
+// ordered fold as sfm_col_stats)
+extern "C" int sfm_col_stats_shifted(const float* y, const float* K, float* S, int M, int C, float* ws, void* stream) {
+  if (!y || !K || !S) return SFM_ERR_ARG;
+  return col_stats_go(y, nullptr, nullptr, nullptr, K, S, M, C, ws, stream);
 }
 
 // Gradient fan-in of a tensor whose first Cb columns also fed a second consumer: out[m, c] = a[m, c] + (c < Cb ? b[m, c] : 0)
@@ -598,10 +643,12 @@ extern "C" int sfm_lstm_hprev16(const float* h, void* out, int B, int Tn, int H,
 }
 
 // BatchNorm1d training statistics finalised on the device (models/conformer.py ConvolutionModule's nn.BatchNorm1d, train() mode):
-// S[c] = {sum y, sum y^2} over the M rows ->  mean, rstd = 1/sqrt(biased var + eps), the folded affine
+// S[c] = {sum (y - K), sum (y - K)^2} over the M rows (sfm_col_stats_shifted with the shift K of sfm_col_pilot) ->
+// mean = K + S0 / M, biased var = S1 / M - (S0 / M)^2, rstd = 1/sqrt(var + eps), the folded affine
 // sc = gamma rstd, sh = beta - mean sc, and the running statistics (unbiased variance, momentum) updated in place.
 // eval_mode: mean / var come from run_mean / run_var and nothing is updated.
-__global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restrict__ S, const float* __restrict__ gamma,
+__global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restrict__ S, const float* __restrict__ K,
+                                                          const float* __restrict__ gamma,
                                                           const float* __restrict__ beta, float* __restrict__ run_mean,
                                                           float* __restrict__ run_var, float* __restrict__ mean,
                                                           float* __restrict__ rstd, float* __restrict__ sc, float* __restrict__ sh,
@@ -613,8 +660,9 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restric
     mu = run_mean[c];
     var = run_var[c];
   } else {
-    mu = S[2 * c] / M;
-    var = fmaxf(S[2 * c + 1] / M - mu * mu, 0.0f);
+    const float d = S[2 * c] / M;
+    mu = K[c] + d;
+    var = fmaxf(S[2 * c + 1] / M - d * d, 0.0f);
     if (run_mean) {
       run_mean[c] = run_mean[c] * (1.0f - momentum) + momentum * mu;
       run_var[c] = run_var[c] * (1.0f - momentum) + momentum * (var * (M / fmaxf(M - 1.0f, 1.0f)));
@@ -628,13 +676,13 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restric
   sh[c] = beta[c] - mu * a;
 }
 
-extern "C" int sfm_bn_finalize(const float* S, const float* gamma, const float* beta, float* run_mean, float* run_var, float* mean,
-                               float* rstd, float* sc, float* sh, int C, long long M, float eps, float momentum, int eval_mode,
-                               void* stream) {
+extern "C" int sfm_bn_finalize(const float* S, const float* K, const float* gamma, const float* beta, float* run_mean,
+                               float* run_var, float* mean, float* rstd, float* sc, float* sh, int C, long long M, float eps,
+                               float momentum, int eval_mode, void* stream) {
   if (!gamma || !beta || !mean || !rstd || !sc || !sh) return SFM_ERR_ARG;
-  if (eval_mode ? (!run_mean || !run_var) : (!S || ((run_mean == nullptr) != (run_var == nullptr)))) return SFM_ERR_ARG;
+  if (eval_mode ? (!run_mean || !run_var) : (!S || !K || ((run_mean == nullptr) != (run_var == nullptr)))) return SFM_ERR_ARG;
   if (C <= 0 || M <= 0) return SFM_ERR_SHAPE;
-  SFM_LAUNCH(bn_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, S, gamma, beta, run_mean, run_var, mean,
+  SFM_LAUNCH(bn_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, S, K, gamma, beta, run_mean, run_var, mean,
              rstd, sc, sh, C, (float)M, eps, momentum, eval_mode);
   return SFM_OK;
 }

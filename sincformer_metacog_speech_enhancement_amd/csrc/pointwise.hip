@@ -649,9 +649,15 @@ static int dwconv_folded_route(const void* x, const float* wT, const float* sc, 
                  total, act, out_f32, frame_off, VARLEN ? B : 0);
     return SFM_OK;
   }
-  // KS 31: fp16 on the dot-product form, bf16 on the multiply-add kernel
+  // KS 31: fp16 with a 16-bit output on the dot-product form (its taps are rounded to fp16: 2^-12 of a tap, under the rounding of
+  // the output), everything else on the multiply-add kernel with fp32 taps - the fp32 output of the training forward, which
+  // feeds the BatchNorm statistics, would carry the tap rounding as its largest error (2e-4 of the output against 3e-7)
 #define DW_GO(L) return L(x, wT, sc, sh, out, B, Tn, C, act, out_f32, st, frame_off, tiles, n_tiles)
-  if (KS == 31) { if (dtype == SFM_DT_F16) DW_GO((launch_dwconv_dot<31, VARLEN>)); else DW_GO((launch_dwconv_reg<BF16, 31, VARLEN>)); }
+  if (KS == 31) {
+    if (dtype == SFM_DT_F16 && !out_f32) DW_GO((launch_dwconv_dot<31, VARLEN>));
+    if (dtype == SFM_DT_F16) DW_GO((launch_dwconv_reg<F16, 31, VARLEN>));
+    DW_GO((launch_dwconv_reg<BF16, 31, VARLEN>));
+  }
   if (dtype == SFM_DT_F16) DW_GO((launch_dwconv_reg<F16, 7, VARLEN>));
   DW_GO((launch_dwconv_reg<BF16, 7, VARLEN>));
 #undef DW_GO

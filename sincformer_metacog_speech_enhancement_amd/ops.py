@@ -1523,12 +1523,27 @@ def ew_train(mode, out, z=None, g=None, N=None, alpha=1.0, p=0.0, seed=0):
 
 
 def col_stats(y32, aux=None, mean=None, rstd=None):
+    """-> S [C, 2] = {sum y, sum y^2}, or with aux {sum y, sum y * xhat(aux)}.  The training step does not call this: its
+    statistics come from col_stats_shifted; the raw moments stay as a public entry point (sfm_col_stats), exercised by the tests"""
     L = _lib.load()
     M, C = y32.shape
     S = torch.zeros(C, 2, device=y32.device, dtype=torch.float32)
     ws = _ws(int(L.sfm_col_stats_ws_floats(M, C)), y32.device) if switch("deterministic") else None
     _call("col_stats", L.sfm_col_stats, (_p(y32), _p(aux), _p(mean), _p(rstd), _p(S), M, C, _p(ws), _stream()))
     return S
+
+
+def col_stats_shifted(y32):
+    """the sums of the BatchNorm statistics: -> S [C, 2] = {sum (y - K), sum (y - K)^2} and the shift K [C] (the mean of up to 128
+    rows spread over the M: a fraction of a standard deviation from the mean, so S1 / M - (S0 / M)^2 does not cancel)"""
+    L = _lib.load()
+    M, C = y32.shape
+    K = torch.empty(C, device=y32.device, dtype=torch.float32)
+    S = torch.zeros(C, 2, device=y32.device, dtype=torch.float32)
+    ws = _ws(int(L.sfm_col_stats_ws_floats(M, C)), y32.device) if switch("deterministic") else None
+    _call("col_stats", L.sfm_col_pilot, (_p(y32), _p(K), M, C, _stream()))
+    _call("col_stats", L.sfm_col_stats_shifted, (_p(y32), _p(K), _p(S), M, C, _p(ws), _stream()))
+    return S, K
 
 
 def add_cols(a, b, M, C, Cb):
@@ -1546,13 +1561,15 @@ def lstm_hprev16(h32, B, T, H):
     return out
 
 
-def bn_finalize(S, gamma, beta, run_mean, run_var, M, eps, momentum, eval_mode=False):
-    """-> mean, rstd, sc [1, C], sh [1, C]; the fp32 running statistics are updated in place (training)"""
+def bn_finalize(S, K, gamma, beta, run_mean, run_var, M, eps, momentum, eval_mode=False):
+    """S, K: the shifted sums and the shift of col_stats_shifted (None in eval mode) -> mean, rstd, sc [1, C], sh [1, C]; the
+    fp32 running statistics are updated in place (training)"""
     L = _lib.load()
     C = gamma.numel()
     buf = torch.empty(4, C, device=gamma.device, dtype=torch.float32)
-    _call("col_stats", L.sfm_bn_finalize, (_p(S), _p(gamma), _p(beta), _p(run_mean), _p(run_var), _p(buf[0]), _p(buf[1]), _p(buf[2]),
-                                           _p(buf[3]), C, M, float(eps), float(momentum), 1 if eval_mode else 0, _stream()))
+    _call("col_stats", L.sfm_bn_finalize, (_p(S), _p(K), _p(gamma), _p(beta), _p(run_mean), _p(run_var), _p(buf[0]), _p(buf[1]),
+                                           _p(buf[2]), _p(buf[3]), C, M, float(eps), float(momentum), 1 if eval_mode else 0,
+                                           _stream()))
     return buf[0], buf[1], buf[2:3], buf[3:4]
 
 
@@ -1572,10 +1589,11 @@ def bn_swish_bwd(g, y32, mean, rstd, gamma, beta, eval_mode=False):
     return dy, S[:, 1].contiguous(), S[:, 0].contiguous()
 
 
-def dwconv_wgrad(x16, dy32, B, T, C, KS):
+def dwconv_wgrad(x16, dy32, B, T, C, KS, dw=None, db=None):
+    """-> dw [C, KS], db [C]; accumulated into dw / db when given (fp32), else into fresh zeros"""
     L = _lib.load()
-    dw = torch.zeros(C, KS, device=x16.device, dtype=torch.float32)
-    db = torch.zeros(C, device=x16.device, dtype=torch.float32)
+    dw = torch.zeros(C, KS, device=x16.device, dtype=torch.float32) if dw is None else dw
+    db = torch.zeros(C, device=x16.device, dtype=torch.float32) if db is None else db
     scratch = torch.empty(int(L.sfm_dwconv_wgrad_scratch_floats(B, T, C, KS)), device=x16.device, dtype=torch.float32)
     _call("dwconv_wgrad", L.sfm_dwconv_wgrad, (_p(x16), _p(dy32), _p(dw), _p(db), _p(scratch), B, T, C, KS, _dt(), _stream()))
     return dw, db

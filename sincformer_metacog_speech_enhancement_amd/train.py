@@ -190,8 +190,9 @@ def _conv_fwd(x, P, B, T, p, seeds, bn_buffers, momentum=0.1, eps=1e-5, bn_eval=
     rm, rv = (bn_buffers[0], bn_buffers[1]) if bn_buffers is not None else (None, None)
     fp32_buffers = rm is not None and rm.dtype == torch.float32 and rv.dtype == torch.float32
     rm32, rv32 = (rm, rv) if fp32_buffers or rm is None else (rm.detach().float(), rv.detach().float())
-    S = None if bn_eval else ops.col_stats(yc)
-    mean, rstd, sc, sh = ops.bn_finalize(S, gam, bet, rm32, rv32, M, eps, momentum, eval_mode=bn_eval)
+    # (sums of y - K, K a sample mean of each channel: csrc/backward.hip, col_stats_shifted)
+    S, K = (None, None) if bn_eval else ops.col_stats_shifted(yc)
+    mean, rstd, sc, sh = ops.bn_finalize(S, K, gam, bet, rm32, rv32, M, eps, momentum, eval_mode=bn_eval)
     if bn_buffers is not None and not bn_eval:
         with torch.no_grad():
             if not fp32_buffers:

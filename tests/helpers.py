@@ -706,3 +706,291 @@ def bptt_forward_error_bound(case, amplitude, seed=0):
     s = case["save64"]
     noisy = s + (torch.rand(s.shape, generator=g, dtype=torch.float64) * 2 - 1) * amplitude
     return bptt_from_save(noisy, case["whh"].double(), case["dout"].double())
+
+
+# ---------------------------------------------------------------------------
+# ConvolutionModule: BatchNorm and depthwise nodes of train._conv_fwd / _conv_bwd
+# ---------------------------------------------------------------------------
+BN_EPS, BN_MOMENTUM = 1e-5, 0.1
+BN_STATS_MUTANTS = ("variance from one-pass fp32 sums of y and y^2 in 128-row blocks",)
+BN_FINALIZE_MUTANTS = ("biased variance in the running update", "momentum applied to the old value")
+BN_BWD_MUTANTS = ("eval mode keeps the batch-statistics correction", "the S1/M xhat correction dropped", "dgamma and dbeta swapped")
+DWCONV_MUTANTS = ("x of the neighbouring utterance read across a batch boundary", "taps mirrored")
+DWGRAD_MUTANTS = DWCONV_MUTANTS + ("halo frames outside a span taken as zero",
+                                   "last chunk of partials dropped at the second reduce level")
+
+
+def seq_sum(t):
+    """sum over dim 0 accumulated row by row in the dtype of t (numpy's cumsum; torch's CPU cumsum and sum accumulate float32 in
+    a wider type or pairwise, and give an e32 near 3e-8 that no fp32 reduction over thousands of rows can meet)"""
+    a = t.detach().numpy()
+    return torch.from_numpy(np.cumsum(a, axis=0, dtype=a.dtype)[-1].copy())
+
+
+def bn_stats64(y, mutant=None):
+    """mean and biased variance of y [M, C] over its rows as nn.BatchNorm1d forms them: two passes, mean first, then the mean of
+    (y - mean)^2; each pass a sequential row-order accumulation in the dtype of y"""
+    M = y.shape[0]
+    if mutant == BN_STATS_MUTANTS[0]:                            # fp32 whatever the input: this IS the rounding
+        a = y.float().numpy()
+        pad = (-M) % 128
+        a = np.concatenate([a, np.zeros((pad, a.shape[1]), np.float32)]).reshape(-1, 128, a.shape[1])
+        s0 = np.cumsum(np.cumsum(a, axis=1, dtype=np.float32)[:, -1], axis=0, dtype=np.float32)[-1]
+        s1 = np.cumsum(np.cumsum(a * a, axis=1, dtype=np.float32)[:, -1], axis=0, dtype=np.float32)[-1]
+        mu = s0 / np.float32(M)
+        var = np.maximum(s1 / np.float32(M) - mu * mu, np.float32(0))
+        return torch.from_numpy(mu).to(y.dtype), torch.from_numpy(var).to(y.dtype)
+    mean = seq_sum(y) / M
+    d = y - mean
+    return mean, seq_sum(d * d) / M
+
+
+def bn_finalize64(y, gamma, beta, run_mean, run_var, eps, momentum, eval_mode, mutant=None, stats=None):
+    """-> mean, rstd, sc = gamma rstd, sh = beta - mean sc, running mean, running variance (nn.BatchNorm1d: the running
+    variance takes the unbiased batch variance M / (M - 1)); eval mode: mean / var are the running statistics, nothing moves"""
+    M = y.shape[0]
+    if eval_mode:
+        mean, var, rm, rv = run_mean, run_var, run_mean, run_var
+    else:
+        mean, var = stats if stats is not None else bn_stats64(y)
+        unb = var if mutant == BN_FINALIZE_MUTANTS[0] else var * (M / (M - 1.0))
+        if mutant == BN_FINALIZE_MUTANTS[1]:
+            rm, rv = momentum * run_mean + (1 - momentum) * mean, momentum * run_var + (1 - momentum) * unb
+        else:
+            rm, rv = (1 - momentum) * run_mean + momentum * mean, (1 - momentum) * run_var + momentum * unb
+    rstd = torch.rsqrt(var + eps)
+    sc = gamma * rstd
+    return mean, rstd, sc, beta - mean * sc, rm, rv
+
+
+def bn_swish64(y, mean, rstd, gamma, beta):
+    """Swish(BatchNorm(y)) from given statistics"""
+    t = (y - mean) * rstd * gamma + beta
+    return t * torch.sigmoid(t)
+
+
+def bn_swish_bwd64(g, y, mean, rstd, gamma, beta, eval_mode, mutant=None):
+    """-> dy, dgamma, dbeta for the cotangent g of bn_swish64; training: mean / rstd are the batch statistics of y, so dy
+    carries their gradient (equal to autograd of the forward; test_host_logic)"""
+    M = y.shape[0]
+    xh = (y - mean) * rstd
+    t = xh * gamma + beta
+    sg = torch.sigmoid(t)
+    dt = g * sg * (1 + t * (1 - sg))
+    dbeta, dgamma = seq_sum(dt), seq_sum(dt * xh)
+    if eval_mode and mutant != BN_BWD_MUTANTS[0]:
+        dy = gamma * rstd * dt
+    elif mutant == BN_BWD_MUTANTS[1]:
+        dy = gamma * rstd * (dt - dbeta / M)
+    else:
+        dy = gamma * rstd * (dt - dbeta / M - xh * (dgamma / M))
+    return (dy, dbeta, dgamma) if mutant == BN_BWD_MUTANTS[2] else (dy, dgamma, dbeta)
+
+
+def _dw_pad(x, KS, mutant=None):
+    B, T, C = x.shape
+    pad = (KS - 1) // 2
+    if mutant == DWCONV_MUTANTS[0]:                               # one long utterance: the edges see the neighbours
+        flat = _F.pad(x.reshape(1, B * T, C), (0, 0, pad, pad))[0]
+        return torch.stack([flat[b * T:b * T + T + 2 * pad] for b in range(B)])
+    return _F.pad(x, (0, 0, pad, pad))
+
+
+def dwconv64(x, w, bias, mutant=None):
+    """depthwise conv over time, channels last: x [B, T, C], w [C, KS], bias [C] -> [B, T, C], zero edges per utterance"""
+    B, T, C = x.shape
+    KS = w.shape[1]
+    xp = _dw_pad(x, KS, mutant)
+    if mutant == DWCONV_MUTANTS[1]:
+        w = torch.flip(w, dims=[1])
+    out = xp.new_zeros(B, T, C) + bias
+    for k in range(KS):
+        out = out + xp[:, k:k + T] * w[:, k]
+    return out
+
+
+def dwgrad_spans(B, T, nparts):
+    """the (utterance, first frame, end frame) of each partial, in the kernel's order"""
+    ny = nparts // B
+    span = -(-T // ny)
+    return [(b, s * span, min(T, (s + 1) * span)) for b in range(B) for s in range(ny)]
+
+
+def dwconv_wgrad64(x, dy, KS, mutant=None, nparts=None):
+    """dw [C, KS], db [C] of dwconv64 for the cotangent dy; with mutant (and the row's partial count) a wrong form of the
+    kernel's span / partial structure"""
+    B, T, C = x.shape
+    pad = (KS - 1) // 2
+    xp = _dw_pad(x, KS, mutant if mutant == DWCONV_MUTANTS[0] else None)
+    parts = [(0, 0, T)] if mutant not in DWGRAD_MUTANTS[2:] else dwgrad_spans(B, T, nparts)
+    if mutant == DWGRAD_MUTANTS[3]:
+        n1 = -(-len(parts) // 32)
+        parts = parts[:32 * (n1 - 1)]
+    dw, db = x.new_zeros(C, KS), x.new_zeros(C)
+    for b, t0, t1 in parts:
+        sel = slice(None) if mutant not in DWGRAD_MUTANTS[2:] else slice(b, b + 1)
+        g, xs = dy[sel, t0:t1], xp[sel]
+        if mutant == DWGRAD_MUTANTS[2]:
+            xs = xs.clone()
+            xs[:, :t0 + pad] = 0
+            xs[:, t1 + pad:] = 0
+        db = db + g.sum(dim=(0, 1))
+        dw = dw + torch.stack([(g * xs[:, t0 + k:t1 + k]).sum(dim=(0, 1)) for k in range(KS)], dim=1)
+    return (torch.flip(dw, dims=[1]) if mutant == DWCONV_MUTANTS[1] else dw), db
+
+
+# (M, C, mean / std): 2 = the smallest batch nn.BatchNorm1d trains on; 129 = one row past a 128-row block of the vector route
+# (C 256: 4 row lanes, C 64: 16, C 512: 2); C 192 / 384 take the scalar route (256-row blocks); 4101 rows = 33 partials, 20011 = 79
+COLSTAT_ROWS = [(2, 256, 0), (129, 256, 0), (129, 256, 8), (129, 256, 64), (257, 192, 0), (257, 192, 8), (257, 192, 64),
+                (300, 64, 1), (4101, 512, 1), (4101, 512, 64), (20011, 384, 8)]
+BNBWD_ROWS = [r for r in COLSTAT_ROWS if r[2] in (0, 8)]
+BNBWD_16BIT_ROWS = [(129, 256, 8), (257, 192, 8)]                 # one vector row, one scalar row
+_case_cache = {}
+
+
+def _cached(fn):
+    def wrapped(*key):
+        k = (fn.__name__,) + key
+        if k not in _case_cache:
+            _case_cache[k] = fn(*key)
+        return _case_cache[k]
+    return wrapped
+
+
+def sum_terms_bound(n_ops, terms_abs_sum):
+    """n 2^-24 sum|terms|: forward bound of an fp32 sum of n_ops roundings per term chain, in any order"""
+    return n_ops * U32 * terms_abs_sum
+
+
+@_cached
+def colstat_case(row):
+    """y = std randn + (mean / std) std with a per-channel std in [0.5, 2] and a per-channel sign of the offset; float64 and
+    float32 evaluations of bn_stats64 / bn_finalize64 (training and eval) and the any-order sum bounds of the mean and of the
+    raw moments from their own terms.  The variance and the running variance have none: their terms (y - mean)^2 are all
+    non-negative, so n 2^-24 sum|terms| is n 2^-24 of the value itself - 1.2e-3 at M 20 011, wide enough to admit the
+    cancellation of sum y^2 / M - mean^2 that the rows are there to catch.  They are held to K_SUM x e32 of the two-pass
+    formula alone."""
+    M, C, ratio = row
+    f64, f32 = torch.float64, torch.float32
+    std = 0.5 + 1.5 * (arr("cs_s", (C,), M + C).abs().clamp(max=3.0) / 3.0)
+    sign = torch.where(arr("cs_g", (C,), M + C + 1) >= 0, 1.0, -1.0)
+    y = (arr("cs_y", (M, C), M + C + 2) * std + sign * ratio * std).float()
+    gamma, beta = arr("cs_ga", (C,), M + 3) * 0.1 + 1, arr("cs_be", (C,), M + 4) * 0.1
+    rm0, rv0 = arr("cs_rm", (C,), M + 5) * 0.5, arr("cs_rv", (C,), M + 6).abs() + 0.5
+    y64 = y.double()
+    m64, v64 = bn_stats64(y64)
+    m32, v32 = bn_stats64(y)
+    n = M + 3                                                    # M - 1 additions, the subtraction, the product, the division
+    bm = sum_terms_bound(n, y64.abs().sum(0)) / M
+    braw = torch.stack([sum_terms_bound(n, y64.abs().sum(0)), sum_terms_bound(n, (y64 * y64).sum(0))], dim=1)
+
+    def fin(dt, eval_mode, mutant=None, stats=None):
+        return bn_finalize64(y.to(dt), gamma.to(dt), beta.to(dt), rm0.to(dt), rv0.to(dt), BN_EPS, BN_MOMENTUM, eval_mode, mutant, stats)
+    c = dict(y=y, gamma=gamma, beta=beta, rm0=rm0, rv0=rv0, mean64=m64, var64=v64, mean32=m32, var32=v32, mean_bound=bm,
+             raw64=torch.stack([y64.sum(0), (y64 * y64).sum(0)], dim=1),
+             raw32=torch.stack([seq_sum(y), seq_sum(y * y)], dim=1), raw_bound=braw, fin=fin,
+             fin64=fin(f64, False, stats=(m64, v64)), fin32=fin(f32, False, stats=(m32, v32)),
+             fin64_eval=fin(f64, True), fin32_eval=fin(f32, True),
+             run_mean_bound=BN_MOMENTUM * bm)                   # the running mean moves by momentum x the batch mean
+    return c
+
+
+FIN_NAMES = ("mean", "rstd", "sc", "sh", "running mean", "running var")
+
+
+@_cached
+def bnbwd_case(row, eval_mode, g_dtype=None):
+    """cotangent g (rounded to g_dtype first, when given: both sides see the same 16-bit values), statistics as the forward
+    hands them over (fp32 roundings of the float64 batch statistics, or the running ones), dy / dgamma / dbeta in float64 and
+    float32 and the sum bounds of dgamma / dbeta from the reference's own terms"""
+    M, C, _ = row
+    c = colstat_case(row)
+    g = arr("bb_g", (M, C), M + C + 9)
+    if g_dtype is not None:
+        g = g.to(g_dtype).float()
+    fin = c["fin64_eval"] if eval_mode else c["fin64"]
+    mean, rstd = fin[0].float(), fin[1].float()
+    ev = lambda dt, mutant=None, em=eval_mode: bn_swish_bwd64(g.to(dt), c["y"].to(dt), mean.to(dt), rstd.to(dt), c["gamma"].to(dt),
+                                                               c["beta"].to(dt), em, mutant)
+    y64 = c["y"].double()
+    xh = (y64 - mean.double()) * rstd.double()
+    t = xh * c["gamma"].double() + c["beta"].double()
+    sg = torch.sigmoid(t)
+    dt_ = (g.double() * sg * (1 + t * (1 - sg))).abs()
+    n = M + 8                                                    # M - 1 additions behind ~8 roundings of each term
+    return dict(g=g, mean=mean, rstd=rstd, ref64=ev(torch.float64), ref32=ev(torch.float32), ev=ev,
+                dbeta_bound=sum_terms_bound(n, dt_.sum(0)), dgamma_bound=sum_terms_bound(n, (dt_ * xh.abs()).sum(0)))
+
+
+# (B, T, C, KS) -> reduce levels of the partial sums (32 partials per level): LDS kernel at the old shape; T 1; T < k; 52
+# partials (two levels, a second chunk of 20); generic <31> kernel with a half-empty second channel block and 39 partials
+# (a remainder of 7 = 4 + 3); 1040 partials (three levels); C even but no multiple of 4; 4 active threads
+DWGRAD_ROWS = [(3, 50, 256, 31), (1, 1, 256, 31), (2, 7, 512, 31), (2, 801, 256, 31), (3, 400, 384, 31), (40, 832, 64, 7),
+               (3, 33, 130, 7), (2, 20, 8, 7)]
+DWGRAD_PARTS = {(3, 50, 256, 31): (6, 1), (1, 1, 256, 31): (1, 1), (2, 7, 512, 31): (2, 1), (2, 801, 256, 31): (52, 2),
+                (3, 400, 384, 31): (39, 2), (40, 832, 64, 7): (1040, 3), (3, 33, 130, 7): (6, 1), (2, 20, 8, 7): (2, 1)}
+
+
+def dwgrad_parts(row):
+    """(partials, reduce levels) of a row from the library's own scratch size (a host function: no GPU needed)"""
+    from sincformer_metacog_speech_enhancement_amd import lib
+    B, T, C, KS = row
+    n = int(lib.load().sfm_dwconv_wgrad_scratch_floats(B, T, C, KS)) // ((KS + 1) * C)
+    levels, m = 1, n
+    while m > 32:
+        m, levels = -(-m // 32), levels + 1
+    return n, levels
+
+
+@_cached
+def dwgrad_case(row, dt16):
+    """x rounded to the 16-bit format before both sides see it, dy fp32.  Both carry an offset (x + 2, dy + 2): the sums over
+    B x T frames then do not cancel, and the any-order sum bound (n 2^-24 sum|terms|, ~ n 2^-24 of the value instead of
+    n^1/2 times more) still sees a dropped chunk of partials at 33 282 frames"""
+    B, T, C, KS = row
+    x = (arr("dg_x", (B, T, C), T + C) + 2.0).to(dt16).float()
+    dy = arr("dg_g", (B, T, C), T + C + 1) + 2.0
+    ev = lambda dt, mutant=None, nparts=None: dwconv_wgrad64(x.to(dt), dy.to(dt), KS, mutant, nparts)
+    xa, ga = x.double().abs(), dy.double().abs()
+    mag = dwconv_wgrad64(xa, ga, KS)
+    n = B * T + 2
+    return dict(x=x, dy=dy, ref64=ev(torch.float64), ref32=ev(torch.float32), ev=ev,
+                dw_bound=sum_terms_bound(n, mag[0]), db_bound=sum_terms_bound(n, mag[1]))
+
+
+DWFOLD_ROWS = [(2, 200, 256, 31), (3, 7, 64, 7), (1, 1, 256, 31), (2, 801, 384, 31)]
+
+
+@_cached
+def dwfold_case(row, dt16):
+    """forward: conv + bias with the forward taps; backward: the input gradient of dwconv64 (torch autograd) for a cotangent
+    rounded to the 16-bit format, which the kernel forms with the flipped taps and a zero bias"""
+    B, T, C, KS = row
+    x = arr("df_x", (B, T, C), T + C).to(dt16).float()
+    w = arr("df_w", (C, KS), T + C + 1) / math.sqrt(KS)
+    bias = arr("df_b", (C,), T + C + 2) * 0.1
+    gy = arr("df_g", (B, T, C), T + C + 3).to(dt16).float()
+    fwd = lambda dt, mutant=None: dwconv64(x.to(dt), w.to(dt), bias.to(dt), mutant)
+    bwd = lambda dt, mutant=None: _grad(lambda xx: (dwconv64(xx, w.to(dt), bias.to(dt), mutant) * gy.to(dt)).sum(), x.to(dt))[0]
+    n = KS + 2
+    wa = w.double().abs()
+    bf = sum_terms_bound(n, dwconv64(x.double().abs(), wa, bias.double().abs()))
+    bb = sum_terms_bound(n, dwconv64(gy.double().abs(), torch.flip(wa, dims=[1]), torch.zeros(C, dtype=torch.float64)))
+    return dict(x=x, w=w, bias=bias, gy=gy, fwd=fwd, bwd=bwd, fwd64=fwd(torch.float64), fwd32=fwd(torch.float32),
+                bwd64=bwd(torch.float64), bwd32=bwd(torch.float32), fwd_bound=bf, bwd_bound=bb)
+
+
+def check_row16(name, got, ref64, ref32, k, dt16):
+    """a 16-bit output against the float64 reference, element by element: one rounding to nearest in the format - the unit
+    roundoff, 2^-8 of the element for bf16 (8 significant bits) and 2^-11 for fp16 (11), which tensor.to() itself reaches; half
+    of that is below what a correctly rounded result can meet - plus k x e32 (the max figure of the float32 evaluation, x
+    max|ref|)"""
+    rnd = 2.0 ** -8 if dt16 == torch.bfloat16 else 2.0 ** -11
+    r = ref64.detach().double()
+    e32 = figs(ref32, r)
+    allow = rnd * r.abs() + k * e32[1] * float(r.abs().max())
+    err = (torch.as_tensor(got).detach().cpu().double() - r).abs()
+    worst = float((err / allow).max())
+    print("ROW | %s | all | e32 %.2e %.2e | bound 1 rounding (%.2e of the element) + %g e32 | observed %.2f of the bound, max err %.2e"
+          % (name, e32[0], e32[1], rnd, k, worst, float(err.max())))
+    assert math.isfinite(worst) and worst <= 1.0, (name, worst)

@@ -575,3 +575,149 @@ def test_train_node_bounds_separate_plausible_wrong_answers():
                 if T == 1 and m == hp.HPREV_MUTANTS[0]:
                     continue                                     # one step: both halves are all zero either way
                 assert not torch.equal(hp.hprev_ref(h, B, T, H, dt, m), ref), (row, dt, m)
+
+
+# ---------------------------------------------------------------------------
+# ConvolutionModule: BatchNorm and depthwise nodes (the section of that name in tests/test_train_nodes_gpu.py)
+# ---------------------------------------------------------------------------
+def _pin64(name, got, ref, tol=1e-11):
+    import helpers as hp
+    e = hp.figs(got, ref)
+    print("%-60s restatement vs torch float64: rel rmse %.2e max/max %.2e" % (name, e[0], e[1]))
+    assert max(e) < tol, (name, e)
+
+
+def test_conv_node_restatements_are_torch_and_the_oracle():
+    """bn_stats64 / bn_finalize64 / bn_swish64 against F.batch_norm in float64 (its running-statistics update included) and the
+    oracle's batch_norm_train / batch_norm_eval / swish; bn_swish_bwd64 against autograd of the forward restatement; dwconv64
+    and dwconv_wgrad64 against F.conv1d and its autograd in float64"""
+    import helpers as hp
+    from sincformer_metacog_speech_enhancement_amd import build
+    build.build(verbose=False)                                   # hp.dwgrad_parts asks the library for its scratch size
+    f64 = torch.float64
+    for row in ((2, 256, 0), (129, 256, 8), (257, 192, 64), (300, 64, 1)):
+        M, C, _ = row
+        c = hp.colstat_case(row)
+        y, ga, be = c["y"].double(), c["gamma"].double(), c["beta"].double()
+        for eval_mode in (False, True):
+            rm, rv = c["rm0"].double().clone(), c["rv0"].double().clone()
+            ref = F.batch_norm(y, rm, rv, ga, be, training=not eval_mode, momentum=hp.BN_MOMENTUM, eps=hp.BN_EPS)
+            mean, rstd, sc, sh, nrm, nrv = c["fin"](f64, eval_mode)
+            tag = "%s eval=%s" % (row, eval_mode)
+            _pin64("bn_finalize64 folded affine " + tag, y * sc + sh, ref)
+            _pin64("bn_finalize64 mean / rstd " + tag, (y - mean) * rstd * ga + be, ref)
+            _pin64("bn_finalize64 running mean " + tag, nrm, rm)
+            _pin64("bn_finalize64 running var " + tag, nrv, rv)
+            _pin64("bn_swish64 " + tag, hp.bn_swish64(y, mean, rstd, ga, be), orc.swish(ref))
+            # autograd of the forward restatement: the statistics are functions of y in training, constants in eval mode
+            g = hp.bnbwd_case(row, eval_mode)["g"].double()
+            yy, gg, bb = (t.clone().requires_grad_(True) for t in (y, ga, be))
+            if eval_mode:
+                m_, r_ = mean, rstd
+            else:
+                m_ = yy.mean(0)
+                r_ = torch.rsqrt(((yy - m_) ** 2).mean(0) + hp.BN_EPS)
+            hp.bn_swish64(yy, m_, r_, gg, bb).backward(g)
+            dy, dga, dbe = hp.bn_swish_bwd64(g, y, mean, rstd, ga, be, eval_mode)
+            _pin64("bn_swish_bwd64 dy " + tag, dy, yy.grad)
+            _pin64("bn_swish_bwd64 dgamma " + tag, dga, gg.grad)
+            _pin64("bn_swish_bwd64 dbeta " + tag, dbe, bb.grad)
+        # the oracle's own parts, on [B, C, T] with B x T = M rows
+        y3 = c["y"].reshape(1, M, C).transpose(1, 2)
+        mean, rstd, sc, sh, _, _ = c["fin"](f64, False)
+        _pin("bn_swish64 = orc.swish(orc.batch_norm_train) %s" % (row,), hp.bn_swish64(y, mean, rstd, ga, be),
+             orc.swish(orc.batch_norm_train(y3, c["gamma"], c["beta"])).transpose(1, 2)[0])
+        mean, rstd, sc, sh, _, _ = c["fin"](f64, True)
+        _pin("bn_swish64 = orc.swish(orc.batch_norm_eval) %s" % (row,), hp.bn_swish64(y, mean, rstd, ga, be),
+             orc.swish(orc.batch_norm_eval(y3, c["gamma"], c["beta"], c["rm0"], c["rv0"])).transpose(1, 2)[0])
+    for row in ((3, 7, 64, 7), (1, 1, 256, 31), (2, 200, 256, 31), (3, 33, 130, 7)):
+        B, T, C, KS = row
+        x = arr("hx", (B, T, C), T).double().requires_grad_(True)
+        w = (arr("hw", (C, KS), T + 1) / math.sqrt(KS)).double().requires_grad_(True)
+        b = (arr("hb", (C,), T + 2) * 0.1).double().requires_grad_(True)
+        gy = arr("hg", (B, T, C), T + 3).double()
+        ref = F.conv1d(x.transpose(1, 2), w.unsqueeze(1), b, padding=(KS - 1) // 2, groups=C).transpose(1, 2)
+        ref.backward(gy)
+        _pin64("dwconv64 %s" % (row,), hp.dwconv64(x.detach(), w.detach(), b.detach()), ref.detach())
+        dw, db = hp.dwconv_wgrad64(x.detach(), gy, KS)
+        _pin64("dwconv_wgrad64 dw %s" % (row,), dw, w.grad)
+        _pin64("dwconv_wgrad64 db %s" % (row,), db, b.grad)
+        # the input gradient as _conv_bwd forms it: the same conv with the flipped taps and a zero bias
+        _pin64("dwconv64 with flipped taps = input gradient %s" % (row,),
+               hp.dwconv64(gy, torch.flip(w.detach(), dims=[1]), torch.zeros(C, dtype=f64)), x.grad)
+    for row in hp.DWGRAD_ROWS:                                   # the table the GPU rows assert against is the library's rule
+        assert hp.dwgrad_parts(row) == hp.DWGRAD_PARTS[row], (row, hp.dwgrad_parts(row))
+
+
+def test_conv_node_bounds_separate_plausible_wrong_answers():
+    """every wrong form of helpers' *_MUTANTS tuples moves the float64 reference by >= 5 x the bound of a row the GPU section
+    checks, on that row's own inputs (one MUTANT line each).
+
+    The one-pass variance (sum y^2 / M - mean^2 from fp32 sums in 128-row blocks) against the variance row's bound, K_SUM x e32:
+    inside it at mean/std 0 and 1 (0.1 .. 0.5 x: the sums do not cancel there, and it need not separate), 20 .. 34 x at
+    mean/std 8 up to M 257, 226 .. 1929 x at mean/std 64.  (20011, 384, 8) is the one row where 5 x is out of reach: the
+    one-pass error there, 2.9e-5, is only 8 x the e32 of the two-pass formula summed sequentially over 20 011 rows, so it
+    stands at 2.0 x the bound - outside it, which is what that row asserts."""
+    import helpers as hp
+    f64 = torch.float64
+    seen = set()
+    for row in hp.COLSTAT_ROWS:
+        M, C, ratio = row
+        c = hp.colstat_case(row)
+        one = hp.bn_stats64(c["y"], hp.BN_STATS_MUTANTS[0])
+        name = "col_stats variance %s" % (row,)
+        if ratio >= 8 and row != (20011, 384, 8):
+            hp.separates(name, hp.BN_STATS_MUTANTS[0], one[1].double(), c["var64"], c["var32"], hp.K_SUM)
+            seen.add(hp.BN_STATS_MUTANTS[0])
+        else:
+            _, b = hp.row_bound(c["var64"], c["var32"], hp.K_SUM)
+            m = hp.figs(one[1].double(), c["var64"])
+            x = min(m[0] / b[0], m[1] / b[1])
+            print("MUTANT | %s | %s | moves the reference by %.2f x the bound" % (name, hp.BN_STATS_MUTANTS[0], x))
+            assert (x > 1.0) if ratio >= 8 else (x < 1.0), (row, x)
+        if M > 300:
+            continue            # 1 / (M - 1) and the cases below are row-independent: the small rows carry them
+        fin64, fin32 = c["fin64"], c["fin32"]
+        for m in hp.BN_FINALIZE_MUTANTS:
+            wrong = c["fin"](f64, False, m, (c["mean64"], c["var64"]))
+            hp.separates("bn_finalize running var %s" % (row,), m, wrong[5], fin64[5], fin32[5], hp.K_SUM)
+            seen.add(m)
+    for row in hp.BNBWD_ROWS:
+        if row[0] > 300:
+            continue
+        for eval_mode in (False, True):
+            c = hp.bnbwd_case(row, eval_mode)
+            for m in hp.BN_BWD_MUTANTS:
+                if (m == hp.BN_BWD_MUTANTS[0]) != eval_mode and m != hp.BN_BWD_MUTANTS[2]:
+                    continue                                     # the correction exists in training only; eval has none to drop
+                w = c["ev"](f64, m)
+                name = "bn_swish_bwd %s eval=%s" % (row, eval_mode)
+                if m == hp.BN_BWD_MUTANTS[2]:
+                    hp.separates(name + " dgamma", m, w[1], c["ref64"][1], c["ref32"][1], hp.K_SUM, c["dgamma_bound"])
+                else:
+                    hp.separates(name + " dy", m, w[0], c["ref64"][0], c["ref32"][0], hp.K_TRANS)
+                seen.add(m)
+    for row in hp.DWGRAD_ROWS:
+        B, T, C, KS = row
+        nparts, levels = hp.DWGRAD_PARTS[row]
+        c = hp.dwgrad_case(row, torch.bfloat16)
+        for m in hp.DWGRAD_MUTANTS:
+            if (m == hp.DWGRAD_MUTANTS[0] and B == 1) or (m == hp.DWGRAD_MUTANTS[2] and nparts == B) or \
+                    (m == hp.DWGRAD_MUTANTS[3] and levels < 2) or (m == hp.DWGRAD_MUTANTS[1] and T == 1):
+                continue            # one utterance / one span per utterance / one reduce level / one frame (only the centre tap)
+            if B * T > 30000 and m in hp.DWCONV_MUTANTS:
+                continue            # 3 edge frames of 832, or the noise of 33 280 terms between two taps: under that row's any-order
+                                    # sum bound (n 2^-24 of the sum); the rows of up to 1602 frames carry these two
+            w = c["ev"](f64, m, nparts)
+            hp.separates("dwconv_wgrad %s" % (row,), m, w[0], c["ref64"][0], c["ref32"][0], hp.K_SUM, c["dw_bound"])
+            seen.add(m)
+    for row in hp.DWFOLD_ROWS:
+        B, T, C, KS = row
+        c = hp.dwfold_case(row, torch.float16)
+        for m in hp.DWCONV_MUTANTS:
+            if (m == hp.DWCONV_MUTANTS[0] and B == 1) or (m == hp.DWCONV_MUTANTS[1] and T == 1):
+                continue
+            hp.separates("dwconv_folded forward %s" % (row,), m, c["fwd"](f64, m), c["fwd64"], c["fwd32"], hp.K_SUM, c["fwd_bound"])
+            hp.separates("dwconv_folded input gradient %s" % (row,), m, c["bwd"](f64, m), c["bwd64"], c["bwd32"], hp.K_SUM,
+                         c["bwd_bound"])
+    assert seen == set(hp.BN_STATS_MUTANTS + hp.BN_FINALIZE_MUTANTS + hp.BN_BWD_MUTANTS + hp.DWGRAD_MUTANTS), seen

@@ -1,4 +1,5 @@
-"""Each fp32 streaming / reduction / recurrence node of the training path (objective, mask heads, glue, BiLSTM) called
+"""Each fp32 streaming / reduction / recurrence node of the training path (objective, mask heads, glue, BiLSTM, the
+BatchNorm and depthwise nodes of the ConvolutionModule) called
 directly and compared, element by element, with a float64 restatement of the same operation (helpers.py; pinned to the oracle
 and shown to separate wrong kernels by tests/test_host_logic.py).
 
@@ -403,3 +404,179 @@ if __name__ == "__main__":                                   # child of test_bil
     for _row in hp.BPTT_ROWS:
         if _row[2] == 128:
             _arm_a(_ops, _row, " <128, 8>")
+
+
+# ---------------------------------------------------------------------------
+# ConvolutionModule: BatchNorm and depthwise nodes
+# ---------------------------------------------------------------------------
+FORMS = [True, False]                                       # ops.set_deterministic: ordered fold of partials / fp32 atomics
+
+
+def _in_form(ops, deterministic, fn):
+    """fn() in one reduction form; the ordered form twice, bitwise equal; the switch goes back to what it was"""
+    before = ops.is_deterministic()
+    try:
+        ops.set_deterministic(deterministic)
+        out = fn()
+        if deterministic:
+            again = fn()
+            for i, (u, v) in enumerate(zip(out, again)):
+                assert torch.equal(u, v), ("ordered form is not bit-reproducible", i)
+        return out
+    finally:
+        ops.set_deterministic(before)
+
+
+def _stats(ops, y):
+    S, K = ops.col_stats_shifted(y)
+    return ops.col_stats(y), S, K
+
+
+@pytest.mark.parametrize("deterministic", FORMS, ids=["ordered", "atomics"])
+@pytest.mark.parametrize("row", hp.COLSTAT_ROWS, ids=_id)
+def test_batchnorm_statistics(ops, row, deterministic):
+    """col_stats_shifted (the pilot shift K, then the sums of y - K) against bn_stats64 (two passes, sequential): mean =
+    K + S0 / M and the biased variance S1 / M - (S0 / M)^2, formed in float64 from the kernels' sums.  Mean: K_SUM x e32 or the
+    any-order sum bound (M + 3) 2^-24 sum|y| / M where larger.  Variance: K_SUM x e32 alone (helpers.colstat_case says why it has
+    no sum bound): a variance from sum y^2 / M - mean^2 fails the mean/std 8 and 64 rows ((20011, 384, 8) in the atomics
+    form only: folded in order, 79 partials of 256 rows leave it 2.7 x e32).  The raw moments sum y, sum y^2 of
+    col_stats are bounded by their own terms."""
+    M, C, _ = row
+    c = hp.colstat_case(row)
+    y = dev(c["y"])
+    raw, S, K = (t.cpu().double() for t in _in_form(ops, deterministic, lambda: _stats(ops, y)))
+    name = "%s %s" % (_id(row), "ordered" if deterministic else "atomics")
+    hp.check_row("col_stats raw moments " + name, raw, c["raw64"], c["raw32"], hp.K_SUM, c["raw_bound"],
+                 {"sum y": lambda t: t[:, 0], "sum y^2": lambda t: t[:, 1]})
+    hp.check_row("col_stats mean " + name, K + S[:, 0] / M, c["mean64"], c["mean32"], hp.K_SUM, c["mean_bound"])
+    var = S[:, 1] / M - (S[:, 0] / M) ** 2
+    hp.check_row("col_stats variance " + name, var, c["var64"], c["var32"], hp.K_SUM)
+
+
+@pytest.mark.parametrize("deterministic", FORMS, ids=["ordered", "atomics"])
+@pytest.mark.parametrize("row", hp.COLSTAT_ROWS, ids=_id)
+def test_bn_finalize(ops, row, deterministic):
+    """col_stats_shifted -> bn_finalize against bn_finalize64: mean and the running statistics (unbiased variance,
+    momentum) at K_SUM x e32 (the two means or their sum bound where larger; the running variance, like the variance, has
+    none); rstd, sc, sh (behind rsqrt) at K_TRANS x e32.  Then eval mode: the statistics
+    are the running ones and the buffers keep their bits."""
+    M, C, _ = row
+    c = hp.colstat_case(row)
+    y, ga, be = dev(c["y"]), dev(c["gamma"]), dev(c["beta"])
+
+    def run():
+        rm, rv = dev(c["rm0"]).clone(), dev(c["rv0"]).clone()
+        S, K = ops.col_stats_shifted(y)
+        mean, rstd, sc, sh = ops.bn_finalize(S, K, ga, be, rm, rv, M, hp.BN_EPS, hp.BN_MOMENTUM)
+        return mean.clone(), rstd.clone(), sc.clone()[0], sh.clone()[0], rm, rv
+    got = [t.cpu() for t in _in_form(ops, deterministic, run)]
+    name = "%s %s" % (_id(row), "ordered" if deterministic else "atomics")
+    r64, r32 = c["fin64"], c["fin32"]
+    sums = {0: c["mean_bound"], 4: c["run_mean_bound"], 5: None}
+    for i, what in enumerate(hp.FIN_NAMES):
+        hp.check_row("bn_finalize %s %s" % (what, name), got[i], r64[i], r32[i], hp.K_SUM if i in sums else hp.K_TRANS, sums.get(i))
+    if deterministic:
+        rm, rv = dev(c["rm0"]).clone(), dev(c["rv0"]).clone()
+        out = ops.bn_finalize(None, None, ga, be, rm, rv, M, hp.BN_EPS, hp.BN_MOMENTUM, eval_mode=True)
+        got = [out[0].cpu(), out[1].cpu(), out[2][0].cpu(), out[3][0].cpu()]
+        assert torch.equal(rm.cpu(), c["rm0"]) and torch.equal(rv.cpu(), c["rv0"]), "eval mode moved the running statistics"
+        assert torch.equal(got[0], c["rm0"])
+        for i in (1, 2, 3):
+            hp.check_row("bn_finalize eval %s %s" % (hp.FIN_NAMES[i], _id(row)), got[i], c["fin64_eval"][i], c["fin32_eval"][i],
+                         hp.K_TRANS)
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("row", hp.BNBWD_ROWS, ids=_id)
+def test_bn_swish_forward(ops, row, dt):
+    """gn_apply(act=2) = Swish(y sc + sh) with the folded affine of the float64 statistics (C 192 / 384: the generic kernel,
+    else the row-walking one), 16-bit output: one rounding to nearest in the format (the unit roundoff: 2^-8 of the element
+    for bf16, 2^-11 for fp16) plus K_TRANS x e32 of the same folded formula"""
+    M, C, _ = row
+    ops.set_compute_dtype(dt)
+    c = hp.colstat_case(row)
+    sc, sh = c["fin64"][2].float(), c["fin64"][3].float()
+    ev = lambda d: (lambda t: t * torch.sigmoid(t))(c["y"].to(d) * sc.to(d) + sh.to(d))
+    out = torch.full((M, C), NAN, device="cuda", dtype=dt)
+    ops.gn_apply(dev(c["y"]), dev(sc.reshape(1, C)), dev(sh.reshape(1, C)), out, 1, M, C, act=2)
+    hp.check_row16("gn_apply swish %s %s" % (_id(row), dt), out.cpu(), ev(torch.float64), ev(torch.float32), hp.K_TRANS, dt)
+
+
+def _bn_bwd(ops, row, eval_mode, deterministic, g_dtype=None):
+    M, C, _ = row
+    c, b = hp.colstat_case(row), hp.bnbwd_case(row, eval_mode, g_dtype)
+    g = dev(b["g"] if g_dtype is None else b["g"].to(g_dtype))
+    args = [dev(t) for t in (c["y"], b["mean"], b["rstd"], c["gamma"], c["beta"])]
+    got = _in_form(ops, deterministic, lambda: ops.bn_swish_bwd(g, *args, eval_mode=eval_mode))
+    name = "%s eval=%s %s%s" % (_id(row), eval_mode, "ordered" if deterministic else "atomics", "" if g_dtype is None else " g %s" % g_dtype)
+    hp.check_row("bn_swish_bwd dy " + name, got[0].cpu(), b["ref64"][0], b["ref32"][0], hp.K_TRANS)
+    hp.check_row("bn_swish_bwd dgamma " + name, got[1].cpu(), b["ref64"][1], b["ref32"][1], hp.K_SUM, b["dgamma_bound"])
+    hp.check_row("bn_swish_bwd dbeta " + name, got[2].cpu(), b["ref64"][2], b["ref32"][2], hp.K_SUM, b["dbeta_bound"])
+
+
+@pytest.mark.parametrize("deterministic", FORMS, ids=["ordered", "atomics"])
+@pytest.mark.parametrize("eval_mode", [False, True], ids=["train", "eval"])
+@pytest.mark.parametrize("row", hp.BNBWD_ROWS, ids=_id)
+def test_bn_swish_bwd(ops, row, eval_mode, deterministic):
+    """dy, dgamma, dbeta against bn_swish_bwd64 (= autograd of Swish(BatchNorm(y)); test_host_logic) with the statistics the
+    forward hands over: dy (behind the sigmoid) at K_TRANS x e32; the reductions dgamma / dbeta at K_SUM x e32 or their sum
+    bound (M + 8) 2^-24 sum|terms| where larger.  eval mode: no batch-statistics correction in dy"""
+    _bn_bwd(ops, row, eval_mode, deterministic)
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("row", hp.BNBWD_16BIT_ROWS, ids=_id)
+def test_bn_swish_bwd_16bit_cotangent(ops, row, dt):
+    """a 16-bit g (the kernel accepts one): both sides see the same rounded values, so the fp32 bounds hold unchanged"""
+    ops.set_compute_dtype(dt)
+    _bn_bwd(ops, row, False, True, dt)
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("row", hp.DWGRAD_ROWS, ids=_id)
+def test_dwconv_wgrad(ops, row, dt):
+    """dw, db against dwconv_wgrad64 at K_SUM x e32 or the sum bound (B T + 2) 2^-24 sum|terms|; the row has the partial count
+    and the reduce levels it is there for; two runs give the same bits"""
+    B, T, C, KS = row
+    ops.set_compute_dtype(dt)
+    assert hp.dwgrad_parts(row) == hp.DWGRAD_PARTS[row], (row, hp.dwgrad_parts(row))
+    c = hp.dwgrad_case(row, dt)
+    x, dy = dev(c["x"].to(dt)), dev(c["dy"])
+    dw, db = ops.dwconv_wgrad(x, dy, B, T, C, KS)
+    dw2, db2 = ops.dwconv_wgrad(x, dy, B, T, C, KS)
+    assert torch.equal(dw, dw2) and torch.equal(db, db2), "not bit-reproducible"
+    hp.check_row("dwconv_wgrad dw %s %s" % (_id(row), dt), dw.cpu(), c["ref64"][0], c["ref32"][0], hp.K_SUM, c["dw_bound"])
+    hp.check_row("dwconv_wgrad db %s %s" % (_id(row), dt), db.cpu(), c["ref64"][1], c["ref32"][1], hp.K_SUM, c["db_bound"])
+
+
+def test_dwconv_wgrad_accumulates_once(ops):
+    """a non-zero dw / db going in comes out as start + gradient, the start added exactly once (two reduce levels)"""
+    row, dt = (2, 801, 256, 31), torch.float16
+    B, T, C, KS = row
+    ops.set_compute_dtype(dt)
+    c = hp.dwgrad_case(row, dt)
+    x, dy = dev(c["x"].to(dt)), dev(c["dy"])
+    dw0, db0 = ops.dwconv_wgrad(x, dy, B, T, C, KS)
+    sw, sb = dev(arr("dg_sw", (C, KS), 5) * 100.0), dev(arr("dg_sb", (C,), 6) * 100.0)
+    dw, db = ops.dwconv_wgrad(x, dy, B, T, C, KS, dw=sw.clone(), db=sb.clone())
+    assert torch.equal(dw, sw + dw0) and torch.equal(db, sb + db0)
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("row", hp.DWFOLD_ROWS, ids=_id)
+def test_dwconv_folded_fp32_out(ops, row, dt):
+    """the forms of the training path, fp32 out, act 0: conv + bias with the forward taps against dwconv64, and the input
+    gradient (flipped taps, zero bias, a 16-bit cotangent) against autograd of dwconv64; K_SUM x e32 or the sum bound
+    (KS + 2) 2^-24 sum|terms|"""
+    B, T, C, KS = row
+    ops.set_compute_dtype(dt)
+    c = hp.dwfold_case(row, dt)
+    ones, zeros = torch.ones(C, device="cuda"), torch.zeros(C, device="cuda")
+    out = torch.full((B * T, C), NAN, device="cuda")
+    ops.dwconv_folded(dev(c["x"].to(dt)), dev(c["w"].t()), ones, dev(c["bias"]), B, T, C, out=out, act=0)
+    hp.check_row("dwconv_folded forward %s %s" % (_id(row), dt), out.cpu().reshape(B, T, C), c["fwd64"], c["fwd32"], hp.K_SUM,
+                 c["fwd_bound"])
+    out = torch.full((B * T, C), NAN, device="cuda")
+    ops.dwconv_folded(dev(c["gy"].to(dt)), dev(torch.flip(c["w"], dims=[1]).t()), ones, zeros, B, T, C, out=out, act=0)
+    hp.check_row("dwconv_folded input gradient %s %s" % (_id(row), dt), out.cpu().reshape(B, T, C), c["bwd64"], c["bwd32"], hp.K_SUM,
+                 c["bwd_bound"])
