@@ -630,6 +630,42 @@ int sfm_curriculum_mask(const float* cr, const float* ci, const float* nr, const
                         const double* table, float* yr, float* yi, float* mask, int B, int T, int F, int kind, float p, float eps,
                         int M, void* stream);
 
+/* The PSO search of OPT-PCIRM's middle step with the STOI fallback as fitness (masks/opt_pcirm.py:101-202, optimizer/pso.py,
+ * evaluation/stoi.py:53-99), one swarm of N particles per utterance (csrc/pso.hip).  B <= 65535, 1 <= N <= 256, M in 2..16,
+ * max_iter >= 1 (SFM_ERR_SHAPE outside).  No atomics: the same bits from run to run and for an utterance alone or in a batch.
+ * sfm_pso_frame_coef: pcirm [B, C, T] fp32, table as sfm_mask_quantize takes it -> a, b [B, T] doubles: the channel mean of
+ *   the mask's frame n quantised with the middle value x is a[n] + x b[n] (bucket membership compared in double, assigned values
+ *   rounded to fp32; M < 3: b = 0, the middle value is unused).
+ * sfm_pso_split: noisy, clean [B, Lmax]; lengths int32 [B]; samp_off int32 [B + 1] = the running sum of the lengths.  Mask frames
+ *   of `frame` samples every `hop` (frame >= hop), frame n < T covering [n hop, min(n hop + frame, length)), overlap-added and
+ *   divided by max(count, 1) give the gains ga, gb.  Writes ya = noisy ga, yb = noisy gb and clean, each utterance's samples
+ *   at samp_off[b] (packed, fp32), and S [B, 4] = {sum ya^2, sum ya yb, sum yb^2, sum clean^2}: one fp64 partial per 4096
+ *   samples, folded in index order.  ws >= 4 * B * ceil(Lmax / 4096) doubles.
+ * sfm_pso_fitness: packed spectra rows [sum_frames, F] (F <= 1024) of clean, ya, yb; frame_off int32 [B + 1].  For each
+ *   utterance whose stopped[b] is 0 and each of its N positions x (rounded to fp32): the clipped frame correlations of
+ *   clean / rms against (ya + x yb) / rms, summed over chunks of 8 frames: partial [B, NC, N], NC >= ceil(frames / 8) of every
+ *   utterance; only an utterance's own chunks are written.
+ * sfm_pso_step: round `it` of the search (0: optimizer/pso.py:92-110; 1..max_iter: one iteration, :114-179) for every swarm
+ *   whose stopped[b] is 0.  The fitness is clip(sum of the partials in chunk order / frames, 0, 1) (0 without a frame), or
+ *   `fitness` [B, N] handed in (exactly one of partial / fitness is non-NULL).  params = {w, c1, c2, lb, ub}; draws [B, 2 N +
+ *   2 N max_iter]: initial positions, initial velocities, then (r1, r2) per iteration and particle.  Updates pbest and gbest
+ *   [B, 2] = {position, fitness}, writes row `it` of hist [B, max_iter + 1, 3 + 2 N] = {gbest fitness, gbest position, mean
+ *   fitness, position[N], fitness[N]}, iters[b] = it, stopped[b] = 1 once np.std(positions) < 1e-6, and unless stopped or
+ *   it == max_iter moves pos / vel to the next iteration's.  The caller sets pos / vel to the first 2 N draws before round 0.
+ * sfm_pso_quantize: sfm_mask_quantize over [B, CT] with middle[b] (double, rounded to fp32) as step 2's value when M >= 3. */
+int sfm_pso_frame_coef(const float* pcirm, const double* table, double* a, double* b, int B, int C, int T, int M, void* stream);
+int sfm_pso_split(const float* noisy, const float* clean, const int* lengths, const int* samp_off, const double* a,
+                  const double* b, float* ya, float* yb, float* clean_packed, double* ws, double* S, int B, int Lmax, int T,
+                  int frame, int hop, void* stream);
+int sfm_pso_fitness(const float* cr, const float* ci, const float* ar, const float* ai, const float* br, const float* bi,
+                    const int* frame_off, const int* lengths, const double* S, const double* pos, const int* stopped,
+                    double* partial, int B, int N, int F, int NC, void* stream);
+int sfm_pso_step(const double* partial, const double* fitness, const int* frame_off, const double* draws, const double* params,
+                 double* pos, double* vel, double* pbest_pos, double* pbest_fit, double* gbest, double* hist, int* iters,
+                 int* stopped, int B, int N, int NC, int it, int max_iter, int maximize, void* stream);
+int sfm_pso_quantize(const float* pcirm, const double* table, const double* middle, float* out, int B, long long CT, int M,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

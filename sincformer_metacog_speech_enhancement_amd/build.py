@@ -22,7 +22,9 @@ FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-u
 # VALU instructions; the default AGPR placement costs ~220 v_accvgpr moves per key tile)
 # -fno-honor-nans: row maxima of the online softmax compile to bare v_max3_f32 (see attention.hip)
 EXTRA = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-nans"],
-         "attention_pipe.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-nans"]}
+         "attention_pipe.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-nans"],
+         # the swarm's float64 recurrences equal numpy's bit for bit: no multiply-add is fused
+         "pso.hip": ["-ffp-contract=off"]}
 
 
 def _newer(src, dst, deps):

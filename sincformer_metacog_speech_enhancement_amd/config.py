@@ -31,6 +31,14 @@ MAA_THRESHOLD_INIT = 0.5
 OPT_NUM_STEPS = 3
 LOCAL_CRITERION_DB = -15
 
+# the swarm that searches OPT-PCIRM's middle step (config.py:81-86 of the reference)
+PSO_NUM_PARTICLES = 30
+PSO_MAX_ITER = 100
+PSO_W = 0.7
+PSO_C1 = 1.5
+PSO_C2 = 1.5
+PSO_BOUNDS = (0.0, 1.0)
+
 # curriculum stages in epochs (config.py:120-122 of the reference)
 CURRICULUM_STAGE1_EPOCHS = 15
 CURRICULUM_STAGE2_EPOCHS = 20

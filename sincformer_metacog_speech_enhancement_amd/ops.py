@@ -1211,6 +1211,119 @@ def curriculum_mask(cr, ci, nr, ni, scale, kind=None, p=0.5, eps=1e-10, table=No
     return yr, yi, mask
 
 
+# ---------------------------------------------------------------------------
+# the PSO search of OPT-PCIRM's middle step (csrc/pso.hip)
+# ---------------------------------------------------------------------------
+PSO_CHUNK = 4096                    # samples per workgroup of sfm_pso_split
+PSO_FRAMES = 8                      # STOI frames per workgroup of sfm_pso_fitness
+PSO_MAX_PARTICLES = 256
+PSO_MAX_BINS = 1024
+
+
+def _pso_is(t, dtype, numel):
+    return t.dtype == dtype and t.is_contiguous() and t.numel() == numel
+
+
+def pso_frame_coef(pcirm, table, M):
+    """pcirm [B, C, T] fp32 contiguous, table of masks.opt_pcirm.quantizer_table -> (a, b) [B, T] fp64: the channel mean of mask
+    frame n quantised with the middle value x is a[n] + x b[n]"""
+    _need_dev(pcirm, table)
+    L = _lib.load()
+    if pcirm.dim() != 3 or not _pso_is(pcirm, torch.float32, pcirm.numel()) or pcirm.numel() == 0 or \
+            not 2 <= M <= QUANT_MAX_STEPS or not _pso_is(table, torch.float64, 2 * M + 1):
+        _lib.check(-2, "pso_frame_coef")
+    B, C, T = pcirm.shape
+    a = torch.empty(B, T, device=pcirm.device, dtype=torch.float64)
+    b = torch.empty(B, T, device=pcirm.device, dtype=torch.float64)
+    _call("pso_prepare", L.sfm_pso_frame_coef, (_p(pcirm), _p(table), _p(a), _p(b), B, C, T, int(M), _stream()), 0.0,
+          4.0 * B * C * T + 16.0 * B * T, "coef B%d C%d T%d" % (B, C, T))
+    return a, b
+
+
+def pso_split(noisy, clean, lengths, samp_off, a, b, sum_L, frame, hop):
+    """noisy, clean [B, Lmax] fp32; lengths int32 [B]; samp_off int32 [B + 1]; a, b [B, T] -> (ya, yb, clean) packed [sum_L] fp32
+    and S [B, 4] fp64 = {sum ya^2, sum ya yb, sum yb^2, sum clean^2} (two launches: chunk sums, then the ordered fold)"""
+    _need_dev(noisy, clean, lengths, samp_off, a, b)
+    L = _lib.load()
+    B, Lmax = noisy.shape
+    T = a.shape[-1]
+    ok = _pso_is(noisy, torch.float32, B * Lmax) and _pso_is(clean, torch.float32, B * Lmax) and Lmax > 0
+    ok = ok and _pso_is(lengths, torch.int32, B) and _pso_is(samp_off, torch.int32, B + 1)
+    ok = ok and _pso_is(a, torch.float64, B * T) and _pso_is(b, torch.float64, B * T) and 0 < hop <= frame
+    if not ok:
+        _lib.check(-2, "pso_split")
+    dev = noisy.device
+    ya, yb, cp = (torch.empty(max(int(sum_L), 1), device=dev, dtype=torch.float32) for _ in range(3))
+    S = torch.empty(B, 4, device=dev, dtype=torch.float64)
+    ws = _ws64(4 * B * ((Lmax + PSO_CHUNK - 1) // PSO_CHUNK), dev)
+    _call("pso_prepare", L.sfm_pso_split, (_p(noisy), _p(clean), _p(lengths), _p(samp_off), _p(a), _p(b), _p(ya), _p(yb), _p(cp),
+                                           _p(ws), _p(S), B, Lmax, T, int(frame), int(hop), _stream()),
+          8.0 * sum_L, 20.0 * sum_L + 16.0 * B * T, "split B%d L%d" % (B, Lmax))
+    return ya, yb, cp, S
+
+
+def pso_fitness(spectra, frame_off, lengths, S, pos, stopped, partial, sum_frames):
+    """spectra: (cr, ci, ar, ai, br, bi) packed rows [sum_frames, F] fp32; pos [B, N] fp64; partial [B, NC, N] fp64 receives one
+    sum of clipped frame correlations per (utterance, chunk of PSO_FRAMES frames, particle).  Each spectrum is read once."""
+    _need_dev(frame_off, lengths, S, pos, stopped, partial, *spectra)
+    L = _lib.load()
+    B, N = pos.shape
+    F = spectra[0].shape[-1]
+    NC = partial.shape[1]
+    ok = len(spectra) == 6 and all(_pso_is(s, torch.float32, spectra[0].numel()) for s in spectra)
+    ok = ok and spectra[0].numel() >= sum_frames * F and 1 <= N <= PSO_MAX_PARTICLES and 0 < F <= PSO_MAX_BINS
+    ok = ok and _pso_is(frame_off, torch.int32, B + 1) and _pso_is(lengths, torch.int32, B) and _pso_is(S, torch.float64, 4 * B)
+    ok = ok and _pso_is(pos, torch.float64, B * N) and _pso_is(stopped, torch.int32, B)
+    ok = ok and _pso_is(partial, torch.float64, B * NC * N) and NC * PSO_FRAMES >= 1
+    if not ok:
+        _lib.check(-2, "pso_fitness")
+    _call("pso_fitness", L.sfm_pso_fitness, tuple(_p(s) for s in spectra) + (_p(frame_off), _p(lengths), _p(S), _p(pos),
+                                                                              _p(stopped), _p(partial), B, N, F, NC, _stream()),
+          16.0 * sum_frames * F * N, 24.0 * sum_frames * F + 8.0 * B * NC * N, "B%d N%d F%d" % (B, N, F))
+    return partial
+
+
+def pso_step(state, it, partial=None, fitness=None, frame_off=None):
+    """round `it` of every swarm of `state` (optimizer.pso.SwarmState) that has not stopped: the fitness from the partials of
+    pso_fitness or handed in as [B, N] fp64, then optimizer/pso.py:92-110 (it = 0) or :114-179"""
+    s = state
+    _need_dev(partial, fitness, frame_off, s.draws, s.params, s.pos, s.vel, s.pbest_pos, s.pbest_fit, s.gbest, s.hist, s.iters,
+              s.stopped)
+    L = _lib.load()
+    B, N, K = s.B, s.N, s.max_iter
+    ok = 1 <= N <= PSO_MAX_PARTICLES and K >= 1 and 0 <= it <= K and (partial is None) != (fitness is None)
+    ok = ok and _pso_is(s.draws, torch.float64, B * (2 * N + 2 * N * K)) and _pso_is(s.params, torch.float64, 5)
+    ok = ok and all(_pso_is(t, torch.float64, B * N) for t in (s.pos, s.vel, s.pbest_pos, s.pbest_fit))
+    ok = ok and _pso_is(s.gbest, torch.float64, 2 * B) and _pso_is(s.hist, torch.float64, B * (K + 1) * (3 + 2 * N))
+    ok = ok and _pso_is(s.iters, torch.int32, B) and _pso_is(s.stopped, torch.int32, B)
+    NC = 0
+    if ok and partial is not None:
+        NC = partial.shape[1]
+        ok = frame_off is not None and _pso_is(frame_off, torch.int32, B + 1) and _pso_is(partial, torch.float64, B * NC * N)
+    if ok and fitness is not None:
+        ok = _pso_is(fitness, torch.float64, B * N)
+    if not ok:
+        _lib.check(-2, "pso_step")
+    _call("pso_step", L.sfm_pso_step, (_p(partial), _p(fitness), _p(frame_off), _p(s.draws), _p(s.params), _p(s.pos), _p(s.vel),
+                                       _p(s.pbest_pos), _p(s.pbest_fit), _p(s.gbest), _p(s.hist), _p(s.iters), _p(s.stopped), B, N,
+                                       NC, int(it), K, 1 if s.maximize else 0, _stream()),
+          12.0 * B * N, 8.0 * B * N * (NC + 10), "B%d N%d" % (B, N))
+
+
+def pso_quantize(pcirm, table, middle, M):
+    """quantize_pcirm over [B, ...] fp32 with middle[b] (fp64 [B]) as the value of step 2 of utterance b (M >= 3)"""
+    _need_dev(pcirm, table, middle)
+    L = _lib.load()
+    B = pcirm.shape[0]
+    n = _same_planes("pso_quantize", pcirm)
+    if not 2 <= M <= QUANT_MAX_STEPS or not _pso_is(table, torch.float64, 2 * M + 1) or not _pso_is(middle, torch.float64, B):
+        _lib.check(-2, "pso_quantize")
+    out = torch.empty_like(pcirm)
+    _call("mask_quantize", L.sfm_pso_quantize, (_p(pcirm), _p(table), _p(middle), _p(out), B, n // B, int(M), _stream()), 0.0,
+          8.0 * n)
+    return out
+
+
 def spec_sums(pr, pi, tr, ti, out=None):
     L = _lib.load()
     S = torch.zeros(4, device=pr.device, dtype=torch.float64) if out is None else out
