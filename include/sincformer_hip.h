@@ -666,6 +666,29 @@ int sfm_pso_step(const double* partial, const double* fitness, const int* frame_
 int sfm_pso_quantize(const float* pcirm, const double* table, const double* middle, float* out, int B, long long CT, int M,
                      void* stream);
 
+/* Gammatone T-F analysis (gammatone.hip; signal_processing/gammatone.py of the reference): a causal FIR bank of C <= 64 channels
+ * and K <= 2048 taps on the fp32 matrix cores and the per-frame power / centre-bin phase of get_tf_magnitudes from five sums per
+ * frame instead of an rfft.  sig [B, L] fp32; taps [K][64] fp32, tap-major, K a multiple of 8 (a bank is padded with zero rows), columns
+ * from C on zero; lengths int32 [B] or NULL (= L): samples from lengths[b] on read as 0.  B <= 65535.  wave64, no atomics: the same bits
+ * from run to run and for an utterance alone or in a batch.
+ * sfm_gammatone_fir: out [B, C, L] = sum_k taps[k][c] sig[b, m - k] (0 from lengths[b] on).
+ * sfm_gammatone_tf: the fused form.  nblocks = L / hop whole hop-blocks; tw [2][hop][64] = cos, sin of 2 pi (k_c t mod N) / N for
+ *   the block-local t; partial [B, nblocks, C, 5] = {sum y^2, sum y, sum (-1)^t y, sum y cos, sum y sin} of each block, summed in
+ *   fp64 in t order and rounded once.  hop even, 2..384, and (25344 + K + 128 hop) * 4 bytes of LDS <= 160 KiB (SFM_ERR_SHAPE
+ *   otherwise).  Blocks that start behind lengths[b] are not written.
+ * sfm_gammatone_moments: y [B, C, L] (sfm_gammatone_fir's) -> partial [B, T, C, 5]: the same five sums over the first w <= frame
+ *   samples of frame n = y[n hop .. n hop + frame), frame-local t; tw [2][w][64].  Frames that end behind lengths[b] are not written.
+ * sfm_gammatone_tf_finish: partial [B, P, C, 5] -> mag, phase and (unless NULL) re, im [B, C, T].  two = 1: frame n is rows n and
+ *   n + 1, the second times rot [2][64] = cos, sin of 2 pi (k_c hop mod N) / N; two = 0: row n alone.  mag = (N s2 + s1^2 + sp^2) / 2,
+ *   phase = atan2(im, re), in fp64 from the fp32 partials; everything from T_b = (lengths[b] - frame) / hop + 1 on is 0. */
+int sfm_gammatone_fir(const float* sig, const float* taps, const int* lengths, float* out, int B, int L, int C, int K, void* stream);
+int sfm_gammatone_tf(const float* sig, const float* taps, const float* tw, const int* lengths, float* partial, int B, int L, int C,
+                     int K, int hop, int nblocks, void* stream);
+int sfm_gammatone_moments(const float* y, const float* tw, const int* lengths, float* partial, int B, int L, int C, int T, int w,
+                          int frame, int hop, void* stream);
+int sfm_gammatone_tf_finish(const float* partial, const float* rot, const int* lengths, float* mag, float* phase, float* re,
+                            float* im, int B, int C, int T, int P, int two, int L, int frame, int hop, int N, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

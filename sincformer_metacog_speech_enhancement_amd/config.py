@@ -12,6 +12,10 @@ FRAME_SIZE = int(SAMPLE_RATE * FRAME_SIZE_MS / 1000)   # 160
 HOP_SIZE = FRAME_SIZE // 2                              # 80
 FFT_SIZE = 256
 NUM_CHANNELS = 64
+# the gammatone filterbank (config.py:26-28 of the reference)
+FREQ_LOW = 50
+FREQ_HIGH = 4000
+FILTER_ORDER = 4
 CONFORMER_NUM_BLOCKS = 6
 CONFORMER_D_MODEL = 256
 CONFORMER_NUM_HEADS = 4

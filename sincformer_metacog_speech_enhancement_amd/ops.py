@@ -33,6 +33,7 @@ _SWITCHES = {
     "steal_grads": ["SFM_STEAL_GRADS", False, False],       # optim.FlatAdamW's default for steal_grads=None
     # read by the library itself (csrc/lstm.hip), never by the package: listed so that it is reported
     "lstm_bwd_lpu": ["SFM_LSTM_BWD_LPU", 4, 4],
+    "gammatone_fused": [None, True, True],                  # set_gammatone_fused: hop-block sums inside the FIR kernel
 }
 for _sw in _SWITCHES.values():
     if _sw[0] is not None and _sw[0] in _os.environ:
@@ -1322,6 +1323,108 @@ def pso_quantize(pcirm, table, middle, M):
     _call("mask_quantize", L.sfm_pso_quantize, (_p(pcirm), _p(table), _p(middle), _p(out), B, n // B, int(M), _stream()), 0.0,
           8.0 * n)
     return out
+
+
+# ---------------------------------------------------------------------------
+# gammatone T-F analysis (csrc/gammatone.hip; signal_processing/gammatone.py)
+# ---------------------------------------------------------------------------
+GT_COLS = 64                        # channel columns of the tap and twiddle operands (C <= 64, zero beyond C)
+GT_ROWS = 384                       # samples per workgroup of sfm_gammatone_fir / sfm_gammatone_tf
+GT_MAX_TAPS = 2048
+GT_LDS_MAX = 160 * 1024
+
+
+def set_gammatone_fused(flag):
+    """get_tf_magnitudes on hop-blocks inside the FIR kernel (sfm_gammatone_tf) where the framing allows it; False = the FIR
+    bank's [B, C, L] result in HBM, then the moments pass over it (A/B testing)"""
+    _SWITCHES["gammatone_fused"][2] = bool(flag)
+
+
+def gammatone_tf_fits(K, hop):
+    """sfm_gammatone_tf takes K taps (a multiple of 8) and this hop: one hop-block fits the workgroup's rows and its LDS image fits"""
+    lds = 4 * (GT_ROWS + K + GT_ROWS * 65 + 2 * hop * GT_COLS)
+    return 8 <= K <= GT_MAX_TAPS and K % 8 == 0 and 2 <= hop <= GT_ROWS and hop % 2 == 0 and lds <= GT_LDS_MAX
+
+
+def _gt_bank(name, sig, taps, C, lengths):
+    """(B, L, K) of sig [B, L] fp32 and taps [K, 64] fp32: anything else is refused (-2) before the call"""
+    ok = sig.dim() == 2 and sig.dtype == torch.float32 and sig.is_contiguous() and sig.numel() > 0
+    ok = ok and taps.dim() == 2 and taps.shape[1] == GT_COLS and taps.dtype == torch.float32 and taps.is_contiguous()
+    ok = ok and 8 <= taps.shape[0] <= GT_MAX_TAPS and taps.shape[0] % 8 == 0 and 1 <= C <= GT_COLS and sig.shape[0] <= 65535
+    ok = ok and (lengths is None or (lengths.dtype == torch.int32 and lengths.numel() == sig.shape[0] and lengths.is_contiguous()))
+    if not ok:
+        _lib.check(-2, name)
+    return sig.shape[0], sig.shape[1], taps.shape[0]
+
+
+def gammatone_fir(sig, taps, C, lengths=None):
+    """sig [B, L], taps [K, 64] -> [B, C, L] = the causal FIR bank (0 from lengths[b] on)"""
+    _need_dev(sig, taps, lengths)
+    L_ = _lib.load()
+    B, L, K = _gt_bank("gammatone_fir", sig, taps, C, lengths)
+    out = torch.empty(B, C, L, device=sig.device, dtype=torch.float32)
+    _call("gammatone_fir", L_.sfm_gammatone_fir, (_p(sig), _p(taps), _p(lengths), _p(out), B, L, C, K, _stream()),
+          2.0 * B * L * C * K, 4.0 * B * L + 4.0 * K * GT_COLS + 4.0 * B * C * L, "B%d L%d C%d K%d" % (B, L, C, K))
+    return out
+
+
+def gammatone_tf(sig, taps, tw, C, hop, lengths=None):
+    """sig [B, L], taps [K, 64], tw [2, hop, 64] -> partial [B, L // hop, C, 5]: the five sums of every whole hop-block of the
+    filtered signal, which is never stored"""
+    _need_dev(sig, taps, tw, lengths)
+    L_ = _lib.load()
+    B, L, K = _gt_bank("gammatone_tf", sig, taps, C, lengths)
+    nblocks = L // hop if hop > 0 else 0
+    if not gammatone_tf_fits(K, hop) or nblocks < 1 or tw.dtype != torch.float32 or tuple(tw.shape) != (2, hop, GT_COLS) or \
+            not tw.is_contiguous():
+        _lib.check(-2, "gammatone_tf")
+    partial = torch.empty(B, nblocks, C, 5, device=sig.device, dtype=torch.float32)
+    n = float(B) * nblocks * hop
+    _call("gammatone_tf", L_.sfm_gammatone_tf, (_p(sig), _p(taps), _p(tw), _p(lengths), _p(partial), B, L, C, K, hop, nblocks,
+                                                _stream()),
+          n * C * (2.0 * K + 10.0), 4.0 * B * L + 4.0 * K * GT_COLS + 8.0 * hop * GT_COLS + 20.0 * B * nblocks * C,
+          "B%d L%d C%d K%d hop%d" % (B, L, C, K, hop))
+    return partial
+
+
+def gammatone_moments(y, tw, T, w, frame, hop, lengths=None):
+    """y [B, C, L] (gammatone_fir's), tw [2, w, 64] -> partial [B, T, C, 5]: the five sums of the first w samples of each frame"""
+    _need_dev(y, tw, lengths)
+    L_ = _lib.load()
+    ok = y.dim() == 3 and y.dtype == torch.float32 and y.is_contiguous() and y.numel() > 0 and y.shape[1] <= GT_COLS
+    ok = ok and tw.dtype == torch.float32 and tuple(tw.shape) == (2, w, GT_COLS) and tw.is_contiguous()
+    ok = ok and T >= 1 and 1 <= w <= frame and hop >= 1 and (T - 1) * hop + frame <= y.shape[2] and y.shape[0] <= 65535
+    ok = ok and (lengths is None or (lengths.dtype == torch.int32 and lengths.numel() == y.shape[0] and lengths.is_contiguous()))
+    if not ok:
+        _lib.check(-2, "gammatone_moments")
+    B, C, L = y.shape
+    partial = torch.empty(B, T, C, 5, device=y.device, dtype=torch.float32)
+    _call("gammatone_moments", L_.sfm_gammatone_moments, (_p(y), _p(tw), _p(lengths), _p(partial), B, L, C, T, w, frame, hop,
+                                                          _stream()),
+          10.0 * B * C * T * w, 4.0 * B * C * L + 8.0 * w * GT_COLS + 20.0 * B * T * C,
+          "B%d L%d C%d T%d w%d hop%d" % (B, L, C, T, w, hop))
+    return partial
+
+
+def gammatone_tf_finish(partial, rot, T, L, frame, hop, N, two, lengths=None, want_bins=False):
+    """partial [B, P, C, 5] -> (mag, phase[, re, im]) [B, C, T]; two: frame n = rows n, n + 1 (rot [2, 64] turns the second)"""
+    _need_dev(partial, rot, lengths)
+    L_ = _lib.load()
+    ok = partial.dim() == 4 and partial.shape[3] == 5 and partial.dtype == torch.float32 and partial.is_contiguous()
+    ok = ok and partial.shape[0] <= 65535 and partial.shape[2] <= GT_COLS and T >= 1 and partial.shape[1] >= T + (1 if two else 0)
+    ok = ok and N >= 2 and N % 2 == 0 and frame >= 1 and hop >= 1 and L >= frame and T <= (L - frame) // hop + 1
+    ok = ok and (not two or (rot is not None and rot.dtype == torch.float32 and tuple(rot.shape) == (2, GT_COLS) and rot.is_contiguous()))
+    ok = ok and (lengths is None or (lengths.dtype == torch.int32 and lengths.numel() == partial.shape[0] and lengths.is_contiguous()))
+    if not ok:
+        _lib.check(-2, "gammatone_tf_finish")
+    B, P, C, _ = partial.shape
+    outs = [torch.empty(B, C, T, device=partial.device, dtype=torch.float32) for _ in range(4 if want_bins else 2)]
+    re, im = (outs[2], outs[3]) if want_bins else (None, None)
+    n = float(B) * C * T
+    _call("gammatone_tf_finish", L_.sfm_gammatone_tf_finish, (_p(partial), _p(rot), _p(lengths), _p(outs[0]), _p(outs[1]), _p(re),
+                                                              _p(im), B, C, T, P, int(bool(two)), L, frame, hop, N, _stream()),
+          20.0 * n, 20.0 * B * C * (T + (1 if two else 0)) + 4.0 * n * len(outs), "B%d C%d T%d two%d" % (B, C, T, int(bool(two))))
+    return tuple(outs)
 
 
 def spec_sums(pr, pi, tr, ti, out=None):

@@ -1,0 +1,48 @@
+"""Mirror of the oracle-mask recipe of training/pipeline.py:153-197: the gammatone T-F analysis of the clean, noise and noisy
+waveforms (signal_processing/gammatone.py) into masks/ on the device.  The rest of that file (feature extraction, the cache, the
+DNN's Dataset with its clipping and nan_to_num) is not mirrored."""
+import torch
+
+from .. import masks
+from ..signal_processing import GammatoneFilterbank
+
+_default_gfb = []
+
+
+def gammatone_mask_target(clean, noise, noisy, mask_type, gfb=None, lengths=None):
+    """-> the [B, T, C] (1-D signals: [T, C]) target 'irm', 'pcirm' or 'opt_pcirm' (the fixed steps) of fp32 device waveforms
+    clean / noisy [B, L] and noise [B, Ln]; any other mask_type gives the IRM, as there.  The noise is used unscaled, trimmed or
+    zero-padded to L.  The three signals are analysed in one launch over a batch of 3 B.  lengths: the sample counts of a
+    zero-padded batch; frames from an utterance's T_b on are analysed as zeros.  No clipping and no nan_to_num is applied."""
+    if gfb is None:
+        if not _default_gfb:
+            _default_gfb.append(GammatoneFilterbank())
+        gfb = _default_gfb[0]
+    for name, t in (("clean", clean), ("noise", noise), ("noisy", noisy)):
+        if not torch.is_tensor(t) or t.dim() != clean.dim() or t.dim() not in (1, 2):
+            raise ValueError("gammatone_mask_target: %s must be a tensor [L] or [B, L] like clean" % name)
+    one_d = clean.dim() == 1
+    c, n, y = (t.reshape(1, -1) if one_d else t for t in (clean, noise, noisy))
+    B, L = c.shape
+    if y.shape != c.shape or n.shape[0] != B:
+        raise ValueError("gammatone_mask_target: clean %s, noise %s, noisy %s" % (tuple(c.shape), tuple(n.shape), tuple(y.shape)))
+    if n.shape[1] >= L:
+        n = n[:, :L]
+    else:
+        n = torch.nn.functional.pad(n, (0, L - n.shape[1]))
+    if lengths is not None:
+        lengths = torch.as_tensor(lengths).reshape(-1).repeat(3)
+    mag, ph = gfb.get_tf_magnitudes(torch.cat([c, n, y], dim=0), lengths=lengths)
+    clean_m, noise_m, noisy_m = mag[:B], mag[B:2 * B], mag[2 * B:]
+    clean_p, noise_p, noisy_p = ph[:B], ph[B:2 * B], ph[2 * B:]
+    if mask_type in ("pcirm", "opt_pcirm"):
+        rho_s, rho_n = masks.compute_correlation_coefficients(noisy_m, clean_m, noise_m)
+        phi1, phi2 = masks.compute_phase_differences(noisy_p, clean_p, noise_p)
+        mask = masks.compute_pcirm(clean_m, noise_m, rho_s, rho_n, phi1, phi2)
+        if mask_type == "opt_pcirm":
+            steps, _ = masks.compute_snr_boundaries()
+            mask = masks.quantize_pcirm(mask, steps)
+    else:
+        mask = masks.compute_irm(clean_m, noise_m)
+    mask = mask.transpose(1, 2).contiguous()
+    return mask[0] if one_d else mask

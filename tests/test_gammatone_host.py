@@ -1,0 +1,206 @@
+"""signal_processing/gammatone.py without a GPU: the host design against the reference's own values (tests/golden/
+g19_gammatone.npz, bit for bit), the float64 restatement of tests/gammatone_cases.py against the reference's magnitudes and
+phases, the five-sum form against the direct one, the block-rotation identity, the mutants that the GPU rows' bounds must
+reject, and the launch costs the new wrappers state (in the style of tests/test_launch_costs_host.py)."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import gammatone_cases as gc
+import helpers as hp
+from sincformer_metacog_speech_enhancement_amd import config, lib, ops
+from sincformer_metacog_speech_enhancement_amd.signal_processing import (GammatoneFilterbank, erb_bandwidth, erb_space,
+                                                                         gammatone_impulse_response)
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+F64, F32 = torch.float64, torch.float32
+
+
+@pytest.fixture(scope="module")
+def fixture():
+    return np.load(os.path.join(GOLDEN, "g19_gammatone.npz"))
+
+
+def test_config_values():
+    assert (config.FREQ_LOW, config.FREQ_HIGH, config.FILTER_ORDER) == (50, 4000, 4)
+
+
+def test_host_design_equals_the_reference_bitwise(fixture):
+    for name, kw in gc.BANKS.items():
+        b = GammatoneFilterbank(**kw)
+        assert b.center_freqs.dtype == np.float64 and np.array_equal(b.center_freqs, fixture[name + ".center_freqs"])
+        assert len(b.impulse_responses) == b.num_channels
+        assert all(len(ir) == int(fixture[name + ".taps"]) and ir.dtype == np.float64 for ir in b.impulse_responses)
+    b = gc.bank("default")
+    assert (b.num_channels, b.freq_low, b.freq_high, b.sample_rate, b.filter_order) == (64, 50, 4000, 8000, 4)
+    assert np.array_equal(erb_space(50, 4000, 64), fixture["default.center_freqs"])
+    assert np.array_equal(erb_bandwidth(b.center_freqs), fixture["erb_bandwidth"])
+    for c in (0, 31, 63):
+        assert np.array_equal(b.impulse_responses[c], fixture["default.ir%d" % c])
+        assert np.array_equal(gammatone_impulse_response(b.center_freqs[c], 8000), fixture["default.ir%d" % c])
+    assert len(gammatone_impulse_response(1000.0, 16000)) == 800 and len(gammatone_impulse_response(1000.0, 8000, 0.01)) == 80
+    assert b.cf_bins(256)[0] == int(b.center_freqs[0] * 256 / 8000) and b.cf_bins(256)[-1] == 128 and b.cf_bins(128)[-1] == 64
+
+
+@pytest.mark.parametrize("name", gc.GOLDEN_CASES)
+def test_float64_restatement_equals_the_reference(fixture, name):
+    a = gc.analysis(name, F64)
+    mag, phase = torch.from_numpy(fixture[name + ".mag"]), torch.from_numpy(fixture[name + ".phase"])
+    assert a["mag"].shape == mag.shape
+    rel = float((a["mag"] - mag).abs().max() / mag.abs().max())
+    # phases: wherever |S[cf_bin]| is not tiny: above 1e-6 of the plane's largest (the reference's fftconvolve leaves
+    # 1e-16 of the signal's largest value in y, so a bin below that has no phase there)
+    size = torch.sqrt(a["re"] ** 2 + a["im"] ** 2)
+    big = size > 1e-6 * size.max()
+    ang = float(gc.angular_distance(a["phase"], phase)[big].max())
+    print("REF | %s | magnitudes rel %.2e | phases %.2e rad over %d of %d units" % (name, rel, ang, int(big.sum()), big.numel()))
+    assert rel <= 1e-9 and ang <= 1e-9
+
+
+def test_float64_filter_equals_the_reference(fixture):
+    name, rows = gc.GOLDEN_FILTER
+    y = gc.analysis(name, F64)["y"][list(rows)]
+    ref = torch.from_numpy(fixture["filter." + name])
+    assert float((y - ref).abs().max() / ref.abs().max()) <= 1e-12
+
+
+@pytest.mark.parametrize("name", list(gc.CASES))
+def test_five_sum_form_equals_the_direct_form(name):
+    a = gc.analysis(name, F64)
+    for q in ("mag", "re", "im"):
+        scale = float(a[q].abs().max())
+        assert float((a["sums"][q] - a[q]).abs().max()) <= 1e-12 * scale, (name, q)
+    live = gc.live_units(a["norm"]) & (torch.sqrt(a["re"] ** 2 + a["im"] ** 2) > 1e-6 * a["norm"])
+    assert float(gc.angular_distance(a["sums"]["phase"], a["phase"])[live].max()) <= 1e-8
+
+
+@pytest.mark.parametrize("name", ["d240", "d1153", "k2403", "c1153"])
+def test_block_rotation_identity(name):
+    """two neighbouring hop-blocks, the second turned by exp(-2 pi i k hop / N), are the frame; the parity sum keeps its sign"""
+    _, bname, _, _, _, (frame, hop, N) = gc.CASES[name]
+    a = gc.analysis(name, F64)
+    bins = gc.bank(bname).cf_bins(N)
+    whole = gc.five_sums(gc.frames_of(a["y"], frame, hop), N, bins)
+    comb = gc.combine_blocks(a["blocks"], hop, N, bins)
+    assert comb.shape == whole.shape
+    for q in range(5):
+        assert float((comb[..., q] - whole[..., q]).abs().max()) <= 1e-12 * float(whole[..., q].abs().max()), (name, q)
+
+
+def test_phase_row_skips_at_most_one_percent():
+    for name in gc.CASES:
+        bound, keep, skipped = gc.phase_bound(name)
+        assert skipped <= 0.01 * keep.numel(), (name, skipped)
+
+
+def _bin_planes(a64, a, form):
+    n = a64["norm"]
+    src = a["sums"] if form == "sums" else a
+    return torch.stack([gc.normalised(src["re"], n), gc.normalised(src["im"], n)])
+
+
+# mutant -> (case, row): the GPU row whose bound must reject it
+MUTANT_ROWS = {"norot": ("d1153", "bins"), "noparity": ("d1153", "mag"), "hist128": ("d1153", "filter"), "cfbin+1": ("d1153", "bins"),
+               "parityflip": ("d1153", "mag"), "lastpartial": ("d239", "mag_padded")}
+
+
+@pytest.mark.parametrize("mutant", gc.MUTANTS)
+def test_gpu_bounds_reject_the_mutants(mutant):
+    name, row = MUTANT_ROWS[mutant]
+    a64, a32, bad = gc.analysis(name, F64), gc.analysis(name, F32), gc.analysis(name, F64, mutant)
+    if row == "filter":
+        hp.separates(row, mutant, bad["y"], a64["y"], a32["y"], gc.K)
+    elif row == "mag":
+        hp.separates(row, mutant, bad["sums"]["mag"], a64["mag"], a32["sums"]["mag"], gc.K)
+    elif row == "bins":
+        hp.separates(row, mutant, _bin_planes(a64, bad, "sums"), _bin_planes(a64, a64, "direct"), _bin_planes(a64, a32, "sums"),
+                     gc.K)
+    else:                                                    # the plane of a padded batch row: zeros from the utterance's T on
+        T = a64["mag"].shape[1] + 1
+        assert bad["sums"]["mag"].shape[1] == T
+        hp.separates(row, mutant, bad["sums"]["mag"], gc.padded(a64["mag"], T), gc.padded(a32["sums"]["mag"], T), gc.K)
+
+
+def test_router_rule():
+    assert ops.gammatone_tf_fits(400, 80) and ops.gammatone_tf_fits(800, 80) and ops.gammatone_tf_fits(2048, 80)
+    assert not ops.gammatone_tf_fits(400, 81) and not ops.gammatone_tf_fits(400, 400) and not ops.gammatone_tf_fits(401, 80)
+    assert not ops.gammatone_tf_fits(400, 160)              # the LDS image of a 160-sample hop does not fit: filter + moments
+    assert ops.switch("gammatone_fused") is True and "gammatone_fused" not in ops.variant_overrides()
+
+
+def test_host_tensors_and_bad_arguments_are_refused():
+    b = gc.bank("default")
+    x = torch.zeros(400)
+    for call in (lambda: b.filter(x), lambda: b.get_tf_magnitudes(x), lambda: b.filter_to_frames(x)):
+        with pytest.raises(RuntimeError, match="no CPU fallback"):
+            call()
+    with pytest.raises(TypeError):
+        b.filter(np.zeros(400, dtype=np.float32))
+    with pytest.raises(ValueError, match="64 x 2048"):
+        GammatoneFilterbank(num_channels=65)._taps("cpu")
+
+
+def test_entry_points_check_their_arguments_without_a_gpu():
+    """argument validation happens before any HIP call"""
+    import ctypes
+    from sincformer_metacog_speech_enhancement_amd import build
+    build.build(verbose=False)
+    L = lib.load()
+    one = ctypes.c_void_p(16)
+    assert L.sfm_gammatone_fir(None, one, None, one, 1, 400, 64, 400, None) == -1
+    assert L.sfm_gammatone_fir(one, one, None, one, 1, 400, 65, 400, None) == -2          # more than 64 channels
+    assert L.sfm_gammatone_fir(one, one, None, one, 1, 400, 64, 402, None) == -2          # K is no multiple of 8
+    assert L.sfm_gammatone_fir(one, one, None, one, 1, 400, 64, 2056, None) == -2         # more than 2048 taps
+    assert L.sfm_gammatone_tf(one, one, None, None, one, 1, 400, 64, 400, 80, 5, None) == -1
+    assert L.sfm_gammatone_tf(one, one, one, None, one, 1, 400, 64, 400, 81, 4, None) == -2  # odd hop
+    assert L.sfm_gammatone_tf(one, one, one, None, one, 1, 400, 64, 400, 160, 2, None) == -2  # the LDS image does not fit
+    assert L.sfm_gammatone_tf(one, one, one, None, one, 1, 400, 64, 400, 80, 6, None) == -2   # more blocks than samples
+    assert L.sfm_gammatone_moments(one, one, None, one, 1, 400, 64, 4, 200, 160, 80, None) == -2   # w > frame
+    assert L.sfm_gammatone_moments(one, one, None, one, 1, 400, 64, 5, 160, 160, 80, None) == -2   # frames run past L
+    assert L.sfm_gammatone_tf_finish(one, None, None, one, one, None, None, 1, 64, 4, 5, 1, 400, 160, 80, 256, None) == -1
+    assert L.sfm_gammatone_tf_finish(one, one, None, one, one, None, None, 1, 64, 4, 5, 1, 400, 160, 80, 255, None) == -2
+    assert L.sfm_gammatone_tf_finish(one, one, None, one, one, None, None, 1, 64, 4, 4, 1, 400, 160, 80, 256, None) == -2
+
+
+class _StubLib:
+    def __getattr__(self, symbol):
+        if not symbol.startswith("sfm_"):
+            raise AttributeError(symbol)
+        fn = lambda *args: 0
+        fn.__name__ = symbol
+        return fn
+
+
+@pytest.fixture
+def launches(monkeypatch):
+    rec = []
+
+    def record(name, fn, args, flops=0.0, nbytes=0.0, tag=None):
+        assert len(args) == len(lib.SIGNATURES[fn.__name__]), fn.__name__
+        rec.append((fn.__name__, name, flops, nbytes, tag))
+
+    monkeypatch.setattr(ops._lib, "load", lambda: _StubLib())
+    monkeypatch.setattr(ops, "_stream", lambda: None)
+    monkeypatch.setattr(ops, "_need_dev", lambda *ts: None)
+    monkeypatch.setattr(ops, "_call", record)
+    return rec
+
+
+def test_gammatone_costs(launches):
+    B, L, C, K, hop = 3, 2403, 64, 400, 80
+    sig, taps = torch.zeros(B, L), torch.zeros(K, 64)
+    y = ops.gammatone_fir(sig, taps, C)
+    p = ops.gammatone_tf(sig, taps, torch.zeros(2, hop, 64), C, hop)
+    assert y.shape == (B, C, L) and p.shape == (B, 30, C, 5)
+    ops.gammatone_tf_finish(p, torch.zeros(2, 64), 29, L, 160, hop, 256, True)
+    q = ops.gammatone_moments(y, torch.zeros(2, 200, 64), 35, 200, 200, 64)
+    ops.gammatone_tf_finish(q, None, 35, L, 200, 64, 256, False, want_bins=True)
+    assert launches == [
+        ("sfm_gammatone_fir", "gammatone_fir", 369100800.0, 1976740.0, "B3 L2403 C64 K400"),
+        ("sfm_gammatone_tf", "gammatone_tf", 373248000.0, 287396.0, "B3 L2403 C64 K400 hop80"),
+        ("sfm_gammatone_tf_finish", "gammatone_tf_finish", 111360.0, 159744.0, "B3 C64 T29 two1"),
+        ("sfm_gammatone_moments", "gammatone_moments", 13440000.0, 2082304.0, "B3 L2403 C64 T35 w200 hop64"),
+        ("sfm_gammatone_tf_finish", "gammatone_tf_finish", 134400.0, 241920.0, "B3 C64 T35 two0"),
+    ]
