@@ -689,6 +689,41 @@ int sfm_gammatone_moments(const float* y, const float* tw, const int* lengths, f
 int sfm_gammatone_tf_finish(const float* partial, const float* rot, const int* lengths, float* mag, float* phase, float* re,
                             float* im, int B, int C, int T, int P, int two, int L, int frame, int hop, int N, void* stream);
 
+/* Meddis inner hair cell (haircell.hip; signal_processing/haircell.py of the reference): x [N, L] fp32, one chain of L Euler steps in
+ * fp64 per row, every operation one IEEE double operation in the reference's order (no fused multiply-add), the three clamps kept.
+ * par fp64 [12] = {A, B, y, l, r, x, h, M, dt, q0, c0, w0}.  A wave stages 64 rows x 64 samples through LDS; no atomics.
+ * sfm_haircell: out [N, L] fp64 = h c[t], bit for bit the reference's process on the same fp32-valued input.
+ * sfm_haircell_frames: frames [N, T] fp64 = the mean of the firing rate over [n hop, n hop + frame), T = (L - frame) / hop + 1,
+ *   frame <= 2 hop (SFM_ERR_SHAPE otherwise), summed in t order; the rate signal is not stored.  Row i belongs to utterance i / C;
+ *   lengths int32 [N / C] or NULL (= L): a chain stops at lengths[b], frames from T_b = (lengths[b] - frame) / hop + 1 on are 0. */
+int sfm_haircell(const float* x, const double* par, double* out, int N, int L, void* stream);
+int sfm_haircell_frames(const float* x, const double* par, const int* lengths, double* frames, int N, int C, int L, int frame,
+                        int hop, int T, void* stream);
+
+/* The DNN front end (features.hip; signal_processing/features.py of the reference).  Rows are frames: row b T + n of utterance b,
+ * T_b = (lengths[b] - frame) / hop + 1 of them live (lengths int32 [B] or NULL = L); rows from T_b on are neither read nor written by
+ * sfm_cepstral / sfm_rasta (the caller zero-fills) and written as 0 by sfm_feature_context.  wave64, no atomics.
+ * sfm_cepstral: out[row ld_out + col_off + j] = sum_m dct[j][m] v[m], j < NC (NC = 0: v itself, j < M), v = compress(fb p),
+ *   fb [M][F] fp32 (NULL: p itself, M = F), M <= 64, F <= 257, NC <= 16, dct [NC][M] fp32.  in_mode 0: p = re^2 + im^2 of the spectrum row
+ *   in[row ld_in + f], in[row ld_in + im_off + f]; 1: its square root; 2: in = partial [B, P, F, 5] of sfm_gammatone_tf,
+ *   p[c] = (partial[b, bmul n + badd, c, 0] + partial[b, bmul n + badd + 1, c, 0]) / window.  compress 0: none, 1: log(v + 1e-10),
+ *   2: sign(v) |v|^(1/3); logarithm, cube root and DCT in fp64, the filterbank an fmaf chain in bin order.
+ * sfm_rasta: logb [B, T, M] fp32 -> lfilter([.2, .1, 0, -.1, -.2], [1, -.98]) per band along the utterance's T_b frames from a zero
+ *   state, exp, times eql [M], cube root, mean over the T_b frames in frame order, DCT rows dct [NC][M]; eql, dct and all of it fp64;
+ *   the NC coefficients go to out[row ld_out + col_off + k] of every live row of the utterance.
+ * sfm_feature_context: feat [B, T, D] -> out [B, T, (2 ctx + 1) D]: row n = rows clamp(n - ctx .. n + ctx, 0, T_b - 1) side by side;
+ *   with mean / std [(2 ctx + 1) D] fp32 (both or neither): nan / inf -> 0, then (f - mean) / std in fp64, then a clip to +-clip.  D even.
+ * sfm_rows_mean: out [B, N] = sum over n < T_b of in[(b T + n) ld_in + col_off + j] / (den > 0 ? den : T_b), fp64 in frame order. */
+int sfm_cepstral(const float* in, const float* fb, const float* dct, const int* lengths, float* out, int B, int T, int L, int frame,
+                 int hop, int in_mode, long long ld_in, int im_off, int F, int M, int NC, int compress, int P, int bmul, int badd,
+                 float window, long long ld_out, int col_off, void* stream);
+int sfm_rasta(const float* logb, const double* eql, const double* dct, const int* lengths, float* out, int B, int T, int L, int frame,
+              int hop, int M, int NC, long long ld_out, int col_off, void* stream);
+int sfm_feature_context(const float* feat, const float* mean, const float* stdv, const int* lengths, float* out, int B, int T, int L,
+                        int frame, int hop, int D, int ctx, float clip, void* stream);
+int sfm_rows_mean(const float* in, const int* lengths, float* out, int B, int T, int L, int frame, int hop, long long ld_in,
+                  int col_off, int N, int den, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,7 +24,9 @@ FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-u
 EXTRA = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-nans"],
          "attention_pipe.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-nans"],
          # the swarm's float64 recurrences equal numpy's bit for bit: no multiply-add is fused
-         "pso.hip": ["-ffp-contract=off"]}
+         "pso.hip": ["-ffp-contract=off"],
+         # the hair cell's Euler steps equal the reference's loop bit for bit, for the same reason
+         "haircell.hip": ["-ffp-contract=off"]}
 
 
 def _newer(src, dst, deps):

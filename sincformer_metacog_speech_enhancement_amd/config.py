@@ -16,6 +16,18 @@ NUM_CHANNELS = 64
 FREQ_LOW = 50
 FREQ_HIGH = 4000
 FILTER_ORDER = 4
+# the DNN front end (config.py:31-46 of the reference): AMS, MFCC, GFCC, RASTA-PLP and the context
+AMS_SEGMENTS = 128
+AMS_OVERLAP = 64
+AMS_FFT_SIZE = 256
+AMS_NUM_BANDS = 15
+MFCC_NUM_COEFF = 13
+MFCC_FFT_SIZE = 512
+MFCC_NUM_FILTERS = 64
+GFCC_NUM_COEFF = 13
+GFCC_DECIMATE_RATE = 100
+RASTA_NUM_COEFF = 13
+CONTEXT_FRAMES = 5
 CONFORMER_NUM_BLOCKS = 6
 CONFORMER_D_MODEL = 256
 CONFORMER_NUM_HEADS = 4

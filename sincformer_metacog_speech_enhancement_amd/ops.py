@@ -1427,6 +1427,165 @@ def gammatone_tf_finish(partial, rot, T, L, frame, hop, N, two, lengths=None, wa
     return tuple(outs)
 
 
+# ---------------------------------------------------------------------------
+# the DNN front end (csrc/features.hip; signal_processing/features.py)
+# ---------------------------------------------------------------------------
+FE_MAX_FILTERS, FE_MAX_BINS, FE_MAX_COEFFS = 64, 257, 16
+CEP_POWER, CEP_MAGNITUDE, CEP_BLOCKS = 0, 1, 2              # sfm_cepstral's in_mode
+CEP_NONE, CEP_LOG, CEP_CBRT = 0, 1, 2                       # its compress
+
+
+def _fe_lengths(name, lengths, B):
+    if lengths is not None and not (lengths.dtype == torch.int32 and lengths.numel() == B and lengths.is_contiguous()):
+        _lib.check(-2, name)
+
+
+def _fe_f32(*ts):
+    return all(t is None or (t.dtype == torch.float32 and t.is_contiguous()) for t in ts)
+
+
+def cepstral(src, fb, dct, out, col_off, *, B, T, L, frame, hop, in_mode, F, compress, im_off=0, bmul=1, badd=0, window=1.0,
+             lengths=None):
+    """rows of src -> out[.., col_off : col_off + (NC or M)]: [power / magnitude / block energy -> fb [M, F] (None: M = F) -> compress
+    -> dct [NC, M] (None: NC = 0)].  src [B, T, ld_in] spectrum rows with re at [0, F) and im at [im_off, im_off + F)
+    (CEP_POWER, CEP_MAGNITUDE) or gammatone_tf's partial [B, P, F, 5] (CEP_BLOCKS: blocks bmul n + badd and the next, over `window`
+    samples).  out [B, T, ld_out] fp32; rows from T_b on are not written."""
+    _need_dev(src, fb, dct, out, lengths)
+    L_ = _lib.load()
+    M = F if fb is None else fb.shape[0]
+    NC = 0 if dct is None else dct.shape[0]
+    ok = _fe_f32(fb, dct, out) and src.dtype == torch.float32 and out.dim() == 3 and tuple(out.shape[:2]) == (B, T) and B >= 1 and T >= 1
+    ok = ok and 1 <= F <= FE_MAX_BINS and 1 <= M <= FE_MAX_FILTERS and NC <= FE_MAX_COEFFS and 0 <= col_off
+    ok = ok and col_off + (NC or M) <= out.shape[2] and (fb is None or tuple(fb.shape) == (M, F)) and (dct is None or tuple(dct.shape) == (NC, M))
+    ok = ok and frame >= 1 and hop >= 1 and L >= frame and T <= (L - frame) // hop + 1 and B * T < 2 ** 31
+    if in_mode == CEP_BLOCKS:
+        ok = ok and src.dim() == 4 and src.is_contiguous() and src.shape[0] == B and src.shape[2] == F and src.shape[3] == 5 and F <= 64
+        ok = ok and bmul >= 1 and badd >= 0 and window > 0 and bmul * (T - 1) + badd + 1 < src.shape[1]
+        ld_in, P = 0, src.shape[1] if src.dim() == 4 else 0
+    else:                                                   # the rows may be a column slice of a wider row matrix
+        ok = ok and in_mode in (CEP_POWER, CEP_MAGNITUDE) and src.dim() == 3 and tuple(src.shape[:2]) == (B, T)
+        ok = ok and src.stride(2) == 1 and src.stride(0) == T * src.stride(1) and src.stride(1) >= src.shape[2]
+        ok = ok and F <= im_off and im_off + F <= src.shape[2]
+        ld_in, P = src.stride(1) if src.dim() == 3 else 0, 0
+    if not ok:
+        _lib.check(-2, "cepstral")
+    _fe_lengths("cepstral", lengths, B)
+    rows = float(B) * T
+    _call("cepstral", L_.sfm_cepstral, (_p(src), _p(fb), _p(dct), _p(lengths), _p(out), B, T, L, frame, hop, in_mode, ld_in, im_off, F,
+                                        M, NC, compress, P, bmul, badd, float(window), out.shape[2], col_off, _stream()),
+          rows * (3.0 * F + (2.0 * M * F if fb is not None else 0.0) + M + 2.0 * NC * M),
+          rows * (8.0 * F + 4.0 * (NC or M)) + (4.0 * M * F if fb is not None else 0.0) + 4.0 * NC * M,
+          "B%d T%d F%d M%d NC%d in%d c%d" % (B, T, F, M, NC, in_mode, compress))
+    return out
+
+
+def rasta(logb, eql, dct, out, col_off, *, L, frame, hop, lengths=None):
+    """logb [B, T, M] fp32 (log bark energies), eql [M] and dct [NC, M] fp64 -> out[b, n < T_b, col_off : col_off + NC] = the
+    utterance's RASTA-PLP vector on every live row.  The recurrence, the mean and the DCT run in fp64 in frame order."""
+    _need_dev(logb, eql, dct, out, lengths)
+    L_ = _lib.load()
+    ok = _fe_f32(logb, out) and logb.dim() == 3 and out.dim() == 3 and tuple(out.shape[:2]) == tuple(logb.shape[:2])
+    ok = ok and eql.dtype == torch.float64 and dct.dtype == torch.float64 and eql.is_contiguous() and dct.is_contiguous() and dct.dim() == 2
+    if not ok:
+        _lib.check(-2, "rasta")
+    B, T, M = logb.shape
+    NC = dct.shape[0]
+    ok = 1 <= M <= FE_MAX_FILTERS and 1 <= NC <= FE_MAX_COEFFS and tuple(eql.shape) == (M,) and dct.shape[1] == M
+    ok = ok and 0 <= col_off and col_off + NC <= out.shape[2] and frame >= 1 and hop >= 1 and L >= frame and 1 <= T <= (L - frame) // hop + 1
+    if not ok:
+        _lib.check(-2, "rasta")
+    _fe_lengths("rasta", lengths, B)
+    _call("rasta", L_.sfm_rasta, (_p(logb), _p(eql), _p(dct), _p(lengths), _p(out), B, T, L, frame, hop, M, NC, out.shape[2], col_off,
+                                  _stream()),
+          12.0 * B * T * M + 2.0 * B * NC * M, 4.0 * B * T * M + 4.0 * B * T * NC + 8.0 * M + 8.0 * NC * M, "B%d T%d M%d NC%d" % (B, T, M, NC))
+    return out
+
+
+def feature_context(feat, ctx, *, L, frame, hop, mean=None, std=None, clip=10.0, lengths=None):
+    """feat [B, T, D] -> [B, T, (2 ctx + 1) D]: rows clamp(n - ctx .. n + ctx, 0, T_b - 1) side by side, 0 from T_b on; with mean and
+    std [(2 ctx + 1) D] the same launch applies nan / inf -> 0, (f - mean) / std and the clip to +-clip"""
+    _need_dev(feat, mean, std, lengths)
+    L_ = _lib.load()
+    ok = _fe_f32(feat, mean, std) and feat.dim() == 3 and feat.numel() > 0 and (mean is None) == (std is None)
+    if not ok:
+        _lib.check(-2, "feature_context")
+    B, T, D = feat.shape
+    W = (2 * ctx + 1) * D
+    ok = D % 2 == 0 and 0 <= ctx <= 64 and clip > 0 and frame >= 1 and hop >= 1 and L >= frame and T <= (L - frame) // hop + 1
+    ok = ok and B * T < 2 ** 31 and (mean is None or (tuple(mean.shape) == (W,) and tuple(std.shape) == (W,)))
+    if not ok:
+        _lib.check(-2, "feature_context")
+    _fe_lengths("feature_context", lengths, B)
+    out = torch.empty(B, T, W, device=feat.device, dtype=torch.float32)
+    n = float(B) * T
+    _call("feature_context", L_.sfm_feature_context, (_p(feat), _p(mean), _p(std), _p(lengths), _p(out), B, T, L, frame, hop, D, ctx,
+                                                      float(clip), _stream()),
+          0.0 if mean is None else 3.0 * n * W, 4.0 * n * (D + W) + (0.0 if mean is None else 8.0 * W),
+          "B%d T%d D%d ctx%d norm%d" % (B, T, D, ctx, int(mean is not None)))
+    return out
+
+
+def rows_mean(src, col_off, N, *, L, frame, hop, den=0, lengths=None):
+    """src [B, T, ld] -> [B, N]: the mean over an utterance's T_b rows of columns col_off .. col_off + N (den > 0: the sum over den)"""
+    _need_dev(src, lengths)
+    L_ = _lib.load()
+    ok = _fe_f32(src) and src.dim() == 3 and src.numel() > 0 and N >= 1 and 0 <= col_off and col_off + N <= src.shape[2] and den >= 0
+    ok = ok and frame >= 1 and hop >= 1 and L >= frame and src.shape[1] <= (L - frame) // hop + 1
+    if not ok:
+        _lib.check(-2, "rows_mean")
+    B, T, ld = src.shape
+    _fe_lengths("rows_mean", lengths, B)
+    out = torch.empty(B, N, device=src.device, dtype=torch.float32)
+    _call("rows_mean", L_.sfm_rows_mean, (_p(src), _p(lengths), _p(out), B, T, L, frame, hop, ld, col_off, N, int(den), _stream()),
+          1.0 * B * T * N, 4.0 * B * T * N + 4.0 * B * N, "B%d T%d N%d" % (B, T, N))
+    return out
+
+
+# ---------------------------------------------------------------------------
+# Meddis hair cell (csrc/haircell.hip; signal_processing/haircell.py)
+# ---------------------------------------------------------------------------
+HC_PARAMS = 12                      # par = {A, B, y, l, r, x, h, M, dt, q0, c0, w0}, fp64
+HC_STEP_FLOPS = 24.0                # fp64 operations of one Euler step: 3 for k, 6 + 6 + 5 for q, c, w with their clamps, 1 for h c,
+                                    # 3 for the two frame sums (counted in both forms: the algorithm, not the variant)
+
+
+def _hc_args(name, x, par, ndim):
+    ok = x.dim() == ndim and x.dtype == torch.float32 and x.is_contiguous() and x.numel() > 0 and x.numel() // x.shape[-1] < 2 ** 31
+    ok = ok and par.dtype == torch.float64 and tuple(par.shape) == (HC_PARAMS,) and par.is_contiguous()
+    if not ok:
+        _lib.check(-2, name)
+
+
+def haircell(x, par):
+    """x [N, L] fp32, par [12] fp64 -> [N, L] fp64: the firing rate h c[t] of each row's chain"""
+    _need_dev(x, par)
+    L_ = _lib.load()
+    _hc_args("haircell", x, par, 2)
+    N, L = x.shape
+    out = torch.empty(N, L, device=x.device, dtype=torch.float64)
+    _call("haircell", L_.sfm_haircell, (_p(x), _p(par), _p(out), N, L, _stream()),
+          HC_STEP_FLOPS * N * L, 12.0 * N * L + 8.0 * HC_PARAMS, "N%d L%d" % (N, L))
+    return out
+
+
+def haircell_frames(x, par, frame, hop, lengths=None):
+    """x [B, C, L] fp32 -> [B, C, T] fp64: the mean firing rate of each frame of `frame` samples at `hop` (frame <= 2 hop); with
+    lengths (int32 [B]) a chain stops at its utterance's end and frames from T_b on are 0.  The rate signal is not stored."""
+    _need_dev(x, par, lengths)
+    L_ = _lib.load()
+    _hc_args("haircell_frames", x, par, 3)
+    B, C, L = x.shape
+    ok = 1 <= hop and 1 <= frame <= 2 * hop and L >= frame
+    ok = ok and (lengths is None or (lengths.dtype == torch.int32 and lengths.numel() == B and lengths.is_contiguous()))
+    if not ok:
+        _lib.check(-2, "haircell_frames")
+    T = (L - frame) // hop + 1
+    out = torch.empty(B, C, T, device=x.device, dtype=torch.float64)
+    _call("haircell_frames", L_.sfm_haircell_frames, (_p(x), _p(par), _p(lengths), _p(out), B * C, C, L, frame, hop, T, _stream()),
+          HC_STEP_FLOPS * B * C * L, 4.0 * B * C * L + 8.0 * B * C * T + 8.0 * HC_PARAMS, "B%d C%d L%d f%d h%d" % (B, C, L, frame, hop))
+    return out
+
+
 def spec_sums(pr, pi, tr, ti, out=None):
     L = _lib.load()
     S = torch.zeros(4, device=pr.device, dtype=torch.float64) if out is None else out

@@ -1,10 +1,12 @@
 """Mirror of the oracle-mask recipe of training/pipeline.py:153-197: the gammatone T-F analysis of the clean, noise and noisy
-waveforms (signal_processing/gammatone.py) into masks/ on the device.  The rest of that file (feature extraction, the cache, the
-DNN's Dataset with its clipping and nan_to_num) is not mirrored."""
+waveforms (signal_processing/gammatone.py) into masks/ on the device, and of _process_single_utterance (:147-197) as a whole:
+dnn_frame_pairs gives the (features, mask) pair of a batch of utterances without file I/O, cache or a host round trip.  The
+Dataset, the DNN and the RBM are not mirrored; the Dataset's feature normalisation is an option of add_context."""
+import numpy as np
 import torch
 
-from .. import masks
-from ..signal_processing import GammatoneFilterbank
+from .. import config, masks
+from ..signal_processing import FeatureExtractor, GammatoneFilterbank
 
 _default_gfb = []
 
@@ -46,3 +48,24 @@ def gammatone_mask_target(clean, noise, noisy, mask_type, gfb=None, lengths=None
         mask = masks.compute_irm(clean_m, noise_m)
     mask = mask.transpose(1, 2).contiguous()
     return mask[0] if one_d else mask
+
+
+_default_fe = {}
+
+
+def dnn_frame_pairs(clean, noise, noisy, mask_type, fe=None, lengths=None, feat_mean=None, feat_std=None):
+    """-> (features [B, T, 594], mask [B, T, 64]) (1-D signals: [T, 594], [T, 64]): the DNN's input rows from `noisy`
+    (FeatureExtractor.extract_frame_features + add_context, normalised and clipped when feat_mean / feat_std are given) and its
+    target from gammatone_mask_target, both over the same frames and with fe's one GammatoneFilterbank.  lengths: the sample counts
+    of a zero-padded batch; rows from an utterance's T_b on are 0 in the features and analysed as zeros in the mask."""
+    if fe is None:
+        if config.SAMPLE_RATE not in _default_fe:
+            _default_fe[config.SAMPLE_RATE] = FeatureExtractor()
+        fe = _default_fe[config.SAMPLE_RATE]
+    mask = gammatone_mask_target(clean, noise, noisy, mask_type, gfb=fe.gfb, lengths=lengths)
+    raw = fe.extract_frame_features(noisy, lengths=lengths)
+    frames = None
+    if lengths is not None:
+        host = np.asarray(lengths.cpu() if torch.is_tensor(lengths) else lengths, dtype=np.int64).reshape(-1)
+        frames = (np.maximum(host, config.FRAME_SIZE) - config.FRAME_SIZE) // config.HOP_SIZE + 1
+    return fe.add_context(raw, feat_mean, feat_std, lengths=frames), mask

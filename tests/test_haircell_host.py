@@ -1,0 +1,137 @@
+"""signal_processing/haircell.py without a GPU: the host-computed steady state against the reference's (tests/golden/
+g21_haircell.npz, bit for bit), the float64 restatement of tests/haircell_cases.py against the reference's captured outputs,
+the mutants, the argument guards and the launch costs the wrappers state.
+
+Measured here: the restatement's firing rate equals the reference's at distance 0 (every step is the same IEEE double operation)
+at both scales; its frame means differ from numpy's by at most 2.3e-16 relative (torch and numpy add a frame's 160 terms in
+different orders)."""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import haircell_cases as hc
+from sincformer_metacog_speech_enhancement_amd import lib, ops
+from sincformer_metacog_speech_enhancement_amd.signal_processing import MeddisHairCell
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+@pytest.fixture(scope="module")
+def fixture():
+    return np.load(os.path.join(GOLDEN, "g21_haircell.npz"))
+
+
+def test_steady_state_equals_the_reference_bitwise(fixture):
+    for fs in (8000, 16000):
+        m = MeddisHairCell(fs)
+        assert np.array_equal(np.array([m.q0, m.c0, m.w0]), fixture["q0c0w0.%d" % fs]) and m.dt == float(fixture["dt.%d" % fs])
+        p = hc.params(fs)
+        assert (p["q0"], p["c0"], p["w0"], p["dt"]) == (m.q0, m.c0, m.w0, m.dt)
+        assert (m.fs, m.A, m.B, m.g, m.y, m.l, m.r, m.x, m.h, m.M) == (fs, 5.0, 300.0, 2000.0, 5.05, 2500.0, 6580.0, 66.31, 50000.0, 1.0)
+    assert MeddisHairCell().fs == 8000
+
+
+@pytest.mark.parametrize("scale", hc.SCALES)
+def test_float64_restatement_equals_the_reference(fixture, scale):
+    x = torch.from_numpy(fixture["x.%g" % scale])
+    assert torch.equal(x, hc.inputs("c64")[list(hc.GOLDEN_ROWS)] * np.float32(scale))          # the fixture's input is the case's
+    rate = hc.haircell(x.double())
+    ref = torch.from_numpy(fixture["rate.%g" % scale])
+    fr, fref = hc.frames(rate), torch.from_numpy(fixture["frames.%g" % scale])
+    d_rate = hc.rel_distance(rate, ref)
+    d_frames = float(((fr - fref).abs() / fref.abs().clamp_min(1e-300)).max())
+    print("REF | haircell scale %g | rate distance %.2e | frame means %.2e relative" % (scale, d_rate, d_frames))
+    assert torch.equal(rate, ref)
+    assert fr.shape == fref.shape and d_frames <= 1e-14
+    assert torch.equal(rate, hc.reference("c64", scale)[0][list(hc.GOLDEN_ROWS)])
+
+
+def test_the_large_scale_reaches_the_clamps(fixture):
+    """at scale 1 the permeability clamp never acts (the mutant without it changes nothing) and the cleft clamp acts on the first
+    step alone (the reference's c0 is no fixed point of its own step: c0 (1 - dt (l + r)) + dt k q0 < 0), so each row has one exact
+    zero; at 1e4 both act throughout"""
+    assert torch.equal(hc.reference("c64", 1.0, "no s clamp")[0], hc.reference("c64", 1.0)[0])
+    small, large = torch.from_numpy(fixture["rate.1"]), torch.from_numpy(fixture["rate.10000"])
+    assert bool((small[:, 0] == 0).all()) and int((small == 0).sum()) == small.shape[0]
+    assert int((large == 0).sum()) > 100 * large.shape[0]
+
+
+@pytest.mark.parametrize("mutant", hc.MUTANTS)
+def test_bounds_reject_the_mutants(mutant):
+    """the rate row is bitwise (bound 0: any movement is caught, shown here against 1e-12 all the same); the frame row's bound is
+    FRAMES_RTOL"""
+    for name in ("c64", "b20"):
+        rate, fr = hc.reference(name, 1e4)
+        bad_rate, bad_fr = hc.reference(name, 1e4, mutant)
+        if mutant == "frame sum off by one":
+            hc.separates("frames " + name, mutant, bad_fr, fr, hc.FRAMES_RTOL)
+        else:
+            hc.separates("rate " + name, mutant, bad_rate, rate, hc.FRAMES_RTOL)
+    if mutant == "frame sum off by one":
+        hc.separates("frames c64 x1", mutant, hc.reference("c64", 1.0, mutant)[1], hc.reference("c64", 1.0)[1], hc.FRAMES_RTOL)
+
+
+def test_host_tensors_and_bad_arguments_are_refused():
+    m = MeddisHairCell()
+    x = torch.zeros(64, 400)
+    for call in (lambda: m.process(x[0]), lambda: m.process_filterbank(x), lambda: m.process_to_frames(x)):
+        with pytest.raises(RuntimeError, match="no CPU fallback"):
+            call()
+    with pytest.raises(TypeError):
+        m.process_filterbank(np.zeros((64, 400), dtype=np.float32))
+    with pytest.raises(ValueError, match="2 hop_size"):                  # a sample would lie in three frames
+        m.process_to_frames(x, frame_size=161, hop_size=80)
+    with pytest.raises(ValueError, match="hop_size"):
+        m.process_to_frames(x, frame_size=160, hop_size=0)
+
+
+def test_entry_points_check_their_arguments_without_a_gpu():
+    """argument validation happens before any HIP call"""
+    from sincformer_metacog_speech_enhancement_amd import build
+    build.build(verbose=False)
+    L = lib.load()
+    one = ctypes.c_void_p(16)
+    assert L.sfm_haircell(None, one, one, 64, 400, None) == -1
+    assert L.sfm_haircell(one, one, one, 0, 400, None) == -2
+    assert L.sfm_haircell_frames(one, one, None, None, 64, 64, 400, 160, 80, 4, None) == -1
+    assert L.sfm_haircell_frames(one, one, None, one, 64, 64, 400, 161, 80, 3, None) == -2      # frame > 2 hop
+    assert L.sfm_haircell_frames(one, one, None, one, 64, 64, 400, 160, 80, 5, None) == -2      # T is not (L - frame) / hop + 1
+    assert L.sfm_haircell_frames(one, one, None, one, 64, 60, 400, 160, 80, 4, None) == -2      # rows are no whole utterances
+    assert L.sfm_haircell_frames(one, one, None, one, 64, 64, 100, 160, 80, 1, None) == -2      # shorter than a frame
+
+
+class _StubLib:
+    def __getattr__(self, symbol):
+        if not symbol.startswith("sfm_"):
+            raise AttributeError(symbol)
+        fn = lambda *args: 0
+        fn.__name__ = symbol
+        return fn
+
+
+def test_haircell_costs(monkeypatch):
+    rec = []
+
+    def record(name, fn, args, flops=0.0, nbytes=0.0, tag=None):
+        assert len(args) == len(lib.SIGNATURES[fn.__name__]), fn.__name__
+        rec.append((fn.__name__, name, flops, nbytes, tag))
+
+    monkeypatch.setattr(ops._lib, "load", lambda: _StubLib())
+    monkeypatch.setattr(ops, "_stream", lambda: None)
+    monkeypatch.setattr(ops, "_need_dev", lambda *ts: None)
+    monkeypatch.setattr(ops, "_call", record)
+    par = torch.zeros(12, dtype=torch.float64)
+    assert ops.haircell(torch.zeros(128, 2403), par).shape == (128, 2403)
+    out = ops.haircell_frames(torch.zeros(2, 64, 2403), par, 160, 80)
+    assert out.shape == (2, 64, 29) and out.dtype == torch.float64
+    assert rec == [
+        ("sfm_haircell", "haircell", 7382016.0, 3691104.0, "N128 L2403"),
+        ("sfm_haircell_frames", "haircell_frames", 7382016.0, 1260128.0, "B2 C64 L2403 f160 h80"),
+    ]
+    with pytest.raises(RuntimeError, match="unsupported shape"):
+        ops.haircell_frames(torch.zeros(2, 64, 2403), par, 161, 80)
+    with pytest.raises(RuntimeError, match="unsupported shape"):
+        ops.haircell(torch.zeros(128, 2403), par.float())
