@@ -29,7 +29,38 @@ PARAM_NAMES = tuple(_NAMES)
 
 
 def _f32(t):
-    return t.detach().float().contiguous()
+    """detached, fp32, contiguous (None stays None)"""
+    return None if t is None else t.detach().float().contiguous()
+
+
+def _rows32(x, batched=False):
+    """x detached and in fp32 with a unit inner stride.  Rows [M, C] keep a wider row stride (a column slice of wider rows is read
+    in place; the kernels are handed stride(0)); batched [B, T, C] rows must also lie T row strides apart (handed stride(1))."""
+    x32 = x.detach().float()
+    if x32.stride(-1) != 1 or (batched and x32.stride(0) != x32.shape[1] * x32.stride(1)):
+        x32 = x32.contiguous()
+    return x32
+
+
+def _flat_views(shapes, align=1, flat=None, device=None):
+    """one fp32 view per shape, cut in order from the flat buffer `flat` (None: a zero-filled one of the size needed, on
+    `device`); every view starts on a multiple of `align` elements, align = 1 packs them densely"""
+    sizes = [math.prod(s) for s in shapes]
+    offs, n = [], 0
+    for k in sizes:
+        offs.append(n)
+        n += ops.round_up(k, align)
+    if flat is None:
+        flat = torch.zeros(n, device=device, dtype=torch.float32)
+    return [flat[o:o + k].view(s) for o, k, s in zip(offs, sizes, shapes)]
+
+
+def _scaled_grads(grads, g, dtypes, n_inputs):
+    """backward of a node whose forward already produced its gradients: each stored gradient times the incoming g, in its input's
+    dtype (None where none was stored, `grads` itself may be None), padded with None to the node's n_inputs"""
+    s = g.float()
+    out = tuple(None if d is None else (d * s).to(dt) for d, dt in zip(grads or (), dtypes))
+    return out + (None,) * (n_inputs - len(out))
 
 
 def _lin_pack(w2d, b):
@@ -251,12 +282,7 @@ def block_train_forward(x32, P, B, T, H, p, seed, bn_buffers=None, momentum=0.1,
 def _zero_grads(shapes, device):
     """{name: zero-filled fp32 tensor of that shape}, all views of ONE buffer (one fill launch instead of one per
     parameter; every view starts on a 256-byte boundary)"""
-    offs, n = {}, 0
-    for k, shp in shapes.items():
-        offs[k] = n
-        n += (int(torch.Size(shp).numel()) + 63) // 64 * 64
-    flat = torch.zeros(n, device=device, dtype=torch.float32)
-    return {k: flat[o:o + torch.Size(shapes[k]).numel()].view(shapes[k]) for k, o in offs.items()}
+    return dict(zip(shapes, _flat_views(list(shapes.values()), align=64, device=device)))
 
 
 def block_train_backward(dy32, ctx, P):
@@ -301,6 +327,28 @@ class ConformerBlockFunction(torch.autograd.Function):
 # LayerNorm -> Linear (input_norm + input_proj, output_norm + heads of SpeechEnhancer,
 # training/conformer_pipeline.py:273-284)
 # ---------------------------------------------------------------------------
+def _linear_bwd(dy, a16, w32, dx_dtype=torch.float32, dx_out=None, want_dx=True):
+    """backward of y = a16[:, :K] @ w32^T + b on 16-bit operands.  dy [M, N]: the cotangent rows, any float dtype, a wider row
+    stride allowed; a16: the operand the forward saved; w32 [N, K].  -> (dx, dW, db, dy16): dW, db fresh fp32; dx [M, K] in
+    dx_dtype (None: the compute format), or written into dx_out (row stride a multiple of 16 bytes), or None with
+    want_dx=False; dy16 = the cotangent as the GEMMs read it, [M, round_up(N, 64)] in the compute format, for a caller with
+    further weight gradients to take from it."""
+    M, N = dy.shape
+    K = w32.shape[1]
+    dev = dy.device
+    dy = _rows32(dy)
+    Np = ops.round_up(N, 64)
+    dy16 = torch.empty(M, Np, device=dev, dtype=ops.compute_dtype())
+    ops.convert_rows(dy, dy16, M, N, Np, dy.stride(0), Np)
+    dW = torch.zeros(N, K, device=dev, dtype=torch.float32)
+    db = torch.zeros(N, device=dev, dtype=torch.float32)
+    ops.gemm16_tn(dy16[:, :N], a16[:, :K], dW, db)
+    dx = None
+    if want_dx:
+        dx = ops.linear16(dy16, ops.pack_linear(w32.t().contiguous(), k_pad_to=Np), out_dtype=dx_dtype, out=dx_out)
+    return dx, dW, db, dy16
+
+
 class LNLinearFunction(torch.autograd.Function):
     """y[M, N] = LayerNorm(x[:, :K]) @ W^T + b, fp32 in / fp32 out, GEMMs on 16-bit operands.
     ln_w = ln_b = None: plain Linear (input_proj / output_proj of ComplexConformer, models/conformer.py:211,222)."""
@@ -309,9 +357,7 @@ class LNLinearFunction(torch.autograd.Function):
     def forward(ctx, x, ln_w, ln_b, W, b):
         M = x.shape[0]
         N, K = W.shape
-        x32 = x.detach().float()
-        if x32.stride(1) != 1:
-            x32 = x32.contiguous()
+        x32 = _rows32(x)
         has_ln = ln_w is not None
         lw, lb, w32 = (_f32(ln_w), _f32(ln_b), _f32(W)) if has_ln else (None, None, _f32(W))
         Kp = ops.round_up(K, 64)
@@ -334,19 +380,8 @@ class LNLinearFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x32, lw, w32, h16 = ctx.saved
-        M, N, K = ctx.dims
-        dev = dy.device
-        dy = dy.float()
-        if dy.stride(1) != 1:
-            dy = dy.contiguous()
-        Np = ops.round_up(N, 64)
-        dy16 = torch.empty(M, Np, device=dev, dtype=ops.compute_dtype())
-        ops.convert_rows(dy, dy16, M, N, Np, dy.stride(0), Np)
-        dW = torch.zeros(N, K, device=dev, dtype=torch.float32)
-        db = torch.zeros(N, device=dev, dtype=torch.float32)
-        ops.gemm16_tn(dy16[:, :N], h16[:, :K], dW, db)
-        bwd = ops.pack_linear(w32.t().contiguous(), k_pad_to=Np)
-        dh = ops.linear16(dy16, bwd, out_dtype=torch.float32 if lw is None else None)   # [M, K]; 16-bit into the LayerNorm backward
+        K, dev = ctx.dims[2], dy.device
+        dh, dW, db, _ = _linear_bwd(dy, h16, w32, dx_dtype=torch.float32 if lw is None else None)   # [M, K]; 16-bit into the LayerNorm backward
         t = ctx.dtypes
         ctx.saved = None
         if lw is None:
@@ -365,7 +400,7 @@ class PolarMaskFunction(torch.autograd.Function):
     def forward(ctx, logits, noisy_real, noisy_imag, phase_scale):
         B, T, F = noisy_real.shape
         lg = logits.detach()
-        nr, ni = noisy_real.detach().float().contiguous(), noisy_imag.detach().float().contiguous()
+        nr, ni = _f32(noisy_real), _f32(noisy_imag)
         dev = lg.device
         er = torch.empty(B, T, F, device=dev, dtype=torch.float32)
         ei = torch.empty(B, T, F, device=dev, dtype=torch.float32)
@@ -433,6 +468,50 @@ def _inv_envelope(L, T, n_fft, hop, win, dev):
     return v
 
 
+def _mr_stft_pass(pw, tw, size, split, Sr_i, dwave, scale, post=None):
+    """one resolution size = (n_fft, hop, win) of the multi-resolution STFT term, prediction pw against target tw [B, L]: the
+    four sums of the resolution go to Sr_i; with dwave given, scale (= 1 / R) times the gradient of its two terms w.r.t. pw is
+    added into dwave through the STFT's adjoint (post: the envelope the last overlap-add multiplies in).  split: the STFTs and
+    the adjoint GEMM on split-bf16 operands.  -> element count of the spectrum.  (The spectra are released before the frames
+    are allocated, and everything else on return: the peak at B 256.)"""
+    from . import functional as Fn
+    nf, hp, wn = size
+    (B, L), dev = pw.shape, pw.device
+    stft_ = Fn.stft_split16 if split else Fn.stft
+    pr, pi = stft_(pw, nf, hp, wn)
+    tr, ti = stft_(tw, nf, hp, wn)
+    ops.spec_sums(pr, pi, tr, ti, out=Sr_i)
+    count = pr.numel()
+    if dwave is not None:
+        Tr, Fr = pr.shape[1], pr.shape[2]
+        Mr = B * Tr
+        ld = ops.round_up(2 * Fr, 8)
+        g = torch.zeros(Mr, ld, device=dev, dtype=torch.float32)
+        ops.spec_loss_bwd(pr, pi, tr, ti, Sr_i, g, g[:, Fr:], Fr, ld, 0, scale=scale)
+        del pr, pi, tr, ti
+        frames = torch.empty(Mr, wn, device=dev, dtype=torch.float32)
+        if split:
+            ops.framed_gemm_split16(g, _adjoint_consts(nf, wn, dev)["fwdT16"], frames, B=1, M=Mr, Ls=Mr * ld,
+                                    sig_batch_stride=0, hop=ld, padl=0, o_batch_stride=0, ldm=wn, mode=0)
+        else:
+            ops.framed_gemm(g, _adjoint_consts(nf, wn, dev)["fwdT"], frames, B=1, M=Mr, Ls=Mr * ld, sig_batch_stride=0,
+                            hop=ld, padl=0, K=2 * Fr, N=wn, o_batch_stride=0, ldm=wn, ldn=1, mode=0)
+        ops.stft_adjoint_ola(frames, dwave, B, Tr, L, nf, hp, wn, accumulate=True, post=post)
+    return count
+
+
+def _istft_adjoint(dwave, T, F, n_fft, hop, win):
+    """adjoint of functional.istft's irfft-by-matrix + overlap-add, applied to dwave [B, L] (the cotangent already divided by
+    the window envelope): frames-x-matrix product with the transposed operand -> (d real, d imag) [B, T, F] fp32"""
+    B, L = dwave.shape
+    d_re = torch.empty(B, T, F, device=dwave.device, dtype=torch.float32)
+    d_im = torch.empty(B, T, F, device=dwave.device, dtype=torch.float32)
+    ops.framed_gemm(dwave, _adjoint_consts(n_fft, win, dwave.device)["invT"], d_re, B=B, M=T, Ls=L, sig_batch_stride=L, hop=hop,
+                    padl=n_fft // 2 - (n_fft - win) // 2, K=win, N=2 * F, o_batch_stride=T * F, ldm=F, ldn=1, mode=0,
+                    out2=d_im, nsplit=F)
+    return d_re, d_im
+
+
 class EnhancerLossFunction(torch.autograd.Function):
     """(enh_real, enh_imag, clean_wave, clean_real, clean_imag) -> total loss (0-dim, differentiable w.r.t. the enhanced
     spectrum) and aux = [neg_sisnr, l1_mag, mr_stft] (monitoring).  The gradient is produced during the forward pass
@@ -441,9 +520,7 @@ class EnhancerLossFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, enh_real, enh_imag, clean_wave, clean_real, clean_imag, n_fft, hop, win):
         from . import functional as Fn
-        er, ei = enh_real.detach().float().contiguous(), enh_imag.detach().float().contiguous()
-        cw = clean_wave.detach().float().contiguous()
-        cr, ci = clean_real.detach().float().contiguous(), clean_imag.detach().float().contiguous()
+        er, ei, cw, cr, ci = (_f32(t) for t in (enh_real, enh_imag, clean_wave, clean_real, clean_imag))
         B, L = cw.shape
         _, T, F = er.shape
         dev = er.device
@@ -453,43 +530,17 @@ class EnhancerLossFunction(torch.autograd.Function):
         Sm = ops.spec_sums(er, ei, cr, ci)
         R = len(Fn.MR_STFT)
         Sr = torch.zeros(R, 4, device=dev, dtype=torch.float64)
-        counts = []
         dwave = None
         if need_grad:
             dwave = torch.empty(B, L, device=dev, dtype=torch.float32)
             ops.sisnr_bwd(enh_wav, cw, Sw, dwave)
         inv_env = _inv_envelope(L, T, n_fft, hop, win, dev) if need_grad else None
-        for i, (nf, hp, wn) in enumerate(Fn.MR_STFT):
-            stft_ = Fn.stft_split16 if LOSS_STFT_SPLIT16 else Fn.stft
-            pr, pi = stft_(enh_wav, nf, hp, wn)
-            tr, ti = stft_(cw, nf, hp, wn)
-            ops.spec_sums(pr, pi, tr, ti, out=Sr[i])
-            counts.append(pr.numel())
-            if need_grad:
-                Tr, Fr = pr.shape[1], pr.shape[2]
-                Mr = B * Tr
-                ld = ops.round_up(2 * Fr, 8)
-                g = torch.zeros(Mr, ld, device=dev, dtype=torch.float32)
-                ops.spec_loss_bwd(pr, pi, tr, ti, Sr[i], g, g[:, Fr:], Fr, ld, 0, scale=1.0 / R)
-                del pr, pi, tr, ti
-                frames = torch.empty(Mr, wn, device=dev, dtype=torch.float32)
-                if LOSS_STFT_SPLIT16:
-                    ops.framed_gemm_split16(g, _adjoint_consts(nf, wn, dev)["fwdT16"], frames, B=1, M=Mr, Ls=Mr * ld,
-                                            sig_batch_stride=0, hop=ld, padl=0, o_batch_stride=0, ldm=wn, mode=0)
-                else:
-                    ops.framed_gemm(g, _adjoint_consts(nf, wn, dev)["fwdT"], frames, B=1, M=Mr, Ls=Mr * ld, sig_batch_stride=0,
-                                    hop=ld, padl=0, K=2 * Fr, N=wn, o_batch_stride=0, ldm=wn, ldn=1, mode=0)
-                ops.stft_adjoint_ola(frames, dwave, B, Tr, L, nf, hp, wn, accumulate=True,
-                                     post=inv_env if i == R - 1 else None)
-                del g, frames
+        counts = [_mr_stft_pass(enh_wav, cw, size, LOSS_STFT_SPLIT16, Sr[i], dwave, 1.0 / R, post=inv_env if i == R - 1 else None)
+                  for i, size in enumerate(Fn.MR_STFT)]
         nr = Fn.counts_tensor(tuple(counts), dev)
         losses = ops.enhancer_loss_finalize(Sw, Sm, Sr, nr, B, L, er.numel())
         if need_grad:
-            d_er = torch.empty(B, T, F, device=dev, dtype=torch.float32)
-            d_ei = torch.empty(B, T, F, device=dev, dtype=torch.float32)
-            ops.framed_gemm(dwave, _adjoint_consts(n_fft, win, dev)["invT"], d_er, B=B, M=T, Ls=L, sig_batch_stride=L, hop=hop,
-                            padl=n_fft // 2 - (n_fft - win) // 2, K=win, N=2 * F, o_batch_stride=T * F, ldm=F, ldn=1, mode=0,
-                            out2=d_ei, nsplit=F)
+            d_er, d_ei = _istft_adjoint(dwave, T, F, n_fft, hop, win)
             ops.spec_loss_bwd(er, ei, cr, ci, Sm, d_er, d_ei, F, F, 1, accumulate=True, scale=0.5)
             ctx.grads = (d_er, d_ei)
         aux = losses[1:].clone()
@@ -499,10 +550,8 @@ class EnhancerLossFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_total, _g_aux, _g_wav):
-        d_er, d_ei = ctx.grads
-        ctx.grads = None
-        s = g_total.float()
-        return (d_er * s).to(ctx.dtypes[0]), (d_ei * s).to(ctx.dtypes[1]), None, None, None, None, None, None
+        grads, ctx.grads = ctx.grads, None
+        return _scaled_grads(grads, g_total, ctx.dtypes, 8)
 
 
 # ---- the objective's three terms as stand-alone nodes (the reference's si_snr_loss / MultiResolutionSTFTLoss /
@@ -536,7 +585,7 @@ class SiSnrFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         d, ctx.grad = ctx.grad, None
-        return (None if d is None else (d * g.float()).to(ctx.dtype)), None
+        return _scaled_grads((d,), g, (ctx.dtype,), 2)
 
 
 class MrStftFunction(torch.autograd.Function):
@@ -553,28 +602,8 @@ class MrStftFunction(torch.autograd.Function):
         need_grad = predicted.requires_grad
         Sr = torch.zeros(R, 4, device=dev, dtype=torch.float64)
         dwave = torch.zeros(B, L, device=dev, dtype=torch.float32) if need_grad else None
-        counts = []
-        for i, (nf, hp, wn) in enumerate(sizes):
-            split = LOSS_STFT_SPLIT16 and nf == wn and nf % 256 == 0
-            stft_ = Fn.stft_split16 if split else Fn.stft
-            pr, pi = stft_(pw, nf, hp, wn)
-            tr, ti = stft_(tw, nf, hp, wn)
-            ops.spec_sums(pr, pi, tr, ti, out=Sr[i])
-            counts.append(pr.numel())
-            if need_grad:
-                Tr, Fr = pr.shape[1], pr.shape[2]
-                Mr = B * Tr
-                ld = ops.round_up(2 * Fr, 8)
-                g = torch.zeros(Mr, ld, device=dev, dtype=torch.float32)
-                ops.spec_loss_bwd(pr, pi, tr, ti, Sr[i], g, g[:, Fr:], Fr, ld, 0, scale=1.0 / R)
-                frames = torch.empty(Mr, wn, device=dev, dtype=torch.float32)
-                if split:
-                    ops.framed_gemm_split16(g, _adjoint_consts(nf, wn, dev)["fwdT16"], frames, B=1, M=Mr, Ls=Mr * ld,
-                                            sig_batch_stride=0, hop=ld, padl=0, o_batch_stride=0, ldm=wn, mode=0)
-                else:
-                    ops.framed_gemm(g, _adjoint_consts(nf, wn, dev)["fwdT"], frames, B=1, M=Mr, Ls=Mr * ld, sig_batch_stride=0,
-                                    hop=ld, padl=0, K=2 * Fr, N=wn, o_batch_stride=0, ldm=wn, ldn=1, mode=0)
-                ops.stft_adjoint_ola(frames, dwave, B, Tr, L, nf, hp, wn, accumulate=True)
+        counts = [_mr_stft_pass(pw, tw, (nf, hp, wn), LOSS_STFT_SPLIT16 and nf == wn and nf % 256 == 0, Sr[i], dwave, 1.0 / R)
+                  for i, (nf, hp, wn) in enumerate(sizes)]
         nr = Fn.counts_tensor(tuple(counts), dev)
         losses = ops.enhancer_loss_finalize(_dummy_moments(dev), Sr[0], Sr, nr, 1, 1, 1)
         ctx.grad = dwave.reshape(predicted.shape) if need_grad else None
@@ -584,7 +613,7 @@ class MrStftFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         d, ctx.grad = ctx.grad, None
-        return (None if d is None else (d * g.float()).to(ctx.dtype)), None, None
+        return _scaled_grads((d,), g, (ctx.dtype,), 3)
 
 
 class L1MagnitudeFunction(torch.autograd.Function):
@@ -592,7 +621,7 @@ class L1MagnitudeFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, er, ei, cr, ci):
-        a = [t.detach().float().contiguous() for t in (er, ei, cr, ci)]
+        a = [_f32(t) for t in (er, ei, cr, ci)]
         dev = a[0].device
         Sm = ops.spec_sums(*a)
         nr = torch.ones(1, device=dev, dtype=torch.int64)
@@ -609,11 +638,8 @@ class L1MagnitudeFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        if ctx.grads is None:
-            return None, None, None, None
-        d_er, d_ei = ctx.grads
-        ctx.grads = None
-        return (d_er * g.float()).to(ctx.dtypes[0]), (d_ei * g.float()).to(ctx.dtypes[1]), None, None
+        grads, ctx.grads = ctx.grads, None
+        return _scaled_grads(grads, g, ctx.dtypes, 4)
 
 
 class PerceptualStoiFunction(torch.autograd.Function):
@@ -625,23 +651,18 @@ class PerceptualStoiFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, enh, enh_im, clean, clean_im, band_w, frame_len, beta):
         pair = enh_im is not None
-        f32 = lambda t: t.detach().float().contiguous()
-        e = (f32(enh), f32(enh_im)) if pair else f32(enh)
-        c = (f32(clean), f32(clean_im)) if pair else f32(clean)
+        e = (_f32(enh), _f32(enh_im)) if pair else _f32(enh)
+        c = (_f32(clean), _f32(clean_im)) if pair else _f32(clean)
         need = enh.requires_grad or (pair and enh_im.requires_grad)
-        loss, grad = ops.pstoi_loss(e, c, f32(band_w), need_grad=need, frame_len=frame_len, beta=beta)
+        loss, grad = ops.pstoi_loss(e, c, _f32(band_w), need_grad=need, frame_len=frame_len, beta=beta)
         ctx.grads = grad if (grad is None or pair) else (grad, None)
         ctx.dtypes = (enh.dtype, enh_im.dtype if pair else None)
         return loss[0].clone()
 
     @staticmethod
     def backward(ctx, g):
-        if ctx.grads is None:
-            return (None,) * 7
-        d0, d1 = ctx.grads
-        ctx.grads = None
-        g = g.float()
-        return ((d0 * g).to(ctx.dtypes[0]), None if d1 is None else (d1 * g).to(ctx.dtypes[1]), None, None, None, None, None)
+        grads, ctx.grads = ctx.grads, None
+        return _scaled_grads(grads, g, ctx.dtypes, 7)
 
 
 class MseFunction(torch.autograd.Function):
@@ -650,15 +671,14 @@ class MseFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, predicted, target):
-        p, t = predicted.detach().float().contiguous(), target.detach().float().contiguous()
-        loss, grad = ops.mse_loss(p, t, need_grad=predicted.requires_grad)
+        loss, grad = ops.mse_loss(_f32(predicted), _f32(target), need_grad=predicted.requires_grad)
         ctx.grad, ctx.dtype = grad, predicted.dtype
         return loss[0].clone()
 
     @staticmethod
     def backward(ctx, g):
         d, ctx.grad = ctx.grad, None
-        return (None if d is None else (d * g.float()).to(ctx.dtype)), None
+        return _scaled_grads((d,), g, (ctx.dtype,), 2)
 
 
 class ComplexMulFunction(torch.autograd.Function):
@@ -667,7 +687,7 @@ class ComplexMulFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, sr, si, mr, mi):
-        a = [t.detach().float().contiguous() for t in (sr, si, mr, mi)]
+        a = [_f32(t) for t in (sr, si, mr, mi)]
         ctx.saved = a
         ctx.dtypes = [t.dtype for t in (sr, si, mr, mi)]
         er, ei = ops.complex_mul(*a)
@@ -688,17 +708,18 @@ class ComplexMulFunction(torch.autograd.Function):
 # ---------------------------------------------------------------------------
 # stand-alone sub-modules (models/conformer.py:28-128) in training mode: the same forward / backward pieces as the block
 # ---------------------------------------------------------------------------
+# kind: (prefix of its parameters in _NAMES, forward(x32, P, B, T, H, p, seeds, bn) -> (y, saved), backward(dy32, saved, G) -> (dx, _));
+# bn = (bn_buffers, momentum, eps, bn_eval)
 _SUB = {
-    "ffn": ("ff1.", ["layer_norm.weight", "layer_norm.bias", "linear1.weight", "linear1.bias", "linear2.weight", "linear2.bias"]),
-    "mhsa": ("mhsa.", ["layer_norm.weight", "layer_norm.bias", "attention.in_proj_weight", "attention.in_proj_bias",
-                       "attention.out_proj.weight", "attention.out_proj.bias"]),
-    "conv": ("conv.", ["layer_norm.weight", "layer_norm.bias", "pointwise1.weight", "pointwise1.bias", "depthwise.weight",
-                       "depthwise.bias", "batch_norm.weight", "batch_norm.bias", "pointwise2.weight", "pointwise2.bias"]),
+    "ffn": ("ff1.", lambda x, P, B, T, H, p, seeds, bn: _ffn_fwd(x, P, "ff1.", p, seeds), lambda dy, c, G: _ffn_bwd(dy, c, G, "ff1.")),
+    "mhsa": ("mhsa.", lambda x, P, B, T, H, p, seeds, bn: _mhsa_fwd(x, P, B, T, H, p, seeds), _mhsa_bwd),
+    "conv": ("conv.", lambda x, P, B, T, H, p, seeds, bn: _conv_fwd(x, P, B, T, p, seeds, *bn), _conv_bwd),
 }
 
 
 def submodule_param_names(kind):
-    return list(_SUB[kind][1])
+    prefix = _SUB[kind][0]
+    return [n[len(prefix):] for n in _NAMES if n.startswith(prefix)]
 
 
 class SubmoduleFunction(torch.autograd.Function):
@@ -707,17 +728,11 @@ class SubmoduleFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, meta, *params):
         kind, H, p, seed, bn_buffers, momentum, eps, bn_eval = meta
-        prefix, names = _SUB[kind]
+        prefix, fwd, _ = _SUB[kind]
         B, T, D = x.shape
-        P = {prefix + n: t for n, t in zip(names, params)}
+        P = {prefix + n: t for n, t in zip(submodule_param_names(kind), params)}
         x32 = x.detach().float().reshape(B * T, D).contiguous()
-        seeds = _Seeds(seed)
-        if kind == "ffn":
-            y, c = _ffn_fwd(x32, P, prefix, p, seeds)
-        elif kind == "mhsa":
-            y, c = _mhsa_fwd(x32, P, B, T, H, p, seeds)
-        else:
-            y, c = _conv_fwd(x32, P, B, T, p, seeds, bn_buffers, momentum, eps, bn_eval)
+        y, c = fwd(x32, P, B, T, H, p, _Seeds(seed), (bn_buffers, momentum, eps, bn_eval))
         ctx.saved, ctx.P, ctx.kind = c, P, kind
         ctx.shape, ctx.in_dtype, ctx.param_dtypes = (B, T, D), x.dtype, [t.dtype for t in params]
         return y.reshape(B, T, D).to(x.dtype)
@@ -725,16 +740,10 @@ class SubmoduleFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         B, T, D = ctx.shape
-        prefix, names = _SUB[ctx.kind]
-        G = _zero_grads({prefix + n: ctx.P[prefix + n].shape for n in names}, dy.device)
-        d = dy.detach().float().reshape(B * T, D).contiguous()
-        if ctx.kind == "ffn":
-            dx, _ = _ffn_bwd(d, ctx.saved, G, prefix)
-        elif ctx.kind == "mhsa":
-            dx, _ = _mhsa_bwd(d, ctx.saved, G)
-        else:
-            dx, _ = _conv_bwd(d, ctx.saved, G)
-        grads = [G[prefix + n].to(t) for n, t in zip(names, ctx.param_dtypes)]
+        bwd = _SUB[ctx.kind][2]
+        G = _zero_grads({k: t.shape for k, t in ctx.P.items()}, dy.device)
+        dx, _ = bwd(dy.detach().float().reshape(B * T, D).contiguous(), ctx.saved, G)
+        grads = [g.to(t) for g, t in zip(G.values(), ctx.param_dtypes)]
         ctx.saved = None
         return (dx.reshape(B, T, D).to(ctx.in_dtype), None) + tuple(grads)
 
@@ -747,7 +756,7 @@ class GeluFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x):
-        x32 = x.detach().float().contiguous()
+        x32 = _f32(x)
         y = torch.empty_like(x32)
         ops.ew_train(ops.EW_GELU_FWD, y, z=x32)
         ctx.saved = x32
@@ -758,7 +767,7 @@ class GeluFunction(torch.autograd.Function):
     def backward(ctx, dy):
         x32 = ctx.saved
         dx = torch.empty_like(x32)
-        ops.ew_train(ops.EW_GELU_BWD, dx, z=x32, g=dy.detach().float().contiguous())
+        ops.ew_train(ops.EW_GELU_BWD, dx, z=x32, g=_f32(dy))
         ctx.saved = None
         return dx.to(ctx.in_dtype)
 
@@ -768,7 +777,7 @@ class LayerNormFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, b):
-        x32 = x.detach().float().contiguous()
+        x32 = _f32(x)
         lw, lb = _f32(w), _f32(b)
         y = torch.empty_like(x32)
         ops.layernorm(x32, lw, lb, out32=y)
@@ -782,7 +791,7 @@ class LayerNormFunction(torch.autograd.Function):
         D = lw.numel()
         dg = torch.zeros(D, device=dy.device, dtype=torch.float32)
         db = torch.zeros(D, device=dy.device, dtype=torch.float32)
-        dx = ops.layernorm_bwd(x32, lw, dy.detach().float().contiguous(), None, dg, db)
+        dx = ops.layernorm_bwd(x32, lw, _f32(dy), None, dg, db)
         t = ctx.dtypes
         ctx.saved = None
         return dx.to(t[0]), dg.to(t[1]), db.to(t[2])
@@ -798,9 +807,7 @@ class MaskHeadFunction(torch.autograd.Function):
     def forward(ctx, lm, lp, mag_bias, B, T, phase_scale):
         merged = lp is None
         if merged:
-            lg = lm.detach().float()
-            if lg.stride(1) != 1:
-                lg = lg.contiguous()
+            lg = _rows32(lm)
             F = lg.shape[-1] // 2
             lm32, lp32 = lg[:, :F], lg[:, F:]
         else:
@@ -808,7 +815,7 @@ class MaskHeadFunction(torch.autograd.Function):
             if lm32.stride(1) != 1 or lp32.stride(1) != 1 or lm32.stride(0) != lp32.stride(0):
                 lm32, lp32 = lm32.contiguous(), lp32.contiguous()
             F = lm32.shape[-1]
-        bias = mag_bias.detach().float().contiguous() if mag_bias is not None else None
+        bias = _f32(mag_bias)
         mr = torch.empty(B, T, F, device=lm.device, dtype=torch.float32)
         mi = torch.empty(B, T, F, device=lm.device, dtype=torch.float32)
         ops.polar_mask(lm32, lp32, B, T, F, phase_scale, lm32.stride(0), mag_bias=bias, mr=mr, mi=mi)
@@ -823,7 +830,7 @@ class MaskHeadFunction(torch.autograd.Function):
         M = B * T
         ld = ops.round_up(2 * F, 8)
         dl = torch.empty(M, ld, device=lm32.device, dtype=torch.float32)
-        ops.polar_mask_bwd(lm32, lp32, None, None, dmr.detach().float().contiguous(), dmi.detach().float().contiguous(), dl, M, F,
+        ops.polar_mask_bwd(lm32, lp32, None, None, _f32(dmr), _f32(dmi), dl, M, F,
                            ps, lm32.stride(0), mag_bias=bias, rows_per_batch=T)
         db = None
         if bias is not None and ctx.needs_input_grad[2]:
@@ -832,6 +839,27 @@ class MaskHeadFunction(torch.autograd.Function):
         if merged:
             return dl[:, :2 * F].to(t0), None, db, None, None, None
         return dl[:, :F].to(t0), dl[:, F:2 * F].to(t1), db, None, None, None
+
+
+def _fusion_bwd(ctx, dy, n_src, c0, aligned=False):
+    """what the backward of the two fusion-input nodes share: the Linear backward on the saved [M, FUSE_LD] operand and, from
+    column c0 of the input gradient df [M, K] on, the noisy STFT's share through sfm_stft_lognorm_bwd.  The node has n_src source
+    inputs (the last two: noisy_real, noisy_imag) followed by W, b; aligned: df gets 16-byte aligned rows, for a caller that
+    hands column blocks of it back as they lie.  -> (df, or None when no source needs a gradient; the n_src source gradients,
+    the last two filled in; dW; db), each in its input's dtype.  Releases ctx.saved."""
+    fused16, w32, nr, ni = ctx.saved
+    need, t = ctx.needs_input_grad, ctx.dtypes
+    (M, K), F = (dy.shape[0], w32.shape[1]), nr.shape[-1]
+    want = any(need[:n_src])
+    buf = torch.empty(M, ops.round_up(K, 8), device=dy.device, dtype=torch.float32)[:, :K] if want and aligned else None
+    df, dW, db, _ = _linear_bwd(dy, fused16, w32, dx_out=buf, want_dx=want)                    # df [M, K] fp32
+    grads = [None] * n_src
+    if want and (need[n_src - 2] or need[n_src - 1]):
+        dre, dim_ = ops.stft_lognorm_bwd(nr.reshape(M, F), ni.reshape(M, F), df[:, c0:], M, F)
+        grads[-2] = dre.reshape(nr.shape).to(t[n_src - 2]) if need[n_src - 2] else None
+        grads[-1] = dim_.reshape(nr.shape).to(t[n_src - 1]) if need[n_src - 1] else None
+    ctx.saved = None
+    return df, grads, dW.to(t[n_src]), db.to(t[n_src + 1])
 
 
 class FusionInputLinearFunction(torch.autograd.Function):
@@ -859,24 +887,10 @@ class FusionInputLinearFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        fused16, w32, nr, ni = ctx.saved
         B, D, T, N, K, oc, F = ctx.dims
-        M = B * T
-        dev = dy.device
-        dy = dy.float()
-        if dy.stride(1) != 1:
-            dy = dy.contiguous()
-        Np = ops.round_up(N, 64)
-        dy16 = torch.empty(M, Np, device=dev, dtype=ops.compute_dtype())
-        ops.convert_rows(dy, dy16, M, N, Np, dy.stride(0), Np)
-        dW = torch.zeros(N, K, device=dev, dtype=torch.float32)
-        db = torch.zeros(N, device=dev, dtype=torch.float32)
-        ops.gemm16_tn(dy16[:, :N], fused16[:, :K], dW, db)
-        need = ctx.needs_input_grad
-        t = ctx.dtypes
-        grads = [None] * 8
-        if any(need[:8]):
-            df = ops.linear16(dy16, ops.pack_linear(w32.t().contiguous(), k_pad_to=Np), out_dtype=torch.float32)   # [M, K]
+        need, t = ctx.needs_input_grad, ctx.dtypes
+        df, grads, dW, db = _fusion_bwd(ctx, dy, 8, 2 * D + 4 * oc)
+        if df is not None:
             dfb = df.reshape(B, T, -1)
             for i in (0, 1):
                 if need[i]:
@@ -884,13 +898,7 @@ class FusionInputLinearFunction(torch.autograd.Function):
             for i in range(4):
                 if need[2 + i]:
                     grads[2 + i] = dfb[..., 2 * D + i * oc:2 * D + (i + 1) * oc].to(t[2 + i])
-            if need[6] or need[7]:
-                c0 = 2 * D + 4 * oc
-                dre, dim_ = ops.stft_lognorm_bwd(nr.reshape(M, F), ni.reshape(M, F), df[:, c0:], M, F)
-                grads[6] = dre.reshape(B, T, F).to(t[6]) if need[6] else None
-                grads[7] = dim_.reshape(B, T, F).to(t[7]) if need[7] else None
-        ctx.saved = None
-        return (*grads, dW.to(t[8]), db.to(t[9]))
+        return (*grads, dW, db)
 
 
 class FusionInputPackedFunction(torch.autograd.Function):
@@ -907,14 +915,10 @@ class FusionInputPackedFunction(torch.autograd.Function):
         C4 = cp_all.shape[-1]
         dt = ops.compute_dtype()
         fused16 = torch.empty(M, Fn.FUSE_LD, device=zcat.device, dtype=dt)
-        z32, c32 = zcat.detach().float().reshape(M, D2), cp_all.detach().float().reshape(M, C4)
-        if z32.stride(1) != 1:
-            z32 = z32.contiguous()
-        if c32.stride(1) != 1:
-            c32 = c32.contiguous()
+        z32, c32 = _rows32(zcat.detach().float().reshape(M, D2)), _rows32(cp_all.detach().float().reshape(M, C4))
         ops.convert_rows(z32, fused16, M, D2, D2, z32.stride(0), Fn.FUSE_LD)
         ops.convert_rows(c32, fused16[:, D2:], M, C4, C4, c32.stride(0), Fn.FUSE_LD)
-        nr, ni = noisy_real.detach().float().contiguous(), noisy_imag.detach().float().contiguous()
+        nr, ni = _f32(noisy_real), _f32(noisy_imag)
         F = nr.shape[-1]
         col = D2 + C4
         ops.stft_lognorm_pack(nr, ni, fused16[:, col:], M, F, Fn.FUSE_LD - col - 2 * F, Fn.FUSE_LD)
@@ -928,35 +932,14 @@ class FusionInputPackedFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        fused16, w32, nr, ni = ctx.saved
         B, T, D2, C4, N, K, F = ctx.dims
-        M = B * T
-        dev = dy.device
-        dy = dy.float()
-        if dy.stride(1) != 1:
-            dy = dy.contiguous()
-        Np = ops.round_up(N, 64)
-        dy16 = torch.empty(M, Np, device=dev, dtype=ops.compute_dtype())
-        ops.convert_rows(dy, dy16, M, N, Np, dy.stride(0), Np)
-        dW = torch.zeros(N, K, device=dev, dtype=torch.float32)
-        db = torch.zeros(N, device=dev, dtype=torch.float32)
-        ops.gemm16_tn(dy16[:, :N], fused16[:, :K], dW, db)
-        need = ctx.needs_input_grad
-        t = ctx.dtypes
-        g = [None] * 4
-        if any(need[:4]):
-            df = torch.empty(M, ops.round_up(K, 8), device=dev, dtype=torch.float32)[:, :K]      # 16-byte aligned rows
-            ops.linear16(dy16, ops.pack_linear(w32.t().contiguous(), k_pad_to=Np), out=df)          # [M, K]
-            if need[0]:
-                g[0] = df[:, :D2].reshape(B, T, D2).to(t[0])                 # row-strided views of df
-            if need[1]:
-                g[1] = df[:, D2:D2 + C4].reshape(B, T, C4).to(t[1])
-            if need[2] or need[3]:
-                dre, dim_ = ops.stft_lognorm_bwd(nr.reshape(M, F), ni.reshape(M, F), df[:, D2 + C4:], M, F)
-                g[2] = dre.reshape(B, T, F).to(t[2]) if need[2] else None
-                g[3] = dim_.reshape(B, T, F).to(t[3]) if need[3] else None
-        ctx.saved = None
-        return (*g, dW.to(t[4]), db.to(t[5]))
+        need, t = ctx.needs_input_grad, ctx.dtypes
+        df, g, dW, db = _fusion_bwd(ctx, dy, 4, D2 + C4, aligned=True)
+        if need[0]:
+            g[0] = df[:, :D2].reshape(B, T, D2).to(t[0])                     # row-strided views of df
+        if need[1]:
+            g[1] = df[:, D2:D2 + C4].reshape(B, T, C4).to(t[1])
+        return (*g, dW, db)
 
 
 class LatentFanoutFunction(torch.autograd.Function):
@@ -976,9 +959,7 @@ class LatentFanoutFunction(torch.autograd.Function):
             return g_all, None
         B, T = g_half.shape[0], g_half.shape[1]
         M = B * T
-        gh = g_half.float().reshape(M, D)
-        if gh.stride(1) != 1:
-            gh = gh.contiguous()
+        gh = _rows32(g_half.float().reshape(M, D))
         if g_all is None:
             out = torch.zeros(B, T, 2 * D, device=g_half.device, dtype=torch.float32)
             out[..., :D].copy_(gh.reshape(B, T, D))
@@ -1029,9 +1010,7 @@ class BiLSTMLayerFunction(torch.autograd.Function):
         H = whf.shape[1]
         M = B * T
         dt = ops.compute_dtype()
-        x32 = x.detach().float()
-        if x32.stride(2) != 1 or x32.stride(0) != T * x32.stride(1):              # (a column slice of a wider row is fine as it is)
-            x32 = x32.contiguous()
+        x32 = _rows32(x, batched=True)                                               # (a column slice of a wider row is fine as it is)
         wih = torch.cat([_f32(wif), _f32(wir)], dim=0)                               # [8H, Din]
         bias = torch.cat([_f32(bif) + _f32(bhf), _f32(bir) + _f32(bhr)], dim=0)
         whh = torch.stack([_f32(whf), _f32(whr)], dim=0).contiguous()                # [2, 4H, H]
@@ -1049,14 +1028,10 @@ class BiLSTMLayerFunction(torch.autograd.Function):
         x16, wih, whh, save, h = ctx.saved
         B, T, Din, H = ctx.dims
         M = B * T
-        dev, dt = dh.device, ops.compute_dtype()
-        dxg = ops.bilstm_layer_bwd(save, whh, dh.detach().float().contiguous(), B, T, H).reshape(M, 8 * H)
-        dxg16 = torch.empty(M, 8 * H, device=dev, dtype=dt)
-        ops.convert_rows(dxg, dxg16, M, 8 * H, 8 * H, 8 * H, 8 * H)
-        dwih = torch.zeros(8 * H, Din, device=dev, dtype=torch.float32)
-        db = torch.zeros(8 * H, device=dev, dtype=torch.float32)
-        ops.gemm16_tn(dxg16, x16, dwih, db)
-        dx = ops.linear16(dxg16, ops.pack_linear(wih.t().contiguous()), out_dtype=torch.float32).reshape(B, T, Din)
+        dev = dh.device
+        dxg = ops.bilstm_layer_bwd(save, whh, _f32(dh), B, T, H).reshape(M, 8 * H)
+        dx, dwih, db, dxg16 = _linear_bwd(dxg, x16, wih)                          # 8H is a multiple of 64: dxg16 has no padding columns
+        dx = dx.reshape(B, T, Din)
         # dW_hh[dir] = sum_t da[t] (x) h_prev[t]: the chain's previous output (zero at its first step)
         hp16 = ops.lstm_hprev16(h, B, T, H)
         dwhh = torch.zeros(2, 4 * H, H, device=dev, dtype=torch.float32)
@@ -1074,7 +1049,7 @@ class DropoutFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, p, seed):
-        x32 = x.detach().float().contiguous()
+        x32 = _f32(x)
         y = torch.empty_like(x32)
         n = x32.shape[-1]
         ops.ew_train(ops.EW_SCALE_DROP, y.reshape(-1, n), g=x32.reshape(-1, n), alpha=1.0, p=p, seed=seed)
@@ -1084,7 +1059,7 @@ class DropoutFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         p, seed, dtp = ctx.meta
-        d = dy.detach().float().contiguous()
+        d = _f32(dy)
         dx = torch.empty_like(d)
         n = d.shape[-1]
         ops.ew_train(ops.EW_SCALE_DROP, dx.reshape(-1, n), g=d.reshape(-1, n), alpha=1.0, p=p, seed=seed)
@@ -1098,12 +1073,9 @@ class CpeaHeadsFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, W, b):
-        import math
         M, K = x.shape
         N = W.shape[0]
-        x32 = x.detach().float()
-        if x32.stride(1) != 1:
-            x32 = x32.contiguous()
+        x32 = _rows32(x)
         w32 = _f32(W)
         x16 = torch.empty(M, K, device=x.device, dtype=ops.compute_dtype())
         ops.convert_rows(x32, x16, M, K, K, x32.stride(0), K)
@@ -1115,20 +1087,10 @@ class CpeaHeadsFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        import math
         x16, w32, y = ctx.saved
-        M, K = x16.shape
-        N = w32.shape[0]
-        dev = dy.device
-        dz = torch.empty(M, N, device=dev, dtype=torch.float32)
-        ops.ew_train(ops.EW_CPEA_BWD, dz, z=y, g=dy.detach().float().contiguous(), alpha=math.pi)
-        Np = ops.round_up(N, 64)
-        dz16 = torch.empty(M, Np, device=dev, dtype=ops.compute_dtype())
-        ops.convert_rows(dz, dz16, M, N, Np, N, Np)
-        dW = torch.zeros(N, K, device=dev, dtype=torch.float32)
-        db = torch.zeros(N, device=dev, dtype=torch.float32)
-        ops.gemm16_tn(dz16[:, :N], x16, dW, db)
-        dx = ops.linear16(dz16, ops.pack_linear(w32.t().contiguous(), k_pad_to=Np), out_dtype=torch.float32)
+        dz = torch.empty_like(y)
+        ops.ew_train(ops.EW_CPEA_BWD, dz, z=y, g=_f32(dy), alpha=math.pi)
+        dx, dW, db, _ = _linear_bwd(dz, x16, w32)
         t = ctx.dtypes
         ctx.saved = None
         return dx.to(t[0]), dW.to(t[1]), db.to(t[2])
@@ -1177,7 +1139,7 @@ class MemoryFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, emb, temperature, *params):
-        e = emb.detach().float().contiguous()
+        e = _f32(emb)
         blob = torch.cat([_f32(p).reshape(-1) for p in params]).contiguous()
         kd, vd, S = params[0].shape[0], params[7].shape[1], params[6].shape[0]
         bias, gate, top, sim = ops.memory_fwd(e, blob, kd, vd, S, temperature)
@@ -1191,16 +1153,10 @@ class MemoryFunction(torch.autograd.Function):
         e, blob = ctx.saved
         kd, vd, S, temp, shapes, dtypes, edt = ctx.meta
         Bn = e.shape[0]
-        dob = d_bias.detach().float().contiguous() if d_bias is not None else torch.zeros(Bn, vd, device=e.device)
+        dob = _f32(d_bias) if d_bias is not None else torch.zeros(Bn, vd, device=e.device)
         dg = d_gate.detach().float().reshape(Bn).contiguous() if d_gate is not None else None
         d_emb, dblob = ops.memory_bwd(e, blob, dob, dg, kd, vd, S, temp, want_d_emb=ctx.needs_input_grad[0])
-        outs, off = [], 0
-        for shp, dt in zip(shapes, dtypes):
-            k = 1
-            for d_ in shp:
-                k *= d_
-            outs.append(dblob[off:off + k].view(shp).to(dt))
-            off += k
+        outs = [v.to(dt) for v, dt in zip(_flat_views(shapes, flat=dblob), dtypes)]
         ctx.saved = None
         return (d_emb.to(edt) if d_emb is not None else None, None, *outs)
 
@@ -1215,13 +1171,13 @@ def memory_train_forward(mem, emb):
 
 class IstftFunction(torch.autograd.Function):
     """batch_istft (training/conformer_pipeline.py:205-211) with its adjoint: irfft-by-matrix + overlap-add forward;
-    backward = frames-x-matrix product of g / envelope with the transposed operand (the objective's own path in
-    EnhancerLossFunction does the same inline)."""
+    backward = frames-x-matrix product of g / envelope with the transposed operand (_istft_adjoint, which the objective's own
+    path in EnhancerLossFunction ends in as well)."""
 
     @staticmethod
     def forward(ctx, real, imag, length, n_fft, hop, win):
         from . import functional as Fn
-        r, i = real.detach().float().contiguous(), imag.detach().float().contiguous()
+        r, i = _f32(real), _f32(imag)
         ctx.meta = (tuple(r.shape), length, n_fft, hop, win, real.dtype, imag.dtype)
         return Fn.istft(r, i, length, n_fft, hop, win)
 
@@ -1229,11 +1185,7 @@ class IstftFunction(torch.autograd.Function):
     def backward(ctx, g):
         (B, T, F), L, n_fft, hop, win, d0, d1 = ctx.meta
         genv = (g.detach().float() * _inv_envelope(L, T, n_fft, hop, win, g.device)).contiguous()
-        dr = torch.empty(B, T, F, device=g.device, dtype=torch.float32)
-        di = torch.empty(B, T, F, device=g.device, dtype=torch.float32)
-        ops.framed_gemm(genv, _adjoint_consts(n_fft, win, g.device)["invT"], dr, B=B, M=T, Ls=L, sig_batch_stride=L, hop=hop,
-                        padl=n_fft // 2 - (n_fft - win) // 2, K=win, N=2 * F, o_batch_stride=T * F, ldm=F, ldn=1, mode=0,
-                        out2=di, nsplit=F)
+        dr, di = _istft_adjoint(genv, T, F, n_fft, hop, win)
         return dr.to(d0), di.to(d1), None, None, None, None
 
 
@@ -1436,7 +1388,7 @@ class PoolTimeFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, Tout):
-        x = x.detach().float().contiguous()
+        x = _f32(x)
         B, Tin, C = x.shape
         out = torch.empty(B, Tout, C, device=x.device, dtype=torch.float32)
         ops.pool_time(x, None, out, B, Tin, Tout, C, C, C)
@@ -1455,10 +1407,8 @@ class MeanTimeFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x):
-        x32 = x.detach().float()
+        x32 = _rows32(x, batched=True)
         B, T, C = x32.shape
-        if x32.stride(2) != 1 or x32.stride(0) != T * x32.stride(1):
-            x32 = x32.contiguous()
         ctx.dims = (B, T, C, x.dtype)
         return ops.mean_time(x32, B, T, C, x32.stride(1))
 
@@ -1506,7 +1456,7 @@ class MaaFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, sigma, stats, w1, b1, w2, b2, w3, b3):
-        s = sigma.detach().float().contiguous()
+        s = _f32(sigma)
         params = torch.cat([_f32(w1).reshape(-1), _f32(b1), _f32(w2).reshape(-1), _f32(b2), _f32(w3).reshape(-1), _f32(b3)]).contiguous()
         logits, probs, dec, conf = ops.maa_forward(s, stats, params)
         ctx.saved = (s, stats.clone(), params)
@@ -1518,15 +1468,9 @@ class MaaFunction(torch.autograd.Function):
     def backward(ctx, g_logits, g_probs, g_conf, _g_dec):
         s, stats, params = ctx.saved
         ctx.saved = None
-        c = lambda g: None if g is None else g.detach().float().contiguous()
-        dsig, dp = ops.maa_backward(s, stats, params, c(g_logits), c(g_probs), c(g_conf))
+        dsig, dp = ops.maa_backward(s, stats, params, _f32(g_logits), _f32(g_probs), _f32(g_conf))
         sdt, pdts, shapes = ctx.meta
-        outs, o = [], 0
-        for dt_, shp in zip(pdts, shapes):
-            n = int(torch.Size(shp).numel())
-            outs.append(dp[o:o + n].view(shp).to(dt_))
-            o += n
-        return (dsig.to(sdt), None) + tuple(outs)
+        return (dsig.to(sdt), None) + tuple(v.to(dt_) for v, dt_ in zip(_flat_views(shapes, flat=dp), pdts))
 
 
 class VQFunction(torch.autograd.Function):
@@ -1534,8 +1478,8 @@ class VQFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, centroids, beta):
-        xf = x.detach().float().contiguous()
-        cf = centroids.detach().float().contiguous()
+        xf = _f32(x)
+        cf = _f32(centroids)
         q, idx, acc = ops.vq_forward(xf, cf)
         loss = (acc[0] * ((1.0 + beta) / xf.numel())).float()
         ctx.saved = (xf, idx, cf)
@@ -1548,7 +1492,7 @@ class VQFunction(torch.autograd.Function):
         xf, idx, cf = ctx.saved
         ctx.saved = None
         beta, xdt, cdt = ctx.meta
-        gq = None if g_q is None else g_q.detach().float().contiguous()
+        gq = _f32(g_q)
         gl = None if g_loss is None else g_loss.detach().float().reshape(1).contiguous()
         dx, dcent = ops.vq_backward(xf, idx, cf, gq, gl, beta)
         return dx.to(xdt), dcent.to(cdt), None
@@ -1672,8 +1616,7 @@ class AdversarialFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, adv, mode, clean, clean_im, enh, enh_im, *params):
         pair = enh_im is not None
-        f32 = lambda t: None if t is None else t.detach().float().contiguous()
-        e, ei, c, ci = f32(enh), f32(enh_im), f32(clean), f32(clean_im)
+        e, ei, c, ci = _f32(enh), _f32(enh_im), _f32(clean), _f32(clean_im)
         if pair:
             B, T, F = e.shape
         else:

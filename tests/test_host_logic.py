@@ -212,6 +212,25 @@ def test_zero_grad_views_share_one_buffer_without_overlap():
     assert all(float(G[k].min()) == float(G[k].max()) == float(i + 1) for i, k in enumerate(G))
 
 
+def test_flat_views_dense_form_tiles_the_buffer_in_order():
+    """train._flat_views with align = 1 (the layout of the memory / arbitration kernels' gradient blobs): the views tile the
+    buffer exactly, in the order given, with no gap - 15 + 7 + 1 + 4096 = 4119 elements"""
+    from sincformer_metacog_speech_enhancement_amd import train
+    shapes = [(3, 5), (7,), (1,), (64, 64)]
+    flat = torch.arange(4119, dtype=torch.float32)
+    views = train._flat_views(shapes, flat=flat)
+    assert [tuple(v.shape) for v in views] == shapes
+    start = 0
+    for v in views:
+        assert v.data_ptr() == flat.data_ptr() + 4 * start and v.is_contiguous()
+        assert torch.equal(v.reshape(-1), flat[start:start + v.numel()])
+        start += v.numel()
+    assert start == flat.numel() == sum(v.numel() for v in views)
+    # without a buffer: a zero-filled one of exactly that size
+    own = train._flat_views(shapes, device=torch.device("cpu"))
+    assert own[-1].data_ptr() + 4 * own[-1].numel() - own[0].data_ptr() == 4 * 4119 and all(float(v.abs().max()) == 0.0 for v in own)
+
+
 def test_counts_tensor_is_cached_per_shape():
     """the objective's per-resolution element counts must not be re-uploaded every step (a pageable host copy synchronises)"""
     a = Fn.counts_tensor((10, 20, 30), torch.device("cpu"))

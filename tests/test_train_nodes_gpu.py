@@ -323,6 +323,65 @@ def test_complex_mul_function(train):
 
 
 # ---------------------------------------------------------------------------
+# LayerNorm -> Linear: the node that is nothing but the shared Linear backward (train._linear_bwd) around one GEMM
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("ln", [True, False], ids=["ln", "plain"])
+@pytest.mark.parametrize("M,K,N", [(130, 200, 10), (130, 256, 258)])
+def test_ln_linear_function(ops, train, dt, ln, M, K, N):
+    """LNLinearFunction: forward, dx, dW, db (and dgamma, dbeta) against float64 on the operands as the node rounds them: the GEMM
+    operand h16 the node saved (itself held to the float64 LayerNorm within one rounding by helpers.check_row16, or, without the
+    LayerNorm, to the bits of tensor.to() of the input), W and the
+    cotangent rounded to the operand format and, with the LayerNorm on, the 16-bit input gradient of the GEMM that its backward
+    reads.  130 rows: a partial 128-row tile; K 200: the zero-padded operand; N 10: both paddings of the cotangent; N 258 = 2F.
+    Bounds are those of tests/test_backward_gpu.py per result format: fp32 GEMM results (forward, dx of the plain Linear)
+    3e-3 max|ref| + 1e-3 (conv dgrad); what comes out of a 16-bit GEMM result (dx, dgamma, dbeta behind the LayerNorm)
+    (3e-3 + one rounding) max|ref| + 1e-3 (conv dgrad 16-bit out); dW 2e-3 sqrt(M / 1000) and db 1e-3 (gemm16_tn, with its
+    operand scales: cotangent 0.1, operand of unit size).  Observed: fp32 results and dW, db within 2e-6; behind the 16-bit
+    result within 1e-7 (bf16) and 2e-4 (fp16, where the float64 rounding of that result and the kernel's differ in a few elements)."""
+    ops.set_compute_dtype(dt)
+    rnd = 2.0 ** -8 if dt is torch.bfloat16 else 2.0 ** -11
+    q = lambda t: t.to(dt).double()
+    x = arr("ll_x", (M, K), 11, 2.0) + 0.3
+    lw, lb = arr("ll_g", (K,), 12) * 0.1 + 1, arr("ll_b", (K,), 13) * 0.1
+    W, b, cot = arr("ll_w", (N, K), 14) * K ** -0.5, arr("ll_c", (N,), 15) * 0.1, arr("ll_dy", (M, N), 16) * 0.1
+    g = {k: t.cuda().requires_grad_(True) for k, t in (("x", x), ("lw", lw), ("lb", lb), ("W", W), ("b", b)) if ln or k[0] != "l"}
+    y = train.LNLinearFunction.apply(g["x"], g.get("lw"), g.get("lb"), g["W"], g["b"])
+    assert y.shape == (M, N) and y.dtype == torch.float32
+    h16 = y.grad_fn.saved[3]                                  # [M, round_up(K, 64)], released by the backward
+    assert h16.dtype == dt and h16.shape == (M, ops.round_up(K, 64)) and not bool(h16[:, K:].any())
+    hq = h16[:, :K].double().cpu()
+    y.backward(cot.cuda())
+
+    r = {k: t.double().requires_grad_(True) for k, t in (("x", x), ("lw", lw), ("lb", lb))}
+    norm = lambda t: torch.nn.functional.layer_norm(t["x"], (K,), t["lw"], t["lb"], 1e-5) if ln else t["x"] * 1.0
+    h64 = norm(r)
+    if ln:
+        hp.check_row16("LNLinearFunction operand LayerNorm", hq, h64.detach(), norm({k: t.detach().float() for k, t in r.items()}),
+                       hp.K_TRANS, dt)
+    else:                                                     # the one rounding to nearest itself, fp16 subnormals included
+        assert torch.equal(h16[:, :K].cpu(), x.to(dt))
+    Wq, dyq = q(W), q(cot)
+    dh = dyq @ Wq                                             # [M, K]
+    want = {"y": (hq @ Wq.t() + b.double(), 0.0), "W": (dyq.t() @ hq, None), "b": (dyq.sum(0), None)}
+    if ln:
+        (h64 * q(dh)).sum().backward()                        # the LayerNorm backward reads the GEMM's 16-bit result
+        want.update({k: (r[k].grad, rnd) for k in ("x", "lw", "lb")})
+    else:
+        want["x"] = (dh, 0.0)
+    bad = []
+    for k, (ref, extra) in want.items():
+        got = (y.detach() if k == "y" else g[k].grad).cpu()
+        tol = {"W": 2e-3 * (M / 1000.0) ** 0.5, "b": 1e-3}.get(k) or (3e-3 + extra) * float(ref.abs().max()) + 1e-3
+        e = hp.maxerr(got, ref.detach())
+        print("LNLinearFunction %s %s M%d K%d N%d: %-2s max|err| %.2e (tol %.1e, max|ref| %.2e)"
+              % ("ln" if ln else "plain", dt, M, K, N, k, e, tol, float(ref.abs().max())))
+        if not (got.shape == ref.shape and e <= tol):
+            bad.append((k, e, tol))
+    assert not bad, bad
+
+
+# ---------------------------------------------------------------------------
 # BiLSTM: BPTT
 # ---------------------------------------------------------------------------
 def _arm_a(ops, row, tag=""):
