@@ -724,6 +724,33 @@ int sfm_feature_context(const float* feat, const float* mean, const float* stdv,
 int sfm_rows_mean(const float* in, const int* lengths, float* out, int B, int T, int L, int frame, int hop, long long ld_in,
                   int col_off, int N, int den, void* stream);
 
+/* CSII and NCM (intelligibility.hip; evaluation/csii.py and evaluation/ncm.py of the reference).  wave64, no atomics, every
+ * cross-thread sum in fp64 in a fixed order: the same bits from run to run and for an utterance alone or in any pack.
+ * sfm_csii_frames_varlen: cr, ci, er, ei = the planes [sum_frames, F] sfm_framed_gemm_f32_varlen wrote for the clean and the enhanced
+ *   pack with the Hamming rfft(., 256) operand, F = 129 (SFM_ERR_SHAPE otherwise); utterance b owns rows [frame_off[b], frame_off[b + 1]).
+ *   Per bin, over the utterance's frames in frame order: Pxx, Pyy, Pxy, divided by the frame count; msc = |Pxy|^2 / (Pxx Pyy + 1e-10)
+ *   clipped to [0, 1] -> msc [B, 129] (or NULL); score [B] = clip(sum_f weights[f] msc[f], 0, 1) in bin order, 0 without a frame.
+ * sfm_hilbert_env: x [R, L] fp32 -> env [R, L] = sqrt(x^2 + y^2), y = h (*) x circularly, h the kernel of scipy.signal.hilbert(.).imag.
+ *   table = 2 L floats.  Odd L: h twice back to back, y[n] = sum_m table[n - m + L] x[m].  Even L (every even lag of h is 0): two
+ *   convolutions of L / 2 samples, y[2 i + p] = sum_j table[p L + i - j + L / 2] x[2 j + 1 - p], i.e. g_p[d] = h[(2 d + 2 p - 1) mod L]
+ *   twice for p = 0, then for p = 1.  L >= 1, L < 2^30.
+ * sfm_hilbert_env_moments: X [2, B, C, L] fp32 (clean and enhanced sfm_gammatone_fir planes, 0 from lengths[b] on), C <= 64 (2 C <= 128
+ *   operand columns; SFM_ERR_SHAPE beyond); utterance b convolves over its own lengths[b] samples with the table at tables + tab_off[b]
+ *   (2 lengths[b] floats, as above).  tiles int32 [n_tiles][2] = (utterance, output tile of 256 samples of a convolution), utterance-
+ *   major, tiles ascending: ceil(L_b / 256) of an odd length, 2 ceil(L_b / 512) of an even one (p = 0, then p = 1);
+ *   partial [n_tiles, C, 5] fp64 = {sum ec, sum ee, sum ec^2, sum ee^2, sum ec ee} of the two envelopes over the tile's samples.
+ *   n_tiles = 0 launches nothing.
+ * sfm_ncm_finish: folds utterance b's tiles [tile_off[b], tile_off[b + 1]) in tile order; ncc [B, C] = cov / sqrt(var var) of the
+ *   envelopes (0 where that root is below 1e-10), clipped to [-1, 1]; score [B] = clip(sum_c weights[c] max(ncc, 0), 0, 1); an
+ *   utterance without a tile gets zeros. */
+int sfm_csii_frames_varlen(const float* cr, const float* ci, const float* er, const float* ei, const int* frame_off,
+                           const double* weights, double* score, double* msc, int B, int sum_frames, int F, void* stream);
+int sfm_hilbert_env(const float* x, const float* table, float* env, int R, int L, void* stream);
+int sfm_hilbert_env_moments(const float* X, const float* tables, const int* tab_off, const int* lengths, const int* tiles,
+                            double* partial, int B, int C, int L, int n_tiles, void* stream);
+int sfm_ncm_finish(const double* partial, const int* tile_off, const int* lengths, const double* weights, double* ncc, double* score,
+                   int B, int C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

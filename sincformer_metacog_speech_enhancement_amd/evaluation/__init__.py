@@ -1,6 +1,9 @@
-"""Batched, on-device counterparts of the reference's evaluation/ssnr.py and of the fallbacks of evaluation/stoi.py and
-evaluation/pesq_eval.py, and the three of them over a ragged set in packed passes."""
+"""Batched, on-device counterparts of the reference's evaluation/ssnr.py, evaluation/csii.py and evaluation/ncm.py and of the
+fallbacks of evaluation/stoi.py and evaluation/pesq_eval.py, and all of them over a ragged set in packed passes."""
 from .ssnr import compute_ssnr, compute_ssnr_improvement  # noqa: F401
 from .stoi import compute_stoi  # noqa: F401
 from .pesq_eval import compute_pesq  # noqa: F401
+from .csii import compute_csii  # noqa: F401
+from .ncm import compute_ncm, hilbert_envelope  # noqa: F401
 from .packed import compute_metrics_packed  # noqa: F401
+from .intelligibility import compute_intelligibility_packed  # noqa: F401

@@ -2407,3 +2407,133 @@ def adv_head_bwd(a16, w16, out, g, coef, cnorm, target, want_dw):
                                            B, T, C, _dt(), _stream()),
           (12.0 if want_dw else 6.0) * B * T * C, (4.0 + (2.0 if want_dw else 0.0)) * B * T * C + 4.0 * B * T + 6.0 * C)
     return da, dwb
+
+
+# ---------------------------------------------------------------------------
+# CSII and NCM (csrc/intelligibility.hip; evaluation/csii.py, evaluation/ncm.py)
+# ---------------------------------------------------------------------------
+CSII_BINS = 129                     # rfft(., 256) bins of the coherence
+HE_ROWS = 256                       # output samples per workgroup of the Hilbert kernel (its output tile)
+HE_KSTEP = 64                       # input samples per staged k-step (one accumulation segment)
+_HILBERT_TAB = {}                   # L -> fp32 [2 L], host (at most HILBERT_TAB_CACHE lengths)
+HILBERT_TAB_CACHE = 1024
+
+
+def hilbert_kernel_table(L):
+    """float64 [L]: h with scipy.signal.hilbert(x).imag[n] = sum_m h[(n - m) mod L] x[m]: imag(ifft(H)), H = 1 at bin 0 (and at
+    the Nyquist bin of an even L), 2 on the bins below L / 2, 0 above.  Host."""
+    L = int(L)
+    if L < 1:
+        raise ValueError("hilbert_kernel_table: L %d" % L)
+    H = np.zeros(L)
+    if L % 2 == 0:
+        H[0] = H[L // 2] = 1.0
+        H[1:L // 2] = 2.0
+    else:
+        H[0] = 1.0
+        H[1:(L + 1) // 2] = 2.0
+    return np.fft.ifft(H).imag
+
+
+def hilbert_table_host(L):
+    """fp32 [2 L], the kernels' table.  Odd L: h twice back to back, so that h[(n - m) mod L] = table[n - m + L].  Even L: every
+    even lag of h is exactly 0, so the outputs 2 i + p are a circular convolution of length L / 2 of the inputs 2 j + 1 - p with
+    g_p[d] = h[(2 d + 2 p - 1) mod L]: g_0 twice, then g_1 twice.  Cached on the host by length (shared: do not modify)."""
+    L = int(L)
+    t = _HILBERT_TAB.get(L)
+    if t is None:
+        h = hilbert_kernel_table(L).astype(np.float32)
+        if L % 2:
+            t = np.concatenate([h, h])
+        else:
+            d = np.arange(L // 2)
+            g0, g1 = h[(2 * d - 1) % L], h[(2 * d + 1) % L]
+            t = np.concatenate([g0, g0, g1, g1])
+        if len(_HILBERT_TAB) >= HILBERT_TAB_CACHE:
+            _HILBERT_TAB.clear()
+        _HILBERT_TAB[L] = t
+    return t
+
+
+def hilbert_table(lengths, device):
+    """the tables of `lengths` (an int or a sequence of ints) back to back, one upload: fp32 [2 sum L] on the device"""
+    lengths = [lengths] if np.isscalar(lengths) else list(lengths)
+    return torch.from_numpy(np.concatenate([hilbert_table_host(L) for L in lengths])).to(device)
+
+
+def hilbert_conv_len(L):
+    """samples of one circular convolution of a signal of L samples: L, or L / 2 (twice) for an even L"""
+    L = np.asarray(L, dtype=np.int64)
+    return np.where(L % 2 == 0, L // 2, L)
+
+
+def hilbert_tiles(lengths, min_len=1):
+    """host tables of sfm_hilbert_env_moments for utterances of `lengths` samples: (tiles int32 [n, 2] = (utterance, tile),
+    tile_off int32 [B + 1], sum over the tiles of their convolution's length); an odd length owns ceil(L / 256) tiles, an even one
+    2 ceil(L / 512) (the two half-size problems one after the other), an utterance shorter than min_len none"""
+    L = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    Lc = hilbert_conv_len(L)
+    nt = np.where(L >= min_len, np.where(L % 2 == 0, 2, 1) * -(-Lc // HE_ROWS), 0)
+    off = np.concatenate([[0], np.cumsum(nt)])
+    utt = np.repeat(np.arange(L.size), nt)
+    tile = np.arange(int(off[-1])) - np.repeat(off[:-1], nt)
+    return np.ascontiguousarray(np.stack([utt, tile], axis=1), dtype=np.int32), off.astype(np.int32), int((nt * Lc).sum())
+
+
+def csii_frames_varlen(cr, ci, er, ei, frame_off, weights, B, want_msc=False):
+    """packed spectra rows [sum_frames, 129] of the clean and the enhanced pack, weights [129] fp64 -> score [B] fp64 (and the
+    msc plane [B, 129] fp64)"""
+    _need_dev(cr, ci, er, ei, frame_off, weights)
+    L = _lib.load()
+    n, F = cr.shape
+    if F != CSII_BINS or any(t.shape != cr.shape or t.dtype != torch.float32 or not t.is_contiguous() for t in (cr, ci, er, ei)) or \
+            weights.dtype != torch.float64 or weights.numel() != CSII_BINS or frame_off.numel() != B + 1:
+        _lib.check(-2, "csii_frames_varlen")
+    score = torch.empty(B, device=cr.device, dtype=torch.float64)
+    msc = torch.empty(B, F, device=cr.device, dtype=torch.float64) if want_msc else None
+    _call("intelligibility", L.sfm_csii_frames_varlen, (_p(cr), _p(ci), _p(er), _p(ei), _p(frame_off), _p(weights), _p(score), _p(msc),
+                                                        B, n, F, _stream()), 14.0 * n * F, 16.0 * n * F)
+    return (score, msc) if want_msc else score
+
+
+def hilbert_env(x):
+    """x [R, L] fp32 -> [R, L] fp32 = |scipy.signal.hilbert(x)| along the last axis"""
+    _need_dev(x)
+    L_ = _lib.load()
+    if x.dim() != 2 or x.dtype != torch.float32 or not x.is_contiguous() or x.numel() == 0:
+        _lib.check(-2, "hilbert_env")
+    R, L = x.shape
+    env = torch.empty_like(x)
+    _call("hilbert_env", L_.sfm_hilbert_env, (_p(x), _p(hilbert_table(L, x.device)), _p(env), R, L, _stream()),
+          2.0 * R * L * int(hilbert_conv_len(L)), 8.0 * R * L + 8.0 * L, "R%d L%d" % (R, L))
+    return env
+
+
+def hilbert_env_moments(X, tables, tab_off, lengths, tiles, C, tile_samples=0):
+    """X [2, B, C, L] fp32 (clean, enhanced gammatone planes), tables / tab_off / lengths / tiles as sfm_hilbert_env_moments
+    takes them -> partial [n_tiles, C, 5] fp64.  tile_samples: hilbert_tiles' third result (the launch's stated cost only)."""
+    _need_dev(X, tables, tab_off, lengths, tiles)
+    L_ = _lib.load()
+    if X.dim() != 4 or X.shape[0] != 2 or X.shape[2] != C or X.dtype != torch.float32 or not X.is_contiguous() or C > GT_COLS or \
+            X.numel() == 0 or tiles.dim() != 2 or tiles.shape[1] != 2 or lengths.numel() != X.shape[1] or tab_off.numel() != X.shape[1]:
+        _lib.check(-2, "hilbert_env_moments")
+    _, B, _, L = X.shape
+    n = tiles.shape[0]
+    partial = torch.empty(max(n, 1), C, 5, device=X.device, dtype=torch.float64)
+    _call("hilbert_env", L_.sfm_hilbert_env_moments, (_p(X), _p(tables), _p(tab_off), _p(lengths), _p(tiles), _p(partial), B, C, L, n,
+                                                      _stream()),
+          4.0 * C * HE_ROWS * tile_samples, 8.0 * B * C * L + 40.0 * n * C, "B%d C%d L%d tiles%d" % (B, C, L, n))
+    return partial
+
+
+def ncm_finish(partial, tile_off, lengths, weights, B, C):
+    """partial [n_tiles, C, 5] fp64 -> (score [B], ncc [B, C]) fp64"""
+    _need_dev(partial, tile_off, lengths, weights)
+    L_ = _lib.load()
+    if weights.dtype != torch.float64 or weights.numel() != C or tile_off.numel() != B + 1 or lengths.numel() != B:
+        _lib.check(-2, "ncm_finish")
+    ncc = torch.empty(B, C, device=partial.device, dtype=torch.float64)
+    score = torch.empty(B, device=partial.device, dtype=torch.float64)
+    _call("intelligibility", L_.sfm_ncm_finish, (_p(partial), _p(tile_off), _p(lengths), _p(weights), _p(ncc), _p(score), B, C,
+                                                 _stream()), 5.0 * partial.shape[0] * C, 40.0 * partial.shape[0] * C)
+    return score, ncc
