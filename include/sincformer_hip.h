@@ -751,6 +751,29 @@ int sfm_hilbert_env_moments(const float* X, const float* tables, const int* tab_
 int sfm_ncm_finish(const double* partial, const int* tile_off, const int* lengths, const double* weights, double* ncc, double* score,
                    int B, int C, void* stream);
 
+/* SpeechEnhancementDNN (dnn.hip; models/dnn.py of the reference: [Linear, ReLU, Dropout] x 3, Linear, Sigmoid).
+ * sfm_dnn_layer: out[M, N] = act(A[M, K] W[N, Kpad]^T + bias) on the 16-bit MFMA of `dtype`, fp32 accumulation.
+ *   W [Npad, Kpad] 16-bit, zero padded, Kpad % 64 == 0, Npad % 64 == 0 (ops.pack_linear); bias fp32 [>= N] or NULL.
+ *   a_mode 0 (rows16): A 16-bit rows, row stride lda (elements), lda % 8 == 0, zero padded to a multiple of 8 columns.
+ *   a_mode 1 (rows32): A fp32 rows [M, K], any K and any lda >= K, converted while staged; read with 8-byte loads when A and lda
+ *     allow it and 4-byte loads otherwise; nothing is read past column K of a row.
+ *   a_mode 2 (context): A = raw [B, T, D] fp32 (8-byte aligned, D even and >= 8: read in pairs) with M = B T and K = D (2 ctx + 1); frames int32 [B] = live frames T_b per utterance
+ *     (NULL: T; 0 is legal).  Row (b, n), column j D + c = raw[b, clamp(n - ctx + j, 0, T_b - 1), c]; with mean / stdv [K] (both or
+ *     neither; K <= 4096): nan / inf -> 0, (f - mean) (1 / std), clip to +-10, in fp32.  Rows n >= T_b are zero rows; nothing is read for them.
+ *     frames, mean and stdv are NULL in the other modes; lda is ignored in this one, T, D and ctx in the others.
+ *   act 0 none, 1 ReLU, 2 sigmoid.  p_drop > 0 (act 1 only): the result is multiplied by keep(seed, m N + n) in {0, 1 / (1 - p)}
+ *     after the ReLU, the keep function of sfm_gemm16_train.
+ *   out_f32 0: 16-bit rows of `dtype`, row stride ldo >= N, columns N .. ldo written as zeros; 1: fp32 rows, row stride ldo.
+ *   The same bits from run to run, and for a row alone or inside any M.
+ * sfm_dnn_act_bwd: dz[M, ldz] 16-bit of `dtype` (ldz % 8 == 0, columns N .. ldz written as zeros) = dy * act'(.), dy fp32 (dy_f32 = 1)
+ *   or 16-bit rows of stride ldy.  act 1: saved = the layer's 16-bit OUTPUT h, dz = dy (h > 0 ? 1 / (1 - p_drop) : 0) - h is positive
+ *   exactly where the unit was active and kept; act 2: saved = the fp32 output y, dz = dy y (1 - y); act 0: dz = dy (saved unused). */
+int sfm_dnn_layer(const void* A, const int* frames, const float* mean, const float* stdv, const void* W, const float* bias, void* out,
+                  int a_mode, int M, int N, int K, long long lda, int T, int D, int ctx, int Kpad, int Npad, long long ldo, int out_f32,
+                  int act, float p_drop, unsigned int seed, int dtype, void* stream);
+int sfm_dnn_act_bwd(const void* dy, int dy_f32, long long ldy, const void* saved, long long ld_saved, void* dz, long long ldz, int M,
+                    int N, int act, float p_drop, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,13 @@ GFCC_NUM_COEFF = 13
 GFCC_DECIMATE_RATE = 100
 RASTA_NUM_COEFF = 13
 CONTEXT_FRAMES = 5
+# the mask-estimating DNN (config.py:64-72 of the reference)
+DNN_HIDDEN_LAYERS = 3
+DNN_HIDDEN_UNITS = 1024
+DNN_DROPOUT = 0.2
+DNN_LEARNING_RATE = 0.001
+DNN_EPOCHS = 50
+DNN_BATCH_SIZE = 256
 CONFORMER_NUM_BLOCKS = 6
 CONFORMER_D_MODEL = 256
 CONFORMER_NUM_HEADS = 4

@@ -1,1 +1,2 @@
+from .dnn import SpeechEnhancementDNN, create_dnn
 from .vq import VectorQuantizer, VQMaskQuantizer

@@ -2537,3 +2537,90 @@ def ncm_finish(partial, tile_off, lengths, weights, B, C):
     _call("intelligibility", L_.sfm_ncm_finish, (_p(partial), _p(tile_off), _p(lengths), _p(weights), _p(ncc), _p(score), B, C,
                                                  _stream()), 5.0 * partial.shape[0] * C, 40.0 * partial.shape[0] * C)
     return score, ncc
+
+
+# ---------------------------------------------------------------------------
+# SpeechEnhancementDNN (csrc/dnn.hip)
+# ---------------------------------------------------------------------------
+DNN_ROW_TILE = 128                  # rows of a workgroup of dnn_layer_kernel (DNN_BM)
+DNN_ACT = {None: 0, "relu": 1, "sigmoid": 2}
+DNN_CONTEXT_MAX_K = 4096            # context rows with statistics: mean and std sit in LDS beside the tiles
+
+
+def dnn_layer(a, pw, *, act=None, out=None, out_dtype=None, p_drop=0.0, seed=0, context=None, frames=None, mean=None, std=None):
+    """out [M, pw.N] = act(A pw.w^T + pw.bias), one sfm_dnn_layer launch.  A is `a`, by its dtype and `context`:
+      a 16-bit [M, >= round_up(pw.K, 8)], zero padded (rows16: a previous launch's result);
+      a fp32 [M, pw.K] with any row stride (rows32: converted while staged);
+      context=ctx: a = raw fp32 [B, T, D] contiguous (D even, >= 8), M = B T, pw.K = D (2 ctx + 1): the context rows of FeatureExtractor.add_context
+        (frames int32 [B] = T_b or None; mean / std fp32 [pw.K] or None) are gathered, normalised and clipped while staged.
+    act None / "relu" / "sigmoid"; p_drop > 0 (relu only): dropout with keep(seed, m N + n) after the ReLU.
+    out (or out_dtype): 16-bit rows in the compute format [M, >= N], columns from N on written as zeros, or fp32 [M, N]."""
+    _need_dev(a, out, frames, mean, std)
+    L = _lib.load()
+    dt = _state["dtype"]
+    if pw.w.dtype != dt or pw.ksize != 1 or pw.glu:
+        raise RuntimeError("dnn_layer: a plain Linear pack in the compute format %s is needed (got %s)" % (dt, pw.w.dtype))
+    T = D = ctx = 0
+    if context is not None:
+        ok = a.dtype == torch.float32 and a.dim() == 3 and a.is_contiguous() and a.numel() > 0 and 0 <= context <= 64
+        ok = ok and a.shape[2] >= 8 and a.shape[2] % 2 == 0 and a.shape[2] * (2 * context + 1) == pw.K and (mean is None) == (std is None)
+        ok = ok and all(s is None or (s.dtype == torch.float32 and s.is_contiguous() and s.numel() == pw.K) for s in (mean, std))
+        ok = ok and (mean is None or pw.K <= DNN_CONTEXT_MAX_K)
+        ok = ok and (frames is None or (frames.dtype == torch.int32 and frames.is_contiguous() and frames.numel() == a.shape[0]))
+        if not ok:
+            _lib.check(-2, "dnn_layer")
+        mode, ctx, (B, T, D) = 2, int(context), a.shape
+        M, lda, abytes = B * T, 0, 4.0 * a.numel() + (8.0 * pw.K if mean is not None else 0.0) + (4.0 * B if frames is not None else 0.0)
+    else:
+        if frames is not None or mean is not None or std is not None or a.dim() != 2 or a.stride(1) != 1 or a.numel() == 0:
+            _lib.check(-2, "dnn_layer")
+        M, lda = a.shape[0], a.stride(0)
+        if a.dtype == torch.float32:
+            mode, ok, abytes = 1, a.shape[1] == pw.K, 4.0 * M * pw.K
+        else:
+            K8 = round_up(pw.K, 8)
+            mode, ok, abytes = 0, a.dtype == dt and a.shape[1] >= K8 and lda % 8 == 0, 2.0 * M * K8
+        if not ok:
+            _lib.check(-2, "dnn_layer")
+    if out is None:
+        odt = out_dtype or dt
+        out = torch.empty(M, pw.N if odt == torch.float32 else round_up(pw.N, 8), device=a.device, dtype=odt)
+    if out.dim() != 2 or out.shape[0] != M or out.stride(1) != 1 or out.dtype not in (torch.float32, dt) or out.shape[1] < pw.N or \
+            (out.dtype == torch.float32 and out.shape[1] != pw.N) or act not in DNN_ACT:
+        _lib.check(-2, "dnn_layer")
+    out_f32 = 1 if out.dtype == torch.float32 else 0
+    # 16-bit rows: the columns N .. ldo are the next layer's K padding, written as zeros
+    ldo = out.stride(0)
+    osz = 4 if out_f32 else 2
+    _call("dnn_layer", L.sfm_dnn_layer, (_p(a), _p(frames), _p(mean), _p(std), _p(pw.w), _p(pw.bias), _p(out), mode, M, pw.N, pw.K, lda,
+                                         T, D, ctx, pw.Kpad, pw.Npad, ldo, out_f32, DNN_ACT[act], float(p_drop), int(seed) & 0xffffffff,
+                                         _dt(), _stream()),
+          2.0 * M * pw.N * pw.K, abytes + 2.0 * pw.Npad * pw.Kpad + 4.0 * pw.N + float(osz) * M * (pw.N if out_f32 else out.shape[1]),
+          "M%d N%d K%d a%d act%d o%d%s" % (M, pw.N, pw.K, mode, DNN_ACT[act], osz, " drop" if p_drop > 0 else ""))
+    return out
+
+
+def dnn_act_bwd(dy, saved, act, N, p_drop=0.0, out=None):
+    """dz [M, round_up(N, 64)] in the compute format = dy[:, :N] * act'(.), the columns from N on zeros: the cotangent of a
+    layer's pre-activation as gemm16_tn and the data-gradient GEMM read it.  dy fp32 or 16-bit rows [M, >= N].
+    act "relu": saved = the layer's 16-bit output h (positive exactly where the unit was active and kept),
+    dz = dy (h > 0 ? 1 / (1 - p_drop) : 0); "sigmoid": saved = the fp32 output y, dz = dy y (1 - y); None: dz = dy."""
+    _need_dev(dy, saved, out)
+    L = _lib.load()
+    dt = _state["dtype"]
+    M = dy.shape[0]
+    ok = dy.dim() == 2 and dy.stride(1) == 1 and dy.shape[1] >= N and dy.dtype in (torch.float32, dt) and act in DNN_ACT and M > 0
+    if act is not None:
+        ok = ok and saved is not None and saved.dim() == 2 and saved.stride(1) == 1 and saved.shape[0] == M and saved.shape[1] >= N
+        ok = ok and saved.dtype == (dt if act == "relu" else torch.float32)
+    if out is None:
+        out = torch.empty(M, round_up(N, 64), device=dy.device, dtype=dt)
+    ok = ok and out.dtype == dt and out.dim() == 2 and out.shape[0] == M and out.is_contiguous() and out.shape[1] >= N and out.shape[1] % 8 == 0
+    if not ok:
+        _lib.check(-2, "dnn_act_bwd")
+    ssz = 0 if act is None else saved.element_size()
+    _call("dnn_act_bwd", L.sfm_dnn_act_bwd, (_p(dy), 1 if dy.dtype == torch.float32 else 0, dy.stride(0), _p(saved),
+                                             0 if saved is None else saved.stride(0), _p(out), out.shape[1], M, N, DNN_ACT[act],
+                                             float(p_drop), _dt(), _stream()),
+          2.0 * M * N, float(M) * N * (dy.element_size() + ssz) + 2.0 * M * out.shape[1], "M%d N%d act%d" % (M, N, DNN_ACT[act]))
+    return out

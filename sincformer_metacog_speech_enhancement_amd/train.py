@@ -392,6 +392,69 @@ class LNLinearFunction(torch.autograd.Function):
         return dx.to(t[0]), dg.to(t[1]), dbt.to(t[2]), dW.to(t[3]), db.to(t[4])
 
 
+# ---------------------------------------------------------------------------
+# SpeechEnhancementDNN (models/dnn.py:22-113): [Linear, ReLU, Dropout] x L, Linear, Sigmoid
+# ---------------------------------------------------------------------------
+def _linear_bwd16(dz16, N, a16, w32, dx_dtype=None, want_dx=True):
+    """_linear_bwd for a cotangent that is already in the GEMMs' layout: dz16 [M, round_up(N, 64)] in the compute format, zero
+    from column N on (ops.dnn_act_bwd writes it so).  -> (dx [M, K] in dx_dtype (None: the compute format) or None, dW, db)"""
+    K = w32.shape[1]
+    dev = dz16.device
+    dW = torch.zeros(N, K, device=dev, dtype=torch.float32)
+    db = torch.zeros(N, device=dev, dtype=torch.float32)
+    ops.gemm16_tn(dz16[:, :N], a16[:, :K], dW, db)
+    dx = ops.linear16(dz16, ops.pack_linear(w32.t().contiguous(), k_pad_to=dz16.shape[1]), out_dtype=dx_dtype) if want_dx else None
+    return dx, dW, db
+
+
+class DnnFunction(torch.autograd.Function):
+    """y[M, out] = the whole network on fp32 rows x [M, in]; params = (W0, b0, W1, b1, ...), the last pair the output layer.
+    Forward: one sfm_dnn_layer launch per Linear (ReLU and dropout keep(seed_l, m N + n) in the epilogue).  Saved: the 16-bit
+    operand of each layer - the zero-padded 16-bit copy of x, then the hidden outputs themselves - the fp32 output and one seed per
+    hidden layer.  No mask and no pre-activation is kept: a hidden output is positive exactly where its unit was active and kept.
+    Backward per layer, last to first: ops.dnn_act_bwd, then the weight, bias and data gradients on the 16-bit GEMMs."""
+
+    @staticmethod
+    def forward(ctx, x, p, seed, *params):
+        M, K0 = x.shape
+        dt = ops.compute_dtype()
+        x32 = _rows32(x)
+        Kp = ops.round_up(K0, 64)
+        a16 = torch.empty(M, Kp, device=x.device, dtype=dt)
+        ops.convert_rows(x32, a16, M, K0, Kp, x32.stride(0), Kp)
+        w32 = [_f32(w) for w in params[0::2]]
+        seeds = _Seeds(seed)
+        acts, h = [a16], a16
+        layer_seeds = []
+        for l, w in enumerate(w32[:-1]):
+            s = seeds.next() if p > 0 else 0
+            layer_seeds.append(s)
+            h = ops.dnn_layer(h, ops.pack_linear(w, _f32(params[2 * l + 1]), k_pad_to=ops.round_up(w.shape[1], 8)), act="relu",
+                              p_drop=p, seed=s)
+            acts.append(h)
+        y = ops.dnn_layer(h, ops.pack_linear(w32[-1], _f32(params[-1]), k_pad_to=ops.round_up(w32[-1].shape[1], 8)), act="sigmoid",
+                          out_dtype=torch.float32)
+        ctx.saved = (acts, y, w32)
+        ctx.meta = (p, tuple(layer_seeds), x.dtype, tuple(t.dtype for t in params), ctx.needs_input_grad[0])
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        acts, y, w32 = ctx.saved
+        p, _, xdt, pdt, want_dx = ctx.meta
+        ctx.saved = None
+        grads = [None] * (2 * len(w32))
+        dz = ops.dnn_act_bwd(_rows32(dy), y, "sigmoid", w32[-1].shape[0])
+        dx = None
+        for l in range(len(w32) - 1, -1, -1):
+            N = w32[l].shape[0]
+            dx, dW, db = _linear_bwd16(dz, N, acts[l], w32[l], dx_dtype=None if l > 0 else torch.float32, want_dx=l > 0 or want_dx)
+            grads[2 * l], grads[2 * l + 1] = dW.to(pdt[2 * l]), db.to(pdt[2 * l + 1])
+            if l > 0:
+                dz = ops.dnn_act_bwd(dx, acts[l], "relu", w32[l - 1].shape[0], p_drop=p)
+        return (dx.to(xdt) if want_dx else None, None, None) + tuple(grads)
+
+
 class PolarMaskFunction(torch.autograd.Function):
     """bounded polar mask applied to the noisy STFT (training/conformer_pipeline.py:283-295):
     logits [M, 2F] (magnitude | phase) -> enh_real, enh_imag, mask_mag (monitoring only, not differentiable)."""

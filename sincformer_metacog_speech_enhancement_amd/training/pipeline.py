@@ -1,7 +1,8 @@
 """Mirror of the oracle-mask recipe of training/pipeline.py:153-197: the gammatone T-F analysis of the clean, noise and noisy
 waveforms (signal_processing/gammatone.py) into masks/ on the device, and of _process_single_utterance (:147-197) as a whole:
-dnn_frame_pairs gives the (features, mask) pair of a batch of utterances without file I/O, cache or a host round trip.  The
-Dataset, the DNN and the RBM are not mirrored; the Dataset's feature normalisation is an option of add_context."""
+dnn_frame_pairs gives the (features, mask) pair of a batch of utterances without file I/O, cache or a host round trip, and
+dnn_estimate_mask the estimator's side of enhance_signal (:846-875, its step 1): features, context and models.SpeechEnhancementDNN in
+one pass.  The Dataset and the RBM are not mirrored; the Dataset's feature normalisation is an option of add_context."""
 import numpy as np
 import torch
 
@@ -53,19 +54,37 @@ def gammatone_mask_target(clean, noise, noisy, mask_type, gfb=None, lengths=None
 _default_fe = {}
 
 
+def _fe_for(fe):
+    if fe is None:
+        if config.SAMPLE_RATE not in _default_fe:
+            _default_fe[config.SAMPLE_RATE] = FeatureExtractor()
+        fe = _default_fe[config.SAMPLE_RATE]
+    return fe
+
+
+def _frame_counts(lengths):
+    """sample counts of a zero-padded batch -> frame counts T_b (numpy int64), None for None"""
+    if lengths is None:
+        return None
+    host = np.asarray(lengths.cpu() if torch.is_tensor(lengths) else lengths, dtype=np.int64).reshape(-1)
+    return (np.maximum(host, config.FRAME_SIZE) - config.FRAME_SIZE) // config.HOP_SIZE + 1
+
+
 def dnn_frame_pairs(clean, noise, noisy, mask_type, fe=None, lengths=None, feat_mean=None, feat_std=None):
     """-> (features [B, T, 594], mask [B, T, 64]) (1-D signals: [T, 594], [T, 64]): the DNN's input rows from `noisy`
     (FeatureExtractor.extract_frame_features + add_context, normalised and clipped when feat_mean / feat_std are given) and its
     target from gammatone_mask_target, both over the same frames and with fe's one GammatoneFilterbank.  lengths: the sample counts
     of a zero-padded batch; rows from an utterance's T_b on are 0 in the features and analysed as zeros in the mask."""
-    if fe is None:
-        if config.SAMPLE_RATE not in _default_fe:
-            _default_fe[config.SAMPLE_RATE] = FeatureExtractor()
-        fe = _default_fe[config.SAMPLE_RATE]
+    fe = _fe_for(fe)
     mask = gammatone_mask_target(clean, noise, noisy, mask_type, gfb=fe.gfb, lengths=lengths)
     raw = fe.extract_frame_features(noisy, lengths=lengths)
-    frames = None
-    if lengths is not None:
-        host = np.asarray(lengths.cpu() if torch.is_tensor(lengths) else lengths, dtype=np.int64).reshape(-1)
-        frames = (np.maximum(host, config.FRAME_SIZE) - config.FRAME_SIZE) // config.HOP_SIZE + 1
-    return fe.add_context(raw, feat_mean, feat_std, lengths=frames), mask
+    return fe.add_context(raw, feat_mean, feat_std, lengths=_frame_counts(lengths)), mask
+
+
+def dnn_estimate_mask(dnn, noisy, fe=None, lengths=None, feat_mean=None, feat_std=None):
+    """-> the estimated mask [B, T, dnn.output_dim] (1-D signal: [T, .]) in [0, 1] of fp32 device waveforms noisy [B, L]:
+    FeatureExtractor.extract_frame_features, then dnn.forward_frames (the context rows, normalised and clipped with the checkpoint's
+    feat_mean / feat_std when given, are formed inside the first layer's launch), then the clip to [0, 1].  lengths: the sample counts
+    of a zero-padded batch; rows from an utterance's T_b on are those of zero input rows."""
+    raw = _fe_for(fe).extract_frame_features(noisy, lengths=lengths)
+    return dnn.forward_frames(raw, feat_mean, feat_std, lengths=_frame_counts(lengths)).clamp_(0.0, 1.0)
