@@ -38,6 +38,54 @@ extern "C" {
 #define SFM_EPI_SIGMA 7      /* exp(.5*clamp(v,-10,10)) agents/perception.py:249       */
 #define SFM_EPI_CPEA 8       /* sigmoid | alpha*tanh   agents/cpea.py:102-105          */
 
+/* ---- shared constants: the tile sizes, limits and mode codes that the host wrappers must agree with the kernels on.  This is
+ * their one statement: the kernels use these names (a number a kernel derives is tied to its name here by a static_assert), and
+ * the Python side reads every `#define SFM_<NAME> <literal>` line of this header into lib.CONSTANTS.  Plain literals only. */
+#define SFM_LAYERNORM_MAX_D 512        /* sfm_layernorm / sfm_layernorm_bwd_*: the widest row they normalise (and so the widest Conformer d_model) */
+#define SFM_ATTN_QTILE 128             /* query rows of a workgroup of attn_fwd_hd64_kernel: the tile of sfm_attention_fwd_varlen's items */
+#define SFM_XCDS 8                     /* workgroups are dealt round-robin over this many XCDs ... */
+#define SFM_XCD_RUN 8                  /* ... and the head_dim-64 attention kernels give each XCD runs of this many consecutive logical items */
+#define SFM_DWCONV_TILE 64             /* frames of a workgroup of the register-resident depthwise kernels: the tile of sfm_dwconv_folded_varlen's table */
+#define SFM_SINC_FIR16_WS_WORDS 278528 /* 16-bit words of sfm_sinc_fir16's staging buffer wsh (8 shifts x (hi, lo) x 64 channels x 272 padded taps) */
+#define SFM_PSTOI_MAX_BANDS 32         /* sfm_pstoi_loss: NB, F and frame_len (2 ..) it takes */
+#define SFM_PSTOI_MAX_BINS 257
+#define SFM_PSTOI_MIN_FRAME_LEN 2
+#define SFM_PSTOI_MAX_FRAME_LEN 32
+#define SFM_MIX_CHUNK 4096             /* samples per workgroup of sfm_mix_scale / sfm_mix_apply */
+#define SFM_QUANT_MAX_STEPS 16         /* sfm_mask_quantize, sfm_curriculum_mask, sfm_pso_*: M in 2 .. this */
+#define SFM_MASK_NONE 0                /* sfm_curriculum_mask's kind */
+#define SFM_MASK_IRM 1
+#define SFM_MASK_PCIRM 2
+#define SFM_MASK_OPT_PCIRM 3
+#define SFM_PSO_CHUNK 4096             /* samples per workgroup of sfm_pso_split */
+#define SFM_PSO_FRAMES 8               /* STOI frames per workgroup of sfm_pso_fitness */
+#define SFM_PSO_MAX_PARTICLES 256
+#define SFM_PSO_MAX_BINS 1024
+#define SFM_GT_COLS 64                 /* channel columns of the tap and twiddle operands (C <= 64, zero beyond C) */
+#define SFM_GT_ROWS 384                /* samples per workgroup of sfm_gammatone_fir / sfm_gammatone_tf */
+#define SFM_GT_MAX_TAPS 2048
+#define SFM_GT_LDS_MAX 163840          /* bytes of LDS sfm_gammatone_tf may ask for (160 KiB) */
+#define SFM_FE_MAX_FILTERS 64          /* sfm_cepstral / sfm_rasta: filters or channels per row, bins per row, DCT rows */
+#define SFM_FE_MAX_BINS 257
+#define SFM_FE_MAX_COEFFS 16
+#define SFM_CEP_POWER 0                /* sfm_cepstral's in_mode */
+#define SFM_CEP_MAGNITUDE 1
+#define SFM_CEP_BLOCKS 2
+#define SFM_CEP_NONE 0                 /* its compress */
+#define SFM_CEP_LOG 1
+#define SFM_CEP_CBRT 2
+#define SFM_HC_PARAMS 12               /* sfm_haircell*: par = {A, B, y, l, r, x, h, M, dt, q0, c0, w0}, fp64 */
+#define SFM_ADV_MAX_WIDTH 512          /* AdversarialLoss: first-layer Cin after zero padding (257 bins -> 512) */
+#define SFM_ADV_LO_SCALE 2048.0        /* adversarial.hip: a forward operand is hi + lo / 2048 */
+#define SFM_CSII_BINS 129              /* rfft(., 256) bins of the coherence */
+#define SFM_HE_ROWS 256                /* output samples per workgroup of the Hilbert kernel (its output tile) */
+#define SFM_HE_KSTEP 64                /* input samples per staged k-step (one accumulation segment) */
+#define SFM_DNN_ROW_TILE 128           /* rows of a workgroup of dnn_layer_kernel */
+#define SFM_DNN_ACT_NONE 0             /* sfm_dnn_layer / sfm_dnn_act_bwd: act */
+#define SFM_DNN_ACT_RELU 1
+#define SFM_DNN_ACT_SIGMOID 2
+#define SFM_DNN_CONTEXT_MAX_K 4096     /* context rows with statistics: mean and std sit in LDS beside the tiles */
+
 int sfm_abi_version(void);
 
 /* Dense layer / channels-last Conv1d as implicit GEMM on 16-bit MFMA.
@@ -244,7 +292,7 @@ int sfm_ffn_fused_ln(const float* x, const float* lnw, const float* lnb, const v
                      const float* ln2b, void* ln_out, int ln_out_f32, int dtype, void* stream);
 /* SincConv1d FIR (agents/perception.py:117) on the 16-bit matrix cores with hi/lo split operands
  * (3 MFMA passes, ~fp32 accuracy).  filt [64,K] fp32 from sfm_sinc_filters; wsh = workspace of
- * 8*2*64*272 uint16; out [B,L,64] channels-last; gn_partial [B][sfm_sinc_fir16_tiles(L)][8][2],
+ * SFM_SINC_FIR16_WS_WORDS uint16; out [B,L,64] channels-last; gn_partial [B][sfm_sinc_fir16_tiles(L)][8][2],
  * which the caller must zero-fill (tiles past L are not written). */
 int sfm_sinc_fir16_tiles(int L);
 int sfm_sinc_fir16(const float* wave, const float* filt, void* wsh, void* out, float* gn_partial, int B,
@@ -265,13 +313,15 @@ int sfm_framed_gemm_split16(const float* sig, const void* Whi, const void* Wlo, 
  * ORDERED REDUCTIONS (every entry point of the training step that sums over workgroups takes an optional workspace `ws`): with
  * it, each workgroup writes its partial into ws and a second pass folds the partials in workgroup order - the step is then
  * bit-reproducible, like the reference's CPU step (training/conformer_pipeline.py:496-532); ws == NULL selects fp32 / f64
- * atomics.  Sizes: sfm_*_ws_floats, or as stated; ws contents are scratch (destroyed), 16-byte aligned.
- * here: ws >= 64 * B * 5 doubles (wave_moments), >= 2048 * 4 doubles (spec_sums). */
+ * atomics.  Sizes: sfm_*_ws_floats / sfm_*_ws_doubles (the element type is part of the name); ws contents are scratch
+ * (destroyed), 16-byte aligned. */
+long long sfm_wave_moments_ws_doubles(int B, int L);
 int sfm_wave_moments(const float* est, const float* tgt, double* S, int B, int L, double* ws, void* stream);
 /* packed form of sfm_wave_moments (atomics only): est / tgt = B signals back to back, signal b = samples
  * [samp_off[b], samp_off[b + 1]) (int32 [B + 1] on the device; an empty signal leaves its row zero); max_L = the longest.
  * The grid is min(ceil(max_L / 256), 64) x B workgroups along x: SFM_ERR_SHAPE when that exceeds 2^31 - 1. */
 int sfm_wave_moments_varlen(const float* est, const float* tgt, double* S, const int* samp_off, int B, int max_L, void* stream);
+long long sfm_spec_sums_ws_doubles(long long n);
 int sfm_spec_sums(const float* pr, const float* pi, const float* tr, const float* ti, double* S, long long n, double* ws,
                   void* stream);
 int sfm_enhancer_loss_finalize(const double* Sw, const double* Sm, const double* Sr, const long long* nr, int B,
@@ -376,7 +426,8 @@ int sfm_vq_backward(const float* x, const long long* idx, const float* centroids
 /* Optimiser step (training/conformer_pipeline.py:424-429 AdamW, :509 NaN/Inf skip, :514 clip_grad_norm_) on flat fp32
  * buffers.  ctl = 8 doubles: [0] step count, [1] sum of squares (sfm_sumsq accumulates; zeroed by the step), [2] flag > 0
  * forces a skip, [3] applied gradient scale, [4] skipped (0/1), [5],[6] bias corrections, [7] gradient norm. */
-int sfm_sumsq(const float* g, long long n, double* out, double* ws, void* stream);        /* ws: >= 2048 doubles */
+long long sfm_sumsq_ws_doubles(long long n);
+int sfm_sumsq(const float* g, long long n, double* out, double* ws, void* stream);        /* ws: sfm_sumsq_ws_doubles(n) */
 int sfm_adamw_step(float* p, float* g, float* m, float* v, long long n, double* ctl, float lr, float beta1, float beta2,
                    float eps, float wd, float inv_scale, float max_norm, int write_back_grad, void* stream);
 /* Same, leaving alone - p, m and v - the parameters that received no gradient in this step (torch.optim.AdamW skips a
@@ -513,9 +564,10 @@ int sfm_memory_fwd(const float* emb, const float* params, float* bias_out, float
                    float* sim_out, int B, int key_dim, int value_dim, int slots, float temperature, void* stream);
 /* Backward of sfm_memory_fwd (EpisodicMemory in train() mode): d_out = gradient of the gated bias [B, value_dim], d_gate = of
  * the gate [B] (or NULL); d_emb [B, key_dim] (or NULL) and dparams = a ZERO-FILLED blob with the layout of `params`
- * (gradients of key_proj, keys, values, value_proj, gate, accumulated over the rows: with ws - B x sfm_memory_param_floats floats -
+ * (gradients of key_proj, keys, values, value_proj, gate, accumulated over the rows: with ws - sfm_memory_bwd_ws_floats floats -
  * every row writes its own copy of the blob and the copies are folded in row order; ws == NULL: fp32 atomics). */
 long long sfm_memory_param_floats(int key_dim, int value_dim, int slots);
+long long sfm_memory_bwd_ws_floats(int B, int key_dim, int value_dim, int slots);
 int sfm_memory_bwd(const float* emb, const float* params, const float* d_out, const float* d_gate, float* d_emb,
                    float* dparams, int B, int key_dim, int value_dim, int slots, float temperature, float* ws, void* stream);
 
@@ -528,12 +580,15 @@ int sfm_memory_bwd(const float* emb, const float* params, const float* d_out, co
  *     sqrt(re^2 + im^2 + 1e-8); (g0, g1) both or neither, [B, T, F].
  *   band_w [NB, F] dense (rows may overlap); beta_db = the clip level in dB (10^(beta / 20) x the clean energy).
  *   The clean side gets no gradient.  Frames t >= S * frame_len are unused and get gradient 0.
- *   ws >= B * S + 1 doubles.  SFM_ERR_SHAPE: NB > 32, F > 257, frame_len outside 2..32, T < frame_len, B * S > 2^31 - 1.
+ *   ws: sfm_pstoi_loss_ws_doubles(B, T, frame_len) doubles.  SFM_ERR_SHAPE: NB > SFM_PSTOI_MAX_BANDS, F > SFM_PSTOI_MAX_BINS,
+ *   frame_len outside SFM_PSTOI_MIN_FRAME_LEN .. SFM_PSTOI_MAX_FRAME_LEN, T < frame_len, B * S > 2^31 - 1.
  * sfm_mse_loss: loss = mean (pred - target)^2 over n elements, summed in double; grad (or NULL) = 2 (pred - target) / n.
- *   ws >= 1025 doubles. */
+ *   ws: sfm_mse_loss_ws_doubles(n) doubles. */
+long long sfm_pstoi_loss_ws_doubles(int B, int T, int frame_len);
 int sfm_pstoi_loss(const float* e0, const float* e1, const float* c0, const float* c1, const float* band_w, float* loss,
                    float* g0, float* g1, double* ws, int B, int T, int F, int NB, int frame_len, float beta_db, int layout,
                    void* stream);
+long long sfm_mse_loss_ws_doubles(long long n);
 int sfm_mse_loss(const float* pred, const float* target, float* loss, float* grad, double* ws, long long n, void* stream);
 
 /* AdversarialLoss (training/losses.py:150-289; adversarial.hip): what a discriminator call needs around the convs, which run on
@@ -560,16 +615,15 @@ int sfm_mse_loss(const float* pred, const float* target, float* loss, float* gra
  *   sqrt(re^2 + im^2 + 1e-8).  -> x16 [B, T, Cp] 16-bit, columns >= F zero, and x32 [B, T, F] fp32 (or NULL).
  * sfm_adv_stage_bwd: the adjoint: d [B, T, Cp] fp32 (carrying S) -> dx [B, F, T], or (dx, dx_im) [B, T, F]; every element written.
  * sfm_adv_leaky: a16 = LeakyReLU_0.2(z) for n fp32 pre-activations (n % 4 == 0); with z_real (the real pass's pre-activation
- *   of the same layer) also loss += scale * sum |leaky(z) - leaky(z_real)|; ws >= 2048 doubles.
+ *   of the same layer) also loss += scale * sum |leaky(z) - leaky(z_real)|; ws: sfm_adv_leaky_ws_doubles(n) doubles.
  * sfm_adv_leaky_bwd: dz16 = (incoming + S * w_fm * g[0] * sign(leaky(z) - leaky(z_real))) * (z > 0 ? 1 : 0.2): the 16-bit dY of the
  *   two gradient GEMMs; incoming or z_real may be NULL (not both).  g = the objective's incoming gradient, on the device.
  * sfm_adv_pool: AvgPool1d(4, 2, 1), padding counted: in32 [B, Tin, F] -> out32 [B, Tin / 2, F] (or NULL), out16 [B, Tin / 2, Cp].
  * sfm_adv_pool_bwd: dx [B, Tin, Cp] += its adjoint of dnext [B, Tin / 2, Cp].
  * sfm_adv_head: out [B, T] = Conv1d(C, 1, 3, pad 1) of a16 [B, T, C] with w16 [3][C] tap-major 16-bit and bias[0];
- *   loss += scale * sum (out - target)^2; ws >= ceil(B T / 4) doubles.
+ *   loss += scale * sum (out - target)^2; ws: sfm_adv_head_ws_doubles(B, T) doubles.
  * sfm_adv_head_bwd: dout = g[0] * coef * (out - target); da [B, T, C] fp32 = S x its adjoint; dwb (or NULL) = dw [3][C] tap-major | db
- *   (not scaled), through
- *   ws >= ceil(B T / 64) * (3 C + 1) floats. */
+ *   (not scaled), through ws: sfm_adv_head_bwd_ws_floats(B, T, C) floats. */
 int sfm_adv_sn_fwd(const long long* table, int n_layers, void* packed, void* packed_lo, float* saved, int training, float eps,
                    int dtype, void* stream);
 int sfm_adv_sn_bwd(const float* G, const float* W, const float* u, const float* v, const float* sigma, float* dW,
@@ -579,6 +633,7 @@ int sfm_adv_stage(const float* x, const float* im, void* x16, void* x16lo, float
                   int dtype, void* stream);
 int sfm_adv_stage_bwd(const float* d, const float* re, const float* im, float* dx, float* dx_im, const float* g, float cnorm, int B,
                       int F, int T, int Cp, int pair, void* stream);
+long long sfm_adv_leaky_ws_doubles(long long n);
 int sfm_adv_leaky(const float* z, const float* z_real, void* a16, void* a16lo, double* ws, double* loss, float scale, long long n,
                   int dtype, void* stream);
 int sfm_adv_leaky_bwd(const float* incoming, const float* z, const float* z_real, const float* g, float w_fm, float cnorm,
@@ -586,8 +641,10 @@ int sfm_adv_leaky_bwd(const float* incoming, const float* z, const float* z_real
 int sfm_adv_pool(const float* in32, float* out32, void* out16, void* out16lo, int B, int Tin, int F, int Cp, int dtype,
                  void* stream);
 int sfm_adv_pool_bwd(const float* dnext, float* dx, int B, int Tin, int Cp, void* stream);
+long long sfm_adv_head_ws_doubles(int B, int T);
 int sfm_adv_head(const void* a16, const void* a16lo, const void* w16, const void* w16lo, const float* bias, float* out, double* ws,
                  double* loss, float target, float scale, int B, int T, int C, int dtype, void* stream);
+long long sfm_adv_head_bwd_ws_floats(int B, int T, int C);
 int sfm_adv_head_bwd(const void* a16, const void* w16, const float* out, const float* g, float coef, float cnorm, float target,
                      float* da, float* dwb, float* ws, int B, int T, int C, int dtype, void* stream);
 
@@ -606,9 +663,9 @@ int sfm_adv_head_bwd(const void* a16, const void* w16, const float* out, const f
  * sfm_mix_scale: clean [B, L]; bank = every noise signal back to back, bank_off int32 [n_noise + 1] ascending from 0;
  *   noise_ids int32 [B] (clamped to the bank); snr_db [B]; lengths int32 [B] or NULL (= L; clamped to 0..L).  Utterance b is
  *   mixed with noise[j mod Ln] at sample j (a shorter noise tiled, a longer one cut).  Two launches: fp64 sums of clean^2 and
- *   noise^2 over the first lengths[b] samples, one partial pair per workgroup of 4096 samples; then ONE workgroup adds each
+ *   noise^2 over the first lengths[b] samples, one partial pair per workgroup of SFM_MIX_CHUNK samples; then ONE workgroup adds each
  *   utterance's partials in index order and writes scale[b] = sqrt(Pc / (Pn 10^(snr_db / 10))), P = mean + 1e-10.
- *   ws >= 2 * B * ceil(L / 4096) doubles.  B <= 65535.
+ *   ws: sfm_mix_scale_ws_doubles(B, L) doubles.  B <= 65535.
  * sfm_mix_apply: noisy[b, j] = clean[b, j] + scale[b] * noise[j mod Ln] for j < lengths[b], 0 from there on; noise_rows
  *   (or NULL) [B, L] receives the unscaled noise[j mod Ln], 0 from lengths[b] on.  Every element is written.
  * sfm_curriculum_mask: (cr, ci), (nr, ni) = spectra [B, T, F] of the clean utterances and of sfm_mix_apply's noise rows.
@@ -622,6 +679,7 @@ int sfm_mask_corr(const float* noisy, const float* clean, const float* noise, fl
 int sfm_mask_pcirm(const float* clean_mag, const float* noise_mag, const float* rho_s, const float* rho_n, const float* phi1,
                    const float* phi2, float* out, long long n, float eps, void* stream);
 int sfm_mask_quantize(const float* pcirm, const double* table, float* out, long long n, int M, void* stream);
+long long sfm_mix_scale_ws_doubles(int B, int L);
 int sfm_mix_scale(const float* clean, const float* bank, const int* bank_off, const int* noise_ids, const float* snr_db,
                   const int* lengths, double* ws, float* scale, int B, int L, int n_noise, void* stream);
 int sfm_mix_apply(const float* clean, const float* bank, const int* bank_off, const int* noise_ids, const int* lengths,
@@ -639,8 +697,8 @@ int sfm_curriculum_mask(const float* cr, const float* ci, const float* nr, const
  * sfm_pso_split: noisy, clean [B, Lmax]; lengths int32 [B]; samp_off int32 [B + 1] = the running sum of the lengths.  Mask frames
  *   of `frame` samples every `hop` (frame >= hop), frame n < T covering [n hop, min(n hop + frame, length)), overlap-added and
  *   divided by max(count, 1) give the gains ga, gb.  Writes ya = noisy ga, yb = noisy gb and clean, each utterance's samples
- *   at samp_off[b] (packed, fp32), and S [B, 4] = {sum ya^2, sum ya yb, sum yb^2, sum clean^2}: one fp64 partial per 4096
- *   samples, folded in index order.  ws >= 4 * B * ceil(Lmax / 4096) doubles.
+ *   at samp_off[b] (packed, fp32), and S [B, 4] = {sum ya^2, sum ya yb, sum yb^2, sum clean^2}: one fp64 partial per
+ *   SFM_PSO_CHUNK samples, folded in index order.  ws: sfm_pso_split_ws_doubles(B, Lmax) doubles.
  * sfm_pso_fitness: packed spectra rows [sum_frames, F] (F <= 1024) of clean, ya, yb; frame_off int32 [B + 1].  For each
  *   utterance whose stopped[b] is 0 and each of its N positions x (rounded to fp32): the clipped frame correlations of
  *   clean / rms against (ya + x yb) / rms, summed over chunks of 8 frames: partial [B, NC, N], NC >= ceil(frames / 8) of every
@@ -654,6 +712,7 @@ int sfm_curriculum_mask(const float* cr, const float* ci, const float* nr, const
  *   it == max_iter moves pos / vel to the next iteration's.  The caller sets pos / vel to the first 2 N draws before round 0.
  * sfm_pso_quantize: sfm_mask_quantize over [B, CT] with middle[b] (double, rounded to fp32) as step 2's value when M >= 3. */
 int sfm_pso_frame_coef(const float* pcirm, const double* table, double* a, double* b, int B, int C, int T, int M, void* stream);
+long long sfm_pso_split_ws_doubles(int B, int Lmax);
 int sfm_pso_split(const float* noisy, const float* clean, const int* lengths, const int* samp_off, const double* a,
                   const double* b, float* ya, float* yb, float* clean_packed, double* ws, double* S, int B, int Lmax, int T,
                   int frame, int hop, void* stream);
@@ -675,13 +734,15 @@ int sfm_pso_quantize(const float* pcirm, const double* table, const double* midd
  * sfm_gammatone_tf: the fused form.  nblocks = L / hop whole hop-blocks; tw [2][hop][64] = cos, sin of 2 pi (k_c t mod N) / N for
  *   the block-local t; partial [B, nblocks, C, 5] = {sum y^2, sum y, sum (-1)^t y, sum y cos, sum y sin} of each block, summed in
  *   fp64 in t order and rounded once.  hop even, 2..384, and (25344 + K + 128 hop) * 4 bytes of LDS <= 160 KiB (SFM_ERR_SHAPE
- *   otherwise).  Blocks that start behind lengths[b] are not written.
+ *   otherwise): sfm_gammatone_tf_fits(K, hop) != 0 - the same rule as a predicate, for the caller's router (no device work).
+ *   Blocks that start behind lengths[b] are not written.
  * sfm_gammatone_moments: y [B, C, L] (sfm_gammatone_fir's) -> partial [B, T, C, 5]: the same five sums over the first w <= frame
  *   samples of frame n = y[n hop .. n hop + frame), frame-local t; tw [2][w][64].  Frames that end behind lengths[b] are not written.
  * sfm_gammatone_tf_finish: partial [B, P, C, 5] -> mag, phase and (unless NULL) re, im [B, C, T].  two = 1: frame n is rows n and
  *   n + 1, the second times rot [2][64] = cos, sin of 2 pi (k_c hop mod N) / N; two = 0: row n alone.  mag = (N s2 + s1^2 + sp^2) / 2,
  *   phase = atan2(im, re), in fp64 from the fp32 partials; everything from T_b = (lengths[b] - frame) / hop + 1 on is 0. */
 int sfm_gammatone_fir(const float* sig, const float* taps, const int* lengths, float* out, int B, int L, int C, int K, void* stream);
+int sfm_gammatone_tf_fits(int K, int hop);
 int sfm_gammatone_tf(const float* sig, const float* taps, const float* tw, const int* lengths, float* partial, int B, int L, int C,
                      int K, int hop, int nblocks, void* stream);
 int sfm_gammatone_moments(const float* y, const float* tw, const int* lengths, float* partial, int B, int L, int C, int T, int w,

@@ -48,7 +48,7 @@ __device__ __forceinline__ float adv_scale(const float* g, float cnorm) {
 // ~2^-20 instead of 2^-11 (fp16) / 2^-8 (bf16).  LeakyReLU and the L1 of the feature term have kinks; with single 16-bit operands
 // a few pre-activations per tensor land on the other side of zero and each costs 0.8 |dz| (2 w) of the gradient: 1e-2..1e-1 of
 // its norm on small tensors, however exact the backward is.  The backward stays on the hi words alone (it is smooth).
-constexpr float LO_SCALE = 2048.f;
+constexpr float LO_SCALE = SFM_ADV_LO_SCALE;  // (the header's literal, as a float: the products below are fp32)
 template <class T>
 __device__ __forceinline__ void split16(float v, u16& hi, u16& lo) {
   hi = T::from_f32(v);
@@ -431,10 +431,14 @@ __global__ __launch_bounds__(NT) void adv_head_dw_kernel(const u16* __restrict__
   }
 }
 
+constexpr int EW_MAX_BLOCKS = 2048;
 inline int ew_grid(long long n4) {
-  long long g = (n4 + NT - 1) / NT;
-  return (int)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
+  const long long g = sfm_capped_blocks(n4, NT, EW_MAX_BLOCKS);
+  return (int)(g < 1 ? 1 : g);
 }
+constexpr int HEAD_WAVES = NT / 64;        // adv_head_kernel: one row per wave, one partial per workgroup
+inline long long head_blocks(int B, int T) { return ((long long)B * T + HEAD_WAVES - 1) / HEAD_WAVES; }
+inline long long head_chunks(int B, int T) { return ((long long)B * T + HEAD_ROWS - 1) / HEAD_ROWS; }
 
 }  // namespace
 
@@ -500,6 +504,8 @@ int sfm_adv_stage_bwd(const float* d, const float* re, const float* im, float* d
   return SFM_OK;
 }
 
+// sized for ew_grid's cap, whatever n: one partial per workgroup
+long long sfm_adv_leaky_ws_doubles(long long n) { (void)n; return EW_MAX_BLOCKS; }
 int sfm_adv_leaky(const float* z, const float* z_real, void* a16, void* a16lo, double* ws, double* loss, float scale, long long n,
                   int dtype, void* stream) {
   if (!z || !a16 || !a16lo || (z_real && (!ws || !loss))) return SFM_ERR_ARG;
@@ -545,12 +551,13 @@ int sfm_adv_pool_bwd(const float* dnext, float* dx, int B, int Tin, int Cp, void
   return SFM_OK;
 }
 
+long long sfm_adv_head_ws_doubles(int B, int T) { return B > 0 && T > 0 ? head_blocks(B, T) : 0; }
 int sfm_adv_head(const void* a16, const void* a16lo, const void* w16, const void* w16lo, const float* bias, float* out, double* ws,
                  double* loss, float target,
                  float scale, int B, int T, int C, int dtype, void* stream) {
   if (!a16 || !a16lo || !w16 || !w16lo || !bias || !out || !ws || !loss) return SFM_ERR_ARG;
   if (B <= 0 || T <= 0 || C <= 0 || (C % 8) != 0) return SFM_ERR_SHAPE;
-  const long long blocks = ((long long)B * T + 3) / 4;
+  const long long blocks = head_blocks(B, T);
   if (blocks >= (1LL << 31)) return SFM_ERR_SHAPE;
   hipStream_t st = (hipStream_t)stream;
   ADV_DT(dtype, SFM_LAUNCH(adv_head_kernel<DT>, dim3((unsigned)blocks), dim3(NT), 0, st, (const u16*)a16, (const u16*)a16lo,
@@ -560,11 +567,13 @@ int sfm_adv_head(const void* a16, const void* a16lo, const void* w16, const void
   return SFM_OK;
 }
 
+// ws[chunk][3 C + 1] of adv_head_dw_kernel
+long long sfm_adv_head_bwd_ws_floats(int B, int T, int C) { return B > 0 && T > 0 && C > 0 ? head_chunks(B, T) * (3 * C + 1) : 0; }
 int sfm_adv_head_bwd(const void* a16, const void* w16, const float* out, const float* g, float coef, float cnorm, float target,
                      float* da, float* dwb, float* ws, int B, int T, int C, int dtype, void* stream) {
   if (!a16 || !w16 || !out || !g || !da || (dwb && !ws)) return SFM_ERR_ARG;
   if (B <= 0 || T <= 0 || C <= 0) return SFM_ERR_SHAPE;
-  const long long n = (long long)B * T * C, chunks = ((long long)B * T + HEAD_ROWS - 1) / HEAD_ROWS;
+  const long long n = (long long)B * T * C, chunks = head_chunks(B, T);
   if ((n + NT - 1) / NT >= (1LL << 31)) return SFM_ERR_SHAPE;
   hipStream_t st = (hipStream_t)stream;
   ADV_DT(dtype, SFM_LAUNCH(adv_head_da_kernel<DT>, dim3((unsigned)((n + NT - 1) / NT)), dim3(NT), 0, st, (const u16*)w16, out, g,

@@ -67,13 +67,15 @@ __global__ __launch_bounds__(256) void attn_fwd_hd64_kernel(const u16* __restric
     qkv += (long long)row0 * ldqkv;
     out += (long long)row0 * ldo;
   } else {
+    static_assert(SFM_XCDS == 8, "the dealing shifts by 3 and masks with 7");
     const int total = gridDim.x, q = total >> 3, r = total & 7, xcd = id & 7, slot = id >> 3;
     id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
     qt = id % nqt;
     h = (id / nqt) % nheads;
     b = id / (nqt * nheads);
   }
-  const int q0 = qt * 128 + wave * 32;
+  static_assert(SFM_ATTN_QTILE == 4 * 32, "a workgroup's query tile: 32 rows per wave");
+  const int q0 = qt * SFM_ATTN_QTILE + wave * 32;
   const int hl = lane >> 5, l31 = lane & 31;
   const u16* base = qkv + (long long)b * qkv_batch_stride + h * 64;
 
@@ -746,7 +748,7 @@ static int attention_fwd_impl(const void* qkv, void* out, float* lse, int B, int
                        qkv_batch_stride, o_batch_stride, sl2, nqt5, H, n_items, lse, out_other);
       return SFM_OK;
     }
-    const int nqt = (T + 127) / 128;
+    const int nqt = (T + SFM_ATTN_QTILE - 1) / SFM_ATTN_QTILE;
     dim3 grid(nqt * H * B), block(256);
 #define ATTN_GO(TT, DD)                                                                                            \
   SFM_LAUNCH((attn_fwd_hd64_kernel<TT, DD>), grid, block, 0, st, (const u16*)qkv, (u16*)out, T, ldqkv, ldo, koff, voff, \
@@ -800,8 +802,9 @@ extern "C" int sfm_attention_fwd_varlen(const void* qkv, void* out, const int* f
   hipStream_t st = (hipStream_t)stream;
   if (hd == 64 && (ldqkv % 8) == 0 && (ldo % 8) == 0 && (koff % 8) == 0 && (voff % 8) == 0) {
     if (!items) return SFM_ERR_ARG;
-    // every (utterance, head) has between 1 and ceil(max_T / 128) tiles
-    if (n_items < B * H || (long long)n_items > (long long)B * H * ((max_T + 127) / 128)) return SFM_ERR_SHAPE;
+    // every (utterance, head) has between 1 and ceil(max_T / SFM_ATTN_QTILE) tiles
+    if (n_items < B * H || (long long)n_items > (long long)B * H * ((max_T + SFM_ATTN_QTILE - 1) / SFM_ATTN_QTILE))
+      return SFM_ERR_SHAPE;
     const float sl2 = (scale > 0.f) ? scale * 1.44269504088896340736f : 1.0f;
     dim3 grid(n_items), block(256);
     if (dtype == SFM_DT_F16)

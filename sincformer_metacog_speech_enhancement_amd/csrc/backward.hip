@@ -177,7 +177,7 @@ static int layernorm_bwd_go(const float* x, const float* gamma, const void* dy, 
                             void* next16, float next_alpha, float next_p, unsigned int next_seed, float* ws, void* stream) {
   if (!x || !gamma || !dy || !dx || !dgamma || !dbeta) return SFM_ERR_ARG;
   if (ws && (((uintptr_t)ws) % 16) != 0) return SFM_ERR_ARG;
-  if (M <= 0 || D <= 0 || D > 512) return SFM_ERR_SHAPE;
+  if (M <= 0 || D <= 0 || D > SFM_LAYERNORM_MAX_D) return SFM_ERR_SHAPE;
   if (ldx < D || ldy < D || ld < D) return SFM_ERR_SHAPE;                 // rows of x, dy, dres / dx must not overlap
   if (next16 && (next_p < 0.f || next_p >= 1.f || ((uintptr_t)next16 % 8) != 0)) return SFM_ERR_SHAPE;
   if (dtype != SFM_DT_BF16 && dtype != SFM_DT_F16) return SFM_ERR_ARG;

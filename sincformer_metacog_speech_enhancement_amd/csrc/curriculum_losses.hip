@@ -16,9 +16,7 @@
 #include "sfm_common.h"
 
 #define PST_EPS 1e-8f
-#define PST_MAX_NB 32
-#define PST_MAX_F 257
-#define PST_MAX_FL 32
+static_assert(SFM_PSTOI_MAX_FRAME_LEN == 32, "a segment's frames are the lanes of a half-wave (pstoi_kernel)");
 
 // sum over the 32 lanes of a half-wave, the same value (bit for bit) in each of them
 static __device__ __forceinline__ float half_sum(float v) {
@@ -264,17 +262,22 @@ __global__ __launch_bounds__(256) void mse_kernel(const float* __restrict__ p, c
 static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // loss[0] = -mean over (B, NB, S = T / frame_len) of the band / segment correlations; g0 (, g1) != NULL: d loss / d enhanced,
-// every element written.  ws: >= B * S + 1 doubles of scratch.
+// every element written.  ws: sfm_pstoi_loss_ws_doubles doubles of scratch (one partial per workgroup, then their sum).
+static long long pstoi_parts(int B, int T, int frame_len) { return (long long)B * (T / frame_len); }
+extern "C" long long sfm_pstoi_loss_ws_doubles(int B, int T, int frame_len) {
+  return B > 0 && T > 0 && frame_len > 0 ? pstoi_parts(B, T, frame_len) + 1 : 0;
+}
 extern "C" int sfm_pstoi_loss(const float* e0, const float* e1, const float* c0, const float* c1, const float* band_w,
                               float* loss, float* g0, float* g1, double* ws, int B, int T, int F, int NB, int frame_len,
                               float beta_db, int layout, void* stream) {
   if (!e0 || !c0 || !band_w || !loss || !ws || (layout != 0 && layout != 1)) return SFM_ERR_ARG;
   if (layout == 1 && (!e1 || !c1 || (g0 != nullptr) != (g1 != nullptr))) return SFM_ERR_ARG;
   if (layout == 0 && g1) return SFM_ERR_ARG;
-  if (B <= 0 || F < 1 || F > PST_MAX_F || NB < 1 || NB > PST_MAX_NB || frame_len < 2 || frame_len > PST_MAX_FL || T < frame_len)
+  if (B <= 0 || F < 1 || F > SFM_PSTOI_MAX_BINS || NB < 1 || NB > SFM_PSTOI_MAX_BANDS || frame_len < SFM_PSTOI_MIN_FRAME_LEN ||
+      frame_len > SFM_PSTOI_MAX_FRAME_LEN || T < frame_len)
     return SFM_ERR_SHAPE;
   const int FL = frame_len, S = T / FL;
-  const long long parts = (long long)B * S;
+  const long long parts = pstoi_parts(B, T, FL);
   if (parts > 2147483647LL) return SFM_ERR_SHAPE;
   const int NBp = (NB + 3) & ~3;
   const bool grad = g0 != nullptr;
@@ -301,13 +304,15 @@ extern "C" int sfm_pstoi_loss(const float* e0, const float* e1, const float* c0,
   return SFM_OK;
 }
 
-// loss[0] = mean (pred - target)^2 over n elements; grad (or NULL) = 2 (pred - target) / n.  ws: >= 1025 doubles of scratch.
+// loss[0] = mean (pred - target)^2 over n elements; grad (or NULL) = 2 (pred - target) / n.  ws: sfm_mse_loss_ws_doubles doubles
+// of scratch (one partial per workgroup, then their sum; sized for the cap, whatever n).
+static constexpr int MSE_MAX_BLOCKS = 1024;
+extern "C" long long sfm_mse_loss_ws_doubles(long long n) { (void)n; return MSE_MAX_BLOCKS + 1; }
 extern "C" int sfm_mse_loss(const float* pred, const float* target, float* loss, float* grad, double* ws, long long n,
                             void* stream) {
   if (!pred || !target || !loss || !ws) return SFM_ERR_ARG;
   if (n <= 0) return SFM_ERR_SHAPE;
-  long long nb = (n + 1023) / 1024;
-  if (nb > 1024) nb = 1024;
+  const long long nb = sfm_capped_blocks(n, 1024, MSE_MAX_BLOCKS);
   hipStream_t st = (hipStream_t)stream;
   SFM_LAUNCH(mse_kernel, dim3((unsigned)nb), dim3(256), 0, st, pred, target, grad, ws, n, 2.0 / (double)n);
   const int rc = sfm_fold_partials_f64(ws, ws + nb, 1, 1, 1, (int)nb, 0, stream);

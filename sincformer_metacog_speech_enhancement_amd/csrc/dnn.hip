@@ -19,8 +19,8 @@
 //   active and kept; sigmoid: y (1 - y)), written as the zero-padded 16-bit rows the weight- and data-gradient GEMMs read.
 #include "sfm_common.h"
 
-#define DNN_BM 128
-#define DNN_TILE_BYTES (DNN_BM * 128)        // one operand tile: 128 rows x 64 16-bit elements
+static_assert(SFM_DNN_ROW_TILE == 128, "rows of a workgroup: four 32-row MFMA tiles, staged as one 128-row operand tile");
+#define DNN_TILE_BYTES (SFM_DNN_ROW_TILE * 128)        // one operand tile: 128 rows x 64 16-bit elements
 
 struct DnnParams {
   const void* A;          // rows16: 16-bit [M, lda]; rows32: fp32 [M, lda]; context: raw fp32 [B, T, D]
@@ -52,7 +52,7 @@ __global__ __launch_bounds__(256) void dnn_layer_kernel(DnnParams p) {
   const int l31 = lane & 31, hl = lane >> 5;
   const int nNt = (p.N + BN - 1) / BN;
   const int ntile = blockIdx.x % nNt, mtile = blockIdx.x / nNt;
-  const int n0 = ntile * BN, m0 = mtile * DNN_BM;
+  const int n0 = ntile * BN, m0 = mtile * SFM_DNN_ROW_TILE;
   const int c8 = tid & 7, r0 = tid >> 3;                     // this thread stages chunk c8 of rows r0, r0 + 32, r0 + 64, r0 + 96
   const bool has_stats = AMODE == DNN_CONTEXT && p.mean != nullptr;
 
@@ -240,10 +240,10 @@ __global__ __launch_bounds__(256) void dnn_layer_kernel(DnnParams p) {
         if (row >= p.M) continue;
         if (col < p.N) {
           float v = acc[i][j][r] + bias;
-          if (p.act == 1) {
+          if (p.act == SFM_DNN_ACT_RELU) {
             v = v > 0.f ? v : 0.f;
             if (p.p_drop > 0.f) v *= sfm_keep_scale(p.seed, (unsigned long long)row * p.N + col, p.p_drop, p.inv_keep);
-          } else if (p.act == 2) {
+          } else if (p.act == SFM_DNN_ACT_SIGMOID) {
             v = sigmoid_f(v);
           }
           if (p.out_f32) o32[(long long)row * p.ldo + col] = v;
@@ -258,7 +258,7 @@ __global__ __launch_bounds__(256) void dnn_layer_kernel(DnnParams p) {
   const int covered = nNt * BN;
   if (!p.out_f32 && ntile == nNt - 1 && p.ldo > covered) {
     const int extra = (int)(p.ldo - covered);
-    const int rows = p.M - m0 < DNN_BM ? p.M - m0 : DNN_BM;
+    const int rows = p.M - m0 < SFM_DNN_ROW_TILE ? p.M - m0 : SFM_DNN_ROW_TILE;
     for (int idx = tid; idx < rows * extra; idx += 256) {
       const int r = idx / extra, c = idx - r * extra;
       o16[(long long)(m0 + r) * p.ldo + covered + c] = 0;
@@ -268,7 +268,7 @@ __global__ __launch_bounds__(256) void dnn_layer_kernel(DnnParams p) {
 
 template <class T, int AMODE>
 static int dnn_layer_launch(const DnnParams& p, int lds, hipStream_t stream) {
-  const int nMt = (p.M + DNN_BM - 1) / DNN_BM;
+  const int nMt = (p.M + SFM_DNN_ROW_TILE - 1) / SFM_DNN_ROW_TILE;
   if (p.N <= 64) {
     SFM_LAUNCH((dnn_layer_kernel<T, AMODE, 64>), dim3((unsigned)nMt), dim3(256), lds, stream, p);
   } else {
@@ -292,8 +292,10 @@ extern "C" int sfm_dnn_layer(const void* A, const int* frames, const float* mean
                              void* stream) {
   if (!A || !W || !out || (mean == nullptr) != (stdv == nullptr)) return SFM_ERR_ARG;
   if (dtype != SFM_DT_BF16 && dtype != SFM_DT_F16) return SFM_ERR_ARG;
-  if (a_mode < DNN_ROWS16 || a_mode > DNN_CONTEXT || act < 0 || act > 2 || (out_f32 != 0 && out_f32 != 1)) return SFM_ERR_ARG;
-  if (!(p_drop >= 0.f && p_drop < 1.f) || (p_drop > 0.f && act != 1)) return SFM_ERR_ARG;
+  if (a_mode < DNN_ROWS16 || a_mode > DNN_CONTEXT || act < SFM_DNN_ACT_NONE || act > SFM_DNN_ACT_SIGMOID ||
+      (out_f32 != 0 && out_f32 != 1))
+    return SFM_ERR_ARG;
+  if (!(p_drop >= 0.f && p_drop < 1.f) || (p_drop > 0.f && act != SFM_DNN_ACT_RELU)) return SFM_ERR_ARG;
   if (a_mode != DNN_CONTEXT && (frames || mean)) return SFM_ERR_ARG;
   if (M <= 0 || N <= 0 || K <= 0 || Kpad < K || (Kpad % 64) != 0 || Npad < N || (Npad % 64) != 0 || ldo < N) return SFM_ERR_SHAPE;
   if ((long long)M * N > 0x7fffffffffLL || K > (1 << 24)) return SFM_ERR_SHAPE;
@@ -312,7 +314,7 @@ extern "C" int sfm_dnn_layer(const void* A, const int* frames, const float* mean
     if (T <= 0 || D < 8 || (D % 2) != 0 || ctx < 0 || ctx > 64 || (M % T) != 0 || (long long)D * (2 * ctx + 1) != K) return SFM_ERR_SHAPE;
     if ((((uintptr_t)A) % 8) != 0) return SFM_ERR_ARG;
     if (mean) {
-      if (K > 4096) return SFM_ERR_SHAPE;                     // the statistics sit in LDS beside the tiles: 64 KB in all
+      if (K > SFM_DNN_CONTEXT_MAX_K) return SFM_ERR_SHAPE;                     // the statistics sit in LDS beside the tiles: 64 KB in all
       lds += 2 * ((K + 63) / 64 * 64) * (int)sizeof(float);
     }
   }
@@ -340,10 +342,10 @@ __global__ __launch_bounds__(256) void dnn_act_bwd_kernel(const void* __restrict
     float v = 0.f;
     if (c < N) {
       v = dy_f32 ? reinterpret_cast<const float*>(dy)[row * ldy + c] : T::to_f32(reinterpret_cast<const u16*>(dy)[row * ldy + c]);
-      if (act == 1) {
+      if (act == SFM_DNN_ACT_RELU) {
         const float h = T::to_f32(reinterpret_cast<const u16*>(saved)[row * ld_saved + c]);
         v = h > 0.f ? v * inv_keep : 0.f;
-      } else if (act == 2) {
+      } else if (act == SFM_DNN_ACT_SIGMOID) {
         const float y = reinterpret_cast<const float*>(saved)[row * ld_saved + c];
         v = v * y * (1.f - y);
       }
@@ -356,11 +358,12 @@ __global__ __launch_bounds__(256) void dnn_act_bwd_kernel(const void* __restrict
 
 extern "C" int sfm_dnn_act_bwd(const void* dy, int dy_f32, long long ldy, const void* saved, long long ld_saved, void* dz,
                                long long ldz, int M, int N, int act, float p_drop, int dtype, void* stream) {
-  if (!dy || !dz || (act != 0 && !saved)) return SFM_ERR_ARG;
+  if (!dy || !dz || (act != SFM_DNN_ACT_NONE && !saved)) return SFM_ERR_ARG;
   if (dtype != SFM_DT_BF16 && dtype != SFM_DT_F16) return SFM_ERR_ARG;
-  if (act < 0 || act > 2 || (dy_f32 != 0 && dy_f32 != 1) || !(p_drop >= 0.f && p_drop < 1.f) || (p_drop > 0.f && act != 1))
+  if (act < SFM_DNN_ACT_NONE || act > SFM_DNN_ACT_SIGMOID || (dy_f32 != 0 && dy_f32 != 1) || !(p_drop >= 0.f && p_drop < 1.f) ||
+      (p_drop > 0.f && act != SFM_DNN_ACT_RELU))
     return SFM_ERR_ARG;
-  if (M <= 0 || N <= 0 || ldy < N || (act != 0 && ld_saved < N) || ldz < N || (ldz % 8) != 0) return SFM_ERR_SHAPE;
+  if (M <= 0 || N <= 0 || ldy < N || (act != SFM_DNN_ACT_NONE && ld_saved < N) || ldz < N || (ldz % 8) != 0) return SFM_ERR_SHAPE;
   if ((((uintptr_t)dz) % 16) != 0) return SFM_ERR_ARG;
   const long long work = (long long)M * (ldz >> 3);
   const long long blocks = (work + 255) / 256;

@@ -15,12 +15,11 @@
 // No atomics anywhere: the same bits from run to run, and for an utterance alone or in a batch.
 #include "sfm_common.h"
 
-#define FE_MMAX 64                    // filters / channels per row
-#define FE_FMAX 257                   // bins per row
-#define FE_NCMAX 16                   // DCT rows
 #define FE_WAVES 4
 #define FE_ROWS 64                    // rows per workgroup (16 per wave): amortises the filterbank's load into LDS
 #define FE_PLD 260                    // per-wave power row (floats)
+static_assert(SFM_FE_MAX_FILTERS <= 64 && SFM_FE_MAX_COEFFS <= 64, "one lane per filter, one lane per DCT row");
+static_assert(SFM_FE_MAX_BINS <= FE_PLD, "a row's bins fit the per-wave power row");
 
 __device__ __forceinline__ int fe_frames(const int* lengths, int b, int L, int frame, int hop) {
   int Lb = lengths ? lengths[b] : L;
@@ -39,25 +38,25 @@ __global__ __launch_bounds__(FE_WAVES * 64) void cepstral_kernel(const float* __
                                                                  int compress, int P, int bmul, int badd, float window,
                                                                  long long ld_out, int col_off) {
   extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];
-  double* vs = reinterpret_cast<double*>(dsm);                 // [FE_WAVES][FE_MMAX]
-  float* ps = reinterpret_cast<float*>(vs + FE_WAVES * FE_MMAX);   // [FE_WAVES][FE_PLD]
-  float* dts = ps + FE_WAVES * FE_PLD;                         // [M][FE_NCMAX]: dct transposed
-  float* fbs = dts + FE_MMAX * FE_NCMAX;                       // [M][F]
+  double* vs = reinterpret_cast<double*>(dsm);                 // [FE_WAVES][SFM_FE_MAX_FILTERS]
+  float* ps = reinterpret_cast<float*>(vs + FE_WAVES * SFM_FE_MAX_FILTERS);   // [FE_WAVES][FE_PLD]
+  float* dts = ps + FE_WAVES * FE_PLD;                         // [M][SFM_FE_MAX_COEFFS]: dct transposed
+  float* fbs = dts + SFM_FE_MAX_FILTERS * SFM_FE_MAX_COEFFS;                       // [M][F]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (fb)
     for (int i = tid; i < M * F; i += FE_WAVES * 64) fbs[i] = fb[i];
   if (dct)
-    for (int i = tid; i < NC * M; i += FE_WAVES * 64) dts[(i % M) * FE_NCMAX + i / M] = dct[i];
+    for (int i = tid; i < NC * M; i += FE_WAVES * 64) dts[(i % M) * SFM_FE_MAX_COEFFS + i / M] = dct[i];
   __syncthreads();
   const long long nrows = (long long)B * T;
   float* pw = ps + wave * FE_PLD;
-  double* vw = vs + wave * FE_MMAX;
+  double* vw = vs + wave * SFM_FE_MAX_FILTERS;
   for (int it = 0; it < FE_ROWS / FE_WAVES; ++it) {            // uniform over the workgroup: every wave meets every barrier
     const long long row = (long long)blockIdx.x * FE_ROWS + it * FE_WAVES + wave;
     const int b = row < nrows ? (int)(row / T) : 0, n = (int)(row - (long long)b * T);
     const bool live = row < nrows && n < fe_frames(lengths, b, L, frame, hop);
     if (live) {
-      if (in_mode == 2) {
+      if (in_mode == SFM_CEP_BLOCKS) {
         if (lane < F) {
           const float* p0 = in + (((long long)b * P + (long long)bmul * n + badd) * F + lane) * 5;
           pw[lane] = (float)(((double)p0[0] + (double)p0[(long long)F * 5]) / (double)window);
@@ -67,7 +66,7 @@ __global__ __launch_bounds__(FE_WAVES * 64) void cepstral_kernel(const float* __
         for (int f = lane; f < F; f += 64) {
           const float a = re[f], c = re[im_off + f];
           const float p = fmaf(a, a, c * c);
-          pw[f] = in_mode == 1 ? sqrtf(p) : p;
+          pw[f] = in_mode == SFM_CEP_MAGNITUDE ? sqrtf(p) : p;
         }
       }
     }
@@ -82,15 +81,15 @@ __global__ __launch_bounds__(FE_WAVES * 64) void cepstral_kernel(const float* __
         e = pw[lane];
       }
       double v = (double)e;
-      if (compress == 1) v = log(v + 1e-10);
-      else if (compress == 2) v = copysign(cbrt(fabs(v)), v);
+      if (compress == SFM_CEP_LOG) v = log(v + 1e-10);
+      else if (compress == SFM_CEP_CBRT) v = copysign(cbrt(fabs(v)), v);
       vw[lane] = v;
       if (NC == 0) out[row * ld_out + col_off + lane] = (float)v;
     }
     __syncthreads();
     if (live && lane < NC) {
       double c = 0.0;
-      for (int m = 0; m < M; ++m) c = fma((double)dts[m * FE_NCMAX + lane], vw[m], c);
+      for (int m = 0; m < M; ++m) c = fma((double)dts[m * SFM_FE_MAX_COEFFS + lane], vw[m], c);
       out[row * ld_out + col_off + lane] = (float)c;
     }
   }
@@ -101,8 +100,8 @@ __global__ __launch_bounds__(64) void rasta_kernel(const float* __restrict__ log
                                                    const double* __restrict__ dct, const int* __restrict__ lengths,
                                                    float* __restrict__ out, int T, int L, int frame, int hop, int M, int NC,
                                                    long long ld_out, int col_off) {
-  __shared__ double mean[FE_MMAX];
-  __shared__ float coef[FE_NCMAX];
+  __shared__ double mean[SFM_FE_MAX_FILTERS];
+  __shared__ float coef[SFM_FE_MAX_COEFFS];
   const int lane = threadIdx.x, b = blockIdx.x;
   int Tb = fe_frames(lengths, b, L, frame, hop);
   Tb = Tb > T ? T : Tb;
@@ -195,7 +194,7 @@ __global__ __launch_bounds__(64) void rows_mean_kernel(const float* __restrict__
 }
 
 static int fe_lds_bytes(int M, int F, bool fb) {
-  return FE_WAVES * FE_MMAX * 8 + (FE_WAVES * FE_PLD + FE_MMAX * FE_NCMAX + (fb ? M * F : 0)) * 4;
+  return FE_WAVES * SFM_FE_MAX_FILTERS * 8 + (FE_WAVES * FE_PLD + SFM_FE_MAX_FILTERS * SFM_FE_MAX_COEFFS + (fb ? M * F : 0)) * 4;
 }
 
 static bool fe_framing_ok(int B, int T, int L, int frame, int hop) {
@@ -206,10 +205,11 @@ extern "C" int sfm_cepstral(const float* in, const float* fb, const float* dct, 
                             int frame, int hop, int in_mode, long long ld_in, int im_off, int F, int M, int NC, int compress, int P,
                             int bmul, int badd, float window, long long ld_out, int col_off, void* stream) {
   if (!in || !out || (NC > 0 && !dct)) return SFM_ERR_ARG;
-  if (!fe_framing_ok(B, T, L, frame, hop) || in_mode < 0 || in_mode > 2 || compress < 0 || compress > 2 || F < 1 || F > FE_FMAX ||
-      M < 1 || M > FE_MMAX || NC < 0 || NC > FE_NCMAX || (!fb && M != F) || col_off < 0 || col_off + (NC ? NC : M) > ld_out)
+  if (!fe_framing_ok(B, T, L, frame, hop) || in_mode < SFM_CEP_POWER || in_mode > SFM_CEP_BLOCKS || compress < SFM_CEP_NONE ||
+      compress > SFM_CEP_CBRT || F < 1 || F > SFM_FE_MAX_BINS || M < 1 || M > SFM_FE_MAX_FILTERS || NC < 0 ||
+      NC > SFM_FE_MAX_COEFFS || (!fb && M != F) || col_off < 0 || col_off + (NC ? NC : M) > ld_out)
     return SFM_ERR_SHAPE;
-  if (in_mode == 2) {
+  if (in_mode == SFM_CEP_BLOCKS) {
     if (F > 64 || bmul < 1 || badd < 0 || !(window > 0.f) || (long long)bmul * (T - 1) + badd + 1 >= P) return SFM_ERR_SHAPE;
   } else if (im_off < F || (long long)im_off + F > ld_in) {
     return SFM_ERR_SHAPE;
@@ -224,7 +224,8 @@ extern "C" int sfm_cepstral(const float* in, const float* fb, const float* dct, 
 extern "C" int sfm_rasta(const float* logb, const double* eql, const double* dct, const int* lengths, float* out, int B, int T, int L,
                          int frame, int hop, int M, int NC, long long ld_out, int col_off, void* stream) {
   if (!logb || !eql || !dct || !out) return SFM_ERR_ARG;
-  if (!fe_framing_ok(B, T, L, frame, hop) || M < 1 || M > FE_MMAX || NC < 1 || NC > FE_NCMAX || col_off < 0 || col_off + NC > ld_out)
+  if (!fe_framing_ok(B, T, L, frame, hop) || M < 1 || M > SFM_FE_MAX_FILTERS || NC < 1 || NC > SFM_FE_MAX_COEFFS || col_off < 0 ||
+      col_off + NC > ld_out)
     return SFM_ERR_SHAPE;
   SFM_LAUNCH(rasta_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, logb, eql, dct, lengths, out, T, L, frame, hop, M, NC, ld_out,
              col_off);

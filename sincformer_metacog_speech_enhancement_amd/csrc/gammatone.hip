@@ -14,20 +14,18 @@
 // Split 16-bit operands (sinc_fir16's form) were not kept: bf16 hi + lo drops the lo x lo term at 2^-16 of a product, the size of
 // 16 e32 of this row, and fp16's range does not hold the taps' tails without a per-channel scale.
 //
-// A workgroup (4 waves) owns GT_ROWS = 384 samples (FIR) or the hop-blocks that fit into them (fused), forms y for all channels
+// A workgroup (4 waves) owns SFM_GT_ROWS = 384 samples (FIR) or the hop-blocks that fit into them (fused), forms y for all channels
 // in accumulators (up to 3 row tiles x 2 column tiles per wave), parks the tile in LDS and then either stores it [B, C, L] or
 // reduces each hop-block in fp64 in t order.  No atomics; nothing depends on the batch: an utterance gets the bits it gets alone.
 #include "sfm_common.h"
 
-#define GT_CP 64                      // channel columns of the operands (C <= 64, padded with zero taps)
 #define GT_WAVES 4
 #define GT_RT 3                       // row tiles per wave
-#define GT_ROWS (GT_WAVES * GT_RT * 32)
 #define GT_YLD 65                     // row stride of the y tile in LDS (floats): conflict-free by row and by channel
-#define GT_KMAX 2048
 #define GT_KC 4                       // k-steps (of 2 taps) per tap prefetch chunk
 #define GT_SEG 8                      // chunks per accumulation segment (64 taps)
-#define GT_LDS_MAX (160 * 1024)
+static_assert(SFM_GT_ROWS == GT_WAVES * GT_RT * 32, "a workgroup's samples: 32 per row tile of each wave");
+static_assert(SFM_GT_COLS == 64, "two 32-column MFMA tiles: C <= 64, padded with zero taps");
 
 template <int NA>
 __device__ __forceinline__ void gt_mfma_tiles(const float* __restrict__ taps, const float* xs, float* yt, int K, int wave, int lane) {
@@ -42,14 +40,14 @@ __device__ __forceinline__ void gt_mfma_tiles(const float* __restrict__ taps, co
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[g][j][r] = tot[g][j][r] = 0.f;
   int seg = 0;
-  const float* tp = taps + hl * GT_CP + l31;
+  const float* tp = taps + hl * SFM_GT_COLS + l31;
   const float* xp = xs + K + wave * 32 + l31 - hl;            // row tile g of this wave: tile g * GT_WAVES + wave
   // taps of GT_KC k-steps at a time, the next chunk's loads issued before this chunk's MFMAs (K is a multiple of 2 GT_KC)
   float nb[GT_KC][2];
 #pragma unroll
   for (int q = 0; q < GT_KC; ++q) {
-    nb[q][0] = tp[2 * q * GT_CP];
-    nb[q][1] = tp[2 * q * GT_CP + 32];
+    nb[q][0] = tp[2 * q * SFM_GT_COLS];
+    nb[q][1] = tp[2 * q * SFM_GT_COLS + 32];
   }
   for (int k0 = 0; k0 < K; k0 += 2 * GT_KC) {
     float bq[GT_KC][2];
@@ -61,8 +59,8 @@ __device__ __forceinline__ void gt_mfma_tiles(const float* __restrict__ taps, co
     const int kn = (k0 + 2 * GT_KC < K) ? k0 + 2 * GT_KC : k0;
 #pragma unroll
     for (int q = 0; q < GT_KC; ++q) {
-      nb[q][0] = tp[(kn + 2 * q) * GT_CP];
-      nb[q][1] = tp[(kn + 2 * q) * GT_CP + 32];
+      nb[q][0] = tp[(kn + 2 * q) * SFM_GT_COLS];
+      nb[q][1] = tp[(kn + 2 * q) * SFM_GT_COLS + 32];
     }
 #pragma unroll
     for (int q = 0; q < GT_KC; ++q)
@@ -102,30 +100,30 @@ __global__ __launch_bounds__(GT_WAVES * 64) void gammatone_kernel(const float* _
                                                                   float* __restrict__ dst, int L, int C, int K, int hop, int nblocks,
                                                                   int nb) {
   extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];
-  float* xs = reinterpret_cast<float*>(dsm);                   // [GT_ROWS + K]: xs[i] = x[m0 - K + i], 0 outside [0, Lb)
-  float* yt = xs + GT_ROWS + K;                                // [GT_ROWS][GT_YLD]
-  float* tws = yt + GT_ROWS * GT_YLD;                          // FUSED: [2][hop][64]
+  float* xs = reinterpret_cast<float*>(dsm);                   // [SFM_GT_ROWS + K]: xs[i] = x[m0 - K + i], 0 outside [0, Lb)
+  float* yt = xs + SFM_GT_ROWS + K;                                // [SFM_GT_ROWS][GT_YLD]
+  float* tws = yt + SFM_GT_ROWS * GT_YLD;                          // FUSED: [2][hop][64]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b = blockIdx.y;
   int Lb = lengths ? lengths[b] : L;
   Lb = Lb < 0 ? 0 : (Lb > L ? L : Lb);
   const int blk0 = blockIdx.x * nb;                            // FUSED: first hop-block of this workgroup
-  const int m0 = FUSED ? blk0 * hop : blockIdx.x * GT_ROWS;
+  const int m0 = FUSED ? blk0 * hop : blockIdx.x * SFM_GT_ROWS;
   int nrows;
   if (FUSED) {
     const int nbw = (nblocks - blk0 < nb) ? nblocks - blk0 : nb;
     nrows = nbw * hop;
     if (m0 >= Lb) return;                                      // blocks behind the utterance feed no frame below T_b
   } else {
-    nrows = (L - m0 < GT_ROWS) ? L - m0 : GT_ROWS;
+    nrows = (L - m0 < SFM_GT_ROWS) ? L - m0 : SFM_GT_ROWS;
   }
   const float* xb = sig + (long long)b * L;
-  for (int i = tid; i < GT_ROWS + K; i += GT_WAVES * 64) {
+  for (int i = tid; i < SFM_GT_ROWS + K; i += GT_WAVES * 64) {
     const int s = m0 - K + i;
     xs[i] = (s >= 0 && s < Lb) ? xb[s] : 0.f;
   }
   if (FUSED)
-    for (int i = tid; i < 2 * hop * GT_CP; i += GT_WAVES * 64) tws[i] = tw[i];
+    for (int i = tid; i < 2 * hop * SFM_GT_COLS; i += GT_WAVES * 64) tws[i] = tw[i];
   __syncthreads();
 
   const int ntile = (nrows + 31) >> 5;                         // <= GT_WAVES * GT_RT
@@ -152,8 +150,8 @@ __global__ __launch_bounds__(GT_WAVES * 64) void gammatone_kernel(const float* _
       s2 = fma(y, y, s2);
       s1 += y;
       sp += (t & 1) ? -y : y;
-      sc = fma(y, (double)tws[t * GT_CP + c], sc);
-      ss = fma(y, (double)tws[(hop + t) * GT_CP + c], ss);
+      sc = fma(y, (double)tws[t * SFM_GT_COLS + c], sc);
+      ss = fma(y, (double)tws[(hop + t) * SFM_GT_COLS + c], ss);
     }
     float* pp = dst + (((long long)b * nblocks + blk0 + j) * C + c) * 5;
     pp[0] = (float)s2; pp[1] = (float)s1; pp[2] = (float)sp; pp[3] = (float)sc; pp[4] = (float)ss;
@@ -178,8 +176,8 @@ __global__ __launch_bounds__(256) void gammatone_moments_kernel(const float* __r
     s2 = fma(v, v, s2);
     s1 += v;
     sp += (t & 1) ? -v : v;
-    sc = fma(v, (double)tw[t * GT_CP + c], sc);
-    ss = fma(v, (double)tw[(w + t) * GT_CP + c], ss);
+    sc = fma(v, (double)tw[t * SFM_GT_COLS + c], sc);
+    ss = fma(v, (double)tw[(w + t) * SFM_GT_COLS + c], ss);
   }
   s2 = wave_sum_d(s2); s1 = wave_sum_d(s1); sp = wave_sum_d(sp); sc = wave_sum_d(sc); ss = wave_sum_d(ss);
   if (lane == 0) {
@@ -196,7 +194,7 @@ __global__ __launch_bounds__(256) void gammatone_finish_kernel(const float* __re
                                                                float* __restrict__ phase, float* __restrict__ re,
                                                                float* __restrict__ im, int C, int T, int P, int two, int L, int frame,
                                                                int hop, int N) {
-  __shared__ float res[4][GT_CP][33];
+  __shared__ float res[4][SFM_GT_COLS][33];
   const int tid = threadIdx.x, b = blockIdx.y, n0 = blockIdx.x * 32;
   int Lb = lengths ? lengths[b] : L;
   Lb = Lb < 0 ? 0 : (Lb > L ? L : Lb);
@@ -209,7 +207,7 @@ __global__ __launch_bounds__(256) void gammatone_finish_kernel(const float* __re
       double s2 = p0[0], s1 = p0[1], sp = p0[2], sr = p0[3], si = p0[4];
       if (two) {
         const float* p1 = p0 + (long long)C * 5;
-        const double rc = rot[c], rs = rot[GT_CP + c], c1 = p1[3], d1 = p1[4];
+        const double rc = rot[c], rs = rot[SFM_GT_COLS + c], c1 = p1[3], d1 = p1[4];
         s2 += (double)p1[0]; s1 += (double)p1[1]; sp += (double)p1[2];
         sr += rc * c1 - rs * d1;
         si += rc * d1 + rs * c1;
@@ -235,34 +233,35 @@ __global__ __launch_bounds__(256) void gammatone_finish_kernel(const float* __re
   }
 }
 
-static int gt_lds_bytes(int K, int hop) { return ((GT_ROWS + K) + GT_ROWS * GT_YLD + 2 * hop * GT_CP) * 4; }
+static int gt_lds_bytes(int K, int hop) { return ((SFM_GT_ROWS + K) + SFM_GT_ROWS * GT_YLD + 2 * hop * SFM_GT_COLS) * 4; }
 
 static bool gt_bank_ok(int B, int L, int C, int K) {
-  return B > 0 && B <= 65535 && L > 0 && C > 0 && C <= GT_CP && K >= 2 * GT_KC && K <= GT_KMAX && K % (2 * GT_KC) == 0;
+  return B > 0 && B <= 65535 && L > 0 && C > 0 && C <= SFM_GT_COLS && K >= 2 * GT_KC && K <= SFM_GT_MAX_TAPS && K % (2 * GT_KC) == 0;
 }
 
 extern "C" int sfm_gammatone_fir(const float* sig, const float* taps, const int* lengths, float* out, int B, int L, int C, int K,
                                  void* stream) {
   if (!sig || !taps || !out) return SFM_ERR_ARG;
   if (!gt_bank_ok(B, L, C, K)) return SFM_ERR_SHAPE;
-  const dim3 grid((L + GT_ROWS - 1) / GT_ROWS, B);
+  const dim3 grid((L + SFM_GT_ROWS - 1) / SFM_GT_ROWS, B);
   SFM_LAUNCH_LDS((gammatone_kernel<0>), grid, dim3(GT_WAVES * 64), gt_lds_bytes(K, 0), (hipStream_t)stream, sig, taps,
                  (const float*)nullptr, lengths, out, L, C, K, 0, 0, 0);
   return SFM_OK;
 }
 
 // sfm_gammatone_tf takes (K, hop) when the workgroup's LDS image fits and at least one hop-block fits its rows
-// (ops.gammatone_tf_fits states the same rule for the router)
-static bool gt_tf_fits(int K, int hop) {
-  return K >= 2 * GT_KC && K <= GT_KMAX && K % (2 * GT_KC) == 0 && hop >= 2 && (hop & 1) == 0 && hop <= GT_ROWS && gt_lds_bytes(K, hop) <= GT_LDS_MAX;
+// (exported: the host's router asks this predicate, ops.gammatone_tf_fits)
+extern "C" int sfm_gammatone_tf_fits(int K, int hop) {
+  return K >= 2 * GT_KC && K <= SFM_GT_MAX_TAPS && K % (2 * GT_KC) == 0 && hop >= 2 && (hop & 1) == 0 && hop <= SFM_GT_ROWS &&
+         gt_lds_bytes(K, hop) <= SFM_GT_LDS_MAX;
 }
 
 extern "C" int sfm_gammatone_tf(const float* sig, const float* taps, const float* tw, const int* lengths, float* partial, int B,
                                 int L, int C, int K, int hop, int nblocks, void* stream) {
   if (!sig || !taps || !tw || !partial) return SFM_ERR_ARG;
-  if (!gt_bank_ok(B, L, C, K) || !gt_tf_fits(K, hop) || nblocks < 1 || (long long)nblocks * hop > L)
+  if (!gt_bank_ok(B, L, C, K) || !sfm_gammatone_tf_fits(K, hop) || nblocks < 1 || (long long)nblocks * hop > L)
     return SFM_ERR_SHAPE;
-  const int nb = GT_ROWS / hop;
+  const int nb = SFM_GT_ROWS / hop;
   const dim3 grid((nblocks + nb - 1) / nb, B);
   SFM_LAUNCH_LDS((gammatone_kernel<1>), grid, dim3(GT_WAVES * 64), gt_lds_bytes(K, hop), (hipStream_t)stream, sig, taps, tw, lengths,
                  partial, L, C, K, hop, nblocks, nb);
@@ -272,7 +271,7 @@ extern "C" int sfm_gammatone_tf(const float* sig, const float* taps, const float
 extern "C" int sfm_gammatone_moments(const float* y, const float* tw, const int* lengths, float* partial, int B, int L, int C, int T,
                                      int w, int frame, int hop, void* stream) {
   if (!y || !tw || !partial) return SFM_ERR_ARG;
-  if (B <= 0 || B > 65535 || C <= 0 || C > GT_CP || L <= 0 || T <= 0 || w <= 0 || w > frame || hop <= 0 ||
+  if (B <= 0 || B > 65535 || C <= 0 || C > SFM_GT_COLS || L <= 0 || T <= 0 || w <= 0 || w > frame || hop <= 0 ||
       (long long)(T - 1) * hop + frame > L)
     return SFM_ERR_SHAPE;
   SFM_LAUNCH(gammatone_moments_kernel, dim3((T + 3) / 4, C, B), dim3(256), 0, (hipStream_t)stream, y, tw, lengths, partial, L, C, T, w,
@@ -284,7 +283,7 @@ extern "C" int sfm_gammatone_tf_finish(const float* partial, const float* rot, c
                                        float* im, int B, int C, int T, int P, int two, int L, int frame, int hop, int N,
                                        void* stream) {
   if (!partial || !mag || !phase || (two && !rot)) return SFM_ERR_ARG;
-  if (B <= 0 || B > 65535 || C <= 0 || C > GT_CP || T <= 0 || frame <= 0 || hop <= 0 || N < 2 || (N & 1) || L < frame ||
+  if (B <= 0 || B > 65535 || C <= 0 || C > SFM_GT_COLS || T <= 0 || frame <= 0 || hop <= 0 || N < 2 || (N & 1) || L < frame ||
       T > (L - frame) / hop + 1 || P < T + (two ? 1 : 0))
     return SFM_ERR_SHAPE;
   SFM_LAUNCH(gammatone_finish_kernel, dim3((T + 31) / 32, B), dim3(256), 0, (hipStream_t)stream, partial, rot, lengths, mag, phase, re,

@@ -17,6 +17,7 @@
 #define HC_T 64                       // samples per tile
 #define HC_LD 65                      // row stride of the tile (doubles)
 enum { HC_A, HC_B, HC_Y, HC_L, HC_R, HC_X, HC_H, HC_M, HC_DT, HC_Q0, HC_C0, HC_W0, HC_NPAR };
+static_assert(HC_NPAR == SFM_HC_PARAMS, "the doubles of `par`");
 
 __device__ __forceinline__ double hc_clamp(double v) { return (0.0 > v) ? 0.0 : v; }
 

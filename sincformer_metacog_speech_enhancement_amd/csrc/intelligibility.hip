@@ -13,21 +13,20 @@
 //   A = h[(n - m) mod L] is one LDS word per lane from a staged window of the table (consecutive addresses over the lanes; the
 //   table is stored twice back to back, index n - m + L, so the wrap costs no modulo; for an even L every even lag of h is exactly
 //   0 and the problem splits into two of half the size, see the kernel), B = x[m][col] one LDS word per lane from a
-//   staged [HE_KS][128] tile.  A staged k-step of HE_KS = 64 samples is one accumulation segment: the chain restarts with it and
+//   staged [SFM_HE_KSTEP][128] tile.  A staged k-step of SFM_HE_KSTEP = 64 samples is one accumulation segment: the chain restarts with it and
 //   the segments are added in order.  The analytic signal is never stored: the epilogue forms env = sqrt(x^2 + y^2) in fp64 and
 //   either writes it (sfm_hilbert_env) or five fp64 sums per (utterance, channel, output tile) that ncm_finish_kernel folds in
 //   tile order.  No atomics; nothing depends on the pack: an utterance gets the bits it gets alone.
 #include "sfm_common.h"
 
 #define HE_WAVES 8
-#define HE_ROWS (HE_WAVES * 32)       // output samples per workgroup: the output tile
-#define HE_KS 64                      // input samples per staged k-step = one accumulation segment
+static_assert(SFM_HE_ROWS == HE_WAVES * 32, "output samples per workgroup (the output tile): one 32-row MFMA tile per wave");
+static_assert(SFM_HE_KSTEP == 64, "input samples per staged k-step = one accumulation segment: one per lane (xs[lane])");
 #define HE_COLS 128                   // columns of the x tile (2 x 64 channel-signals)
 #define HE_XLD 129                    // row stride of the x tile in LDS (floats): conflict-free by sample and by column
-#define HE_WIN (HE_ROWS + HE_KS)      // floats kept for the table window (HE_ROWS + HE_KS - 1 used)
-#define HE_XPT (HE_KS * HE_COLS / (HE_WAVES * 64))   // x words staged per thread and k-step (16)
-#define HE_LDS_BYTES (HE_WAVES * 2 * 64 * 5 * 8)     // the epilogue's fp64 exchange; >= (HE_WIN + HE_KS * HE_XLD) * 4
-#define CSII_F 129
+#define HE_WIN (SFM_HE_ROWS + SFM_HE_KSTEP)      // floats kept for the table window (SFM_HE_ROWS + SFM_HE_KSTEP - 1 used)
+#define HE_XPT (SFM_HE_KSTEP * HE_COLS / (HE_WAVES * 64))   // x words staged per thread and k-step (16)
+#define HE_LDS_BYTES (HE_WAVES * 2 * 64 * 5 * 8)     // the epilogue's fp64 exchange; >= (HE_WIN + SFM_HE_KSTEP * HE_XLD) * 4
 
 // ENV = 1: x [R, L], workgroup (tile, group of 128 rows), env [R, L]; tiles and table of an even L as below.
 // ENV = 0: x = X [2, B, C, L] (clean, enhanced; 0 from lengths[b] on), workgroup i = tiles[i] = (utterance, output tile),
@@ -39,8 +38,8 @@ __global__ __launch_bounds__(HE_WAVES * 64) void hilbert_kernel(const float* __r
                                                                 const int* __restrict__ tiles, float* __restrict__ env,
                                                                 double* __restrict__ partial, int B, int C, int L, int R) {
   __shared__ __attribute__((aligned(16))) unsigned char dsm[HE_LDS_BYTES];
-  float* hs = reinterpret_cast<float*>(dsm);                   // [HE_WIN]: hs[i] = hh[n0 - m0 - (HE_KS - 1) + Lc + i], 0 outside [0, 2 Lc)
-  float* xs = hs + HE_WIN;                                     // [HE_KS][HE_XLD]: xs[k][col] = sample m0 + k of the column's convolution, 0 from Lc on
+  float* hs = reinterpret_cast<float*>(dsm);                   // [HE_WIN]: hs[i] = hh[n0 - m0 - (SFM_HE_KSTEP - 1) + Lc + i], 0 outside [0, 2 Lc)
+  float* xs = hs + HE_WIN;                                     // [SFM_HE_KSTEP][HE_XLD]: xs[k][col] = sample m0 + k of the column's convolution, 0 from Lc on
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hl = lane >> 5;
   int b, t, Lb;
   if (ENV) {
@@ -55,11 +54,11 @@ __global__ __launch_bounds__(HE_WAVES * 64) void hilbert_kernel(const float* __r
   // 2 j + 1 - p with g_p[d] = h[(2 d + 2 p - 1) mod Lb]; tiles [0, ntp) are p = 0, [ntp, 2 ntp) p = 1, the table holds g_0 twice, g_1 twice
   const bool even = (Lb & 1) == 0;
   const int Lc = even ? Lb >> 1 : Lb, xst = even ? 2 : 1;       // samples of the convolution, stride of its samples in x
-  const int ntp = (Lc + HE_ROWS - 1) / HE_ROWS;
+  const int ntp = (Lc + SFM_HE_ROWS - 1) / SFM_HE_ROWS;
   const int par = (even && ntp > 0) ? t / ntp : 0;
   if (even) t -= par * ntp;
   const int xin = even ? 1 - par : 0, xout = even ? par : 0;    // first input / output sample in x
-  const int n0 = t * HE_ROWS;
+  const int n0 = t * SFM_HE_ROWS;
   if (n0 >= Lc || par > 1) {                                   // a tile behind the utterance (tables that disagree with lengths)
     if (!ENV)
       for (int i = tid; i < C * 5; i += HE_WAVES * 64) partial[(long long)blockIdx.x * C * 5 + i] = 0.0;
@@ -83,8 +82,8 @@ __global__ __launch_bounds__(HE_WAVES * 64) void hilbert_kernel(const float* __r
   auto fetch = [&](int m0) {                                   // global -> registers, one k-step ahead of the MFMAs
 #pragma unroll
     for (int i = 0; i < HE_XPT; ++i) xr[i] = (xcol[i] && m0 + lane < Lc) ? xcol[i][xst * (m0 + lane) + xin] : 0.f;
-    const int idx = n0 - m0 - (HE_KS - 1) + Lc + tid;
-    hr = (tid < HE_ROWS + HE_KS - 1 && idx >= 0 && idx < 2 * Lc) ? hh[idx] : 0.f;
+    const int idx = n0 - m0 - (SFM_HE_KSTEP - 1) + Lc + tid;
+    hr = (tid < SFM_HE_ROWS + SFM_HE_KSTEP - 1 && idx >= 0 && idx < 2 * Lc) ? hh[idx] : 0.f;
   };
 
   f32x16 acc[4], tot[4];
@@ -93,19 +92,19 @@ __global__ __launch_bounds__(HE_WAVES * 64) void hilbert_kernel(const float* __r
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[j][r] = tot[j][r] = 0.f;
   const bool active = n0 + wave * 32 < Lc;                     // this wave's 32 rows hold a sample of the utterance
-  const float* ap = hs + wave * 32 + l31 + (HE_KS - 1) - hl;
+  const float* ap = hs + wave * 32 + l31 + (SFM_HE_KSTEP - 1) - hl;
   const float* bp = xs + hl * HE_XLD + l31;
   fetch(0);
-  for (int m0 = 0; m0 < Lc; m0 += HE_KS) {
+  for (int m0 = 0; m0 < Lc; m0 += SFM_HE_KSTEP) {
     __syncthreads();                                           // the previous k-step's operand reads are done
 #pragma unroll
     for (int i = 0; i < HE_XPT; ++i) xs[lane * HE_XLD + wave + HE_WAVES * i] = xr[i];
     if (tid < HE_WIN) hs[tid] = hr;
     __syncthreads();
-    if (m0 + HE_KS < Lc) fetch(m0 + HE_KS);
+    if (m0 + SFM_HE_KSTEP < Lc) fetch(m0 + SFM_HE_KSTEP);
     if (active) {
 #pragma unroll 8
-      for (int q = 0; q < HE_KS / 2; ++q) {
+      for (int q = 0; q < SFM_HE_KSTEP / 2; ++q) {
         const float a = ap[-2 * q];
 #pragma unroll
         for (int j = 0; j < 4; ++j)
@@ -208,14 +207,14 @@ __global__ __launch_bounds__(192) void csii_frames_kernel(const float* __restric
                                                           const float* __restrict__ er, const float* __restrict__ ei,
                                                           const int* __restrict__ frame_off, const double* __restrict__ w,
                                                           double* __restrict__ score, double* __restrict__ msc) {
-  __shared__ double term[CSII_F];
+  __shared__ double term[SFM_CSII_BINS];
   const int b = blockIdx.x, f = threadIdx.x;
   const int f0 = frame_off[b], f1 = frame_off[b + 1];
-  if (f < CSII_F) {
+  if (f < SFM_CSII_BINS) {
     double pxx = 0.0, pyy = 0.0, pr = 0.0, pi = 0.0;
 #pragma unroll 4
     for (int n = f0; n < f1; ++n) {
-      const long long off = (long long)n * CSII_F + f;
+      const long long off = (long long)n * SFM_CSII_BINS + f;
       const double a0 = cr[off], a1 = ci[off], b0 = er[off], b1 = ei[off];
       pxx += a0 * a0 + a1 * a1;
       pyy += b0 * b0 + b1 * b1;
@@ -228,13 +227,13 @@ __global__ __launch_bounds__(192) void csii_frames_kernel(const float* __restric
       pxx /= cnt; pyy /= cnt; pr /= cnt; pi /= cnt;
       m = fmin(fmax((pr * pr + pi * pi) / (pxx * pyy + 1e-10), 0.0), 1.0);
     }
-    if (msc) msc[(long long)b * CSII_F + f] = m;
+    if (msc) msc[(long long)b * SFM_CSII_BINS + f] = m;
     term[f] = w[f] * m;
   }
   __syncthreads();
   if (f == 0) {
     double s = 0.0;
-    for (int i = 0; i < CSII_F; ++i) s += term[i];
+    for (int i = 0; i < SFM_CSII_BINS; ++i) s += term[i];
     score[b] = f1 > f0 ? fmin(fmax(s, 0.0), 1.0) : 0.0;
   }
 }
@@ -243,7 +242,7 @@ extern "C" int sfm_csii_frames_varlen(const float* cr, const float* ci, const fl
                                       const double* weights, double* score, double* msc, int B, int sum_frames, int F,
                                       void* stream) {
   if (!cr || !ci || !er || !ei || !frame_off || !weights || !score) return SFM_ERR_ARG;
-  if (B <= 0 || sum_frames < 0 || F != CSII_F) return SFM_ERR_SHAPE;
+  if (B <= 0 || sum_frames < 0 || F != SFM_CSII_BINS) return SFM_ERR_SHAPE;
   SFM_LAUNCH(csii_frames_kernel, dim3(B), dim3(192), 0, (hipStream_t)stream, cr, ci, er, ei, frame_off, weights, score, msc);
   return SFM_OK;
 }
@@ -252,7 +251,7 @@ extern "C" int sfm_hilbert_env(const float* x, const float* table, float* env, i
   if (!x || !table || !env) return SFM_ERR_ARG;
   if (R < 1 || L < 1 || L > (1 << 30) - 1 || (R + HE_COLS - 1) / HE_COLS > 65535) return SFM_ERR_SHAPE;
   const int Lc = (L & 1) ? L : L / 2;                          // an even L: two convolutions of half the length
-  const dim3 grid(((L & 1) ? 1 : 2) * ((Lc + HE_ROWS - 1) / HE_ROWS), (R + HE_COLS - 1) / HE_COLS);
+  const dim3 grid(((L & 1) ? 1 : 2) * ((Lc + SFM_HE_ROWS - 1) / SFM_HE_ROWS), (R + HE_COLS - 1) / HE_COLS);
   SFM_LAUNCH((hilbert_kernel<1>), grid, dim3(HE_WAVES * 64), 0, (hipStream_t)stream, x, table, (const int*)nullptr,
              (const int*)nullptr, (const int*)nullptr, env, (double*)nullptr, 1, 0, L, R);
   return SFM_OK;

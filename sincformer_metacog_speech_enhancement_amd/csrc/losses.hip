@@ -126,14 +126,20 @@ __global__ void enhancer_loss_finalize_kernel(const double* __restrict__ Sw, con
   out[3] = (float)mr;
 }
 
-// ws (optional; >= 64 * B * 5 doubles for sfm_wave_moments, >= 2048 * 4 doubles for sfm_spec_sums): one partial per workgroup,
+// ws (optional; sfm_wave_moments_ws_doubles / sfm_spec_sums_ws_doubles): one partial per workgroup,
 // folded in workgroup order by reduce.hip - the sums (and with them the loss value and its gradient) are then bit-reproducible;
 // NULL = f64 atomics
+static constexpr int WM_MAX_BLOCKS = 64;                          // workgroups per signal
+static constexpr int SPEC_MAX_BLOCKS = 2048;
+static int wave_moments_blocks(int L) { return (int)sfm_capped_blocks(L, 256, WM_MAX_BLOCKS); }
+// sized for the cap, whatever L: the scratch is one grow-only buffer
+extern "C" long long sfm_wave_moments_ws_doubles(int B, int L) { (void)L; return (long long)WM_MAX_BLOCKS * (B > 0 ? B : 0) * 5; }
+extern "C" long long sfm_spec_sums_ws_doubles(long long n) { (void)n; return (long long)SPEC_MAX_BLOCKS * 4; }
+
 extern "C" int sfm_wave_moments(const float* est, const float* tgt, double* S, int B, int L, double* ws, void* stream) {
   if (!est || !tgt || !S) return SFM_ERR_ARG;
   if (B <= 0 || L <= 0) return SFM_ERR_SHAPE;
-  int nb = (L + 255) / 256;
-  if (nb > 64) nb = 64;
+  const int nb = wave_moments_blocks(L);
   SFM_LAUNCH(wave_moments_kernel, dim3(nb, B), dim3(256), 0, (hipStream_t)stream, est, tgt, S, L, ws);
   return ws ? sfm_fold_partials_f64(ws, S, B, 5, 5, nb, 1, stream) : SFM_OK;
 }
@@ -143,8 +149,7 @@ extern "C" int sfm_wave_moments_varlen(const float* est, const float* tgt, doubl
                                        void* stream) {
   if (!est || !tgt || !S || !samp_off) return SFM_ERR_ARG;
   if (B <= 0 || max_L <= 0) return SFM_ERR_SHAPE;
-  int nb = (max_L + 255) / 256;
-  if (nb > 64) nb = 64;
+  const int nb = wave_moments_blocks(max_L);
   if ((long long)nb * B > 0x7fffffffLL) return SFM_ERR_SHAPE;    // grid x
   SFM_LAUNCH(wave_moments_varlen_kernel, dim3((unsigned)(nb * B)), dim3(256), 0, (hipStream_t)stream, est, tgt, S, samp_off, nb);
   return SFM_OK;
@@ -154,8 +159,7 @@ extern "C" int sfm_spec_sums(const float* pr, const float* pi, const float* tr, 
                              double* ws, void* stream) {
   if (!pr || !pi || !tr || !ti || !S) return SFM_ERR_ARG;
   if (n <= 0) return SFM_ERR_SHAPE;
-  long long nb = (n + 255) / 256;
-  if (nb > 2048) nb = 2048;
+  const long long nb = sfm_capped_blocks(n, 256, SPEC_MAX_BLOCKS);
   SFM_LAUNCH(spec_sums_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, pr, pi, tr, ti, S, n, ws);
   return ws ? sfm_fold_partials_f64(ws, S, 1, 4, 4, (int)nb, 1, stream) : SFM_OK;
 }

@@ -8,15 +8,14 @@
 //   PcirmOp    rho_s (c |cos phi1|)^2 / (the same + rho_n (n |cos phi2|)^2 + eps)                       masks/pcirm.py:122-131
 //   QuantOp    the step of `table` whose [boundary m, boundary m + 1) holds x, compared in double      masks/opt_pcirm.py:79-101
 //   CurrOp     Y = C + s[b] N and the mask target from C, s N, Y; the cosines of the phase differences are Re(C conj Y) / (|C| |Y|)
-// mix          mix_power_kernel: fp64 sums of clean^2 and noise^2 over fixed MIX_CHUNK-sample chunks of each utterance;
+// mix          mix_power_kernel: fp64 sums of clean^2 and noise^2 over fixed SFM_MIX_CHUNK-sample chunks of each utterance;
 //              mix_scale_kernel: ONE workgroup folds the chunks of each utterance in index order and writes scale;
 //              mix_apply_kernel: noisy = clean + scale * noise (0 at and beyond the utterance's length), and on request the
 //              unscaled noise row the utterance was mixed with (the operand of the noise STFT).
 #include "sfm_common.h"
 #include <math.h>
 
-#define MIX_CHUNK 4096                   // samples per workgroup: 16 per thread
-#define QUANT_MAX_M 16
+static_assert(SFM_MIX_CHUNK == 16 * 256, "a workgroup's chunk: 16 samples per thread");
 
 static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 static __device__ __forceinline__ float clip01(float v) { return v < 0.f ? 0.f : (v > 1.f ? 1.f : v); }   // (a NaN stays one: np.clip)
@@ -141,7 +140,7 @@ struct QuantOp {
   __device__ __forceinline__ void f(const float (&x)[NI], float (&y)[NO], NoCtx, int) const { y[0] = quant_rule(x[0], table, M); }
 };
 
-// kind: 0 spectra only, 1 IRM, 2 PCIRM, 3 OPT-PCIRM (PCIRM, quantised by `table`)
+// kind (SFM_MASK_*): NONE spectra only, IRM, PCIRM, OPT_PCIRM (the PCIRM, quantised by `table`)
 struct CurrCtx {
   float s0, s1;                          // scale of the utterance of element i, and of the next one
   int left;                              // elements of this utterance from i on
@@ -168,12 +167,12 @@ struct CurrOp {
     const float yr = cr + nr, yi = ci + ni;
     y[0] = yr;
     y[1] = yi;
-    if (kind == 0) {
+    if (kind == SFM_MASK_NONE) {
       y[2] = 0.f;
       return;
     }
     const float c2 = cr * cr + ci * ci, n2 = nr * nr + ni * ni;
-    if (kind == 1) {
+    if (kind == SFM_MASK_IRM) {
       y[2] = irm_rule(c2, n2, p, eps, root != 0);
       return;
     }
@@ -188,7 +187,7 @@ struct CurrOp {
       no = sqrtf((y2 * n2) / (ye * (n2 + eps))) * (d2 * d2 * ry);
     }
     const float m = clip01(sp / (sp + no + eps));
-    y[2] = kind == 3 ? quant_rule(m, table, M) : m;
+    y[2] = kind == SFM_MASK_OPT_PCIRM ? quant_rule(m, table, M) : m;
   }
 };
 
@@ -235,8 +234,8 @@ __global__ __launch_bounds__(256) void mix_power_kernel(const float* __restrict_
   __shared__ double red[8];
   const int b = blockIdx.y, tid = threadIdx.x;
   const MixRow r = mix_row(bank, off, ids, lengths, b, L, n_noise);
-  const int j0 = blockIdx.x * MIX_CHUNK;
-  int j1 = j0 + MIX_CHUNK;
+  const int j0 = blockIdx.x * SFM_MIX_CHUNK;
+  int j1 = j0 + SFM_MIX_CHUNK;
   if (j1 > r.len) j1 = r.len;
   double pc = 0.0, pn = 0.0;
   if (j1 > j0) {
@@ -301,8 +300,8 @@ __global__ __launch_bounds__(256) void mix_apply_kernel(const float* __restrict_
   const int b = blockIdx.y, tid = threadIdx.x;
   const MixRow r = mix_row(bank, off, ids, lengths, b, L, n_noise);
   const float sc = scale[b];
-  const int j0 = blockIdx.x * MIX_CHUNK;
-  int j1 = j0 + MIX_CHUNK;
+  const int j0 = blockIdx.x * SFM_MIX_CHUNK;
+  int j1 = j0 + SFM_MIX_CHUNK;
   if (j1 > L) j1 = L;
   const long long base = (long long)b * L;
   const float* row = clean + base;
@@ -376,7 +375,7 @@ extern "C" int sfm_mask_pcirm(const float* clean_mag, const float* noise_mag, co
 
 extern "C" int sfm_mask_quantize(const float* pcirm, const double* table, float* out, long long n, int M, void* stream) {
   if (!pcirm || !table || !out) return SFM_ERR_ARG;
-  if (M < 2 || M > QUANT_MAX_M || ew_size(n) != SFM_OK) return SFM_ERR_SHAPE;
+  if (M < 2 || M > SFM_QUANT_MAX_STEPS || ew_size(n) != SFM_OK) return SFM_ERR_SHAPE;
   QuantOp op;
   op.in[0] = pcirm, op.out[0] = out;
   op.table = table, op.M = M;
@@ -389,11 +388,15 @@ static int mix_check(int B, int L, int n_noise) {
   return SFM_OK;
 }
 
+static int mix_chunks(int L) { return (L + SFM_MIX_CHUNK - 1) / SFM_MIX_CHUNK; }
+// ws of sfm_mix_scale: a (clean^2, noise^2) pair of partials per utterance and chunk
+extern "C" long long sfm_mix_scale_ws_doubles(int B, int L) { return B > 0 && L > 0 ? 2LL * B * mix_chunks(L) : 0; }
+
 extern "C" int sfm_mix_scale(const float* clean, const float* bank, const int* bank_off, const int* noise_ids, const float* snr_db,
                              const int* lengths, double* ws, float* scale, int B, int L, int n_noise, void* stream) {
   if (!clean || !bank || !bank_off || !noise_ids || !snr_db || !ws || !scale) return SFM_ERR_ARG;
   if (mix_check(B, L, n_noise) != SFM_OK) return SFM_ERR_SHAPE;
-  const int NC = (L + MIX_CHUNK - 1) / MIX_CHUNK;
+  const int NC = mix_chunks(L);
   hipStream_t st = (hipStream_t)stream;
   SFM_LAUNCH(mix_power_kernel, dim3((unsigned)NC, (unsigned)B), dim3(256), 0, st, clean, bank, bank_off, noise_ids, lengths, ws, L,
              n_noise, (int)al16(clean));
@@ -405,7 +408,7 @@ extern "C" int sfm_mix_apply(const float* clean, const float* bank, const int* b
                              const float* scale, float* noisy, float* noise_rows, int B, int L, int n_noise, void* stream) {
   if (!clean || !bank || !bank_off || !noise_ids || !scale || !noisy) return SFM_ERR_ARG;
   if (mix_check(B, L, n_noise) != SFM_OK) return SFM_ERR_SHAPE;
-  const int NC = (L + MIX_CHUNK - 1) / MIX_CHUNK;
+  const int NC = mix_chunks(L);
   const int vec = al16(clean) && al16(noisy) && al16(noise_rows);
   SFM_LAUNCH(mix_apply_kernel, dim3((unsigned)NC, (unsigned)B), dim3(256), 0, (hipStream_t)stream, clean, bank, bank_off, noise_ids,
              lengths, scale, noisy, noise_rows, L, n_noise, vec);
@@ -416,10 +419,12 @@ extern "C" int sfm_curriculum_mask(const float* cr, const float* ci, const float
                                    const double* table, float* yr, float* yi, float* mask, int B, int T, int F, int kind, float p,
                                    float eps, int M, void* stream) {
   if (!cr || !ci || !nr || !ni || !scale || !yr || !yi) return SFM_ERR_ARG;
-  if (kind < 0 || kind > 3 || (kind != 0 && !mask) || (kind == 3 && !table) || !(eps >= 0.f)) return SFM_ERR_ARG;
-  if (kind == 1 && !(p > 0.f)) return SFM_ERR_ARG;
+  if (kind < SFM_MASK_NONE || kind > SFM_MASK_OPT_PCIRM || (kind != SFM_MASK_NONE && !mask) ||
+      (kind == SFM_MASK_OPT_PCIRM && !table) || !(eps >= 0.f))
+    return SFM_ERR_ARG;
+  if (kind == SFM_MASK_IRM && !(p > 0.f)) return SFM_ERR_ARG;
   if (B <= 0 || T <= 0 || F <= 0) return SFM_ERR_SHAPE;
-  if (kind == 3 && (M < 2 || M > QUANT_MAX_M)) return SFM_ERR_SHAPE;
+  if (kind == SFM_MASK_OPT_PCIRM && (M < 2 || M > SFM_QUANT_MAX_STEPS)) return SFM_ERR_SHAPE;
   const long long n = (long long)B * T * F;
   if ((long long)T * F > 2147483647LL || ew_size(n) != SFM_OK) return SFM_ERR_SHAPE;
   CurrOp op;

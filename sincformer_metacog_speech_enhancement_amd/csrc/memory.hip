@@ -349,7 +349,10 @@ extern "C" long long sfm_memory_param_floats(int kd, int vd, int S) {
   return 2LL * kd * kd + 4LL * kd + (long long)S * kd + (long long)S * vd + (long long)vd * vd + vd + kd + vd + 1;
 }
 
-// ws (optional, >= B * sfm_memory_param_floats(key_dim, value_dim, slots) floats): per-row copies of the gradient blob, folded in row order
+// ws (optional, sfm_memory_bwd_ws_floats floats): per-row copies of the gradient blob, folded in row order
+extern "C" long long sfm_memory_bwd_ws_floats(int B, int key_dim, int value_dim, int slots) {
+  return B > 0 ? B * sfm_memory_param_floats(key_dim, value_dim, slots) : 0;
+}
 extern "C" int sfm_memory_bwd(const float* emb, const float* params, const float* d_out, const float* d_gate, float* d_emb,
                               float* dparams, int B, int key_dim, int value_dim, int slots, float temperature, float* ws,
                               void* stream) {

@@ -131,12 +131,14 @@ __global__ __launch_bounds__(256) void adamw_apply_kernel(float* __restrict__ p,
   }
 }
 
-// ws (optional, >= 2048 doubles): one partial per workgroup folded in workgroup order (reduce.hip) instead of an f64 atomic each
+// ws (optional, sfm_sumsq_ws_doubles doubles): one partial per workgroup folded in workgroup order (reduce.hip) instead of an f64
+// atomic each; sized for the cap, whatever n
+static constexpr int SUMSQ_MAX_BLOCKS = 2048;
+extern "C" long long sfm_sumsq_ws_doubles(long long n) { (void)n; return SUMSQ_MAX_BLOCKS; }
 extern "C" int sfm_sumsq(const float* g, long long n, double* out, double* ws, void* stream) {
   if (!g || !out) return SFM_ERR_ARG;
   if (n <= 0) return SFM_ERR_SHAPE;
-  long long nb = (n + 255) / 256;
-  if (nb > 2048) nb = 2048;
+  const long long nb = sfm_capped_blocks(n, 256, SUMSQ_MAX_BLOCKS);
   SFM_LAUNCH(sumsq_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, g, n, out, ws);
   return ws ? sfm_fold_partials_f64(ws, out, 1, 1, 1, (int)nb, 1, stream) : SFM_OK;
 }

@@ -87,7 +87,7 @@ __global__ __launch_bounds__(256) void layernorm256_kernel(const float* __restri
 extern "C" int sfm_layernorm(const float* x, const float* w, const float* b, void* out16, float* out32, int M, int D,
                              int ldx, int ld16, int ld32, float eps, int act, int dtype, void* stream) {
   if (!x || !w || !b || (!out16 && !out32)) return SFM_ERR_ARG;
-  if (M <= 0 || D <= 0 || D > 512) return SFM_ERR_SHAPE;
+  if (M <= 0 || D <= 0 || D > SFM_LAYERNORM_MAX_D) return SFM_ERR_SHAPE;
   // every row stride must cover the D normalised columns, or rows would overlap (and the last one run past its buffer)
   if (ldx < D || (out16 && ld16 < D) || (out32 && ld32 < D)) return SFM_ERR_SHAPE;
   if (dtype != SFM_DT_BF16 && dtype != SFM_DT_F16) return SFM_ERR_ARG;
@@ -315,7 +315,7 @@ extern "C" int sfm_gn_apply(const void* x1, const float* sc1, const float* sh1, 
 // Tile = 64 frames (+ k-1 halo) x C channels in LDS; each work item computes
 // 4 consecutive frames of one channel pair with a sliding weight window.
 // ---------------------------------------------------------------------------
-#define DW_TT 64
+static_assert(SFM_DWCONV_TILE == 64, "frames of a workgroup of the register-resident depthwise kernels");
 template <class T>
 __global__ __launch_bounds__(256) void dwconv_bn_swish_kernel(const u16* __restrict__ x, const float* __restrict__ wdw,
                                                               const float* __restrict__ bdw, const float* __restrict__ bnw,
@@ -324,13 +324,13 @@ __global__ __launch_bounds__(256) void dwconv_bn_swish_kernel(const u16* __restr
                                                               int Tlen, int C, int KS, float eps) {
   extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];
   const int halo = KS - 1, padl = (KS - 1) / 2;
-  const int rows = DW_TT + halo;
+  const int rows = SFM_DWCONV_TILE + halo;
   u16* xs = reinterpret_cast<u16*>(dsm);                                 // [rows][C]
   float* ws = reinterpret_cast<float*>(dsm + (((size_t)rows * C * 2 + 15) & ~(size_t)15));  // [KS][C]
   float* scs = ws + (size_t)KS * C;                                      // [C] scale
   float* shs = scs + C;                                                  // [C] shift (conv bias folded)
   const int tid = threadIdx.x;
-  const int t0 = blockIdx.x * DW_TT;
+  const int t0 = blockIdx.x * SFM_DWCONV_TILE;
   const int b = blockIdx.y;
   const u16* xb = x + (long long)b * Tlen * C;
   const int cpr = C >> 3;
@@ -352,7 +352,7 @@ __global__ __launch_bounds__(256) void dwconv_bn_swish_kernel(const u16* __restr
   }
   __syncthreads();
   const int npair = C >> 1;
-  const int items = (DW_TT / 4) * npair;
+  const int items = (SFM_DWCONV_TILE / 4) * npair;
   u16* ob = out + (long long)b * Tlen * C;
   for (int it = tid; it < items; it += 256) {
     int pair = it % npair, tq = it / npair;
@@ -403,14 +403,14 @@ __global__ __launch_bounds__(256) void dwconv_reg_kernel(const u16* __restrict__
                                                          const int* __restrict__ frame_off = nullptr,
                                                          const int* __restrict__ tiles = nullptr) {
   extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];
-  u16* xs = reinterpret_cast<u16*>(dsm);                                 // [DW_TT + KS - 1][C]
-  constexpr int padl = (KS - 1) / 2, rows = DW_TT + KS - 1;
+  u16* xs = reinterpret_cast<u16*>(dsm);                                 // [SFM_DWCONV_TILE + KS - 1][C]
+  constexpr int padl = (KS - 1) / 2, rows = SFM_DWCONV_TILE + KS - 1;
   const int tid = threadIdx.x;
-  int t0 = blockIdx.x * DW_TT;
+  int t0 = blockIdx.x * SFM_DWCONV_TILE;
   long long row0 = (long long)blockIdx.y * Tlen;                         // first row of the utterance
   if (VARLEN) {
     const int u = tiles[2 * blockIdx.x];
-    t0 = tiles[2 * blockIdx.x + 1] * DW_TT;
+    t0 = tiles[2 * blockIdx.x + 1] * SFM_DWCONV_TILE;
     row0 = frame_off[u];
     Tlen = frame_off[u + 1] - (int)row0;
   }
@@ -436,7 +436,7 @@ __global__ __launch_bounds__(256) void dwconv_reg_kernel(const u16* __restrict__
   const float s0 = sc[c], s1 = sc[c + 1], h0 = sh[c], h1 = sh[c + 1];
   __syncthreads();
   const long long obase = row0 * C;
-  const int per = DW_TT / ngrp;                                          // frames per thread (multiple of 4)
+  const int per = SFM_DWCONV_TILE / ngrp;                                          // frames per thread (multiple of 4)
   for (int tl = grp * per; tl < (grp + 1) * per; tl += 4) {
     float a0[4] = {0.f, 0.f, 0.f, 0.f}, a1[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -483,16 +483,16 @@ __global__ __launch_bounds__(256) void dwconv_dot_kernel(const u16* __restrict__
                                                          const int* __restrict__ frame_off = nullptr,
                                                          const int* __restrict__ tiles = nullptr) {
   extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];
-  u16* xs = reinterpret_cast<u16*>(dsm);                                 // [DW_TT + KS - 1][C]
-  constexpr int padl = (KS - 1) / 2, rows = DW_TT + KS - 1;
+  u16* xs = reinterpret_cast<u16*>(dsm);                                 // [SFM_DWCONV_TILE + KS - 1][C]
+  constexpr int padl = (KS - 1) / 2, rows = SFM_DWCONV_TILE + KS - 1;
   constexpr int NP = (KS + 1) / 2;                                       // tap pairs (the last one = (w[KS-1], 0))
   constexpr int NR = KS + 3;                                             // staged rows a step of 4 outputs reads
   const int tid = threadIdx.x;
-  int t0 = blockIdx.x * DW_TT;
+  int t0 = blockIdx.x * SFM_DWCONV_TILE;
   long long row0 = (long long)blockIdx.y * Tlen;                         // first row of the utterance
   if (VARLEN) {
     const int u = tiles[2 * blockIdx.x];
-    t0 = tiles[2 * blockIdx.x + 1] * DW_TT;
+    t0 = tiles[2 * blockIdx.x + 1] * SFM_DWCONV_TILE;
     row0 = frame_off[u];
     Tlen = frame_off[u + 1] - (int)row0;
   }
@@ -533,7 +533,7 @@ __global__ __launch_bounds__(256) void dwconv_dot_kernel(const u16* __restrict__
   const float s0 = sc[c], s1 = sc[c + 1], h0 = sh[c], h1 = sh[c + 1];
   __syncthreads();
   const long long obase = row0 * C;
-  const int per = DW_TT / ngrp;                                          // frames per thread (multiple of 4)
+  const int per = SFM_DWCONV_TILE / ngrp;                                          // frames per thread (multiple of 4)
   for (int tl = grp * per; tl < (grp + 1) * per; tl += 4) {
     uint32_t d[NR + 1];                                                  // row k of the step: (x[k][c], x[k][c + 1])
 #pragma unroll
@@ -574,8 +574,8 @@ template <int KS, bool VARLEN = false>
 static int launch_dwconv_dot(const void* x, const float* wT, const float* sc, const float* sh, void* out, int B, int Tn,
                              int C, int act, int out_f32, hipStream_t st, const int* frame_off = nullptr,
                              const int* tiles = nullptr, int n_tiles = 0) {
-  const int lds = (DW_TT + KS - 1) * C * 2;                  // grows with C: the grant follows the widest launch so far
-  const dim3 grid = VARLEN ? dim3(n_tiles, 1) : dim3((Tn + DW_TT - 1) / DW_TT, B);
+  const int lds = (SFM_DWCONV_TILE + KS - 1) * C * 2;                  // grows with C: the grant follows the widest launch so far
+  const dim3 grid = VARLEN ? dim3(n_tiles, 1) : dim3((Tn + SFM_DWCONV_TILE - 1) / SFM_DWCONV_TILE, B);
   SFM_LAUNCH_LDS((dwconv_dot_kernel<KS, VARLEN>), grid, dim3(256), lds, st, (const u16*)x, wT, sc, sh, out, Tn, C, act, out_f32,
                  frame_off, tiles);
   return SFM_OK;
@@ -585,8 +585,8 @@ template <class T, int KS, bool VARLEN = false>
 static int launch_dwconv_reg(const void* x, const float* wT, const float* sc, const float* sh, void* out, int B, int Tn,
                              int C, int act, int out_f32, hipStream_t st, const int* frame_off = nullptr,
                              const int* tiles = nullptr, int n_tiles = 0) {
-  const int lds = (DW_TT + KS - 1) * C * 2;                  // as above
-  const dim3 grid = VARLEN ? dim3(n_tiles, 1) : dim3((Tn + DW_TT - 1) / DW_TT, B);
+  const int lds = (SFM_DWCONV_TILE + KS - 1) * C * 2;                  // as above
+  const dim3 grid = VARLEN ? dim3(n_tiles, 1) : dim3((Tn + SFM_DWCONV_TILE - 1) / SFM_DWCONV_TILE, B);
   SFM_LAUNCH_LDS((dwconv_reg_kernel<T, KS, VARLEN>), grid, dim3(256), lds, st, (const u16*)x, wT, sc, sh, out, Tn, C, act, out_f32,
                  frame_off, tiles);
   return SFM_OK;
@@ -628,7 +628,7 @@ __global__ __launch_bounds__(256) void dwconv_generic_kernel(const u16* __restri
 
 // KS 7 / 31 with C in {32, 64, 128, 256, 512}: the shapes of the register-resident kernels
 static bool dwconv_reg_shape(int C, int KS) {
-  return (KS == 7 || KS == 31) && C % 8 == 0 && C <= 512 && (256 % (C / 2)) == 0 && (DW_TT / (256 / (C / 2))) % 4 == 0;
+  return (KS == 7 || KS == 31) && C % 8 == 0 && C <= 512 && (256 % (C / 2)) == 0 && (SFM_DWCONV_TILE / (256 / (C / 2))) % 4 == 0;
 }
 
 // The routing of sfm_dwconv_folded and of its packed form (VARLEN: Tn = 0, rows = sum_T, B utterances in frame_off): the
@@ -687,7 +687,7 @@ extern "C" int sfm_dwconv_folded_varlen(const void* x, const float* wT, const fl
   if (dtype != SFM_DT_BF16 && dtype != SFM_DT_F16) return SFM_ERR_ARG;
   if (dwconv_reg_shape(C, KS)) {                               // (only these kernels read the tile table)
     if (!tiles) return SFM_ERR_ARG;
-    if (n_tiles < B || (long long)n_tiles > (long long)B * ((max_T + DW_TT - 1) / DW_TT)) return SFM_ERR_SHAPE;
+    if (n_tiles < B || (long long)n_tiles > (long long)B * ((max_T + SFM_DWCONV_TILE - 1) / SFM_DWCONV_TILE)) return SFM_ERR_SHAPE;
   }
   return dwconv_folded_route<true>(x, wT, sc, sh, out, B, 0, sum_T, C, KS, act, out_f32, dtype, (hipStream_t)stream, frame_off,
                                    tiles, n_tiles);
@@ -698,11 +698,11 @@ extern "C" int sfm_dwconv_bn_swish(const void* x, const float* wdw, const float*
                                    int C, int KS, float eps, int dtype, void* stream) {
   if (!x || !wdw || !bdw || !bnw || !bnb || !bnm || !bnv || !out) return SFM_ERR_ARG;
   if (C % 8 != 0 || KS < 1 || (KS & 1) == 0 || B <= 0 || T <= 0) return SFM_ERR_SHAPE;
-  size_t rows = DW_TT + KS - 1;
+  size_t rows = SFM_DWCONV_TILE + KS - 1;
   size_t lds_sz = ((rows * C * 2 + 15) & ~(size_t)15) + ((size_t)KS * C + 2 * (size_t)C) * 4;
   if (lds_sz > 160 * 1024) return SFM_ERR_SHAPE;
   const int lds = (int)lds_sz;
-  dim3 grid((T + DW_TT - 1) / DW_TT, B), block(256);
+  dim3 grid((T + SFM_DWCONV_TILE - 1) / SFM_DWCONV_TILE, B), block(256);
   if (dtype == SFM_DT_F16)
     SFM_LAUNCH_LDS((dwconv_bn_swish_kernel<F16>), grid, block, lds, (hipStream_t)stream, (const u16*)x, wdw, bdw,
                    bnw, bnb, bnm, bnv, (u16*)out, T, C, KS, eps);

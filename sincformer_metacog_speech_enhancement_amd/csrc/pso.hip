@@ -8,10 +8,10 @@
 //   pso_frame_coef_kernel   pcirm [B, C, T] -> a, b [B, T] (fp64): integer bucket counts, membership decided in double as
 //                           quant_rule of masks.hip decides it, the assigned values rounded to fp32 as the mask array holds them
 //   pso_split_kernel        noisy, clean [B, Lmax] -> ya, yb, clean packed back to back (fp32) and one fp64 partial of
-//                           {sum ya^2, sum ya yb, sum yb^2, sum clean^2} per PSO_CHUNK samples; pso_moments_kernel folds the
+//                           {sum ya^2, sum ya yb, sum yb^2, sum clean^2} per SFM_PSO_CHUNK samples; pso_moments_kernel folds the
 //                           chunks of each utterance in index order (the convention of the SNR mix)
 // and per round of the search (max_iter + 1 rounds, no host synchronisation):
-//   pso_fitness_kernel      grid (chunk of PSO_FR STOI frames, utterance): a wave keeps one frame's |C|, A, B in registers and
+//   pso_fitness_kernel      grid (chunk of SFM_PSO_FRAMES STOI frames, utterance): a wave keeps one frame's |C|, A, B in registers and
 //                           loops over the N positions; evaluation/stoi.py:84-95 per frame and particle in fp64; the frames of
 //                           a chunk are added in frame order: one fp64 partial per (utterance, chunk, particle)
 //   pso_step_kernel         one workgroup per swarm, one thread per particle: folds the chunks in order, then optimizer/pso.py
@@ -22,10 +22,9 @@
 #include "sfm_common.h"
 #include <math.h>
 
-#define PSO_CHUNK 4096                   // samples per workgroup of the split: 16 per thread
-#define PSO_FR 8                         // STOI frames per workgroup of the fitness: 2 per wave
-#define PSO_MAX_N 256
-#define PSO_MAX_M 16
+static_assert(SFM_PSO_CHUNK == 16 * 256, "a workgroup's chunk of the split: 16 samples per thread");
+static_assert(SFM_PSO_FRAMES == 2 * 4, "STOI frames per workgroup of the fitness: 2 per wave");
+static_assert(SFM_PSO_MAX_BINS == 16 * 64, "pso_fitness_kernel<16> holds 16 bins per lane");
 
 // index of the step that holds x (the reference's loop: a later step overrides an earlier one), -1 where none does
 static __device__ __forceinline__ int pso_bucket(float x, const double* __restrict__ table, int M) {
@@ -41,20 +40,20 @@ __global__ __launch_bounds__(256) void pso_frame_coef_kernel(const float* __rest
                                                              double* __restrict__ a, double* __restrict__ b, int C, int T, int M) {
   const int t = blockIdx.x * 256 + threadIdx.x, u = blockIdx.y;
   if (t >= T) return;
-  int cnt[PSO_MAX_M];
+  int cnt[SFM_QUANT_MAX_STEPS];
 #pragma unroll
-  for (int m = 0; m < PSO_MAX_M; ++m) cnt[m] = 0;
+  for (int m = 0; m < SFM_QUANT_MAX_STEPS; ++m) cnt[m] = 0;
   const float* col = pcirm + (long long)u * C * T + t;
   for (int c = 0; c < C; ++c) {
     const int k = pso_bucket(col[(long long)c * T], table, M);
 #pragma unroll
-    for (int m = 0; m < PSO_MAX_M; ++m) cnt[m] += (k == m) ? 1 : 0;
+    for (int m = 0; m < SFM_QUANT_MAX_STEPS; ++m) cnt[m] += (k == m) ? 1 : 0;
   }
   const int mid = M >= 3 ? 1 : -1;       // M < 3: the middle value is unused, step 2 keeps its own value
   double s = 0.0;
   int nb = 0;
 #pragma unroll
-  for (int m = 0; m < PSO_MAX_M; ++m) {
+  for (int m = 0; m < SFM_QUANT_MAX_STEPS; ++m) {
     if (m >= M) continue;
     if (m == mid) nb = cnt[m];
     else s += (double)cnt[m] * (double)(float)table[M + 1 + m];
@@ -79,8 +78,8 @@ __global__ __launch_bounds__(256) void pso_split_kernel(const float* __restrict_
   __shared__ double red[4][4];
   const int u = blockIdx.y, tid = threadIdx.x;
   const int len = pso_len(lengths, samp_off, u, Lmax);
-  const int j0 = blockIdx.x * PSO_CHUNK;
-  int j1 = j0 + PSO_CHUNK;
+  const int j0 = blockIdx.x * SFM_PSO_CHUNK;
+  int j1 = j0 + SFM_PSO_CHUNK;
   if (j1 > len) j1 = len;
   const long long src = (long long)u * Lmax, dst = samp_off[u];
   const double* au = a + (long long)u * T;
@@ -135,13 +134,13 @@ __global__ __launch_bounds__(256) void pso_fitness_kernel(const float* __restric
                                                           const double* __restrict__ S, const double* __restrict__ pos,
                                                           const int* __restrict__ stopped, double* __restrict__ partial, int N,
                                                           int F, int NC) {
-  __shared__ double corr[PSO_FR][PSO_MAX_N];
-  __shared__ double xs[PSO_MAX_N], kes[PSO_MAX_N];
+  __shared__ double corr[SFM_PSO_FRAMES][SFM_PSO_MAX_PARTICLES];
+  __shared__ double xs[SFM_PSO_MAX_PARTICLES], kes[SFM_PSO_MAX_PARTICLES];
   const int u = blockIdx.y, c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (stopped[u]) return;
-  const int f0 = frame_off[u], nf = frame_off[u + 1] - f0, k0 = c * PSO_FR;
+  const int f0 = frame_off[u], nf = frame_off[u + 1] - f0, k0 = c * SFM_PSO_FRAMES;
   if (k0 >= nf) return;
-  const int kn = nf - k0 < PSO_FR ? nf - k0 : PSO_FR;
+  const int kn = nf - k0 < SFM_PSO_FRAMES ? nf - k0 : SFM_PSO_FRAMES;
   const double Ls = (double)(lengths[u] < 1 ? 1 : lengths[u]);
   const double kc = 1.0 / (sqrt(S[4 * u + 3] / Ls) + 1e-10);                 // evaluation/stoi.py:66
   if (tid < N) {
@@ -221,7 +220,8 @@ static __device__ double pso_np_sum(const double* v, int n) {
 static __device__ __forceinline__ bool pso_better(double x, double y, int maximize) { return maximize ? x > y : x < y; }
 
 // params: {w, c1, c2, lb, ub}.  hist row `it` of swarm u: {gbest fitness, gbest position, mean fitness, position[N], fitness[N]}
-__global__ __launch_bounds__(PSO_MAX_N) void pso_step_kernel(const double* __restrict__ partial, const double* __restrict__ fit_in,
+__global__ __launch_bounds__(SFM_PSO_MAX_PARTICLES) void pso_step_kernel(const double* __restrict__ partial,
+                                                                         const double* __restrict__ fit_in,
                                                              const int* __restrict__ frame_off, const double* __restrict__ draws,
                                                              const double* __restrict__ params, double* __restrict__ pos,
                                                              double* __restrict__ vel, double* __restrict__ pbest_pos,
@@ -229,7 +229,8 @@ __global__ __launch_bounds__(PSO_MAX_N) void pso_step_kernel(const double* __res
                                                              double* __restrict__ hist, int* __restrict__ iters,
                                                              int* __restrict__ stopped, int N, int NC, int it, int max_iter,
                                                              int maximize) {
-  __shared__ double s_fit[PSO_MAX_N], s_pos[PSO_MAX_N], s_pbf[PSO_MAX_N], s_pbp[PSO_MAX_N], s_dev[PSO_MAX_N];
+  __shared__ double s_fit[SFM_PSO_MAX_PARTICLES], s_pos[SFM_PSO_MAX_PARTICLES], s_pbf[SFM_PSO_MAX_PARTICLES],
+      s_pbp[SFM_PSO_MAX_PARTICLES], s_dev[SFM_PSO_MAX_PARTICLES];
   __shared__ double s_g;
   __shared__ int s_done;
   const int u = blockIdx.x, p = threadIdx.x;
@@ -243,7 +244,7 @@ __global__ __launch_bounds__(PSO_MAX_N) void pso_step_kernel(const double* __res
     } else {
       const int nf = frame_off[u + 1] - frame_off[u];
       if (nf > 0) {
-        int nc = (nf + PSO_FR - 1) / PSO_FR;
+        int nc = (nf + SFM_PSO_FRAMES - 1) / SFM_PSO_FRAMES;
         if (nc > NC) nc = NC;
         double s = 0.0;
         for (int c = 0; c < nc; ++c) s += partial[((long long)u * NC + c) * N + p];
@@ -347,7 +348,7 @@ __global__ __launch_bounds__(256) void pso_quantize_kernel(const float* __restri
 }
 
 // ---- entry points -------------------------------------------------------------------------------------------------------------
-static int pso_steps(int M) { return M < 2 || M > PSO_MAX_M ? SFM_ERR_SHAPE : SFM_OK; }
+static int pso_steps(int M) { return M < 2 || M > SFM_QUANT_MAX_STEPS ? SFM_ERR_SHAPE : SFM_OK; }
 
 extern "C" int sfm_pso_frame_coef(const float* pcirm, const double* table, double* a, double* b, int B, int C, int T, int M,
                                   void* stream) {
@@ -359,13 +360,17 @@ extern "C" int sfm_pso_frame_coef(const float* pcirm, const double* table, doubl
   return SFM_OK;
 }
 
+static int pso_chunks(int Lmax) { return (Lmax + SFM_PSO_CHUNK - 1) / SFM_PSO_CHUNK; }
+// ws of sfm_pso_split: the four sums' partials per utterance and chunk
+extern "C" long long sfm_pso_split_ws_doubles(int B, int Lmax) { return B > 0 && Lmax > 0 ? 4LL * B * pso_chunks(Lmax) : 0; }
+
 extern "C" int sfm_pso_split(const float* noisy, const float* clean, const int* lengths, const int* samp_off, const double* a,
                              const double* b, float* ya, float* yb, float* clean_packed, double* ws, double* S, int B, int Lmax,
                              int T, int frame, int hop, void* stream) {
   if (!noisy || !clean || !lengths || !samp_off || !a || !b || !ya || !yb || !clean_packed || !ws || !S) return SFM_ERR_ARG;
   if (B <= 0 || B > 65535 || Lmax <= 0 || T <= 0 || hop <= 0 || frame < hop) return SFM_ERR_SHAPE;
   if ((long long)B * Lmax > 2147483647LL) return SFM_ERR_SHAPE;
-  const int NC = (Lmax + PSO_CHUNK - 1) / PSO_CHUNK;
+  const int NC = pso_chunks(Lmax);
   hipStream_t st = (hipStream_t)stream;
   SFM_LAUNCH(pso_split_kernel, dim3((unsigned)NC, (unsigned)B), dim3(256), 0, st, noisy, clean, lengths, samp_off, a, b, ya, yb,
              clean_packed, ws, Lmax, T, frame, hop);
@@ -373,13 +378,13 @@ extern "C" int sfm_pso_split(const float* noisy, const float* clean, const int* 
   return SFM_OK;
 }
 
-static int pso_swarm(int B, int N) { return B <= 0 || B > 65535 || N < 1 || N > PSO_MAX_N ? SFM_ERR_SHAPE : SFM_OK; }
+static int pso_swarm(int B, int N) { return B <= 0 || B > 65535 || N < 1 || N > SFM_PSO_MAX_PARTICLES ? SFM_ERR_SHAPE : SFM_OK; }
 
 extern "C" int sfm_pso_fitness(const float* cr, const float* ci, const float* ar, const float* ai, const float* br, const float* bi,
                                const int* frame_off, const int* lengths, const double* S, const double* pos, const int* stopped,
                                double* partial, int B, int N, int F, int NC, void* stream) {
   if (!cr || !ci || !ar || !ai || !br || !bi || !frame_off || !lengths || !S || !pos || !stopped || !partial) return SFM_ERR_ARG;
-  if (pso_swarm(B, N) != SFM_OK || F <= 0 || F > 1024 || NC <= 0) return SFM_ERR_SHAPE;
+  if (pso_swarm(B, N) != SFM_OK || F <= 0 || F > SFM_PSO_MAX_BINS || NC <= 0) return SFM_ERR_SHAPE;
   const dim3 grid((unsigned)NC, (unsigned)B);
   hipStream_t st = (hipStream_t)stream;
   if (F <= 128)
@@ -401,8 +406,8 @@ extern "C" int sfm_pso_step(const double* partial, const double* fitness, const 
   if (!draws || !params || !pos || !vel || !pbest_pos || !pbest_fit || !gbest || !hist || !iters || !stopped) return SFM_ERR_ARG;
   if ((partial != nullptr) == (fitness != nullptr) || (partial && !frame_off)) return SFM_ERR_ARG;
   if (pso_swarm(B, N) != SFM_OK || max_iter < 1 || it < 0 || it > max_iter || (partial && NC <= 0)) return SFM_ERR_SHAPE;
-  SFM_LAUNCH(pso_step_kernel, dim3((unsigned)B), dim3(PSO_MAX_N), 0, (hipStream_t)stream, partial, fitness, frame_off, draws, params,
-             pos, vel, pbest_pos, pbest_fit, gbest, hist, iters, stopped, N, NC, it, max_iter, maximize ? 1 : 0);
+  SFM_LAUNCH(pso_step_kernel, dim3((unsigned)B), dim3(SFM_PSO_MAX_PARTICLES), 0, (hipStream_t)stream, partial, fitness, frame_off,
+             draws, params, pos, vel, pbest_pos, pbest_fit, gbest, hist, iters, stopped, N, NC, it, max_iter, maximize ? 1 : 0);
   return SFM_OK;
 }
 

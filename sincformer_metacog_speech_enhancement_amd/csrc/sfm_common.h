@@ -320,6 +320,13 @@ inline int sfm_cu_count() {
   return n;
 }
 
+// workgroups of a grid-stride reduction over n elements, `per` of them per workgroup and pass, `cap` workgroups at most: the
+// launcher's grid and - one partial per workgroup - the count its size query (sfm_*_ws_floats / _ws_doubles) answers with
+static inline long long sfm_capped_blocks(long long n, int per, long long cap) {
+  const long long nb = (n + per - 1) / per;
+  return nb > cap ? cap : nb;
+}
+
 // reduce.hip: the ordered second pass of the split reductions (deterministic training step).  ws [S][rows][cols] compact.
 // (ws is used as scratch by the multi-level fold: its contents are destroyed)
 int sfm_fold_partials(float* ws, float* out, long long rows, int cols, long long ldo, int S, int accumulate, void* stream);

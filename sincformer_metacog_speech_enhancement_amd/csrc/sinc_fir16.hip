@@ -23,6 +23,7 @@
 #define FIR_NSUB 4                 // sub-tiles per workgroup chunk
 #define FIR_XPT ((FIR_SUB + FIR_KP + FIR_WAVES * 64 - 1) / (FIR_WAVES * 64))   // staged samples per thread
 #define FIR_SPAN (FIR_SUB + FIR_KP)
+static_assert(SFM_SINC_FIR16_WS_WORDS == 8 * 2 * FIR_C * FIR_KP, "wsh [8 shifts][2 (hi, lo)][C][FIR_KP]");
 
 // filt [C][K] fp32 -> wsh [8][2 (hi,lo)][C][FIR_KP] 16-bit, W_o[k'] = 2^12 * h[k' - o]
 template <class T>
@@ -168,7 +169,7 @@ __global__ __launch_bounds__(FIR_WAVES * 64) void sinc_fir16_kernel(const float*
   }
 }
 
-// wave [B, L] fp32, filt [64, K] fp32 (sfm_sinc_filters), wsh: workspace of 8*2*64*272 u16,
+// wave [B, L] fp32, filt [64, K] fp32 (sfm_sinc_filters), wsh: workspace of SFM_SINC_FIR16_WS_WORDS u16,
 // out [B, L, 64] channels-last (16-bit or fp32), gn_partial [B][P][8][2] with P = sfm_sinc_fir16_tiles(L).
 extern "C" int sfm_sinc_fir16_tiles(int L) {
   const int chunk = FIR_NSUB * FIR_SUB;

@@ -22,7 +22,8 @@ _CTYPES = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "float": ctypes.
 
 
 def _parse_header(path):
-    """name -> (restype, [argtypes], [parameter names]) of every `sfm_*` function the header declares, in its order"""
+    """(name -> (restype, [argtypes], [parameter names]) of every `sfm_*` function the header declares, in its order;
+    name -> int or float of every `#define SFM_<NAME> <literal>` line, without the prefix)"""
     def ctype(text, decl):
         words = [w for w in text.replace("*", " * ").split() if w != "const"]
         if "*" not in words and " ".join(words) not in _CTYPES:
@@ -31,6 +32,15 @@ def _parse_header(path):
 
     with open(path) as f:
         src = re.sub(r"/\*.*?\*/|//[^\n]*", " ", f.read(), flags=re.S)
+    constants = {}
+    for line in re.findall(r"^[ \t]*#[ \t]*define[ \t]+SFM_[^\n]*", src, flags=re.M):      # as loud as the declarations below
+        m = re.match(r"\s*#\s*define\s+SFM_(\w+)\s+\(?(-?\d+(\.\d+)?)\)?\s*$", line)
+        if m is None or m.group(1) in constants:
+            raise SyntaxError("%s: not a (new) `#define SFM_<NAME> <literal>` line: %s" % (path, line.strip()))
+        constants[m.group(1)] = float(m.group(2)) if m.group(3) else int(m.group(2))
+    n_defines = len(re.findall(r"#\s*define\s+SFM_", src))                    # (one that does not start its line is lost above)
+    if n_defines != len(constants):
+        raise SyntaxError("%s: %d `#define SFM_` occurrences, %d parsed constants" % (path, n_defines, len(constants)))
     abi = {}
     for m in re.finditer(r"^([^\n;(){}#]*?)\b(sfm_\w+)\s*\(([^()]*)\)\s*;", src, flags=re.M):
         ret, name, params = m.groups()
@@ -40,10 +50,10 @@ def _parse_header(path):
     lost = [src[m.start():m.start() + 80].split("\n")[0] for m in seen if m.group(0).rstrip("( \t\n") not in abi]
     if lost or len(seen) != len(abi):
         raise SyntaxError("%s: %d `sfm_*(` occurrences, %d parsed declarations; not parsed: %s" % (path, len(seen), len(abi), lost))
-    return abi
+    return abi, constants
 
 
-ABI = _parse_header(HEADER)
+ABI, CONSTANTS = _parse_header(HEADER)                                        # CONSTANTS["MIX_CHUNK"] = SFM_MIX_CHUNK
 SIGNATURES = {name: argtypes for name, (_, argtypes, _) in ABI.items()}      # name -> argtypes, in the header's order
 
 _lib = None
@@ -73,7 +83,7 @@ def load():
     return lib
 
 
-_ERR = {-1: "bad argument", -2: "unsupported shape", -3: "kernel launch failed"}
+_ERR = {CONSTANTS["ERR_ARG"]: "bad argument", CONSTANTS["ERR_SHAPE"]: "unsupported shape", CONSTANTS["ERR_LAUNCH"]: "kernel launch failed"}
 
 
 def check(rc, name):

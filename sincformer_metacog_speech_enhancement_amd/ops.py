@@ -9,9 +9,11 @@ import torch
 
 from . import lib as _lib
 
-EPI_NONE, EPI_SWISH, EPI_GELU, EPI_RESID, EPI_GLU, EPI_SIGMOID, EPI_TANH_SCALE, EPI_SIGMA, EPI_CPEA = range(9)
+_K = _lib.CONSTANTS                 # every number shared with the kernels is read from include/sincformer_hip.h (SFM_<NAME>)
+EPI_NONE, EPI_SWISH, EPI_GELU, EPI_RESID, EPI_GLU, EPI_SIGMOID, EPI_TANH_SCALE, EPI_SIGMA, EPI_CPEA = (
+    _K["EPI_" + _n] for _n in ("NONE", "SWISH", "GELU", "RESID", "GLU", "SIGMOID", "TANH_SCALE", "SIGMA", "CPEA"))
 
-_DT_ID = {torch.bfloat16: 0, torch.float16: 1}
+_DT_ID = {torch.bfloat16: _K["DT_BF16"], torch.float16: _K["DT_F16"]}
 import os as _os
 TRAIN_DTYPE = torch.float16         # base (training) operand format: the reference's own AMP recipe, see reset_precision
 _state = {"dtype": TRAIN_DTYPE}
@@ -649,7 +651,7 @@ def attention(qkv16, B, T, H, hd, out=None, prescaled=False, out_dtype=None):
     return out
 
 
-LAYERNORM_MAX_D = 512      # sfm_layernorm / sfm_layernorm_bwd_*: the widest row they normalise (and so the widest Conformer d_model)
+LAYERNORM_MAX_D = _K["LAYERNORM_MAX_D"]      # the widest row sfm_layernorm / sfm_layernorm_bwd_* normalise (so the widest d_model)
 
 
 def layernorm_bytes(M, D, has_out16, has_out32):
@@ -801,9 +803,9 @@ def istft_ola(frames, win2, out, B, T, Ln, n_fft, hop, win, ld_frames):
 # of every [sum_T, ...] matrix, its samples = [samp_off[u], samp_off[u + 1]) of the packed waveform; the offsets are int32 device
 # tensors (functional.PackedSegments uploads them with the two work tables below in one copy).
 # ---------------------------------------------------------------------------
-ATTN_QTILE = 128      # query rows of a workgroup of attn_fwd_hd64_kernel
-DWCONV_TILE = 64      # frames of a workgroup of the register-resident depthwise kernels (DW_TT)
-_XCDS, _XCD_RUN = 8, 8
+ATTN_QTILE = _K["ATTN_QTILE"]       # query rows of a workgroup of attn_fwd_hd64_kernel
+DWCONV_TILE = _K["DWCONV_TILE"]     # frames of a workgroup of the register-resident depthwise kernels
+_XCDS, _XCD_RUN = _K["XCDS"], _K["XCD_RUN"]
 
 
 def attention_items(frame_counts, H):
@@ -962,7 +964,7 @@ def sinc_fir16(wave, filt, out, B, L, C, K, want_stats=True, passes=0):
     (fp32-class accuracy), 1 = operands rounded once, 0 = auto (1 for fp16 operands with a 16-bit result, else 3)."""
     Lb = _lib.load()
     dev = wave.device
-    wsh = torch.empty(8 * 2 * 64 * 272, device=dev, dtype=torch.int16)
+    wsh = torch.empty(_K["SINC_FIR16_WS_WORDS"], device=dev, dtype=torch.int16)
     P = Lb.sfm_sinc_fir16_tiles(L)
     part = torch.zeros(B, P, 8, 2, device=dev, dtype=torch.float32) if want_stats else None
     out_f32 = 1 if out.dtype == torch.float32 else 0
@@ -976,7 +978,8 @@ def wave_moments(est, tgt):
     L = _lib.load()
     B, Ln = est.shape
     S = torch.zeros(B, 5, device=est.device, dtype=torch.float64)
-    _call("loss_reduce", L.sfm_wave_moments, (_p(est), _p(tgt), _p(S), B, Ln, _p(_ws(64 * B * 5, est.device, torch.float64)), _stream()),
+    _call("loss_reduce", L.sfm_wave_moments, (_p(est), _p(tgt), _p(S), B, Ln,
+                                              _p(_ws(L.sfm_wave_moments_ws_doubles(B, Ln), est.device, torch.float64)), _stream()),
           0.0, 8.0 * B * Ln)
     return S
 
@@ -1040,6 +1043,10 @@ def _ws64(n, device):
     return t if t is not None else torch.empty(int(n), device=device, dtype=torch.float64)
 
 
+PSTOI_MAX_BANDS, PSTOI_MAX_BINS = _K["PSTOI_MAX_BANDS"], _K["PSTOI_MAX_BINS"]             # sfm_pstoi_loss: NB, F
+PSTOI_MIN_FRAME_LEN, PSTOI_MAX_FRAME_LEN = _K["PSTOI_MIN_FRAME_LEN"], _K["PSTOI_MAX_FRAME_LEN"]
+
+
 def pstoi_loss(enh, clean, band_w, need_grad=False, frame_len=30, beta=15.0):
     """PerceptualSTOILoss (training/losses.py:89-143) in one launch.  enh / clean: fp32 contiguous magnitudes [B, F, T], or
     (real, imag) pairs of channels-last [B, T, F] tensors; band_w [NB, F].  -> (loss [1] fp32, gradient to enh or None: one
@@ -1055,7 +1062,8 @@ def pstoi_loss(enh, clean, band_w, need_grad=False, frame_len=30, beta=15.0):
         B, F, T = e0.shape
     NB = band_w.shape[0]
     FL = int(frame_len)
-    if band_w.shape[1] != F or c0.shape != e0.shape or NB > 32 or F > 257 or not 2 <= FL <= 32 or T < FL:
+    if band_w.shape[1] != F or c0.shape != e0.shape or NB > PSTOI_MAX_BANDS or F > PSTOI_MAX_BINS or \
+            not PSTOI_MIN_FRAME_LEN <= FL <= PSTOI_MAX_FRAME_LEN or T < FL:
         _lib.check(-2, "pstoi_loss")
     loss = torch.empty(1, device=e0.device, dtype=torch.float32)
     g0 = torch.empty_like(e0) if need_grad else None
@@ -1063,8 +1071,8 @@ def pstoi_loss(enh, clean, band_w, need_grad=False, frame_len=30, beta=15.0):
     S = T // FL
     n = e0.numel()
     _call("pstoi_loss", L.sfm_pstoi_loss, (_p(e0), _p(e1), _p(c0), _p(c1), _p(band_w), _p(loss), _p(g0), _p(g1),
-                                           _p(_ws64(B * S + 1, e0.device)), B, T, F, NB, FL, float(beta), 1 if pair else 0,
-                                           _stream()),
+                                           _p(_ws64(L.sfm_pstoi_loss_ws_doubles(B, T, FL), e0.device)), B, T, F, NB, FL, float(beta),
+                                           1 if pair else 0, _stream()),
           (6.0 if need_grad else 4.0) * NB * F * B * S * FL,
           pstoi_bytes(B, T, F, FL, pair, need_grad))
     return loss, ((g0, g1) if pair else g0) if need_grad else None
@@ -1088,7 +1096,8 @@ def mse_loss(pred, target, need_grad=False):
     loss = torch.empty(1, device=pred.device, dtype=torch.float32)
     grad = torch.empty_like(pred) if need_grad else None
     n = pred.numel()
-    _call("mse_loss", L.sfm_mse_loss, (_p(pred), _p(target), _p(loss), _p(grad), _p(_ws64(1025, pred.device)), n, _stream()),
+    _call("mse_loss", L.sfm_mse_loss, (_p(pred), _p(target), _p(loss), _p(grad), _p(_ws64(L.sfm_mse_loss_ws_doubles(n), pred.device)),
+                                       n, _stream()),
           3.0 * n, (12.0 if need_grad else 8.0) * n)
     return loss, grad
 
@@ -1096,9 +1105,9 @@ def mse_loss(pred, target, need_grad=False):
 # ---------------------------------------------------------------------------
 # curriculum batches: mask targets and the SNR mix (csrc/masks.hip)
 # ---------------------------------------------------------------------------
-MIX_CHUNK = 4096                    # samples per workgroup of sfm_mix_scale / sfm_mix_apply
-QUANT_MAX_STEPS = 16                # sfm_mask_quantize
-MASK_KINDS = {None: 0, "irm": 1, "pcirm": 2, "opt_pcirm": 3}
+MIX_CHUNK = _K["MIX_CHUNK"]                    # samples per workgroup of sfm_mix_scale / sfm_mix_apply
+QUANT_MAX_STEPS = _K["QUANT_MAX_STEPS"]        # sfm_mask_quantize
+MASK_KINDS = {None: _K["MASK_NONE"], "irm": _K["MASK_IRM"], "pcirm": _K["MASK_PCIRM"], "opt_pcirm": _K["MASK_OPT_PCIRM"]}
 
 
 def _same_planes(name, *ts):
@@ -1173,7 +1182,7 @@ def mix_scale(clean, bank, bank_off, noise_ids, snr_db, lengths=None):
     B, Ln = clean.shape
     n_noise = bank_off.numel() - 1
     scale = torch.empty(B, device=clean.device, dtype=torch.float32)
-    ws = _ws64(2 * B * ((Ln + MIX_CHUNK - 1) // MIX_CHUNK), clean.device)
+    ws = _ws64(L.sfm_mix_scale_ws_doubles(B, Ln), clean.device)
     _call("mix", L.sfm_mix_scale, (_p(clean), _p(bank), _p(bank_off), _p(noise_ids), _p(snr_db), _p(lengths), _p(ws), _p(scale), B,
                                    Ln, n_noise, _stream()), 4.0 * B * Ln, 8.0 * B * Ln, "scale B%d L%d" % (B, Ln))
     return scale
@@ -1201,7 +1210,8 @@ def curriculum_mask(cr, ci, nr, ni, scale, kind=None, p=0.5, eps=1e-10, table=No
     B, T, F = cr.shape
     _same_planes("curriculum_mask", cr, ci, nr, ni)
     k = MASK_KINDS[kind]
-    if scale.numel() != B or scale.dtype != torch.float32 or (k == 3 and (table is None or table.numel() != 2 * M + 1)):
+    if scale.numel() != B or scale.dtype != torch.float32 or \
+            (k == MASK_KINDS["opt_pcirm"] and (table is None or table.numel() != 2 * M + 1)):
         _lib.check(-2, "curriculum_mask")
     yr, yi = torch.empty_like(cr), torch.empty_like(cr)
     mask = torch.empty_like(cr) if k else None
@@ -1215,10 +1225,10 @@ def curriculum_mask(cr, ci, nr, ni, scale, kind=None, p=0.5, eps=1e-10, table=No
 # ---------------------------------------------------------------------------
 # the PSO search of OPT-PCIRM's middle step (csrc/pso.hip)
 # ---------------------------------------------------------------------------
-PSO_CHUNK = 4096                    # samples per workgroup of sfm_pso_split
-PSO_FRAMES = 8                      # STOI frames per workgroup of sfm_pso_fitness
-PSO_MAX_PARTICLES = 256
-PSO_MAX_BINS = 1024
+PSO_CHUNK = _K["PSO_CHUNK"]                    # samples per workgroup of sfm_pso_split
+PSO_FRAMES = _K["PSO_FRAMES"]                  # STOI frames per workgroup of sfm_pso_fitness
+PSO_MAX_PARTICLES = _K["PSO_MAX_PARTICLES"]
+PSO_MAX_BINS = _K["PSO_MAX_BINS"]
 
 
 def _pso_is(t, dtype, numel):
@@ -1256,7 +1266,7 @@ def pso_split(noisy, clean, lengths, samp_off, a, b, sum_L, frame, hop):
     dev = noisy.device
     ya, yb, cp = (torch.empty(max(int(sum_L), 1), device=dev, dtype=torch.float32) for _ in range(3))
     S = torch.empty(B, 4, device=dev, dtype=torch.float64)
-    ws = _ws64(4 * B * ((Lmax + PSO_CHUNK - 1) // PSO_CHUNK), dev)
+    ws = _ws64(L.sfm_pso_split_ws_doubles(B, Lmax), dev)
     _call("pso_prepare", L.sfm_pso_split, (_p(noisy), _p(clean), _p(lengths), _p(samp_off), _p(a), _p(b), _p(ya), _p(yb), _p(cp),
                                            _p(ws), _p(S), B, Lmax, T, int(frame), int(hop), _stream()),
           8.0 * sum_L, 20.0 * sum_L + 16.0 * B * T, "split B%d L%d" % (B, Lmax))
@@ -1328,10 +1338,10 @@ def pso_quantize(pcirm, table, middle, M):
 # ---------------------------------------------------------------------------
 # gammatone T-F analysis (csrc/gammatone.hip; signal_processing/gammatone.py)
 # ---------------------------------------------------------------------------
-GT_COLS = 64                        # channel columns of the tap and twiddle operands (C <= 64, zero beyond C)
-GT_ROWS = 384                       # samples per workgroup of sfm_gammatone_fir / sfm_gammatone_tf
-GT_MAX_TAPS = 2048
-GT_LDS_MAX = 160 * 1024
+GT_COLS = _K["GT_COLS"]                        # channel columns of the tap and twiddle operands (C <= 64, zero beyond C)
+GT_ROWS = _K["GT_ROWS"]                        # samples per workgroup of sfm_gammatone_fir / sfm_gammatone_tf
+GT_MAX_TAPS = _K["GT_MAX_TAPS"]
+GT_LDS_MAX = _K["GT_LDS_MAX"]
 
 
 def set_gammatone_fused(flag):
@@ -1341,9 +1351,9 @@ def set_gammatone_fused(flag):
 
 
 def gammatone_tf_fits(K, hop):
-    """sfm_gammatone_tf takes K taps (a multiple of 8) and this hop: one hop-block fits the workgroup's rows and its LDS image fits"""
-    lds = 4 * (GT_ROWS + K + GT_ROWS * 65 + 2 * hop * GT_COLS)
-    return 8 <= K <= GT_MAX_TAPS and K % 8 == 0 and 2 <= hop <= GT_ROWS and hop % 2 == 0 and lds <= GT_LDS_MAX
+    """sfm_gammatone_tf takes K taps (a multiple of 8) and this hop: one hop-block fits the workgroup's rows and its LDS image fits
+    (the library's own predicate; no device work)"""
+    return bool(_lib.load().sfm_gammatone_tf_fits(int(K), int(hop)))
 
 
 def _gt_bank(name, sig, taps, C, lengths):
@@ -1375,8 +1385,8 @@ def gammatone_tf(sig, taps, tw, C, hop, lengths=None):
     L_ = _lib.load()
     B, L, K = _gt_bank("gammatone_tf", sig, taps, C, lengths)
     nblocks = L // hop if hop > 0 else 0
-    if not gammatone_tf_fits(K, hop) or nblocks < 1 or tw.dtype != torch.float32 or tuple(tw.shape) != (2, hop, GT_COLS) or \
-            not tw.is_contiguous():
+    # (K and hop themselves - sfm_gammatone_tf_fits - are the launcher's to refuse: it sees them)
+    if nblocks < 1 or tw.dtype != torch.float32 or tuple(tw.shape) != (2, hop, GT_COLS) or not tw.is_contiguous():
         _lib.check(-2, "gammatone_tf")
     partial = torch.empty(B, nblocks, C, 5, device=sig.device, dtype=torch.float32)
     n = float(B) * nblocks * hop
@@ -1430,9 +1440,9 @@ def gammatone_tf_finish(partial, rot, T, L, frame, hop, N, two, lengths=None, wa
 # ---------------------------------------------------------------------------
 # the DNN front end (csrc/features.hip; signal_processing/features.py)
 # ---------------------------------------------------------------------------
-FE_MAX_FILTERS, FE_MAX_BINS, FE_MAX_COEFFS = 64, 257, 16
-CEP_POWER, CEP_MAGNITUDE, CEP_BLOCKS = 0, 1, 2              # sfm_cepstral's in_mode
-CEP_NONE, CEP_LOG, CEP_CBRT = 0, 1, 2                       # its compress
+FE_MAX_FILTERS, FE_MAX_BINS, FE_MAX_COEFFS = _K["FE_MAX_FILTERS"], _K["FE_MAX_BINS"], _K["FE_MAX_COEFFS"]
+CEP_POWER, CEP_MAGNITUDE, CEP_BLOCKS = _K["CEP_POWER"], _K["CEP_MAGNITUDE"], _K["CEP_BLOCKS"]      # sfm_cepstral's in_mode
+CEP_NONE, CEP_LOG, CEP_CBRT = _K["CEP_NONE"], _K["CEP_LOG"], _K["CEP_CBRT"]                        # its compress
 
 
 def _fe_lengths(name, lengths, B):
@@ -1544,7 +1554,7 @@ def rows_mean(src, col_off, N, *, L, frame, hop, den=0, lengths=None):
 # ---------------------------------------------------------------------------
 # Meddis hair cell (csrc/haircell.hip; signal_processing/haircell.py)
 # ---------------------------------------------------------------------------
-HC_PARAMS = 12                      # par = {A, B, y, l, r, x, h, M, dt, q0, c0, w0}, fp64
+HC_PARAMS = _K["HC_PARAMS"]         # par = {A, B, y, l, r, x, h, M, dt, q0, c0, w0}, fp64
 HC_STEP_FLOPS = 24.0                # fp64 operations of one Euler step: 3 for k, 6 + 6 + 5 for q, c, w with their clamps, 1 for h c,
                                     # 3 for the two frame sums (counted in both forms: the algorithm, not the variant)
 
@@ -1590,7 +1600,8 @@ def spec_sums(pr, pi, tr, ti, out=None):
     L = _lib.load()
     S = torch.zeros(4, device=pr.device, dtype=torch.float64) if out is None else out
     _call("loss_reduce", L.sfm_spec_sums, (_p(pr), _p(pi), _p(tr), _p(ti), _p(S), pr.numel(),
-                                           _p(_ws(2048 * 4, pr.device, torch.float64)), _stream()), 0.0, 16.0 * pr.numel())
+                                           _p(_ws(L.sfm_spec_sums_ws_doubles(pr.numel()), pr.device, torch.float64)), _stream()),
+          0.0, 16.0 * pr.numel())
     return S
 
 
@@ -2068,7 +2079,7 @@ def memory_bwd(emb, params, d_out, d_gate, key_dim, value_dim, slots, temperatur
         npar = int(L.sfm_memory_param_floats(key_dim, value_dim, slots))
         if npar != params.numel():
             raise RuntimeError("memory_bwd: the parameter blob has %d floats, the kernel's layout %d" % (params.numel(), npar))
-        ws = _ws(Bn * npar, emb.device)
+        ws = _ws(L.sfm_memory_bwd_ws_floats(Bn, key_dim, value_dim, slots), emb.device)
     _call("memory_bwd", L.sfm_memory_bwd, (_p(emb), _p(params), _p(d_out), _p(d_gate), _p(d_emb), _p(dparams), Bn, key_dim, value_dim,
                                            slots, float(temperature), _p(ws), _stream()))
     return d_emb, dparams
@@ -2204,7 +2215,7 @@ def vq_backward(x, idx, centroids, g_q, g_loss, beta):
 # ---------------------------------------------------------------------------
 # AdversarialLoss (training/losses.py:150-289): csrc/adversarial.hip around gemm16 / conv_wgrad16 / conv_dgrad16
 # ---------------------------------------------------------------------------
-ADV_MAX_WIDTH = 512                     # first-layer Cin after zero padding (257 bins -> 512)
+ADV_MAX_WIDTH = _K["ADV_MAX_WIDTH"]     # first-layer Cin after zero padding (257 bins -> 512)
 
 
 def adv_plan(n_freq, channels):
@@ -2237,7 +2248,7 @@ def adv_sn_table(plan, convs, device):
     return torch.tensor(rows, dtype=torch.int64).to(device)
 
 
-ADV_LO_SCALE = 2048.0               # adversarial.hip: a forward operand is hi + lo / 2048
+ADV_LO_SCALE = _K["ADV_LO_SCALE"]   # adversarial.hip: a forward operand is hi + lo / 2048
 
 
 def adv_sn_views(L_, packed, saved, packed_lo=None):
@@ -2332,7 +2343,7 @@ def adv_leaky(z, z_real=None, loss=None, scale=0.0):
     n = z.numel()
     a16 = torch.empty(z.shape, device=z.device, dtype=_state["dtype"])
     lo = torch.empty_like(a16)
-    ws = _ws64(2048, z.device) if z_real is not None else None
+    ws = _ws64(L.sfm_adv_leaky_ws_doubles(n), z.device) if z_real is not None else None
     _call("adv_leaky", L.sfm_adv_leaky, (_p(z), _p(z_real), _p(a16), _p(lo), _p(ws), _p(loss), float(scale), n, _dt(), _stream()),
           (4.0 if z_real is not None else 1.0) * n, (12.0 if z_real is not None else 8.0) * n)
     return a16, lo
@@ -2383,7 +2394,7 @@ def adv_head(a16, a16lo, w16, w16lo, bias, loss, target, scale):
     L = _lib.load()
     B, T, C = a16.shape
     out = torch.empty(B, T, device=a16.device, dtype=torch.float32)
-    ws = _ws64((B * T + 3) // 4, a16.device)
+    ws = _ws64(L.sfm_adv_head_ws_doubles(B, T), a16.device)
     _call("adv_head", L.sfm_adv_head, (_p(a16), _p(a16lo), _p(w16), _p(w16lo), _p(bias), _p(out), _p(ws), _p(loss), float(target),
                                        float(scale), B, T, C, _dt(), _stream()),
           6.0 * B * T * C, 4.0 * B * T * C + 12.0 * C + 4.0 * B * T)
@@ -2399,7 +2410,7 @@ def adv_head_bwd(a16, w16, out, g, coef, cnorm, target, want_dw):
     dwb = torch.empty(3 * C + 1, device=a16.device, dtype=torch.float32) if want_dw else None
     ws = None
     if want_dw:
-        n = (B * T + 63) // 64 * (3 * C + 1)
+        n = L.sfm_adv_head_bwd_ws_floats(B, T, C)
         ws = _ws(n, a16.device)
         ws = ws if ws is not None else torch.empty(n, device=a16.device, dtype=torch.float32)
     _call("adv_head", L.sfm_adv_head_bwd, (_p(a16), _p(w16), _p(out), _p(g), float(coef), float(cnorm), float(target), _p(da), _p(dwb),
@@ -2412,9 +2423,9 @@ def adv_head_bwd(a16, w16, out, g, coef, cnorm, target, want_dw):
 # ---------------------------------------------------------------------------
 # CSII and NCM (csrc/intelligibility.hip; evaluation/csii.py, evaluation/ncm.py)
 # ---------------------------------------------------------------------------
-CSII_BINS = 129                     # rfft(., 256) bins of the coherence
-HE_ROWS = 256                       # output samples per workgroup of the Hilbert kernel (its output tile)
-HE_KSTEP = 64                       # input samples per staged k-step (one accumulation segment)
+CSII_BINS = _K["CSII_BINS"]         # rfft(., 256) bins of the coherence
+HE_ROWS = _K["HE_ROWS"]             # output samples per workgroup of the Hilbert kernel (its output tile)
+HE_KSTEP = _K["HE_KSTEP"]           # input samples per staged k-step (one accumulation segment)
 _HILBERT_TAB = {}                   # L -> fp32 [2 L], host (at most HILBERT_TAB_CACHE lengths)
 HILBERT_TAB_CACHE = 1024
 
@@ -2542,9 +2553,9 @@ def ncm_finish(partial, tile_off, lengths, weights, B, C):
 # ---------------------------------------------------------------------------
 # SpeechEnhancementDNN (csrc/dnn.hip)
 # ---------------------------------------------------------------------------
-DNN_ROW_TILE = 128                  # rows of a workgroup of dnn_layer_kernel (DNN_BM)
-DNN_ACT = {None: 0, "relu": 1, "sigmoid": 2}
-DNN_CONTEXT_MAX_K = 4096            # context rows with statistics: mean and std sit in LDS beside the tiles
+DNN_ROW_TILE = _K["DNN_ROW_TILE"]   # rows of a workgroup of dnn_layer_kernel
+DNN_ACT = {None: _K["DNN_ACT_NONE"], "relu": _K["DNN_ACT_RELU"], "sigmoid": _K["DNN_ACT_SIGMOID"]}
+DNN_CONTEXT_MAX_K = _K["DNN_CONTEXT_MAX_K"]    # context rows with statistics: mean and std sit in LDS beside the tiles
 
 
 def dnn_layer(a, pw, *, act=None, out=None, out_dtype=None, p_drop=0.0, seed=0, context=None, frames=None, mean=None, std=None):

@@ -90,7 +90,6 @@ class PerceptualSTOILoss(HipModule):
 
 
 ADV_MIN_FRAMES = 4                  # 4 -> 2 -> 1 through the two pools; at 3 the second pool has no output
-ADV_MAX_WIDTH = 512                 # first-layer Cin after zero padding (ops.ADV_MAX_WIDTH)
 ADV_CHANNELS = ((64, 128, 256, 512), (64, 128, 256), (32, 64, 128))
 
 
@@ -127,8 +126,9 @@ class SubDiscriminator(HipModule):
 
 
 def _adv_check(n_freq, x, name="AdversarialLoss", cl=False):
-    if n_freq > ADV_MAX_WIDTH:
-        raise NotImplementedError("%s (HIP build): at most %d frequency bins; got %d" % (name, ADV_MAX_WIDTH, n_freq))
+    from .. import ops
+    if n_freq > ops.ADV_MAX_WIDTH:
+        raise NotImplementedError("%s (HIP build): at most %d frequency bins; got %d" % (name, ops.ADV_MAX_WIDTH, n_freq))
     if x.dim() != 3:
         raise ValueError("%s: a rank-3 spectrogram is needed; got shape %s" % (name, tuple(x.shape)))
     frames_dim, bins_dim = (1, 2) if cl else (2, 1)

@@ -29,6 +29,7 @@ INPUTS = {
     "e": (6, 64, 4000, 50, 16000),           # STOI frames of 409 samples, 205 bins
     "f": (8, 64, 4000, 50, 44100),           # STOI frames of 1128 samples, 565 bins: the fitness kernel's widest form
     "short": (7, 64, 150, 2, 8000),          # no STOI frame
+    "g": (9, 5, 4097, 52, 8000),             # one sample past the split's 4096-sample chunk: two partials per sum
 }
 # the searches run against the reference: name -> (input, N, max_iter, np.random seed)
 TRAJECTORIES = {"t1": ("a", 8, 8, 1), "t2": ("b", 8, 8, 3), "t3": ("a", 12, 10, 5), "t4": ("c", 6, 8, 2)}

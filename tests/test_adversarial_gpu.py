@@ -226,6 +226,57 @@ def test_every_element_of_the_input_gradient_is_written(mods, shape, pair):
         assert torch.equal(dx, d[:, :, :F].transpose(1, 2))
 
 
+@pytest.mark.parametrize("n", [4 * 256 + 4, 2048 * 4 * 256 + 4])
+def test_leaky_feature_term_partials(mods, n):
+    """sfm_adv_leaky with z_real, called directly: one quad past one workgroup's share of a pass (256 threads x 4), and one quad
+    past the share of the 2048 workgroups its grid is capped at.  loss += scale x sum |leaky(z) - leaky(z_real)|, the terms in
+    fp32 (two products by the slope and a difference: three roundings of values no larger than |leaky(z)| + |leaky(z_real)|),
+    the sum in float64 in a fixed order: within 4 x 2^-24 x scale x sum (|leaky(z)| + |leaky(z_real)|) of the float64 value,
+    the factor this suite gives rows that only add and multiply; and the same bits from run to run."""
+    ops = mods["ops"]
+    ops.set_compute_dtype(torch.float16)
+    g = torch.Generator().manual_seed(177)
+    z, zr = torch.randn(n, generator=g), torch.randn(n, generator=g)
+    scale, start = 0.37, 1.5
+    leaky = lambda t: torch.where(t > 0, t.double(), 0.2 * t.double())
+    want = start + scale * float((leaky(z) - leaky(zr)).abs().sum())
+    bound = 4 * U32 * scale * float((leaky(z).abs() + leaky(zr).abs()).sum())
+    got = []
+    for _ in range(2):
+        loss = torch.full((1,), start, device="cuda", dtype=torch.float64)
+        a16, _ = ops.adv_leaky(z.cuda(), zr.cuda(), loss, scale)
+        got.append(float(loss))
+    print("ROW | adv_leaky n %d | bound %.3e | observed %.3e" % (n, bound, abs(got[0] - want)))
+    assert abs(got[0] - want) <= bound and got[0] == got[1]
+    assert torch.equal(a16.cpu(), torch.where(z > 0, z, 0.2 * z).half())
+
+
+@pytest.mark.parametrize("fmt", list(FMTS))
+def test_head_weight_gradient_over_two_chunks(mods, fmt):
+    """sfm_adv_head_bwd with the weight gradient, called directly at B T = 65: one row past the 64 rows of a chunk, so two
+    partial rows [3 C + 1] are folded.  dw, db and da against float64 on the same 16-bit operands, within this file's gradient
+    bound; an utterance boundary falls inside the first chunk (the taps must not cross it)."""
+    ops = mods["ops"]
+    ops.set_compute_dtype(FMTS[fmt])
+    B, T, C = 5, 13, 8
+    g = torch.Generator().manual_seed(178)
+    a16 = torch.randn(B, T, C, generator=g).to(FMTS[fmt])
+    w16 = (0.3 * torch.randn(3, C, generator=g)).to(FMTS[fmt])
+    out = torch.randn(B, T, generator=g)
+    gin, coef, target = torch.tensor([0.7]), 0.25, 1.0
+    da, dwb = ops.adv_head_bwd(a16.cuda(), w16.reshape(-1).cuda(), out.cuda(), gin.cuda(), coef, 1.0, target, True)
+    dout = (float(gin) * coef) * (out.double() - target)                                  # [B, T]
+    ap = torch.nn.functional.pad(a16.double(), (0, 0, 1, 1))                                # [B, T + 2, C]
+    dw = torch.stack([(dout.unsqueeze(-1) * ap[:, tap:tap + T]).sum((0, 1)) for tap in range(3)])
+    dp = torch.nn.functional.pad(dout, (1, 1))
+    da64 = sum(dp[:, 2 - tap:2 - tap + T].unsqueeze(-1) * w16.double()[tap] for tap in range(3))
+    figs = {"dw": ac.rel_rmse(dwb[:3 * C].cpu().reshape(3, C), dw), "db": rel(dwb[3 * C], dout.sum())}
+    S = 2.0 ** (6 - math.frexp(abs(float(gin)) * 1.0)[1])                                  # the pass's scale: |g cnorm| S in [32, 64)
+    figs["da"] = ac.rel_rmse(da.cpu() / S, da64)
+    print("ROW | adv_head_bwd B T 65 %s | %s (bound %.1e)" % (fmt, {k: "%.2e" % v for k, v in figs.items()}, GRAD_BOUND[fmt]))
+    assert max(figs.values()) <= GRAD_BOUND[fmt], figs
+
+
 def test_no_poison_reaches_the_gradients(mods):
     """the allocator's free blocks are filled with NaN before the step: whatever the step leaves unwritten would show"""
     name = "a1_odd_f9_t37"

@@ -207,9 +207,10 @@ def test_clean_side_gets_no_gradient(mods):
         assert not m(e, cl).requires_grad
 
 
-@pytest.mark.parametrize("shape", [(2, 61, 129), (70001,)], ids=str)
+@pytest.mark.parametrize("shape", [(2, 61, 129), (70001,), (1025,), (1024 * 1024 + 1,)], ids=str)
 def test_mse_mask_loss(mods, shape):
-    """value and gradient against float64; n = 70001 walks the grid-stride loop (69 workgroups of 256 threads)"""
+    """value and gradient against float64; n = 70001 walks the grid-stride loop (69 workgroups of 256 threads); n = 1025 is two
+    workgroups, the second with one element; n = 1024 x 1024 + 1 is one element past the cap of 1024 workgroups"""
     p, t = lc.mse_case(shape, 161)
     p64 = p.double().requires_grad_(True)
     l64 = lc.mse(p64, t.double())

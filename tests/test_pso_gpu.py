@@ -74,7 +74,7 @@ def padded(names):
 
 
 # ---- 1. fitness --------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", ["a", "b", "d", "e", "f"])
+@pytest.mark.parametrize("name", ["a", "b", "d", "e", "f", "g"])
 def test_fitness_against_the_restatement(masks, name):
     xs = pc.probe_positions(pc.INPUTS[name][0])
     cfg = {"num_particles": xs.size, "max_iter": 1, "draws": still_draws(xs)}

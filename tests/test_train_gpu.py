@@ -292,6 +292,22 @@ def test_speech_enhancer_train_step_matches_autograd():
 # ---------------------------------------------------------------------------
 # optimiser step (training/conformer_pipeline.py:424-429, 509, 514)
 # ---------------------------------------------------------------------------
+@pytest.mark.parametrize("n", [257, 2048 * 256 + 1])
+def test_sumsq_partials(n):
+    """sfm_sumsq through its ordered fold: n 257 = two workgroups, the second with one element; n 2048 x 256 + 1 = one element
+    past the cap of 2048 workgroups.  Against float64, within the 1e-4 the optimiser tests below hold the gradient norm to."""
+    from sincformer_metacog_speech_enhancement_amd import ops
+    L = ops._lib.load()
+    g = arr("ssq", (n,), 840 + n)
+    out = torch.zeros(1, device="cuda", dtype=torch.float64)
+    ws = ops._ws(L.sfm_sumsq_ws_doubles(n), out.device, torch.float64)
+    assert ws is not None and ws.numel() >= 2048
+    gd = g.cuda()
+    ops._call("optim", L.sfm_sumsq, (ops._p(gd), n, ops._p(out), ops._p(ws), ops._stream()))
+    want = float(g.double().pow(2).sum())
+    assert abs(float(out) - want) < 1e-4 * want
+
+
 def test_flat_adamw_matches_torch_adamw_with_clip_and_skip():
     from sincformer_metacog_speech_enhancement_amd.optim import FlatAdamW
     torch.manual_seed(3)

@@ -76,6 +76,38 @@ def test_sisnr_bwd(ops, row):
     hp.check_row("sisnr_bwd %s" % _id(row), dwave.cpu(), c["ref64"], c["ref32"], hp.K_TRANS)
 
 
+@pytest.mark.parametrize("L", [257, 16385])
+def test_wave_moments_partials(ops, L):
+    """the ordered fold's partials: L 257 = two workgroups per signal, the second with one sample; L 16385 = one sample past
+    64 x 256, where the cap of 64 workgroups begins and each strides on.  The bound of test_sisnr_bwd."""
+    c = hp.sisnr_case((3, L, 1.0))
+    Sw = ops.wave_moments(dev(c["est"]), dev(c["tgt"]))
+    e, t = c["est"].double(), c["tgt"].double()
+    ref = torch.stack([e.sum(1), t.sum(1), (e * e).sum(1), (t * t).sum(1), (e * t).sum(1)], dim=1)
+    mag = torch.stack([e.abs().sum(1), t.abs().sum(1), (e * e).sum(1), (t * t).sum(1), (e * t).abs().sum(1)], dim=1)
+    assert bool(((Sw.cpu() - ref).abs() <= 2 * L * 2.0 ** -53 * mag).all()), (Sw.cpu() - ref).abs().max()
+
+
+@pytest.mark.parametrize("n", [257, 2048 * 256 + 1])
+def test_spec_sums_partials(ops, n):
+    """the four sums themselves against float64: n 257 = two workgroups, the second with one bin; n 2048 x 256 + 1 = one bin
+    past the cap of 2048 workgroups.  Every term is an fp32 expression behind sqrt / log, summed in float64: the error is within
+    K_TRANS x 2^-24 x the sum of the magnitudes the term is formed from (the rule of this file: 16 x the fp32 unit behind the
+    hardware's transcendentals), the float64 accumulation adds 2 n 2^-53 of it."""
+    pr, pi, tr, ti = (arr("ss%d" % i, (n,), 40 + i + n) for i in range(4))
+    S = ops.spec_sums(dev(pr), dev(pi), dev(tr), dev(ti)).cpu()
+    p2, t2 = pr.double() ** 2 + pi.double() ** 2, tr.double() ** 2 + ti.double() ** 2
+    pm, tm = p2.sqrt(), t2.sqrt()
+    ref = torch.stack([((tm - pm) ** 2).sum(), t2.sum(), ((pm + 1e-8).log() - (tm + 1e-8).log()).abs().sum(),
+                       ((p2 + 1e-8).sqrt() - (t2 + 1e-8).sqrt()).abs().sum()])
+    mag = torch.stack([((tm + pm) ** 2).sum(), t2.sum(), ((pm + 1e-8).log().abs() + (tm + 1e-8).log().abs()).sum(),
+                       ((p2 + 1e-8).sqrt() + (t2 + 1e-8).sqrt()).sum()])
+    bound = (hp.K_TRANS * hp.U32 + 2 * n * 2.0 ** -53) * mag
+    err = (S - ref).abs()
+    print("ROW | spec_sums n %d | bound %s | observed %s" % (n, ["%.2e" % float(v) for v in bound / ref], ["%.2e" % float(v) for v in err / ref]))
+    assert bool((err <= bound).all()), (err, bound)
+
+
 def _spec_run(ops, row, c):
     M, F, mode, padded, acc, scale = row
     pr, pi, tr, ti = (dev(c[k]) for k in ("pr", "pi", "tr", "ti"))
