@@ -546,9 +546,15 @@ int sfm_headpool(const void* xd, const void* W, const float* bias, void* pooled,
 /* one direction-pair of an nn.LSTM layer (agents/cpea.py:43-50,99), see lstm.hip */
 int sfm_bilstm_layer(const float* xg, const float* whh, float* out, int B, int T, int H, int dtype, void* stream);
 /* inference only: w16 != 0 runs the recurrent product W_hh h on fp16 operands (weights and h rounded once, fp32 accumulation, gates /
-   cell state / output fp32): half the registers, so two chains share a CU - 1.6 x at batch 256; H 32 keeps the fp32 kernel.
-   (agents/cpea.py:43-50,99: the same nn.LSTM recurrence) */
+   cell state / output fp32).  H 128: four chains of one direction per workgroup, the product on v_mfma_f32_4x4x4_16b_f16
+   (2.3 x the fp32 kernel at batch 256, 1.2 x at batch 64); a chain's result does not depend on B or on the other chains.  H 64:
+   v_dot2_f32_f16, one chain per workgroup; H 32 keeps the fp32 kernel.  (agents/cpea.py:43-50,99: the same nn.LSTM recurrence) */
 int sfm_bilstm_layer_ex(const float* xg, const float* whh, float* out, int B, int T, int H, int w16, void* stream);
+/* the same recurrence with the result written as 16-bit rows out16 [B * T, ld16] (ld16 >= 2H elements) in `dtype` (SFM_DT_F16 /
+   SFM_DT_BF16): bit for bit sfm_convert_rows of sfm_bilstm_layer_ex's fp32 result, which is then never written.  H 128 with
+   w16 != 0 only (else SFM_ERR_SHAPE): the fused forward, whose next GEMM reads these rows. */
+int sfm_bilstm_layer_rows16(const float* xg, const float* whh, void* out16, long long ld16, int B, int T, int H, int w16,
+                            int dtype, void* stream);
 /* sfm_bilstm_layer_train with the same fp16-operand recurrent product (the reference's LSTM runs under fp16 autocast in training:
    training/conformer_pipeline.py:504); `save` and the BPTT (sfm_bilstm_layer_bwd) stay fp32 */
 int sfm_bilstm_layer_train_ex(const float* xg, const float* whh, float* out, float* save, int B, int T, int H, int w16, void* stream);

@@ -720,6 +720,9 @@ def _cpea_forward(z16, pk, B, T, out):
     x16 = z16
     for lp in pk["layers"]:
         xg = ops.linear16(x16, lp["wih"], out_dtype=torch.float32)                  # [M, 8H] = [B,T,2,4H]
+        if H == 128 and ops.lstm_w16():                                            # the kernel writes the next GEMM's rows itself
+            x16 = ops.bilstm_layer_rows16(xg, lp["whh"], B, T, H)                   # [M, 2H] 16-bit
+            continue
         h = ops.bilstm_layer(xg, lp["whh"], B, T, H, w16=ops.lstm_w16())            # [B, T, 2H] fp32
         x16 = torch.empty(M, 2 * H, device=h.device, dtype=dt)
         ops.convert_rows(h, x16, M, 2 * H, 2 * H, 2 * H, 2 * H)

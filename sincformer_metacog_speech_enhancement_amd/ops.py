@@ -2037,6 +2037,18 @@ def bilstm_layer(xg, whh, B, T, H, w16=False):
     return out
 
 
+def bilstm_layer_rows16(xg, whh, B, T, H, out16=None):
+    """bilstm_layer(..., w16=True) at H 128 with the result as 16-bit rows [B * T, 2H] in the stage's format (`out16` may be a view
+    with a wider row stride): bit for bit convert_rows of the fp32 result, which is never written"""
+    L = _lib.load()
+    if out16 is None:
+        out16 = torch.empty(B * T, 2 * H, device=xg.device, dtype=compute_dtype())
+    flops, nbytes = 2.0 * B * T * 2 * 4 * H * H, B * T * (8 * H * 4 + 2 * H * 2)
+    _call("bilstm_layer", L.sfm_bilstm_layer_rows16, (_p(xg), _p(whh), _p(out16), out16.stride(0), B, T, H, 1, _dt(), _stream()),
+          flops, nbytes)
+    return out16
+
+
 def bilstm_layer_train(xg, whh, B, T, H, w16=None):
     """forward of one BiLSTM layer that also saves the activated gates / cell states [B, T, 2, 5, H] for the BPTT.
     w16 (default: lstm_w16() when the training format is fp16): the recurrent product on fp16 operands, as under the reference's
