@@ -85,6 +85,11 @@ extern "C" {
 #define SFM_DNN_ACT_RELU 1
 #define SFM_DNN_ACT_SIGMOID 2
 #define SFM_DNN_CONTEXT_MAX_K 4096     /* context rows with statistics: mean and std sit in LDS beside the tiles */
+#define SFM_RESYNTH_TILE_FRAMES 64     /* frames a workgroup of sfm_mask_resynth computes; it owns one output hop fewer */
+#define SFM_RESYNTH_MAX_NFFT 256       /* the largest n_fft and frame its LDS layout holds */
+#define SFM_RESYNTH_MAX_FRAME 256
+#define SFM_RESYNTH_MAX_CHANNELS 64
+#define SFM_RESYNTH_COL_ALIGN 32       /* operand columns (n_fft of Wf, frame of Wi) are zero padded to a multiple of this */
 
 int sfm_abi_version(void);
 
@@ -840,6 +845,26 @@ int sfm_dnn_layer(const void* A, const int* frames, const float* mean, const flo
                   int act, float p_drop, unsigned int seed, int dtype, void* stream);
 int sfm_dnn_act_bwd(const void* dy, int dy_f32, long long ldy, const void* saved, long long ld_saved, void* dz, long long ldz, int M,
                     int N, int act, float p_drop, int dtype, void* stream);
+
+/* Mask to waveform (resynth.hip; steps 2-4 of TrainingPipeline.enhance_signal, training/pipeline.py:877-934 of the reference) in one
+ * launch, exact fp32 on v_mfma_f32_32x32x2_f32, no atomics.  noisy, out [B, L] fp32; mask [B, T_mask, C] fp32; lengths int32 [B] = the
+ * sample counts L_b of the zero-padded batch, or NULL (= L).  Per utterance: T_b = (L_b - frame) / hop + 1 (0 below one frame), the
+ * frames n < N_b = min(T_b, T_mask) are windowed, transformed (rfft(., n_fft)), multiplied per bin by the mask row interpolated onto
+ * the bins, transformed back, cropped to `frame`, windowed and overlap-added; every sample is divided by the sum of the squared
+ * window over the frames that cover it.  Every element of out is written: 0 where no frame n < N_b covers it.  Mask rows from N_b on
+ * and samples from L_b on are not read.  The same bits from run to run and for an utterance alone or anywhere in a batch.
+ * Host-built operands, NC = n_fft and FR = frame rounded up to SFM_RESYNTH_COL_ALIGN, F = n_fft / 2 + 1:
+ *   Wf [FR, NC]: column j < F = w[n] cos(2 pi (n j mod n_fft) / n_fft), column F + k - 1 = -w[n] sin(..k..), 1 <= k <= F - 2 (the
+ *     imaginary parts of DC and Nyquist are identically zero and have no column); zero beyond row `frame` and column n_fft.
+ *   Wi [NC, FR]: the matching rows of irfft (coefficients 1, 2, .., 2, 1 over n_fft), columns n < frame, times w[n]; zero beyond.
+ *   tab_idx int32 [NC], tab_wt [NC]: gain of column c = (1 - wt) mask[.., idx] + wt mask[.., idx + 1], 0 <= idx <= C - 2.
+ *   inv_wsum [3, hop]: 1 / window sum of the utterance's first hop, of an interior hop, of its last covered hop (a sum below 1e-8
+ *     counts as 1).
+ * hop * 2 == frame, frame <= n_fft <= SFM_RESYNTH_MAX_NFFT, n_fft even, 2 <= C <= SFM_RESYNTH_MAX_CHANNELS, T_mask >= 1
+ * (SFM_ERR_SHAPE otherwise). */
+int sfm_mask_resynth(const float* noisy, const float* mask, const int* lengths, const float* Wf, const float* Wi, const int* tab_idx,
+                     const float* tab_wt, const float* inv_wsum, float* out, int B, int L, int T_mask, int frame, int hop, int n_fft,
+                     int C, void* stream);
 
 #ifdef __cplusplus
 }

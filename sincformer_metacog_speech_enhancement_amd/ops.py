@@ -2647,3 +2647,118 @@ def dnn_act_bwd(dy, saved, act, N, p_drop=0.0, out=None):
                                              float(p_drop), _dt(), _stream()),
           2.0 * M * N, float(M) * N * (dy.element_size() + ssz) + 2.0 * M * out.shape[1], "M%d N%d act%d" % (M, N, DNN_ACT[act]))
     return out
+
+
+# ---------------------------------------------------------------------------
+# Mask to waveform (csrc/resynth.hip; steps 2-4 of enhance_signal, training/pipeline.py:877-934)
+# ---------------------------------------------------------------------------
+RESYNTH_TILE_FRAMES = _K["RESYNTH_TILE_FRAMES"]    # frames a workgroup computes; it owns one output hop fewer
+RESYNTH_MAX_NFFT = _K["RESYNTH_MAX_NFFT"]          # the largest n_fft / frame the kernel's LDS layout holds
+RESYNTH_MAX_FRAME = _K["RESYNTH_MAX_FRAME"]
+RESYNTH_MAX_CHANNELS = _K["RESYNTH_MAX_CHANNELS"]
+RESYNTH_COL_ALIGN = _K["RESYNTH_COL_ALIGN"]
+_RESYNTH_OPS = {}                                  # (frame, hop, n_fft, fs, cf, device) -> device operands
+RESYNTH_OPS_CACHE = 16
+
+
+def resynth_supported(frame, hop, n_fft, C):
+    """the shapes sfm_mask_resynth takes (everything else is SFM_ERR_SHAPE there)"""
+    return hop > 0 and hop * 2 == frame and frame <= n_fft and n_fft % 2 == 0 and n_fft <= RESYNTH_MAX_NFFT and \
+        frame <= RESYNTH_MAX_FRAME and 2 <= C <= RESYNTH_MAX_CHANNELS
+
+
+def resynth_matrices_host(frame, n_fft):
+    """float64 (Wf [frame, n_fft], Wi [n_fft, frame]) with w = np.hanning(frame), phases (n k) mod n_fft as in stft_matrix:
+    x[frame] @ Wf = the n_fft real numbers of rfft(x w, n_fft) - Re X[0 .. F - 1], then Im X[1 .. F - 2] (the imaginary parts of
+    DC and Nyquist are identically zero and have no column); that row @ Wi = irfft(X, n_fft)[:frame] w."""
+    F = n_fft // 2 + 1
+    w = np.hanning(frame)
+    n = np.arange(frame, dtype=np.int64)
+    k = np.arange(F, dtype=np.int64)
+    ang = 2.0 * np.pi * ((n[:, None] * k[None, :]) % n_fft) / n_fft
+    Wf = np.concatenate([w[:, None] * np.cos(ang), -w[:, None] * np.sin(ang[:, 1:F - 1])], axis=1)
+    coef = np.full(F, 2.0)
+    coef[0] = coef[F - 1] = 1.0
+    Wi = np.concatenate([(coef[:, None] * np.cos(ang.T)) / n_fft * w[None, :],
+                         (-coef[1:F - 1, None] * np.sin(ang.T[1:F - 1])) / n_fft * w[None, :]], axis=0)
+    return Wf, Wi
+
+
+def resynth_interp_table(fs, n_fft, cf):
+    """np.interp(k (fs / 2) / (F - 1), cf, m, left=m[0], right=m[-1]) as a table per bin k: (idx int64 [F], wt float64 [F]) with the
+    value (1 - wt) m[idx] + wt m[idx + 1], 0 <= idx <= len(cf) - 2: idx = the interval of cf the bin frequency falls into, wt its
+    position in it, clipped to [0, 1] (so a bin below cf[0] takes m[0] and one above cf[-1] takes m[-1]).  cf ascending, float64."""
+    cf = np.asarray(cf, dtype=np.float64).reshape(-1)
+    if cf.size < 2 or not np.all(np.diff(cf) > 0):
+        raise ValueError("resynth_interp_table: the centre frequencies must be at least 2 and strictly ascending")
+    F = n_fft // 2 + 1
+    x = np.arange(F, dtype=np.float64) * (float(fs) / 2.0) / (F - 1)
+    idx = np.clip(np.searchsorted(cf, x, side="right") - 1, 0, cf.size - 2)
+    wt = np.clip((x - cf[idx]) / (cf[idx + 1] - cf[idx]), 0.0, 1.0)
+    return idx.astype(np.int64), wt
+
+
+def resynth_inv_wsum_host(frame, hop):
+    """float64 [3, hop]: 1 / (sum of np.hanning(frame) ** 2 over the frames that cover a sample) for the utterance's first hop (frame
+    0 alone), an interior hop (two frames) and the last covered hop (the last frame alone); a sum below 1e-8 counts as 1"""
+    w2 = np.hanning(frame) ** 2
+    ws = np.stack([w2[:hop], w2[:hop] + w2[hop:], w2[hop:]])
+    ws[ws < 1e-8] = 1.0
+    return 1.0 / ws
+
+
+def resynth_operands(frame, hop, n_fft, fs, cf, device):
+    """the device operands of sfm_mask_resynth (Wf, Wi, tab_idx, tab_wt, inv_wsum), built in float64 and cast to fp32, cached by
+    (frame, hop, n_fft, fs, cf) per device (shared: do not modify)"""
+    cf = np.ascontiguousarray(cf, dtype=np.float64).reshape(-1)
+    key = (int(frame), int(hop), int(n_fft), float(fs), cf.tobytes(), str(device))
+    ops_ = _RESYNTH_OPS.get(key)
+    if ops_ is None:
+        F = n_fft // 2 + 1
+        NC, FR = round_up(n_fft, RESYNTH_COL_ALIGN), round_up(frame, RESYNTH_COL_ALIGN)
+        Wf64, Wi64 = resynth_matrices_host(frame, n_fft)
+        Wf = np.zeros((FR, NC), dtype=np.float32)
+        Wf[:frame, :n_fft] = Wf64
+        Wi = np.zeros((NC, FR), dtype=np.float32)
+        Wi[:n_fft, :frame] = Wi64
+        idx, wt = resynth_interp_table(fs, n_fft, cf)
+        col_bin = np.concatenate([np.arange(F), np.arange(1, F - 1)])           # the bin of every operand column
+        tab_idx = np.zeros(NC, dtype=np.int32)
+        tab_wt = np.zeros(NC, dtype=np.float32)
+        tab_idx[:n_fft], tab_wt[:n_fft] = idx[col_bin], wt[col_bin]
+        host = (Wf, Wi, tab_idx, tab_wt, resynth_inv_wsum_host(frame, hop).astype(np.float32))
+        ops_ = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(device) for a in host)
+        if len(_RESYNTH_OPS) >= RESYNTH_OPS_CACHE:
+            _RESYNTH_OPS.clear()
+        _RESYNTH_OPS[key] = ops_
+    return ops_
+
+
+def mask_resynth(noisy, mask, lengths=None, *, frame, hop, n_fft, fs, cf, out=None, frames=None):
+    """noisy [B, L] fp32, mask [B, T_mask, C] fp32, lengths int32 [B] on the device or None (= L) -> out [B, L] fp32: one
+    sfm_mask_resynth launch.  cf: the C ascending centre frequencies of the mask's channels (host).  frames: the number of frames
+    the launch computes, sum_b min(T_b, T_mask), for its stated cost (None: every utterance is L samples long)."""
+    _need_dev(noisy, mask, lengths, out)
+    L_ = _lib.load()
+    ok = noisy.dim() == 2 and mask.dim() == 3 and noisy.dtype == torch.float32 and mask.dtype == torch.float32
+    ok = ok and noisy.is_contiguous() and mask.is_contiguous() and noisy.numel() > 0 and mask.numel() > 0
+    ok = ok and mask.shape[0] == noisy.shape[0] and mask.shape[2] == len(cf) and resynth_supported(frame, hop, n_fft, mask.shape[2])
+    ok = ok and (lengths is None or (lengths.dtype == torch.int32 and lengths.is_contiguous() and lengths.numel() == noisy.shape[0]))
+    if not ok:
+        _lib.check(_K["ERR_SHAPE"], "mask_resynth")
+    B, L = noisy.shape
+    T_mask, C = mask.shape[1], mask.shape[2]
+    if out is None:
+        out = torch.empty(B, L, device=noisy.device, dtype=torch.float32)
+    if out.shape != noisy.shape or out.dtype != torch.float32 or not out.is_contiguous():
+        _lib.check(_K["ERR_SHAPE"], "mask_resynth")
+    Wf, Wi, tab_idx, tab_wt, inv_wsum = resynth_operands(frame, hop, n_fft, fs, cf, noisy.device)
+    if frames is None:
+        frames = B * min((L - frame) // hop + 1 if L >= frame else 0, T_mask)
+    two_f = n_fft + 2
+    nbytes = 4.0 * (noisy.numel() + mask.numel() + Wf.numel() + Wi.numel() + tab_idx.numel() + tab_wt.numel() + inv_wsum.numel() +
+                    (0 if lengths is None else B) + out.numel())
+    _call("resynth", L_.sfm_mask_resynth, (_p(noisy), _p(mask), _p(lengths), _p(Wf), _p(Wi), _p(tab_idx), _p(tab_wt), _p(inv_wsum),
+                                           _p(out), B, L, T_mask, frame, hop, n_fft, C, _stream()),
+          (2.0 * frame * two_f + 2.0 * two_f * frame) * frames, nbytes, "B%d L%d T%d f%d n%d C%d" % (B, L, T_mask, frame, n_fft, C))
+    return out

@@ -2,7 +2,9 @@
 waveforms (signal_processing/gammatone.py) into masks/ on the device, and of _process_single_utterance (:147-197) as a whole:
 dnn_frame_pairs gives the (features, mask) pair of a batch of utterances without file I/O, cache or a host round trip, and
 dnn_estimate_mask the estimator's side of enhance_signal (:846-875, its step 1): features, context and models.SpeechEnhancementDNN in
-one pass.  The Dataset and the RBM are not mirrored; the Dataset's feature normalisation is an option of add_context."""
+one pass; resynthesize its steps 2-4 (:877-934): the STFT of the noisy signal, the mask interpolated onto the STFT bins, the masked
+irfft and the overlap-add in one launch; dnn_enhance_signal the two together.  The Dataset and the RBM are not mirrored; the
+Dataset's feature normalisation is an option of add_context."""
 import numpy as np
 import torch
 
@@ -88,3 +90,68 @@ def dnn_estimate_mask(dnn, noisy, fe=None, lengths=None, feat_mean=None, feat_st
     of a zero-padded batch; rows from an utterance's T_b on are those of zero input rows."""
     raw = _fe_for(fe).extract_frame_features(noisy, lengths=lengths)
     return dnn.forward_frames(raw, feat_mean, feat_std, lengths=_frame_counts(lengths)).clamp_(0.0, 1.0)
+
+
+_default_cf = []
+
+
+def resynthesize(noisy, mask, lengths=None, fs=None, center_freqs=None, *, frame=None, hop=None, n_fft=None):
+    """-> the enhanced waveforms [B, L] (1-D signal: [L]) fp32, steps 2-4 of enhance_signal (:877-934) in one launch
+    (ops.mask_resynth): the Hann STFT of fp32 device waveforms noisy [B, L], the mask [B, T_mask, C] ([T_mask, C]) interpolated from
+    its channels' centre frequencies onto the STFT bins as np.interp does (a bin below the first channel takes the first, one above
+    the last takes the last), the masked irfft, the overlap-add and the division by the window sum.  Frames from min(T_b, T_mask)
+    on contribute nothing; samples no such frame covers are 0, so an utterance shorter than one frame gives zeros (the reference
+    raises below one hop).  The mask is used as given: the clip to [0, 1] is dnn_estimate_mask's.  lengths: the sample counts of a
+    zero-padded batch.  fs: config.SAMPLE_RATE; center_freqs: erb_space(FREQ_LOW, FREQ_HIGH, NUM_CHANNELS), any ascending
+    frequencies, one per mask channel; frame, hop, n_fft: config's framing.  No autograd history."""
+    fs = config.SAMPLE_RATE if fs is None else fs
+    frame = config.FRAME_SIZE if frame is None else int(frame)
+    hop = config.HOP_SIZE if hop is None else int(hop)
+    n_fft = config.FFT_SIZE if n_fft is None else int(n_fft)
+    if center_freqs is None:
+        if not _default_cf:
+            from ..signal_processing.gammatone import erb_space
+            _default_cf.append(np.asarray(erb_space(config.FREQ_LOW, config.FREQ_HIGH, config.NUM_CHANNELS), dtype=np.float64))
+        center_freqs = _default_cf[0]
+    cf = np.asarray(center_freqs, dtype=np.float64).reshape(-1)
+    for name, t, dims in (("noisy", noisy, (1, 2)), ("mask", mask, (2, 3))):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() not in dims:
+            raise ValueError("resynthesize: %s must be an fp32 tensor of %d or %d dimensions" % ((name,) + dims))
+    if (noisy.dim() == 1) != (mask.dim() == 2):
+        raise ValueError("resynthesize: noisy %s and mask %s: both batched or both single" % (tuple(noisy.shape), tuple(mask.shape)))
+    one_d = noisy.dim() == 1
+    y, m = (noisy.reshape(1, -1), mask.unsqueeze(0)) if one_d else (noisy, mask)
+    B, L = y.shape
+    if m.shape[0] != B:
+        raise ValueError("resynthesize: %d waveforms, %d masks" % (B, m.shape[0]))
+    if m.shape[2] != cf.size:
+        raise ValueError("resynthesize: the mask has %d channels, there are %d centre frequencies" % (m.shape[2], cf.size))
+    if cf.size < 2 or not np.all(np.diff(cf) > 0):
+        raise ValueError("resynthesize: the centre frequencies must be strictly ascending")
+    from .. import ops
+    if not ops.resynth_supported(frame, hop, n_fft, cf.size):
+        raise ValueError("resynthesize: frame %d, hop %d, n_fft %d, %d channels: hop * 2 == frame <= n_fft <= %d, n_fft even and 2 .. %d "
+                         "channels are supported" % (frame, hop, n_fft, cf.size, ops.RESYNTH_MAX_NFFT, ops.RESYNTH_MAX_CHANNELS))
+    if B == 0 or L == 0 or m.shape[1] == 0:
+        raise ValueError("resynthesize: empty noisy %s or mask %s" % (tuple(noisy.shape), tuple(mask.shape)))
+    if not y.is_cuda or m.device != y.device:
+        raise ValueError("resynthesize: noisy (%s) and mask (%s) must be on one device; there is no host path" % (y.device, m.device))
+    T_mask = m.shape[1]
+    dev_lengths = None
+    host = np.full(B, L, dtype=np.int64)
+    if lengths is not None:
+        host = np.asarray(lengths.cpu() if torch.is_tensor(lengths) else lengths, dtype=np.int64).reshape(-1)
+        if host.size != B:
+            raise ValueError("resynthesize: %d lengths for %d waveforms" % (host.size, B))
+        host = np.clip(host, 0, L)
+        dev_lengths = torch.from_numpy(host.astype(np.int32)).to(y.device)
+    frames = int(np.minimum(np.where(host >= frame, (host - frame) // hop + 1, 0), T_mask).sum())
+    out = ops.mask_resynth(y.detach().contiguous(), m.detach().contiguous(), dev_lengths, frame=frame, hop=hop, n_fft=n_fft, fs=fs,
+                           cf=cf, frames=frames)
+    return out[0] if one_d else out
+
+
+def dnn_enhance_signal(dnn, noisy, fe=None, lengths=None, feat_mean=None, feat_std=None):
+    """-> the enhanced waveforms [B, L] (1-D signal: [L]): the whole of enhance_signal (:819-934) for a batch,
+    resynthesize(noisy, dnn_estimate_mask(dnn, noisy, ...), lengths) with config's framing and centre frequencies."""
+    return resynthesize(noisy, dnn_estimate_mask(dnn, noisy, fe=fe, lengths=lengths, feat_mean=feat_mean, feat_std=feat_std), lengths)
