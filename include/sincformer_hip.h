@@ -90,6 +90,13 @@ extern "C" {
 #define SFM_RESYNTH_MAX_FRAME 256
 #define SFM_RESYNTH_MAX_CHANNELS 64
 #define SFM_RESYNTH_COL_ALIGN 32       /* operand columns (n_fft of Wf, frame of Wi) are zero padded to a multiple of this */
+#define SFM_RBM_TILE 32                /* sfm_rbm_*: a workgroup's output tile is 32 x 32; ceil(n_visible / 32) fp64 error partials per step */
+#define SFM_RBM_KCHUNK 256             /* k staged per pass of sfm_rbm_prob (sfm_rbm_update: half of it) */
+#define SFM_RBM_MAX_UNITS 16384        /* n_visible, n_hidden in 1 .. this */
+#define SFM_RBM_MAX_BATCH 65536        /* rows of one update */
+#define SFM_RBM_SAMPLE_NONE 0          /* sfm_rbm_prob's sample_mode */
+#define SFM_RBM_SAMPLE_REPLAY 1
+#define SFM_RBM_SAMPLE_COUNTER 2
 
 int sfm_abi_version(void);
 
@@ -865,6 +872,36 @@ int sfm_dnn_act_bwd(const void* dy, int dy_f32, long long ldy, const void* saved
 int sfm_mask_resynth(const float* noisy, const float* mask, const int* lengths, const float* Wf, const float* Wi, const int* tab_idx,
                      const float* tab_wt, const float* inv_wsum, float* out, int B, int L, int T_mask, int frame, int hop, int n_fft,
                      int C, void* stream);
+
+/* RBM pre-training (rbm.hip; models/rbm.py of the reference: CD-k).  Everything fp32 on the device, every product exact fp32 on
+ * v_mfma_f32_32x32x2_f32; W [n_visible, n_hidden] row-major as there.  No atomics: the same bits from run to run.
+ * sfm_rbm_prob: prob[M, N] = sigmoid(A[M, K] op(W) + bias[N]), sigmoid(x) = 1 / (1 + exp(-x)) (0 and 1 at the extremes, never NaN).
+ *   down 0: K = n_visible, N = n_hidden, op(W) = W, bias = h_bias;  down 1: K = n_hidden, N = n_visible, op(W) = W^T, bias = v_bias.
+ *   Row m of A = data[rows[m]] (rows int32 [M]; NULL: row m itself), data [n_rows, lda] fp32 with lda >= K and 4-byte aligned rows;
+ *   an index outside 0 .. n_rows - 1 reads as a row of zeros.  prob [M, N] compact.  A row's result has the same bits alone or
+ *   inside any M, and through `rows` or from a gathered copy.
+ *   sample_mode SFM_RBM_SAMPLE_NONE: sample and u NULL.
+ *   SFM_RBM_SAMPLE_REPLAY: sample[M, N] fp32 = ((double)prob > u[m N + n]) ? 1 : 0, u fp64 [M, N] (np.random.random of the reference).
+ *   SFM_RBM_SAMPLE_COUNTER: u NULL; sample[m, n] = 1 iff word(seed, m N + n) < ceil(prob * 2^24), else 0, where for the element
+ *     index e (64-bit) word is the 24-bit number that the dropout keep function sfm_keep_scale(seed, e, .) compares with its
+ *     threshold: g = hash(seed, e >> 3) (the full counter hash of the 8-element group), x = g + (e & 7) * 0x9E3779B1,
+ *     x ^= x >> 15, x *= 0x846CA68B, x ^= x >> 16, word = x >> 8 (32-bit arithmetic); ceil(prob * 2^24) is formed in fp32 (exact).
+ * sfm_rbm_update: W[i, j] += (lr / B) sum_b (v[b, i] ph[b, j] - nv[b, i] nh[b, j]) as one accumulation over 2 B terms (term 2 b
+ *   positive, 2 b + 1 negative), in place, every element read and written once; v_bias[i] += lr mean_b(v - nv), h_bias[j] += lr
+ *   mean_b(ph - nh) (column sums in fp64); err_partial[t], t < ceil(n_visible / SFM_RBM_TILE), = sum over b and the tile's 32
+ *   visible units of (v - nv)^2 in fp64.  v[b] = data[rows[b]] as above; ph, nh [B, n_hidden], nv [B, n_visible] compact.
+ *   B = the rows of THIS batch (1 .. SFM_RBM_MAX_BATCH): the last batch of an epoch is shorter.
+ * sfm_rbm_fold_error: partial [n_steps, n_tiles] of the batches of one epoch over num_samples rows (batch s has
+ *   min(batch_size, num_samples - s batch_size) rows; n_steps = ceil(num_samples / batch_size), n_tiles = ceil(n_visible / SFM_RBM_TILE),
+ *   SFM_ERR_SHAPE otherwise) -> out[0] = mean over s of (sum_t partial[s, t]) / (rows_s n_visible), summed in a fixed order. */
+int sfm_rbm_prob(const float* data, const int* rows, const float* W, const float* bias, float* prob, float* sample, const double* u,
+                 int M, int n_visible, int n_hidden, int n_rows, long long lda, int down, int sample_mode, unsigned int seed,
+                 void* stream);
+int sfm_rbm_update(const float* data, const int* rows, const float* ph, const float* nv, const float* nh, float* W, float* v_bias,
+                   float* h_bias, double* err_partial, int B, int n_visible, int n_hidden, int n_rows, long long ldv, float lr,
+                   void* stream);
+int sfm_rbm_fold_error(const double* partial, double* out, int n_steps, int n_tiles, int num_samples, int batch_size, int n_visible,
+                       void* stream);
 
 #ifdef __cplusplus
 }

@@ -35,6 +35,11 @@ DNN_DROPOUT = 0.2
 DNN_LEARNING_RATE = 0.001
 DNN_EPOCHS = 50
 DNN_BATCH_SIZE = 256
+# the RBM pre-training of the DNN (config.py:75-78 of the reference)
+RBM_LEARNING_RATE = 0.01
+RBM_EPOCHS = 10
+RBM_BATCH_SIZE = 256
+RBM_K_STEPS = 1
 CONFORMER_NUM_BLOCKS = 6
 CONFORMER_D_MODEL = 256
 CONFORMER_NUM_HEADS = 4

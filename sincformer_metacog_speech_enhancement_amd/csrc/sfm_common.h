@@ -97,6 +97,12 @@ __device__ __forceinline__ float sfm_keep_from_group(uint32_t gh, uint32_t j, ui
   x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
   return ((x >> 8) >= thr24) ? inv_keep : 0.f;
 }
+// the 24-bit word sfm_keep_from_group compares with its threshold (rbm.hip samples with it: 1 iff the word is BELOW the threshold)
+__device__ __forceinline__ uint32_t sfm_keep_word24(uint32_t gh, uint32_t j) {
+  uint32_t x = gh + j * 0x9E3779B1u;
+  x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
+  return x >> 8;
+}
 __device__ __forceinline__ float sfm_keep_scale(uint32_t seed, unsigned long long idx, float p, float inv_keep) {
   // 0 if dropped, 1/(1-p) if kept
   return sfm_keep_from_group(sfm_hash(seed, idx >> 3), (uint32_t)(idx & 7ull), sfm_keep_threshold(p), inv_keep);

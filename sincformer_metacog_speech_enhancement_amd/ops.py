@@ -2762,3 +2762,105 @@ def mask_resynth(noisy, mask, lengths=None, *, frame, hop, n_fft, fs, cf, out=No
                                            _p(out), B, L, T_mask, frame, hop, n_fft, C, _stream()),
           (2.0 * frame * two_f + 2.0 * two_f * frame) * frames, nbytes, "B%d L%d T%d f%d n%d C%d" % (B, L, T_mask, frame, n_fft, C))
     return out
+
+
+# ---------------------------------------------------------------------------
+# RBM pre-training (csrc/rbm.hip; models/rbm.py of the reference)
+# ---------------------------------------------------------------------------
+RBM_TILE = _K["RBM_TILE"]                    # a workgroup's 32 x 32 output tile; ceil(n_visible / RBM_TILE) fp64 error partials per step
+RBM_MAX_UNITS = _K["RBM_MAX_UNITS"]
+RBM_MAX_BATCH = _K["RBM_MAX_BATCH"]
+RBM_SAMPLE = {None: _K["RBM_SAMPLE_NONE"], "replay": _K["RBM_SAMPLE_REPLAY"], "counter": _K["RBM_SAMPLE_COUNTER"]}
+
+
+def rbm_error_tiles(n_visible):
+    """fp64 partials sfm_rbm_update writes per step"""
+    return (int(n_visible) + RBM_TILE - 1) // RBM_TILE
+
+
+def _rbm_rows_ok(data, rows, M, K):
+    ok = data.dim() == 2 and data.dtype == torch.float32 and data.stride(1) == 1 and data.shape[1] == K and data.shape[0] >= 1 and \
+        data.stride(0) >= K
+    if rows is None:
+        return ok and M <= data.shape[0]
+    return ok and rows.dtype == torch.int32 and rows.dim() == 1 and rows.is_contiguous() and rows.numel() == M
+
+
+def rbm_prob(data, W, bias, *, down=False, rows=None, M=None, prob=None, sample=None, u=None, seed=None):
+    """prob [M, N] = sigmoid(A op(W) + bias), one sfm_rbm_prob launch.  W fp32 [n_visible, n_hidden] contiguous; down=False: A rows
+    of n_visible values, op(W) = W, bias = h_bias [n_hidden]; down=True: rows of n_hidden values, op(W) = W^T, bias = v_bias.
+    Row m of A = data[rows[m]] (rows int32 [M] on the device) or data[m] for m < M (default: every row of data).
+    u fp64 [M, N]: also the sample plane (prob > u) as fp32 0 / 1 (replay); seed: the sample plane of the counter rule of
+    include/sincformer_hip.h; neither: probabilities only.  -> prob, or (prob, sample)."""
+    _need_dev(data, W, bias, rows, prob, sample, u)
+    L = _lib.load()
+    if W.dim() != 2 or W.dtype != torch.float32 or not W.is_contiguous() or not 1 <= W.shape[0] <= RBM_MAX_UNITS or \
+            not 1 <= W.shape[1] <= RBM_MAX_UNITS:
+        _lib.check(_K["ERR_SHAPE"], "rbm_prob")
+    V, H = W.shape
+    K, N = (H, V) if down else (V, H)
+    if M is None:
+        M = rows.numel() if rows is not None else (data.shape[0] if data.dim() == 2 else 0)
+    M = int(M)
+    ok = M >= 1 and _rbm_rows_ok(data, rows, M, K) and bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == N
+    ok = ok and not (u is not None and seed is not None)
+    ok = ok and (u is None or (u.dtype == torch.float64 and u.is_contiguous() and u.numel() == M * N))
+    if not ok:
+        _lib.check(_K["ERR_SHAPE"], "rbm_prob")
+    mode = "replay" if u is not None else ("counter" if seed is not None else None)
+    if prob is None:
+        prob = torch.empty(M, N, device=data.device, dtype=torch.float32)
+    if mode is not None and sample is None:
+        sample = torch.empty(M, N, device=data.device, dtype=torch.float32)
+    for t in (prob, sample) if mode is not None else (prob,):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != M * N:
+            _lib.check(_K["ERR_SHAPE"], "rbm_prob")
+    if mode is None and sample is not None:
+        _lib.check(_K["ERR_ARG"], "rbm_prob")
+    nbytes = 4.0 * (M * K + V * H + N + M * N) + (4.0 * M if rows is not None else 0.0) + \
+        (4.0 * M * N if mode is not None else 0.0) + (8.0 * M * N if mode == "replay" else 0.0)
+    _call("rbm_prob", L.sfm_rbm_prob, (_p(data), _p(rows), _p(W), _p(bias), _p(prob), _p(sample) if mode is not None else None, _p(u),
+                                       M, V, H, data.shape[0], data.stride(0), 1 if down else 0, RBM_SAMPLE[mode],
+                                       (int(seed) & 0xffffffff) if seed is not None else 0, _stream()),
+          2.0 * M * N * K, nbytes, "M%d N%d K%d %s s%d" % (M, N, K, "down" if down else "up", RBM_SAMPLE[mode]))
+    return prob if mode is None else (prob, sample)
+
+
+def rbm_update(data, ph, nv, nh, W, v_bias, h_bias, err_partial, lr, *, rows=None, B=None):
+    """W += (lr / B) (v^T ph - nv^T nh), v_bias += lr mean(v - nv), h_bias += lr mean(ph - nh) in place, and err_partial
+    [rbm_error_tiles(n_visible)] fp64 = the partial sums of (v - nv)^2: one sfm_rbm_update launch.  v[b] = data[rows[b]] (rows int32
+    [B]) or data[b]; ph, nh [B, n_hidden], nv [B, n_visible] fp32 contiguous (their first B rows when they hold more)."""
+    _need_dev(data, ph, nv, nh, W, v_bias, h_bias, err_partial, rows)
+    L = _lib.load()
+    if W.dim() != 2 or W.dtype != torch.float32 or not W.is_contiguous() or not 1 <= W.shape[0] <= RBM_MAX_UNITS or \
+            not 1 <= W.shape[1] <= RBM_MAX_UNITS:
+        _lib.check(_K["ERR_SHAPE"], "rbm_update")
+    V, H = W.shape
+    if B is None:
+        B = rows.numel() if rows is not None else (data.shape[0] if data.dim() == 2 else 0)
+    B = int(B)
+    ok = 1 <= B <= RBM_MAX_BATCH and _rbm_rows_ok(data, rows, B, V)
+    for t, n in ((ph, H), (nv, V), (nh, H)):
+        ok = ok and t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous() and t.shape[1] == n and t.shape[0] >= B
+    for t, n in ((v_bias, V), (h_bias, H)):
+        ok = ok and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n
+    ok = ok and err_partial.dtype == torch.float64 and err_partial.is_contiguous() and err_partial.numel() >= rbm_error_tiles(V)
+    if not ok:
+        _lib.check(_K["ERR_SHAPE"], "rbm_update")
+    nbytes = 4.0 * (2 * B * V + 2 * B * H) + 8.0 * (V * H + V + H) + 8.0 * rbm_error_tiles(V) + (4.0 * B if rows is not None else 0.0)
+    _call("rbm_update", L.sfm_rbm_update, (_p(data), _p(rows), _p(ph), _p(nv), _p(nh), _p(W), _p(v_bias), _p(h_bias), _p(err_partial),
+                                           B, V, H, data.shape[0], data.stride(0), float(lr), _stream()),
+          2.0 * (2 * B) * V * H + 3.0 * B * V + 2.0 * B * H, nbytes, "B%d V%d H%d" % (B, V, H))
+
+
+def rbm_fold_error(partial, out, n_steps, num_samples, batch_size, n_visible):
+    """out[0] (fp64) = the mean over an epoch's n_steps batches of each batch's mean squared reconstruction error, from the
+    partials [n_steps, rbm_error_tiles(n_visible)] that rbm_update wrote: one small launch, fixed order"""
+    _need_dev(partial, out)
+    L = _lib.load()
+    tiles = rbm_error_tiles(n_visible)
+    if partial.dtype != torch.float64 or out.dtype != torch.float64 or not partial.is_contiguous() or out.numel() < 1 or \
+            partial.numel() < n_steps * tiles or n_steps != (num_samples + batch_size - 1) // max(batch_size, 1):
+        _lib.check(_K["ERR_SHAPE"], "rbm_fold_error")
+    _call("rbm_fold", L.sfm_rbm_fold_error, (_p(partial), _p(out), int(n_steps), tiles, int(num_samples), int(batch_size), int(n_visible),
+                                             _stream()), float(n_steps) * (tiles + 2), 8.0 * n_steps * tiles + 8.0)

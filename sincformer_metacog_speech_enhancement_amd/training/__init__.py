@@ -1,8 +1,8 @@
 from .conformer_pipeline import CurriculumBatch, NoiseBank, curriculum_batch, mix_at_snr, mix_batch
 from .curriculum import CurriculumScheduler
-from .pipeline import dnn_enhance_signal, dnn_estimate_mask, dnn_frame_pairs, gammatone_mask_target, resynthesize
+from .pipeline import dnn_enhance_signal, dnn_estimate_mask, dnn_frame_pairs, gammatone_mask_target, rbm_pretrain, resynthesize
 from .losses import AdversarialLoss, MSEMaskLoss, PerceptualSTOILoss, SubDiscriminator
 
 __all__ = ["AdversarialLoss", "CurriculumBatch", "CurriculumScheduler", "MSEMaskLoss", "NoiseBank", "PerceptualSTOILoss",
            "SubDiscriminator", "curriculum_batch", "dnn_enhance_signal", "dnn_estimate_mask", "dnn_frame_pairs", "gammatone_mask_target",
-           "mix_at_snr", "mix_batch", "resynthesize"]
+           "mix_at_snr", "mix_batch", "rbm_pretrain", "resynthesize"]

@@ -3,8 +3,8 @@ waveforms (signal_processing/gammatone.py) into masks/ on the device, and of _pr
 dnn_frame_pairs gives the (features, mask) pair of a batch of utterances without file I/O, cache or a host round trip, and
 dnn_estimate_mask the estimator's side of enhance_signal (:846-875, its step 1): features, context and models.SpeechEnhancementDNN in
 one pass; resynthesize its steps 2-4 (:877-934): the STFT of the noisy signal, the mask interpolated onto the STFT bins, the masked
-irfft and the overlap-add in one launch; dnn_enhance_signal the two together.  The Dataset and the RBM are not mirrored; the
-Dataset's feature normalisation is an option of add_context."""
+irfft and the overlap-add in one launch; dnn_enhance_signal the two together; rbm_pretrain is _rbm_pretrain (:712-759), the layer-wise
+RBM pre-training of the DNN on models.rbm.  The Dataset is not mirrored; its feature normalisation is an option of add_context."""
 import numpy as np
 import torch
 
@@ -155,3 +155,43 @@ def dnn_enhance_signal(dnn, noisy, fe=None, lengths=None, feat_mean=None, feat_s
     """-> the enhanced waveforms [B, L] (1-D signal: [L]): the whole of enhance_signal (:819-934) for a batch,
     resynthesize(noisy, dnn_estimate_mask(dnn, noisy, ...), lengths) with config's framing and centre frequencies."""
     return resynthesize(noisy, dnn_estimate_mask(dnn, noisy, fe=fe, lengths=lengths, feat_mean=feat_mean, feat_std=feat_std), lengths)
+
+
+def rbm_weights_degenerate(rbm_weights):
+    """the reference's check (:750-756): the index of the first layer whose W has np.std below 1e-6 or NaN, None when every layer is
+    fine.  Tensors (one readback for the whole stack) or numpy arrays."""
+    if all(torch.is_tensor(w) for w, _, _ in rbm_weights):
+        stds = torch.stack([w.detach().double().std(unbiased=False) for w, _, _ in rbm_weights]).cpu().numpy()
+    else:
+        stds = np.array([np.std(np.asarray(w.detach().cpu() if torch.is_tensor(w) else w, dtype=np.float64)) for w, _, _ in rbm_weights])
+    for i, w_std in enumerate(stds):
+        if w_std < 1e-6 or np.isnan(w_std):
+            return i
+    return None
+
+
+def rbm_pretrain(dnn, features, max_samples=50000, seed=None, verbose=True):
+    """_rbm_pretrain (:712-759) on the device: at most max_samples rows of the normalised features [N, dnn.input_dim] (fp32 device
+    tensor; what dnn_frame_pairs returns with statistics, flattened over utterances) are squashed with RBM.sigmoid, a stack of RBMs
+    of sizes [input_dim] + [hidden_dim] * num_hidden_layers is trained on them (models.pretrain_dnn_with_rbm, counter mode with
+    `seed`), and - unless a layer's weights are degenerate (std < 1e-6 or NaN: nothing is loaded, False) - loaded into the DNN's
+    hidden Linears (True).  The output layer is never set."""
+    from ..models.rbm import RBM, pretrain_dnn_with_rbm
+    if not torch.is_tensor(features) or features.dtype != torch.float32 or features.dim() < 2 or features.shape[-1] != dnn.input_dim:
+        raise ValueError("rbm_pretrain: fp32 features [..., %d] are needed" % dnn.input_dim)
+    if not features.is_cuda:
+        raise RuntimeError("rbm_pretrain: the RBM only runs on an MI355X device tensor; got a CPU tensor (there is no CPU fallback)")
+    rbm_data_01 = RBM.sigmoid(features.detach().reshape(-1, dnn.input_dim)[:max_samples]).contiguous()
+    layer_sizes = [dnn.input_dim] + [dnn.hidden_dim] * dnn.num_hidden_layers
+    if verbose:
+        print(f"  RBM data: {rbm_data_01.shape[0]:,} samples, dim={rbm_data_01.shape[1]}")
+    rbm_weights = pretrain_dnn_with_rbm(rbm_data_01, layer_sizes, verbose=verbose, seed=seed)
+    bad = rbm_weights_degenerate(rbm_weights)
+    if bad is not None:
+        if verbose:
+            print(f"  RBM layer {bad+1} weights degenerate. Skipping load.")
+        return False
+    dnn.load_rbm_weights(rbm_weights)
+    if verbose:
+        print("  RBM weights loaded into DNN")
+    return True
