@@ -8,7 +8,9 @@
 // (sfm_gn_finalize); the two-input form is the residual block's  GELU(GN(main) + GN(skip))  (agents/perception.py:129).
 // What changes against sfm_gemm16's implicit GEMM:
 //   * the input rows of a 128-row output tile ("patch": 127 s + k rows x 64 channels) are fetched ONCE, transformed in
-//     registers (unpack, scale / shift, exact-erf GELU by Abramowitz-Stegun 7.1.26, |err| < 1.5e-7, pack) and written to LDS;
+//     registers and written back to LDS: scale / shift, then GELU - for fp16 operands (the default policy) a logistic fit of the
+//     normal CDF on packed fp16 pairs (gelu_lg_h2p below, with its error figures), for bf16 operands the erf form by
+//     Abramowitz-Stegun 7.1.26 in fp32 (|err| < 1.5e-7);
 //     the k taps then read the same patch at shifted rows (stride 2: even / odd input rows live in two planes, so that the
 //     rows of consecutive outputs stay consecutive in LDS and the usual chunk swizzle keeps ds_read_b128 conflict-free).
 //     The implicit im2col of sfm_gemm16 re-reads every input row k / s times from L2 and cannot transform in flight
@@ -18,7 +20,8 @@
 //     second accumulator / output (N = 128 layers); N = 256 runs as two 128-column passes over the same patch (NPASS);
 //   * weights stream L2 -> LDS by LDS-DMA in 128 x 64 tiles through a 2-stage ring, one barrier per k-tile, as in gemm16w.
 // LDS: patch 16.6-33.8 KB + ring 32 KB: two workgroups per CU, so one's staging (VALU) overlaps the other's MFMA loop.
-// Epilogue = gemm16_epilogue_strips (bias, GroupNorm partials of the raw output, 16-byte row stores).
+// The accumulators start from the bias (convp_acc_init); the epilogue (convp_epilogue_impl) takes the GroupNorm partials of the
+// raw output from them and stores 16-byte rows.
 // ---------------------------------------------------------------------------------------------------------------
 struct ConvPParams {
   Gemm2Params g;                                       // main conv: W [N][KS * Cin] tap-major, bias, out, gn_partial, ...
@@ -38,30 +41,51 @@ __device__ __forceinline__ float gelu_as(float z) {    // z Phi(z), erf by A&S 7
   return z * (0.5f + 0.5f * copysignf(erfa, z));
 }
 
-// The same arithmetic on TWO fp16 values per instruction (v_pk_fma_f16 is a real 2 x, unlike v_pk_fma_f32): 21 instructions per
-// pair instead of ~21 per value.  Used when the stage's operand format is fp16 (the default policy): the result is rounded to
-// fp16 anyway; the fp16 intermediates cost ~1 ulp (|err| <= 6e-4 relative on GELU, 2.5e-4 |z| absolute near 0, where
-// 1 - poly * ex cancels).  z itself (scale / shift of the GroupNorm) is still formed in fp32 from the fp16 inputs: a packed
-// x * a + d would cancel |mean / std| ulps.
+// GELU on TWO fp16 values per instruction (v_pk_fma_f16 is a real 2 x, unlike v_pk_fma_f32), used when the stage's operand format
+// is fp16 (the default policy).  The result is rounded to fp16 anyway, so the form is chosen for fp16 arithmetic, not carried over
+// from the fp32 one:
+//     GELU(z) = max(z, 0) - |z| Phi(-|z|),   Phi(-a) = e / (1 + e),   e = 2^(-a q(a)),   q = c0 + c1 a + c2 a^2 + c3 a^3 + c4 a^4
+// a logistic fit of the normal CDF.  e <= 1, so nothing overflows; the tail is  |z| e  with e accurate relative to itself down to
+// the subnormals (the A&S erf form computed 1 - poly * ex there, whose fp16 rounding near 1 is 2.4e-4: 9 % of GELU(-3), and all of
+// it below -4); the last operation is ONE fma, so a large z comes back exactly (e t |z| < half an ulp from z = 3.45 on, e = 0 from
+// a q(a) > 25 on) and the negative side ends in a zero.  q grows without bound (c4 > 0): |z| up to 65504 needs no clamp, q = inf gives
+// e = 0, and no product is 0 x inf (q >= c0).  10 packed / bit operations and the same four transcendentals per pair, against 13.
+// Coefficients: least squares on log2(Phi(a) / Phi(-a)) / a over (0, 5.8], then the fp16 neighbours of each searched for the
+// smallest maximum error, in fp16 ulps of the float64 erf GELU, of this very sequence of fp16 roundings over all 63 488 finite
+// inputs, under the condition that every z >= 3.447 (from where on the float64 GELU rounds to z) comes back as z even with the
+// exponential one fp16 ulp off either way: at z = 3.447 the exact result lies 5e-7 above a rounding boundary, so that condition is
+// a matter of which side -a q(a) rounds to.  tests/test_gelu_fp16_host.py pins the coefficients and repeats the sweep.  Largest
+// error 11.9 ulps (at z = -4.16) and 1.02e-3 absolute (at z = 2.09, half an ulp of the result), the same on the MI355X as in the
+// emulation, against 2 043 ulps and 1.93e-3 of the A&S form in fp16 (profiles/r23/gelu_fp16_sweep.txt); in ulps it is also the
+// smaller of the two on each of [-6, -4), [-4, -2), [-2, -1), [-1, 0), [0, 1), [1, 2), [2, 4) taken alone.
+// z itself (scale / shift of the GroupNorm) is still formed in fp32 from the fp16 inputs: a packed x * a + d would cancel
+// |mean / std| ulps.
 typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
+#define SFM_GELU_H_C0 2.333984375f
+#define SFM_GELU_H_C1 (-0.08050537109375f)
+#define SFM_GELU_H_C2 0.1683349609375f
+#define SFM_GELU_H_C3 (-0.0183258056640625f)
+#define SFM_GELU_H_C4 0.0007991790771484375f
 // z pair already packed (the GroupNorm affine of the fp16 inputs formed by v_fma_mixlo / mixhi_f16: fp32 arithmetic, ONE rounding
 // to fp16, no unpack / pack instructions)
-__device__ __forceinline__ uint32_t gelu_as_h2p(uint32_t zb) {
+__device__ __forceinline__ uint32_t gelu_lg_h2p(uint32_t zb) {
   const h2_t z = __builtin_bit_cast(h2_t, zb);
   const h2_t az = __builtin_bit_cast(h2_t, zb & 0x7fff7fffu);
-  const h2_t u = az * (h2_t)(_Float16)(0.3275911f * 0.70710678118654752440f) + (h2_t)(_Float16)1.0f;
+  h2_t q = az * (_Float16)SFM_GELU_H_C4 + (_Float16)SFM_GELU_H_C3;
+  q = q * az + (_Float16)SFM_GELU_H_C2;
+  q = q * az + (_Float16)SFM_GELU_H_C1;
+  q = q * az + (_Float16)SFM_GELU_H_C0;
+  const h2_t e = __builtin_elementwise_exp2(-(q * az));
+  const h2_t u = e + (_Float16)1.0f;
   h2_t t;
   t[0] = __builtin_amdgcn_rcph(u[0]);
   t[1] = __builtin_amdgcn_rcph(u[1]);
-  const h2_t ex = __builtin_elementwise_exp2(z * z * (h2_t)(_Float16)(-0.72134752044448170368f));
-  h2_t poly = t * (_Float16)1.061405429f + (_Float16)(-1.453152027f);
-  poly = poly * t + (_Float16)1.421413741f;
-  poly = poly * t + (_Float16)(-0.284496736f);
-  poly = poly * t + (_Float16)0.254829592f;
-  poly = poly * t;
-  const h2_t erfa = (h2_t)(_Float16)1.0f - poly * ex;
-  const h2_t sg = __builtin_bit_cast(h2_t, (__builtin_bit_cast(uint32_t, erfa) & 0x7fff7fffu) | (zb & 0x80008000u));
-  return __builtin_bit_cast(uint32_t, z * (sg * (_Float16)0.5f + (_Float16)0.5f));
+  const h2_t m = az * e;
+  // max(z, 0) on the bit patterns as signed 16-bit integers (every negative half, -0 included, is a negative integer): the
+  // floating-point maximum would first canonicalise z, a second instruction
+  typedef short s2_t __attribute__((ext_vector_type(2)));
+  const h2_t r = __builtin_bit_cast(h2_t, __builtin_elementwise_max(__builtin_bit_cast(s2_t, zb), (s2_t)(short)0));
+  return __builtin_bit_cast(uint32_t, __builtin_elementwise_fma(-m, t, r));
 }
 
 // Epilogue of one 64 x 64 wave tile.  The accumulators hold the TRANSPOSED tile (weights were the A operand of the MFMAs):
@@ -80,27 +104,27 @@ __device__ __forceinline__ uint32_t gelu_as_h2p(uint32_t zb) {
 // 2 x 64 converts + 128 v_cndmask per tile); the row stores are buffer stores (32-bit offsets against a per-utterance descriptor
 // whose range check drops the rows beyond Lout: no 64-bit address arithmetic, no exec-mask branches).
 template <class T, bool FULL>
-__device__ __forceinline__ void convp_epilogue_impl(const Gemm2Params& g, f32x16 (&acc)[2][2], unsigned char* img, const float* bias_s,
+__device__ __forceinline__ void convp_epilogue_impl(const Gemm2Params& g, f32x16 (&acc)[2][2], unsigned char* img,
                                                     int lane, int b, int colb, int row_base) {
   constexpr int ROWB = 144;                            // image row: 64 x 16-bit + 16 bytes of padding (fp32 mode: two passes)
   const int l31 = lane & 31, hl = lane >> 5;
-  // ---- bias, statistics ----
+  // ---- statistics (the accumulators started from the bias: convp_acc_init) ----
   float ps[2][4], pq[2][4];                            // per (n-block j, 8-channel quad-pair g): sums over this lane's rows
 #pragma unroll
   for (int j = 0; j < 2; ++j)
 #pragma unroll
     for (int gq = 0; gq < 4; ++gq) {
-      const int n0 = colb + j * 32 + 8 * gq + 4 * hl;
-      const f32x4 bv = *reinterpret_cast<const f32x4*>(bias_s + n0);     // LDS copy made at kernel start (zeros without a bias)
       float s_ = 0.f, q_ = 0.f;
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const bool rowok = FULL || (row_base + i * 32 + l31 < g.Lout);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const float v = acc[i][j][4 * gq + e] + bv[e];
-          acc[i][j][4 * gq + e] = v;
-          if (rowok) {
+          const float v = acc[i][j][4 * gq + e];
+          if (FULL && i == 0 && e == 0) {              // the sums start from their first term (0 + v is not folded: -0)
+            s_ = v;
+            q_ = v * v;
+          } else if (rowok) {
             s_ += v;
             q_ = __builtin_fmaf(v, v, q_);
           }
@@ -114,7 +138,8 @@ __device__ __forceinline__ void convp_epilogue_impl(const Gemm2Params& g, f32x16
     // squares}) go through ONE transposing reduction; lane v < 16 then holds the tile total of (stat = v >> 3, j = (v >> 2) & 1,
     // gq = v & 3).  Groups wider than 8 channels add the neighbouring lanes' chunks (gq pairs: xor 1, quads: xor 2).
     const int cpg = g.gn_group >> 3;                   // 8-channel chunks per group: 1, 2 or 4
-    const int ngroups = g.N / g.gn_group;
+    const int gsh = 31 - __builtin_clz(g.gn_group);    // gn_group is 8, 16 or 32 (sfm_conv16p checks): shifts, not divisions
+    const int ngroups = g.N >> gsh;
     float v16[16];
 #pragma unroll
     for (int j = 0; j < 2; ++j)
@@ -128,7 +153,8 @@ __device__ __forceinline__ void convp_epilogue_impl(const Gemm2Params& g, f32x16
     if (cpg == 4) tot += dpp_perm<0x4E>(tot);
     const int gq_ = lane & 3, j_ = (lane >> 2) & 1, stat = (lane >> 3) & 1;
     if (lane < 16 && (gq_ & (cpg - 1)) == 0 && (row_base >> 6) < g.gn_slots) {
-      const long long sl = ((long long)b * g.gn_slots + (row_base >> 6)) * ngroups + (colb + j_ * 32 + 8 * gq_) / g.gn_group;
+      // the partials are fewer than B Lout words, and B Lout N outputs fit the device's memory: a 32-bit index
+      const int sl = (b * g.gn_slots + (row_base >> 6)) * ngroups + ((colb + j_ * 32 + 8 * gq_) >> gsh);
       g.gn_partial[sl * 2 + stat] = tot;
     }
   }
@@ -190,10 +216,28 @@ __device__ __forceinline__ void convp_epilogue_impl(const Gemm2Params& g, f32x16
 }
 
 template <class T>
-__device__ __forceinline__ void convp_epilogue(const Gemm2Params& g, f32x16 (&acc)[2][2], unsigned char* img, const float* bias_s,
+__device__ __forceinline__ void convp_epilogue(const Gemm2Params& g, f32x16 (&acc)[2][2], unsigned char* img,
                                                int lane, int b, int colb, int row_base) {
-  if (row_base + 64 <= g.Lout) convp_epilogue_impl<T, true>(g, acc, img, bias_s, lane, b, colb, row_base);       // wave-uniform
-  else convp_epilogue_impl<T, false>(g, acc, img, bias_s, lane, b, colb, row_base);
+  if (row_base + 64 <= g.Lout) convp_epilogue_impl<T, true>(g, acc, img, lane, b, colb, row_base);       // wave-uniform
+  else convp_epilogue_impl<T, false>(g, acc, img, lane, b, colb, row_base);
+}
+
+// The accumulators of one 64 x 64 wave tile start from the bias of their channels (the register -> channel map above) instead of
+// adding it in the epilogue: 16 LDS reads straight into the accumulator registers replace 64 adds and 8 LDS reads per tile.
+// bias_s = the LDS copy made at kernel start.  Called behind the first patch's barriers, just before the first MFMA: loaded at
+// kernel start the accumulators would be live across the first patch's staging, which cost b0.c2 its third workgroup per CU
+// (135 -> 213 VGPRs) and spilled in the k 7 + skip kernels.
+__device__ __forceinline__ void convp_acc_init(const float* bias_s, f32x16 (&acc)[2][2], int hl) {
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int gq = 0; gq < 4; ++gq) {
+        const f32x4 bv = *reinterpret_cast<const f32x4*>(bias_s + j * 32 + 8 * gq + 4 * hl);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[i][j][4 * gq + e] = bv[e];
+      }
 }
 
 template <class T, int KS, int STRIDE, int NPASS, bool SKIP, bool TWO_IN>
@@ -209,8 +253,7 @@ __global__ __launch_bounds__(256, 2) void conv16p_kernel(ConvPParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* ring = smem + PATCH;                  // 2 weight tiles; TWO_IN: also the landing area of the second raw input
   constexpr int RING = (TWO_IN && PATCH > 2 * WT) ? PATCH : 2 * WT;
-  float* bias_s = reinterpret_cast<float*>(smem + PATCH + RING);     // [256 main | 128 skip]: a global load in the epilogue
-                                                                     // would put a memory round trip in front of the statistics
+  float* bias_s = reinterpret_cast<float*>(smem + PATCH + RING);     // [256 main | 128 skip]: what the accumulators start from
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -257,7 +300,7 @@ __global__ __launch_bounds__(256, 2) void conv16p_kernel(ConvPParams p) {
     }
   };
 
-  f32x16 acc[NPASS][2][2], accs[2][2];
+  f32x16 acc[NPASS][2][2], accs[2][2];                 // started from the bias behind the first patch (convp_acc_init)
 #pragma unroll
   for (int n = 0; n < NPASS; ++n)
 #pragma unroll
@@ -303,6 +346,18 @@ __global__ __launch_bounds__(256, 2) void conv16p_kernel(ConvPParams p) {
     const int pos = l0 * STRIDE - p.pad + j;
     return (lr < LROWS && j < R && pos >= 0 && pos < p.Lin) ? pos : -1;
   };
+  // the same as ranges: LDS rows [tr_lo, tr_hi) of plane pl are the ones with row_pos >= 0 (j = JS idx + pl in [jlo, jhi))
+  int tr_lo[PLANES], tr_hi[PLANES];
+  {
+    constexpr int JS = (PLANES == 2) ? 2 : JSTEP;
+    const int base = l0 * STRIDE - p.pad;
+    const int jlo = max(-base, 0), jhi = min(p.Lin - base, R);
+#pragma unroll
+    for (int pl = 0; pl < PLANES; ++pl) {
+      tr_lo[pl] = pl * PR + (jlo - pl + JS - 1) / JS;                // jlo - pl + JS - 1 >= 0
+      tr_hi[pl] = pl * PR + min((max(jhi - pl, 0) + JS - 1) / JS, PR);
+    }
+  }
   const int sp_ = tid & 7, srow = tid >> 3;
   const int sc_ = sp_ ^ ((srow >> 1) & 7);                           // logical chunk (8 channels) this thread owns in every row
   auto stage_patch = [&](int slab) {
@@ -332,9 +387,13 @@ __global__ __launch_bounds__(256, 2) void conv16p_kernel(ConvPParams p) {
     }
     wait_vmcnt<0>();                                   // this wave's pieces have landed ...
     __syncthreads();                                   // ... everyone's have
+    // The rows with row_pos >= 0 are one run of consecutive LDS rows per plane, [tr_lo, tr_hi) (wave-uniform, worked out once per
+    // tile above); a thread's rows are srow + 32 i, so it walks from its first row at or above tr_lo to tr_hi without a test
+    // per chunk.  The rows outside stay the zeros the DMA left: the conv's zero padding.
+#pragma unroll
+    for (int pl = 0; pl < PLANES; ++pl)
 #pragma unroll 2
-    for (int lr = srow; lr < LROWS; lr += 32) {
-      if (row_pos(lr) < 0) continue;                   // zero-filled row: stays the conv's zero padding
+    for (int lr = srow + (max(tr_lo[pl] - srow + 31, 0) & ~31); lr < tr_hi[pl]; lr += 32) {
       unsigned char* q1 = smem + lr * 128 + sp_ * 16;
       const u32x4 v1 = *reinterpret_cast<const u32x4*>(q1);
       u32x4 v2 = {0u, 0u, 0u, 0u};
@@ -354,7 +413,7 @@ __global__ __launch_bounds__(256, 2) void conv16p_kernel(ConvPParams p) {
           asm("v_fma_mixlo_f16 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,0]\n\t"
               "v_fma_mixhi_f16 %0, %1, %4, %5 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
               : "=&v"(zpk) : "v"(v1[e]), "v"(a1[2 * e]), "v"(t0), "v"(a1[2 * e + 1]), "v"(t1));
-          o[e] = gelu_as_h2p(zpk);
+          o[e] = gelu_lg_h2p(zpk);
           continue;
         }
         // bf16: unpack, fp32 affine and GELU, pack
@@ -401,6 +460,11 @@ __global__ __launch_bounds__(256, 2) void conv16p_kernel(ConvPParams p) {
     __syncthreads();                                   // patch complete
     const int q0 = slab * TPS;
     if (TWO_IN) issue_w(q0);                           // the ring held the second raw input until now
+    if (slab == 0) {                                   // wave-uniform; bias_s was written before the patch's barriers
+#pragma unroll
+      for (int n = 0; n < NPASS; ++n) convp_acc_init(bias_s + n * 128 + wn * 64, acc[n], hl);
+      if (SKIP) convp_acc_init(bias_s + 256 + wn * 64, accs, hl);
+    }
 #pragma unroll
     for (int j = 0; j < TPS; ++j) {
       const int q = q0 + j;
@@ -425,8 +489,8 @@ __global__ __launch_bounds__(256, 2) void conv16p_kernel(ConvPParams p) {
   __syncthreads();                                     // the ring becomes the epilogue strips
   unsigned char* img = smem + wave * 9216;             // 64 x 144 B per wave, in the (now free) patch + ring area
 #pragma unroll
-  for (int n = 0; n < NPASS; ++n) convp_epilogue<T>(p.g, acc[n], img, bias_s, lane, b, n * 128 + wn * 64, l0 + wm * 64);
-  if (SKIP) convp_epilogue<T>(p.gs, accs, img, bias_s + 256, lane, b, wn * 64, l0 + wm * 64);
+  for (int n = 0; n < NPASS; ++n) convp_epilogue<T>(p.g, acc[n], img, lane, b, n * 128 + wn * 64, l0 + wm * 64);
+  if (SKIP) convp_epilogue<T>(p.gs, accs, img, lane, b, wn * 64, l0 + wm * 64);
 }
 
 template <class T, int KS, int STRIDE, int NPASS, bool SKIP, bool TWO_IN>
@@ -468,7 +532,7 @@ extern "C" int sfm_conv16p(const void* x1, const float* sc1, const float* sh1, c
   if ((x2 != nullptr) != (sc2 != nullptr) || (x2 != nullptr) != (sh2 != nullptr)) return SFM_ERR_ARG;
   if (B <= 0 || Lin <= 0 || Cin <= 0 || (Cin % 64) != 0 || (N != 128 && N != 256)) return SFM_ERR_SHAPE;
   if (out_f32 < 0 || out_f32 > 2) return SFM_ERR_SHAPE;
-  if (gn_partial && gn_group != 8 && gn_group != 16 && gn_group != 32) return SFM_ERR_SHAPE;
+  if ((gn_partial || gn_partial_s) && gn_group != 8 && gn_group != 16 && gn_group != 32) return SFM_ERR_SHAPE;
   if ((long long)Lin * Cin * 2 >= (1LL << 31) || (long long)N * ksize * Cin * 2 >= (1LL << 31)) return SFM_ERR_SHAPE;
   if ((long long)((Lin + 2 * pad - ksize) / stride + 1) * N * 4 >= (1LL << 31)) return SFM_ERR_SHAPE;       // 32-bit store offsets per utterance
   const int Lout = (Lin + 2 * pad - ksize) / stride + 1;
