@@ -85,6 +85,9 @@ extern "C" {
 #define SFM_DNN_ACT_RELU 1
 #define SFM_DNN_ACT_SIGMOID 2
 #define SFM_DNN_CONTEXT_MAX_K 4096     /* context rows with statistics: mean and std sit in LDS beside the tiles */
+#define SFM_MSE_GATHER_MAX_BLOCKS 1024 /* sfm_mse_gather_loss: workgroups at most, one fp64 partial each = its ws in doubles */
+#define SFM_MOMENTS_CHUNK_ROWS 256     /* sfm_context_moments: rows of a chunk at least */
+#define SFM_MOMENTS_MAX_CHUNKS 1024    /* chunks at most; ws = (SFM_MOMENTS_MAX_CHUNKS + 1) D (2 ctx + 1) doubles */
 #define SFM_RESYNTH_TILE_FRAMES 64     /* frames a workgroup of sfm_mask_resynth computes; it owns one output hop fewer */
 #define SFM_RESYNTH_MAX_NFFT 256       /* the largest n_fft and frame its LDS layout holds */
 #define SFM_RESYNTH_MAX_FRAME 256
@@ -459,6 +462,17 @@ int sfm_adamw_step_scaled(float* p, float* g, float* m, float* v, long long n, d
                           float eps, float wd, float inv_world, float max_norm, int write_back_grad, const long long* spans,
                           const float* touched, int n_params, float* loss_scale, float growth_factor, float backoff_factor,
                           int growth_interval, void* stream);
+/* torch.optim.Adam(weight_decay = wd) behind clip_grad_norm_(max_norm) (training/pipeline.py:563-567, 664-669 of the reference) on
+ * the same flat buffers, ctl layout, spans / touched mask and loss-scale state (loss_scale NULL: S = 1).  The norm (ctl[7]) and the
+ * clip coefficient are those of the unscaled gradient WITHOUT the decay term; then g <- g + wd p, m <- beta1 m + (1 - beta1) g,
+ * v <- beta2 v + (1 - beta2) g^2, p <- p - (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps).  A step skipped for a non-finite gradient or
+ * for the flag ctl[2] leaves p, m, v and the step count alone and multiplies S by backoff_factor (counted in loss_scale[2] and
+ * loss_scale[3]).  g is left as it was.  The betas are given as 1 - beta (in 0 .. 1]: 0.001f is 1 - 0.999 to 5e-8 relative, while
+ * 1 - 0.999f is that only to 1.3e-5, which v would inherit. */
+int sfm_adam_l2_step(float* p, float* g, float* m, float* v, long long n, double* ctl, float lr, float one_minus_beta1,
+                     float one_minus_beta2, float eps, float wd, float inv_world, float max_norm, const long long* spans,
+                     const float* touched, int n_params, float* loss_scale, float growth_factor, float backoff_factor,
+                     int growth_interval, void* stream);
 /* ---- training path of the ConformerBlock (backward of models/conformer.py:28-151) ---- */
 /* dW[n,k] += sum_m G[m,n] X[m,k] (weight gradient; M is split over workgroups: with ws (>= sfm_tn_ws_floats(M, N, K) floats) every
  * split writes its partial [N][K] and the partials are added to dW in split order, without ws by fp32 atomics; zero dW first);
@@ -852,6 +866,36 @@ int sfm_dnn_layer(const void* A, const int* frames, const float* mean, const flo
                   int act, float p_drop, unsigned int seed, int dtype, void* stream);
 int sfm_dnn_act_bwd(const void* dy, int dy_f32, long long ldy, const void* saved, long long ld_saved, void* dz, long long ldz, int M,
                     int N, int act, float p_drop, int dtype, void* stream);
+
+/* Training the DNN from a frame set kept at D columns (training/pipeline.py of the reference: SpeechEnhancementDataset :217-289,
+ * _train_epoch :643-685).  raw [n_frames, D] fp32 are the packed frames of all utterances, bounds int32 [n_frames, 2] (8-byte
+ * aligned) the first and the one-past-last packed row of each frame's utterance.  No atomics, the same bits from run to run.
+ * sfm_context_moments: mean, stdv fp32 [K], K = D (2 ctx + 1), of the context rows of all n_frames frames - column j D + c of
+ *   frame n = raw[clamp(n - ctx + j, lo_n, hi_n - 1), c], nan / inf read as 0 - without forming them: the mean, then the
+ *   population standard deviation from the squares centred on it, both summed in fp64 (one partial per chunk of rows and column,
+ *   folded in chunk order), rounded to fp32; stdv < 1e-6 -> 1.  ws: (SFM_MOMENTS_MAX_CHUNKS + 1) K doubles.
+ * sfm_dnn_layer_indexed: sfm_dnn_layer's context mode on an index list: row m of the operand is the context row of packed frame
+ *   index[m] (int32 [M]; a repeated index is legal; < 0 or >= n_frames: a zero row), its neighbours clamped to bounds[index[m]];
+ *   mean / stdv [K] (both or neither; K <= SFM_DNN_CONTEXT_MAX_K) as there.  D even and >= 8, K = D (2 ctx + 1).  a16_out (or
+ *   NULL): [M, ld16] 16-bit of `dtype`, ld16 = K rounded up to 64, 16-byte aligned: the staged operand rows, columns K .. ld16
+ *   zeros, written by the workgroups of column tile 0 - what sfm_gemm16_tn reads for the layer's weight gradient.  W, bias, out,
+ *   ldo, out_f32, act, p_drop, seed as sfm_dnn_layer.  A row's result has the same bits alone or inside any M, and the bits of
+ *   the context mode on the frame's utterance alone.
+ * sfm_mse_gather_loss: y fp32 [M, C] compact, mask fp32 [n_frames, C] compact, t = clip(nan_to_num(mask[index[m], c], nan 0, +inf 1,
+ *   -inf 0), 0, 1); loss[0] (or NULL) = mean (y - t)^2 over the M C elements (fp64 partials per workgroup, folded in order by a
+ *   one-workgroup kernel).  dz (or NULL: validation): [M, ldz] 16-bit of `dtype`, ldz % 8 == 0, columns C .. ldz zeros,
+ *   = S 2 (y - t) / (M C) y (1 - y), S = loss_scale[0] (device, NULL: 1): the output layer's pre-activation cotangent under the
+ *   loss scale.  rec (or NULL) 4 doubles, the epoch's record: [0] += loss and [1] += 1 when the loss is finite, else [2] += 1;
+ *   [3] = loss.  ctl (or NULL): the optimiser's control block, ctl[2] = 1 when the loss is not finite (the step is skipped).
+ *   A row whose index is outside 0 .. n_frames - 1 adds nothing and gets a zero dz row.  ws: SFM_MSE_GATHER_MAX_BLOCKS doubles. */
+int sfm_context_moments(const float* raw, const int* bounds, float* mean, float* stdv, double* ws, int n_frames, int D, int ctx,
+                        void* stream);
+int sfm_dnn_layer_indexed(const float* raw, const int* bounds, const int* index, const float* mean, const float* stdv, const void* W,
+                          const float* bias, void* out, void* a16_out, int M, int N, int K, int n_frames, int D, int ctx, int Kpad,
+                          int Npad, long long ldo, long long ld16, int out_f32, int act, float p_drop, unsigned int seed, int dtype,
+                          void* stream);
+int sfm_mse_gather_loss(const float* y, const float* mask, const int* index, const float* loss_scale, void* dz, long long ldz,
+                        float* loss, double* rec, double* ctl, double* ws, int M, int C, int n_frames, int dtype, void* stream);
 
 /* Mask to waveform (resynth.hip; steps 2-4 of TrainingPipeline.enhance_signal, training/pipeline.py:877-934 of the reference) in one
  * launch, exact fp32 on v_mfma_f32_32x32x2_f32, no atomics.  noisy, out [B, L] fp32; mask [B, T_mask, C] fp32; lengths int32 [B] = the

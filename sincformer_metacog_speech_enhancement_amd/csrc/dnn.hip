@@ -34,9 +34,14 @@ struct DnnParams {
   int M, N, K, T, D, ctx, Kpad, Npad, out_f32, act, pair;
   float p_drop, inv_keep;
   uint32_t seed;
+  // indexed context (sfm_dnn_layer_indexed): A = raw [n_frames, D] packed, T = n_frames
+  const int* index;       // int32 [M]: the packed frame of row m (< 0 or >= n_frames: a zero row)
+  const int* bounds;      // int32 [n_frames, 2]: first and one-past-last packed row of the frame's utterance
+  u16* a16;               // [M, ld16] or NULL: the staged 16-bit operand rows, written by the workgroups of column tile 0
+  long long ld16;
 };
 
-enum { DNN_ROWS16 = 0, DNN_ROWS32 = 1, DNN_CONTEXT = 2 };
+enum { DNN_ROWS16 = 0, DNN_ROWS32 = 1, DNN_CONTEXT = 2, DNN_INDEXED = 3 };
 
 template <class T, int AMODE, int BN>
 __global__ __launch_bounds__(256) void dnn_layer_kernel(DnnParams p) {
@@ -54,7 +59,7 @@ __global__ __launch_bounds__(256) void dnn_layer_kernel(DnnParams p) {
   const int ntile = blockIdx.x % nNt, mtile = blockIdx.x / nNt;
   const int n0 = ntile * BN, m0 = mtile * SFM_DNN_ROW_TILE;
   const int c8 = tid & 7, r0 = tid >> 3;                     // this thread stages chunk c8 of rows r0, r0 + 32, r0 + 64, r0 + 96
-  const bool has_stats = AMODE == DNN_CONTEXT && p.mean != nullptr;
+  const bool has_stats = (AMODE == DNN_CONTEXT || AMODE == DNN_INDEXED) && p.mean != nullptr;
 
   if (has_stats) {
     for (int k = tid; k < nt * 64; k += 256) {
@@ -79,6 +84,22 @@ __global__ __launch_bounds__(256) void dnn_layer_kernel(DnnParams p) {
         src[i] = reinterpret_cast<const float*>(p.A) + (long long)b * p.T * p.D;
         frame_n[i] = n;
         frame_tb[i] = tb;
+      }
+    }
+    if constexpr (AMODE == DNN_INDEXED) {
+      // the row's packed frame and its utterance's bounds: an index load and one 8-byte load per row, once, ahead of the k loop;
+      // from here on the row is an utterance (src), a frame in it and its frame count, as in the context mode
+      if (row < p.M) {
+        const int f = p.index[row];
+        if (f >= 0 && f < p.T) {
+          const int2 lh = *reinterpret_cast<const int2*>(p.bounds + 2 * (long long)f);
+          const int lo = lh.x < 0 ? 0 : lh.x, hi = lh.y > p.T ? p.T : lh.y;
+          if (lo <= f && f < hi) {
+            src[i] = reinterpret_cast<const float*>(p.A) + (long long)lo * p.D;
+            frame_n[i] = f - lo;
+            frame_tb[i] = hi - lo;
+          }
+        }
       }
     }
   }
@@ -176,6 +197,12 @@ __global__ __launch_bounds__(256) void dnn_layer_kernel(DnnParams p) {
         v = u32x4{pack2<T>(f[0], f[1]), pack2<T>(f[2], f[3]), pack2<T>(f[4], f[5]), pack2<T>(f[6], f[7])};
       }
       *reinterpret_cast<u32x4*>(sA + row * 128 + ((c8 ^ ((row >> 1) & 7)) << 4)) = v;
+      if constexpr (AMODE == DNN_INDEXED) {
+        // the first layer's weight gradient reads these rows (ld16 = 64 nt: every chunk of every k tile lies inside the row;
+        // the columns K .. ld16 were staged as zeros)
+        if (p.a16 != nullptr && ntile == 0 && m0 + row < p.M)
+          *reinterpret_cast<u32x4*>(p.a16 + (long long)(m0 + row) * p.ld16 + kt * 64 + c8 * 8) = v;
+      }
     }
   };
 
@@ -321,8 +348,38 @@ extern "C" int sfm_dnn_layer(const void* A, const int* frames, const float* mean
   p.A = A; p.frames = frames; p.mean = mean; p.stdv = stdv; p.W = (const u16*)W; p.bias = bias; p.out = out;
   p.lda = lda; p.ldo = ldo; p.M = M; p.N = N; p.K = K; p.T = T; p.D = D; p.ctx = ctx; p.Kpad = Kpad; p.Npad = Npad;
   p.out_f32 = out_f32; p.act = act; p.p_drop = p_drop; p.inv_keep = 1.0f / (1.0f - p_drop); p.seed = seed;
+  p.index = nullptr; p.bounds = nullptr; p.a16 = nullptr; p.ld16 = 0;
   if (dtype == SFM_DT_F16) return dnn_layer_mode<F16>(p, a_mode, lds, (hipStream_t)stream);
   return dnn_layer_mode<BF16>(p, a_mode, lds, (hipStream_t)stream);
+}
+
+// The first layer on an index list: the context mode with a per-row frame in place of (row / T, row % T)
+extern "C" int sfm_dnn_layer_indexed(const float* raw, const int* bounds, const int* index, const float* mean, const float* stdv,
+                                     const void* W, const float* bias, void* out, void* a16_out, int M, int N, int K, int n_frames,
+                                     int D, int ctx, int Kpad, int Npad, long long ldo, long long ld16, int out_f32, int act,
+                                     float p_drop, unsigned int seed, int dtype, void* stream) {
+  if (!raw || !bounds || !index || !W || !out || (mean == nullptr) != (stdv == nullptr)) return SFM_ERR_ARG;
+  if (act < SFM_DNN_ACT_NONE || act > SFM_DNN_ACT_SIGMOID || (out_f32 != 0 && out_f32 != 1)) return SFM_ERR_ARG;
+  if (!(p_drop >= 0.f && p_drop < 1.f) || (p_drop > 0.f && act != SFM_DNN_ACT_RELU)) return SFM_ERR_ARG;
+  if (M <= 0 || N <= 0 || K <= 0 || Kpad < K || (Kpad % 64) != 0 || Npad < N || (Npad % 64) != 0 || ldo < N) return SFM_ERR_SHAPE;
+  if ((long long)M * N > 0x7fffffffffLL || K > (1 << 24)) return SFM_ERR_SHAPE;
+  if (n_frames <= 0 || D < 8 || (D % 2) != 0 || ctx < 0 || ctx > 64 || (long long)D * (2 * ctx + 1) != K) return SFM_ERR_SHAPE;
+  if (a16_out && ld16 != (long long)((K + 63) / 64) * 64) return SFM_ERR_SHAPE;
+  if ((((uintptr_t)W) % 16) != 0 || (((uintptr_t)raw) % 8) != 0 || (((uintptr_t)bounds) % 8) != 0 || (((uintptr_t)a16_out) % 16) != 0)
+    return SFM_ERR_ARG;
+  int lds = 2 * DNN_TILE_BYTES;
+  if (mean) {
+    if (K > SFM_DNN_CONTEXT_MAX_K) return SFM_ERR_SHAPE;
+    lds += 2 * ((K + 63) / 64 * 64) * (int)sizeof(float);
+  }
+  if (dtype != SFM_DT_BF16 && dtype != SFM_DT_F16) return SFM_ERR_ARG;      // last: a call refused for it alone passed every other check
+  DnnParams p;
+  p.A = raw; p.frames = nullptr; p.mean = mean; p.stdv = stdv; p.W = (const u16*)W; p.bias = bias; p.out = out;
+  p.lda = 0; p.ldo = ldo; p.M = M; p.N = N; p.K = K; p.T = n_frames; p.D = D; p.ctx = ctx; p.Kpad = Kpad; p.Npad = Npad;
+  p.out_f32 = out_f32; p.act = act; p.pair = 0; p.p_drop = p_drop; p.inv_keep = 1.0f / (1.0f - p_drop); p.seed = seed;
+  p.index = index; p.bounds = bounds; p.a16 = (u16*)a16_out; p.ld16 = ld16;
+  if (dtype == SFM_DT_F16) return dnn_layer_launch<F16, DNN_INDEXED>(p, lds, (hipStream_t)stream);
+  return dnn_layer_launch<BF16, DNN_INDEXED>(p, lds, (hipStream_t)stream);
 }
 
 // one thread per 8 consecutive columns of a dz row: [M, ldz / 8] chunks; columns N .. ldz are written as zeros
@@ -375,5 +432,98 @@ extern "C" int sfm_dnn_act_bwd(const void* dy, int dy_f32, long long ldy, const 
   else
     SFM_LAUNCH((dnn_act_bwd_kernel<BF16>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, dy, dy_f32, ldy, saved, ld_saved,
                (u16*)dz, ldz, M, N, act, inv_keep);
+  return SFM_OK;
+}
+
+// ---- the training loss on gathered targets, and the output layer's pre-activation cotangent, in one pass over y ----------------
+// mse_gather_kernel: one thread per 8 consecutive columns of a dz row (as dnn_act_bwd_kernel), grid-stride over the [M, ldz / 8]
+//   chunks; t = clip(nan_to_num(mask[index[m], c], nan 0, +inf 1, -inf 0), 0, 1) (the Dataset's treatment of the mask),
+//   d = y - t, the squares summed in fp64 per workgroup -> ws[workgroup]; dz = (S 2 / (M C)) d y (1 - y) in fp32, rounded once.
+// mse_gather_finish_kernel: one workgroup folds the partials in workgroup order, loss = sum / (M C), and keeps the epoch's record
+//   rec = {sum of finite batch losses, finite batches, non-finite batches, the last loss}; a non-finite loss raises ctl[2], the
+//   optimiser's skip flag.
+static_assert(SFM_MSE_GATHER_MAX_BLOCKS == 1024, "one fp64 partial per workgroup: the scratch the wrapper allocates");
+
+__device__ __forceinline__ float mask_target(float t) {
+  if (t != t) return 0.f;
+  return t < 0.f ? 0.f : (t > 1.f ? 1.f : t);                 // -inf -> 0, +inf -> 1
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void mse_gather_kernel(const float* __restrict__ y, const float* __restrict__ mask,
+                                                         const int* __restrict__ index, const float* __restrict__ loss_scale,
+                                                         u16* __restrict__ dz, long long ldz, double* __restrict__ ws, int M, int C,
+                                                         int n_frames) {
+  __shared__ double red[4];
+  const long long chunks = ldz >> 3;
+  const long long work = (long long)M * chunks;
+  const float S = loss_scale ? loss_scale[0] : 1.f;
+  const float k = (float)((double)S * 2.0 / ((double)M * (double)C));
+  double sq = 0.0;
+  for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < work; idx += (long long)gridDim.x * 256) {
+    const long long row = idx / chunks;
+    const int c0 = (int)(idx - row * chunks) * 8;
+    const int f = index[row];
+    const bool live = f >= 0 && f < n_frames;
+    float g[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int c = c0 + e;
+      g[e] = 0.f;
+      if (live && c < C) {
+        const float yv = y[row * C + c];
+        const float d = yv - mask_target(mask[(long long)f * C + c]);
+        sq += (double)d * (double)d;
+        g[e] = k * d * (yv * (1.f - yv));
+      }
+    }
+    if (dz != nullptr)
+      *reinterpret_cast<u32x4*>(dz + row * ldz + c0) =
+          u32x4{pack2<T>(g[0], g[1]), pack2<T>(g[2], g[3]), pack2<T>(g[4], g[5]), pack2<T>(g[6], g[7])};
+  }
+  sq = wave_sum_d(sq);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sq;
+  __syncthreads();
+  if (threadIdx.x == 0) ws[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+__global__ __launch_bounds__(256) void mse_gather_finish_kernel(const double* __restrict__ ws, int nb, double count,
+                                                                float* __restrict__ loss, double* __restrict__ rec,
+                                                                double* __restrict__ ctl) {
+  __shared__ double part[256];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < nb; i += 256) s += ws[i];
+  part[threadIdx.x] = s;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double total = 0.0;
+  for (int i = 0; i < 256; ++i) total += part[i];
+  const double l = total / count;
+  const bool finite = l == l && l <= 1.7e308 && l >= -1.7e308;
+  if (loss) loss[0] = (float)l;
+  if (rec) {
+    if (finite) { rec[0] += l; rec[1] += 1.0; } else { rec[2] += 1.0; }
+    rec[3] = l;
+  }
+  if (ctl && !finite) ctl[2] = 1.0;
+}
+
+extern "C" int sfm_mse_gather_loss(const float* y, const float* mask, const int* index, const float* loss_scale, void* dz, long long ldz,
+                                   float* loss, double* rec, double* ctl, double* ws, int M, int C, int n_frames, int dtype,
+                                   void* stream) {
+  if (!y || !mask || !index || !ws || (!loss && !rec)) return SFM_ERR_ARG;
+  if (M <= 0 || C <= 0 || n_frames <= 0 || ldz < C || (ldz % 8) != 0) return SFM_ERR_SHAPE;
+  if ((((uintptr_t)dz) % 16) != 0) return SFM_ERR_ARG;
+  if (dtype != SFM_DT_BF16 && dtype != SFM_DT_F16) return SFM_ERR_ARG;      // last, as in sfm_dnn_layer_indexed
+  const long long work = (long long)M * (ldz >> 3);
+  const int nb = (int)sfm_capped_blocks(work, 256, SFM_MSE_GATHER_MAX_BLOCKS);
+  if (dtype == SFM_DT_F16)
+    SFM_LAUNCH((mse_gather_kernel<F16>), dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, y, mask, index, loss_scale, (u16*)dz, ldz,
+               ws, M, C, n_frames);
+  else
+    SFM_LAUNCH((mse_gather_kernel<BF16>), dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, y, mask, index, loss_scale, (u16*)dz, ldz,
+               ws, M, C, n_frames);
+  SFM_LAUNCH(mse_gather_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)ws, nb, (double)M * (double)C, loss, rec,
+             ctl);
   return SFM_OK;
 }

@@ -249,3 +249,72 @@ extern "C" int sfm_rows_mean(const float* in, const int* lengths, float* out, in
   SFM_LAUNCH(rows_mean_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, in, lengths, out, T, L, frame, hop, ld_in, col_off, N, den);
   return SFM_OK;
 }
+
+// ---- the Dataset's statistics over the context rows, from the packed raw rows (training/pipeline.py:246-256 of the reference) -----
+// Column k = j D + c of the context row of packed frame n is raw[clamp(n - ctx + j, lo_n, hi_n - 1), c] (bounds[n] = {lo_n, hi_n}:
+// the frame's utterance), nan / inf read as 0: the [N, K] rows are never formed.  Two passes in fp64, because a column's mean can
+// lie far above its spread (MFCC c0) and raw moments would cancel: pass 0 sums the values, pass 1 the squares of (value - mean).
+// context_moments_partial_kernel: grid (chunks, ceil(K / 256)), a thread owns one column over the chunk's rows -> ws[chunk K + k];
+// context_moments_fold_kernel: one workgroup adds the chunks in chunk order: the same bits from run to run.
+static_assert(SFM_MOMENTS_MAX_CHUNKS == 1024 && SFM_MOMENTS_CHUNK_ROWS == 256, "ws = (SFM_MOMENTS_MAX_CHUNKS + 1) K doubles");
+
+__global__ __launch_bounds__(256) void context_moments_partial_kernel(const float* __restrict__ raw, const int* __restrict__ bounds,
+                                                                      const double* __restrict__ mean_d, double* __restrict__ ws,
+                                                                      int N, int D, int ctx, int K, int rows_per_chunk) {
+  const int k = blockIdx.y * 256 + threadIdx.x;
+  if (k >= K) return;
+  const int j = k / D, c = k - j * D;
+  const int n0 = blockIdx.x * rows_per_chunk;
+  const int n1 = n0 + rows_per_chunk < N ? n0 + rows_per_chunk : N;
+  const double mu = mean_d ? mean_d[k] : 0.0;
+  double s = 0.0;
+  for (int n = n0; n < n1; ++n) {
+    const int2 lh = *reinterpret_cast<const int2*>(bounds + 2 * (long long)n);
+    const int lo = lh.x < 0 ? 0 : lh.x, hi = lh.y > N ? N : lh.y;
+    double x = 0.0;
+    if (lo < hi) {
+      int r = n - ctx + j;
+      r = r < lo ? lo : (r > hi - 1 ? hi - 1 : r);
+      const float f = raw[(long long)r * D + c];
+      x = isfinite(f) ? (double)f : 0.0;
+    }
+    const double d = x - mu;
+    s += mean_d ? d * d : x;
+  }
+  ws[(long long)blockIdx.x * K + k] = s;
+}
+
+__global__ __launch_bounds__(256) void context_moments_fold_kernel(const double* __restrict__ ws, int chunks, int K, int N, int pass,
+                                                                   double* __restrict__ mean_d, float* __restrict__ out) {
+  for (int k = threadIdx.x; k < K; k += 256) {
+    double s = 0.0;
+    for (int c = 0; c < chunks; ++c) s += ws[(long long)c * K + k];
+    if (pass == 0) {
+      mean_d[k] = s / (double)N;
+      out[k] = (float)(s / (double)N);
+    } else {
+      const float sd = (float)sqrt(s / (double)N);
+      out[k] = sd < 1e-6f ? 1.0f : sd;                                       // a constant column: no division by zero
+    }
+  }
+}
+
+extern "C" int sfm_context_moments(const float* raw, const int* bounds, float* mean, float* stdv, double* ws, int N, int D, int ctx,
+                                   void* stream) {
+  if (!raw || !bounds || !mean || !stdv || !ws) return SFM_ERR_ARG;
+  if (N <= 0 || D < 1 || ctx < 0 || ctx > 64 || (long long)D * (2 * ctx + 1) > (1 << 20)) return SFM_ERR_SHAPE;
+  if ((((uintptr_t)bounds) % 8) != 0) return SFM_ERR_ARG;
+  const int K = D * (2 * ctx + 1);
+  int chunks = (int)sfm_capped_blocks(N, SFM_MOMENTS_CHUNK_ROWS, SFM_MOMENTS_MAX_CHUNKS);
+  const int rows_per_chunk = (N + chunks - 1) / chunks;
+  chunks = (N + rows_per_chunk - 1) / rows_per_chunk;
+  double* mean_d = ws + (long long)SFM_MOMENTS_MAX_CHUNKS * K;
+  const dim3 grid((unsigned)chunks, (unsigned)((K + 255) / 256));
+  SFM_LAUNCH(context_moments_partial_kernel, grid, dim3(256), 0, (hipStream_t)stream, raw, bounds, (const double*)nullptr, ws, N, D, ctx,
+             K, rows_per_chunk);
+  SFM_LAUNCH(context_moments_fold_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)ws, chunks, K, N, 0, mean_d, mean);
+  SFM_LAUNCH(context_moments_partial_kernel, grid, dim3(256), 0, (hipStream_t)stream, raw, bounds, (const double*)mean_d, ws, N, D, ctx,
+             K, rows_per_chunk);
+  SFM_LAUNCH(context_moments_fold_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)ws, chunks, K, N, 1, mean_d, stdv);
+  return SFM_OK;
+}

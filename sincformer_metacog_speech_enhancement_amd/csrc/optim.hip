@@ -192,3 +192,106 @@ extern "C" int sfm_adamw_step_scaled(float* p, float* g, float* m, float* v, lon
   return adamw_step_impl(p, g, m, v, n, ctl, lr, beta1, beta2, eps, wd, inv_world, max_norm, write_back_grad, spans, touched,
                          n_params, stream, loss_scale, growth_factor, backoff_factor, growth_interval);
 }
+
+// ---- torch.optim.Adam(weight_decay = wd) behind clip_grad_norm_ (the reference's training/pipeline.py:563-567, 664-669) --------------
+// The same ctl layout, spans / touched mask and loss-scale state as the AdamW step above.  What differs:
+//   - the decay is L2 ADDED TO THE GRADIENT (g <- g + wd p) after the clip, so the norm in ctl[7] and the clip coefficient are
+//     those of the unscaled gradient without the decay term (clip_grad_norm_ runs before optimizer.step);
+//   - eps stands outside the square root of the bias-corrected v, step size lr / bc1 (torch's formulas; the AdamW apply above
+//     writes the same denominator);
+//   - a step skipped for the flag (ctl[2], a non-finite loss) backs the scale off like one skipped for a non-finite gradient:
+//     the flag is raised on the device (sfm_mse_gather_loss) behind a forward that ran in the 16-bit format.
+// loss_scale may be NULL: S = 1 and no scale state.
+__global__ void adam_l2_prepare_kernel(double* __restrict__ ctl, float* __restrict__ ls, double inv_world, double max_norm, double beta1,
+                                       double beta2, float growth, float backoff, float interval) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const double S = ls ? (double)ls[0] : 1.0;
+  const double inv_scale = inv_world / S;
+  const double norm = sqrt(ctl[1]) * inv_scale;
+  const bool bad_grad = !(norm == norm) || norm > 1.7e308;
+  const bool bad_loss = ctl[2] > 0.0;
+  const bool bad = bad_grad || bad_loss;
+  double coef = 1.0;
+  if (max_norm > 0.0 && norm > max_norm) coef = max_norm / (norm + 1e-6);     // torch.nn.utils.clip_grad_norm_
+  ctl[7] = norm;
+  ctl[4] = bad ? 1.0 : 0.0;
+  ctl[3] = inv_scale * coef;
+  if (!bad) {
+    const double step = ctl[0] + 1.0;
+    ctl[0] = step;
+    ctl[5] = 1.0 - pow(beta1, step);
+    ctl[6] = 1.0 - pow(beta2, step);
+  }
+  if (ls) {
+    if (bad) {
+      ls[0] = fmaxf(ls[0] * backoff, 1.17549435e-38f);
+      ls[1] = 0.f;
+      ls[bad_loss ? 3 : 2] += 1.f;
+    } else {
+      const float t = ls[1] + 1.f;
+      if (t >= interval) {
+        const float grown = ls[0] * growth;
+        ls[0] = (grown == grown && grown < 3.0e38f) ? grown : ls[0];
+        ls[1] = 0.f;
+      } else {
+        ls[1] = t;
+      }
+    }
+  }
+  ctl[1] = 0.0;
+  ctl[2] = 0.0;
+}
+
+__global__ __launch_bounds__(256) void adam_l2_apply_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                            float* __restrict__ v, long long n, const double* __restrict__ ctl,
+                                                            float lr, float omb1, float omb2, float eps, float wd,
+                                                            const long long* __restrict__ spans, const float* __restrict__ touched,
+                                                            int n_params) {
+  if (ctl[4] > 0.0) return;                                                    // skipped step: nothing changes
+  // 1 - beta arrives as given (0.001f is 1 - 0.999 to 5e-8, 1 - 0.999f only to 1.3e-5); beta is formed from it
+  const float beta1 = (float)(1.0 - (double)omb1), beta2 = (float)(1.0 - (double)omb2);
+  const float gs = (float)ctl[3];
+  const float step_size = lr / (float)ctl[5];
+  const float inv_sqrt_bc2 = (float)(1.0 / sqrt(ctl[6]));
+  for (long long base = (long long)blockIdx.x * 256; base < n; base += (long long)gridDim.x * 256) {
+    const long long i = base + threadIdx.x;
+    if (spans) {                                                               // as adamw_apply_kernel
+      int lo = 0, hi = n_params - 1;
+      while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (spans[mid] <= base) lo = mid; else hi = mid - 1;
+      }
+      int k = lo;
+      while (k + 1 < n_params && spans[k + 1] <= i) ++k;
+      if (i < n && touched[k] <= 0.f) continue;
+    }
+    if (i >= n) continue;
+    const float pi = p[i];
+    const float gi = g[i] * gs + wd * pi;
+    const float mi = beta1 * m[i] + omb1 * gi;
+    const float vi = beta2 * v[i] + omb2 * gi * gi;
+    const float denom = sqrtf(vi) * inv_sqrt_bc2 + eps;
+    p[i] = pi - step_size * (mi / denom);
+    m[i] = mi;
+    v[i] = vi;
+  }
+}
+
+extern "C" int sfm_adam_l2_step(float* p, float* g, float* m, float* v, long long n, double* ctl, float lr, float one_minus_beta1,
+                                float one_minus_beta2, float eps, float wd, float inv_world, float max_norm, const long long* spans,
+                                const float* touched, int n_params, float* loss_scale, float growth_factor, float backoff_factor,
+                                int growth_interval, void* stream) {
+  if (!p || !g || !m || !v || !ctl) return SFM_ERR_ARG;
+  if ((spans != nullptr) != (touched != nullptr) || (spans && n_params <= 0)) return SFM_ERR_ARG;
+  if (!(growth_factor >= 1.f) || !(backoff_factor > 0.f && backoff_factor <= 1.f) || growth_interval < 1) return SFM_ERR_ARG;
+  if (!(one_minus_beta1 > 0.f && one_minus_beta1 <= 1.f) || !(one_minus_beta2 > 0.f && one_minus_beta2 <= 1.f)) return SFM_ERR_ARG;
+  if (!(lr >= 0.f) || !(wd >= 0.f) || !(eps > 0.f) || !(inv_world > 0.f)) return SFM_ERR_ARG;
+  if (n <= 0) return SFM_ERR_SHAPE;
+  SFM_LAUNCH(adam_l2_prepare_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, ctl, loss_scale, (double)inv_world, (double)max_norm,
+             1.0 - (double)one_minus_beta1, 1.0 - (double)one_minus_beta2, growth_factor, backoff_factor, (float)growth_interval);
+  long long nb = (n + 255) / 256;
+  if (nb > 8192) nb = 8192;
+  SFM_LAUNCH(adam_l2_apply_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, p, (const float*)g, m, v, n, (const double*)ctl,
+             lr, one_minus_beta1, one_minus_beta2, eps, wd, spans, touched, n_params);
+  return SFM_OK;
+}

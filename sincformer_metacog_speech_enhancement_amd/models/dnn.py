@@ -102,6 +102,31 @@ class SpeechEnhancementDNN(HipModule):
         y = self._tail(h, packs).reshape(B, T, self.output_dim)
         return y[0] if two_d else y
 
+    def forward_indexed(self, frames, index):
+        """frames: a training.FrameSet (raw [N, D], bounds, feat_mean / feat_std on the device), index int32 device tensor [M] of
+        packed frames (repeats allowed, < 0: a zero input row) -> fp32 [M, output_dim]: forward(frames.rows(index)[0]) with the
+        context rows gathered, normalised and clipped inside the first layer's launch.  train(), or autograd wanted:
+        train.DnnIndexedFunction (the staged 16-bit rows are kept for the first layer's weight gradient); eval() without
+        autograd: the four inference launches."""
+        self._require_device(frames.raw)
+        if index.dtype != torch.int32 or index.dim() != 1 or index.numel() == 0 or index.device != frames.raw.device:
+            raise ValueError("SpeechEnhancementDNN.forward_indexed: an int32 device index [M] is needed; got %s %s" % (index.dtype, tuple(index.shape)))
+        if frames.raw.shape[1] * (2 * frames.context + 1) != self.input_dim:
+            raise ValueError("SpeechEnhancementDNN.forward_indexed: frames of %d columns and context %d for rows of %d"
+                             % (frames.raw.shape[1], frames.context, self.input_dim))
+        index = index.contiguous()
+        if self.training or self._wants_autograd(frames.raw):
+            from .. import train
+            p = float(self.dropout_rate) if self.training else 0.0
+            seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if p > 0 else 0
+            params = [t for m in self._linears() for t in (m.weight, m.bias)]
+            return train.DnnIndexedFunction.apply(frames.raw, frames.bounds, frames.mean_dev, frames.std_dev, index, frames.context, p, seed,
+                                                  *params)
+        packs = self._packs()
+        h = ops.dnn_layer_indexed(frames.raw, frames.bounds, index, packs[0], context=frames.context, act="relu", mean=frames.mean_dev,
+                                  std=frames.std_dev)
+        return self._tail(h, packs)
+
     def get_layer_params(self):
         return [(m.weight, m.bias) for m in self._linears()]
 

@@ -2650,6 +2650,114 @@ def dnn_act_bwd(dy, saved, act, N, p_drop=0.0, out=None):
 
 
 # ---------------------------------------------------------------------------
+# Training the DNN from a frame set kept at D columns (csrc/features.hip, dnn.hip, optim.hip; training/dnn_training.py)
+# ---------------------------------------------------------------------------
+MSE_GATHER_MAX_BLOCKS = _K["MSE_GATHER_MAX_BLOCKS"]     # sfm_mse_gather_loss: its scratch in doubles
+MOMENTS_CHUNK_ROWS = _K["MOMENTS_CHUNK_ROWS"]           # sfm_context_moments: rows of a chunk at least
+MOMENTS_MAX_CHUNKS = _K["MOMENTS_MAX_CHUNKS"]           # chunks at most: its scratch is (MOMENTS_MAX_CHUNKS + 1) K doubles
+
+
+def _frames_ok(raw, bounds):
+    return raw.dtype == torch.float32 and raw.dim() == 2 and raw.is_contiguous() and raw.numel() > 0 and bounds.dtype == torch.int32 \
+        and bounds.is_contiguous() and tuple(bounds.shape) == (raw.shape[0], 2) and raw.shape[0] < 2 ** 31
+
+
+def context_moments(raw, bounds, ctx):
+    """-> (mean, std) fp32 [D (2 ctx + 1)] of the context rows of the packed frames raw [N, D] fp32 (bounds int32 [N, 2]: each
+    frame's utterance as first and one-past-last packed row), nan / inf read as 0, two fp64 passes, std < 1e-6 -> 1: the
+    statistics of the reference's Dataset without its [N, K] rows.  Four launches, once per frame set."""
+    _need_dev(raw, bounds)
+    L = _lib.load()
+    if not _frames_ok(raw, bounds) or not 0 <= int(ctx) <= 64:
+        _lib.check(-2, "context_moments")
+    N, D = raw.shape
+    K = D * (2 * int(ctx) + 1)
+    mean = torch.empty(K, device=raw.device, dtype=torch.float32)
+    std = torch.empty(K, device=raw.device, dtype=torch.float32)
+    ws = _ws64((MOMENTS_MAX_CHUNKS + 1) * K, raw.device)
+    _call("context_moments", L.sfm_context_moments, (_p(raw), _p(bounds), _p(mean), _p(std), _p(ws), N, D, int(ctx), _stream()),
+          5.0 * N * K, 2.0 * (4.0 * N * D + 8.0 * N) + 8.0 * K, "N%d D%d ctx%d" % (N, D, ctx))
+    return mean, std
+
+
+def dnn_layer_indexed(raw, bounds, index, pw, *, context, act=None, out=None, out_dtype=None, p_drop=0.0, seed=0, mean=None, std=None,
+                      a16_out=None):
+    """out [M, pw.N] = act(A pw.w^T + pw.bias), one sfm_dnn_layer_indexed launch: row m of A is the context row (FeatureExtractor.
+    add_context: clamped to the utterance, normalised with mean / std [pw.K] when given, clipped to +-10) of packed frame index[m]
+    of raw [N, D] (bounds int32 [N, 2]; index int32 [M], < 0: a zero row, repeats allowed).  a16_out [M, round_up(pw.K, 64)] in the
+    compute format (True: allocated): the staged operand rows, zero padded - returned beside out when asked for."""
+    _need_dev(raw, bounds, index, out, mean, std, a16_out if torch.is_tensor(a16_out) else None)
+    L = _lib.load()
+    dt = _state["dtype"]
+    if pw.w.dtype != dt or pw.ksize != 1 or pw.glu:
+        raise RuntimeError("dnn_layer_indexed: a plain Linear pack in the compute format %s is needed (got %s)" % (dt, pw.w.dtype))
+    ok = _frames_ok(raw, bounds) and index.dtype == torch.int32 and index.dim() == 1 and index.is_contiguous() and index.numel() > 0
+    ok = ok and 0 <= int(context) <= 64 and raw.shape[1] >= 8 and raw.shape[1] % 2 == 0 and raw.shape[1] * (2 * int(context) + 1) == pw.K
+    ok = ok and (mean is None) == (std is None) and (mean is None or pw.K <= DNN_CONTEXT_MAX_K)
+    ok = ok and all(s is None or (s.dtype == torch.float32 and s.is_contiguous() and s.numel() == pw.K) for s in (mean, std))
+    if not ok:
+        _lib.check(-2, "dnn_layer_indexed")
+    (N, D), M, ctx = raw.shape, index.numel(), int(context)
+    K64 = round_up(pw.K, 64)
+    want_a16 = a16_out is not None and a16_out is not False
+    if a16_out is True:
+        a16_out = torch.empty(M, K64, device=raw.device, dtype=dt)
+    if want_a16 and (a16_out.dtype != dt or tuple(a16_out.shape) != (M, K64) or not a16_out.is_contiguous()):
+        _lib.check(-2, "dnn_layer_indexed")
+    if out is None:
+        odt = out_dtype or dt
+        out = torch.empty(M, pw.N if odt == torch.float32 else round_up(pw.N, 8), device=raw.device, dtype=odt)
+    if out.dim() != 2 or out.shape[0] != M or out.stride(1) != 1 or out.dtype not in (torch.float32, dt) or out.shape[1] < pw.N or \
+            (out.dtype == torch.float32 and out.shape[1] != pw.N) or act not in DNN_ACT:
+        _lib.check(-2, "dnn_layer_indexed")
+    out_f32 = 1 if out.dtype == torch.float32 else 0
+    osz = 4 if out_f32 else 2
+    # each gathered raw row read once per context column block (2 ctx + 1 times D floats per operand row), index and bounds once
+    abytes = 4.0 * M * pw.K + 12.0 * M + (8.0 * pw.K if mean is not None else 0.0) + (2.0 * M * K64 if want_a16 else 0.0)
+    _call("dnn_layer", L.sfm_dnn_layer_indexed,
+          (_p(raw), _p(bounds), _p(index), _p(mean), _p(std), _p(pw.w), _p(pw.bias), _p(out), _p(a16_out) if want_a16 else None, M, pw.N,
+           pw.K, N, D, ctx, pw.Kpad, pw.Npad, out.stride(0), K64 if want_a16 else 0, out_f32, DNN_ACT[act], float(p_drop),
+           int(seed) & 0xffffffff, _dt(), _stream()),
+          2.0 * M * pw.N * pw.K, abytes + 2.0 * pw.Npad * pw.Kpad + 4.0 * pw.N + float(osz) * M * (pw.N if out_f32 else out.shape[1]),
+          "M%d N%d K%d a3 act%d o%d%s" % (M, pw.N, pw.K, DNN_ACT[act], osz, " drop" if p_drop > 0 else ""))
+    return (out, a16_out) if want_a16 else out
+
+
+def mse_gather_loss(y, mask, index, *, loss_scale=None, need_dz=True, rec=None, ctl=None, loss=None, dz=None):
+    """nn.MSELoss()(y, clip(nan_to_num(mask[index]), 0, 1)) of y fp32 [M, C] against the rows index (int32 [M]) of mask fp32 [N, C]
+    -> (loss fp32 [1], dz or None), two launches.  dz [M, round_up(C, 64)] in the compute format = S 2 (y - t) / (M C) y (1 - y),
+    zero padded: the output layer's pre-activation cotangent as the gradient GEMMs read it, S = loss_scale[0] on the device
+    (optim.DynamicLossScale.state; None: 1).  rec: 4 doubles {sum of finite losses, finite batches, non-finite batches, last loss},
+    updated in place; ctl: an optimiser's control block, ctl[2] is raised when the loss is not finite."""
+    _need_dev(y, mask, index, loss_scale, rec, ctl, loss, dz)
+    L = _lib.load()
+    dt = _state["dtype"]
+    ok = y.dtype == torch.float32 and y.dim() == 2 and y.is_contiguous() and y.numel() > 0 and mask.dtype == torch.float32 and mask.dim() == 2
+    ok = ok and mask.is_contiguous() and mask.shape[0] > 0 and mask.shape[1] == y.shape[1] and index.dtype == torch.int32
+    ok = ok and index.dim() == 1 and index.is_contiguous() and index.numel() == y.shape[0]
+    ok = ok and (loss_scale is None or (loss_scale.dtype == torch.float32 and loss_scale.numel() >= 1))
+    ok = ok and (rec is None or (rec.dtype == torch.float64 and rec.numel() == 4 and rec.is_contiguous()))
+    ok = ok and (ctl is None or (ctl.dtype == torch.float64 and ctl.numel() >= 8 and ctl.is_contiguous()))
+    if not ok:
+        _lib.check(-2, "mse_gather_loss")
+    M, C = y.shape
+    Cz = round_up(C, 64)
+    if need_dz and dz is None:
+        dz = torch.empty(M, Cz, device=y.device, dtype=dt)
+    if not need_dz:
+        dz = None
+    if dz is not None and (dz.dtype != dt or tuple(dz.shape) != (M, Cz) or not dz.is_contiguous()):
+        _lib.check(-2, "mse_gather_loss")
+    if loss is None:
+        loss = torch.empty(1, device=y.device, dtype=torch.float32)
+    ws = _ws64(MSE_GATHER_MAX_BLOCKS, y.device)
+    _call("mse_loss", L.sfm_mse_gather_loss, (_p(y), _p(mask), _p(index), _p(loss_scale), _p(dz), Cz, _p(loss), _p(rec), _p(ctl), _p(ws),
+                                              M, C, mask.shape[0], _dt(), _stream()),
+          (8.0 if need_dz else 3.0) * M * C, 8.0 * M * C + 4.0 * M + (2.0 * M * Cz if need_dz else 0.0), "M%d C%d dz%d" % (M, C, int(need_dz)))
+    return loss, dz
+
+
+# ---------------------------------------------------------------------------
 # Mask to waveform (csrc/resynth.hip; steps 2-4 of enhance_signal, training/pipeline.py:877-934)
 # ---------------------------------------------------------------------------
 RESYNTH_TILE_FRAMES = _K["RESYNTH_TILE_FRAMES"]    # frames a workgroup computes; it owns one output hop fewer

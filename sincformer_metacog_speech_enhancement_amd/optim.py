@@ -148,3 +148,37 @@ class FlatAdamW:
         """host sync: {'step', 'grad_norm', 'skipped'} of the last step."""
         c = self.ctl.cpu()
         return {"step": int(c[0]), "grad_norm": float(c[7]), "skipped": bool(c[4] > 0)}
+
+
+class FlatAdam(FlatAdamW):
+    """torch.optim.Adam(lr, betas, eps, weight_decay) behind clip_grad_norm_(max_norm): the optimiser of the reference's DNN
+    training (training/pipeline.py:563-567, 664-669) on FlatAdamW's flat buffers, synchroniser and control block
+    (csrc/optim.hip, sfm_adam_l2_step).  The decay is L2 added to the gradient after the clip - the norm in stats() is that of the
+    unscaled gradient without it - and eps stands outside the square root of the bias-corrected v.  `lr` is a per-call argument:
+    the scheduler stays on the host.  The skip flag ctl[2] is raised either from `loss` (as FlatAdamW) or, when no loss is
+    handed over, by a kernel that wrote it on the device (ops.mse_gather_loss); a skipped step leaves p, m, v and the step count
+    alone and backs the scaler's scale off."""
+
+    def __init__(self, params, lr=None, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-5, max_norm=5.0, sync=None,
+                 bucket_bytes=16 << 20, overlap=True, steal_grads=None):
+        from . import config
+        super().__init__(params, lr=lr or config.DNN_LEARNING_RATE, betas=betas, eps=eps, weight_decay=weight_decay, max_norm=max_norm,
+                         sync=sync, bucket_bytes=bucket_bytes, overlap=overlap, steal_grads=steal_grads)
+
+    def step(self, loss=None, grad_scale=1.0, lr=None, scaler=None):
+        self.sync.finish(loss)
+        L = ops._lib.load()
+        n = self.sync.n
+        ws = ops._ws(L.sfm_sumsq_ws_doubles(n), self.flat_p.device, torch.float64)
+        ops._call("optim", L.sfm_sumsq, (ops._p(self.sync.flat), n, self.ctl[1:].data_ptr(), ops._p(ws), ops._stream()), 0.0, 4.0 * n)
+        if loss is not None:
+            self.ctl[2:3].copy_(self.sync.flag.double())
+        ls = scaler._alloc(self.flat_p.device) if scaler is not None and scaler.enabled else None
+        growth, backoff, interval = (scaler.growth_factor, scaler.backoff_factor, scaler.growth_interval) if ls is not None else (2.0, 0.5, 2000)
+        ops._call("optim", L.sfm_adam_l2_step,
+                  (ops._p(self.flat_p), ops._p(self.sync.flat), ops._p(self.m), ops._p(self.v), n, ops._p(self.ctl),
+                   float(lr if lr is not None else self.lr), 1.0 - self.betas[0], 1.0 - self.betas[1], self.eps, self.weight_decay,
+                   1.0 / (float(grad_scale) * self.sync.world), float(self.max_norm or 0.0), ops._p(self.spans),
+                   ops._p(self.sync.touched_dev), len(self.sync.params), ops._p(ls), growth, backoff, interval, ops._stream()),
+                  0.0, 28.0 * n)
+        self._bump_versions()

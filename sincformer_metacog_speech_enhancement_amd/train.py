@@ -455,6 +455,65 @@ class DnnFunction(torch.autograd.Function):
         return (dx.to(xdt) if want_dx else None, None, None) + tuple(grads)
 
 
+def dnn_backward_from_dz(acts, w32, dz, p):
+    """DnnFunction's backward from the output layer's pre-activation cotangent on: dz [M, round_up(out, 64)] 16-bit, zero padded
+    (ops.dnn_act_bwd or ops.mse_gather_loss) -> [dW0, db0, dW1, db1, ...] fp32; no input gradient."""
+    grads = [None] * (2 * len(w32))
+    for l in range(len(w32) - 1, -1, -1):
+        dx, grads[2 * l], grads[2 * l + 1] = _linear_bwd16(dz, w32[l].shape[0], acts[l], w32[l], want_dx=l > 0)
+        if l > 0:
+            dz = ops.dnn_act_bwd(dx, acts[l], "relu", w32[l - 1].shape[0], p_drop=p)
+    return grads
+
+
+class DnnIndexedFunction(torch.autograd.Function):
+    """DnnFunction on an index list: y[M, out] = the network on the context rows of the packed frames index [M] of a
+    training.FrameSet (raw [N, D], bounds [N, 2], mean, std [D (2 ctx + 1)]), which are gathered, normalised and clipped while the
+    first layer stages them (ops.dnn_layer_indexed); the same launch writes the staged 16-bit rows, acts[0], that the first
+    layer's weight gradient reads, so neither the fp32 [M, in] rows nor their conversion exists.  Saved set and backward as
+    DnnFunction from acts[0] on; there is no input gradient.  step_gradients(y, dz) is the backward from a cotangent that is
+    already the output layer's dz (ops.mse_gather_loss), outside the autograd engine."""
+
+    @staticmethod
+    def forward(ctx, raw, bounds, mean, std, index, context, p, seed, *params):
+        w32 = [_f32(w) for w in params[0::2]]
+        seeds = _Seeds(seed)
+        s = seeds.next() if p > 0 else 0
+        layer_seeds = [s]
+        h, a16 = ops.dnn_layer_indexed(raw, bounds, index, ops.pack_linear(w32[0], _f32(params[1]), k_pad_to=ops.round_up(w32[0].shape[1], 8)),
+                                       context=context, act="relu", p_drop=p, seed=s, mean=mean, std=std, a16_out=True)
+        acts = [a16, h]
+        for l, w in enumerate(w32[1:-1], start=1):
+            s = seeds.next() if p > 0 else 0
+            layer_seeds.append(s)
+            h = ops.dnn_layer(h, ops.pack_linear(w, _f32(params[2 * l + 1]), k_pad_to=ops.round_up(w.shape[1], 8)), act="relu",
+                              p_drop=p, seed=s)
+            acts.append(h)
+        y = ops.dnn_layer(h, ops.pack_linear(w32[-1], _f32(params[-1]), k_pad_to=ops.round_up(w32[-1].shape[1], 8)), act="sigmoid",
+                          out_dtype=torch.float32)
+        ctx.saved = (acts, y, w32)
+        ctx.meta = (p, tuple(layer_seeds), torch.float32, tuple(t.dtype for t in params), False)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        acts, y, w32 = ctx.saved
+        p, pdt = ctx.meta[0], ctx.meta[3]
+        ctx.saved = None
+        dz = ops.dnn_act_bwd(_rows32(dy), y, "sigmoid", w32[-1].shape[0])
+        grads = dnn_backward_from_dz(acts, w32, dz, p)
+        return (None,) * 8 + tuple(g.to(dt) for g, dt in zip(grads, pdt))
+
+    @staticmethod
+    def step_gradients(y, dz):
+        """y: the node's result (still attached); dz: ops.mse_gather_loss's -> the fp32 parameter gradients, in parameter order.
+        The node's saved tensors are released, as by backward."""
+        fn = y.grad_fn
+        acts, _, w32 = fn.saved
+        fn.saved = None
+        return dnn_backward_from_dz(acts, w32, dz, fn.meta[0])
+
+
 class PolarMaskFunction(torch.autograd.Function):
     """bounded polar mask applied to the noisy STFT (training/conformer_pipeline.py:283-295):
     logits [M, 2F] (magnitude | phase) -> enh_real, enh_imag, mask_mag (monitoring only, not differentiable)."""

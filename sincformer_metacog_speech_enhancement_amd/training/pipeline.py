@@ -4,7 +4,8 @@ dnn_frame_pairs gives the (features, mask) pair of a batch of utterances without
 dnn_estimate_mask the estimator's side of enhance_signal (:846-875, its step 1): features, context and models.SpeechEnhancementDNN in
 one pass; resynthesize its steps 2-4 (:877-934): the STFT of the noisy signal, the mask interpolated onto the STFT bins, the masked
 irfft and the overlap-add in one launch; dnn_enhance_signal the two together; rbm_pretrain is _rbm_pretrain (:712-759), the layer-wise
-RBM pre-training of the DNN on models.rbm.  The Dataset is not mirrored; its feature normalisation is an option of add_context."""
+RBM pre-training of the DNN on models.rbm.  The Dataset and the training loop are in training/dnn_training.py (FrameSet,
+TrainingPipeline); the Dataset's feature normalisation is also an option of add_context."""
 import numpy as np
 import torch
 
