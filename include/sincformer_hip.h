@@ -704,7 +704,17 @@ int sfm_adv_head_bwd(const void* a16, const void* w16, const float* out, const f
  *   (yr, yi) = C + scale[b] N, the spectrum of the mix (the STFT is linear).  kind 0: no mask (mask may be NULL); 1: the IRM
  *   of |C| and |s N| with exponent p; 2: the PCIRM of |C|, |s N|, |Y| with rho_s, rho_n as sfm_mask_corr gives them for
  *   those magnitudes and phi1 = arg C - arg Y, phi2 = arg N - arg Y, whose cosines are taken as Re(C conj Y) / (|C| |Y|) (a zero
- *   counts as phase 0); 3: that PCIRM quantised by `table` (sfm_mask_quantize's, M steps). */
+ *   counts as phase 0); 3: that PCIRM quantised by `table` (sfm_mask_quantize's, M steps).
+ * sfm_mix_scale_varlen: sfm_mix_scale on packed utterances.  Utterance u is packed[utt_off[u] .. utt_off[u + 1]), utt_off int32
+ *   [n_utt + 1] ascending from 0 (clamped to 0 .. total, the sample count of `packed`); its length is its own, any alignment.  The
+ *   same chunk partials, ordered fold and formula; the grid is the chunks of max_len (the longest utterance) x n_utt, samples of
+ *   an utterance beyond max_len are not summed.  ws: sfm_mix_scale_varlen_ws_doubles(n_utt, max_len) doubles - an int, which is
+ *   SFM_ERR_SHAPE where the entry point refuses: n_utt outside 1 .. 65535, max_len < 1, more than 2^31 - 1 doubles.
+ * sfm_wave_batch: out [2, B, L] from index int32 [B] into a packed set (packed, utt_off, noise_ids [n_utt], scale [n_utt]).  With
+ *   u = index[b]: out[0, b, j] = packed[utt_off[u] + j] + scale[u] * noise[j mod Ln], out[1, b, j] = packed[utt_off[u] + j] for
+ *   j < min(length of u, L), and 0 from there on; both rows are 0 where u is outside 0 .. n_utt - 1 (-1: an empty row).  Every
+ *   element is written.  A mixed row has the bits sfm_mix_apply gives for the padded utterance with that scale.  2 B L <= 2^31 - 1,
+ *   B <= 65535. */
 int sfm_mask_irm(const float* clean_mag, const float* noise_mag, float* out, long long n, float p, float eps, void* stream);
 int sfm_mask_corr(const float* noisy, const float* clean, const float* noise, float* rho_s, float* rho_n, long long n, float eps,
                   void* stream);
@@ -716,6 +726,13 @@ int sfm_mix_scale(const float* clean, const float* bank, const int* bank_off, co
                   const int* lengths, double* ws, float* scale, int B, int L, int n_noise, void* stream);
 int sfm_mix_apply(const float* clean, const float* bank, const int* bank_off, const int* noise_ids, const int* lengths,
                   const float* scale, float* noisy, float* noise_rows, int B, int L, int n_noise, void* stream);
+int sfm_mix_scale_varlen_ws_doubles(int n_utt, int max_len);
+int sfm_mix_scale_varlen(const float* packed, const int* utt_off, const float* bank, const int* bank_off, const int* noise_ids,
+                         const float* snr_db, double* ws, float* scale, int n_utt, int max_len, int total, int n_noise,
+                         void* stream);
+int sfm_wave_batch(const float* packed, const int* utt_off, const float* bank, const int* bank_off, const int* noise_ids,
+                   const float* scale, const int* index, float* out, int B, int L, int n_utt, int total, int n_noise,
+                   void* stream);
 int sfm_curriculum_mask(const float* cr, const float* ci, const float* nr, const float* ni, const float* scale,
                         const double* table, float* yr, float* yi, float* mask, int B, int T, int F, int kind, float p, float eps,
                         int M, void* stream);

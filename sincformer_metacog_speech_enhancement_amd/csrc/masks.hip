@@ -12,6 +12,9 @@
 //              mix_scale_kernel: ONE workgroup folds the chunks of each utterance in index order and writes scale;
 //              mix_apply_kernel: noisy = clean + scale * noise (0 at and beyond the utterance's length), and on request the
 //              unscaled noise row the utterance was mixed with (the operand of the noise STFT).
+// packed set   training.WaveformSet keeps its clean utterances back to back: mix_power_varlen_kernel / mix_scale_varlen_kernel are
+//              the two mix kernels above on packed[off[u] .. off[u + 1]), and wave_batch_kernel gathers the rows of an index list,
+//              mixes them and writes the step's (noisy, clean) pair in one launch.
 #include "sfm_common.h"
 #include <math.h>
 
@@ -227,20 +230,17 @@ static __device__ __forceinline__ RowSplit row_split(long long first, int count,
   return s;
 }
 
-__global__ __launch_bounds__(256) void mix_power_kernel(const float* __restrict__ clean, const float* __restrict__ bank,
-                                                        const int* __restrict__ off, const int* __restrict__ ids,
-                                                        const int* __restrict__ lengths, double* __restrict__ part, int L,
-                                                        int n_noise, int vec) {
+// one workgroup's (clean^2, noise^2) partial: the samples [j0, j0 + SFM_MIX_CHUNK) below r.len of the utterance `row`, whose sample
+// 0 is element `first` of a buffer that is 16-byte aligned when vec
+static __device__ __forceinline__ void mix_power_chunk(const float* __restrict__ row, long long first, const MixRow r, int j0,
+                                                       double* __restrict__ o, int vec) {
   __shared__ double red[8];
-  const int b = blockIdx.y, tid = threadIdx.x;
-  const MixRow r = mix_row(bank, off, ids, lengths, b, L, n_noise);
-  const int j0 = blockIdx.x * SFM_MIX_CHUNK;
+  const int tid = threadIdx.x;
   int j1 = j0 + SFM_MIX_CHUNK;
   if (j1 > r.len) j1 = r.len;
   double pc = 0.0, pn = 0.0;
   if (j1 > j0) {
-    const float* row = clean + (long long)b * L;
-    const RowSplit s = row_split((long long)b * L + j0, j1 - j0, vec);
+    const RowSplit s = row_split(first + j0, j1 - j0, vec);
     for (int q = tid; q < s.nq; q += 256) {
       const int j = j0 + s.head + 4 * q;
       const f32x4 c = *reinterpret_cast<const f32x4*>(row + j);
@@ -268,10 +268,53 @@ __global__ __launch_bounds__(256) void mix_power_kernel(const float* __restrict_
   }
   __syncthreads();
   if (tid == 0) {
-    double* o = part + 2 * ((long long)b * gridDim.x + blockIdx.x);
     o[0] = (red[0] + red[1]) + (red[2] + red[3]);
     o[1] = (red[4] + red[5]) + (red[6] + red[7]);
   }
+}
+
+__global__ __launch_bounds__(256) void mix_power_kernel(const float* __restrict__ clean, const float* __restrict__ bank,
+                                                        const int* __restrict__ off, const int* __restrict__ ids,
+                                                        const int* __restrict__ lengths, double* __restrict__ part, int L,
+                                                        int n_noise, int vec) {
+  const int b = blockIdx.y;
+  const MixRow r = mix_row(bank, off, ids, lengths, b, L, n_noise);
+  mix_power_chunk(clean + (long long)b * L, (long long)b * L, r, blockIdx.x * SFM_MIX_CHUNK,
+                  part + 2 * ((long long)b * gridDim.x + blockIdx.x), vec);
+}
+
+// The packed form: utterance u is packed[uoff[u] .. uoff[u + 1]) (offsets clamped to 0..total and to ascending), its length its own;
+// the grid is the chunks of the longest utterance x the utterances, a chunk past an utterance's end writes a pair of zeros.
+struct PackedRow {
+  int start, len;
+};
+static __device__ __forceinline__ PackedRow packed_row(const int* __restrict__ uoff, int u, int total) {
+  int s = uoff[u], e = uoff[u + 1];
+  s = s < 0 ? 0 : (s > total ? total : s);
+  e = e < s ? s : (e > total ? total : e);
+  PackedRow p;
+  p.start = s, p.len = e - s;
+  return p;
+}
+static __device__ __forceinline__ MixRow packed_mix_row(const float* __restrict__ bank, const int* __restrict__ off, int id,
+                                                        int len, int n_noise) {
+  id = id < 0 ? 0 : (id >= n_noise ? n_noise - 1 : id);
+  MixRow r;
+  r.noise = bank + off[id];
+  r.Ln = off[id + 1] - off[id];
+  if (r.Ln < 0) r.Ln = 0;
+  r.len = r.Ln > 0 ? len : 0;
+  return r;
+}
+
+__global__ __launch_bounds__(256) void mix_power_varlen_kernel(const float* __restrict__ packed, const int* __restrict__ uoff,
+                                                               const float* __restrict__ bank, const int* __restrict__ off,
+                                                               const int* __restrict__ ids, double* __restrict__ part, int total,
+                                                               int n_noise, int vec) {
+  const int u = blockIdx.y;
+  const PackedRow p = packed_row(uoff, u, total);
+  const MixRow r = packed_mix_row(bank, off, ids[u], p.len, n_noise);
+  mix_power_chunk(packed + p.start, p.start, r, blockIdx.x * SFM_MIX_CHUNK, part + 2 * ((long long)u * gridDim.x + blockIdx.x), vec);
 }
 
 // one workgroup: utterance b's NC chunk sums in index order, then scale = sqrt(Pc / (Pn 10^(snr / 10))), P = mean + 1e-10
@@ -289,6 +332,24 @@ __global__ __launch_bounds__(256) void mix_scale_kernel(const double* __restrict
     len = len < 1 ? 1 : (len > L ? L : len);
     const double pc = sc / (double)len + 1e-10, pn = sn / (double)len + 1e-10;
     scale[b] = (float)sqrt(pc / (pn * pow(10.0, (double)snr_db[b] / 10.0)));
+  }
+}
+
+// the same fold and formula for packed utterances (a length below 1 counts as 1, as above)
+__global__ __launch_bounds__(256) void mix_scale_varlen_kernel(const double* __restrict__ part, const float* __restrict__ snr_db,
+                                                               const int* __restrict__ uoff, float* __restrict__ scale, int U,
+                                                               int total, int NC) {
+  for (int u = threadIdx.x; u < U; u += 256) {
+    double sc = 0.0, sn = 0.0;
+    const double* p = part + 2 * (long long)u * NC;
+    for (int c = 0; c < NC; ++c) {
+      sc += p[2 * c];
+      sn += p[2 * c + 1];
+    }
+    int len = packed_row(uoff, u, total).len;
+    len = len < 1 ? 1 : len;
+    const double pc = sc / (double)len + 1e-10, pn = sn / (double)len + 1e-10;
+    scale[u] = (float)sqrt(pc / (pn * pow(10.0, (double)snr_db[u] / 10.0)));
   }
 }
 
@@ -335,6 +396,84 @@ __global__ __launch_bounds__(256) void mix_apply_kernel(const float* __restrict_
     }
     out[j] = y;
     if (nrow) nrow[j] = z;
+  }
+}
+
+// From an index list to a training step's two waveforms: out [2, B, L], plane 0 (blockIdx.z) = the mix of utterance index[b] of a
+// packed set, plane 1 its clean samples, both 0 from the utterance's length on and in a row whose index is outside 0 .. U - 1
+// (-1: dnn_layer_indexed's empty row).  The packed source row starts at any 4-byte boundary, so it is read with 4-byte-aligned
+// 16-byte loads (global memory takes them); the stores are 16-byte ones where the OUTPUT row allows them (row_split).  A mixed
+// sample is mix_apply_kernel's expression, so a row has that kernel's bits for the padded utterance.
+typedef float f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
+
+__global__ __launch_bounds__(256) void wave_batch_kernel(const float* __restrict__ packed, const int* __restrict__ uoff,
+                                                         const float* __restrict__ bank, const int* __restrict__ off,
+                                                         const int* __restrict__ ids, const float* __restrict__ scale,
+                                                         const int* __restrict__ index, float* __restrict__ out, int B, int L, int U,
+                                                         int total, int n_noise, int vec) {
+  const int b = blockIdx.y, tid = threadIdx.x, mixed = blockIdx.z == 0;
+  const int u = index[b];
+  const float* row = packed;
+  MixRow r;
+  r.noise = bank, r.Ln = 0, r.len = 0;
+  int len = 0;                           // samples of the utterance that the row holds
+  float sc = 0.f;
+  if (u >= 0 && u < U) {
+    const PackedRow p = packed_row(uoff, u, total);
+    len = p.len > L ? L : p.len;
+    row = packed + p.start;
+    if (mixed) {
+      r = packed_mix_row(bank, off, ids[u], len, n_noise);
+      sc = scale[u];
+      len = r.len;                       // (an empty noise entry: zeros, as mix_apply_kernel writes them)
+    }
+  }
+  const int j0 = blockIdx.x * SFM_MIX_CHUNK;
+  int j1 = j0 + SFM_MIX_CHUNK;
+  if (j1 > L) j1 = L;
+  const long long base = ((long long)blockIdx.z * B + b) * L;
+  float* o = out + base;
+  const RowSplit s = row_split(base + j0, j1 - j0, vec);
+  for (int q = tid; q < s.nq; q += 256) {
+    const int j = j0 + s.head + 4 * q;
+    f32x4 y = {0.f, 0.f, 0.f, 0.f};
+    if (j < len) {
+      f32x4 c = {0.f, 0.f, 0.f, 0.f};
+      if (j + 4 <= len) {
+        c = *reinterpret_cast<const f32x4_a4*>(row + j);
+      } else {                           // the utterance's last quad: what follows it belongs to the next one, or to nobody
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (j + k < len) c[k] = row[j + k];
+      }
+      if (mixed) {
+        int w = mix_wrap(j, r.Ln);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if (j + k < len) {
+            const float z = r.noise[w];
+            y[k] = c[k] + sc * z;
+          }
+          w = w + 1 == r.Ln ? 0 : w + 1;
+        }
+      } else {
+        y = c;
+      }
+    }
+    *reinterpret_cast<f32x4*>(o + j) = y;
+  }
+  for (int t = tid; t < s.head + s.rest; t += 256) {
+    const int j = t < s.head ? j0 + t : j0 + 4 * s.nq + t;
+    float y = 0.f;
+    if (j < len) {
+      if (mixed) {
+        const float z = r.noise[mix_wrap(j, r.Ln)];
+        y = row[j] + sc * z;
+      } else {
+        y = row[j];
+      }
+    }
+    o[j] = y;
   }
 }
 
@@ -412,6 +551,38 @@ extern "C" int sfm_mix_apply(const float* clean, const float* bank, const int* b
   const int vec = al16(clean) && al16(noisy) && al16(noise_rows);
   SFM_LAUNCH(mix_apply_kernel, dim3((unsigned)NC, (unsigned)B), dim3(256), 0, (hipStream_t)stream, clean, bank, bank_off, noise_ids,
              lengths, scale, noisy, noise_rows, L, n_noise, vec);
+  return SFM_OK;
+}
+
+// ws of sfm_mix_scale_varlen: a pair of partials per utterance and chunk of the LONGEST utterance.  An int like a status: the
+// count is refused (SFM_ERR_SHAPE) where it leaves 1 .. 2^31 - 1, as the entry point refuses that shape.
+extern "C" int sfm_mix_scale_varlen_ws_doubles(int n_utt, int max_len) {
+  if (n_utt <= 0 || max_len <= 0 || n_utt > 65535) return SFM_ERR_SHAPE;
+  const long long n = 2LL * n_utt * mix_chunks(max_len);
+  return n > 2147483647LL ? SFM_ERR_SHAPE : (int)n;
+}
+
+extern "C" int sfm_mix_scale_varlen(const float* packed, const int* utt_off, const float* bank, const int* bank_off,
+                                    const int* noise_ids, const float* snr_db, double* ws, float* scale, int n_utt, int max_len,
+                                    int total, int n_noise, void* stream) {
+  if (!packed || !utt_off || !bank || !bank_off || !noise_ids || !snr_db || !ws || !scale) return SFM_ERR_ARG;
+  if (total <= 0 || n_noise <= 0 || sfm_mix_scale_varlen_ws_doubles(n_utt, max_len) < 0) return SFM_ERR_SHAPE;
+  const int NC = mix_chunks(max_len);
+  hipStream_t st = (hipStream_t)stream;
+  SFM_LAUNCH(mix_power_varlen_kernel, dim3((unsigned)NC, (unsigned)n_utt), dim3(256), 0, st, packed, utt_off, bank, bank_off,
+             noise_ids, ws, total, n_noise, (int)al16(packed));
+  SFM_LAUNCH(mix_scale_varlen_kernel, dim3(1), dim3(256), 0, st, ws, snr_db, utt_off, scale, n_utt, total, NC);
+  return SFM_OK;
+}
+
+extern "C" int sfm_wave_batch(const float* packed, const int* utt_off, const float* bank, const int* bank_off,
+                              const int* noise_ids, const float* scale, const int* index, float* out, int B, int L, int n_utt,
+                              int total, int n_noise, void* stream) {
+  if (!packed || !utt_off || !bank || !bank_off || !noise_ids || !scale || !index || !out) return SFM_ERR_ARG;
+  if (B <= 0 || L <= 0 || n_utt <= 0 || total <= 0 || n_noise <= 0 || B > 65535) return SFM_ERR_SHAPE;
+  if (2LL * B * L > 2147483647LL) return SFM_ERR_SHAPE;
+  SFM_LAUNCH(wave_batch_kernel, dim3((unsigned)mix_chunks(L), (unsigned)B, 2), dim3(256), 0, (hipStream_t)stream, packed, utt_off,
+             bank, bank_off, noise_ids, scale, index, out, B, L, n_utt, total, n_noise, (int)al16(out));
   return SFM_OK;
 }
 

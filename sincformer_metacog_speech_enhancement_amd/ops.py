@@ -1202,6 +1202,59 @@ def mix_apply(clean, bank, bank_off, noise_ids, scale, lengths=None, want_rows=F
     return noisy, rows
 
 
+def _packed_columns(name, packed, utt_off, bank, bank_off, noise_ids, *per_utterance):
+    """the packed forms' operands have the size and type the kernels assume: refused (-2) before the call otherwise -> utterances"""
+    U = utt_off.numel() - 1
+    ok = packed.dim() == 1 and packed.dtype == torch.float32 and packed.is_contiguous() and 0 < packed.numel() < 2 ** 31
+    ok = ok and utt_off.dtype == torch.int32 and utt_off.dim() == 1 and U >= 1 and utt_off.is_contiguous()
+    ok = ok and bank.dtype == torch.float32 and bank_off.dtype == torch.int32 and bank_off.numel() >= 2
+    ok = ok and noise_ids.dtype == torch.int32 and noise_ids.numel() == U and noise_ids.is_contiguous()
+    ok = ok and all(t.dtype == torch.float32 and t.numel() == U and t.is_contiguous() for t in per_utterance)
+    if not ok:
+        _lib.check(-2, name)
+    return U
+
+
+def mix_scale_varlen(packed, utt_off, bank, bank_off, noise_ids, snr_db, max_len):
+    """mix_scale on packed utterances: packed fp32 [total], utterance u = packed[utt_off[u] : utt_off[u + 1]] (int32 [U + 1]);
+    noise_ids int32 [U], snr_db fp32 [U]; max_len = the longest utterance (a host int) -> scale [U] fp32.  Two launches per 65535
+    utterances: fp64 chunk sums, then the ordered fold."""
+    _need_dev(packed, utt_off, bank, bank_off, noise_ids, snr_db)
+    L = _lib.load()
+    U = _packed_columns("mix_scale_varlen", packed, utt_off, bank, bank_off, noise_ids, snr_db)
+    total, n_noise, max_len = packed.numel(), bank_off.numel() - 1, int(max_len)
+    scale = torch.empty(U, device=packed.device, dtype=torch.float32)
+    for a in range(0, U, 65535):                    # (the utterances are the grid's y dimension)
+        n = min(65535, U - a)
+        need = L.sfm_mix_scale_varlen_ws_doubles(n, max_len)
+        if need < 0:
+            _lib.check(need, "mix_scale_varlen")
+        ws = _ws64(need, packed.device)
+        _call("mix", L.sfm_mix_scale_varlen, (_p(packed), _p(utt_off[a:]), _p(bank), _p(bank_off), _p(noise_ids[a:]), _p(snr_db[a:]),
+                                              _p(ws), _p(scale[a:]), n, max_len, total, n_noise, _stream()),
+              4.0 * total, 8.0 * total, "scale_varlen U%d L%d" % (n, max_len))
+    return scale
+
+
+def wave_batch(packed, utt_off, bank, bank_off, noise_ids, scale, index, L_out, out=None):
+    """index int32 [B] into a packed set -> out fp32 [2, B, L_out]: out[0] the mixes packed[u] + scale[u] * noise (tiled / cut), out[1]
+    the clean rows, both zero-padded; an index outside 0 .. U - 1 (-1) gives zero rows.  One launch, every element written."""
+    _need_dev(packed, utt_off, bank, bank_off, noise_ids, scale, index, out)
+    L = _lib.load()
+    U = _packed_columns("wave_batch", packed, utt_off, bank, bank_off, noise_ids, scale)
+    B, L_out = index.numel(), int(L_out)
+    if index.dtype != torch.int32 or index.dim() != 1 or not index.is_contiguous() or B == 0:
+        _lib.check(-2, "wave_batch")
+    if out is None:
+        out = torch.empty(2, B, L_out, device=packed.device, dtype=torch.float32)
+    elif out.shape != (2, B, L_out) or out.dtype != torch.float32 or not out.is_contiguous():
+        _lib.check(-2, "wave_batch")
+    _call("mix", L.sfm_wave_batch, (_p(packed), _p(utt_off), _p(bank), _p(bank_off), _p(noise_ids), _p(scale), _p(index), _p(out), B,
+                                    L_out, U, packed.numel(), bank_off.numel() - 1, _stream()),
+          2.0 * B * L_out, 16.0 * B * L_out, "wave_batch B%d L%d" % (B, L_out))
+    return out
+
+
 def curriculum_mask(cr, ci, nr, ni, scale, kind=None, p=0.5, eps=1e-10, table=None, M=0):
     """spectra [B, T, F] of the clean utterances and of the noise rows, scale [B] -> (yr, yi, mask or None): the spectrum of
     the mix and the mask target `kind` (MASK_KINDS), one launch"""

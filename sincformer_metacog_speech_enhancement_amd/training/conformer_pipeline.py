@@ -3,8 +3,9 @@
 ConformerPipeline._compute_loss :539, _save_best :611, save_model :618, load_model :628, enhance_signal :653) and the
 north-star agent composition (EnhancementPath; SURVEY.md §3.3 with the glue of DESIGN.md), and of what its data set does
 to a batch (_add_noise_at_snr :142, the assignment of WaveformDataset :162-171) as device passes: mix_at_snr, mix_batch,
-curriculum_batch.
-The data loaders / optimiser loop of the reference are out of scope.
+curriculum_batch; WaveformDataset :153-189 as WaveformSet, a waveform set kept on the device, and train :403-484 with its warm-up
+and cosine schedule (WarmupCosineRule).
+The file search, audio loading and resampling of the reference (prepare_data) are out of scope.
 """
 import math
 import os
@@ -181,6 +182,139 @@ def curriculum_batch(clean, noise_bank_, snr_levels, mask_type, first_index=0, l
                 else (None, 0))
     yr, yi, mask = ops.curriculum_mask(cr, ci, nr, ni, scale, mask_type, p=p, table=table, M=M)
     return CurriculumBatch(noisy, yr, yi, cr, ci, mask, scale)
+
+
+class _Batches:
+    """the (noisy, clean) pairs of one pass over a WaveformSet in slices of `index`; iterating enqueues one launch per pair"""
+
+    def __init__(self, wave_set, index, batch_size, drop_last):
+        self.set, self.index, self.batch_size = wave_set, index, int(batch_size)
+        n = index.numel()
+        self.count = n // self.batch_size if drop_last else -(-n // self.batch_size)
+
+    def __len__(self):
+        return self.count
+
+    def __iter__(self):
+        for k in range(self.count):
+            yield self.set.batch(self.index[k * self.batch_size:(k + 1) * self.batch_size])
+
+
+class WaveformSet:
+    """WaveformDataset (training/conformer_pipeline.py:153-189) on the device.  clean_list: the data set's files in order, each a
+    1-D numpy array or tensor (host or device), or None for a file that failed to load; noise_signals: 1-D device tensors as a
+    dict or list in the reference's key order, or a NoiseBank.  An entry is kept when it has config.FRAME_SIZE * 4 samples; entry
+    i - its position in clean_list, skipped entries counted - is mixed with noise i % n_noise at snr_levels[i % len(snr_levels)].
+    Held: the kept clean utterances cut to max_len, back to back (`clean` fp32, `offsets` int32 [N + 1]), `file_index` (host
+    list), `noise_ids` int32 [N], `scale` fp32 [N] and the NoiseBank: 4 bytes a sample, the mixes are never stored.  `scale` is
+    taken once, here, over each utterance's FULL length (ops.mix_scale_varlen), as the reference mixes before it cuts.
+    batch(index) makes the (noisy, clean) pair of an int32 device index list in one launch (ops.wave_batch)."""
+
+    def __init__(self, clean_list, noise_signals, snr_levels, fs=None, max_len=None, device=None):
+        self.max_len = int(max_len or (fs or config.SAMPLE_RATE) * 4)
+        snr_levels = [float(s) for s in snr_levels]
+        if self.max_len < 1 or not snr_levels:
+            raise ValueError("WaveformSet: a positive max_len and at least one SNR level are needed")
+        if isinstance(noise_signals, dict):
+            noise_signals = list(noise_signals.values())
+        self.bank = noise_signals if isinstance(noise_signals, NoiseBank) else NoiseBank(noise_signals)
+        dev = self.bank.buffer.device if device is None else torch.device(device)
+        kept, self.file_index = [], []
+        for i, c in enumerate(clean_list):
+            if c is None:
+                continue
+            c = c.detach() if torch.is_tensor(c) else torch.from_numpy(np.ascontiguousarray(c, dtype=np.float32))
+            if c.dim() != 1:
+                raise ValueError("WaveformSet: entry %d has shape %s; 1-D signals are needed" % (i, tuple(c.shape)))
+            if c.numel() >= config.FRAME_SIZE * 4:
+                kept.append(c)
+                self.file_index.append(i)
+        if not kept:
+            raise ValueError("WaveformSet: no utterance of at least %d samples" % (config.FRAME_SIZE * 4))
+        full_len = [c.numel() for c in kept]
+        if sum(full_len) > 2 ** 31 - 1:
+            raise ValueError("WaveformSet: %d samples; the offset table is int32" % sum(full_len))
+        if all(not c.is_cuda for c in kept):                                   # one host-to-device copy for the whole list
+            full = torch.cat([c.float() for c in kept]).to(dev)
+        else:
+            full = torch.cat([c.to(dev, torch.float32) for c in kept])
+        pos = np.asarray(self.file_index, dtype=np.int64)
+        self.noise_ids = torch.from_numpy((pos % self.bank.count).astype(np.int32)).to(dev)
+        self.snr_db = torch.tensor([snr_levels[i % len(snr_levels)] for i in self.file_index], dtype=torch.float32, device=dev)
+        full_off = np.concatenate([[0], np.cumsum(full_len)])
+        self.scale = ops.mix_scale_varlen(full, torch.from_numpy(full_off.astype(np.int32)).to(dev), self.bank.buffer,
+                                          self.bank.offsets, self.noise_ids, self.snr_db, max(full_len))
+        self.lengths = [min(n, self.max_len) for n in full_len]
+        if self.lengths != full_len:
+            full = torch.cat([full[a:a + n] for a, n in zip(full_off[:-1].tolist(), self.lengths)])
+        self.clean = full.contiguous()
+        self.offsets = torch.from_numpy(np.concatenate([[0], np.cumsum(self.lengths)]).astype(np.int32)).to(dev)
+
+    @classmethod
+    def from_padded(cls, clean, lengths, noise_signals, snr_levels, fs=None, max_len=None):
+        """clean [N, L] fp32 on the device, row i holding lengths[i] samples (a host sequence or a tensor; None: all of L)"""
+        if not torch.is_tensor(clean) or not clean.is_cuda:
+            raise RuntimeError("WaveformSet.from_padded: the rows live on the MI355X; got a CPU tensor (there is no CPU fallback)")
+        if clean.dim() != 2:
+            raise ValueError("WaveformSet.from_padded: clean [N, L] is needed; got shape %s" % (tuple(clean.shape),))
+        N, L = clean.shape
+        host = [L] * N if lengths is None else [int(v) for v in np.asarray(lengths.cpu() if torch.is_tensor(lengths) else lengths).reshape(-1)]
+        if len(host) != N or (N and (min(host) < 0 or max(host) > L)):
+            raise ValueError("WaveformSet.from_padded: lengths %r for clean %s" % (host, tuple(clean.shape)))
+        return cls([clean[i, :host[i]] for i in range(N)], noise_signals, snr_levels, fs, max_len, device=clean.device)
+
+    def __len__(self):
+        return len(self.lengths)
+
+    def batch(self, index):
+        """index: int32 device tensor [B] (-1: a zero row) -> (noisy [B, max_len], clean [B, max_len])"""
+        if not torch.is_tensor(index) or not index.is_cuda:
+            raise RuntimeError("WaveformSet.batch: the index lives on the MI355X; got a host value (there is no CPU fallback)")
+        out = ops.wave_batch(self.clean, self.offsets, self.bank.buffer, self.bank.offsets, self.noise_ids, self.scale,
+                             index.to(torch.int32).reshape(-1).contiguous(), self.max_len)
+        return out[0], out[1]
+
+    def __getitem__(self, idx):
+        i, n = int(idx), len(self)
+        if not -n <= i < n:                                 # (the sequence protocol ends an iteration on this)
+            raise IndexError("WaveformSet: utterance %d of %d" % (i, n))
+        noisy, clean = self.batch(torch.tensor([i % n], dtype=torch.int32, device=self.clean.device))
+        return noisy[0], clean[0]
+
+    def batches(self, batch_size, order=None, drop_last=False, shuffle=False):
+        """an iterable of batch() pairs over the set: in `order` (an int32 device permutation), else in a torch.randperm drawn on
+        the device when `shuffle`, else in the stored order.  drop_last leaves the last partial batch out."""
+        if int(batch_size) < 1:
+            raise ValueError("WaveformSet.batches: batch_size %r" % (batch_size,))
+        dev = self.clean.device
+        if order is not None:
+            if not torch.is_tensor(order) or not order.is_cuda:
+                raise RuntimeError("WaveformSet.batches: the order lives on the MI355X; got a host value (there is no CPU fallback)")
+            index = order.to(torch.int32).reshape(-1).contiguous()
+        elif shuffle:
+            index = torch.randperm(len(self), device=dev, dtype=torch.int32)
+        else:
+            index = torch.arange(len(self), device=dev, dtype=torch.int32)
+        return _Batches(self, index, batch_size, drop_last)
+
+
+class WarmupCosineRule:
+    """The LambdaLR of ConformerPipeline.train (:432-441) restated on the host: warmup = max(1, min(5, total // 5)) epochs of
+    (e + 1) / warmup, then max(0.01, 0.5 (1 + cos(pi (e - warmup) / max(1, total - warmup)))).  There is no torch optimiser to hand
+    a scheduler: lr(epoch) is assigned to FlatAdamW.lr before the epoch."""
+
+    def __init__(self, total_epochs, base_lr=5e-4):
+        self.total, self.base_lr = int(total_epochs), float(base_lr)
+        self.warmup = max(1, min(5, self.total // 5))
+
+    def multiplier(self, epoch):
+        if epoch < self.warmup:
+            return (epoch + 1) / self.warmup
+        progress = (epoch - self.warmup) / max(1, self.total - self.warmup)
+        return max(0.01, 0.5 * (1 + math.cos(math.pi * progress)))
+
+    def lr(self, epoch):
+        return self.base_lr * self.multiplier(epoch)
 
 
 def si_snr_loss(estimated, target):
@@ -454,11 +588,13 @@ class EnhancementPath(HipModule):
 
 
 class ConformerPipeline:
-    """training/conformer_pipeline.py:308-685 without its data loading: the training step (_train_epoch :484, _validate :574,
-    _compute_loss :539), model I/O (:611-649) and enhance_signal (:653)."""
+    """training/conformer_pipeline.py:308-685 without its file search and audio loading: train (:403) on two WaveformSets, the
+    training step (_train_epoch :484, _validate :574, _compute_loss :539), model I/O (:611-649) and enhance_signal (:653).
+    model_dir overrides config.MODEL_DIR."""
 
-    def __init__(self, fs=None, device=None):
+    def __init__(self, fs=None, device=None, *, model_dir=None):
         self.fs = fs or config.SAMPLE_RATE
+        self.model_dir = model_dir or config.MODEL_DIR          # where the checkpoint methods write and look
         self.fft_size, self.hop_size, self.frame_size = config.FFT_SIZE, config.HOP_SIZE, config.FRAME_SIZE
         if not torch.cuda.is_available():
             raise RuntimeError("ConformerPipeline (HIP build) needs an MI355X; there is no CPU fallback")
@@ -467,6 +603,8 @@ class ConformerPipeline:
         self.use_amp = True           # :334 `use_amp = device.type == 'cuda'`: fp16 operands + dynamic loss scale (make_optimizer)
         self.use_graph = False        # True: enhance_signal replays one hipGraph per signal length (graph.GraphedForward)
         self._graphed = None
+        self.history = []             # train(): (train_loss, train_sisnr, val_loss, val_sisnr, lr) per epoch
+        self.optimizer = self.scaler = None
 
     def _compute_loss(self, noisy_real, noisy_imag, clean_wav, clean_real, clean_imag, mr_stft_fn):
         """training/conformer_pipeline.py:539-572: model forward -> iSTFT -> SI-SNR + 0.5 * L1 magnitude +
@@ -542,27 +680,77 @@ class ConformerPipeline:
         n = max(float(a[2]), 1.0)
         return float(a[0]) / n, float(a[1]) / n
 
+    # -- the loop (training/conformer_pipeline.py:403-484) ------------------------------------------------------------------
+    def _new_model(self):
+        return SpeechEnhancer(n_freq=self.fft_size // 2 + 1, d_model=256, num_blocks=4, num_heads=4, d_ff=1024, kernel_size=31,
+                              dropout=0.15)
+
+    def train(self, train_set, test_set, epochs=None, *, seed=None, order=None, batch_size=8, verbose=True):
+        """ConformerPipeline.train on two WaveformSets: `epochs or 50` epochs of _train_epoch over shuffled full batches and
+        _validate over all of test_set in its order, the rate of WarmupCosineRule assigned before each epoch, best_conformer.pt
+        written when the validation loss improves.  self.history: (train_loss, train_sisnr, val_loss, val_sisnr, lr) per epoch,
+        lr the rate the epoch ran at.  seed: torch.manual_seed before the model is built (the initial weights, the dropout seeds
+        and the shuffles follow it).  order: instead of the shuffles, one int32 device permutation for every epoch or a sequence
+        of one per epoch.  An epoch's data never touches the host: each batch is one ops.wave_batch launch."""
+        total_epochs = epochs or 50
+        if seed is not None:
+            torch.manual_seed(seed)
+        self.model = self._new_model().to(self.device)
+        self._graphed = None
+        mr_stft_loss = MultiResolutionSTFTLoss()
+        optimizer, scaler = self.optimizer, self.scaler = self.make_optimizer()        # (kept: their stats() after the run)
+        rule = WarmupCosineRule(total_epochs, optimizer.lr)
+        if verbose:
+            print(f"\n  Model: {sum(p.numel() for p in self.model.parameters() if p.requires_grad):,} parameters -> {self.device}")
+            print(f"\n{'=' * 60}")
+            print(f"  DCSE Training: {total_epochs} epochs")
+            print(f"  Loss: SI-SNR + L1 Mag + Multi-Resolution STFT")
+            print(f"  Optimizer: AdamW (lr={rule.base_lr:.0e}, wd={optimizer.weight_decay})")
+            print(f"  Warmup: {rule.warmup} epochs, then cosine decay")
+            print(f"  Gradient clip: {optimizer.max_norm}, AMP: {'ON' if self.use_amp else 'OFF'}")
+            print(f"{'=' * 60}")
+        best_val_loss = float('inf')
+        self.history = []
+        for epoch in range(total_epochs):
+            lr = optimizer.lr = rule.lr(epoch)
+            epoch_order = order if order is None or torch.is_tensor(order) else order[epoch]
+            train_loss, train_sisnr = self._train_epoch(
+                train_set.batches(batch_size, order=epoch_order, drop_last=True, shuffle=True), optimizer, mr_stft_loss, scaler)
+            val_loss, val_sisnr = self._validate(test_set.batches(batch_size), mr_stft_loss)
+            improved = val_loss < best_val_loss
+            if improved:
+                best_val_loss = val_loss
+                self._save_best()
+            self.history.append((train_loss, train_sisnr, val_loss, val_sisnr, lr))
+            if verbose:                                      # (the reference prints the rate its scheduler has just stepped to)
+                print(f"  Epoch {epoch + 1:3d}/{total_epochs} | "
+                      f"Train: {train_loss:.4f} (SI-SNR: {train_sisnr:+.2f}) | "
+                      f"Val: {val_loss:.4f} (SI-SNR: {val_sisnr:+.2f}) | "
+                      f"LR: {rule.lr(epoch + 1):.2e} {'*' if improved else ''}")
+        if verbose:
+            print(f"\n  Best validation loss: {best_val_loss:.4f}")
+
     # -- model I/O (training/conformer_pipeline.py:611-649): {'model_state', 'model_class'} checkpoints ----------------
     def _checkpoint(self):
         return {"model_state": {k: v.detach().cpu() for k, v in self.model.state_dict().items()}, "model_class": "SpeechEnhancer"}
 
     def _save_best(self):
-        os.makedirs(config.MODEL_DIR, exist_ok=True)
-        torch.save(self._checkpoint(), os.path.join(config.MODEL_DIR, "best_conformer.pt"))
+        os.makedirs(self.model_dir, exist_ok=True)
+        torch.save(self._checkpoint(), os.path.join(self.model_dir, "best_conformer.pt"))
 
     def save_model(self, filename="conformer_final.pt"):
         if self.model is None:
             return
-        os.makedirs(config.MODEL_DIR, exist_ok=True)
-        path = os.path.join(config.MODEL_DIR, filename)
+        os.makedirs(self.model_dir, exist_ok=True)
+        path = os.path.join(self.model_dir, filename)
         torch.save(self._checkpoint(), path)
         print(f"  + Model saved: {path}")
 
     def load_model(self, path=None):
         if path is None:
-            path = os.path.join(config.MODEL_DIR, "conformer_final.pt")
+            path = os.path.join(self.model_dir, "conformer_final.pt")
             if not os.path.exists(path):
-                path = os.path.join(config.MODEL_DIR, "best_conformer.pt")
+                path = os.path.join(self.model_dir, "best_conformer.pt")
         # tensors only: a checkpoint is {'model_state': state_dict, 'model_class': str} (the reference unpickles with
         # weights_only=False; nothing in its checkpoints needs that)
         ckpt = torch.load(path, map_location="cpu", weights_only=True)
