@@ -964,6 +964,61 @@ int sfm_rbm_update(const float* data, const int* rows, const float* ph, const fl
 int sfm_rbm_fold_error(const double* partial, double* out, int n_steps, int n_tiles, int num_samples, int batch_size, int n_visible,
                        void* stream);
 
+/* STOI of Taal et al. (2011) and ESTOI of Jensen & Taal (2016) (stoi.hip): what evaluation/stoi.py:46-50 of the reference computes
+ * when pystoi is installed.  wave64, no atomics, every cross-thread sum in fp64 in a fixed order: an utterance has the same bits
+ * alone, in a batch and in any packed set.  Nothing waits for the device: an utterance's kept-frame count stays there, and every
+ * table is sized for all frames kept.  The kernels behind the resampler work at SFM_STOI_FS.  Utterance u = samples
+ * [sig_off[u], sig_off[u] + sig_len[u]) of sig; it owns the
+ * n_u = (sig_len[u] - SFM_STOI_FRAME) / SFM_STOI_HOP + 1 (0 below one frame) rows [frame_off[u], frame_off[u + 1]) of energy, src
+ * and the band rows; sig_off, sig_len int32 [B], frame_off int32 [B + 1], all on the device.  win fp32 [SFM_STOI_FRAME] =
+ * hanning(SFM_STOI_FRAME + 2)[1:-1]. */
+#define SFM_STOI_FS 10000
+#define SFM_STOI_FRAME 256
+#define SFM_STOI_HOP 128
+#define SFM_STOI_NFFT 512
+#define SFM_STOI_BANDS 15
+#define SFM_STOI_SEG 30
+#define SFM_STOI_FIRST_BIN 7
+#define SFM_STOI_LAST_BIN 218
+#define SFM_STOI_DFT_COLS 432
+#define SFM_STOI_ROW_TILE 16
+#define SFM_STOI_SEG_TILE 32
+#define SFM_STOI_TAP_HALF 10
+#define SFM_STOI_MAX_RATE 8
+/* evaluation/stoi.py:46-50, step 0 (rate): the polyphase FIR resampler.  Utterance u of `in` = samples [in_off[u], in_off[u] + in_len[u]),
+ * of `out` = [out_off[u], out_off[u] + out_len[u]), out_len[u] = ceil(in_len[u] up / down) (the host's figure; all four int32 [B] on the
+ * device).  out[n = t up + p] = sum_k in[t down + k - padl] taps[k up + p], zeros beyond both ends of the utterance, taps fp32 [K, up]:
+ * fp32 operands, the sum an fma chain in fp64 in k order, stored as fp32.  max_out_len = the largest out_len (0 launches nothing).
+ * 1 <= up, down <= SFM_STOI_MAX_RATE, 1 <= K <= 2 SFM_STOI_TAP_HALF SFM_STOI_MAX_RATE + 1, 0 <= padl < K, B <= 65535
+ * (SFM_ERR_SHAPE otherwise). */
+int sfm_stoi_resample(const float* in, const float* taps, const int* in_off, const int* in_len, const int* out_off, const int* out_len,
+                      float* out, int B, int max_out_len, int up, int down, int K, int padl, void* stream);
+/* evaluation/stoi.py:46-50, step 1 (silent frames) on the CLEAN signal: energy[f] = 20 log10(||win x_f|| + eps) in fp64, eps = 2^-52;
+ * frame f is kept when energy[f] > max_f energy[f] - 40; src[frame_off[u] + k] = the k-th kept frame of utterance u in order,
+ * kept[u] = their count K_u (0 without a frame).  One workgroup per utterance: energies, maximum, mask, exclusive scan. */
+int sfm_stoi_keep(const float* sig, const float* win, const int* sig_off, const int* sig_len, const int* frame_off, double* energy,
+                  int* src, int* kept, int B, void* stream);
+/* evaluation/stoi.py:46-50, steps 1 (overlap-add of the kept windowed frames), 2 (spectra) and 3 (bands) of nsig = 1 or 2 signals that
+ * share the kept list: spectral frame m < K_u - 1 of utterance u is rebuilt from the source frames src[m - 1], src[m], src[m + 1]
+ * (each half = two windowed source half-frames), windowed again (fp64) and multiplied on v_mfma_f64_16x16x4_f64 (fp64 sums) by dft
+ * [SFM_STOI_FRAME, SFM_STOI_DFT_COLS] fp32: column c < 212 = cos(2 pi n (c + SFM_STOI_FIRST_BIN) / SFM_STOI_NFFT), column 212 + c the
+ * negated sine, zero beyond 424 (fp32 values).  bands0 / bands1 [frame_off[B], SFM_STOI_BANDS] fp32: row frame_off[u] + m, band j = sqrt(sum of
+ * |X|^2 over the bins [lo_j, hi_j)) of edges 7 9 11 14 17 22 27 34 43 55 69 87 109 138 174 219, summed in fp64 in bin order; rows from
+ * K_u - 1 on are not written.  tiles int32 [n_tiles, 2] = (utterance, tile of SFM_STOI_ROW_TILE spectral frames), ceil((n_u - 1) /
+ * SFM_STOI_ROW_TILE) per utterance; a tile beyond K_u - 1 does nothing.  sig1 / bands1 NULL when nsig = 1.  n_tiles = 0 launches
+ * nothing, and tiles may then be NULL (no utterance has two frames: every score is 1e-5). */
+int sfm_stoi_bands(const float* sig0, const float* sig1, const float* win, const float* dft, const int* sig_off, const int* frame_off,
+                   const int* src, const int* kept, const int* tiles, float* bands0, float* bands1, int n_tiles, int nsig,
+                   void* stream);
+/* evaluation/stoi.py:46-50, steps 4 (too few frames) and 5 (segments): score[u] fp64 from the band rows xb (clean) and yb of
+ * sfm_stoi_bands; M = K_u - 1 < SFM_STOI_SEG gives 1e-5.  Segment m = SFM_STOI_SEG .. M is the block of rows m - 30 .. m - 1, all in
+ * fp64.  extended 0: per band alpha = ||x|| / (||y|| + eps), y' = min(alpha y, x (1 + 10^(15/20))), the correlation of the
+ * mean-removed rows, averaged over bands and segments.  extended 1: rows, then columns, mean-removed and divided by (norm + eps); the
+ * sum of x y over the block / 30, averaged over segments.  One workgroup per utterance; the rows go through a ring in LDS, each read
+ * once, SFM_STOI_SEG_TILE segments per stage, the segment values added in segment order.  No row from K_u - 1 on is read. */
+int sfm_stoi_segments(const float* xb, const float* yb, const int* frame_off, const int* kept, double* score, int B, int extended,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,9 +6,11 @@ import torch
 
 from .. import config, functional as Fn, ops
 from .pesq_eval import pesq_framing, pesq_from_lsd
+from . import stoi_taal
 from .stoi import _dft_operand
 
 METRICS = ("stoi", "pesq", "ssnr")
+ALL_METRICS = METRICS + stoi_taal.TAAL_METRICS      # "stoi" is the reference's fallback, "stoi_taal" / "estoi" the standard measure
 
 
 def metric_framings(fs=None):
@@ -21,9 +23,9 @@ def metric_framings(fs=None):
 
 def _check_metrics(metrics):
     metrics = tuple(metrics)
-    bad = [m for m in metrics if m not in METRICS]
+    bad = [m for m in metrics if m not in ALL_METRICS]
     if bad or not metrics:
-        raise ValueError("metrics %r: choose from %r" % (metrics, METRICS))
+        raise ValueError("metrics %r: choose from %r" % (metrics, ALL_METRICS))
     return metrics
 
 
@@ -63,6 +65,31 @@ def _spectra(wave, W, samp_off, tab, B, frame, hop):
     return re, im
 
 
+def pack_pairs(clean, enhanced, seg, who):
+    """the calling convention of the packed measures: with `seg`, clean / enhanced are [sum_L] device tensors (checked, made fp32
+    and contiguous); without, two lists of 1-D signals that are cut pairwise and packed once through pinned memory.
+    -> (clean, enhanced, seg), or (None, None, None) for two empty lists"""
+    if seg is None:
+        c, e = trim_pairs(clean, enhanced)
+        if not c:
+            return None, None, None
+        L = np.asarray([s.size for s in c], dtype=np.int64)
+        seg = Fn.PackedSegments(1 + L // config.HOP_SIZE, L)
+        stage = torch.empty(2, max(seg.sum_L, 1), dtype=torch.float32, pin_memory=True)
+        np.concatenate(c, out=stage.numpy()[0, :seg.sum_L])
+        np.concatenate(e, out=stage.numpy()[1, :seg.sum_L])
+        both = stage.cuda(non_blocking=True)
+        clean, enhanced = both[0, :seg.sum_L], both[1, :seg.sum_L]
+    if seg.lengths is None:
+        raise ValueError("%s: the segments must carry the signal lengths" % who)
+    ops._need_dev(clean, enhanced)
+    clean, enhanced = clean.float().contiguous(), enhanced.float().contiguous()
+    if clean.dim() != 1 or clean.numel() != seg.sum_L or enhanced.shape != clean.shape:
+        raise RuntimeError("%s: %s / %s samples, the segments describe [%d]" % (
+            who, tuple(clean.shape), tuple(enhanced.shape), seg.sum_L))
+    return clean, enhanced, seg
+
+
 def compute_metrics_packed(clean, enhanced, seg=None, fs=None, metrics=METRICS, clean_spectra=None):
     """clean, enhanced: [sum_L] fp32 device tensors holding the utterances of `seg` (a functional.PackedSegments that carries
     `lengths`) back to back - or two lists of 1-D arrays / tensors, then each pair is cut to its shorter member and the set is
@@ -74,30 +101,20 @@ def compute_metrics_packed(clean, enhanced, seg=None, fs=None, metrics=METRICS, 
     metrics = _check_metrics(metrics)
     if not torch.cuda.is_available():
         raise RuntimeError("the HIP metrics need an MI355X (no CPU fallback)")
+    clean, enhanced, seg = pack_pairs(clean, enhanced, seg, "compute_metrics_packed")
     if seg is None:
-        c, e = trim_pairs(clean, enhanced)
-        if not c:
-            return {m: torch.zeros(0, device="cuda", dtype=torch.float64) for m in metrics}
-        L = np.asarray([s.size for s in c], dtype=np.int64)
-        seg = Fn.PackedSegments(1 + L // config.HOP_SIZE, L)
-        stage = torch.empty(2, max(seg.sum_L, 1), dtype=torch.float32, pin_memory=True)
-        np.concatenate(c, out=stage.numpy()[0, :seg.sum_L])
-        np.concatenate(e, out=stage.numpy()[1, :seg.sum_L])
-        both = stage.cuda(non_blocking=True)
-        clean, enhanced = both[0, :seg.sum_L], both[1, :seg.sum_L]
-    if seg.lengths is None:
-        raise ValueError("compute_metrics_packed: the segments must carry the signal lengths")
-    ops._need_dev(clean, enhanced)
-    clean, enhanced = clean.float().contiguous(), enhanced.float().contiguous()
-    if clean.dim() != 1 or clean.numel() != seg.sum_L or enhanced.shape != clean.shape:
-        raise RuntimeError("compute_metrics_packed: %s / %s samples, the segments describe [%d]" % (
-            tuple(clean.shape), tuple(enhanced.shape), seg.sum_L))
+        return {m: torch.zeros(0, device="cuda", dtype=torch.float64) for m in metrics}
     dev, B = clean.device, seg.B
     fr = metric_framings(fs)
-    tabs = seg.metric_tables(dev, tuple(fr[m] for m in metrics))
+    tabs = seg.metric_tables(dev, tuple(fr[m] for m in metrics if m in fr))
     samp_off = seg.tables(dev)["samp_off"]
     out = {}
+    taal = tuple(m for m in metrics if m in stoi_taal.TAAL_METRICS)
+    if taal:                                                   # one pass serves both measures: they share everything but the segments
+        out.update(stoi_taal.score_packed(clean, enhanced, seg, fs, taal, clean_spectra))
     for m in metrics:
+        if m in out:
+            continue
         frame, hop = fr[m]
         tab = tabs[fr[m]]
         if tab["sum"] == 0:                                   # no utterance reaches one frame of this measure
@@ -126,4 +143,4 @@ def compute_metrics_packed(clean, enhanced, seg=None, fs=None, metrics=METRICS, 
         else:
             acc = ops.lsd_frames_varlen(cs[0], cs[1], es[0], es[1], tab["frame_off"], B)
             out[m] = torch.where(some, pesq_from_lsd(acc, n.clamp_min(1.0)), torch.ones_like(acc))
-    return out
+    return {m: out[m] for m in metrics}

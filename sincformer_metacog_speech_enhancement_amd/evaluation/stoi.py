@@ -1,7 +1,12 @@
 """evaluation/stoi.py: the reference calls pystoi when it is installed and otherwise its own simplified measure
 (_stoi_simplified :53-99).  pystoi exists neither in the reference's environment here nor on the GPU box, so the
 simplified measure is what the reference computes; that one is batched here on the device (`extended` is accepted and
-ignored, as in the fallback)."""
+ignored, as in the fallback).
+
+Which function is which measure:
+  compute_stoi(...)                     the reference's FALLBACK, _stoi_simplified (:53-99): a per-frame spectral cosine similarity
+  compute_stoi(..., method="taal")      STOI of Taal et al. (2011), and ESTOI (Jensen & Taal 2016) with extended=True: what :46-50
+  stoi_taal.compute_stoi_taal(...)      computes with pystoi installed (stoi_taal.py; its resampling filter is scipy's default)"""
 import numpy as np
 import torch
 
@@ -28,8 +33,14 @@ def _dft_operand(frame_len, dev, window="hann"):
     return m
 
 
-def compute_stoi(clean_signal, enhanced_signal, fs=None, extended=False):
-    """1-D inputs -> float; [B, L] inputs -> tensor [B]."""
+def compute_stoi(clean_signal, enhanced_signal, fs=None, extended=False, method=None):
+    """1-D inputs -> float; [B, L] inputs -> tensor [B].  method None: the reference's fallback measure (`extended` ignored);
+    "taal": stoi_taal.compute_stoi_taal, which honours `extended`."""
+    if method == "taal":
+        from .stoi_taal import compute_stoi_taal
+        return compute_stoi_taal(clean_signal, enhanced_signal, fs, extended)
+    if method is not None:
+        raise ValueError("compute_stoi: method %r; None (the reference's fallback) or \"taal\"" % (method,))
     fs = fs or config.SAMPLE_RATE
     (c, e), one_d = to_device_batch(clean_signal, enhanced_signal)
     B, L = c.shape

@@ -3025,3 +3025,90 @@ def rbm_fold_error(partial, out, n_steps, num_samples, batch_size, n_visible):
         _lib.check(_K["ERR_SHAPE"], "rbm_fold_error")
     _call("rbm_fold", L.sfm_rbm_fold_error, (_p(partial), _p(out), int(n_steps), tiles, int(num_samples), int(batch_size), int(n_visible),
                                              _stream()), float(n_steps) * (tiles + 2), 8.0 * n_steps * tiles + 8.0)
+
+
+# ---------------------------------------------------------------------------
+# STOI of Taal et al. and ESTOI (csrc/stoi.hip; evaluation/stoi_taal.py plans the tables)
+# ---------------------------------------------------------------------------
+STOI_FS, STOI_FRAME, STOI_HOP, STOI_NFFT = _K["STOI_FS"], _K["STOI_FRAME"], _K["STOI_HOP"], _K["STOI_NFFT"]
+STOI_BANDS, STOI_SEG, STOI_FIRST_BIN, STOI_LAST_BIN = _K["STOI_BANDS"], _K["STOI_SEG"], _K["STOI_FIRST_BIN"], _K["STOI_LAST_BIN"]
+STOI_DFT_COLS, STOI_ROW_TILE, STOI_SEG_TILE = _K["STOI_DFT_COLS"], _K["STOI_ROW_TILE"], _K["STOI_SEG_TILE"]
+STOI_TAP_HALF, STOI_MAX_RATE = _K["STOI_TAP_HALF"], _K["STOI_MAX_RATE"]
+STOI_NBIN = STOI_LAST_BIN - STOI_FIRST_BIN + 1
+
+
+def _i32(*ts):
+    return all(t.dtype == torch.int32 and t.is_contiguous() for t in ts)
+
+
+def stoi_resample(sig, taps, in_off, in_len, out_off, out_len, B, n_out, max_out_len, n_in, up, down, padl):
+    """polyphase FIR to 10 kHz: sig fp32 (flat), utterance u = sig[in_off[u] : in_off[u] + in_len[u]] -> out fp32 [n_out], utterance u at
+    out_off[u], out_len[u] samples; taps fp32 [K, up] (evaluation.stoi_taal.resample_operand).  fp32 operands, fp64 sums.  n_out,
+    max_out_len, n_in: host sums / maximum (sizes and the cost)."""
+    _need_dev(sig, taps, in_off, in_len, out_off, out_len)
+    L = _lib.load()
+    if sig.dtype != torch.float32 or not sig.is_contiguous() or taps.dtype != torch.float32 or taps.dim() != 2 or taps.shape[1] != up or \
+            not taps.is_contiguous() or not _i32(in_off, in_len, out_off, out_len) or any(t.numel() != B for t in (in_off, in_len, out_off, out_len)):
+        _lib.check(_K["ERR_SHAPE"], "stoi_resample")
+    K = taps.shape[0]
+    out = torch.empty(max(n_out, 1), device=sig.device, dtype=torch.float32)
+    _call("stoi", L.sfm_stoi_resample, (_p(sig), _p(taps), _p(in_off), _p(in_len), _p(out_off), _p(out_len), _p(out), B, int(max_out_len),
+                                        int(up), int(down), K, int(padl), _stream()),
+          2.0 * K * n_out, 4.0 * (n_in + n_out) + 4.0 * K * up + 16.0 * B, "resample %d/%d B%d out%d" % (up, down, B, n_out))
+    return out
+
+
+def stoi_keep(sig, win, sig_off, sig_len, frame_off, B, sum_frames, n_samples):
+    """silent-frame decision of the clean signals at 10 kHz: sig fp32 (flat), utterance u = sig[sig_off[u] : sig_off[u] + sig_len[u]],
+    its frames = rows [frame_off[u], frame_off[u + 1]) -> (src int32 [sum_frames] the kept source frames of each utterance in
+    order, kept int32 [B] their counts, energy fp64 [sum_frames] in dB).  sum_frames, n_samples: host sums (sizes and the cost)."""
+    _need_dev(sig, win, sig_off, sig_len, frame_off)
+    L = _lib.load()
+    if sig.dtype != torch.float32 or not sig.is_contiguous() or win.dtype != torch.float32 or win.numel() != STOI_FRAME or \
+            not _i32(sig_off, sig_len, frame_off) or sig_off.numel() != B or sig_len.numel() != B or frame_off.numel() != B + 1:
+        _lib.check(_K["ERR_SHAPE"], "stoi_keep")
+    energy = torch.empty(max(sum_frames, 1), device=sig.device, dtype=torch.float64)
+    src = torch.empty(max(sum_frames, 1), device=sig.device, dtype=torch.int32)
+    kept = torch.empty(B, device=sig.device, dtype=torch.int32)
+    _call("stoi", L.sfm_stoi_keep, (_p(sig), _p(win), _p(sig_off), _p(sig_len), _p(frame_off), _p(energy), _p(src), _p(kept), B,
+                                    _stream()),
+          3.0 * STOI_FRAME * sum_frames, 4.0 * n_samples + 12.0 * sum_frames + 16.0 * B + 4.0 * STOI_FRAME, "keep B%d frames%d" % (B, sum_frames))
+    return src, kept, energy
+
+
+def stoi_bands(sigs, win, dft, sig_off, frame_off, src, kept, tiles, sum_frames, spec_rows, n_samples):
+    """one-third-octave band rows of one or two signals that share a kept list: sigs = (sig,) or (sig0, sig1) -> a tuple of fp32
+    [sum_frames, 15] (rows beyond an utterance's K - 1 are not written).  tiles int32 [n, 2] on the device; spec_rows: the most
+    spectral frames there can be (all frames kept), n_samples: samples of ONE signal (the cost)."""
+    _need_dev(win, dft, sig_off, frame_off, src, kept, tiles, *sigs)
+    L = _lib.load()
+    nsig = len(sigs)
+    if nsig not in (1, 2) or any(s.dtype != torch.float32 or not s.is_contiguous() for s in sigs) or dft.dtype != torch.float32 or \
+            tuple(dft.shape) != (STOI_FRAME, STOI_DFT_COLS) or not dft.is_contiguous() or win.numel() != STOI_FRAME or \
+            not _i32(sig_off, frame_off, src, kept, tiles) or tiles.dim() != 2 or tiles.shape[1] != 2 or src.numel() < sum_frames:
+        _lib.check(_K["ERR_SHAPE"], "stoi_bands")
+    outs = tuple(torch.empty(max(sum_frames, 1), STOI_BANDS, device=sigs[0].device, dtype=torch.float32) for _ in sigs)
+    n_tiles = tiles.shape[0]
+    _call("stoi", L.sfm_stoi_bands, (_p(sigs[0]), _p(sigs[1]) if nsig == 2 else None, _p(win), _p(dft), _p(sig_off), _p(frame_off),
+                                     _p(src), _p(kept), _p(tiles), _p(outs[0]), _p(outs[1]) if nsig == 2 else None, n_tiles, nsig,
+                                     _stream()),
+          nsig * 2.0 * spec_rows * STOI_FRAME * 2 * STOI_NBIN,
+          nsig * (4.0 * n_samples + 4.0 * STOI_BANDS * spec_rows) + 4.0 * STOI_FRAME * (2 * STOI_NBIN + 1) + 4.0 * sum_frames + 8.0 * n_tiles,
+          "bands x%d rows%d" % (nsig, spec_rows))
+    return outs
+
+
+def stoi_segments(xb, yb, frame_off, kept, B, extended, spec_rows, segments):
+    """band rows of the clean and the enhanced signals -> score fp64 [B]: STOI, or ESTOI when extended; 1e-5 below 30 spectral
+    frames.  spec_rows as stoi_bands, segments: the most segments there can be (the cost: every row read once, 12 flops per
+    element of a 15 x 30 segment)."""
+    _need_dev(xb, yb, frame_off, kept)
+    L = _lib.load()
+    if xb.dtype != torch.float32 or yb.dtype != torch.float32 or xb.shape != yb.shape or xb.dim() != 2 or xb.shape[1] != STOI_BANDS or \
+            not xb.is_contiguous() or not yb.is_contiguous() or not _i32(frame_off, kept) or frame_off.numel() != B + 1 or kept.numel() != B:
+        _lib.check(_K["ERR_SHAPE"], "stoi_segments")
+    score = torch.empty(B, device=xb.device, dtype=torch.float64)
+    _call("stoi", L.sfm_stoi_segments, (_p(xb), _p(yb), _p(frame_off), _p(kept), _p(score), B, 1 if extended else 0, _stream()),
+          12.0 * STOI_SEG * STOI_BANDS * segments, 8.0 * STOI_BANDS * spec_rows + 8.0 * B + 4.0 * (2 * B + 1),
+          "%s B%d rows%d" % ("estoi" if extended else "stoi", B, spec_rows))
+    return score
