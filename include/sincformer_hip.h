@@ -1018,6 +1018,38 @@ int sfm_stoi_bands(const float* sig0, const float* sig1, const float* win, const
  * once, SFM_STOI_SEG_TILE segments per stage, the segment values added in segment order.  No row from K_u - 1 on is read. */
 int sfm_stoi_segments(const float* xb, const float* yb, const int* frame_off, const int* kept, double* score, int B, int extended,
                       void* stream);
+/* The gradient of the measure with respect to the ENHANCED signal (stoi_bwd.hip), three kernels that walk the forward back; the
+ * kept list and K_u belong to the clean signal and are constants, so the gradient is exact.  A norm at the zero vector and a band
+ * value of exactly 0 pass nothing back.  fp32 operands and stored results, every sum fp64 in a fixed order, no atomics.
+ * Step 5 back: dyb [frame_off[B], SFM_STOI_BANDS] fp32 = gscore[u] (fp64 [B], the cotangent of score[u]) times the derivative of
+ * score[u] by the band rows yb, from the same stored rows the forward read (so a clip decision is the forward's: an element with
+ * alpha y > x (1 + 10^(15/20)) passes nothing, neither directly nor through alpha).  A row lies in up to SFM_STOI_SEG segments; its
+ * cotangent is their sum in segment order, kept in LDS until the last of them has passed, then written once.  EVERY row of
+ * [frame_off[u], frame_off[u + 1]) is written: zeros from K_u - 1 on and for an utterance below SFM_STOI_SEG spectral frames.
+ * One workgroup per SFM_STOI_BWD_ROWS rows of an utterance: it walks every segment that holds one of its rows (the up to
+ * SFM_STOI_SEG - 1 that reach in from the rows below included) and adds to its own rows only, so no sum crosses a workgroup and
+ * the bits do not depend on the split.  max_rows: the largest frame_off[u + 1] - frame_off[u] (the host's figure; 0 launches
+ * nothing). */
+#define SFM_STOI_BWD_ROWS 32
+int sfm_stoi_segments_bwd(const float* xb, const float* yb, const int* frame_off, const int* kept, const double* gscore, float* dyb,
+                          int B, int max_rows, int extended, void* stream);
+/* Steps 3 and 2 back, per tile of SFM_STOI_ROW_TILE spectral frames of sig (the resampled enhanced signal): the windowed rebuilt
+ * frames and their Re | Im exactly as sfm_stoi_bands forms them, each bin scaled by dyb / band of its band (band = sqrt(sum |X|^2),
+ * 0 where that is 0), the scaled tile multiplied on the same matrix instruction by dft_t [SFM_STOI_DFT_COLS, SFM_STOI_FRAME] fp32 (the
+ * transpose of dft), times the window: dframes [frame_off[B], SFM_STOI_FRAME] fp32, row frame_off[u] + m = the cotangent of the
+ * rebuilt signal's samples [128 m, 128 m + 256) through spectral frame m.  Rows of utterances with K_u - 1 >= SFM_STOI_SEG only, and
+ * of those the rows below K_u - 1; no other row is written or read by sfm_stoi_fold_bwd.  n_tiles = 0 launches nothing. */
+int sfm_stoi_bands_bwd(const float* sig, const float* win, const float* dft, const float* dft_t, const int* sig_off,
+                       const int* frame_off, const int* src, const int* kept, const int* tiles, const float* dyb, float* dframes,
+                       int n_tiles, void* stream);
+/* Step 1 back, the overlap-add adjoint as a gather: dsig[sig_off[u] + s], s < sig_len[u], = sum over the at most two kept source
+ * frames src[k] that cover sample s (found by a search in the ascending list) of win times the at most two dframes terms of the
+ * rebuilt sample 128 k + s - 128 src[k], in ascending frame order.  Every sample is written once: 0 where no kept frame covers it,
+ * where only the last kept frame's second half does, and for an utterance below SFM_STOI_SEG spectral frames; samples
+ * sig_len[u] <= s < pad_to are written as 0 as well (pad_to = the row length of a zero-padded batch at SFM_STOI_FS, else 0).
+ * max_len = the largest of sig_len and pad_to (0 launches nothing), B <= 65535. */
+int sfm_stoi_fold_bwd(const float* dframes, const float* win, const int* sig_off, const int* sig_len, const int* frame_off,
+                      const int* src, const int* kept, float* dsig, int B, int max_len, int pad_to, void* stream);
 
 #ifdef __cplusplus
 }

@@ -67,6 +67,9 @@ PSO_C1 = 1.5
 PSO_C2 = 1.5
 PSO_BOUNDS = (0.0, 1.0)
 
+# evaluation/stoi.py of the reference asks pystoi for the extended measure (config.py:116 of the reference)
+STOI_EXTENDED = False
+
 # curriculum stages in epochs (config.py:120-122 of the reference)
 CURRICULUM_STAGE1_EPOCHS = 15
 CURRICULUM_STAGE2_EPOCHS = 20

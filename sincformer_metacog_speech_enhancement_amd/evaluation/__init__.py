@@ -3,7 +3,7 @@ fallbacks of evaluation/stoi.py and evaluation/pesq_eval.py, and all of them ove
 Taal et al. with its extended form, the pystoi branch of evaluation/stoi.py (stoi_taal.py)."""
 from .ssnr import compute_ssnr, compute_ssnr_improvement  # noqa: F401
 from .stoi import compute_stoi  # noqa: F401
-from .stoi_taal import compute_stoi_taal, compute_stoi_taal_packed  # noqa: F401
+from .stoi_taal import compute_stoi_taal, compute_stoi_taal_packed, stoi_taal_scores  # noqa: F401
 from .pesq_eval import compute_pesq  # noqa: F401
 from .csii import compute_csii  # noqa: F401
 from .ncm import compute_ncm, hilbert_envelope  # noqa: F401

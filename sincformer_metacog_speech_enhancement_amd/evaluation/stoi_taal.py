@@ -11,6 +11,12 @@ The host designs operands and tables in float64 with numpy (no scipy); the devic
 results are fp32, every sum is fp64 (the resampler's taps on the vector pipe, the DFT on the fp64 matrix instruction).  Nothing here waits for the device: an utterance's kept-frame count stays there
 and every table is sized for all frames kept.
 
+The measure as a training objective: stoi_taal_scores is compute_stoi_taal for a [B, L] batch with a graph behind the enhanced
+signal (train.StoiTaalFunction, training.TaalSTOILoss).  The kept list and K belong to the clean signal, so the gradient is exact;
+gradient_flat walks segments, bands and overlap-add back (csrc/stoi_bwd.hip) and applies the resampler's adjoint, which is the
+resampling kernel itself with up and down exchanged (resample_adjoint_operand).  batch_plan keeps plan and uploaded tables per
+batch shape: a repeated shape costs no host-device copy and no synchronisation.
+
 The resampler: pystoi resamples with its own Octave-style filter; the default filter of scipy.signal.resample_poly (Kaiser 5.0
 windowed sinc, 2 * 10 * max(up, down) + 1 taps, zero phase, zeros beyond both ends) stands in for it here.  The difference
 between the two on the score is unmeasured."""
@@ -29,6 +35,8 @@ TOO_SHORT = 1e-5
 TAAL_METRICS = ("stoi_taal", "estoi")
 
 _operands = {}
+_plans = {}
+PLAN_CACHE = 64                 # batch shapes whose plan and uploaded tables are kept (batch_plan)
 
 
 # ---- host design (float64, numpy only) ----
@@ -70,6 +78,24 @@ def resample_operand(up, down):
     for p in range(up):
         for k in range(K):
             i = p * down - (k - padl) * up + half
+            if 0 <= i < h.size:
+                W[k, p] = h[i]
+    return W, padl
+
+
+def resample_adjoint_operand(up, down):
+    """(W float64 [K, down], padl) of the ADJOINT of the conversion that resample_operand(up, down) states: with y = R x,
+    (R^T g)[t * down + p] = sum_k g[t * up + k - padl] W[k, p], zeros beyond both ends of g - dx[m] = sum_n dy[n] h[n down - m up + half],
+    the same polyphase form with up and down exchanged and the forward's own taps"""
+    h = resample_taps(up, down)
+    half = (h.size - 1) // 2
+    j_min = -(half // down)
+    j_max = ((down - 1) * up + half) // down
+    K, padl = j_max - j_min + 1, -j_min
+    W = np.zeros((K, down))
+    for p in range(down):
+        for k in range(K):
+            i = (k - padl) * down - p * up + half
             if 0 <= i < h.size:
                 W[k, p] = h[i]
     return W, padl
@@ -179,15 +205,22 @@ def _resample(sig, plan, tabs, op):
                              plan["n_samples"], int(plan["sig_len"].max()), plan["n_in"], plan["up"], plan["down"], op["padl"])
 
 
-def score_flat(clean, enhanced, plan, tabs, measures, clean_state=None):
-    """clean, enhanced: flat fp32 device signals at plan["fs"], utterance u = plan["in_len"][u] samples from plan["in_off"][u] (nothing
-    beyond them is read); tabs = the uploaded plan.  -> {measure: [B] fp64} for measures out of TAAL_METRICS.
-    clean_state: a dict that keeps what later calls on the same clean pack need of the clean side - the kept list ("src", "kept")
-    and the band rows ("bands"), so the clean signal is neither resampled nor analysed again."""
-    dev, B = clean.device, plan["B"]
-    if plan["sum_frames"] == 0:
-        return {m: torch.full((B,), TOO_SHORT, device=dev, dtype=torch.float64) for m in measures}
-    op = _device_operands(dev, plan["fs"])
+def _adjoint_operands(dev, fs):
+    """the forward's operands and, made on first use, what the gradient adds: the transposed DFT matrix and the adjoint taps"""
+    o = _device_operands(dev, fs)
+    if "dft_t" not in o:
+        o["dft_t"] = torch.from_numpy(np.ascontiguousarray(dft_operand().astype(np.float32).T)).to(dev)
+        if fs != FS:
+            W, padl = resample_adjoint_operand(*rate_ratio(fs))
+            o["taps_t"], o["padl_t"] = torch.from_numpy(W.astype(np.float32)).to(dev).contiguous(), padl
+    return o
+
+
+def analyse_flat(clean, enhanced, plan, tabs, clean_state=None):
+    """steps 0-3 of score_flat (plan["sum_frames"] > 0) -> {"re": the enhanced signal at 10 kHz, "src", "kept": the kept list,
+    "xb", "yb": the band rows of the clean and the enhanced signal} - what the segment kernel reads and the gradient keeps"""
+    B = plan["B"]
+    op = _device_operands(clean.device, plan["fs"])
     args = (op["win"], op["dft"], tabs["sig_off"], tabs["frame_off"])
     cs = None if clean_state is None else clean_state.get(("stoi_taal", plan["fs"]))
     re = _resample(enhanced, plan, tabs, op)
@@ -201,7 +234,60 @@ def score_flat(clean, enhanced, plan, tabs, measures, clean_state=None):
     else:
         src, kept, xb = cs["src"], cs["kept"], cs["bands"]
         yb, = ops.stoi_bands((re,), *args, src, kept, tabs["tiles"], plan["sum_frames"], plan["spec_rows"], plan["n_samples"])
-    return {m: ops.stoi_segments(xb, yb, tabs["frame_off"], kept, B, m == "estoi", plan["spec_rows"], plan["segments"]) for m in measures}
+    return {"re": re, "src": src, "kept": kept, "xb": xb, "yb": yb}
+
+
+def score_flat(clean, enhanced, plan, tabs, measures, clean_state=None):
+    """clean, enhanced: flat fp32 device signals at plan["fs"], utterance u = plan["in_len"][u] samples from plan["in_off"][u] (nothing
+    beyond them is read); tabs = the uploaded plan.  -> {measure: [B] fp64} for measures out of TAAL_METRICS.
+    clean_state: a dict that keeps what later calls on the same clean pack need of the clean side - the kept list ("src", "kept")
+    and the band rows ("bands"), so the clean signal is neither resampled nor analysed again."""
+    dev, B = clean.device, plan["B"]
+    if plan["sum_frames"] == 0:
+        return {m: torch.full((B,), TOO_SHORT, device=dev, dtype=torch.float64) for m in measures}
+    a = analyse_flat(clean, enhanced, plan, tabs, clean_state)
+    return {m: ops.stoi_segments(a["xb"], a["yb"], tabs["frame_off"], a["kept"], B, m == "estoi", plan["spec_rows"], plan["segments"])
+            for m in measures}
+
+
+def gradient_flat(a, plan, tabs, gscore, extended, row):
+    """the gradient of sum_u gscore[u] score[u] by the enhanced signal of a [B, row] batch: a = analyse_flat's result, gscore fp64
+    [B] on the device -> fp32 [B * row], every element written, zeros from in_len[u] on.  Segments, bands and overlap-add walked
+    back (csrc/stoi_bwd.hip), then the resampler's adjoint: sfm_stoi_resample with resample_adjoint_operand."""
+    dev, B, fs = a["re"].device, plan["B"], plan["fs"]
+    op = _adjoint_operands(dev, fs)
+    dyb = ops.stoi_segments_bwd(a["xb"], a["yb"], tabs["frame_off"], a["kept"], gscore, B, int(plan["frames"].max()), extended,
+                                plan["spec_rows"], plan["segments"])
+    dfr = ops.stoi_bands_bwd(a["re"], op["win"], op["dft"], op["dft_t"], tabs["sig_off"], tabs["frame_off"], a["src"], a["kept"],
+                             tabs["tiles"], dyb, plan["sum_frames"], plan["spec_rows"], plan["n_samples"])
+    fold = (dfr, op["win"], tabs["sig_off"], tabs["sig_len"], tabs["frame_off"], a["src"], a["kept"], B)
+    if fs == FS:                                              # the 10 kHz signal IS the batch: rows of `row` samples
+        return ops.stoi_fold_bwd(*fold, B * row, row, row, plan["sum_frames"])[:B * row]
+    d10 = ops.stoi_fold_bwd(*fold, plan["n_samples"], int(plan["sig_len"].max()), 0, plan["sum_frames"])
+    ragged = int(plan["in_len"].min()) < row
+    out = (torch.zeros if ragged else torch.empty)(B * row, device=dev, dtype=torch.float32)
+    ops.stoi_resample(d10, op["taps_t"], tabs["sig_off"], tabs["sig_len"], tabs["in_off"], tabs["in_len"], B, B * row,
+                      int(plan["in_len"].max()), plan["n_samples"], plan["down"], plan["up"], op["padl_t"], out=out)
+    return out
+
+
+def batch_plan(fs, B, L, lengths, dev):
+    """(plan, uploaded tables) of a [B, L] batch whose row u holds lengths[u] samples (None: L), kept by (device, fs, B, L, lengths):
+    a repeated shape costs neither a host-device copy nor a synchronisation"""
+    if lengths is None:
+        Lh = (L,) * B
+    else:
+        Lh = tuple(int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths))
+        if len(Lh) != B or (B and (min(Lh) < 0 or max(Lh) > L)):
+            raise ValueError("lengths %r for a [%d, %d] batch" % (list(Lh), B, L))
+    key = (str(dev), fs, B, L, Lh)
+    hit = _plans.get(key)
+    if hit is None:
+        plan = plan_tables(Lh, fs, np.arange(B, dtype=np.int64) * L)
+        if len(_plans) >= PLAN_CACHE:
+            _plans.clear()
+        hit = _plans[key] = (plan, _upload(plan, dev))
+    return hit
 
 
 def _packed_plan(seg, fs, dev):
@@ -253,3 +339,29 @@ def compute_stoi_taal_packed(clean, enhanced, seg=None, fs=None, extended=False,
     if seg is None:
         return torch.zeros(0, device="cuda", dtype=torch.float64)
     return score_packed(clean, enhanced, seg, fs, (m,), clean_state)[m]
+
+
+def scores_and_kept(enhanced, clean, fs, extended, lengths, name="stoi_taal_scores"):
+    """stoi_taal_scores with the device's int32 [B] kept-frame counts beside the scores (training.TaalSTOILoss decides from them
+    which utterances count)"""
+    from .. import train
+    fs = check_rate(fs)
+    for t in (enhanced, clean):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise RuntimeError("%s: device tensors are needed (there is deliberately no CPU fallback)" % name)
+    if enhanced.shape != clean.shape or enhanced.dim() not in (1, 2) or enhanced.dtype != torch.float32 or clean.dtype != torch.float32:
+        raise ValueError("%s: two fp32 waveforms [L] or [B, L] of one shape are needed; got %s %s and %s %s"
+                         % (name, tuple(enhanced.shape), enhanced.dtype, tuple(clean.shape), clean.dtype))
+    B, L = (1, enhanced.shape[0]) if enhanced.dim() == 1 else enhanced.shape
+    if B < 1 or L < 1:
+        raise ValueError("%s: an empty batch" % name)
+    plan, tabs = batch_plan(fs, B, L, lengths, enhanced.device)
+    return train.StoiTaalFunction.apply(enhanced, clean, plan, tabs, bool(extended))
+
+
+def stoi_taal_scores(enhanced, clean, fs=None, extended=False, lengths=None):
+    """compute_stoi_taal for a batch with a graph behind `enhanced`: fp32 device waveforms [L] or [B, L] of one shape -> [B] fp64
+    on the device, bit for bit compute_stoi_taal's values (the same four kernels); the node is train.StoiTaalFunction, the
+    gradient goes to `enhanced` only.  lengths: a host sequence [B], the sample counts of zero-padded rows (nothing behind a
+    row's length is read; the gradient there is 0)."""
+    return scores_and_kept(enhanced, clean, fs, extended, lengths)[0]

@@ -3033,7 +3033,7 @@ def rbm_fold_error(partial, out, n_steps, num_samples, batch_size, n_visible):
 STOI_FS, STOI_FRAME, STOI_HOP, STOI_NFFT = _K["STOI_FS"], _K["STOI_FRAME"], _K["STOI_HOP"], _K["STOI_NFFT"]
 STOI_BANDS, STOI_SEG, STOI_FIRST_BIN, STOI_LAST_BIN = _K["STOI_BANDS"], _K["STOI_SEG"], _K["STOI_FIRST_BIN"], _K["STOI_LAST_BIN"]
 STOI_DFT_COLS, STOI_ROW_TILE, STOI_SEG_TILE = _K["STOI_DFT_COLS"], _K["STOI_ROW_TILE"], _K["STOI_SEG_TILE"]
-STOI_TAP_HALF, STOI_MAX_RATE = _K["STOI_TAP_HALF"], _K["STOI_MAX_RATE"]
+STOI_TAP_HALF, STOI_MAX_RATE, STOI_BWD_ROWS = _K["STOI_TAP_HALF"], _K["STOI_MAX_RATE"], _K["STOI_BWD_ROWS"]
 STOI_NBIN = STOI_LAST_BIN - STOI_FIRST_BIN + 1
 
 
@@ -3041,17 +3041,20 @@ def _i32(*ts):
     return all(t.dtype == torch.int32 and t.is_contiguous() for t in ts)
 
 
-def stoi_resample(sig, taps, in_off, in_len, out_off, out_len, B, n_out, max_out_len, n_in, up, down, padl):
+def stoi_resample(sig, taps, in_off, in_len, out_off, out_len, B, n_out, max_out_len, n_in, up, down, padl, out=None):
     """polyphase FIR to 10 kHz: sig fp32 (flat), utterance u = sig[in_off[u] : in_off[u] + in_len[u]] -> out fp32 [n_out], utterance u at
     out_off[u], out_len[u] samples; taps fp32 [K, up] (evaluation.stoi_taal.resample_operand).  fp32 operands, fp64 sums.  n_out,
-    max_out_len, n_in: host sums / maximum (sizes and the cost)."""
-    _need_dev(sig, taps, in_off, in_len, out_off, out_len)
+    max_out_len, n_in: host sums / maximum (sizes and the cost).  out: a buffer of the caller's (the adjoint's zero-padded rows)."""
+    _need_dev(sig, taps, in_off, in_len, out_off, out_len, out)
     L = _lib.load()
     if sig.dtype != torch.float32 or not sig.is_contiguous() or taps.dtype != torch.float32 or taps.dim() != 2 or taps.shape[1] != up or \
             not taps.is_contiguous() or not _i32(in_off, in_len, out_off, out_len) or any(t.numel() != B for t in (in_off, in_len, out_off, out_len)):
         _lib.check(_K["ERR_SHAPE"], "stoi_resample")
     K = taps.shape[0]
-    out = torch.empty(max(n_out, 1), device=sig.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty(max(n_out, 1), device=sig.device, dtype=torch.float32)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < n_out:
+        _lib.check(_K["ERR_SHAPE"], "stoi_resample")
     _call("stoi", L.sfm_stoi_resample, (_p(sig), _p(taps), _p(in_off), _p(in_len), _p(out_off), _p(out_len), _p(out), B, int(max_out_len),
                                         int(up), int(down), K, int(padl), _stream()),
           2.0 * K * n_out, 4.0 * (n_in + n_out) + 4.0 * K * up + 16.0 * B, "resample %d/%d B%d out%d" % (up, down, B, n_out))
@@ -3112,3 +3115,66 @@ def stoi_segments(xb, yb, frame_off, kept, B, extended, spec_rows, segments):
           12.0 * STOI_SEG * STOI_BANDS * segments, 8.0 * STOI_BANDS * spec_rows + 8.0 * B + 4.0 * (2 * B + 1),
           "%s B%d rows%d" % ("estoi" if extended else "stoi", B, spec_rows))
     return score
+
+
+def stoi_segments_bwd(xb, yb, frame_off, kept, gscore, B, max_rows, extended, spec_rows, segments):
+    """the cotangent of the enhanced band rows: gscore fp64 [B] (the cotangent of stoi_segments' score) -> dyb fp32 like yb, EVERY
+    row written (zeros from K - 1 on and below 30 spectral frames).  max_rows: the most frames of one utterance (the grid: one
+    workgroup per STOI_BWD_ROWS rows).  The cost: the forward's terms again and their derivatives, 30 flops per element of a
+    15 x 30 segment, each segment once (a workgroup recomputes the up to 29 that reach into its rows); both row sets read once,
+    one written."""
+    _need_dev(xb, yb, frame_off, kept, gscore)
+    L = _lib.load()
+    if xb.dtype != torch.float32 or yb.dtype != torch.float32 or xb.shape != yb.shape or xb.dim() != 2 or xb.shape[1] != STOI_BANDS or \
+            not xb.is_contiguous() or not yb.is_contiguous() or not _i32(frame_off, kept) or frame_off.numel() != B + 1 or \
+            kept.numel() != B or gscore.dtype != torch.float64 or gscore.numel() != B or not gscore.is_contiguous() or \
+            not 0 <= max_rows <= xb.shape[0]:
+        _lib.check(_K["ERR_SHAPE"], "stoi_segments_bwd")
+    dyb = torch.empty_like(yb)
+    _call("stoi", L.sfm_stoi_segments_bwd, (_p(xb), _p(yb), _p(frame_off), _p(kept), _p(gscore), _p(dyb), B, int(max_rows),
+                                            1 if extended else 0, _stream()),
+          30.0 * STOI_SEG * STOI_BANDS * segments, 12.0 * STOI_BANDS * spec_rows + 8.0 * B + 4.0 * (2 * B + 1),
+          "%s bwd B%d rows%d" % ("estoi" if extended else "stoi", B, spec_rows))
+    return dyb
+
+
+def stoi_bands_bwd(sig, win, dft, dft_t, sig_off, frame_off, src, kept, tiles, dyb, sum_frames, spec_rows, n_samples):
+    """dyb (stoi_segments_bwd) -> dframes fp32 [sum_frames, 256]: row frame_off[u] + m = the cotangent of the rebuilt enhanced
+    signal's samples [128 m, 128 m + 256) through spectral frame m.  sig: the resampled enhanced signal; dft_t [432, 256] the
+    transpose of dft.  Only the rows stoi_fold_bwd reads are written.  The cost: the forward's product and the adjoint one."""
+    _need_dev(sig, win, dft, dft_t, sig_off, frame_off, src, kept, tiles, dyb)
+    L = _lib.load()
+    if sig.dtype != torch.float32 or not sig.is_contiguous() or dft.dtype != torch.float32 or dft_t.dtype != torch.float32 or \
+            tuple(dft.shape) != (STOI_FRAME, STOI_DFT_COLS) or tuple(dft_t.shape) != (STOI_DFT_COLS, STOI_FRAME) or \
+            not dft.is_contiguous() or not dft_t.is_contiguous() or win.numel() != STOI_FRAME or win.dtype != torch.float32 or \
+            not _i32(sig_off, frame_off, src, kept, tiles) or tiles.dim() != 2 or tiles.shape[1] != 2 or src.numel() < sum_frames or \
+            dyb.dtype != torch.float32 or not dyb.is_contiguous() or dyb.dim() != 2 or dyb.shape[1] != STOI_BANDS or \
+            dyb.shape[0] < sum_frames:
+        _lib.check(_K["ERR_SHAPE"], "stoi_bands_bwd")
+    dframes = torch.empty(max(sum_frames, 1), STOI_FRAME, device=sig.device, dtype=torch.float32)
+    n_tiles = tiles.shape[0]
+    _call("stoi", L.sfm_stoi_bands_bwd, (_p(sig), _p(win), _p(dft), _p(dft_t), _p(sig_off), _p(frame_off), _p(src), _p(kept), _p(tiles),
+                                         _p(dyb), _p(dframes), n_tiles, _stream()),
+          2.0 * spec_rows * STOI_FRAME * (2 * STOI_NBIN + STOI_DFT_COLS),
+          4.0 * n_samples + 4.0 * (STOI_BANDS + STOI_FRAME) * spec_rows + 4.0 * STOI_FRAME * (2 * STOI_NBIN + STOI_DFT_COLS + 1) +
+          4.0 * sum_frames + 8.0 * n_tiles, "bands bwd rows%d" % spec_rows)
+    return dframes
+
+
+def stoi_fold_bwd(dframes, win, sig_off, sig_len, frame_off, src, kept, B, n_out, max_len, pad_to, sum_frames):
+    """the overlap-add adjoint: dframes (stoi_bands_bwd) -> dsig fp32 [n_out], utterance u's 10 kHz samples at sig_off[u], every
+    one written once (and zeros up to pad_to behind sig_len[u]: the rows of a zero-padded 10 kHz batch).  max_len: the largest
+    of sig_len and pad_to (host figures)."""
+    _need_dev(dframes, win, sig_off, sig_len, frame_off, src, kept)
+    L = _lib.load()
+    if dframes.dtype != torch.float32 or not dframes.is_contiguous() or dframes.dim() != 2 or dframes.shape[1] != STOI_FRAME or \
+            dframes.shape[0] < sum_frames or win.dtype != torch.float32 or win.numel() != STOI_FRAME or \
+            not _i32(sig_off, sig_len, frame_off, src, kept) or sig_off.numel() != B or sig_len.numel() != B or \
+            frame_off.numel() != B + 1 or kept.numel() != B or src.numel() < sum_frames or not 0 <= pad_to <= max_len:
+        _lib.check(_K["ERR_SHAPE"], "stoi_fold_bwd")
+    dsig = torch.empty(max(n_out, 1), device=dframes.device, dtype=torch.float32)
+    _call("stoi", L.sfm_stoi_fold_bwd, (_p(dframes), _p(win), _p(sig_off), _p(sig_len), _p(frame_off), _p(src), _p(kept), _p(dsig), B,
+                                        int(max_len), int(pad_to), _stream()),
+          8.0 * n_out, 4.0 * n_out + 4.0 * STOI_FRAME * sum_frames + 4.0 * sum_frames + 20.0 * B + 4.0 * STOI_FRAME,
+          "fold bwd B%d out%d" % (B, n_out))
+    return dsig

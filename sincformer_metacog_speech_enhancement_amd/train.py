@@ -787,6 +787,44 @@ class PerceptualStoiFunction(torch.autograd.Function):
         return _scaled_grads(grads, g, ctx.dtypes, 7)
 
 
+class StoiTaalFunction(torch.autograd.Function):
+    """evaluation.stoi_taal_scores: STOI / ESTOI of Taal et al. of a [B, L] batch (flat, rows of plan's lengths) -> (score fp64 [B],
+    kept int32 [B]), the forward kernels of compute_stoi_taal.  Saved for the backward (save_for_backward: freed with the graph,
+    kept under retain_graph, and an in-place change of the waveform - which at 10 kHz IS the saved signal - is detected): the
+    enhanced signal at 10 kHz, the kept list, both band-row sets; plan and tables are the caller's cached ones.  The gradient
+    goes to `enhanced` only: the kept list and the clean rows are constants of it; the cotangent [B] is read as fp64."""
+    SAVED = ("re", "src", "kept", "xb", "yb")
+
+    @staticmethod
+    def forward(ctx, enhanced, clean, plan, tabs, extended):
+        from .evaluation import stoi_taal as st
+        B = plan["B"]
+        ctx.meta = (plan, tabs, extended, enhanced.shape, enhanced.numel() // B)
+        ctx.constant = plan["sum_frames"] == 0                # no utterance reaches one frame: constants, a zero gradient
+        if ctx.constant:
+            score = torch.full((B,), st.TOO_SHORT, device=enhanced.device, dtype=torch.float64)
+            kept = torch.zeros(B, device=enhanced.device, dtype=torch.int32)
+        else:
+            a = st.analyse_flat(clean.detach().contiguous().reshape(-1), enhanced.detach().contiguous().reshape(-1), plan, tabs)
+            ctx.save_for_backward(*(a[k] for k in StoiTaalFunction.SAVED))
+            score = ops.stoi_segments(a["xb"], a["yb"], tabs["frame_off"], a["kept"], B, extended, plan["spec_rows"], plan["segments"])
+            kept = a["kept"]
+        ctx.mark_non_differentiable(kept)
+        return score, kept
+
+    @staticmethod
+    def backward(ctx, g, _):
+        from .evaluation import stoi_taal as st
+        plan, tabs, extended, shape, row = ctx.meta
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        if ctx.constant:
+            return torch.zeros(shape, device=g.device, dtype=torch.float32), None, None, None, None
+        a = dict(zip(StoiTaalFunction.SAVED, ctx.saved_tensors))
+        d = st.gradient_flat(a, plan, tabs, g.to(torch.float64).contiguous(), extended, row)
+        return d.reshape(shape), None, None, None, None
+
+
 class MseFunction(torch.autograd.Function):
     """nn.MSELoss() (MSEMaskLoss, training/losses.py:22-30): mean squared difference, summed in double in a fixed order.
     The gradient goes to `predicted` only; `target` gets None."""

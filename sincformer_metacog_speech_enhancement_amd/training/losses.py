@@ -89,6 +89,30 @@ class PerceptualSTOILoss(HipModule):
                                                   int(self.frame_len), float(self.beta))
 
 
+class TaalSTOILoss(HipModule):
+    """minus the mean STOI (extended: ESTOI) of Taal et al. over the utterances with at least 30 spectral frames - the measure
+    evaluation.compute_stoi_taal reports, on waveforms (train.IstftFunction returns one with a graph); the sign convention of
+    PerceptualSTOILoss.  An utterance below 30 frames scores a constant: it is left out of the mean and gets a zero gradient;
+    with no utterance left the loss is 0.  Which utterances count is decided on the device from the kept-frame counts.  The
+    gradient goes to `enhanced` only.  sample_rate 8, 10 or 16 kHz; extended=None follows config.STOI_EXTENDED at each call."""
+
+    def __init__(self, sample_rate=None, extended=None):
+        super().__init__()
+        from ..evaluation.stoi_taal import check_rate
+        self.sample_rate = check_rate(sample_rate or config.SAMPLE_RATE)
+        self.extended = extended
+
+    def forward(self, enhanced, clean, lengths=None):
+        """fp32 device waveforms [L] or [B, L] of one shape; lengths: host sequence [B], the sample counts of zero-padded rows
+        -> fp32 scalar"""
+        from ..evaluation import stoi_taal as st
+        self._require_device(enhanced, clean)
+        ext = config.STOI_EXTENDED if self.extended is None else self.extended
+        score, kept = st.scores_and_kept(enhanced, clean, self.sample_rate, bool(ext), lengths, "TaalSTOILoss")
+        q = (kept > st.SEG).to(torch.float64)                  # K - 1 >= 30 spectral frames
+        return (-(score * q).sum() / q.sum().clamp(min=1.0)).float()
+
+
 ADV_MIN_FRAMES = 4                  # 4 -> 2 -> 1 through the two pools; at 3 the second pool has no output
 ADV_CHANNELS = ((64, 128, 256, 512), (64, 128, 256), (32, 64, 128))
 
