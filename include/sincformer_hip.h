@@ -89,7 +89,8 @@ extern "C" {
 #define SFM_MOMENTS_CHUNK_ROWS 256     /* sfm_context_moments: rows of a chunk at least */
 #define SFM_MOMENTS_MAX_CHUNKS 1024    /* chunks at most; ws = (SFM_MOMENTS_MAX_CHUNKS + 1) D (2 ctx + 1) doubles */
 #define SFM_RESYNTH_TILE_FRAMES 64     /* frames a workgroup of sfm_mask_resynth computes; it owns one output hop fewer */
-#define SFM_RESYNTH_MAX_NFFT 256       /* the largest n_fft and frame its LDS layout holds */
+#define SFM_RESYNTH_BWD_TILE_FRAMES 64 /* frames, hence rows of dmask, a workgroup of sfm_mask_resynth_bwd computes */
+#define SFM_RESYNTH_MAX_NFFT 256      /* the largest n_fft and frame its LDS layout holds */
 #define SFM_RESYNTH_MAX_FRAME 256
 #define SFM_RESYNTH_MAX_CHANNELS 64
 #define SFM_RESYNTH_COL_ALIGN 32       /* operand columns (n_fft of Wf, frame of Wi) are zero padded to a multiple of this */
@@ -933,6 +934,26 @@ int sfm_mse_gather_loss(const float* y, const float* mask, const int* index, con
 int sfm_mask_resynth(const float* noisy, const float* mask, const int* lengths, const float* Wf, const float* Wi, const int* tab_idx,
                      const float* tab_wt, const float* inv_wsum, float* out, int B, int L, int T_mask, int frame, int hop, int n_fft,
                      int C, void* stream);
+
+/* The adjoint of sfm_mask_resynth with respect to the mask (resynth.hip), one launch, exact fp32 on v_mfma_f32_32x32x2_f32, no
+ * atomics.  The forward is linear in the mask, so the mask itself is no operand.  noisy [B, L] fp32 and lengths as there; dout
+ * [B, L] fp32 = the cotangent of out; dmask [B, T_mask, C] fp32, every element written: with N_b = min(T_b, T_mask),
+ *   dy_n[j] = dout[n hop + j] * inv_wsum[row of hop n + (j >= hop)][j mod hop]  (row 0 for the utterance's hop 0, 2 for hop N_b, else 1),
+ *   P_n = (frame_n(noisy) Wf) * (dy_n WiT) element by element, dg_n[k] = P_n[k] + P_n[F + k - 1] (the second for 1 <= k <= F - 2),
+ *   dmask[b, n, c] = sum over the bins of channel c - 1 of tab_wt[k] dg_n[k] + sum over the bins of channel c of (1 - tab_wt[k])
+ *   dg_n[k], each in ascending k, for n < N_b; rows n >= N_b are 0.
+ * Samples of noisy from L_b on and of dout from min(L_b, (N_b + 1) hop) on are not read (they have no influence on the forward).
+ * No gradient to noisy is offered.  The same bits from run to run and for an utterance alone or anywhere in a batch.
+ * Host-built operands, NC, FR, F as above:
+ *   Wf [FR, NC], tab_wt [NC] (its first F words, one per bin, are read), inv_wsum [3, hop]: those of sfm_mask_resynth.
+ *   WiT [FR, NC]: Wi transposed, row n < frame = the irfft coefficients of sample n times w[n] per spectrum column; zero beyond row
+ *     `frame` and column n_fft.
+ *   chan_bins int32 [C + 1]: the bins k with tab_idx[k] == c are chan_bins[c] .. chan_bins[c + 1] - 1 (tab_idx ascends with k), so
+ *     chan_bins[0] = 0 and chan_bins[C - 1] = chan_bins[C] = F; a channel that brackets no bin has an empty range.
+ * Shapes as sfm_mask_resynth (SFM_ERR_SHAPE otherwise). */
+int sfm_mask_resynth_bwd(const float* noisy, const float* dout, const int* lengths, const float* Wf, const float* WiT,
+                         const float* tab_wt, const float* inv_wsum, const int* chan_bins, float* dmask, int B, int L, int T_mask,
+                         int frame, int hop, int n_fft, int C, void* stream);
 
 /* RBM pre-training (rbm.hip; models/rbm.py of the reference: CD-k).  Everything fp32 on the device, every product exact fp32 on
  * v_mfma_f32_32x32x2_f32; W [n_visible, n_hidden] row-major as there.  No atomics: the same bits from run to run.

@@ -223,3 +223,160 @@ extern "C" int sfm_mask_resynth(const float* noisy, const float* mask, const int
   SFM_LAUNCH_LDS(mask_resynth_kernel, dim3((unsigned)(tiles * B)), dim3(RS_THREADS), lds, (hipStream_t)stream, p);
   return SFM_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// sfm_mask_resynth_bwd: the adjoint of sfm_mask_resynth with respect to the mask.  The forward is linear in the mask, so the
+// cotangent needs the noisy signal and dout alone:
+//   dy_n[j]   = dout[n hop + j] / wsum(n hop + j)              the forward's row choice: first hop, interior, last covered hop
+//   X  [R, NC] = frames [R, frame] x Wf  [FR, NC]              the forward's own first product
+//   dZ [R, NC] = dy     [R, frame] x WiT [FR, NC]              Wi transposed: the same shape, so rs_block<2> serves both
+//   P = X * dZ;   dg[k] = P[k] + P[F + k - 1] (the Im column exists for 1 <= k <= F - 2)
+//   dmask[n, c] = sum_{idx[k] == c - 1} wt[k] dg[k] + sum_{idx[k] == c} (1 - wt[k]) dg[k]
+// idx ascends with k, so both sums run over contiguous bins: chan_bins[c] .. chan_bins[c + 1] - 1 are the bins with idx == c.
+// A dmask row belongs to one frame, so workgroup t of an utterance computes the R = SFM_RESYNTH_BWD_TILE_FRAMES frames from t R on
+// and shares none with its neighbours.  The R + 1 hop rows of the signal and of dout / wsum (the quotient is formed on the way into
+// LDS, from the table in global memory: one round trip, no table plane) are staged, a wave owns column blocks and both row blocks so
+// that X and dZ of an element meet in its registers, and only P goes to LDS.  The fold turns the tile: lane = row, a wave walks
+// channels, so the trip count and the table words are wave-uniform and the reads of P (odd row stride) conflict-free; the R x C
+// result goes through LDS (over the dead signal planes) to stores with c fastest.  No atomics; rows from N_b on are written as 0;
+// dout is not read from min(L_b, (N_b + 1) hop) on.
+#define RSB_R SFM_RESYNTH_BWD_TILE_FRAMES
+static_assert(RSB_R == 64, "two 32-row MFMA blocks per tile, one fold row per lane");
+
+struct ResynthBwdParams {
+  const float* noisy;
+  const float* dout;
+  const int* lengths;
+  const float* Wf;
+  const float* WiT;
+  const float* tab_wt;
+  const float* inv_wsum;
+  const int* chan_bins;
+  float* dmask;
+  int B, L, T_mask, frame, hop, C, F, FK, NC, tiles;
+};
+
+// words of dynamic LDS: two signal planes of R + 1 hop rows (reused as the [R][65] result tile), the plane of P
+static inline long long resynth_bwd_lds_words(int hop, int NC) {
+  const long long S = hop | 1, planes = 2 * (RSB_R + 1) * S, tile = (long long)RSB_R * RS_MS;
+  return (planes > tile ? planes : tile) + (long long)RSB_R * (NC + 1);
+}
+
+__global__ __launch_bounds__(RS_THREADS) void mask_resynth_bwd_kernel(ResynthBwdParams p) {
+  extern __shared__ float rs_lds[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.x / p.tiles, t = blockIdx.x - b * p.tiles;
+  const int hop = p.hop, S = hop | 1, XS = p.NC + 1;
+  const int plane = (RSB_R + 1) * S;
+  float* sigL = rs_lds;                                   // [R + 1][S] hop rows of the signal
+  float* dyL = sigL + plane;                              // [R + 1][S] hop rows of dout / wsum
+  float* Ds = rs_lds;                                     // [R][65] the tile of dmask, once both products are done
+  float* Ps = rs_lds + max(2 * plane, RSB_R * RS_MS);     // [R][NC + 1] X * dZ
+
+  int Lb = p.lengths ? p.lengths[b] : p.L;
+  Lb = Lb < 0 ? 0 : (Lb > p.L ? p.L : Lb);
+  const int Tb = Lb >= p.frame ? (Lb - p.frame) / hop + 1 : 0;
+  const int Nb = Tb < p.T_mask ? Tb : p.T_mask;
+  const int f0 = t * RSB_R;
+  const int nrow = min(RSB_R, p.T_mask - f0);             // rows of dmask this tile owns (tiles = ceil(T_mask / R): at least 1)
+  float* dg = p.dmask + ((long long)b * p.T_mask + f0) * p.C;
+
+  if (f0 >= Nb) {                                         // no frame of this tile is live (workgroup-uniform): zeros
+    for (int i = tid; i < nrow * p.C; i += RS_THREADS) dg[i] = 0.f;
+    return;
+  }
+
+  // ---- stage: R + 1 hops of the signal (0 from L_b on) and of dout / wsum (0 from min(L_b, (N_b + 1) hop) on: never read there).
+  //      All of a thread's loads are issued before its first LDS store ----
+  {
+    constexpr int NS = ((RSB_R + 1) * (SFM_RESYNTH_MAX_FRAME / 2) + RS_THREADS - 1) / RS_THREADS;
+    const float* sg = p.noisy + (long long)b * p.L;
+    const float* dd = p.dout + (long long)b * p.L;
+    const long long live = (long long)(Nb + 1) * hop;
+    const long long lim = live < Lb ? live : (long long)Lb;
+    float vs[NS], vd[NS], vw[NS];
+    int at[NS];
+#pragma unroll
+    for (int u = 0; u < NS; ++u) {
+      const int i = tid + u * RS_THREADS, h = i / hop, j = i - h * hop, hg = f0 + h;
+      const bool in = i < (RSB_R + 1) * hop;
+      const long long s = (long long)f0 * hop + i;
+      const int row = hg == 0 ? 0 : (hg == Nb ? 2 : 1);   // first hop of the utterance, interior, last covered hop
+      at[u] = in ? h * S + j : -1;
+      vs[u] = (in && s < Lb) ? sg[s] : 0.f;
+      vd[u] = (in && s < lim) ? dd[s] : 0.f;
+      vw[u] = in ? p.inv_wsum[row * hop + j] : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < NS; ++u)
+      if (at[u] >= 0) {
+        sigL[at[u]] = vs[u];
+        dyL[at[u]] = vd[u] * vw[u];
+      }
+  }
+  __syncthreads();
+
+  // ---- both products, then P = X * dZ ----
+  const int l31 = lane & 31;
+  for (int cb = wave; cb < p.NC / 32; cb += RS_WAVES) {
+    f32x16 ax[2], az[2];
+    auto rows_of = [&](const float* pl) {
+      return [=](int j, int k) {
+        k = min(k, p.frame - 1);                          // rows frame .. FK of Wf and WiT are zero: any finite value serves
+        const int hr = k >= hop ? 1 : 0;
+        return pl[(j * 32 + l31 + hr) * S + k - hr * hop];
+      };
+    };
+    rs_block<2>(ax, p.Wf + cb * 32, p.NC, p.FK / 2, lane, rows_of(sigL));
+    rs_block<2>(az, p.WiT + cb * 32, p.NC, p.FK / 2, lane, rows_of(dyL));
+    const int col = cb * 32 + l31;
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) Ps[(j * 32 + mfma_row(r, lane)) * XS + col] = ax[j][r] * az[j][r];
+  }
+  __syncthreads();
+
+  // ---- channel fold: lane = row, the wave's channel is uniform; ascending bins, Re and Im column of each ----
+  {
+    const int wv = __builtin_amdgcn_readfirstlane(wave), F = p.F;
+    const float* pr = Ps + lane * XS;
+    auto bin = [&](int k) { return (k >= 1 && k <= F - 2) ? pr[k] + pr[F + k - 1] : pr[k]; };
+    for (int c = wv; c < p.C; c += RS_WAVES) {
+      const int k1 = min(max(p.chan_bins[c], 0), F), k2 = min(max(p.chan_bins[c + 1], k1), F);
+      float acc = 0.f;
+      if (c > 0) {
+        const int k0 = min(max(p.chan_bins[c - 1], 0), k1);
+        for (int k = k0; k < k1; ++k) acc = __builtin_fmaf(p.tab_wt[k], bin(k), acc);
+      }
+      for (int k = k1; k < k2; ++k) acc = __builtin_fmaf(1.f - p.tab_wt[k], bin(k), acc);
+      Ds[lane * RS_MS + c] = f0 + lane < Nb ? acc : 0.f;
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < nrow * 64; i += RS_THREADS) {
+    const int r = i >> 6, c = i & 63;
+    if (c < p.C) dg[r * p.C + c] = Ds[r * RS_MS + c];
+  }
+}
+
+extern "C" int sfm_mask_resynth_bwd(const float* noisy, const float* dout, const int* lengths, const float* Wf, const float* WiT,
+                                    const float* tab_wt, const float* inv_wsum, const int* chan_bins, float* dmask, int B, int L,
+                                    int T_mask, int frame, int hop, int n_fft, int C, void* stream) {
+  if (!noisy || !dout || !Wf || !WiT || !tab_wt || !inv_wsum || !chan_bins || !dmask) return SFM_ERR_ARG;
+  if (B <= 0 || L <= 0 || T_mask <= 0 || hop <= 0 || frame <= 0 || n_fft <= 0) return SFM_ERR_SHAPE;
+  if (hop * 2 != frame || frame > n_fft || (n_fft & 1) || C > SFM_RESYNTH_MAX_CHANNELS || C < 2) return SFM_ERR_SHAPE;
+  if (n_fft > SFM_RESYNTH_MAX_NFFT || frame > SFM_RESYNTH_MAX_FRAME) return SFM_ERR_SHAPE;
+  ResynthBwdParams p;
+  p.noisy = noisy; p.dout = dout; p.lengths = lengths; p.Wf = Wf; p.WiT = WiT; p.tab_wt = tab_wt; p.inv_wsum = inv_wsum;
+  p.chan_bins = chan_bins; p.dmask = dmask;
+  p.B = B; p.L = L; p.T_mask = T_mask; p.frame = frame; p.hop = hop; p.C = C; p.F = n_fft / 2 + 1;
+  p.NC = (n_fft + SFM_RESYNTH_COL_ALIGN - 1) / SFM_RESYNTH_COL_ALIGN * SFM_RESYNTH_COL_ALIGN;
+  p.FK = (frame + SFM_RESYNTH_COL_ALIGN - 1) / SFM_RESYNTH_COL_ALIGN * SFM_RESYNTH_COL_ALIGN;
+  const long long tiles = ((long long)T_mask + RSB_R - 1) / RSB_R;
+  if (tiles * B > 2147483647LL) return SFM_ERR_SHAPE;
+  p.tiles = (int)tiles;
+  const int lds = (int)(resynth_bwd_lds_words(hop, p.NC) * 4);
+  SFM_LAUNCH_LDS(mask_resynth_bwd_kernel, dim3((unsigned)(tiles * B)), dim3(RS_THREADS), lds, (hipStream_t)stream, p);
+  return SFM_OK;
+}

@@ -2814,6 +2814,7 @@ def mse_gather_loss(y, mask, index, *, loss_scale=None, need_dz=True, rec=None, 
 # Mask to waveform (csrc/resynth.hip; steps 2-4 of enhance_signal, training/pipeline.py:877-934)
 # ---------------------------------------------------------------------------
 RESYNTH_TILE_FRAMES = _K["RESYNTH_TILE_FRAMES"]    # frames a workgroup computes; it owns one output hop fewer
+RESYNTH_BWD_TILE_FRAMES = _K["RESYNTH_BWD_TILE_FRAMES"]    # frames (rows of dmask) a workgroup of the mask adjoint computes
 RESYNTH_MAX_NFFT = _K["RESYNTH_MAX_NFFT"]          # the largest n_fft / frame the kernel's LDS layout holds
 RESYNTH_MAX_FRAME = _K["RESYNTH_MAX_FRAME"]
 RESYNTH_MAX_CHANNELS = _K["RESYNTH_MAX_CHANNELS"]
@@ -2868,9 +2869,19 @@ def resynth_inv_wsum_host(frame, hop):
     return 1.0 / ws
 
 
-def resynth_operands(frame, hop, n_fft, fs, cf, device):
+def resynth_channel_bins(idx, C):
+    """the inverse of resynth_interp_table's idx (ascending in the bin k): int32 [C + 1] with the bins of lower channel c being
+    bins[c] .. bins[c + 1] - 1, so bins[0] = 0 and bins[C - 1] = bins[C] = F (no bin has the last channel as its lower one)"""
+    idx = np.asarray(idx, dtype=np.int64).reshape(-1)
+    if idx.size == 0 or np.any(np.diff(idx) < 0) or idx[0] < 0 or idx[-1] > C - 2:
+        raise ValueError("resynth_channel_bins: the lower channels must ascend within 0 .. C - 2")
+    return np.searchsorted(idx, np.arange(C + 1), side="left").astype(np.int32)
+
+
+def resynth_operands(frame, hop, n_fft, fs, cf, device, bwd=False):
     """the device operands of sfm_mask_resynth (Wf, Wi, tab_idx, tab_wt, inv_wsum), built in float64 and cast to fp32, cached by
-    (frame, hop, n_fft, fs, cf) per device (shared: do not modify)"""
+    (frame, hop, n_fft, fs, cf) per device (shared: do not modify).  bwd: followed by the two that sfm_mask_resynth_bwd adds, WiT
+    [FR, NC] (Wi transposed) and chan_bins int32 [C + 1] (resynth_channel_bins), built and cached with the five."""
     cf = np.ascontiguousarray(cf, dtype=np.float64).reshape(-1)
     key = (int(frame), int(hop), int(n_fft), float(fs), cf.tobytes(), str(device))
     ops_ = _RESYNTH_OPS.get(key)
@@ -2887,12 +2898,12 @@ def resynth_operands(frame, hop, n_fft, fs, cf, device):
         tab_idx = np.zeros(NC, dtype=np.int32)
         tab_wt = np.zeros(NC, dtype=np.float32)
         tab_idx[:n_fft], tab_wt[:n_fft] = idx[col_bin], wt[col_bin]
-        host = (Wf, Wi, tab_idx, tab_wt, resynth_inv_wsum_host(frame, hop).astype(np.float32))
+        host = (Wf, Wi, tab_idx, tab_wt, resynth_inv_wsum_host(frame, hop).astype(np.float32), Wi.T, resynth_channel_bins(idx, cf.size))
         ops_ = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(device) for a in host)
         if len(_RESYNTH_OPS) >= RESYNTH_OPS_CACHE:
             _RESYNTH_OPS.clear()
         _RESYNTH_OPS[key] = ops_
-    return ops_
+    return ops_ if bwd else ops_[:5]
 
 
 def mask_resynth(noisy, mask, lengths=None, *, frame, hop, n_fft, fs, cf, out=None, frames=None):
@@ -2922,6 +2933,37 @@ def mask_resynth(noisy, mask, lengths=None, *, frame, hop, n_fft, fs, cf, out=No
     _call("resynth", L_.sfm_mask_resynth, (_p(noisy), _p(mask), _p(lengths), _p(Wf), _p(Wi), _p(tab_idx), _p(tab_wt), _p(inv_wsum),
                                            _p(out), B, L, T_mask, frame, hop, n_fft, C, _stream()),
           (2.0 * frame * two_f + 2.0 * two_f * frame) * frames, nbytes, "B%d L%d T%d f%d n%d C%d" % (B, L, T_mask, frame, n_fft, C))
+    return out
+
+
+def mask_resynth_bwd(noisy, dout, lengths=None, *, frame, hop, n_fft, fs, cf, T_mask, out=None, frames=None):
+    """noisy [B, L] fp32, dout [B, L] fp32 (the cotangent of mask_resynth's result), lengths as there -> dmask [B, T_mask, C] fp32,
+    the cotangent of the mask, every element written: one sfm_mask_resynth_bwd launch.  The forward is linear in the mask, so the
+    mask is no argument; the gradient to `noisy` is not offered.  frames: as mask_resynth, for the stated cost."""
+    _need_dev(noisy, dout, lengths, out)
+    L_ = _lib.load()
+    C = len(cf)
+    ok = noisy.dim() == 2 and dout.dim() == 2 and noisy.dtype == torch.float32 and dout.dtype == torch.float32
+    ok = ok and noisy.is_contiguous() and dout.is_contiguous() and noisy.numel() > 0 and dout.shape == noisy.shape
+    ok = ok and int(T_mask) > 0 and resynth_supported(frame, hop, n_fft, C)
+    ok = ok and (lengths is None or (lengths.dtype == torch.int32 and lengths.is_contiguous() and lengths.numel() == noisy.shape[0]))
+    if not ok:
+        _lib.check(_K["ERR_SHAPE"], "mask_resynth_bwd")
+    B, L = noisy.shape
+    T_mask = int(T_mask)
+    if out is None:
+        out = torch.empty(B, T_mask, C, device=noisy.device, dtype=torch.float32)
+    if tuple(out.shape) != (B, T_mask, C) or out.dtype != torch.float32 or not out.is_contiguous():
+        _lib.check(_K["ERR_SHAPE"], "mask_resynth_bwd")
+    Wf, _, _, tab_wt, inv_wsum, WiT, chan_bins = resynth_operands(frame, hop, n_fft, fs, cf, noisy.device, bwd=True)
+    if frames is None:
+        frames = B * min((L - frame) // hop + 1 if L >= frame else 0, T_mask)
+    two_f = n_fft + 2
+    nbytes = 4.0 * (noisy.numel() + dout.numel() + Wf.numel() + WiT.numel() + tab_wt.numel() + inv_wsum.numel() + chan_bins.numel() +
+                    (0 if lengths is None else B) + out.numel())
+    _call("resynth_bwd", L_.sfm_mask_resynth_bwd, (_p(noisy), _p(dout), _p(lengths), _p(Wf), _p(WiT), _p(tab_wt), _p(inv_wsum),
+                                                   _p(chan_bins), _p(out), B, L, T_mask, frame, hop, n_fft, C, _stream()),
+          2.0 * (2.0 * frame * two_f) * frames, nbytes, "B%d L%d T%d f%d n%d C%d" % (B, L, T_mask, frame, n_fft, C))
     return out
 
 

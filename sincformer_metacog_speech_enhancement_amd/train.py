@@ -1349,6 +1349,27 @@ class IstftFunction(torch.autograd.Function):
         return dr.to(d0), di.to(d1), None, None, None, None
 
 
+class ResynthFunction(torch.autograd.Function):
+    """training.resynthesize (steps 2-4 of enhance_signal) with its adjoint in the mask: forward = ops.mask_resynth, the bits of the
+    call without autograd; backward = one ops.mask_resynth_bwd launch on the cotangent.  The forward is linear in the mask, so
+    the mask is not kept: saved are the noisy waveforms and the device lengths (save_for_backward).  framing = the keywords of
+    both launches (frame, hop, n_fft, fs, cf); frames: the live frames, for the stated costs.  The gradient goes to `mask` only
+    (training.resynthesize refuses a noisy signal that requires one); no second derivative."""
+
+    @staticmethod
+    def forward(ctx, noisy, mask, lengths, frames, framing):
+        ctx.save_for_backward(noisy, lengths)
+        ctx.meta = (mask.shape[1], frames, framing)
+        return ops.mask_resynth(noisy, mask.detach(), lengths, frames=frames, **framing)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        noisy, lengths = ctx.saved_tensors
+        T_mask, frames, framing = ctx.meta
+        return None, ops.mask_resynth_bwd(noisy, g.contiguous(), lengths, T_mask=T_mask, frames=frames, **framing), None, None, None
+
+
 # ---------------------------------------------------------------------------
 # PerceptionAgent (agents/perception.py:132-254) in training mode
 # ---------------------------------------------------------------------------

@@ -88,9 +88,12 @@ def dnn_estimate_mask(dnn, noisy, fe=None, lengths=None, feat_mean=None, feat_st
     """-> the estimated mask [B, T, dnn.output_dim] (1-D signal: [T, .]) in [0, 1] of fp32 device waveforms noisy [B, L]:
     FeatureExtractor.extract_frame_features, then dnn.forward_frames (the context rows, normalised and clipped with the checkpoint's
     feat_mean / feat_std when given, are formed inside the first layer's launch), then the clip to [0, 1].  lengths: the sample counts
-    of a zero-padded batch; rows from an utterance's T_b on are those of zero input rows."""
+    of a zero-padded batch; rows from an utterance's T_b on are those of zero input rows.  Under autograd (dnn in train() or with
+    enable_eval_autograd()) the mask carries the history of train.DnnFunction and the clip is out of place - the node keeps its
+    output for its backward - and passes the gradient on [0, 1] inclusive, as torch.clamp does."""
     raw = _fe_for(fe).extract_frame_features(noisy, lengths=lengths)
-    return dnn.forward_frames(raw, feat_mean, feat_std, lengths=_frame_counts(lengths)).clamp_(0.0, 1.0)
+    mask = dnn.forward_frames(raw, feat_mean, feat_std, lengths=_frame_counts(lengths))
+    return mask.clamp(0.0, 1.0) if mask.requires_grad else mask.clamp_(0.0, 1.0)
 
 
 _default_cf = []
@@ -104,7 +107,11 @@ def resynthesize(noisy, mask, lengths=None, fs=None, center_freqs=None, *, frame
     on contribute nothing; samples no such frame covers are 0, so an utterance shorter than one frame gives zeros (the reference
     raises below one hop).  The mask is used as given: the clip to [0, 1] is dnn_estimate_mask's.  lengths: the sample counts of a
     zero-padded batch.  fs: config.SAMPLE_RATE; center_freqs: erb_space(FREQ_LOW, FREQ_HIGH, NUM_CHANNELS), any ascending
-    frequencies, one per mask channel; frame, hop, n_fft: config's framing.  No autograd history."""
+    frequencies, one per mask channel; frame, hop, n_fft: config's framing.
+    Autograd: when it is enabled and the mask requires a gradient, the result carries train.ResynthFunction, whose backward is one
+    launch of the adjoint in the mask (ops.mask_resynth_bwd; the waveform is linear in the mask); the forward's bits are the same.
+    In every other case the result has no history.  The gradient to `noisy` does not exist here: a noisy signal that requires one
+    raises NotImplementedError under autograd, and the node has no second derivative."""
     fs = config.SAMPLE_RATE if fs is None else fs
     frame = config.FRAME_SIZE if frame is None else int(frame)
     hop = config.HOP_SIZE if hop is None else int(hop)
@@ -120,6 +127,9 @@ def resynthesize(noisy, mask, lengths=None, fs=None, center_freqs=None, *, frame
             raise ValueError("resynthesize: %s must be an fp32 tensor of %d or %d dimensions" % ((name,) + dims))
     if (noisy.dim() == 1) != (mask.dim() == 2):
         raise ValueError("resynthesize: noisy %s and mask %s: both batched or both single" % (tuple(noisy.shape), tuple(mask.shape)))
+    if torch.is_grad_enabled() and noisy.requires_grad:
+        raise NotImplementedError("resynthesize: the gradient with respect to the noisy signal is not implemented (only the mask's "
+                                  "is: ops.mask_resynth_bwd); detach `noisy`")
     one_d = noisy.dim() == 1
     y, m = (noisy.reshape(1, -1), mask.unsqueeze(0)) if one_d else (noisy, mask)
     B, L = y.shape
@@ -147,14 +157,23 @@ def resynthesize(noisy, mask, lengths=None, fs=None, center_freqs=None, *, frame
         host = np.clip(host, 0, L)
         dev_lengths = torch.from_numpy(host.astype(np.int32)).to(y.device)
     frames = int(np.minimum(np.where(host >= frame, (host - frame) // hop + 1, 0), T_mask).sum())
-    out = ops.mask_resynth(y.detach().contiguous(), m.detach().contiguous(), dev_lengths, frame=frame, hop=hop, n_fft=n_fft, fs=fs,
-                           cf=cf, frames=frames)
+    if torch.is_grad_enabled() and m.requires_grad:
+        from .. import train
+        out = train.ResynthFunction.apply(y.detach().contiguous(), m.contiguous(), dev_lengths, frames,
+                                          dict(frame=frame, hop=hop, n_fft=n_fft, fs=fs, cf=cf))
+    else:
+        out = ops.mask_resynth(y.detach().contiguous(), m.detach().contiguous(), dev_lengths, frame=frame, hop=hop, n_fft=n_fft, fs=fs,
+                               cf=cf, frames=frames)
     return out[0] if one_d else out
 
 
 def dnn_enhance_signal(dnn, noisy, fe=None, lengths=None, feat_mean=None, feat_std=None):
     """-> the enhanced waveforms [B, L] (1-D signal: [L]): the whole of enhance_signal (:819-934) for a batch,
-    resynthesize(noisy, dnn_estimate_mask(dnn, noisy, ...), lengths) with config's framing and centre frequencies."""
+    resynthesize(noisy, dnn_estimate_mask(dnn, noisy, ...), lengths) with config's framing and centre frequencies.  With dnn in
+    train() or with enable_eval_autograd() the result is differentiable with respect to the DNN's parameters (train.DnnFunction,
+    the clip, train.ResynthFunction), so a waveform objective trains the mask estimator, e.g.
+    TaalSTOILoss(extended=True)(dnn_enhance_signal(dnn, noisy, lengths=l), clean, l).backward(); in eval() without it nothing is
+    recorded."""
     return resynthesize(noisy, dnn_estimate_mask(dnn, noisy, fe=fe, lengths=lengths, feat_mean=feat_mean, feat_std=feat_std), lengths)
 
 
