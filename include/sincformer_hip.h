@@ -1039,6 +1039,25 @@ int sfm_stoi_bands(const float* sig0, const float* sig1, const float* win, const
  * once, SFM_STOI_SEG_TILE segments per stage, the segment values added in segment order.  No row from K_u - 1 on is read. */
 int sfm_stoi_segments(const float* xb, const float* yb, const int* frame_off, const int* kept, double* score, int B, int extended,
                       void* stream);
+/* The measure as the fitness of the OPT-PCIRM search (masks/opt_pcirm.py:146-183 with evaluation/stoi.py:46-50; stoi.hip).  The
+ * candidate x gives the enhanced signal ya + x yb (sfm_pso_split); the resampler, the kept list (the clean signal's), the
+ * overlap-add and the windowed DFT are linear in it, so spectral frame m is A_m + x B_m and the energy of band j is
+ *   E(x) = P + 2 x Q + x^2 R,  P = sum_k |A_k|^2,  Q = sum_k Re(A_k conj B_k),  R = sum_k |B_k|^2  over the band's bins.
+ * sfm_stoi_bands_pair: sfm_stoi_bands' grid, tile and operands for siga = ya and sigb = yb at SFM_STOI_FS -> planes fp64
+ *   [frame_off[B], SFM_STOI_PLANES, SFM_STOI_BANDS]: row frame_off[u] + m holds P | Q | R of spectral frame m; rows from K_u - 1 on
+ *   are not written.  The products a a, a b, b b are formed from the fp64 accumulators (Q never by a difference of band rows).
+ *   Dynamic LDS (two A tiles, 65792 B), granted by the launcher.  n_tiles = 0 launches nothing, tiles may then be NULL.
+ * sfm_pso_fitness_taal: fitness [B, N] fp64 = sfm_stoi_segments' score of the clean rows xb (sfm_stoi_bands, fp32) against the rows
+ *   sqrt(max(E(x), 0)) in fp64 at x = pos[u, p] rounded to fp32 (the mask array holds the middle value so), formed while the ring is
+ *   filled; 1e-5 where K_u - 1 < SFM_STOI_SEG.  One workgroup per (particle, utterance), the segment arithmetic is the one function
+ *   sfm_stoi_segments runs.  A swarm whose stopped[u] is set is skipped (its row of fitness is left as it is).
+ *   B <= 65535, 1 <= N <= SFM_PSO_MAX_PARTICLES, extended 0 / 1 as sfm_stoi_segments. */
+#define SFM_STOI_PLANES 3
+int sfm_stoi_bands_pair(const float* siga, const float* sigb, const float* win, const float* dft, const int* sig_off,
+                        const int* frame_off, const int* src, const int* kept, const int* tiles, double* planes, int n_tiles,
+                        void* stream);
+int sfm_pso_fitness_taal(const float* xb, const double* planes, const int* frame_off, const int* kept, const double* pos,
+                         const int* stopped, double* fitness, int B, int N, int extended, void* stream);
 /* The gradient of the measure with respect to the ENHANCED signal (stoi_bwd.hip), three kernels that walk the forward back; the
  * kept list and K_u belong to the clean signal and are constants, so the gradient is exact.  A norm at the zero vector and a band
  * value of exactly 0 pass nothing back.  fp32 operands and stored results, every sum fp64 in a fixed order, no atomics.

@@ -19,6 +19,9 @@
 //                           is compiled with -ffp-contract=off (build.py), sums over the particles follow numpy's pairwise rule
 //   pso_quantize_kernel     the final mask, each utterance quantised with its own middle value
 // No atomics anywhere: the same bits from run to run, and an utterance gets the same bits alone and in any batch.
+// The search on the STOI / ESTOI of Taal et al. uses the first two and the last two kernels as they are; its fitness
+// (pso_fitness_taal_kernel) stands in stoi.hip beside the segment arithmetic it shares with the measure, which is compiled with
+// fused multiply-adds - this file is not - and hands pso_step_kernel its values as `fit_in`.
 #include "sfm_common.h"
 #include <math.h>
 

@@ -1,5 +1,5 @@
 // STOI (Taal et al. 2011) and ESTOI (Jensen & Taal 2016) at 10 kHz: what evaluation/stoi.py:46-50 of the reference computes when
-// pystoi is installed.  Four kernels (include/sincformer_hip.h states the layouts):
+// pystoi is installed.  Four kernels of the measure (include/sincformer_hip.h states the layouts):
 //   stoi_resample_kernel  the polyphase FIR to 10 kHz, fp32 operands, fp64 sums
 //   stoi_keep_kernel      one workgroup per utterance: frame energies of the clean signal in fp64, their maximum, the keep mask,
 //                         an exclusive scan of the mask -> the list of kept source frames and its length K (device data)
@@ -10,6 +10,10 @@
 //                         score by up to 1e-7, more than the float32-operand evaluation's own error: profiles/README.md round 26)
 //   stoi_segments_kernel  one workgroup per utterance: band rows through a ring in LDS (each read once), the 15 x 30 segment
 //                         terms in fp64, added in segment order
+// and for the OPT-PCIRM search that climbs this measure (masks/opt_pcirm.py, "fitness": "stoi_taal" / "estoi"):
+//   stoi_bands_pair_kernel  stoi_bands_kernel for ya and yb at once -> the fp64 planes P | Q | R of the band energy P + 2 x Q + x^2 R
+//   pso_fitness_taal_kernel one workgroup per (particle, utterance): the segment kernel's walk with the enhanced rows formed from the
+//                           planes at the particle's x; the segment arithmetic itself (sk_score) exists once
 // No atomics; every cross-lane sum is a fixed butterfly in fp64, so an utterance's bits do not depend on what it is packed with.
 #include "sfm_common.h"
 
@@ -171,6 +175,112 @@ __global__ __launch_bounds__(256) void stoi_bands_kernel(const float* __restrict
   }
 }
 
+// stoi_bands_kernel for the two signals ya, yb of the OPT-PCIRM search (pso.hip: the candidate's enhanced signal is ya + x yb), which
+// share the clean signal's kept list.  Spectral frame m of ya + x yb is A + x B, so the energy of band j is P + 2 x Q + x^2 R with
+// P = sum |A_k|^2, Q = sum Re(A_k conj B_k), R = sum |B_k|^2 over the band's bins: planes[frame_off[u] + m][3][15] in fp64 (the quadratic
+// is evaluated at arbitrary x later; Q is formed from the fp64 products, never by a difference of rounded band rows).  Both tiles
+// are rebuilt and windowed side by side (dynamic LDS: two A tiles), one B fragment of the DFT operand feeds both accumulator sets,
+// which share their lane layout: a a, a b, b b are formed in registers and go through the one product tile, one plane after the other.
+#define SK_PAIR_LDS (2 * SFM_STOI_ROW_TILE * SK_AS * (int)sizeof(double))
+static_assert(2 * SK_AS >= SK_CS, "the product tile fits in the two A tiles");
+
+__global__ __launch_bounds__(256) void stoi_bands_pair_kernel(const float* __restrict__ siga, const float* __restrict__ sigb,
+                                                              const float* __restrict__ win, const float* __restrict__ dft,
+                                                              const int* __restrict__ sig_off, const int* __restrict__ frame_off,
+                                                              const int* __restrict__ src, const int* __restrict__ kept,
+                                                              const int* __restrict__ tiles, double* __restrict__ planes) {
+  extern __shared__ double pair_tile[];                     // the A tiles [2][16][257], then the products [16][433]
+  __shared__ int stab[SFM_STOI_ROW_TILE + 2];               // src[m0 - 1 .. m0 + 16]
+  double* tile = pair_tile;
+  double* tile_b = pair_tile + SFM_STOI_ROW_TILE * SK_AS;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int u = tiles[2 * blockIdx.x], m0 = tiles[2 * blockIdx.x + 1] * SFM_STOI_ROW_TILE;
+  const int f0 = frame_off[u], K = kept[u], M = K - 1;      // M spectral frames: the last kept frame starts none
+  if (m0 >= M) return;
+  const float* xa = siga + sig_off[u];
+  const float* xb = sigb + sig_off[u];
+  if (tid < SFM_STOI_ROW_TILE + 2) {
+    const int k = m0 - 1 + tid;
+    stab[tid] = (k >= 0 && k < K) ? src[f0 + k] : 0;
+  }
+  __syncthreads();
+  {
+    const int n = tid, no = tid ^ SFM_STOI_HOP;
+    const double wn = (double)win[n], wo = (double)win[no];
+    for (int r = 0; r < SFM_STOI_ROW_TILE; ++r) {
+      const int m = m0 + r;
+      double za = 0.0, zb = 0.0;
+      if (m < M) {
+        const long long c = (long long)stab[r + 1] * SFM_STOI_HOP + n;
+        double va = wn * (double)xa[c], vb = wn * (double)xb[c];
+        if (n >= SFM_STOI_HOP) {                            // head of kept frame m + 1
+          const long long o = (long long)stab[r + 2] * SFM_STOI_HOP + no;
+          va += wo * (double)xa[o];
+          vb += wo * (double)xb[o];
+        } else if (m >= 1) {                                // tail of kept frame m - 1
+          const long long o = (long long)stab[r] * SFM_STOI_HOP + no;
+          va += wo * (double)xa[o];
+          vb += wo * (double)xb[o];
+        }
+        za = wn * va;
+        zb = wn * vb;
+      }
+      tile[r * SK_AS + n] = za;
+      tile_b[r * SK_AS + n] = zb;
+    }
+  }
+  __syncthreads();
+  constexpr int NCT = SFM_STOI_DFT_COLS / 16;               // 27 column tiles: wave w takes w, w + 4, .. (7, 7, 7, 6)
+  constexpr int NJ = (NCT + 3) / 4;
+  f64x4 acca[NJ], accb[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) acca[j] = accb[j] = f64x4{0.0, 0.0, 0.0, 0.0};
+  const double* apa = tile + (lane & 15) * SK_AS + (lane >> 4);
+  const double* apb = tile_b + (lane & 15) * SK_AS + (lane >> 4);
+  const float* bp = dft + (long long)(lane >> 4) * SFM_STOI_DFT_COLS + wave * 16 + (lane & 15);
+#pragma unroll 2
+  for (int ks = 0; ks < SFM_STOI_FRAME / 4; ++ks) {
+    const double a = apa[4 * ks], b = apb[4 * ks];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      if (wave + 4 * j < NCT) {
+        const double bv = (double)bp[(long long)(4 * ks) * SFM_STOI_DFT_COLS + 64 * j];
+        acca[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bv, acca[j], 0, 0, 0);
+        accb[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(b, bv, accb[j], 0, 0, 0);
+      }
+    }
+  }
+  // rows and columns of this lane's four results, asked of the instruction as stoi_bands_kernel asks
+  const double idx = (lane >> 4) == 0 ? (double)(lane & 15) : 0.0, one = (lane >> 4) == 0 ? 1.0 : 0.0;
+  const f64x4 zero = {0.0, 0.0, 0.0, 0.0};
+  const f64x4 drow = __builtin_amdgcn_mfma_f64_16x16x4f64(idx, one, zero, 0, 0, 0);
+  const f64x4 dcol = __builtin_amdgcn_mfma_f64_16x16x4f64(one, idx, zero, 0, 0, 0);
+#pragma unroll
+  for (int pl = 0; pl < SFM_STOI_PLANES; ++pl) {
+    __syncthreads();                                        // every wave has read its A fragments / the last plane's products
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      if (wave + 4 * j < NCT) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = min(max((int)drow[r], 0), SFM_STOI_ROW_TILE - 1), col = min(max((int)dcol[r], 0), 15);
+          const double l = pl == 2 ? accb[j][r] : acca[j][r], h = pl == 0 ? acca[j][r] : accb[j][r];
+          tile[row * SK_CS + (wave + 4 * j) * 16 + col] = l * h;
+        }
+      }
+    }
+    __syncthreads();
+    for (int it = tid; it < SFM_STOI_ROW_TILE * SFM_STOI_BANDS; it += 256) {
+      const int r = it / SFM_STOI_BANDS, b = it - r * SFM_STOI_BANDS;
+      if (m0 + r >= M) continue;
+      const double* row = tile + r * SK_CS;
+      double s = 0.0;
+      for (int c = sk_edges[b] - SFM_STOI_FIRST_BIN; c < sk_edges[b + 1] - SFM_STOI_FIRST_BIN; ++c) s += row[c] + row[SK_NBIN + c];
+      planes[((long long)(f0 + m0 + r) * SFM_STOI_PLANES + pl) * SFM_STOI_BANDS + b] = s;
+    }
+  }
+}
+
 // Step 0, the polyphase resampler: out sample n = t up + p of utterance u = sum_k in[t down + k - padl] taps[k][p] over the samples
 // the utterance has, fp32 operands, the sum an fma chain in fp64 in k order, stored as fp32.  One thread per output sample.
 __global__ __launch_bounds__(256) void stoi_resample_kernel(const float* __restrict__ in, const float* __restrict__ taps,
@@ -190,19 +300,32 @@ __global__ __launch_bounds__(256) void stoi_resample_kernel(const float* __restr
   out[(long long)out_off[u] + n] = (float)acc;
 }
 
-template <bool EXT>
-__global__ __launch_bounds__(256) void stoi_segments_kernel(const float* __restrict__ xb, const float* __restrict__ yb,
-                                                            const int* __restrict__ frame_off, const int* __restrict__ kept,
-                                                            double* __restrict__ score) {
-  __shared__ float ring[2][SK_RING][SFM_STOI_BANDS];
+// Steps 4 and 5 for one utterance of M >= SFM_STOI_SEG spectral frames, by the whole workgroup: the band rows go through a ring in
+// LDS, SFM_STOI_SEG_TILE segments per stage, each element fetched once through load(i, x, y), i = row * SFM_STOI_BANDS + band (x the
+// clean value, y the other signal's, held as TY); a wave takes one segment at a time, one lane per band (STOI: scale, clip,
+// correlate) or per band and then per frame (ESTOI: rows, then columns normalised); the segment values are added in segment order.
+// -> the score, on thread 0.  The one statement of the segment arithmetic: stoi_segments_kernel and pso_fitness_taal_kernel call it.
+template <typename T>
+static __device__ __forceinline__ void sk_row_norm(const T (*ring)[SFM_STOI_BANDS], double (*out)[SFM_STOI_SEG], int r0, int lane) {
+  double s = 0.0;
+  for (int n = 0; n < SFM_STOI_SEG; ++n) s += (double)ring[(r0 + n) & (SK_RING - 1)][lane];
+  const double mean = s / SFM_STOI_SEG;
+  double ss = 0.0;
+  for (int n = 0; n < SFM_STOI_SEG; ++n) {
+    const double d = (double)ring[(r0 + n) & (SK_RING - 1)][lane] - mean;
+    ss += d * d;
+  }
+  const double inv = 1.0 / (sqrt(ss) + SK_EPS);
+  for (int n = 0; n < SFM_STOI_SEG; ++n) out[lane][n] = ((double)ring[(r0 + n) & (SK_RING - 1)][lane] - mean) * inv;
+}
+
+template <bool EXT, typename TY, typename LOAD>
+static __device__ __forceinline__ double sk_score(int M, LOAD load) {
+  __shared__ float ringx[SK_RING][SFM_STOI_BANDS];
+  __shared__ TY ringy[SK_RING][SFM_STOI_BANDS];
   __shared__ double rows[EXT ? 4 : 1][2][SFM_STOI_BANDS][SFM_STOI_SEG];      // ESTOI: the row-normalised block of each wave
   __shared__ double segval[SFM_STOI_SEG_TILE];
-  const int u = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int f0 = frame_off[u], M = kept[u] - 1;
-  if (M < SFM_STOI_SEG) {
-    if (tid == 0) score[u] = 1e-5;
-    return;
-  }
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nseg = M - SFM_STOI_SEG + 1;
   const double clip = 1.0 + 5.623413251903491;              // 1 + 10^(15/20)
   double acc = 0.0;
@@ -212,8 +335,7 @@ __global__ __launch_bounds__(256) void stoi_segments_kernel(const float* __restr
     const int need = s0 + cnt - 1 + SFM_STOI_SEG;            // rows [0, need) serve the segments up to s0 + cnt - 1; need <= M
     for (int i = loaded * SFM_STOI_BANDS + tid; i < need * SFM_STOI_BANDS; i += 256) {
       const int r = i / SFM_STOI_BANDS, b = i - r * SFM_STOI_BANDS;
-      ring[0][r & (SK_RING - 1)][b] = xb[(long long)f0 * SFM_STOI_BANDS + i];
-      ring[1][r & (SK_RING - 1)][b] = yb[(long long)f0 * SFM_STOI_BANDS + i];
+      load(i, ringx[r & (SK_RING - 1)][b], ringy[r & (SK_RING - 1)][b]);
     }
     loaded = need;
     __syncthreads();
@@ -226,21 +348,21 @@ __global__ __launch_bounds__(256) void stoi_segments_kernel(const float* __restr
         if (active && lane < SFM_STOI_BANDS) {
           double sx2 = 0.0, sy2 = 0.0;
           for (int n = 0; n < SFM_STOI_SEG; ++n) {
-            const double xv = (double)ring[0][(r0 + n) & (SK_RING - 1)][lane], yv = (double)ring[1][(r0 + n) & (SK_RING - 1)][lane];
+            const double xv = (double)ringx[(r0 + n) & (SK_RING - 1)][lane], yv = (double)ringy[(r0 + n) & (SK_RING - 1)][lane];
             sx2 += xv * xv;
             sy2 += yv * yv;
           }
           const double alpha = sqrt(sx2) / (sqrt(sy2) + SK_EPS);
           double sx = 0.0, sy = 0.0;
           for (int n = 0; n < SFM_STOI_SEG; ++n) {
-            const double xv = (double)ring[0][(r0 + n) & (SK_RING - 1)][lane], yv = (double)ring[1][(r0 + n) & (SK_RING - 1)][lane];
+            const double xv = (double)ringx[(r0 + n) & (SK_RING - 1)][lane], yv = (double)ringy[(r0 + n) & (SK_RING - 1)][lane];
             sx += xv;
             sy += fmin(alpha * yv, xv * clip);
           }
           const double mx = sx / SFM_STOI_SEG, my = sy / SFM_STOI_SEG;
           double sxx = 0.0, syy = 0.0, sxy = 0.0;
           for (int n = 0; n < SFM_STOI_SEG; ++n) {
-            const double xv = (double)ring[0][(r0 + n) & (SK_RING - 1)][lane], yv = (double)ring[1][(r0 + n) & (SK_RING - 1)][lane];
+            const double xv = (double)ringx[(r0 + n) & (SK_RING - 1)][lane], yv = (double)ringy[(r0 + n) & (SK_RING - 1)][lane];
             const double dx = xv - mx, dy = fmin(alpha * yv, xv * clip) - my;
             sxx += dx * dx;
             syy += dy * dy;
@@ -250,20 +372,8 @@ __global__ __launch_bounds__(256) void stoi_segments_kernel(const float* __restr
         }
       } else {
         if (active && lane < SFM_STOI_BANDS) {
-#pragma unroll
-          for (int q = 0; q < 2; ++q) {
-            double s = 0.0;
-            for (int n = 0; n < SFM_STOI_SEG; ++n) s += (double)ring[q][(r0 + n) & (SK_RING - 1)][lane];
-            const double mean = s / SFM_STOI_SEG;
-            double ss = 0.0;
-            for (int n = 0; n < SFM_STOI_SEG; ++n) {
-              const double d = (double)ring[q][(r0 + n) & (SK_RING - 1)][lane] - mean;
-              ss += d * d;
-            }
-            const double inv = 1.0 / (sqrt(ss) + SK_EPS);
-            for (int n = 0; n < SFM_STOI_SEG; ++n)
-              rows[wave][q][lane][n] = ((double)ring[q][(r0 + n) & (SK_RING - 1)][lane] - mean) * inv;
-          }
+          sk_row_norm(ringx, rows[wave][0], r0, lane);
+          sk_row_norm(ringy, rows[wave][1], r0, lane);
         }
         __syncthreads();
         if (active && lane < SFM_STOI_SEG) {
@@ -291,7 +401,55 @@ __global__ __launch_bounds__(256) void stoi_segments_kernel(const float* __restr
       for (int i = 0; i < cnt; ++i) acc += segval[i];
     __syncthreads();
   }
-  if (tid == 0) score[u] = EXT ? acc / nseg : acc / ((double)nseg * SFM_STOI_BANDS);
+  return EXT ? acc / nseg : acc / ((double)nseg * SFM_STOI_BANDS);
+}
+
+template <bool EXT>
+__global__ __launch_bounds__(256) void stoi_segments_kernel(const float* __restrict__ xb, const float* __restrict__ yb,
+                                                            const int* __restrict__ frame_off, const int* __restrict__ kept,
+                                                            double* __restrict__ score) {
+  const int u = blockIdx.x, tid = threadIdx.x;
+  const int M = kept[u] - 1;
+  if (M < SFM_STOI_SEG) {
+    if (tid == 0) score[u] = 1e-5;
+    return;
+  }
+  const float* xr = xb + (long long)frame_off[u] * SFM_STOI_BANDS;
+  const float* yr = yb + (long long)frame_off[u] * SFM_STOI_BANDS;
+  const double s = sk_score<EXT, float>(M, [&](int i, float& x, float& y) {
+    x = xr[i];
+    y = yr[i];
+  });
+  if (tid == 0) score[u] = s;
+}
+
+// The fitness of the OPT-PCIRM search on this measure: one workgroup per (particle, utterance).  The enhanced signal of the candidate x
+// is ya + x yb (pso.hip), every step before the band energies is linear in it, so band j of spectral frame m has the energy
+// P + 2 x Q + x^2 R of stoi_bands_pair_kernel's planes: the row of the other signal is sqrt(max(., 0)) in fp64, formed while the ring is
+// filled and never stored; the clean rows are sfm_stoi_bands' (fp32).  x is rounded to fp32 first: the mask array holds it so.
+template <bool EXT>
+__global__ __launch_bounds__(256) void pso_fitness_taal_kernel(const float* __restrict__ xb, const double* __restrict__ planes,
+                                                               const int* __restrict__ frame_off, const int* __restrict__ kept,
+                                                               const double* __restrict__ pos, const int* __restrict__ stopped,
+                                                               double* __restrict__ fitness, int N) {
+  const int p = blockIdx.x, u = blockIdx.y, tid = threadIdx.x;
+  if (stopped[u]) return;
+  const int M = kept[u] - 1;
+  const long long q = (long long)u * N + p;
+  if (M < SFM_STOI_SEG) {
+    if (tid == 0) fitness[q] = 1e-5;
+    return;
+  }
+  const double x = (double)(float)pos[q], x2 = 2.0 * x, xx = x * x;
+  const float* xr = xb + (long long)frame_off[u] * SFM_STOI_BANDS;
+  const double* pr = planes + (long long)frame_off[u] * (SFM_STOI_PLANES * SFM_STOI_BANDS);
+  const double s = sk_score<EXT, double>(M, [&](int i, float& cx, double& y) {
+    const int r = i / SFM_STOI_BANDS, b = i - r * SFM_STOI_BANDS;
+    const double* e = pr + r * (SFM_STOI_PLANES * SFM_STOI_BANDS) + b;
+    cx = xr[i];
+    y = sqrt(fmax(e[0] + x2 * e[SFM_STOI_BANDS] + xx * e[2 * SFM_STOI_BANDS], 0.0));
+  });
+  if (tid == 0) fitness[q] = s;
 }
 
 extern "C" int sfm_stoi_keep(const float* sig, const float* win, const int* sig_off, const int* sig_len, const int* frame_off,
@@ -313,6 +471,32 @@ extern "C" int sfm_stoi_bands(const float* sig0, const float* sig1, const float*
   if (!tiles) return SFM_ERR_ARG;
   SFM_LAUNCH(stoi_bands_kernel, dim3(n_tiles, nsig), dim3(256), 0, (hipStream_t)stream, sig0, sig1, win, dft, sig_off, frame_off, src,
              kept, tiles, bands0, bands1);
+  return SFM_OK;
+}
+
+extern "C" int sfm_stoi_bands_pair(const float* siga, const float* sigb, const float* win, const float* dft, const int* sig_off,
+                                   const int* frame_off, const int* src, const int* kept, const int* tiles, double* planes,
+                                   int n_tiles, void* stream) {
+  if (!siga || !sigb || !win || !dft || !sig_off || !frame_off || !src || !kept || !planes) return SFM_ERR_ARG;
+  if (n_tiles < 0 || n_tiles > 65535 * 1024) return SFM_ERR_SHAPE;
+  if (n_tiles == 0) return SFM_OK;                          // no utterance has a spectral frame: an empty table has no address
+  if (!tiles) return SFM_ERR_ARG;
+  SFM_LAUNCH_LDS(stoi_bands_pair_kernel, dim3(n_tiles), dim3(256), SK_PAIR_LDS, (hipStream_t)stream, siga, sigb, win, dft, sig_off,
+                 frame_off, src, kept, tiles, planes);
+  return SFM_OK;
+}
+
+extern "C" int sfm_pso_fitness_taal(const float* xb, const double* planes, const int* frame_off, const int* kept, const double* pos,
+                                    const int* stopped, double* fitness, int B, int N, int extended, void* stream) {
+  if (!xb || !planes || !frame_off || !kept || !pos || !stopped || !fitness) return SFM_ERR_ARG;
+  if (B <= 0 || B > 65535 || N < 1 || N > SFM_PSO_MAX_PARTICLES || (extended != 0 && extended != 1)) return SFM_ERR_SHAPE;
+  const dim3 grid((unsigned)N, (unsigned)B);
+  if (extended)
+    SFM_LAUNCH(pso_fitness_taal_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, xb, planes, frame_off, kept, pos, stopped, fitness,
+               N);
+  else
+    SFM_LAUNCH(pso_fitness_taal_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, xb, planes, frame_off, kept, pos, stopped,
+               fitness, N);
   return SFM_OK;
 }
 

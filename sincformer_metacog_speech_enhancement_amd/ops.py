@@ -3159,6 +3159,56 @@ def stoi_segments(xb, yb, frame_off, kept, B, extended, spec_rows, segments):
     return score
 
 
+STOI_PLANES = _K["STOI_PLANES"]                # P | Q | R of sfm_stoi_bands_pair
+
+
+def stoi_bands_pair(ya, yb, win, dft, sig_off, frame_off, src, kept, tiles, sum_frames, spec_rows, n_samples):
+    """the band energies of ya + x yb as a quadratic in x: ya, yb fp32 (flat, at 10 kHz, laid out as stoi_bands' signals) that share
+    the clean signal's kept list -> planes fp64 [sum_frames, 3, 15], row m = P | Q | R with E(x) = P + 2 x Q + x^2 R (rows beyond an
+    utterance's K - 1 are not written).  One DFT operand read serves both signals; spec_rows, n_samples as stoi_bands (the cost)."""
+    _need_dev(ya, yb, win, dft, sig_off, frame_off, src, kept, tiles)
+    L = _lib.load()
+    if any(s.dtype != torch.float32 or not s.is_contiguous() or s.dim() != 1 for s in (ya, yb)) or ya.numel() != yb.numel() or \
+            dft.dtype != torch.float32 or tuple(dft.shape) != (STOI_FRAME, STOI_DFT_COLS) or not dft.is_contiguous() or \
+            win.dtype != torch.float32 or win.numel() != STOI_FRAME or not _i32(sig_off, frame_off, src, kept, tiles) or \
+            tiles.dim() != 2 or tiles.shape[1] != 2 or src.numel() < sum_frames:
+        _lib.check(_K["ERR_SHAPE"], "stoi_bands_pair")
+    planes = torch.empty(max(sum_frames, 1), STOI_PLANES, STOI_BANDS, device=ya.device, dtype=torch.float64)
+    n_tiles = tiles.shape[0]
+    _call("stoi", L.sfm_stoi_bands_pair, (_p(ya), _p(yb), _p(win), _p(dft), _p(sig_off), _p(frame_off), _p(src), _p(kept), _p(tiles),
+                                          _p(planes), n_tiles, _stream()),
+          2 * 2.0 * spec_rows * STOI_FRAME * 2 * STOI_NBIN + 3.0 * spec_rows * 2 * STOI_NBIN,
+          2 * 4.0 * n_samples + 8.0 * STOI_PLANES * STOI_BANDS * spec_rows + 4.0 * STOI_FRAME * (2 * STOI_NBIN + 1) + 4.0 * sum_frames +
+          8.0 * n_tiles, "bands pair rows%d" % spec_rows)
+    return planes
+
+
+def pso_fitness_taal(xb, planes, frame_off, kept, pos, stopped, fitness, extended, spec_rows, segments):
+    """the Taal measure of every particle of every swarm that has not stopped: xb fp32 [sum_frames, 15] the clean band rows
+    (stoi_bands), planes fp64 [sum_frames, 3, 15] (stoi_bands_pair), pos [B, N] fp64, stopped int32 [B] -> fitness [B, N] fp64
+    (written in place, returned): STOI, or ESTOI when extended; 1e-5 below 30 spectral frames.  The cost: per particle the
+    quadratic and a square root per row element (6 flops) and stoi_segments' 12 flops per element of a 15 x 30 segment; the rows
+    are counted once (every particle of an utterance reads the same ones)."""
+    _need_dev(xb, planes, frame_off, kept, pos, stopped, fitness)
+    L = _lib.load()
+    ok = pos.dim() == 2 and fitness.shape == pos.shape
+    if ok:
+        B, N = pos.shape
+        rows = xb.shape[0] if xb.dim() == 2 else -1
+        ok = 1 <= N <= PSO_MAX_PARTICLES and B >= 1 and _pso_is(pos, torch.float64, B * N) and _pso_is(fitness, torch.float64, B * N)
+        ok = ok and _pso_is(stopped, torch.int32, B) and _pso_is(frame_off, torch.int32, B + 1) and _pso_is(kept, torch.int32, B)
+        ok = ok and rows >= 1 and _pso_is(xb, torch.float32, rows * STOI_BANDS) and xb.shape[1] == STOI_BANDS
+        ok = ok and _pso_is(planes, torch.float64, rows * STOI_PLANES * STOI_BANDS) and tuple(planes.shape[1:]) == (STOI_PLANES, STOI_BANDS)
+    if not ok:
+        _lib.check(_K["ERR_SHAPE"], "pso_fitness_taal")
+    _call("pso_fitness", L.sfm_pso_fitness_taal, (_p(xb), _p(planes), _p(frame_off), _p(kept), _p(pos), _p(stopped), _p(fitness), B, N,
+                                                  1 if extended else 0, _stream()),
+          N * (12.0 * STOI_SEG * STOI_BANDS * segments + 6.0 * STOI_BANDS * spec_rows),
+          (4.0 + 8.0 * STOI_PLANES) * STOI_BANDS * spec_rows + 16.0 * B * N + 4.0 * (3 * B + 1),
+          "%s B%d N%d rows%d" % ("estoi" if extended else "stoi", B, N, spec_rows))
+    return fitness
+
+
 def stoi_segments_bwd(xb, yb, frame_off, kept, gscore, B, max_rows, extended, spec_rows, segments):
     """the cotangent of the enhanced band rows: gscore fp64 [B] (the cotangent of stoi_segments' score) -> dyb fp32 like yb, EVERY
     row written (zeros from K - 1 on and below 30 spectral frames).  max_rows: the most frames of one utterance (the grid: one
