@@ -740,3 +740,119 @@ def test_conv_node_bounds_separate_plausible_wrong_answers():
             hp.separates("dwconv_folded input gradient %s" % (row,), m, c["bwd"](f64, m), c["bwd64"], c["bwd32"], hp.K_SUM,
                          c["bwd_bound"])
     assert seen == set(hp.BN_STATS_MUTANTS + hp.BN_FINALIZE_MUTANTS + hp.BN_BWD_MUTANTS + hp.DWGRAD_MUTANTS), seen
+
+
+# ---------------------------------------------------------------------------
+# PerceptionAgent: GroupNorm and time-pooling training nodes (tests/test_pa_nodes_gpu.py; restatements in tests/pa_nodes_cases.py)
+# ---------------------------------------------------------------------------
+def test_pa_node_restatements_are_torch_autograd():
+    """gn_fwd64 against F.group_norm + F.gelu / F.silu in float64; gn_partials64 + gn_finalize64 against the two-pass
+    statistics; gn_bwd64 (the closed form) against float64 autograd of F.group_norm + F.gelu at every backward row; pool64 and
+    pool_adjoint64 against F.adaptive_avg_pool1d and its autograd, with and without the affine"""
+    import helpers as hp
+    import pa_nodes_cases as pc
+    f64 = torch.float64
+    for row in pc.GN_BWD_ROWS:
+        B, L, C, G, act, two = row
+        c = pc.gn_bwd_case(row, None)
+        xs = [x.double().requires_grad_(True) for x in c["xs"]]
+        ga = [g.double().requires_grad_(True) for g in c["gam"]]
+        be = [b.double().requires_grad_(True) for b in c["bet"]]
+        p = sum(F.group_norm(x.transpose(1, 2), G, g, b, pc.GN_EPS).transpose(1, 2) for x, g, b in zip(xs, ga, be))
+        out = F.gelu(p) if act else p
+        out.backward(c["dout"].double())
+        fw = pc.gn_fwd64([x.detach() for x in xs], [g.detach() for g in ga], [b.detach() for b in be], G, act)
+        _pin64("gn_fwd64 out %s" % (row,), fw["out"], out.detach())
+        _pin64("gn_fwd64 out act 2 %s" % (row,), pc.act64(fw["p"], 2), F.silu(p.detach()))
+        # the closed form on the exact float64 statistics (the case's own are rounded to fp32: 6e-8 of them)
+        got = pc.gn_bwd64(c["dout"].double(), [x.detach() for x in xs], [g.detach() for g in ga], [b.detach() for b in be],
+                          fw["mean"], fw["rstd"], G, act)
+        want = (xs[0].grad, xs[1].grad if two else None, ga[0].grad, ga[1].grad if two else None, be[0].grad)
+        for name, g_, w_ in zip(pc.GN_BWD_NAMES, got, want):
+            assert (g_ is None) == (w_ is None)
+            if g_ is not None:
+                _pin64("gn_bwd64 %s %s" % (name, row), g_, w_, 1e-10)
+        if two:
+            _pin64("gn_bwd64 dbeta is that of both inputs %s" % (row,), be[1].grad, be[0].grad)
+        for name, g_, w_ in zip(pc.GN_BWD_NAMES, c["ref64"], want):
+            if g_ is not None:
+                _pin64("gn_bwd_case %s from fp32 statistics %s" % (name, row), g_, w_, 1e-5 if L > 1 else 1e-3)
+    for P, (C, G), dc in ((1, (64, 8), 0.0), (65, (64, 8), 30.0), (513, (512, 32), 30.0)):
+        c = pc.gn_finalize_case(P, C, G, dc)
+        x = arr("gf_x", (c["B"], c["L"], C), P + C + 2)
+        assert pc.gn_partials64(x.double(), G, 64).shape[1] == -(-c["L"] // 64)
+        for name, g_, w_ in zip(pc.GN_FIN_NAMES, c["ref64"], c["exact"]):
+            e = hp.figs(g_, w_)
+            print("gn_finalize64 on fp32 partials vs the statistics of x: %s P %d dc %g: %.2e %.2e" % (name, P, dc, e[0], e[1]))
+            assert max(e) < (1e-6 if dc == 0 else 2e-3)
+    for C, (Tin, Tout) in ((64, (7, 7)), (24, (12, 2)), (64, (13, 2)), (24, (200, 21)), (64, (21, 200)), (24, (150, 1))):
+        c = pc.pool_case(2, Tin, Tout, C)
+        x = c["srcs"][torch.float32].double().requires_grad_(True)
+        ref = F.adaptive_avg_pool1d(x.transpose(1, 2), Tout).transpose(1, 2)
+        (ref * c["y"].double()).sum().backward()
+        _pin64("pool64 %s" % ((C, Tin, Tout),), c["plain64"], ref.detach())
+        _pin64("pool64 affine %s" % ((C, Tin, Tout),), c[("aff64", torch.float32)],
+               ref.detach() * c["scale"].double().unsqueeze(1) + c["shift"].double().unsqueeze(1))
+        _pin64("pool_adjoint64 %s" % ((C, Tin, Tout),), c["adj64"], x.grad)
+    s, e = pc.pool_windows(*pc.POOL_BIG)
+    assert int(s[0]) == 0 and int(e[-1]) == pc.POOL_BIG[0] and int((e - s).min()) == 2 and int((e - s).max()) == 3
+    assert pc.POOL_BIG[0] * (pc.POOL_BIG[1] + 1) >= 2 ** 31 - 1 > pc.POOL_BIG[0] * pc.POOL_BIG[1] // 2     # pool_time_vec_kernel's test
+
+
+def test_pa_node_bounds_separate_plausible_wrong_answers():
+    """every wrong form of pa_nodes_cases' *_MUTANTS tuples moves the float64 reference by >= 5 x the bound of a row that
+    tests/test_pa_nodes_gpu.py checks, on that row's own inputs and with that row's own bound (one MUTANT line each)"""
+    import helpers as hp
+    import pa_nodes_cases as pc
+    f64, f32 = torch.float64, torch.float32
+    seen = set()
+    M = pc.GN_BWD_MUTANTS
+    for row in pc.GN_BWD_ROWS:
+        B, L, C, G, act, two = row
+        c = pc.gn_bwd_case(row, None)                            # the fp32-storage rows (the latent heads)
+        r64, r32 = c["ref64"], c["ref32"]
+        for m in M:
+            if (m == M[3] and not two) or (m == M[5] and act == 0) or (m == M[6] and L <= pc.ROW_TILE) or \
+                    (m in (M[0], M[1], M[2]) and L == 1) or (m == M[7] and B == 1):
+                continue            # one input / no GELU / a single row tile / one row: N = C / G and the two group terms cancel dx /
+                                    # one utterance
+            w = c["ev"](f64, m)
+            # dx where the wrong form shows in dx (dx2 for the second input's statistics), else the parameter gradients
+            i = {M[3]: 1, M[4]: 2, M[6]: 4, M[7]: 2}.get(m, 0)
+            name = "gn_act_backward %s %s" % (pc.GN_BWD_NAMES[i], row)
+            if i < 2 and act == 0:
+                hp.separates(name, m, w[i], r64[i], r32[i], hp.K_TRANS)
+            elif i < 2:
+                pc.separates_elem(name, m, w[i], r64[i], r32[i], hp.K_TRANS, c["extra"][i])
+            else:
+                pc.separates_elem(name, m, w[i], r64[i], r32[i], hp.K_SUM, c["extra"][i], None, c["sums"][i])
+            seen.add(m)
+    for row in pc.GN_APPLY_ROWS:
+        if row[0] == 1:
+            continue                                             # one utterance: no other row to read
+        for two in (False, True):
+            c = pc.gn_apply_case(row, two, None)
+            for act in (0, 1, 2):
+                m = pc.GN_APPLY_MUTANTS[0]
+                hp.separates("gn_apply act %d two %s %s" % (act, two, row), m, c["ev"](f64, act, m)[1], c["ev"](f64, act)[1],
+                             c["ev"](f32, act)[1], hp.K_TRANS)
+                if act == 1:                                     # and under the widest bound a GELU row has: bf16 + the eps_poly term
+                    pc.separates_elem("gn_apply act 1 bf16 result two %s %s" % (two, row), m, c["ev"](f64, 1, m)[1], c["ev"](f64, 1)[1],
+                                      c["ev"](f32, 1)[1], hp.K_TRANS, pc.gn_apply_extra(c["p64"], c["p32"]), torch.bfloat16)
+                seen.add(m)
+    for C in pc.POOL_C:
+        for Tin, Tout in pc.POOL_T:
+            c = pc.pool_case(2, Tin, Tout, C)
+            for m in pc.POOL_MUTANTS:
+                if m == pc.POOL_MUTANTS[0] and Tin % Tout == 0:
+                    continue                                     # floor = ceil where Tout divides Tin
+                if m == pc.POOL_MUTANTS[0] and Tin < Tout:
+                    continue                                     # floored, an upsampling window can be empty: no value to compare
+                hp.separates("pool_time affine %s" % ((C, Tin, Tout),), m, c["ev"](f64, f32, True, m), c[("aff64", f32)],
+                             c[("aff32", f32)], hp.K_SUM)
+                seen.add(m)
+            m = pc.POOL_BWD_MUTANTS[0]
+            if Tin < Tout:                                       # (each source row in one window, or all windows of one length: the same)
+                hp.separates("pool_time_bwd %s" % ((C, Tin, Tout),), m, c["adj"](f64, m), c["adj64"], c["adj32"], hp.K_SUM)
+                seen.add(m)
+    assert seen == set(pc.GN_BWD_MUTANTS + pc.GN_APPLY_MUTANTS + pc.POOL_MUTANTS + pc.POOL_BWD_MUTANTS), seen
