@@ -1,6 +1,12 @@
 """Thin Python wrappers over the C ABI (one function per entry point) plus the
 host-side weight packing the kernels expect.  Tensors must live on the HIP
-device; there is no CPU fallback (lib.load() raises if the .so is missing)."""
+device; there is no CPU fallback (lib.load() raises if the .so is missing).
+
+A wrapper checks what its launcher cannot see behind a pointer - each tensor operand's dtype, contiguity and shape or element
+count, all with the one predicate _is - and refuses through _refuse with the header's SFM_ERR_SHAPE, the launcher's own answer,
+before any shape is unpacked or anything is enqueued.  The scalar ranges of a contract (2 <= M <= QUANT_MAX_STEPS, 0 < hop <=
+frame, ...) are tested inline beside the operands they size; only sfm_gammatone_tf's own fit of K and hop is left to its launcher.
+The Conformer hot path (gemm16 ... istft_ola, the training GEMMs, the LSTM) checks nothing."""
 import ctypes
 import math
 import re as _re
@@ -184,6 +190,61 @@ def _need_dev(*ts):
     for t in ts:
         if t is not None and not t.is_cuda:
             raise RuntimeError("sincformer HIP ops need device tensors (no CPU fallback); got a CPU tensor")
+
+
+_F32, _F64, _I32 = torch.float32, torch.float64, torch.int32
+
+
+def _is(t, dtype, size=None, least=None, rows=None, opt=False, contig=True, ndim=None):
+    """the one operand predicate: t is a tensor of `dtype` (None: any), contiguous (contig="last": only its last stride must be 1,
+    a row matrix; contig=False: not asked), of `size`: an int = that many elements in any shape, a tuple = that shape, where a
+    None entry is a dimension of any size that the caller binds afterwards (ndim=k: k such dimensions).  least: at least that
+    many elements; rows: at least that many in the first dimension; opt=True: None passes (an optional operand).  A bool; never
+    raises on a tensor or None.  It runs before every launch of a checking wrapper: the plain cases come first and cost a call."""
+    if t is None:
+        return opt
+    if t.dtype is not dtype and dtype is not None:          # (torch's dtypes are singletons)
+        return False
+    if contig is True:
+        if not t.is_contiguous():
+            return False
+    elif contig and (t.dim() == 0 or t.stride(-1) != 1):
+        return False
+    if size is not None:
+        if size.__class__ is not tuple:
+            if t.numel() != size:
+                return False
+        else:
+            shape = t.shape
+            if shape != size:                               # (an exact shape passes here; the loop is for the None entries)
+                if len(shape) != len(size):
+                    return False
+                for want, have in zip(size, shape):
+                    if want is not None and want != have:
+                        return False
+    if ndim is not None and t.dim() != ndim:
+        return False
+    if least is not None and t.numel() < least:
+        return False
+    return rows is None or (t.dim() > 0 and t.shape[0] >= rows)
+
+
+def _each(dtype, n, *ts):
+    """_is(t, dtype, n) of every t in one call: contiguous tensors of `dtype` with n elements each (n None: of any size)"""
+    for t in ts:
+        if t is None or t.dtype is not dtype or not t.is_contiguous() or (n is not None and t.numel() != n):
+            return False
+    return True
+
+
+def _lengths_ok(lengths, B):
+    """the per-utterance `lengths` operand (and `frames` of dnn_layer): None, or int32 [B] contiguous"""
+    return lengths is None or _is(lengths, _I32, B)
+
+
+def _refuse(name):
+    """the one refusal of a wrapper's contract: RuntimeError("<name> failed: unsupported shape (-2)"), the launcher's own answer"""
+    _lib.check(_K["ERR_SHAPE"], name)
 
 
 def round_up(x, m):
@@ -1056,15 +1117,15 @@ def pstoi_loss(enh, clean, band_w, need_grad=False, frame_len=30, beta=15.0):
     c0, c1 = clean if pair else (clean, None)
     _need_dev(e0, e1, c0, c1, band_w)
     L = _lib.load()
-    if pair:
-        B, T, F = e0.shape
-    else:
-        B, F, T = e0.shape
-    NB = band_w.shape[0]
     FL = int(frame_len)
-    if band_w.shape[1] != F or c0.shape != e0.shape or NB > PSTOI_MAX_BANDS or F > PSTOI_MAX_BINS or \
-            not PSTOI_MIN_FRAME_LEN <= FL <= PSTOI_MAX_FRAME_LEN or T < FL:
-        _lib.check(-2, "pstoi_loss")
+    if not (_is(e0, None, ndim=3, contig=False) and
+            _is(c0, None, tuple(e0.shape), contig=False) and
+            _is(band_w, None, (None, e0.shape[2 if pair else 1]), contig=False) and
+            band_w.shape[0] <= PSTOI_MAX_BANDS and band_w.shape[1] <= PSTOI_MAX_BINS and
+            PSTOI_MIN_FRAME_LEN <= FL <= PSTOI_MAX_FRAME_LEN and e0.shape[1 if pair else 2] >= FL):
+        _refuse("pstoi_loss")
+    B, T, F = e0.shape if pair else (e0.shape[0], e0.shape[2], e0.shape[1])
+    NB = band_w.shape[0]
     loss = torch.empty(1, device=e0.device, dtype=torch.float32)
     g0 = torch.empty_like(e0) if need_grad else None
     g1 = torch.empty_like(e0) if need_grad and pair else None
@@ -1091,8 +1152,8 @@ def mse_loss(pred, target, need_grad=False):
     """nn.MSELoss() of two fp32 contiguous tensors of one shape -> (loss [1] fp32, 2 (pred - target) / n or None)"""
     _need_dev(pred, target)
     L = _lib.load()
-    if pred.shape != target.shape or pred.numel() == 0:
-        _lib.check(-2, "mse_loss")
+    if not (_is(pred, None, least=1, contig=False) and _is(target, None, tuple(pred.shape), contig=False)):
+        _refuse("mse_loss")
     loss = torch.empty(1, device=pred.device, dtype=torch.float32)
     grad = torch.empty_like(pred) if need_grad else None
     n = pred.numel()
@@ -1110,18 +1171,18 @@ QUANT_MAX_STEPS = _K["QUANT_MAX_STEPS"]        # sfm_mask_quantize
 MASK_KINDS = {None: _K["MASK_NONE"], "irm": _K["MASK_IRM"], "pcirm": _K["MASK_PCIRM"], "opt_pcirm": _K["MASK_OPT_PCIRM"]}
 
 
-def _same_planes(name, *ts):
-    """the element count of fp32 contiguous tensors of one shape: anything else is refused (-2) before the call"""
-    if any(t.shape != ts[0].shape or t.dtype != torch.float32 or not t.is_contiguous() for t in ts) or ts[0].numel() == 0:
-        _lib.check(-2, name)
-    return ts[0].numel()
+def _planes_ok(first, *others):
+    """non-empty fp32 contiguous tensors of one shape"""
+    return _is(first, _F32, least=1) and all(_is(t, _F32, tuple(first.shape)) for t in others)
 
 
 def mask_irm(clean_mag, noise_mag, p=0.5, eps=1e-10):
     """masks/irm.py:17-39 on two fp32 contiguous tensors of one shape -> fp32 tensor of that shape"""
     _need_dev(clean_mag, noise_mag)
     L = _lib.load()
-    n = _same_planes("mask_irm", clean_mag, noise_mag)
+    if not _planes_ok(clean_mag, noise_mag):
+        _refuse("mask_irm")
+    n = clean_mag.numel()
     out = torch.empty_like(clean_mag)
     _call("mask_irm", L.sfm_mask_irm, (_p(clean_mag), _p(noise_mag), _p(out), n, float(p), float(eps), _stream()),
           6.0 * n, 12.0 * n)
@@ -1132,7 +1193,9 @@ def mask_corr(noisy, clean, noise, eps=1e-10):
     """masks/pcirm.py:49-57, 70-72 per element -> (rho_s, rho_n)"""
     _need_dev(noisy, clean, noise)
     L = _lib.load()
-    n = _same_planes("mask_corr", noisy, clean, noise)
+    if not _planes_ok(noisy, clean, noise):
+        _refuse("mask_corr")
+    n = noisy.numel()
     rho_s, rho_n = torch.empty_like(noisy), torch.empty_like(noisy)
     _call("mask_corr", L.sfm_mask_corr, (_p(noisy), _p(clean), _p(noise), _p(rho_s), _p(rho_n), n, float(eps), _stream()),
           14.0 * n, 20.0 * n)
@@ -1143,7 +1206,9 @@ def mask_pcirm(clean_mag, noise_mag, rho_s, rho_n, phi1, phi2, eps=1e-10):
     """masks/pcirm.py:122-131 per element"""
     _need_dev(clean_mag, noise_mag, rho_s, rho_n, phi1, phi2)
     L = _lib.load()
-    n = _same_planes("mask_pcirm", clean_mag, noise_mag, rho_s, rho_n, phi1, phi2)
+    if not _planes_ok(clean_mag, noise_mag, rho_s, rho_n, phi1, phi2):
+        _refuse("mask_pcirm")
+    n = clean_mag.numel()
     out = torch.empty_like(clean_mag)
     _call("mask_pcirm", L.sfm_mask_pcirm, (_p(clean_mag), _p(noise_mag), _p(rho_s), _p(rho_n), _p(phi1), _p(phi2), _p(out), n,
                                            float(eps), _stream()), 12.0 * n, 28.0 * n)
@@ -1154,23 +1219,13 @@ def mask_quantize(pcirm, table, M):
     """masks/opt_pcirm.py:79-101; table: float64 device tensor, M + 1 boundaries then M values (masks.opt_pcirm.quantizer_table)"""
     _need_dev(pcirm, table)
     L = _lib.load()
-    n = _same_planes("mask_quantize", pcirm)
-    if table.dtype != torch.float64 or table.numel() != 2 * M + 1 or not 2 <= M <= QUANT_MAX_STEPS:
-        _lib.check(-2, "mask_quantize")
+    if not (_planes_ok(pcirm) and
+            _is(table, _F64, 2 * M + 1, contig=False) and 2 <= M <= QUANT_MAX_STEPS):
+        _refuse("mask_quantize")
+    n = pcirm.numel()
     out = torch.empty_like(pcirm)
     _call("mask_quantize", L.sfm_mask_quantize, (_p(pcirm), _p(table), _p(out), n, int(M), _stream()), 0.0, 8.0 * n)
     return out
-
-
-def _mix_columns(name, clean, bank, bank_off, noise_ids, lengths, *per_utterance):
-    """what the mix kernels index with has the size and type they assume: refused (-2) before the call otherwise"""
-    B = clean.shape[0]
-    ok = clean.dim() == 2 and clean.dtype == torch.float32 and bank.dtype == torch.float32 and bank_off.dtype == torch.int32
-    ok = ok and bank_off.numel() >= 2 and noise_ids.dtype == torch.int32 and noise_ids.numel() == B
-    ok = ok and (lengths is None or (lengths.dtype == torch.int32 and lengths.numel() == B))
-    ok = ok and all(t.dtype == torch.float32 and t.numel() == B for t in per_utterance)
-    if not ok:
-        _lib.check(-2, name)
 
 
 def mix_scale(clean, bank, bank_off, noise_ids, snr_db, lengths=None):
@@ -1178,7 +1233,13 @@ def mix_scale(clean, bank, bank_off, noise_ids, snr_db, lengths=None):
     [B] or None -> scale [B] fp32 (two launches: fp64 chunk sums, then the ordered fold)"""
     _need_dev(clean, bank, bank_off, noise_ids, snr_db, lengths)
     L = _lib.load()
-    _mix_columns("mix_scale", clean, bank, bank_off, noise_ids, lengths, snr_db)
+    if not (_is(clean, _F32, ndim=2, contig=False) and
+            _is(bank, _F32, contig=False) and
+            _is(bank_off, _I32, least=2, contig=False) and
+            _is(noise_ids, _I32, clean.shape[0], contig=False) and
+            _is(snr_db, _F32, clean.shape[0], contig=False) and
+            _is(lengths, _I32, clean.shape[0], opt=True, contig=False)):
+        _refuse("mix_scale")
     B, Ln = clean.shape
     n_noise = bank_off.numel() - 1
     scale = torch.empty(B, device=clean.device, dtype=torch.float32)
@@ -1192,7 +1253,13 @@ def mix_apply(clean, bank, bank_off, noise_ids, scale, lengths=None, want_rows=F
     """-> (noisy [B, L], the unscaled noise rows [B, L] or None); every element written"""
     _need_dev(clean, bank, bank_off, noise_ids, scale, lengths)
     L = _lib.load()
-    _mix_columns("mix_apply", clean, bank, bank_off, noise_ids, lengths, scale)
+    if not (_is(clean, _F32, ndim=2, contig=False) and
+            _is(bank, _F32, contig=False) and
+            _is(bank_off, _I32, least=2, contig=False) and
+            _is(noise_ids, _I32, clean.shape[0], contig=False) and
+            _is(scale, _F32, clean.shape[0], contig=False) and
+            _is(lengths, _I32, clean.shape[0], opt=True, contig=False)):
+        _refuse("mix_apply")
     B, Ln = clean.shape
     noisy = torch.empty_like(clean)
     rows = torch.empty_like(clean) if want_rows else None
@@ -1202,26 +1269,20 @@ def mix_apply(clean, bank, bank_off, noise_ids, scale, lengths=None, want_rows=F
     return noisy, rows
 
 
-def _packed_columns(name, packed, utt_off, bank, bank_off, noise_ids, *per_utterance):
-    """the packed forms' operands have the size and type the kernels assume: refused (-2) before the call otherwise -> utterances"""
-    U = utt_off.numel() - 1
-    ok = packed.dim() == 1 and packed.dtype == torch.float32 and packed.is_contiguous() and 0 < packed.numel() < 2 ** 31
-    ok = ok and utt_off.dtype == torch.int32 and utt_off.dim() == 1 and U >= 1 and utt_off.is_contiguous()
-    ok = ok and bank.dtype == torch.float32 and bank_off.dtype == torch.int32 and bank_off.numel() >= 2
-    ok = ok and noise_ids.dtype == torch.int32 and noise_ids.numel() == U and noise_ids.is_contiguous()
-    ok = ok and all(t.dtype == torch.float32 and t.numel() == U and t.is_contiguous() for t in per_utterance)
-    if not ok:
-        _lib.check(-2, name)
-    return U
-
-
 def mix_scale_varlen(packed, utt_off, bank, bank_off, noise_ids, snr_db, max_len):
     """mix_scale on packed utterances: packed fp32 [total], utterance u = packed[utt_off[u] : utt_off[u + 1]] (int32 [U + 1]);
     noise_ids int32 [U], snr_db fp32 [U]; max_len = the longest utterance (a host int) -> scale [U] fp32.  Two launches per 65535
     utterances: fp64 chunk sums, then the ordered fold."""
     _need_dev(packed, utt_off, bank, bank_off, noise_ids, snr_db)
     L = _lib.load()
-    U = _packed_columns("mix_scale_varlen", packed, utt_off, bank, bank_off, noise_ids, snr_db)
+    if not (_is(packed, _F32, ndim=1, least=1) and packed.numel() < 2 ** 31 and
+            _is(utt_off, _I32, ndim=1, least=2) and
+            _is(bank, _F32, contig=False) and
+            _is(bank_off, _I32, least=2, contig=False) and
+            _is(noise_ids, _I32, utt_off.numel() - 1) and
+            _is(snr_db, _F32, utt_off.numel() - 1)):
+        _refuse("mix_scale_varlen")
+    U = utt_off.numel() - 1
     total, n_noise, max_len = packed.numel(), bank_off.numel() - 1, int(max_len)
     scale = torch.empty(U, device=packed.device, dtype=torch.float32)
     for a in range(0, U, 65535):                    # (the utterances are the grid's y dimension)
@@ -1241,14 +1302,19 @@ def wave_batch(packed, utt_off, bank, bank_off, noise_ids, scale, index, L_out, 
     the clean rows, both zero-padded; an index outside 0 .. U - 1 (-1) gives zero rows.  One launch, every element written."""
     _need_dev(packed, utt_off, bank, bank_off, noise_ids, scale, index, out)
     L = _lib.load()
-    U = _packed_columns("wave_batch", packed, utt_off, bank, bank_off, noise_ids, scale)
-    B, L_out = index.numel(), int(L_out)
-    if index.dtype != torch.int32 or index.dim() != 1 or not index.is_contiguous() or B == 0:
-        _lib.check(-2, "wave_batch")
+    L_out = int(L_out)
+    if not (_is(packed, _F32, ndim=1, least=1) and packed.numel() < 2 ** 31 and
+            _is(utt_off, _I32, ndim=1, least=2) and
+            _is(bank, _F32, contig=False) and
+            _is(bank_off, _I32, least=2, contig=False) and
+            _is(noise_ids, _I32, utt_off.numel() - 1) and
+            _is(scale, _F32, utt_off.numel() - 1) and
+            _is(index, _I32, ndim=1, least=1) and
+            _is(out, _F32, (2, index.numel(), L_out), opt=True)):
+        _refuse("wave_batch")
+    U, B = utt_off.numel() - 1, index.numel()
     if out is None:
         out = torch.empty(2, B, L_out, device=packed.device, dtype=torch.float32)
-    elif out.shape != (2, B, L_out) or out.dtype != torch.float32 or not out.is_contiguous():
-        _lib.check(-2, "wave_batch")
     _call("mix", L.sfm_wave_batch, (_p(packed), _p(utt_off), _p(bank), _p(bank_off), _p(noise_ids), _p(scale), _p(index), _p(out), B,
                                     L_out, U, packed.numel(), bank_off.numel() - 1, _stream()),
           2.0 * B * L_out, 16.0 * B * L_out, "wave_batch B%d L%d" % (B, L_out))
@@ -1260,12 +1326,12 @@ def curriculum_mask(cr, ci, nr, ni, scale, kind=None, p=0.5, eps=1e-10, table=No
     the mix and the mask target `kind` (MASK_KINDS), one launch"""
     _need_dev(cr, ci, nr, ni, scale, table)
     L = _lib.load()
-    B, T, F = cr.shape
-    _same_planes("curriculum_mask", cr, ci, nr, ni)
     k = MASK_KINDS[kind]
-    if scale.numel() != B or scale.dtype != torch.float32 or \
-            (k == MASK_KINDS["opt_pcirm"] and (table is None or table.numel() != 2 * M + 1)):
-        _lib.check(-2, "curriculum_mask")
+    if not (_is(cr, _F32, ndim=3) and _planes_ok(cr, ci, nr, ni) and
+            _is(scale, _F32, cr.shape[0], contig=False) and
+            (k != MASK_KINDS["opt_pcirm"] or _is(table, None, 2 * M + 1, contig=False))):
+        _refuse("curriculum_mask")
+    B, T, F = cr.shape
     yr, yi = torch.empty_like(cr), torch.empty_like(cr)
     mask = torch.empty_like(cr) if k else None
     n = B * T * F
@@ -1284,18 +1350,14 @@ PSO_MAX_PARTICLES = _K["PSO_MAX_PARTICLES"]
 PSO_MAX_BINS = _K["PSO_MAX_BINS"]
 
 
-def _pso_is(t, dtype, numel):
-    return t.dtype == dtype and t.is_contiguous() and t.numel() == numel
-
-
 def pso_frame_coef(pcirm, table, M):
     """pcirm [B, C, T] fp32 contiguous, table of masks.opt_pcirm.quantizer_table -> (a, b) [B, T] fp64: the channel mean of mask
     frame n quantised with the middle value x is a[n] + x b[n]"""
     _need_dev(pcirm, table)
     L = _lib.load()
-    if pcirm.dim() != 3 or not _pso_is(pcirm, torch.float32, pcirm.numel()) or pcirm.numel() == 0 or \
-            not 2 <= M <= QUANT_MAX_STEPS or not _pso_is(table, torch.float64, 2 * M + 1):
-        _lib.check(-2, "pso_frame_coef")
+    if not (_is(pcirm, _F32, ndim=3, least=1) and
+            2 <= M <= QUANT_MAX_STEPS and _is(table, _F64, 2 * M + 1)):
+        _refuse("pso_frame_coef")
     B, C, T = pcirm.shape
     a = torch.empty(B, T, device=pcirm.device, dtype=torch.float64)
     b = torch.empty(B, T, device=pcirm.device, dtype=torch.float64)
@@ -1309,13 +1371,14 @@ def pso_split(noisy, clean, lengths, samp_off, a, b, sum_L, frame, hop):
     and S [B, 4] fp64 = {sum ya^2, sum ya yb, sum yb^2, sum clean^2} (two launches: chunk sums, then the ordered fold)"""
     _need_dev(noisy, clean, lengths, samp_off, a, b)
     L = _lib.load()
-    B, Lmax = noisy.shape
-    T = a.shape[-1]
-    ok = _pso_is(noisy, torch.float32, B * Lmax) and _pso_is(clean, torch.float32, B * Lmax) and Lmax > 0
-    ok = ok and _pso_is(lengths, torch.int32, B) and _pso_is(samp_off, torch.int32, B + 1)
-    ok = ok and _pso_is(a, torch.float64, B * T) and _pso_is(b, torch.float64, B * T) and 0 < hop <= frame
-    if not ok:
-        _lib.check(-2, "pso_split")
+    if not (_is(noisy, _F32, ndim=2) and noisy.shape[1] > 0 and
+            _is(clean, _F32, noisy.numel()) and
+            _is(lengths, _I32, noisy.shape[0]) and
+            _is(samp_off, _I32, noisy.shape[0] + 1) and
+            _is(a, _F64) and a.dim() >= 1 and a.numel() == noisy.shape[0] * a.shape[-1] and
+            _is(b, _F64, a.numel()) and 0 < hop <= frame):
+        _refuse("pso_split")
+    (B, Lmax), T = noisy.shape, a.shape[-1]
     dev = noisy.device
     ya, yb, cp = (torch.empty(max(int(sum_L), 1), device=dev, dtype=torch.float32) for _ in range(3))
     S = torch.empty(B, 4, device=dev, dtype=torch.float64)
@@ -1331,16 +1394,18 @@ def pso_fitness(spectra, frame_off, lengths, S, pos, stopped, partial, sum_frame
     sum of clipped frame correlations per (utterance, chunk of PSO_FRAMES frames, particle).  Each spectrum is read once."""
     _need_dev(frame_off, lengths, S, pos, stopped, partial, *spectra)
     L = _lib.load()
-    B, N = pos.shape
-    F = spectra[0].shape[-1]
-    NC = partial.shape[1]
-    ok = len(spectra) == 6 and all(_pso_is(s, torch.float32, spectra[0].numel()) for s in spectra)
-    ok = ok and spectra[0].numel() >= sum_frames * F and 1 <= N <= PSO_MAX_PARTICLES and 0 < F <= PSO_MAX_BINS
-    ok = ok and _pso_is(frame_off, torch.int32, B + 1) and _pso_is(lengths, torch.int32, B) and _pso_is(S, torch.float64, 4 * B)
-    ok = ok and _pso_is(pos, torch.float64, B * N) and _pso_is(stopped, torch.int32, B)
-    ok = ok and _pso_is(partial, torch.float64, B * NC * N) and NC * PSO_FRAMES >= 1
-    if not ok:
-        _lib.check(-2, "pso_fitness")
+    if not (len(spectra) == 6 and _is(spectra[0], _F32) and spectra[0].dim() >= 1 and
+            all(_is(s, _F32, spectra[0].numel()) for s in spectra[1:]) and
+            0 < spectra[0].shape[-1] <= PSO_MAX_BINS and spectra[0].numel() >= sum_frames * spectra[0].shape[-1] and
+            _is(pos, _F64, ndim=2) and 1 <= pos.shape[1] <= PSO_MAX_PARTICLES and
+            _is(frame_off, _I32, pos.shape[0] + 1) and
+            _is(lengths, _I32, pos.shape[0]) and
+            _is(S, _F64, 4 * pos.shape[0]) and
+            _is(stopped, _I32, pos.shape[0]) and
+            _is(partial, _F64) and partial.dim() >= 2 and partial.shape[1] >= 1 and
+            partial.numel() == pos.numel() * partial.shape[1]):
+        _refuse("pso_fitness")
+    (B, N), F, NC = pos.shape, spectra[0].shape[-1], partial.shape[1]
     _call("pso_fitness", L.sfm_pso_fitness, tuple(_p(s) for s in spectra) + (_p(frame_off), _p(lengths), _p(S), _p(pos),
                                                                               _p(stopped), _p(partial), B, N, F, NC, _stream()),
           16.0 * sum_frames * F * N, 24.0 * sum_frames * F + 8.0 * B * NC * N, "B%d N%d F%d" % (B, N, F))
@@ -1355,19 +1420,18 @@ def pso_step(state, it, partial=None, fitness=None, frame_off=None):
               s.stopped)
     L = _lib.load()
     B, N, K = s.B, s.N, s.max_iter
-    ok = 1 <= N <= PSO_MAX_PARTICLES and K >= 1 and 0 <= it <= K and (partial is None) != (fitness is None)
-    ok = ok and _pso_is(s.draws, torch.float64, B * (2 * N + 2 * N * K)) and _pso_is(s.params, torch.float64, 5)
-    ok = ok and all(_pso_is(t, torch.float64, B * N) for t in (s.pos, s.vel, s.pbest_pos, s.pbest_fit))
-    ok = ok and _pso_is(s.gbest, torch.float64, 2 * B) and _pso_is(s.hist, torch.float64, B * (K + 1) * (3 + 2 * N))
-    ok = ok and _pso_is(s.iters, torch.int32, B) and _pso_is(s.stopped, torch.int32, B)
-    NC = 0
-    if ok and partial is not None:
-        NC = partial.shape[1]
-        ok = frame_off is not None and _pso_is(frame_off, torch.int32, B + 1) and _pso_is(partial, torch.float64, B * NC * N)
-    if ok and fitness is not None:
-        ok = _pso_is(fitness, torch.float64, B * N)
-    if not ok:
-        _lib.check(-2, "pso_step")
+    if not (1 <= N <= PSO_MAX_PARTICLES and K >= 1 and 0 <= it <= K and (partial is None) != (fitness is None) and
+            _is(s.draws, _F64, B * (2 * N + 2 * N * K)) and
+            _is(s.params, _F64, 5) and
+            _each(_F64, B * N, s.pos, s.vel, s.pbest_pos, s.pbest_fit) and
+            _is(s.gbest, _F64, 2 * B) and
+            _is(s.hist, _F64, B * (K + 1) * (3 + 2 * N)) and
+            _each(_I32, B, s.iters, s.stopped) and
+            (partial is None or (_is(frame_off, _I32, B + 1) and _is(partial, _F64) and partial.dim() >= 2 and
+                                 partial.numel() == B * partial.shape[1] * N)) and
+            _is(fitness, _F64, B * N, opt=True)):
+        _refuse("pso_step")
+    NC = 0 if partial is None else partial.shape[1]
     _call("pso_step", L.sfm_pso_step, (_p(partial), _p(fitness), _p(frame_off), _p(s.draws), _p(s.params), _p(s.pos), _p(s.vel),
                                        _p(s.pbest_pos), _p(s.pbest_fit), _p(s.gbest), _p(s.hist), _p(s.iters), _p(s.stopped), B, N,
                                        NC, int(it), K, 1 if s.maximize else 0, _stream()),
@@ -1378,10 +1442,11 @@ def pso_quantize(pcirm, table, middle, M):
     """quantize_pcirm over [B, ...] fp32 with middle[b] (fp64 [B]) as the value of step 2 of utterance b (M >= 3)"""
     _need_dev(pcirm, table, middle)
     L = _lib.load()
-    B = pcirm.shape[0]
-    n = _same_planes("pso_quantize", pcirm)
-    if not 2 <= M <= QUANT_MAX_STEPS or not _pso_is(table, torch.float64, 2 * M + 1) or not _pso_is(middle, torch.float64, B):
-        _lib.check(-2, "pso_quantize")
+    if not (_planes_ok(pcirm) and pcirm.dim() >= 1 and
+            2 <= M <= QUANT_MAX_STEPS and _is(table, _F64, 2 * M + 1) and
+            _is(middle, _F64, pcirm.shape[0])):
+        _refuse("pso_quantize")
+    B, n = pcirm.shape[0], pcirm.numel()
     out = torch.empty_like(pcirm)
     _call("mask_quantize", L.sfm_pso_quantize, (_p(pcirm), _p(table), _p(middle), _p(out), B, n // B, int(M), _stream()), 0.0,
           8.0 * n)
@@ -1409,22 +1474,15 @@ def gammatone_tf_fits(K, hop):
     return bool(_lib.load().sfm_gammatone_tf_fits(int(K), int(hop)))
 
 
-def _gt_bank(name, sig, taps, C, lengths):
-    """(B, L, K) of sig [B, L] fp32 and taps [K, 64] fp32: anything else is refused (-2) before the call"""
-    ok = sig.dim() == 2 and sig.dtype == torch.float32 and sig.is_contiguous() and sig.numel() > 0
-    ok = ok and taps.dim() == 2 and taps.shape[1] == GT_COLS and taps.dtype == torch.float32 and taps.is_contiguous()
-    ok = ok and 8 <= taps.shape[0] <= GT_MAX_TAPS and taps.shape[0] % 8 == 0 and 1 <= C <= GT_COLS and sig.shape[0] <= 65535
-    ok = ok and (lengths is None or (lengths.dtype == torch.int32 and lengths.numel() == sig.shape[0] and lengths.is_contiguous()))
-    if not ok:
-        _lib.check(-2, name)
-    return sig.shape[0], sig.shape[1], taps.shape[0]
-
-
 def gammatone_fir(sig, taps, C, lengths=None):
     """sig [B, L], taps [K, 64] -> [B, C, L] = the causal FIR bank (0 from lengths[b] on)"""
     _need_dev(sig, taps, lengths)
     L_ = _lib.load()
-    B, L, K = _gt_bank("gammatone_fir", sig, taps, C, lengths)
+    if not (_is(sig, _F32, ndim=2, least=1) and sig.shape[0] <= 65535 and
+            _is(taps, _F32, (None, GT_COLS)) and 8 <= taps.shape[0] <= GT_MAX_TAPS and taps.shape[0] % 8 == 0 and
+            1 <= C <= GT_COLS and _lengths_ok(lengths, sig.shape[0])):
+        _refuse("gammatone_fir")
+    (B, L), K = sig.shape, taps.shape[0]
     out = torch.empty(B, C, L, device=sig.device, dtype=torch.float32)
     _call("gammatone_fir", L_.sfm_gammatone_fir, (_p(sig), _p(taps), _p(lengths), _p(out), B, L, C, K, _stream()),
           2.0 * B * L * C * K, 4.0 * B * L + 4.0 * K * GT_COLS + 4.0 * B * C * L, "B%d L%d C%d K%d" % (B, L, C, K))
@@ -1436,11 +1494,14 @@ def gammatone_tf(sig, taps, tw, C, hop, lengths=None):
     filtered signal, which is never stored"""
     _need_dev(sig, taps, tw, lengths)
     L_ = _lib.load()
-    B, L, K = _gt_bank("gammatone_tf", sig, taps, C, lengths)
-    nblocks = L // hop if hop > 0 else 0
     # (K and hop themselves - sfm_gammatone_tf_fits - are the launcher's to refuse: it sees them)
-    if nblocks < 1 or tw.dtype != torch.float32 or tuple(tw.shape) != (2, hop, GT_COLS) or not tw.is_contiguous():
-        _lib.check(-2, "gammatone_tf")
+    if not (_is(sig, _F32, ndim=2, least=1) and sig.shape[0] <= 65535 and
+            _is(taps, _F32, (None, GT_COLS)) and 8 <= taps.shape[0] <= GT_MAX_TAPS and taps.shape[0] % 8 == 0 and
+            _is(tw, _F32, (2, hop, GT_COLS)) and
+            1 <= C <= GT_COLS and 0 < hop <= sig.shape[1] and _lengths_ok(lengths, sig.shape[0])):
+        _refuse("gammatone_tf")
+    (B, L), K = sig.shape, taps.shape[0]
+    nblocks = L // hop
     partial = torch.empty(B, nblocks, C, 5, device=sig.device, dtype=torch.float32)
     n = float(B) * nblocks * hop
     _call("gammatone_tf", L_.sfm_gammatone_tf, (_p(sig), _p(taps), _p(tw), _p(lengths), _p(partial), B, L, C, K, hop, nblocks,
@@ -1454,12 +1515,11 @@ def gammatone_moments(y, tw, T, w, frame, hop, lengths=None):
     """y [B, C, L] (gammatone_fir's), tw [2, w, 64] -> partial [B, T, C, 5]: the five sums of the first w samples of each frame"""
     _need_dev(y, tw, lengths)
     L_ = _lib.load()
-    ok = y.dim() == 3 and y.dtype == torch.float32 and y.is_contiguous() and y.numel() > 0 and y.shape[1] <= GT_COLS
-    ok = ok and tw.dtype == torch.float32 and tuple(tw.shape) == (2, w, GT_COLS) and tw.is_contiguous()
-    ok = ok and T >= 1 and 1 <= w <= frame and hop >= 1 and (T - 1) * hop + frame <= y.shape[2] and y.shape[0] <= 65535
-    ok = ok and (lengths is None or (lengths.dtype == torch.int32 and lengths.numel() == y.shape[0] and lengths.is_contiguous()))
-    if not ok:
-        _lib.check(-2, "gammatone_moments")
+    if not (_is(y, _F32, ndim=3, least=1) and y.shape[0] <= 65535 and y.shape[1] <= GT_COLS and
+            _is(tw, _F32, (2, w, GT_COLS)) and
+            T >= 1 and 1 <= w <= frame and hop >= 1 and (T - 1) * hop + frame <= y.shape[2] and
+            _lengths_ok(lengths, y.shape[0])):
+        _refuse("gammatone_moments")
     B, C, L = y.shape
     partial = torch.empty(B, T, C, 5, device=y.device, dtype=torch.float32)
     _call("gammatone_moments", L_.sfm_gammatone_moments, (_p(y), _p(tw), _p(lengths), _p(partial), B, L, C, T, w, frame, hop,
@@ -1473,13 +1533,12 @@ def gammatone_tf_finish(partial, rot, T, L, frame, hop, N, two, lengths=None, wa
     """partial [B, P, C, 5] -> (mag, phase[, re, im]) [B, C, T]; two: frame n = rows n, n + 1 (rot [2, 64] turns the second)"""
     _need_dev(partial, rot, lengths)
     L_ = _lib.load()
-    ok = partial.dim() == 4 and partial.shape[3] == 5 and partial.dtype == torch.float32 and partial.is_contiguous()
-    ok = ok and partial.shape[0] <= 65535 and partial.shape[2] <= GT_COLS and T >= 1 and partial.shape[1] >= T + (1 if two else 0)
-    ok = ok and N >= 2 and N % 2 == 0 and frame >= 1 and hop >= 1 and L >= frame and T <= (L - frame) // hop + 1
-    ok = ok and (not two or (rot is not None and rot.dtype == torch.float32 and tuple(rot.shape) == (2, GT_COLS) and rot.is_contiguous()))
-    ok = ok and (lengths is None or (lengths.dtype == torch.int32 and lengths.numel() == partial.shape[0] and lengths.is_contiguous()))
-    if not ok:
-        _lib.check(-2, "gammatone_tf_finish")
+    if not (_is(partial, _F32, (None, None, None, 5)) and partial.shape[0] <= 65535 and partial.shape[2] <= GT_COLS and
+            T >= 1 and partial.shape[1] >= T + (1 if two else 0) and
+            (not two or _is(rot, _F32, (2, GT_COLS))) and
+            N >= 2 and N % 2 == 0 and frame >= 1 and hop >= 1 and L >= frame and T <= (L - frame) // hop + 1 and
+            _lengths_ok(lengths, partial.shape[0])):
+        _refuse("gammatone_tf_finish")
     B, P, C, _ = partial.shape
     outs = [torch.empty(B, C, T, device=partial.device, dtype=torch.float32) for _ in range(4 if want_bins else 2)]
     re, im = (outs[2], outs[3]) if want_bins else (None, None)
@@ -1498,15 +1557,6 @@ CEP_POWER, CEP_MAGNITUDE, CEP_BLOCKS = _K["CEP_POWER"], _K["CEP_MAGNITUDE"], _K[
 CEP_NONE, CEP_LOG, CEP_CBRT = _K["CEP_NONE"], _K["CEP_LOG"], _K["CEP_CBRT"]                        # its compress
 
 
-def _fe_lengths(name, lengths, B):
-    if lengths is not None and not (lengths.dtype == torch.int32 and lengths.numel() == B and lengths.is_contiguous()):
-        _lib.check(-2, name)
-
-
-def _fe_f32(*ts):
-    return all(t is None or (t.dtype == torch.float32 and t.is_contiguous()) for t in ts)
-
-
 def cepstral(src, fb, dct, out, col_off, *, B, T, L, frame, hop, in_mode, F, compress, im_off=0, bmul=1, badd=0, window=1.0,
              lengths=None):
     """rows of src -> out[.., col_off : col_off + (NC or M)]: [power / magnitude / block energy -> fb [M, F] (None: M = F) -> compress
@@ -1515,24 +1565,27 @@ def cepstral(src, fb, dct, out, col_off, *, B, T, L, frame, hop, in_mode, F, com
     samples).  out [B, T, ld_out] fp32; rows from T_b on are not written."""
     _need_dev(src, fb, dct, out, lengths)
     L_ = _lib.load()
+    blocks = in_mode == CEP_BLOCKS                          # otherwise the rows may be a column slice of a wider row matrix
+    if not (_is(src, _F32, (B, None, F, 5) if blocks else (B, T, None), contig=True if blocks else "last") and
+            _is(fb, _F32, (None, F), opt=True) and
+            _is(dct, _F32, (None, F if fb is None else fb.shape[0]), opt=True) and
+            _is(out, _F32, (B, T, None)) and
+            B >= 1 and T >= 1 and B * T < 2 ** 31 and 1 <= F <= FE_MAX_BINS and
+            frame >= 1 and hop >= 1 and L >= frame and T <= (L - frame) // hop + 1 and
+            _lengths_ok(lengths, B)):
+        _refuse("cepstral")
     M = F if fb is None else fb.shape[0]
     NC = 0 if dct is None else dct.shape[0]
-    ok = _fe_f32(fb, dct, out) and src.dtype == torch.float32 and out.dim() == 3 and tuple(out.shape[:2]) == (B, T) and B >= 1 and T >= 1
-    ok = ok and 1 <= F <= FE_MAX_BINS and 1 <= M <= FE_MAX_FILTERS and NC <= FE_MAX_COEFFS and 0 <= col_off
-    ok = ok and col_off + (NC or M) <= out.shape[2] and (fb is None or tuple(fb.shape) == (M, F)) and (dct is None or tuple(dct.shape) == (NC, M))
-    ok = ok and frame >= 1 and hop >= 1 and L >= frame and T <= (L - frame) // hop + 1 and B * T < 2 ** 31
-    if in_mode == CEP_BLOCKS:
-        ok = ok and src.dim() == 4 and src.is_contiguous() and src.shape[0] == B and src.shape[2] == F and src.shape[3] == 5 and F <= 64
-        ok = ok and bmul >= 1 and badd >= 0 and window > 0 and bmul * (T - 1) + badd + 1 < src.shape[1]
-        ld_in, P = 0, src.shape[1] if src.dim() == 4 else 0
-    else:                                                   # the rows may be a column slice of a wider row matrix
-        ok = ok and in_mode in (CEP_POWER, CEP_MAGNITUDE) and src.dim() == 3 and tuple(src.shape[:2]) == (B, T)
-        ok = ok and src.stride(2) == 1 and src.stride(0) == T * src.stride(1) and src.stride(1) >= src.shape[2]
+    ok = 1 <= M <= FE_MAX_FILTERS and NC <= FE_MAX_COEFFS and 0 <= col_off and col_off + (NC or M) <= out.shape[2]
+    if blocks:
+        ok = ok and F <= 64 and bmul >= 1 and badd >= 0 and window > 0 and bmul * (T - 1) + badd + 1 < src.shape[1]
+        ld_in, P = 0, src.shape[1]
+    else:
+        ok = ok and in_mode in (CEP_POWER, CEP_MAGNITUDE) and src.stride(0) == T * src.stride(1) and src.stride(1) >= src.shape[2]
         ok = ok and F <= im_off and im_off + F <= src.shape[2]
-        ld_in, P = src.stride(1) if src.dim() == 3 else 0, 0
+        ld_in, P = src.stride(1), 0
     if not ok:
-        _lib.check(-2, "cepstral")
-    _fe_lengths("cepstral", lengths, B)
+        _refuse("cepstral")
     rows = float(B) * T
     _call("cepstral", L_.sfm_cepstral, (_p(src), _p(fb), _p(dct), _p(lengths), _p(out), B, T, L, frame, hop, in_mode, ld_in, im_off, F,
                                         M, NC, compress, P, bmul, badd, float(window), out.shape[2], col_off, _stream()),
@@ -1547,17 +1600,14 @@ def rasta(logb, eql, dct, out, col_off, *, L, frame, hop, lengths=None):
     utterance's RASTA-PLP vector on every live row.  The recurrence, the mean and the DCT run in fp64 in frame order."""
     _need_dev(logb, eql, dct, out, lengths)
     L_ = _lib.load()
-    ok = _fe_f32(logb, out) and logb.dim() == 3 and out.dim() == 3 and tuple(out.shape[:2]) == tuple(logb.shape[:2])
-    ok = ok and eql.dtype == torch.float64 and dct.dtype == torch.float64 and eql.is_contiguous() and dct.is_contiguous() and dct.dim() == 2
-    if not ok:
-        _lib.check(-2, "rasta")
-    B, T, M = logb.shape
-    NC = dct.shape[0]
-    ok = 1 <= M <= FE_MAX_FILTERS and 1 <= NC <= FE_MAX_COEFFS and tuple(eql.shape) == (M,) and dct.shape[1] == M
-    ok = ok and 0 <= col_off and col_off + NC <= out.shape[2] and frame >= 1 and hop >= 1 and L >= frame and 1 <= T <= (L - frame) // hop + 1
-    if not ok:
-        _lib.check(-2, "rasta")
-    _fe_lengths("rasta", lengths, B)
+    if not (_is(logb, _F32, ndim=3) and 1 <= logb.shape[2] <= FE_MAX_FILTERS and
+            _is(eql, _F64, (logb.shape[2],)) and
+            _is(dct, _F64, (None, logb.shape[2])) and 1 <= dct.shape[0] <= FE_MAX_COEFFS and
+            _is(out, _F32, (logb.shape[0], logb.shape[1], None)) and 0 <= col_off and col_off + dct.shape[0] <= out.shape[2] and
+            frame >= 1 and hop >= 1 and L >= frame and 1 <= logb.shape[1] <= (L - frame) // hop + 1 and
+            _lengths_ok(lengths, logb.shape[0])):
+        _refuse("rasta")
+    (B, T, M), NC = logb.shape, dct.shape[0]
     _call("rasta", L_.sfm_rasta, (_p(logb), _p(eql), _p(dct), _p(lengths), _p(out), B, T, L, frame, hop, M, NC, out.shape[2], col_off,
                                   _stream()),
           12.0 * B * T * M + 2.0 * B * NC * M, 4.0 * B * T * M + 4.0 * B * T * NC + 8.0 * M + 8.0 * NC * M, "B%d T%d M%d NC%d" % (B, T, M, NC))
@@ -1569,16 +1619,15 @@ def feature_context(feat, ctx, *, L, frame, hop, mean=None, std=None, clip=10.0,
     std [(2 ctx + 1) D] the same launch applies nan / inf -> 0, (f - mean) / std and the clip to +-clip"""
     _need_dev(feat, mean, std, lengths)
     L_ = _lib.load()
-    ok = _fe_f32(feat, mean, std) and feat.dim() == 3 and feat.numel() > 0 and (mean is None) == (std is None)
-    if not ok:
-        _lib.check(-2, "feature_context")
+    if not (_is(feat, _F32, ndim=3, least=1) and feat.shape[2] % 2 == 0 and feat.shape[0] * feat.shape[1] < 2 ** 31 and
+            0 <= ctx <= 64 and clip > 0 and (mean is None) == (std is None) and
+            _is(mean, _F32, ((2 * ctx + 1) * feat.shape[2],), opt=True) and
+            _is(std, _F32, ((2 * ctx + 1) * feat.shape[2],), opt=True) and
+            frame >= 1 and hop >= 1 and L >= frame and feat.shape[1] <= (L - frame) // hop + 1 and
+            _lengths_ok(lengths, feat.shape[0])):
+        _refuse("feature_context")
     B, T, D = feat.shape
     W = (2 * ctx + 1) * D
-    ok = D % 2 == 0 and 0 <= ctx <= 64 and clip > 0 and frame >= 1 and hop >= 1 and L >= frame and T <= (L - frame) // hop + 1
-    ok = ok and B * T < 2 ** 31 and (mean is None or (tuple(mean.shape) == (W,) and tuple(std.shape) == (W,)))
-    if not ok:
-        _lib.check(-2, "feature_context")
-    _fe_lengths("feature_context", lengths, B)
     out = torch.empty(B, T, W, device=feat.device, dtype=torch.float32)
     n = float(B) * T
     _call("feature_context", L_.sfm_feature_context, (_p(feat), _p(mean), _p(std), _p(lengths), _p(out), B, T, L, frame, hop, D, ctx,
@@ -1592,12 +1641,12 @@ def rows_mean(src, col_off, N, *, L, frame, hop, den=0, lengths=None):
     """src [B, T, ld] -> [B, N]: the mean over an utterance's T_b rows of columns col_off .. col_off + N (den > 0: the sum over den)"""
     _need_dev(src, lengths)
     L_ = _lib.load()
-    ok = _fe_f32(src) and src.dim() == 3 and src.numel() > 0 and N >= 1 and 0 <= col_off and col_off + N <= src.shape[2] and den >= 0
-    ok = ok and frame >= 1 and hop >= 1 and L >= frame and src.shape[1] <= (L - frame) // hop + 1
-    if not ok:
-        _lib.check(-2, "rows_mean")
+    if not (_is(src, _F32, ndim=3, least=1) and
+            N >= 1 and 0 <= col_off and col_off + N <= src.shape[2] and den >= 0 and
+            frame >= 1 and hop >= 1 and L >= frame and src.shape[1] <= (L - frame) // hop + 1 and
+            _lengths_ok(lengths, src.shape[0])):
+        _refuse("rows_mean")
     B, T, ld = src.shape
-    _fe_lengths("rows_mean", lengths, B)
     out = torch.empty(B, N, device=src.device, dtype=torch.float32)
     _call("rows_mean", L_.sfm_rows_mean, (_p(src), _p(lengths), _p(out), B, T, L, frame, hop, ld, col_off, N, int(den), _stream()),
           1.0 * B * T * N, 4.0 * B * T * N + 4.0 * B * N, "B%d T%d N%d" % (B, T, N))
@@ -1612,18 +1661,13 @@ HC_STEP_FLOPS = 24.0                # fp64 operations of one Euler step: 3 for k
                                     # 3 for the two frame sums (counted in both forms: the algorithm, not the variant)
 
 
-def _hc_args(name, x, par, ndim):
-    ok = x.dim() == ndim and x.dtype == torch.float32 and x.is_contiguous() and x.numel() > 0 and x.numel() // x.shape[-1] < 2 ** 31
-    ok = ok and par.dtype == torch.float64 and tuple(par.shape) == (HC_PARAMS,) and par.is_contiguous()
-    if not ok:
-        _lib.check(-2, name)
-
-
 def haircell(x, par):
     """x [N, L] fp32, par [12] fp64 -> [N, L] fp64: the firing rate h c[t] of each row's chain"""
     _need_dev(x, par)
     L_ = _lib.load()
-    _hc_args("haircell", x, par, 2)
+    if not (_is(x, _F32, ndim=2, least=1) and x.shape[0] < 2 ** 31 and
+            _is(par, _F64, (HC_PARAMS,))):
+        _refuse("haircell")
     N, L = x.shape
     out = torch.empty(N, L, device=x.device, dtype=torch.float64)
     _call("haircell", L_.sfm_haircell, (_p(x), _p(par), _p(out), N, L, _stream()),
@@ -1636,12 +1680,12 @@ def haircell_frames(x, par, frame, hop, lengths=None):
     lengths (int32 [B]) a chain stops at its utterance's end and frames from T_b on are 0.  The rate signal is not stored."""
     _need_dev(x, par, lengths)
     L_ = _lib.load()
-    _hc_args("haircell_frames", x, par, 3)
+    if not (_is(x, _F32, ndim=3, least=1) and x.shape[0] * x.shape[1] < 2 ** 31 and
+            _is(par, _F64, (HC_PARAMS,)) and
+            1 <= hop and 1 <= frame <= 2 * hop and x.shape[2] >= frame and
+            _lengths_ok(lengths, x.shape[0])):
+        _refuse("haircell_frames")
     B, C, L = x.shape
-    ok = 1 <= hop and 1 <= frame <= 2 * hop and L >= frame
-    ok = ok and (lengths is None or (lengths.dtype == torch.int32 and lengths.numel() == B and lengths.is_contiguous()))
-    if not ok:
-        _lib.check(-2, "haircell_frames")
     T = (L - frame) // hop + 1
     out = torch.empty(B, C, T, device=x.device, dtype=torch.float64)
     _call("haircell_frames", L_.sfm_haircell_frames, (_p(x), _p(par), _p(lengths), _p(out), B * C, C, L, frame, hop, T, _stream()),
@@ -2561,10 +2605,11 @@ def csii_frames_varlen(cr, ci, er, ei, frame_off, weights, B, want_msc=False):
     msc plane [B, 129] fp64)"""
     _need_dev(cr, ci, er, ei, frame_off, weights)
     L = _lib.load()
+    if not (_is(cr, _F32, (None, CSII_BINS)) and all(_is(t, _F32, tuple(cr.shape)) for t in (ci, er, ei)) and
+            _is(frame_off, None, B + 1, contig=False) and
+            _is(weights, _F64, CSII_BINS, contig=False)):
+        _refuse("csii_frames_varlen")
     n, F = cr.shape
-    if F != CSII_BINS or any(t.shape != cr.shape or t.dtype != torch.float32 or not t.is_contiguous() for t in (cr, ci, er, ei)) or \
-            weights.dtype != torch.float64 or weights.numel() != CSII_BINS or frame_off.numel() != B + 1:
-        _lib.check(-2, "csii_frames_varlen")
     score = torch.empty(B, device=cr.device, dtype=torch.float64)
     msc = torch.empty(B, F, device=cr.device, dtype=torch.float64) if want_msc else None
     _call("intelligibility", L.sfm_csii_frames_varlen, (_p(cr), _p(ci), _p(er), _p(ei), _p(frame_off), _p(weights), _p(score), _p(msc),
@@ -2576,8 +2621,8 @@ def hilbert_env(x):
     """x [R, L] fp32 -> [R, L] fp32 = |scipy.signal.hilbert(x)| along the last axis"""
     _need_dev(x)
     L_ = _lib.load()
-    if x.dim() != 2 or x.dtype != torch.float32 or not x.is_contiguous() or x.numel() == 0:
-        _lib.check(-2, "hilbert_env")
+    if not _is(x, _F32, ndim=2, least=1):
+        _refuse("hilbert_env")
     R, L = x.shape
     env = torch.empty_like(x)
     _call("hilbert_env", L_.sfm_hilbert_env, (_p(x), _p(hilbert_table(L, x.device)), _p(env), R, L, _stream()),
@@ -2590,9 +2635,11 @@ def hilbert_env_moments(X, tables, tab_off, lengths, tiles, C, tile_samples=0):
     takes them -> partial [n_tiles, C, 5] fp64.  tile_samples: hilbert_tiles' third result (the launch's stated cost only)."""
     _need_dev(X, tables, tab_off, lengths, tiles)
     L_ = _lib.load()
-    if X.dim() != 4 or X.shape[0] != 2 or X.shape[2] != C or X.dtype != torch.float32 or not X.is_contiguous() or C > GT_COLS or \
-            X.numel() == 0 or tiles.dim() != 2 or tiles.shape[1] != 2 or lengths.numel() != X.shape[1] or tab_off.numel() != X.shape[1]:
-        _lib.check(-2, "hilbert_env_moments")
+    if not (_is(X, _F32, (2, None, C, None), least=1) and C <= GT_COLS and
+            _is(tab_off, None, X.shape[1], contig=False) and
+            _is(lengths, None, X.shape[1], contig=False) and
+            _is(tiles, None, (None, 2), contig=False)):
+        _refuse("hilbert_env_moments")
     _, B, _, L = X.shape
     n = tiles.shape[0]
     partial = torch.empty(max(n, 1), C, 5, device=X.device, dtype=torch.float64)
@@ -2606,8 +2653,11 @@ def ncm_finish(partial, tile_off, lengths, weights, B, C):
     """partial [n_tiles, C, 5] fp64 -> (score [B], ncc [B, C]) fp64"""
     _need_dev(partial, tile_off, lengths, weights)
     L_ = _lib.load()
-    if weights.dtype != torch.float64 or weights.numel() != C or tile_off.numel() != B + 1 or lengths.numel() != B:
-        _lib.check(-2, "ncm_finish")
+    if not (partial is not None and partial.dim() >= 1 and  # (its rows are the stated cost; nothing else is asked of it)
+            _is(tile_off, None, B + 1, contig=False) and
+            _is(lengths, None, B, contig=False) and
+            _is(weights, _F64, C, contig=False)):
+        _refuse("ncm_finish")
     ncc = torch.empty(B, C, device=partial.device, dtype=torch.float64)
     score = torch.empty(B, device=partial.device, dtype=torch.float64)
     _call("intelligibility", L_.sfm_ncm_finish, (_p(partial), _p(tile_off), _p(lengths), _p(weights), _p(ncc), _p(score), B, C,
@@ -2638,32 +2688,28 @@ def dnn_layer(a, pw, *, act=None, out=None, out_dtype=None, p_drop=0.0, seed=0, 
         raise RuntimeError("dnn_layer: a plain Linear pack in the compute format %s is needed (got %s)" % (dt, pw.w.dtype))
     T = D = ctx = 0
     if context is not None:
-        ok = a.dtype == torch.float32 and a.dim() == 3 and a.is_contiguous() and a.numel() > 0 and 0 <= context <= 64
-        ok = ok and a.shape[2] >= 8 and a.shape[2] % 2 == 0 and a.shape[2] * (2 * context + 1) == pw.K and (mean is None) == (std is None)
-        ok = ok and all(s is None or (s.dtype == torch.float32 and s.is_contiguous() and s.numel() == pw.K) for s in (mean, std))
-        ok = ok and (mean is None or pw.K <= DNN_CONTEXT_MAX_K)
-        ok = ok and (frames is None or (frames.dtype == torch.int32 and frames.is_contiguous() and frames.numel() == a.shape[0]))
-        if not ok:
-            _lib.check(-2, "dnn_layer")
+        if not (_is(a, _F32, ndim=3, least=1) and 0 <= context <= 64 and
+                a.shape[2] >= 8 and a.shape[2] % 2 == 0 and a.shape[2] * (2 * context + 1) == pw.K and
+                _lengths_ok(frames, a.shape[0]) and
+                (mean is None) == (std is None) and (mean is None or pw.K <= DNN_CONTEXT_MAX_K) and
+                _is(mean, _F32, pw.K, opt=True) and _is(std, _F32, pw.K, opt=True)):
+            _refuse("dnn_layer")
         mode, ctx, (B, T, D) = 2, int(context), a.shape
         M, lda, abytes = B * T, 0, 4.0 * a.numel() + (8.0 * pw.K if mean is not None else 0.0) + (4.0 * B if frames is not None else 0.0)
     else:
-        if frames is not None or mean is not None or std is not None or a.dim() != 2 or a.stride(1) != 1 or a.numel() == 0:
-            _lib.check(-2, "dnn_layer")
+        K8 = round_up(pw.K, 8)
+        if not (frames is None and mean is None and std is None and
+                (_is(a, _F32, (None, pw.K), least=1, contig="last") or
+                 (_is(a, dt, ndim=2, least=1, contig="last") and a.shape[1] >= K8 and a.stride(0) % 8 == 0))):
+            _refuse("dnn_layer")
         M, lda = a.shape[0], a.stride(0)
-        if a.dtype == torch.float32:
-            mode, ok, abytes = 1, a.shape[1] == pw.K, 4.0 * M * pw.K
-        else:
-            K8 = round_up(pw.K, 8)
-            mode, ok, abytes = 0, a.dtype == dt and a.shape[1] >= K8 and lda % 8 == 0, 2.0 * M * K8
-        if not ok:
-            _lib.check(-2, "dnn_layer")
+        mode, abytes = (1, 4.0 * M * pw.K) if a.dtype == torch.float32 else (0, 2.0 * M * K8)
     if out is None:
         odt = out_dtype or dt
         out = torch.empty(M, pw.N if odt == torch.float32 else round_up(pw.N, 8), device=a.device, dtype=odt)
-    if out.dim() != 2 or out.shape[0] != M or out.stride(1) != 1 or out.dtype not in (torch.float32, dt) or out.shape[1] < pw.N or \
-            (out.dtype == torch.float32 and out.shape[1] != pw.N) or act not in DNN_ACT:
-        _lib.check(-2, "dnn_layer")
+    if not ((_is(out, _F32, (M, pw.N), contig="last") or (_is(out, dt, (M, None), contig="last") and out.shape[1] >= pw.N)) and
+            act in DNN_ACT):
+        _refuse("dnn_layer")
     out_f32 = 1 if out.dtype == torch.float32 else 0
     # 16-bit rows: the columns N .. ldo are the next layer's K padding, written as zeros
     ldo = out.stride(0)
@@ -2684,16 +2730,14 @@ def dnn_act_bwd(dy, saved, act, N, p_drop=0.0, out=None):
     _need_dev(dy, saved, out)
     L = _lib.load()
     dt = _state["dtype"]
+    if not (_is(dy, None, ndim=2, rows=1, contig="last") and dy.dtype in (torch.float32, dt) and dy.shape[1] >= N and
+            act in DNN_ACT and
+            (act is None or (_is(saved, dt if act == "relu" else _F32, (dy.shape[0], None), contig="last") and saved.shape[1] >= N)) and
+            (out is None or (_is(out, dt, (dy.shape[0], None)) and out.shape[1] >= N and out.shape[1] % 8 == 0))):
+        _refuse("dnn_act_bwd")
     M = dy.shape[0]
-    ok = dy.dim() == 2 and dy.stride(1) == 1 and dy.shape[1] >= N and dy.dtype in (torch.float32, dt) and act in DNN_ACT and M > 0
-    if act is not None:
-        ok = ok and saved is not None and saved.dim() == 2 and saved.stride(1) == 1 and saved.shape[0] == M and saved.shape[1] >= N
-        ok = ok and saved.dtype == (dt if act == "relu" else torch.float32)
     if out is None:
         out = torch.empty(M, round_up(N, 64), device=dy.device, dtype=dt)
-    ok = ok and out.dtype == dt and out.dim() == 2 and out.shape[0] == M and out.is_contiguous() and out.shape[1] >= N and out.shape[1] % 8 == 0
-    if not ok:
-        _lib.check(-2, "dnn_act_bwd")
     ssz = 0 if act is None else saved.element_size()
     _call("dnn_act_bwd", L.sfm_dnn_act_bwd, (_p(dy), 1 if dy.dtype == torch.float32 else 0, dy.stride(0), _p(saved),
                                              0 if saved is None else saved.stride(0), _p(out), out.shape[1], M, N, DNN_ACT[act],
@@ -2710,19 +2754,16 @@ MOMENTS_CHUNK_ROWS = _K["MOMENTS_CHUNK_ROWS"]           # sfm_context_moments: r
 MOMENTS_MAX_CHUNKS = _K["MOMENTS_MAX_CHUNKS"]           # chunks at most: its scratch is (MOMENTS_MAX_CHUNKS + 1) K doubles
 
 
-def _frames_ok(raw, bounds):
-    return raw.dtype == torch.float32 and raw.dim() == 2 and raw.is_contiguous() and raw.numel() > 0 and bounds.dtype == torch.int32 \
-        and bounds.is_contiguous() and tuple(bounds.shape) == (raw.shape[0], 2) and raw.shape[0] < 2 ** 31
-
-
 def context_moments(raw, bounds, ctx):
     """-> (mean, std) fp32 [D (2 ctx + 1)] of the context rows of the packed frames raw [N, D] fp32 (bounds int32 [N, 2]: each
     frame's utterance as first and one-past-last packed row), nan / inf read as 0, two fp64 passes, std < 1e-6 -> 1: the
     statistics of the reference's Dataset without its [N, K] rows.  Four launches, once per frame set."""
     _need_dev(raw, bounds)
     L = _lib.load()
-    if not _frames_ok(raw, bounds) or not 0 <= int(ctx) <= 64:
-        _lib.check(-2, "context_moments")
+    if not (_is(raw, _F32, ndim=2, least=1) and raw.shape[0] < 2 ** 31 and
+            _is(bounds, _I32, (raw.shape[0], 2)) and
+            0 <= int(ctx) <= 64):
+        _refuse("context_moments")
     N, D = raw.shape
     K = D * (2 * int(ctx) + 1)
     mean = torch.empty(K, device=raw.device, dtype=torch.float32)
@@ -2744,25 +2785,28 @@ def dnn_layer_indexed(raw, bounds, index, pw, *, context, act=None, out=None, ou
     dt = _state["dtype"]
     if pw.w.dtype != dt or pw.ksize != 1 or pw.glu:
         raise RuntimeError("dnn_layer_indexed: a plain Linear pack in the compute format %s is needed (got %s)" % (dt, pw.w.dtype))
-    ok = _frames_ok(raw, bounds) and index.dtype == torch.int32 and index.dim() == 1 and index.is_contiguous() and index.numel() > 0
-    ok = ok and 0 <= int(context) <= 64 and raw.shape[1] >= 8 and raw.shape[1] % 2 == 0 and raw.shape[1] * (2 * int(context) + 1) == pw.K
-    ok = ok and (mean is None) == (std is None) and (mean is None or pw.K <= DNN_CONTEXT_MAX_K)
-    ok = ok and all(s is None or (s.dtype == torch.float32 and s.is_contiguous() and s.numel() == pw.K) for s in (mean, std))
-    if not ok:
-        _lib.check(-2, "dnn_layer_indexed")
-    (N, D), M, ctx = raw.shape, index.numel(), int(context)
+    if not _is(raw, _F32, ndim=2, least=1):
+        _refuse("dnn_layer_indexed")
+    (N, D), ctx = raw.shape, int(context)
+    if not (N < 2 ** 31 and D >= 8 and D % 2 == 0 and 0 <= ctx <= 64 and D * (2 * ctx + 1) == pw.K and
+            _is(bounds, _I32, (N, 2)) and
+            _is(index, _I32, ndim=1, least=1) and
+            (mean is None) == (std is None) and (mean is None or pw.K <= DNN_CONTEXT_MAX_K) and
+            _is(mean, _F32, pw.K, opt=True) and _is(std, _F32, pw.K, opt=True)):
+        _refuse("dnn_layer_indexed")
+    M = index.numel()
     K64 = round_up(pw.K, 64)
     want_a16 = a16_out is not None and a16_out is not False
+    odt = out_dtype or dt
+    if not ((not want_a16 or a16_out is True or _is(a16_out, dt, (M, K64))) and
+            (odt in (torch.float32, dt) if out is None else
+             _is(out, _F32, (M, pw.N), contig="last") or (_is(out, dt, (M, None), contig="last") and out.shape[1] >= pw.N)) and
+            act in DNN_ACT):
+        _refuse("dnn_layer_indexed")
     if a16_out is True:
         a16_out = torch.empty(M, K64, device=raw.device, dtype=dt)
-    if want_a16 and (a16_out.dtype != dt or tuple(a16_out.shape) != (M, K64) or not a16_out.is_contiguous()):
-        _lib.check(-2, "dnn_layer_indexed")
     if out is None:
-        odt = out_dtype or dt
         out = torch.empty(M, pw.N if odt == torch.float32 else round_up(pw.N, 8), device=raw.device, dtype=odt)
-    if out.dim() != 2 or out.shape[0] != M or out.stride(1) != 1 or out.dtype not in (torch.float32, dt) or out.shape[1] < pw.N or \
-            (out.dtype == torch.float32 and out.shape[1] != pw.N) or act not in DNN_ACT:
-        _lib.check(-2, "dnn_layer_indexed")
     out_f32 = 1 if out.dtype == torch.float32 else 0
     osz = 4 if out_f32 else 2
     # each gathered raw row read once per context column block (2 ctx + 1 times D floats per operand row), index and bounds once
@@ -2785,22 +2829,21 @@ def mse_gather_loss(y, mask, index, *, loss_scale=None, need_dz=True, rec=None, 
     _need_dev(y, mask, index, loss_scale, rec, ctl, loss, dz)
     L = _lib.load()
     dt = _state["dtype"]
-    ok = y.dtype == torch.float32 and y.dim() == 2 and y.is_contiguous() and y.numel() > 0 and mask.dtype == torch.float32 and mask.dim() == 2
-    ok = ok and mask.is_contiguous() and mask.shape[0] > 0 and mask.shape[1] == y.shape[1] and index.dtype == torch.int32
-    ok = ok and index.dim() == 1 and index.is_contiguous() and index.numel() == y.shape[0]
-    ok = ok and (loss_scale is None or (loss_scale.dtype == torch.float32 and loss_scale.numel() >= 1))
-    ok = ok and (rec is None or (rec.dtype == torch.float64 and rec.numel() == 4 and rec.is_contiguous()))
-    ok = ok and (ctl is None or (ctl.dtype == torch.float64 and ctl.numel() >= 8 and ctl.is_contiguous()))
-    if not ok:
-        _lib.check(-2, "mse_gather_loss")
-    M, C = y.shape
-    Cz = round_up(C, 64)
-    if need_dz and dz is None:
-        dz = torch.empty(M, Cz, device=y.device, dtype=dt)
     if not need_dz:
         dz = None
-    if dz is not None and (dz.dtype != dt or tuple(dz.shape) != (M, Cz) or not dz.is_contiguous()):
-        _lib.check(-2, "mse_gather_loss")
+    if not _is(y, _F32, ndim=2, least=1):
+        _refuse("mse_gather_loss")
+    M, C = y.shape
+    Cz = round_up(C, 64)
+    if not (_is(mask, _F32, ndim=2, least=1) and mask.shape[1] == C and
+            _is(index, _I32, (M,)) and
+            (loss_scale is None or _is(loss_scale, _F32, least=1, contig=False)) and
+            (rec is None or _is(rec, _F64, 4)) and
+            (ctl is None or _is(ctl, _F64, least=8)) and
+            (dz is None or _is(dz, dt, (M, Cz)))):
+        _refuse("mse_gather_loss")
+    if need_dz and dz is None:
+        dz = torch.empty(M, Cz, device=y.device, dtype=dt)
     if loss is None:
         loss = torch.empty(1, device=y.device, dtype=torch.float32)
     ws = _ws64(MSE_GATHER_MAX_BLOCKS, y.device)
@@ -2912,18 +2955,15 @@ def mask_resynth(noisy, mask, lengths=None, *, frame, hop, n_fft, fs, cf, out=No
     the launch computes, sum_b min(T_b, T_mask), for its stated cost (None: every utterance is L samples long)."""
     _need_dev(noisy, mask, lengths, out)
     L_ = _lib.load()
-    ok = noisy.dim() == 2 and mask.dim() == 3 and noisy.dtype == torch.float32 and mask.dtype == torch.float32
-    ok = ok and noisy.is_contiguous() and mask.is_contiguous() and noisy.numel() > 0 and mask.numel() > 0
-    ok = ok and mask.shape[0] == noisy.shape[0] and mask.shape[2] == len(cf) and resynth_supported(frame, hop, n_fft, mask.shape[2])
-    ok = ok and (lengths is None or (lengths.dtype == torch.int32 and lengths.is_contiguous() and lengths.numel() == noisy.shape[0]))
-    if not ok:
-        _lib.check(_K["ERR_SHAPE"], "mask_resynth")
+    if not (_is(noisy, _F32, ndim=2, least=1) and
+            _is(mask, _F32, (noisy.shape[0], None, len(cf)), least=1) and resynth_supported(frame, hop, n_fft, len(cf)) and
+            _lengths_ok(lengths, noisy.shape[0]) and
+            _is(out, _F32, tuple(noisy.shape), opt=True)):
+        _refuse("mask_resynth")
     B, L = noisy.shape
     T_mask, C = mask.shape[1], mask.shape[2]
     if out is None:
         out = torch.empty(B, L, device=noisy.device, dtype=torch.float32)
-    if out.shape != noisy.shape or out.dtype != torch.float32 or not out.is_contiguous():
-        _lib.check(_K["ERR_SHAPE"], "mask_resynth")
     Wf, Wi, tab_idx, tab_wt, inv_wsum = resynth_operands(frame, hop, n_fft, fs, cf, noisy.device)
     if frames is None:
         frames = B * min((L - frame) // hop + 1 if L >= frame else 0, T_mask)
@@ -2943,18 +2983,16 @@ def mask_resynth_bwd(noisy, dout, lengths=None, *, frame, hop, n_fft, fs, cf, T_
     _need_dev(noisy, dout, lengths, out)
     L_ = _lib.load()
     C = len(cf)
-    ok = noisy.dim() == 2 and dout.dim() == 2 and noisy.dtype == torch.float32 and dout.dtype == torch.float32
-    ok = ok and noisy.is_contiguous() and dout.is_contiguous() and noisy.numel() > 0 and dout.shape == noisy.shape
-    ok = ok and int(T_mask) > 0 and resynth_supported(frame, hop, n_fft, C)
-    ok = ok and (lengths is None or (lengths.dtype == torch.int32 and lengths.is_contiguous() and lengths.numel() == noisy.shape[0]))
-    if not ok:
-        _lib.check(_K["ERR_SHAPE"], "mask_resynth_bwd")
-    B, L = noisy.shape
     T_mask = int(T_mask)
+    if not (_is(noisy, _F32, ndim=2, least=1) and
+            _is(dout, _F32, tuple(noisy.shape)) and
+            _lengths_ok(lengths, noisy.shape[0]) and
+            T_mask > 0 and resynth_supported(frame, hop, n_fft, C) and
+            _is(out, _F32, (noisy.shape[0], T_mask, C), opt=True)):
+        _refuse("mask_resynth_bwd")
+    B, L = noisy.shape
     if out is None:
         out = torch.empty(B, T_mask, C, device=noisy.device, dtype=torch.float32)
-    if tuple(out.shape) != (B, T_mask, C) or out.dtype != torch.float32 or not out.is_contiguous():
-        _lib.check(_K["ERR_SHAPE"], "mask_resynth_bwd")
     Wf, _, _, tab_wt, inv_wsum, WiT, chan_bins = resynth_operands(frame, hop, n_fft, fs, cf, noisy.device, bwd=True)
     if frames is None:
         frames = B * min((L - frame) // hop + 1 if L >= frame else 0, T_mask)
@@ -2981,14 +3019,6 @@ def rbm_error_tiles(n_visible):
     return (int(n_visible) + RBM_TILE - 1) // RBM_TILE
 
 
-def _rbm_rows_ok(data, rows, M, K):
-    ok = data.dim() == 2 and data.dtype == torch.float32 and data.stride(1) == 1 and data.shape[1] == K and data.shape[0] >= 1 and \
-        data.stride(0) >= K
-    if rows is None:
-        return ok and M <= data.shape[0]
-    return ok and rows.dtype == torch.int32 and rows.dim() == 1 and rows.is_contiguous() and rows.numel() == M
-
-
 def rbm_prob(data, W, bias, *, down=False, rows=None, M=None, prob=None, sample=None, u=None, seed=None):
     """prob [M, N] = sigmoid(A op(W) + bias), one sfm_rbm_prob launch.  W fp32 [n_visible, n_hidden] contiguous; down=False: A rows
     of n_visible values, op(W) = W, bias = h_bias [n_hidden]; down=True: rows of n_hidden values, op(W) = W^T, bias = v_bias.
@@ -2997,28 +3027,27 @@ def rbm_prob(data, W, bias, *, down=False, rows=None, M=None, prob=None, sample=
     include/sincformer_hip.h; neither: probabilities only.  -> prob, or (prob, sample)."""
     _need_dev(data, W, bias, rows, prob, sample, u)
     L = _lib.load()
-    if W.dim() != 2 or W.dtype != torch.float32 or not W.is_contiguous() or not 1 <= W.shape[0] <= RBM_MAX_UNITS or \
-            not 1 <= W.shape[1] <= RBM_MAX_UNITS:
-        _lib.check(_K["ERR_SHAPE"], "rbm_prob")
+    if not (_is(W, _F32, ndim=2) and 1 <= W.shape[0] <= RBM_MAX_UNITS and 1 <= W.shape[1] <= RBM_MAX_UNITS):
+        _refuse("rbm_prob")
     V, H = W.shape
     K, N = (H, V) if down else (V, H)
     if M is None:
-        M = rows.numel() if rows is not None else (data.shape[0] if data.dim() == 2 else 0)
+        M = rows.numel() if rows is not None else (data.shape[0] if _is(data, None, ndim=2, contig=False) else 0)
     M = int(M)
-    ok = M >= 1 and _rbm_rows_ok(data, rows, M, K) and bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == N
-    ok = ok and not (u is not None and seed is not None)
-    ok = ok and (u is None or (u.dtype == torch.float64 and u.is_contiguous() and u.numel() == M * N))
-    if not ok:
-        _lib.check(_K["ERR_SHAPE"], "rbm_prob")
+    if not (M >= 1 and
+            _is(data, _F32, (None, K), rows=1 if rows is not None else M, contig="last") and data.stride(0) >= K and
+            _is(rows, _I32, (M,), opt=True) and
+            _is(bias, _F32, N) and
+            not (u is not None and seed is not None) and _is(u, _F64, M * N, opt=True)):
+        _refuse("rbm_prob")
     mode = "replay" if u is not None else ("counter" if seed is not None else None)
     if prob is None:
         prob = torch.empty(M, N, device=data.device, dtype=torch.float32)
     if mode is not None and sample is None:
         sample = torch.empty(M, N, device=data.device, dtype=torch.float32)
-    for t in (prob, sample) if mode is not None else (prob,):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != M * N:
-            _lib.check(_K["ERR_SHAPE"], "rbm_prob")
-    if mode is None and sample is not None:
+    if not (_is(prob, _F32, M * N) and (mode is None or _is(sample, _F32, M * N))):
+        _refuse("rbm_prob")
+    if mode is None and sample is not None:                 # a sample plane without a source of randomness: the header's ERR_ARG
         _lib.check(_K["ERR_ARG"], "rbm_prob")
     nbytes = 4.0 * (M * K + V * H + N + M * N) + (4.0 * M if rows is not None else 0.0) + \
         (4.0 * M * N if mode is not None else 0.0) + (8.0 * M * N if mode == "replay" else 0.0)
@@ -3035,21 +3064,22 @@ def rbm_update(data, ph, nv, nh, W, v_bias, h_bias, err_partial, lr, *, rows=Non
     [B]) or data[b]; ph, nh [B, n_hidden], nv [B, n_visible] fp32 contiguous (their first B rows when they hold more)."""
     _need_dev(data, ph, nv, nh, W, v_bias, h_bias, err_partial, rows)
     L = _lib.load()
-    if W.dim() != 2 or W.dtype != torch.float32 or not W.is_contiguous() or not 1 <= W.shape[0] <= RBM_MAX_UNITS or \
-            not 1 <= W.shape[1] <= RBM_MAX_UNITS:
-        _lib.check(_K["ERR_SHAPE"], "rbm_update")
+    if not (_is(W, _F32, ndim=2) and 1 <= W.shape[0] <= RBM_MAX_UNITS and 1 <= W.shape[1] <= RBM_MAX_UNITS):
+        _refuse("rbm_update")
     V, H = W.shape
     if B is None:
-        B = rows.numel() if rows is not None else (data.shape[0] if data.dim() == 2 else 0)
+        B = rows.numel() if rows is not None else (data.shape[0] if _is(data, None, ndim=2, contig=False) else 0)
     B = int(B)
-    ok = 1 <= B <= RBM_MAX_BATCH and _rbm_rows_ok(data, rows, B, V)
-    for t, n in ((ph, H), (nv, V), (nh, H)):
-        ok = ok and t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous() and t.shape[1] == n and t.shape[0] >= B
-    for t, n in ((v_bias, V), (h_bias, H)):
-        ok = ok and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n
-    ok = ok and err_partial.dtype == torch.float64 and err_partial.is_contiguous() and err_partial.numel() >= rbm_error_tiles(V)
-    if not ok:
-        _lib.check(_K["ERR_SHAPE"], "rbm_update")
+    if not (1 <= B <= RBM_MAX_BATCH and
+            _is(data, _F32, (None, V), rows=1 if rows is not None else B, contig="last") and data.stride(0) >= V and
+            _is(rows, _I32, (B,), opt=True) and
+            _is(ph, _F32, (None, H), rows=B) and
+            _is(nv, _F32, (None, V), rows=B) and
+            _is(nh, _F32, (None, H), rows=B) and
+            _is(v_bias, _F32, V) and
+            _is(h_bias, _F32, H) and
+            _is(err_partial, _F64, least=rbm_error_tiles(V))):
+        _refuse("rbm_update")
     nbytes = 4.0 * (2 * B * V + 2 * B * H) + 8.0 * (V * H + V + H) + 8.0 * rbm_error_tiles(V) + (4.0 * B if rows is not None else 0.0)
     _call("rbm_update", L.sfm_rbm_update, (_p(data), _p(rows), _p(ph), _p(nv), _p(nh), _p(W), _p(v_bias), _p(h_bias), _p(err_partial),
                                            B, V, H, data.shape[0], data.stride(0), float(lr), _stream()),
@@ -3062,9 +3092,10 @@ def rbm_fold_error(partial, out, n_steps, num_samples, batch_size, n_visible):
     _need_dev(partial, out)
     L = _lib.load()
     tiles = rbm_error_tiles(n_visible)
-    if partial.dtype != torch.float64 or out.dtype != torch.float64 or not partial.is_contiguous() or out.numel() < 1 or \
-            partial.numel() < n_steps * tiles or n_steps != (num_samples + batch_size - 1) // max(batch_size, 1):
-        _lib.check(_K["ERR_SHAPE"], "rbm_fold_error")
+    if not (_is(partial, _F64, least=n_steps * tiles) and
+            _is(out, _F64, least=1, contig=False) and
+            n_steps == (num_samples + batch_size - 1) // max(batch_size, 1)):
+        _refuse("rbm_fold_error")
     _call("rbm_fold", L.sfm_rbm_fold_error, (_p(partial), _p(out), int(n_steps), tiles, int(num_samples), int(batch_size), int(n_visible),
                                              _stream()), float(n_steps) * (tiles + 2), 8.0 * n_steps * tiles + 8.0)
 
@@ -3079,24 +3110,20 @@ STOI_TAP_HALF, STOI_MAX_RATE, STOI_BWD_ROWS = _K["STOI_TAP_HALF"], _K["STOI_MAX_
 STOI_NBIN = STOI_LAST_BIN - STOI_FIRST_BIN + 1
 
 
-def _i32(*ts):
-    return all(t.dtype == torch.int32 and t.is_contiguous() for t in ts)
-
-
 def stoi_resample(sig, taps, in_off, in_len, out_off, out_len, B, n_out, max_out_len, n_in, up, down, padl, out=None):
     """polyphase FIR to 10 kHz: sig fp32 (flat), utterance u = sig[in_off[u] : in_off[u] + in_len[u]] -> out fp32 [n_out], utterance u at
     out_off[u], out_len[u] samples; taps fp32 [K, up] (evaluation.stoi_taal.resample_operand).  fp32 operands, fp64 sums.  n_out,
     max_out_len, n_in: host sums / maximum (sizes and the cost).  out: a buffer of the caller's (the adjoint's zero-padded rows)."""
     _need_dev(sig, taps, in_off, in_len, out_off, out_len, out)
     L = _lib.load()
-    if sig.dtype != torch.float32 or not sig.is_contiguous() or taps.dtype != torch.float32 or taps.dim() != 2 or taps.shape[1] != up or \
-            not taps.is_contiguous() or not _i32(in_off, in_len, out_off, out_len) or any(t.numel() != B for t in (in_off, in_len, out_off, out_len)):
-        _lib.check(_K["ERR_SHAPE"], "stoi_resample")
+    if not (_is(sig, _F32) and
+            _is(taps, _F32, (None, up)) and
+            _is(in_off, _I32, B) and _is(in_len, _I32, B) and _is(out_off, _I32, B) and _is(out_len, _I32, B) and
+            _is(out, _F32, least=n_out, opt=True)):
+        _refuse("stoi_resample")
     K = taps.shape[0]
     if out is None:
         out = torch.empty(max(n_out, 1), device=sig.device, dtype=torch.float32)
-    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < n_out:
-        _lib.check(_K["ERR_SHAPE"], "stoi_resample")
     _call("stoi", L.sfm_stoi_resample, (_p(sig), _p(taps), _p(in_off), _p(in_len), _p(out_off), _p(out_len), _p(out), B, int(max_out_len),
                                         int(up), int(down), K, int(padl), _stream()),
           2.0 * K * n_out, 4.0 * (n_in + n_out) + 4.0 * K * up + 16.0 * B, "resample %d/%d B%d out%d" % (up, down, B, n_out))
@@ -3109,9 +3136,11 @@ def stoi_keep(sig, win, sig_off, sig_len, frame_off, B, sum_frames, n_samples):
     order, kept int32 [B] their counts, energy fp64 [sum_frames] in dB).  sum_frames, n_samples: host sums (sizes and the cost)."""
     _need_dev(sig, win, sig_off, sig_len, frame_off)
     L = _lib.load()
-    if sig.dtype != torch.float32 or not sig.is_contiguous() or win.dtype != torch.float32 or win.numel() != STOI_FRAME or \
-            not _i32(sig_off, sig_len, frame_off) or sig_off.numel() != B or sig_len.numel() != B or frame_off.numel() != B + 1:
-        _lib.check(_K["ERR_SHAPE"], "stoi_keep")
+    if not (_is(sig, _F32) and
+            _is(win, _F32, STOI_FRAME, contig=False) and
+            _is(sig_off, _I32, B) and _is(sig_len, _I32, B) and
+            _is(frame_off, _I32, B + 1)):
+        _refuse("stoi_keep")
     energy = torch.empty(max(sum_frames, 1), device=sig.device, dtype=torch.float64)
     src = torch.empty(max(sum_frames, 1), device=sig.device, dtype=torch.int32)
     kept = torch.empty(B, device=sig.device, dtype=torch.int32)
@@ -3128,10 +3157,13 @@ def stoi_bands(sigs, win, dft, sig_off, frame_off, src, kept, tiles, sum_frames,
     _need_dev(win, dft, sig_off, frame_off, src, kept, tiles, *sigs)
     L = _lib.load()
     nsig = len(sigs)
-    if nsig not in (1, 2) or any(s.dtype != torch.float32 or not s.is_contiguous() for s in sigs) or dft.dtype != torch.float32 or \
-            tuple(dft.shape) != (STOI_FRAME, STOI_DFT_COLS) or not dft.is_contiguous() or win.numel() != STOI_FRAME or \
-            not _i32(sig_off, frame_off, src, kept, tiles) or tiles.dim() != 2 or tiles.shape[1] != 2 or src.numel() < sum_frames:
-        _lib.check(_K["ERR_SHAPE"], "stoi_bands")
+    if not (nsig in (1, 2) and _each(_F32, None, *sigs) and
+            _is(win, None, STOI_FRAME, contig=False) and
+            _is(dft, _F32, (STOI_FRAME, STOI_DFT_COLS)) and
+            _each(_I32, None, sig_off, frame_off, kept) and
+            _is(src, _I32, least=sum_frames) and
+            _is(tiles, _I32, ndim=2) and tiles.shape[1] == 2):
+        _refuse("stoi_bands")
     outs = tuple(torch.empty(max(sum_frames, 1), STOI_BANDS, device=sigs[0].device, dtype=torch.float32) for _ in sigs)
     n_tiles = tiles.shape[0]
     _call("stoi", L.sfm_stoi_bands, (_p(sigs[0]), _p(sigs[1]) if nsig == 2 else None, _p(win), _p(dft), _p(sig_off), _p(frame_off),
@@ -3149,9 +3181,11 @@ def stoi_segments(xb, yb, frame_off, kept, B, extended, spec_rows, segments):
     element of a 15 x 30 segment)."""
     _need_dev(xb, yb, frame_off, kept)
     L = _lib.load()
-    if xb.dtype != torch.float32 or yb.dtype != torch.float32 or xb.shape != yb.shape or xb.dim() != 2 or xb.shape[1] != STOI_BANDS or \
-            not xb.is_contiguous() or not yb.is_contiguous() or not _i32(frame_off, kept) or frame_off.numel() != B + 1 or kept.numel() != B:
-        _lib.check(_K["ERR_SHAPE"], "stoi_segments")
+    if not (_is(xb, _F32, (None, STOI_BANDS)) and
+            _is(yb, _F32, tuple(xb.shape)) and
+            _is(frame_off, _I32, B + 1) and
+            _is(kept, _I32, B)):
+        _refuse("stoi_segments")
     score = torch.empty(B, device=xb.device, dtype=torch.float64)
     _call("stoi", L.sfm_stoi_segments, (_p(xb), _p(yb), _p(frame_off), _p(kept), _p(score), B, 1 if extended else 0, _stream()),
           12.0 * STOI_SEG * STOI_BANDS * segments, 8.0 * STOI_BANDS * spec_rows + 8.0 * B + 4.0 * (2 * B + 1),
@@ -3168,11 +3202,14 @@ def stoi_bands_pair(ya, yb, win, dft, sig_off, frame_off, src, kept, tiles, sum_
     utterance's K - 1 are not written).  One DFT operand read serves both signals; spec_rows, n_samples as stoi_bands (the cost)."""
     _need_dev(ya, yb, win, dft, sig_off, frame_off, src, kept, tiles)
     L = _lib.load()
-    if any(s.dtype != torch.float32 or not s.is_contiguous() or s.dim() != 1 for s in (ya, yb)) or ya.numel() != yb.numel() or \
-            dft.dtype != torch.float32 or tuple(dft.shape) != (STOI_FRAME, STOI_DFT_COLS) or not dft.is_contiguous() or \
-            win.dtype != torch.float32 or win.numel() != STOI_FRAME or not _i32(sig_off, frame_off, src, kept, tiles) or \
-            tiles.dim() != 2 or tiles.shape[1] != 2 or src.numel() < sum_frames:
-        _lib.check(_K["ERR_SHAPE"], "stoi_bands_pair")
+    if not (_is(ya, _F32, ndim=1) and
+            _is(yb, _F32, (ya.numel(),)) and
+            _is(win, _F32, STOI_FRAME, contig=False) and
+            _is(dft, _F32, (STOI_FRAME, STOI_DFT_COLS)) and
+            _each(_I32, None, sig_off, frame_off, kept) and
+            _is(src, _I32, least=sum_frames) and
+            _is(tiles, _I32, ndim=2) and tiles.shape[1] == 2):
+        _refuse("stoi_bands_pair")
     planes = torch.empty(max(sum_frames, 1), STOI_PLANES, STOI_BANDS, device=ya.device, dtype=torch.float64)
     n_tiles = tiles.shape[0]
     _call("stoi", L.sfm_stoi_bands_pair, (_p(ya), _p(yb), _p(win), _p(dft), _p(sig_off), _p(frame_off), _p(src), _p(kept), _p(tiles),
@@ -3191,16 +3228,15 @@ def pso_fitness_taal(xb, planes, frame_off, kept, pos, stopped, fitness, extende
     are counted once (every particle of an utterance reads the same ones)."""
     _need_dev(xb, planes, frame_off, kept, pos, stopped, fitness)
     L = _lib.load()
-    ok = pos.dim() == 2 and fitness.shape == pos.shape
-    if ok:
-        B, N = pos.shape
-        rows = xb.shape[0] if xb.dim() == 2 else -1
-        ok = 1 <= N <= PSO_MAX_PARTICLES and B >= 1 and _pso_is(pos, torch.float64, B * N) and _pso_is(fitness, torch.float64, B * N)
-        ok = ok and _pso_is(stopped, torch.int32, B) and _pso_is(frame_off, torch.int32, B + 1) and _pso_is(kept, torch.int32, B)
-        ok = ok and rows >= 1 and _pso_is(xb, torch.float32, rows * STOI_BANDS) and xb.shape[1] == STOI_BANDS
-        ok = ok and _pso_is(planes, torch.float64, rows * STOI_PLANES * STOI_BANDS) and tuple(planes.shape[1:]) == (STOI_PLANES, STOI_BANDS)
-    if not ok:
-        _lib.check(_K["ERR_SHAPE"], "pso_fitness_taal")
+    if not (_is(xb, _F32, (None, STOI_BANDS), rows=1) and
+            _is(planes, _F64, (xb.shape[0], STOI_PLANES, STOI_BANDS)) and
+            _is(pos, _F64, ndim=2, rows=1) and 1 <= pos.shape[1] <= PSO_MAX_PARTICLES and
+            _is(frame_off, _I32, pos.shape[0] + 1) and
+            _is(kept, _I32, pos.shape[0]) and
+            _is(stopped, _I32, pos.shape[0]) and
+            _is(fitness, _F64, tuple(pos.shape))):
+        _refuse("pso_fitness_taal")
+    B, N = pos.shape
     _call("pso_fitness", L.sfm_pso_fitness_taal, (_p(xb), _p(planes), _p(frame_off), _p(kept), _p(pos), _p(stopped), _p(fitness), B, N,
                                                   1 if extended else 0, _stream()),
           N * (12.0 * STOI_SEG * STOI_BANDS * segments + 6.0 * STOI_BANDS * spec_rows),
@@ -3217,11 +3253,12 @@ def stoi_segments_bwd(xb, yb, frame_off, kept, gscore, B, max_rows, extended, sp
     one written."""
     _need_dev(xb, yb, frame_off, kept, gscore)
     L = _lib.load()
-    if xb.dtype != torch.float32 or yb.dtype != torch.float32 or xb.shape != yb.shape or xb.dim() != 2 or xb.shape[1] != STOI_BANDS or \
-            not xb.is_contiguous() or not yb.is_contiguous() or not _i32(frame_off, kept) or frame_off.numel() != B + 1 or \
-            kept.numel() != B or gscore.dtype != torch.float64 or gscore.numel() != B or not gscore.is_contiguous() or \
-            not 0 <= max_rows <= xb.shape[0]:
-        _lib.check(_K["ERR_SHAPE"], "stoi_segments_bwd")
+    if not (_is(xb, _F32, (None, STOI_BANDS)) and 0 <= max_rows <= xb.shape[0] and
+            _is(yb, _F32, tuple(xb.shape)) and
+            _is(frame_off, _I32, B + 1) and
+            _is(kept, _I32, B) and
+            _is(gscore, _F64, B)):
+        _refuse("stoi_segments_bwd")
     dyb = torch.empty_like(yb)
     _call("stoi", L.sfm_stoi_segments_bwd, (_p(xb), _p(yb), _p(frame_off), _p(kept), _p(gscore), _p(dyb), B, int(max_rows),
                                             1 if extended else 0, _stream()),
@@ -3236,13 +3273,15 @@ def stoi_bands_bwd(sig, win, dft, dft_t, sig_off, frame_off, src, kept, tiles, d
     transpose of dft.  Only the rows stoi_fold_bwd reads are written.  The cost: the forward's product and the adjoint one."""
     _need_dev(sig, win, dft, dft_t, sig_off, frame_off, src, kept, tiles, dyb)
     L = _lib.load()
-    if sig.dtype != torch.float32 or not sig.is_contiguous() or dft.dtype != torch.float32 or dft_t.dtype != torch.float32 or \
-            tuple(dft.shape) != (STOI_FRAME, STOI_DFT_COLS) or tuple(dft_t.shape) != (STOI_DFT_COLS, STOI_FRAME) or \
-            not dft.is_contiguous() or not dft_t.is_contiguous() or win.numel() != STOI_FRAME or win.dtype != torch.float32 or \
-            not _i32(sig_off, frame_off, src, kept, tiles) or tiles.dim() != 2 or tiles.shape[1] != 2 or src.numel() < sum_frames or \
-            dyb.dtype != torch.float32 or not dyb.is_contiguous() or dyb.dim() != 2 or dyb.shape[1] != STOI_BANDS or \
-            dyb.shape[0] < sum_frames:
-        _lib.check(_K["ERR_SHAPE"], "stoi_bands_bwd")
+    if not (_is(sig, _F32) and
+            _is(win, _F32, STOI_FRAME, contig=False) and
+            _is(dft, _F32, (STOI_FRAME, STOI_DFT_COLS)) and
+            _is(dft_t, _F32, (STOI_DFT_COLS, STOI_FRAME)) and
+            _each(_I32, None, sig_off, frame_off, kept) and
+            _is(src, _I32, least=sum_frames) and
+            _is(tiles, _I32, ndim=2) and tiles.shape[1] == 2 and
+            _is(dyb, _F32, (None, STOI_BANDS), rows=sum_frames)):
+        _refuse("stoi_bands_bwd")
     dframes = torch.empty(max(sum_frames, 1), STOI_FRAME, device=sig.device, dtype=torch.float32)
     n_tiles = tiles.shape[0]
     _call("stoi", L.sfm_stoi_bands_bwd, (_p(sig), _p(win), _p(dft), _p(dft_t), _p(sig_off), _p(frame_off), _p(src), _p(kept), _p(tiles),
@@ -3259,11 +3298,14 @@ def stoi_fold_bwd(dframes, win, sig_off, sig_len, frame_off, src, kept, B, n_out
     of sig_len and pad_to (host figures)."""
     _need_dev(dframes, win, sig_off, sig_len, frame_off, src, kept)
     L = _lib.load()
-    if dframes.dtype != torch.float32 or not dframes.is_contiguous() or dframes.dim() != 2 or dframes.shape[1] != STOI_FRAME or \
-            dframes.shape[0] < sum_frames or win.dtype != torch.float32 or win.numel() != STOI_FRAME or \
-            not _i32(sig_off, sig_len, frame_off, src, kept) or sig_off.numel() != B or sig_len.numel() != B or \
-            frame_off.numel() != B + 1 or kept.numel() != B or src.numel() < sum_frames or not 0 <= pad_to <= max_len:
-        _lib.check(_K["ERR_SHAPE"], "stoi_fold_bwd")
+    if not (_is(dframes, _F32, (None, STOI_FRAME), rows=sum_frames) and
+            _is(win, _F32, STOI_FRAME, contig=False) and
+            _is(sig_off, _I32, B) and _is(sig_len, _I32, B) and
+            _is(frame_off, _I32, B + 1) and
+            _is(src, _I32, least=sum_frames) and
+            _is(kept, _I32, B) and
+            0 <= pad_to <= max_len):
+        _refuse("stoi_fold_bwd")
     dsig = torch.empty(max(n_out, 1), device=dframes.device, dtype=torch.float32)
     _call("stoi", L.sfm_stoi_fold_bwd, (_p(dframes), _p(win), _p(sig_off), _p(sig_len), _p(frame_off), _p(src), _p(kept), _p(dsig), B,
                                         int(max_len), int(pad_to), _stream()),

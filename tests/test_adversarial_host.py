@@ -192,28 +192,11 @@ def test_layer_plan():
 
 
 # ---- launch costs: stub library, recorded _call, literal expectations (tests/test_launch_costs_host.py) ------------------------
-class _StubLib:
-    def __getattr__(self, symbol):
-        if not symbol.startswith("sfm_"):
-            raise AttributeError(symbol)
-        fn = lambda *args: 0
-        fn.__name__ = symbol
-        return fn
-
-
 @pytest.fixture
 def launches(monkeypatch):
-    from sincformer_metacog_speech_enhancement_amd import lib, ops
-    rec = []
-
-    def record(name, fn, args, flops=0.0, nbytes=0.0, tag=None):
-        assert len(args) == len(lib.SIGNATURES[fn.__name__]), fn.__name__
-        rec.append((fn.__name__, name, flops, nbytes))
-
-    monkeypatch.setattr(ops._lib, "load", lambda: _StubLib())
-    monkeypatch.setattr(ops, "_stream", lambda: None)
-    monkeypatch.setattr(ops, "_need_dev", lambda *ts: None)
-    monkeypatch.setattr(ops, "_call", record)
+    import ops_stub
+    from sincformer_metacog_speech_enhancement_amd import ops
+    rec = ops_stub.install(monkeypatch, tags=False)
     monkeypatch.setattr(ops, "_ws", lambda n, device, dtype=torch.float32: torch.zeros(1, dtype=dtype))
     return rec
 

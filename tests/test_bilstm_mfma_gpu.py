@@ -130,29 +130,10 @@ def test_rows16_is_convert_rows_of_the_fp32_result(ops, data, dt, pad):
 
 
 # ---- routing of the fused forward, on the CPU: the wrappers run against a stub library and a recording _call ------------------
-class _StubLib:
-    def __getattr__(self, symbol):
-        if not symbol.startswith("sfm_"):
-            raise AttributeError(symbol)
-        fn = lambda *args: 0
-        fn.__name__ = symbol
-        return fn
-
-
 @pytest.fixture
 def launches(monkeypatch):
-    from sincformer_metacog_speech_enhancement_amd import lib, ops as _ops
-    rec = []
-
-    def record(name, fn, args, flops=0.0, nbytes=0.0, tag=None):
-        assert len(args) == len(lib.SIGNATURES[fn.__name__]), fn.__name__
-        rec.append((fn.__name__, name, flops, nbytes))
-
-    monkeypatch.setattr(_ops._lib, "load", lambda: _StubLib())
-    monkeypatch.setattr(_ops, "_stream", lambda: None)
-    monkeypatch.setattr(_ops, "_need_dev", lambda *ts: None)
-    monkeypatch.setattr(_ops, "_call", record)
-    return rec
+    import ops_stub
+    return ops_stub.install(monkeypatch, tags=False)
 
 
 def _cpea_pack(ops_, Hh, D=64):

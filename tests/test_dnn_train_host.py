@@ -13,6 +13,7 @@ import torch
 
 import dnn_cases as dn
 import dnn_train_cases as tc
+import ops_stub
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g25_dnn_train.npz")
 
@@ -245,23 +246,8 @@ def test_argument_guards_without_a_gpu(built):
 
 
 def test_launch_costs(monkeypatch):
-    from sincformer_metacog_speech_enhancement_amd import lib, ops
-    rec = []
-
-    class Stub:
-        def __getattr__(self, symbol):
-            fn = lambda *a: 0
-            fn.__name__ = symbol
-            return fn
-
-    def record(name, fn, args, flops=0.0, nbytes=0.0, tag=None):
-        assert len(args) == len(lib.SIGNATURES[fn.__name__]), fn.__name__
-        rec.append((fn.__name__, name, flops, nbytes, tag))
-    monkeypatch.setattr(ops._lib, "load", lambda: Stub())
-    monkeypatch.setattr(ops, "_stream", lambda: None)
-    monkeypatch.setattr(ops, "_need_dev", lambda *ts: None)
-    monkeypatch.setattr(ops, "_call", record)
-    monkeypatch.setattr(ops, "_ws64", lambda n, device: None)
+    from sincformer_metacog_speech_enhancement_amd import ops
+    rec = ops_stub.install(monkeypatch)
     ops.set_compute_dtype(torch.float16)
     N, D, M = 1000, 54, 256
     raw, bounds = torch.zeros(N, D), torch.zeros(N, 2, dtype=torch.int32)

@@ -16,6 +16,7 @@ import torch
 
 import feature_cases as fc
 import helpers as hp
+import ops_stub
 from sincformer_metacog_speech_enhancement_amd import config, lib, ops
 from sincformer_metacog_speech_enhancement_amd.signal_processing import (FeatureExtractor, bark_to_hz, extract_ams, extract_gfcc,
                                                                          extract_mfcc, extract_rasta_plp, hz_to_bark, hz_to_mel,
@@ -172,26 +173,8 @@ def test_entry_points_check_their_arguments_without_a_gpu():
     assert L.sfm_rows_mean(one, None, one, 1, 4, 400, 160, 80, 13, 0, 14, 0, None) == -2
 
 
-class _StubLib:
-    def __getattr__(self, symbol):
-        if not symbol.startswith("sfm_"):
-            raise AttributeError(symbol)
-        fn = lambda *args: 0
-        fn.__name__ = symbol
-        return fn
-
-
 def test_front_end_costs(monkeypatch):
-    rec = []
-
-    def record(name, fn, args, flops=0.0, nbytes=0.0, tag=None):
-        assert len(args) == len(lib.SIGNATURES[fn.__name__]), fn.__name__
-        rec.append((fn.__name__, name, flops, nbytes, tag))
-
-    monkeypatch.setattr(ops._lib, "load", lambda: _StubLib())
-    monkeypatch.setattr(ops, "_stream", lambda: None)
-    monkeypatch.setattr(ops, "_need_dev", lambda *ts: None)
-    monkeypatch.setattr(ops, "_call", record)
+    rec = ops_stub.install(monkeypatch)
     B, T, L = 3, 29, 2403
     spec, out = torch.zeros(B, T, 772), torch.zeros(B, T, 54)
     fr = dict(B=B, T=T, L=L, frame=160, hop=80)

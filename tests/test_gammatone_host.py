@@ -10,6 +10,7 @@ import torch
 
 import gammatone_cases as gc
 import helpers as hp
+import ops_stub
 from sincformer_metacog_speech_enhancement_amd import config, lib, ops
 from sincformer_metacog_speech_enhancement_amd.signal_processing import (GammatoneFilterbank, erb_bandwidth, erb_space,
                                                                          gammatone_impulse_response)
@@ -164,28 +165,9 @@ def test_entry_points_check_their_arguments_without_a_gpu():
     assert L.sfm_gammatone_tf_finish(one, one, None, one, one, None, None, 1, 64, 4, 4, 1, 400, 160, 80, 256, None) == -2
 
 
-class _StubLib:
-    def __getattr__(self, symbol):
-        if not symbol.startswith("sfm_"):
-            raise AttributeError(symbol)
-        fn = lambda *args: 0
-        fn.__name__ = symbol
-        return fn
-
-
 @pytest.fixture
 def launches(monkeypatch):
-    rec = []
-
-    def record(name, fn, args, flops=0.0, nbytes=0.0, tag=None):
-        assert len(args) == len(lib.SIGNATURES[fn.__name__]), fn.__name__
-        rec.append((fn.__name__, name, flops, nbytes, tag))
-
-    monkeypatch.setattr(ops._lib, "load", lambda: _StubLib())
-    monkeypatch.setattr(ops, "_stream", lambda: None)
-    monkeypatch.setattr(ops, "_need_dev", lambda *ts: None)
-    monkeypatch.setattr(ops, "_call", record)
-    return rec
+    return ops_stub.install(monkeypatch)
 
 
 def test_gammatone_costs(launches):

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import haircell_cases as hc
+import ops_stub
 from sincformer_metacog_speech_enhancement_amd import lib, ops
 from sincformer_metacog_speech_enhancement_amd.signal_processing import MeddisHairCell
 
@@ -103,26 +104,8 @@ def test_entry_points_check_their_arguments_without_a_gpu():
     assert L.sfm_haircell_frames(one, one, None, one, 64, 64, 100, 160, 80, 1, None) == -2      # shorter than a frame
 
 
-class _StubLib:
-    def __getattr__(self, symbol):
-        if not symbol.startswith("sfm_"):
-            raise AttributeError(symbol)
-        fn = lambda *args: 0
-        fn.__name__ = symbol
-        return fn
-
-
 def test_haircell_costs(monkeypatch):
-    rec = []
-
-    def record(name, fn, args, flops=0.0, nbytes=0.0, tag=None):
-        assert len(args) == len(lib.SIGNATURES[fn.__name__]), fn.__name__
-        rec.append((fn.__name__, name, flops, nbytes, tag))
-
-    monkeypatch.setattr(ops._lib, "load", lambda: _StubLib())
-    monkeypatch.setattr(ops, "_stream", lambda: None)
-    monkeypatch.setattr(ops, "_need_dev", lambda *ts: None)
-    monkeypatch.setattr(ops, "_call", record)
+    rec = ops_stub.install(monkeypatch)
     par = torch.zeros(12, dtype=torch.float64)
     assert ops.haircell(torch.zeros(128, 2403), par).shape == (128, 2403)
     out = ops.haircell_frames(torch.zeros(2, 64, 2403), par, 160, 80)

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import intelligibility_cases as ic
+import ops_stub
 from sincformer_metacog_speech_enhancement_amd import evaluation, lib, ops
 from sincformer_metacog_speech_enhancement_amd.evaluation import csii, intelligibility, ncm
 
@@ -166,26 +167,8 @@ def test_abi_guards_without_a_gpu():
     assert L.sfm_ncm_finish(one, one, one, one, one, one, 1, 65, None) == -2
 
 
-class _StubLib:
-    def __getattr__(self, symbol):
-        if not symbol.startswith("sfm_"):
-            raise AttributeError(symbol)
-        fn = lambda *args: 0
-        fn.__name__ = symbol
-        return fn
-
-
 def test_launch_costs(monkeypatch):
-    rec = []
-
-    def record(name, fn, args, flops=0.0, nbytes=0.0, tag=None):
-        assert len(args) == len(lib.SIGNATURES[fn.__name__]), fn.__name__
-        rec.append((fn.__name__, name, flops, nbytes, tag))
-
-    monkeypatch.setattr(ops._lib, "load", lambda: _StubLib())
-    monkeypatch.setattr(ops, "_stream", lambda: None)
-    monkeypatch.setattr(ops, "_need_dev", lambda *ts: None)
-    monkeypatch.setattr(ops, "_call", record)
+    rec = ops_stub.install(monkeypatch)
     monkeypatch.setattr(ops, "hilbert_table", lambda L, dev: torch.zeros(2 * L))
     B, C, L = 2, 64, 1000
     planes = torch.zeros(4, 30, 129)

@@ -4,38 +4,16 @@ library is needed; the expected figures are literals (each 
 import torch
 import pytest
 
-from sincformer_metacog_speech_enhancement_amd import lib, ops
+import ops_stub
+from sincformer_metacog_speech_enhancement_amd import ops
 
 F16, F32 = torch.float16, torch.float32
-
-
-class _StubLib:
-    """every entry point returns 0; the size helpers (*_floats, *_doubles, *_tiles) return a small positive count, which is
-    also a true answer of the predicate sfm_gammatone_tf_fits"""
-
-    def __getattr__(self, symbol):
-        if not symbol.startswith("sfm_"):
-            raise AttributeError(symbol)
-        rc = 4 if symbol.endswith(("_floats", "_doubles", "_tiles", "_fits")) else 0
-        fn = lambda *args: rc
-        fn.__name__ = symbol
-        return fn
 
 
 @pytest.fixture
 def launches(monkeypatch):
     """[(symbol, family, flops, bytes, tag)] of every launch the wrappers under test enqueue"""
-    rec = []
-
-    def record(name, fn, args, flops=0.0, nbytes=0.0, tag=None):
-        assert len(args) == len(lib.SIGNATURES[fn.__name__]), fn.__name__       # the tuple has the header's length
-        rec.append((fn.__name__, name, flops, nbytes, tag))
-
-    monkeypatch.setattr(ops._lib, "load", lambda: _StubLib())
-    monkeypatch.setattr(ops, "_stream", lambda: None)
-    monkeypatch.setattr(ops, "_need_dev", lambda *ts: None)
-    monkeypatch.setattr(ops, "_call", record)
-    return rec
+    return ops_stub.install(monkeypatch)
 
 
 def _pack(N, K, Npad, Kpad, ksize, cin, glu=False):

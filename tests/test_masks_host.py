@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import mask_cases as mc
+import ops_stub
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 MASKS = ("irm", "pcirm")
@@ -172,28 +173,10 @@ def test_argument_guards_without_a_gpu():
         assert curr(kind=3, table=one, M=M) == -2
 
 
-class _StubLib:
-    def __getattr__(self, symbol):
-        if not symbol.startswith("sfm_"):
-            raise AttributeError(symbol)
-        fn = lambda *args: 0
-        fn.__name__ = symbol
-        return fn
-
-
 def test_launch_costs_of_the_new_wrappers(monkeypatch):
     """(symbol, family, flops, bytes, tag) of every launch, literals: each operand read once, each result written once"""
-    from sincformer_metacog_speech_enhancement_amd import lib, ops
-    rec = []
-
-    def record(name, fn, args, flops=0.0, nbytes=0.0, tag=None):
-        assert len(args) == len(lib.SIGNATURES[fn.__name__]), fn.__name__
-        rec.append((fn.__name__, name, flops, nbytes, tag))
-    monkeypatch.setattr(ops._lib, "load", lambda: _StubLib())
-    monkeypatch.setattr(ops, "_stream", lambda: None)
-    monkeypatch.setattr(ops, "_need_dev", lambda *ts: None)
-    monkeypatch.setattr(ops, "_call", record)
-    monkeypatch.setattr(ops, "_ws64", lambda n, device: torch.zeros(int(n), dtype=torch.float64))
+    from sincformer_metacog_speech_enhancement_amd import ops
+    rec = ops_stub.install(monkeypatch)
     x = torch.zeros(2, 5, 129)                                       # n = 1290
     ops.mask_irm(x, x)
     ops.mask_corr(x, x, x)

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import ops_stub
 import pso_cases as pc
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -159,25 +160,9 @@ def test_entry_points_refuse_bad_arguments_before_any_launch(L):
 
 
 def test_wrappers_state_their_launch_costs(monkeypatch):
-    from sincformer_metacog_speech_enhancement_amd import lib, ops
+    from sincformer_metacog_speech_enhancement_amd import ops
     from sincformer_metacog_speech_enhancement_amd.optimizer import SwarmState
-    rec = []
-
-    class Stub:
-        def __getattr__(self, symbol):
-            fn = lambda *args: 0
-            fn.__name__ = symbol
-            return fn
-
-    def record(name, fn, args, flops=0.0, nbytes=0.0, tag=None):
-        assert len(args) == len(lib.SIGNATURES[fn.__name__]), fn.__name__
-        rec.append((fn.__name__, name, flops, nbytes, tag))
-
-    monkeypatch.setattr(ops._lib, "load", lambda: Stub())
-    monkeypatch.setattr(ops, "_stream", lambda: None)
-    monkeypatch.setattr(ops, "_need_dev", lambda *ts: None)
-    monkeypatch.setattr(ops, "_call", record)
-    monkeypatch.setattr(ops, "_ws64", lambda n, device: torch.zeros(int(n), dtype=torch.float64))
+    rec = ops_stub.install(monkeypatch)
     B, C, T, Lmax, N, K, F, NF = 2, 64, 50, 4000, 8, 3, 103, 38
     table = torch.zeros(7, dtype=torch.float64)
     a, b = ops.pso_frame_coef(torch.zeros(B, C, T), table, 3)

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import dropout_cases as dc
+import ops_stub
 import rbm_cases as rc
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -231,30 +232,9 @@ def test_rbm_update_and_fold_guards_without_a_gpu(L):
 
 
 # ---- the launch costs the wrappers state ----
-class _StubLib:
-    def __getattr__(self, symbol):
-        if not symbol.startswith("sfm_"):
-            raise AttributeError(symbol)
-        fn = lambda *args: 0
-        fn.__name__ = symbol
-        return fn
-
-
 @pytest.fixture
-def launches(monkeypatch, pkg):
-    from sincformer_metacog_speech_enhancement_amd import lib
-    ops = pkg["ops"]
-    rec = []
-
-    def record(name, fn, args, flops=0.0, nbytes=0.0, tag=None):
-        assert len(args) == len(lib.SIGNATURES[fn.__name__]), fn.__name__
-        rec.append((fn.__name__, name, flops, nbytes, tag))
-
-    monkeypatch.setattr(ops._lib, "load", lambda: _StubLib())
-    monkeypatch.setattr(ops, "_stream", lambda: None)
-    monkeypatch.setattr(ops, "_need_dev", lambda *ts: None)
-    monkeypatch.setattr(ops, "_call", record)
-    return rec
+def launches(monkeypatch):
+    return ops_stub.install(monkeypatch)
 
 
 def test_rbm_launch_costs(launches, pkg):

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import ops_stub
 import resynth_cases as rc
 from sincformer_metacog_speech_enhancement_amd import lib, ops, training
 
@@ -158,30 +159,10 @@ def test_python_guards_raise_value_error():
 
 
 # ---- the launch's stated cost (the stub-library pattern of tests/test_launch_costs_host.py) ----
-class _StubLib:
-    def __getattr__(self, symbol):
-        if not symbol.startswith("sfm_"):
-            raise AttributeError(symbol)
-        rc_ = 4 if symbol.endswith(("_floats", "_doubles", "_tiles", "_fits")) else 0
-        fn = lambda *args: rc_
-        fn.__name__ = symbol
-        return fn
-
-
 @pytest.fixture
 def launches(monkeypatch):
     """[(symbol, family, flops, bytes, tag)] of every launch the wrappers under test enqueue"""
-    rec = []
-
-    def record(name, fn, args, flops=0.0, nbytes=0.0, tag=None):
-        assert len(args) == len(lib.SIGNATURES[fn.__name__]), fn.__name__       # the tuple has the header's length
-        rec.append((fn.__name__, name, flops, nbytes, tag))
-
-    monkeypatch.setattr(ops._lib, "load", lambda: _StubLib())
-    monkeypatch.setattr(ops, "_stream", lambda: None)
-    monkeypatch.setattr(ops, "_need_dev", lambda *ts: None)
-    monkeypatch.setattr(ops, "_call", record)
-    return rec
+    return ops_stub.install(monkeypatch)
 
 
 def test_mask_resynth_cost(launches):

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import ops_stub
 import stoi_loss_cases as lc
 import stoi_taal_cases as sc
 from sincformer_metacog_speech_enhancement_amd import lib, ops
@@ -162,25 +163,8 @@ def test_refusals_without_a_gpu():
 
 
 # ---- the entry points ----
-class _StubLib:
-    def __getattr__(self, symbol):
-        if not symbol.startswith("sfm_"):
-            raise AttributeError(symbol)
-        fn = lambda *args: 0
-        fn.__name__ = symbol
-        return fn
-
-
 def test_backward_launch_costs(monkeypatch):
-    rec = []
-
-    def record(name, fn, args, flops=0.0, nbytes=0.0, tag=None):
-        assert len(args) == len(lib.SIGNATURES[fn.__name__]), fn.__name__
-        rec.append((fn.__name__, name, flops, nbytes, tag))
-    monkeypatch.setattr(ops._lib, "load", lambda: _StubLib())
-    monkeypatch.setattr(ops, "_stream", lambda: None)
-    monkeypatch.setattr(ops, "_need_dev", lambda *ts: None)
-    monkeypatch.setattr(ops, "_call", record)
+    rec = ops_stub.install(monkeypatch)
     p = st.plan_tables([6000, 100, 9601], 16000, np.arange(3) * 9601)
     i32 = lambda a: torch.from_numpy(np.asarray(a).astype(np.int32))
     so, sl, fo, tiles = i32(p["sig_off"]), i32(p["sig_len"]), i32(p["frame_off"]), i32(p["tiles"])

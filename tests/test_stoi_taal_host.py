@@ -8,6 +8,7 @@ import pytest
 import torch
 from scipy import signal
 
+import ops_stub
 import stoi_taal_cases as sc
 from sincformer_metacog_speech_enhancement_amd import lib, ops
 from sincformer_metacog_speech_enhancement_amd.evaluation import packed, stoi as pstoi, stoi_taal as st
@@ -155,28 +156,9 @@ def test_unsupported_rate_and_unknown_names():
 
 
 # ---- launch costs: the recording _call of tests/test_launch_costs_host.py ----
-class _StubLib:
-    def __getattr__(self, symbol):
-        if not symbol.startswith("sfm_"):
-            raise AttributeError(symbol)
-        fn = lambda *args: 0
-        fn.__name__ = symbol
-        return fn
-
-
 @pytest.fixture
 def launches(monkeypatch):
-    rec = []
-
-    def record(name, fn, args, flops=0.0, nbytes=0.0, tag=None):
-        assert len(args) == len(lib.SIGNATURES[fn.__name__]), fn.__name__
-        rec.append((fn.__name__, name, flops, nbytes, tag))
-
-    monkeypatch.setattr(ops._lib, "load", lambda: _StubLib())
-    monkeypatch.setattr(ops, "_stream", lambda: None)
-    monkeypatch.setattr(ops, "_need_dev", lambda *ts: None)
-    monkeypatch.setattr(ops, "_call", record)
-    return rec
+    return ops_stub.install(monkeypatch)
 
 
 def test_stoi_launch_costs(launches):
