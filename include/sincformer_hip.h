@@ -47,7 +47,8 @@ extern "C" {
 #define SFM_XCD_RUN 8                  /* ... and the head_dim-64 attention kernels give each XCD runs of this many consecutive logical items */
 #define SFM_DWCONV_TILE 64             /* frames of a workgroup of the register-resident depthwise kernels: the tile of sfm_dwconv_folded_varlen's table */
 #define SFM_SINC_FIR16_WS_WORDS 278528 /* 16-bit words of sfm_sinc_fir16's staging buffer wsh (8 shifts x (hi, lo) x 64 channels x 272 padded taps) */
-#define SFM_PSTOI_MAX_BANDS 32         /* sfm_pstoi_loss: NB, F and frame_len (2 ..) it takes */
+#define SFM_SINC_FIR16_STREAM1 (-1)    /* sfm_sinc_fir16_ex's passes: one pass by the streaming kernel (taps in LDS), the bitwise reference of passes = 1 */
+#define SFM_PSTOI_MAX_BANDS 32        /* sfm_pstoi_loss: NB, F and frame_len (2 ..) it takes */
 #define SFM_PSTOI_MAX_BINS 257
 #define SFM_PSTOI_MIN_FRAME_LEN 2
 #define SFM_PSTOI_MAX_FRAME_LEN 32
@@ -314,7 +315,9 @@ int sfm_sinc_fir16_tiles(int L);
 int sfm_sinc_fir16(const float* wave, const float* filt, void* wsh, void* out, float* gn_partial, int B,
                    int L, int C, int K, int out_f32, int dtype, void* stream);
 /* passes: 3 = split operands (hi x hi + hi x lo + lo x hi: 1e-7 / 1e-6 max error), 1 = one rounding of waveform and taps to the
- * operand format, 0 = auto (1 for fp16 operands with a 16-bit result, else 3) - sfm_sinc_fir16 = passes 0 */
+ * operand format (the kernel that keeps a shift's taps in registers), 0 = auto (1 for fp16 operands with a 16-bit result,
+ * else 3) - sfm_sinc_fir16 = passes 0; SFM_SINC_FIR16_STREAM1 = the result of passes 1, bit for bit (out and gn_partial), from
+ * the streaming one-pass kernel that keeps the taps in LDS: kept as the reference and A/B partner of the resident one */
 int sfm_sinc_fir16_ex(const float* wave, const float* filt, void* wsh, void* out, float* gn_partial, int B, int L, int C, int K,
                       int out_f32, int dtype, int passes, void* stream);
 /* The same frames-x-matrix product on the 16-bit matrix cores with split bf16 operands (hi + lo, 3 MFMAs per k-step,

@@ -300,21 +300,23 @@ __global__ __launch_bounds__(256, 2) void conv16p_kernel(ConvPParams p) {
     }
   };
 
-  f32x16 acc[NPASS][2][2], accs[2][2];                 // started from the bias behind the first patch (convp_acc_init)
+  // Started from the bias behind the first patch (convp_acc_init, under `if (slab == 0)` in the slab loop).  Until then their
+  // contents do not matter, but a zero fill here is not dead to the compiler (the overwrite is conditional): it cost 64 x NPASS
+  // (+ 64 for the skip tile) v_mov per lane and tile.  The empty asm defines each register tuple with NO instruction; left
+  // plainly uninitialised the compiler peels the first slab instead and spills in the k 7 + skip kernels.
+  f32x16 acc[NPASS][2][2], accs[2][2];
 #pragma unroll
   for (int n = 0; n < NPASS; ++n)
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-      for (int j = 0; j < 2; ++j)
+      for (int j = 0; j < 2; ++j) asm volatile("" : "=v"(acc[n][i][j]));
+  if (SKIP) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc[n][i][j][r] = 0.f;
+    for (int i = 0; i < 2; ++i)
 #pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) accs[i][j][r] = 0.f;
+      for (int j = 0; j < 2; ++j) asm volatile("" : "=v"(accs[i][j]));
+  }
 
   int fb_off[2][4];
 #pragma unroll

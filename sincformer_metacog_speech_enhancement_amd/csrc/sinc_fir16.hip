@@ -13,6 +13,12 @@
 // sub-tile's samples are prefetched into registers under the MFMAs.
 // Epilogue: * 2^-12 (filters are pre-scaled by 2^12 to stay out of fp16 subnormals), GroupNorm
 // partial sums, LDS transpose, full 128-byte channels-last row stores.
+//
+// Two kernels share this scheme.  sinc_fir16_kernel<T, PASSES> (streaming: taps in LDS, as described above) runs the three-pass
+// product and remains the bitwise reference of the one-pass one.  sinc_fir16_resident_kernel<T> is the one-pass path
+// (passes = 1 and the fp16 / 16-bit default): workgroup (4 waves) = (shift o, segment of 1024-sample spans, utterance), the hi
+// taps of the shift live in each wave's REGISTERS (136 VGPRs), nothing of the lo halves is loaded, computed or stored, the
+// signal span is staged hi-only in a double buffer with one barrier per span, and two workgroups fit a CU (40 000 B of LDS).
 #include "sfm_common.h"
 
 #define FIR_C 64
@@ -169,6 +175,152 @@ __global__ __launch_bounds__(FIR_WAVES * 64) void sinc_fir16_kernel(const float*
   }
 }
 
+// ---- one pass, taps resident in registers ----
+// With one pass the B fragments of a shift are 2 column blocks x 17 k-steps x 4 VGPRs = 136 VGPRs: a wave loads them ONCE from
+// wsh (hi part only) and keeps them while it walks the wave-tiles of its workgroup's segment, so the k-loop reads LDS for the 17
+// signal fragments alone (the streaming kernel above reads 34 tap fragments as well and is bound by those reads).  Workgroup
+// (4 waves) = (shift o, segment of 1024-sample spans, utterance); LDS = two hi-only signal spans (double buffer, ONE barrier per
+// span: the fp32 loads of span s + 2 are in flight under the MFMAs of span s + 1) + the per-wave fp32 images = 40 000 B, so two
+// workgroups share a CU and one's epilogue runs under the other's MFMAs.  Per wave-tile g = sample / 256 everything the
+// streaming kernel computes is computed in the same order - k0 ascending into the same two accumulators, * 2^-12, image, GroupNorm
+// sums per lane over r0 then e, xor shuffles, 16-byte row stores, partial slot (g / 8) * 64 + o * 8 + g % 8 - so out and
+// gn_partial are bit-identical to sinc_fir16_kernel<T, 1>.
+#define FIRR_WAVES 4
+#define FIRR_OUT (FIRR_WAVES * 256)                            // output samples per span
+#define FIRR_SPAN (FIRR_OUT + FIR_KP)                          // staged samples per span
+#define FIRR_XPT ((FIRR_SPAN + FIRR_WAVES * 64 - 1) / (FIRR_WAVES * 64))
+#define FIRR_LDS (2 * FIRR_SPAN * 2 + FIRR_WAVES * 32 * 68 * 4)
+static_assert((FIRR_SPAN * 2) % 16 == 0, "the second span buffer and the images stay 16-byte aligned");
+static_assert((FIRR_WAVES - 1) * 256 + 8 * 31 + 8 + (FIR_KP - 16) + 8 <= FIRR_SPAN, "the last lane's last fragment lies inside the span");
+static_assert(FIR_NSUB * FIR_SUB % FIRR_OUT == 0, "a chunk of sfm_sinc_fir16_tiles is whole spans: its slots cover every wave-tile walked");
+
+template <class T>
+__global__ __launch_bounds__(FIRR_WAVES * 64, 2) void sinc_fir16_resident_kernel(const float* __restrict__ sig,
+                                                                                const u16* __restrict__ wsh, void* __restrict__ out,
+                                                                                float* __restrict__ gn_partial, int L, int pad,
+                                                                                int out_f32, int tiles_per_batch, int spans_per_wg) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];
+  u16* Xh = reinterpret_cast<u16*>(dsm);                       // [2][FIRR_SPAN]
+  float* img = reinterpret_cast<float*>(Xh + 2 * FIRR_SPAN);   // FIRR_WAVES x [32][68] floats
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l31 = lane & 31, hl = lane >> 5;
+  const int o = blockIdx.x, b = blockIdx.z;
+  const int s0 = blockIdx.y * spans_per_wg;
+  const int s1 = min(s0 + spans_per_wg, (L + FIRR_OUT - 1) / FIRR_OUT);
+  const float* xb = sig + (long long)b * L;
+
+  // this shift's taps (hi), as the B fragments of every k-step: registers for the whole life of the wave
+  u32x4 wt[2][FIR_KP / 16];
+  {
+    const u16* src = wsh + (long long)o * 2 * FIR_C * FIR_KP;
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int s = 0; s < FIR_KP / 16; ++s)
+        wt[j][s] = *reinterpret_cast<const u32x4*>(src + (j * 32 + l31) * FIR_KP + s * 16 + 8 * hl);
+  }
+
+  constexpr int NT = FIRR_WAVES * 64;
+  float xr[FIRR_XPT];
+  auto load_span = [&](int m0) {
+#pragma unroll
+    for (int q = 0; q < FIRR_XPT; ++q) {
+      const int i = tid + q * NT;
+      const int sidx = m0 + i - pad;
+      xr[q] = (i < FIRR_SPAN && sidx >= 0 && sidx < L) ? xb[sidx] : 0.f;
+    }
+  };
+  auto write_span = [&](u16* X) {
+#pragma unroll
+    for (int q = 0; q < FIRR_XPT; ++q) {
+      const int i = tid + q * NT;
+      if (i < FIRR_SPAN) X[i] = T::from_f32(xr[q]);
+    }
+  };
+  load_span(s0 * FIRR_OUT);
+  write_span(Xh);
+  if (s0 + 1 < s1) load_span((s0 + 1) * FIRR_OUT);
+#pragma unroll
+  for (int j = 0; j < 2; ++j)
+#pragma unroll
+    for (int s = 0; s < FIR_KP / 16; ++s) asm volatile("" : "+v"(wt[j][s]));      // loaded here, once: never re-fetched in the loop
+  __syncthreads();
+
+  float* im = img + wave * (32 * 68);
+  const int xoff = wave * 256 + 8 * l31 + 8 * hl;              // + k0: 16-byte aligned for every lane
+  const int c8 = (lane & 7) * 8, rsub = lane >> 3;             // epilogue: 8 channels per lane, 8 rows per pass
+  for (int s = s0; s < s1; ++s) {
+    const int cur = (s - s0) & 1;
+    const u16* X = Xh + cur * FIRR_SPAN;
+    const int g = s * FIRR_WAVES + wave;                       // global wave-tile: samples [256 g, 256 g + 256) before the shift
+    const int m0 = g * 256;
+    if (m0 < L) {                                              // wave-uniform; a tile past L has no row to store and sums to zero
+      f32x16 acc[2];
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+#pragma unroll
+      for (int k0 = 0; k0 < FIR_KP; k0 += 16) {
+        const u32x4 ah = *reinterpret_cast<const u32x4*>(X + xoff + k0);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[j] = T::mfma(ah, wt[j][k0 / 16], acc[j]);
+      }
+
+      // ---- epilogue of sinc_fir16_kernel, unchanged: scale back, per-wave image [32 rows][64 ch], stats, row stores ----
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) im[mfma_row(r, lane) * 68 + j * 32 + l31] = acc[j][r] * (1.0f / 4096.0f);
+      __builtin_amdgcn_s_waitcnt(0xC07F);
+      __builtin_amdgcn_wave_barrier();
+      float gsum = 0.f, gsq = 0.f;
+#pragma unroll
+      for (int r0 = 0; r0 < 32; r0 += 8) {
+        const int row = r0 + rsub;
+        const int m = m0 + o + 8 * row;                        // output sample of this image row
+        const f32x4 x0 = *reinterpret_cast<const f32x4*>(&im[row * 68 + c8]);
+        const f32x4 x1 = *reinterpret_cast<const f32x4*>(&im[row * 68 + c8 + 4]);
+        if (m < L) {
+          const float v[8] = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
+#pragma unroll
+          for (int e = 0; e < 8; ++e) { gsum += v[e]; gsq += v[e] * v[e]; }
+          const long long off = ((long long)b * L + m) * FIR_C + c8;
+          if (out_f32) {
+            float* op = reinterpret_cast<float*>(out) + off;
+            *reinterpret_cast<f32x4*>(op) = x0;
+            *reinterpret_cast<f32x4*>(op + 4) = x1;
+          } else {
+            u32x4 pk;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) pk[e] = pack2<T>(v[2 * e], v[2 * e + 1]);
+            *reinterpret_cast<u32x4*>(reinterpret_cast<u16*>(out) + off) = pk;
+          }
+        }
+      }
+      if (gn_partial) {                                        // GroupNorm(8, 64): one 8-channel chunk = one group
+        for (int sh = 8; sh < 64; sh <<= 1) {
+          gsum += __shfl_xor(gsum, sh, 64);
+          gsq += __shfl_xor(gsq, sh, 64);
+        }
+        if (lane < 8) {
+          const long long tile = (long long)(g >> 3) * 64 + o * 8 + (g & 7);
+          const long long slot = (((long long)b * tiles_per_batch + tile) * 8 + lane) * 2;
+          gn_partial[slot] = gsum;
+          gn_partial[slot + 1] = gsq;
+        }
+      }
+    }
+    if (s + 1 < s1) {
+      write_span(Xh + (cur ^ 1) * FIRR_SPAN);                  // its last readers passed the barrier that ended span s - 1
+      if (s + 2 < s1) load_span((s + 2) * FIRR_OUT);           // lands under the MFMAs of span s + 1
+    }
+    __syncthreads();                                           // span s + 1 is complete; every reader of span s is done
+  }
+}
+
 // wave [B, L] fp32, filt [64, K] fp32 (sfm_sinc_filters), wsh: workspace of SFM_SINC_FIR16_WS_WORDS u16,
 // out [B, L, 64] channels-last (16-bit or fp32), gn_partial [B][P][8][2] with P = sfm_sinc_fir16_tiles(L).
 extern "C" int sfm_sinc_fir16_tiles(int L) {
@@ -186,12 +338,34 @@ static int sinc_fir16_go(const float* wave, const float* filt, void* wsh, void* 
   return SFM_OK;
 }
 
+// Spans per workgroup of the resident kernel: the whole utterance when 8 x B workgroups already give every CU its two several
+// times over, else segments of at least 16 spans (16 wave-tiles per wave: the 35 KB of taps a wave loads stay small against
+// the 512 KB it writes).  The result does not depend on the choice.
+static int sinc_fir16_resident_spans(int B, int spans) {
+  const int want = (4 * 2 * 256 + 8 * B - 1) / (8 * B);        // segments per (utterance, shift) for ~4 workgroups per slot
+  const int nseg = std::max(1, std::min(want, spans / 16));
+  return (spans + nseg - 1) / nseg;
+}
+
+template <class T>
+static int sinc_fir16_resident_go(const float* wave, const float* filt, void* wsh, void* out, float* gn_partial, int B, int L, int K,
+                                  int out_f32, int tpb, hipStream_t st) {
+  const int spans = (L + FIRR_OUT - 1) / FIRR_OUT;
+  const int spw = sinc_fir16_resident_spans(B, spans);
+  SFM_LAUNCH((sinc_fir16_prep_kernel<T>), dim3(8, FIR_C), dim3(256), 0, st, filt, (u16*)wsh, K);
+  SFM_LAUNCH_LDS((sinc_fir16_resident_kernel<T>), dim3(8, (spans + spw - 1) / spw, B), dim3(FIRR_WAVES * 64), FIRR_LDS, st, wave,
+                 (const u16*)wsh, out, gn_partial, L, K / 2, out_f32, tpb, spw);
+  return SFM_OK;
+}
+
 // passes: 3 = split operands (hi x hi + hi x lo + lo x hi, fp32-class accuracy), 1 = hi x hi only (one rounding of the waveform
-// and the taps to the operand format), 0 = auto: 1 for fp16 operands with a 16-bit result, 3 otherwise
+// and the taps to the operand format; the resident-tap kernel), 0 = auto: 1 for fp16 operands with a 16-bit result, 3 otherwise,
+// SFM_SINC_FIR16_STREAM1 = what 1 computes, bit for bit, by the streaming kernel (taps in LDS): the reference and A/B partner
 extern "C" int sfm_sinc_fir16_ex(const float* wave, const float* filt, void* wsh, void* out, float* gn_partial, int B, int L, int C,
                                  int K, int out_f32, int dtype, int passes, void* stream) {
   if (!wave || !filt || !wsh || !out) return SFM_ERR_ARG;
-  if (C != FIR_C || K < 1 || K + 7 > FIR_KP || (K & 1) == 0 || B <= 0 || L <= 0 || (passes != 0 && passes != 1 && passes != 3))
+  if (C != FIR_C || K < 1 || K + 7 > FIR_KP || (K & 1) == 0 || B <= 0 || L <= 0 ||
+      (passes != 0 && passes != 1 && passes != 3 && passes != SFM_SINC_FIR16_STREAM1))
     return SFM_ERR_SHAPE;
   hipStream_t st = (hipStream_t)stream;
   const int chunk = FIR_NSUB * FIR_SUB;
@@ -200,10 +374,13 @@ extern "C" int sfm_sinc_fir16_ex(const float* wave, const float* filt, void* wsh
   const int tpb = nchunks * FIR_NSUB * 8 * FIR_WAVES;
   dim3 grid(8, nchunks, B);
   if (passes == 0) passes = (dtype == SFM_DT_F16 && out_f32 == 0) ? 1 : 3;
+  if (passes == 1)
+    return dtype == SFM_DT_F16 ? sinc_fir16_resident_go<F16>(wave, filt, wsh, out, gn_partial, B, L, K, out_f32, tpb, st)
+                               : sinc_fir16_resident_go<BF16>(wave, filt, wsh, out, gn_partial, B, L, K, out_f32, tpb, st);
   if (dtype == SFM_DT_F16)
-    return passes == 1 ? sinc_fir16_go<F16, 1>(wave, filt, wsh, out, gn_partial, L, K, out_f32, grid, lds, tpb, st)
+    return passes != 3 ? sinc_fir16_go<F16, 1>(wave, filt, wsh, out, gn_partial, L, K, out_f32, grid, lds, tpb, st)
                        : sinc_fir16_go<F16, 3>(wave, filt, wsh, out, gn_partial, L, K, out_f32, grid, lds, tpb, st);
-  return passes == 1 ? sinc_fir16_go<BF16, 1>(wave, filt, wsh, out, gn_partial, L, K, out_f32, grid, lds, tpb, st)
+  return passes != 3 ? sinc_fir16_go<BF16, 1>(wave, filt, wsh, out, gn_partial, L, K, out_f32, grid, lds, tpb, st)
                      : sinc_fir16_go<BF16, 3>(wave, filt, wsh, out, gn_partial, L, K, out_f32, grid, lds, tpb, st);
 }
 

@@ -42,6 +42,7 @@ _SWITCHES = {
     # read by the library itself (csrc/lstm.hip), never by the package: listed so that it is reported
     "lstm_bwd_lpu": ["SFM_LSTM_BWD_LPU", 4, 4],
     "gammatone_fused": [None, True, True],                  # set_gammatone_fused: hop-block sums inside the FIR kernel
+    "sinc_fir_resident": [None, True, True],                # set_sinc_fir_resident: one-pass sinc FIR with the taps in registers
 }
 for _sw in _SWITCHES.values():
     if _sw[0] is not None and _sw[0] in _os.environ:
@@ -1020,6 +1021,12 @@ def ffn_fused_ln(x32, lnw, lnb, w1_16, b1, w2_16, b2, ln2w, ln2b, ln_f32, want_y
     return y, ln
 
 
+def set_sinc_fir_resident(flag):
+    """True (default): the one-pass sinc FIR keeps a shift's taps in registers (sinc_fir16_resident_kernel).  False: the
+    streaming one-pass kernel with the taps in LDS computes it - the same out and gn_partial bit for bit (A/B, reference)."""
+    _SWITCHES["sinc_fir_resident"][2] = bool(flag)
+
+
 def sinc_fir16(wave, filt, out, B, L, C, K, want_stats=True, passes=0):
     """SincConv1d FIR on 16-bit operands -> out [B, L, C] channels-last (+ GroupNorm partials).  passes: 3 = split operands
     (fp32-class accuracy), 1 = operands rounded once, 0 = auto (1 for fp16 operands with a 16-bit result, else 3)."""
@@ -1029,6 +1036,8 @@ def sinc_fir16(wave, filt, out, B, L, C, K, want_stats=True, passes=0):
     P = Lb.sfm_sinc_fir16_tiles(L)
     part = torch.zeros(B, P, 8, 2, device=dev, dtype=torch.float32) if want_stats else None
     out_f32 = 1 if out.dtype == torch.float32 else 0
+    if not switch("sinc_fir_resident") and (passes == 1 or (passes == 0 and _dt() == _K["DT_F16"] and not out_f32)):
+        passes = _K["SINC_FIR16_STREAM1"]               # wherever one pass is asked for or chosen (the launcher's own auto rule)
     flops, nbytes = 2.0 * B * L * C * K, B * L * 4 + B * L * C * (4 if out_f32 else 2)
     _call("sinc_fir16", Lb.sfm_sinc_fir16_ex, (_p(wave), _p(filt), _p(wsh), _p(out), _p(part), B, L, C, K, out_f32, _dt(), int(passes),
                                                _stream()), flops, nbytes)
