@@ -573,6 +573,53 @@ int sfm_headpool_frames_per_tile(int Tin, int Tout);
 int sfm_headpool(const void* xd, const void* W, const float* bias, void* pooled, float* gn_partial, int B, int Tin, int Tout, int NW,
                  int lda, int ldp, int gcols, int dtype, void* stream);
 
+/* ---- The ragged front end: PerceptionAgent, pooling and CPEA on a zero-padded batch, one row per utterance,
+   every buffer laid out for the LONGEST row, the valid length of each row in an int32 device table.  Each entry point is its
+   dense one with a length per row.  Common contract: nothing beyond a row's length is READ (it is the dense kernel's own zero
+   edge); what is WRITTEN for row b is, bit for bit, what the dense entry point writes for that utterance alone (B = 1); what
+   lies beyond a row's length is either left untouched or written as ZEROS, as stated per entry point.  Tables are trusted to be
+   consistent (the host builds them with the dense path's integer formulas); lengths are clamped to the buffers. ----
+   sfm_sinc_fir16_varlen: the one-pass resident-tap kernel of sfm_sinc_fir16_ex.  wave [B, Lrow] fp32, lengths[b] <= Lrow valid
+   samples; out [B, Lrow, 64]: rows < lengths[b] written, the others untouched; gn_partial [B][sfm_sinc_fir16_tiles(Lrow)][8][2]
+   ZERO-FILLED by the caller: the slots of the tiles past lengths[b] stay zero, the others are those of the row alone (same slot
+   indices).  passes: 1, or 0 where the auto rule picks 1 (fp16 operands, 16-bit result); else SFM_ERR_SHAPE. */
+int sfm_sinc_fir16_varlen(const float* wave, const int* lengths, const float* filt, void* wsh, void* out, float* gn_partial, int B,
+                          int Lrow, int C, int K, int out_f32, int dtype, int passes, void* stream);
+/* sfm_conv16p with lin_tab[b] <= Lin input rows and lout_tab[b] = (lin_tab[b] + 2 pad - ksize) / stride + 1 output rows of
+   utterance b.  x1, x2 [B, Lin, Cin]: rows >= lin_tab[b] never read.  out (out_s) [B, Lout, N]: rows < lout_tab[b] written, the
+   others untouched.  gn_partial (_s) [B][2 ceil(Lout / 128)][N / gn_group][2] ZERO-FILLED by the caller: a workgroup whose tile
+   starts at or past lout_tab[b] leaves before it stages anything.  Shapes as sfm_conv16p, skip and two-input forms included;
+   fp16 operands only (SFM_DT_BF16: SFM_ERR_SHAPE). */
+int sfm_conv16p_varlen(const void* x1, const float* sc1, const float* sh1, const void* x2, const float* sc2, const float* sh2,
+                       const void* W, const float* bias, void* out, float* gn_partial, const void* Ws, const float* bias_s,
+                       void* out_s, float* gn_partial_s, const int* lin_tab, const int* lout_tab, int B, int Lin, int Cin, int N,
+                       int ksize, int stride, int pad, int out_f32, int gn_group, int dtype, void* stream);
+/* sfm_gn_finalize with rows_tab[b] rows and p_tab[b] <= Pmax partial slots of utterance b: partial [B, Pmax, G, 2], of which the
+   first p_tab[b] slots of row b are folded, in sfm_gn_finalize's order; the others are never read.  scale, shift [B, C]: all written. */
+int sfm_gn_finalize_varlen(const float* partial, const float* w, const float* b, float* scale, float* shift, const int* rows_tab,
+                           const int* p_tab, int B, int Pmax, int G, int C, float eps, void* stream);
+/* sfm_gn_apply(act = 1, one input) on 16-bit rows with a 16-bit result: x1, out [B, L, C] in `dtype`, C a power of two in
+   [64, 2048].  Rows < rows_tab[b]: GELU(x1 * sc1[b] + sh1[b]); rows >= rows_tab[b]: never read, written as ZEROS (the zero edge of
+   the k 3 uncertainty conv that sfm_gemm16 then runs on out). */
+int sfm_gn_apply_varlen(const void* x1, const float* sc1, const float* sh1, void* out, const int* rows_tab, int B, int L, int C,
+                        int dtype, void* stream);
+/* sfm_headpool with tab int32 [B][4] = (Tin_b, Tout_b, sfm_headpool_frames_per_tile(Tin_b, Tout_b), ceil(Tout_b / that)):
+   xd [B, TinS, lda]: rows >= Tin_b never read; pooled [B, ToutS, ldp]: rows < Tout_b as sfm_headpool, rows >= Tout_b ZEROS (NW
+   columns); gn_partial [B, PS, NW / gcols, 2] ZERO-FILLED by the caller: a tile at or past P_b leaves. */
+int sfm_headpool_varlen(const void* xd, const void* W, const float* bias, void* pooled, float* gn_partial, const int* tab, int B,
+                        int TinS, int ToutS, int PS, int NW, int lda, int ldp, int gcols, int dtype, void* stream);
+/* sfm_bilstm_layer_rows16 with ttab[b] <= T steps of chain b: the forward chain walks 0 .. ttab[b] - 1, the reverse one starts at
+   ttab[b] - 1.  xg [B, T, 2, 4H]: rows >= ttab[b] never read; out16 [B * T, ld16]: rows < ttab[b] as the dense kernel gives for
+   the chain alone, rows >= ttab[b] ZEROS (2H columns).  A finished chain idles while the others of its workgroup go on.  H 128
+   with w16 != 0 only (else SFM_ERR_SHAPE). */
+int sfm_bilstm_layer_rows16_varlen(const float* xg, const float* whh, void* out16, long long ld16, const int* ttab, int B, int T,
+                                   int H, int w16, int dtype, void* stream);
+/* The hand-over to the packed back half, on 32-bit words: src [B, src_rows, ld_src] -> dst [sum_b rows_tab[b], ld_dst]; the first
+   `width` words of row r < rows_tab[b] of utterance b go to row dst_off[b] + r (dst_off = exclusive prefix sums of rows_tab).
+   Rows >= rows_tab[b] never read; every word of dst's `width` columns written. */
+int sfm_rows_gather32(const void* src, void* dst, const int* rows_tab, const int* dst_off, int B, int src_rows, int width,
+                      long long ld_src, long long ld_dst, void* stream);
+
 /* one direction-pair of an nn.LSTM layer (agents/cpea.py:43-50,99), see lstm.hip */
 int sfm_bilstm_layer(const float* xg, const float* whh, float* out, int B, int T, int H, int dtype, void* stream);
 /* inference only: w16 != 0 runs the recurrent product W_hh h on fp16 operands (weights and h rounded once, fp32 accumulation, gates /

@@ -24,7 +24,16 @@ class CorrelationPhaseEstimationAgent(HipModule):
         self.phi1_head = nn.Sequential(nn.Linear(width, self.output_channels), nn.Tanh())
         self.phi2_head = nn.Sequential(nn.Linear(width, self.output_channels), nn.Tanh())
 
-    def forward(self, z_t):
+    def forward(self, z_t, lengths=None):
+        """lengths: the frames of every utterance of a zero-padded batch (a sequence of B ints; eval() only): both chains of
+        utterance b run over its own frames, the reverse one from its last; the rows beyond them hold filler."""
+        if lengths is not None:
+            if self.training or self._wants_autograd(z_t):
+                raise RuntimeError("CorrelationPhaseEstimationAgent.forward(lengths=...) is an inference path: call eval() and "
+                                   "pass a latent that does not require grad")
+            if self.hidden_size != 128 or not ops.lstm_w16():
+                raise NotImplementedError("CorrelationPhaseEstimationAgent.forward(lengths=...): the ragged BiLSTM is built for "
+                                          "hidden_size 128 with fp16 recurrent operands (lstm_w16)")
         self._require_device(z_t)
         if self.training or self._wants_autograd(z_t):
             from .. import train                   # train() (or eval() under autograd): BPTT on the HIP kernels
@@ -42,7 +51,7 @@ class CorrelationPhaseEstimationAgent(HipModule):
             z16 = torch.empty(B * T, D, device=z.device, dtype=dt)
             with ops.stage("front"):
                 ops.convert_rows(z.contiguous(), z16, B * T, D, D, D, D)
-        out = Fn.cpea_forward(z16, pk, B, T).reshape(B, T, -1)
+        out = Fn.cpea_forward(z16, pk, B, T, lengths=lengths).reshape(B, T, -1)
         oc = self.output_channels
         return {"rho_s": out[..., :oc], "rho_n": out[..., oc:2 * oc], "phi1": out[..., 2 * oc:3 * oc],
                 "phi2": out[..., 3 * oc:4 * oc]}

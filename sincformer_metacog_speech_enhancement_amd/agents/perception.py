@@ -103,12 +103,20 @@ class PerceptionAgent(HipModule):
                 if m.bias is not None:
                     nn.init.zeros_(m.bias)
 
-    def forward_channels_last(self, waveform):
-        """Internal layout: zcat [B, T_pa, 2D] fp32 (z_real | z_imag), sigma [B, T_pa]."""
+    def forward_channels_last(self, waveform, lengths=None):
+        """Internal layout: zcat [B, T_pa, 2D] fp32 (z_real | z_imag), sigma [B, T_pa].
+        lengths: the valid samples of every row of a zero-padded batch (eval() only) -> the ragged front end's product
+        (functional.perception_forward_ragged): (raw latent heads pooled to each utterance's STFT frames [B, Tmax, 2D] 16-bit,
+        GroupNorm scale, shift [B, 2D]), sigma [B, Tpa_max]; what follows a row's length is never read."""
         if waveform.dim() == 3:
             waveform = waveform.squeeze(1)
+        if lengths is not None and (self.training or self._wants_autograd(waveform)):
+            raise RuntimeError("PerceptionAgent.forward_channels_last(lengths=...) is an inference path: call eval() and pass a "
+                               "waveform that does not require grad")
         self._require_device(waveform)
         pk = self._packed(lambda sd: Fn.pack_perception(sd, self.sample_rate))
+        if lengths is not None:
+            return Fn.perception_forward(waveform.float(), pk, latents=False, lengths=lengths)
         return Fn.perception_forward(waveform.float(), pk)
 
     def forward(self, waveform):

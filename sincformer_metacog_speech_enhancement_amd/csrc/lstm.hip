@@ -221,113 +221,12 @@ constexpr int LSTM_MFMA_CHAINS = 4;
 // OUT: the format of `out` rows (row stride ldo elements): LSTM_OUT_F32, or SFM_DT_F16 / SFM_DT_BF16 = the rows the next GEMM
 // reads, rounded from the fp32 h exactly as sfm_convert_rows rounds them
 constexpr int LSTM_OUT_F32 = -1;
-template <int OUT>
-__global__ __launch_bounds__(512) void bilstm_layer16_mfma_kernel(const float* __restrict__ xg, const float* __restrict__ whh,
-                                                                  void* __restrict__ out, long long ldo, int B, int T) {
-  typedef typename std::conditional<OUT == LSTM_OUT_F32, float, u16>::type out_t;
-  constexpr int H = 128;
-  constexpr int CS = 2 * H + 64;                             // byte stride of a chain's h
-  constexpr int BUF = LSTM_MFMA_CHAINS * CS;                 // bytes of one buffer
-  __shared__ __attribute__((aligned(16))) uint32_t hs[2 * BUF / 4];
-  const int tid = threadIdx.x;
-  const int u = tid >> 2, j = tid & 3;                       // hidden unit (16 per wave); gate row of A = chain column of B and D
-  const int dir = blockIdx.x;
-  const int chain = blockIdx.y * LSTM_MFMA_CHAINS + j;
-  const bool live = chain < B;
-  const int b = live ? chain : B - 1;
-  lstm_h4 w[H / 4];
-  {
-    const float* wr = whh + ((long long)dir * 4 * H + j * H + u) * H;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(wr + 32 * q + 4 * i);
-        w[8 * q + i] = lstm_h4{(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
-      }
-      __builtin_amdgcn_sched_barrier(0);                     // a quarter of the fp32 row in flight at a time
-    }
-  }
-  for (int i = tid; i < 2 * BUF / 4; i += 512) hs[i] = 0u;
-  __syncthreads();
-  float c = 0.f;
-  const int t0 = dir ? (T - 1) : 0, dt = dir ? -1 : 1;
-  const float* xb = xg + (((long long)b * T + t0) * 2 + dir) * (4 * H) + u;      // step s: + s * dt * 8H, gate g: + g * H
-  out_t* ob = reinterpret_cast<out_t*>(out) + ((long long)b * T + t0) * ldo + dir * H + u;
-  const long long xstep = (long long)dt * (8 * H), ostep = (long long)dt * ldo;
-  const uint32_t hbase = (uint32_t)(uintptr_t)(lds_ptr_t)&hs[0];
-  const int grp = (tid >> 4) & 3;                            // 16-lane group of the wave
-  const uint32_t hread = hbase + j * CS + grp * 16;           // this column's chain, this group's 8 halves of every 32
-  const uint32_t hslot = hbase + j * CS + u * 2;              // where this lane publishes its h
-  // xg runs PF steps ahead of its use (a step is shorter than an HBM miss): ring slot s % PF.  Every step issues its four loads -
-  // past the end it re-reads step T - 1 - so that the wait in front of a use can be a counted one: the main loop below has
-  // no branch that would change how many loads follow the one waited for.
-  constexpr int PF = 4;
-  f32x4 xr[PF];
-  auto fetch = [&](f32x4& x, int s) {
-    const float* xs = xb + (s < T ? s : T - 1) * xstep;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) x[g] = xs[g * H];
-  };
-#pragma unroll
-  for (int i = 0; i < PF; ++i) fetch(xr[i], i);
-  // one time step; `par` = s & 1 is the buffer read, the other one is written
-  auto step = [&](f32x4& x, int s, int par) {
-    f32x4 a0 = x, a1 = {0.f, 0.f, 0.f, 0.f}, a2 = a1, a3 = a1;
-    fetch(x, s + PF);
-    const uint32_t hc = hread + (uint32_t)(par * BUF);
-    u32x4 hv[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(hv[q]) : "v"(hc), "n"(q * 64) : "memory");
-    // read q (k = 32q .. 32q + 31 over the four groups) passes through its counted wait, then feeds two MFMAs of each
-    // accumulator in k order: BLGP 4 + g hands group g's B operand to all four groups.  The scheduling barrier keeps the next
-    // wait from rising above these MFMAs.
-#define LSTM_MFMA_PAIR(q, g, acc0, acc1)                                                                                         \
-    acc0 = __builtin_amdgcn_mfma_f32_4x4x4f16(w[8 * q + 2 * g], __builtin_shufflevector(p, p, 0, 1, 2, 3), acc0, 0, 0, 4 + g);   \
-    acc1 = __builtin_amdgcn_mfma_f32_4x4x4f16(w[8 * q + 2 * g + 1], __builtin_shufflevector(p, p, 4, 5, 6, 7), acc1, 0, 0, 4 + g);
-#define LSTM_MFMA_GROUP(q, left)                                                                                                 \
-    {                                                                                                                            \
-      asm volatile("s_waitcnt lgkmcnt(" #left ")" : "+v"(hv[q])::"memory");                                                      \
-      const f16x8_t p = __builtin_bit_cast(f16x8_t, hv[q]);                                                                      \
-      LSTM_MFMA_PAIR(q, 0, a0, a1)                                                                                               \
-      LSTM_MFMA_PAIR(q, 1, a2, a3)                                                                                               \
-      LSTM_MFMA_PAIR(q, 2, a0, a1)                                                                                               \
-      LSTM_MFMA_PAIR(q, 3, a2, a3)                                                                                               \
-    }                                                                                                                            \
-    __builtin_amdgcn_sched_barrier(0);
-    LSTM_MFMA_GROUP(0, 3)
-    LSTM_MFMA_GROUP(1, 2)
-    LSTM_MFMA_GROUP(2, 1)
-    LSTM_MFMA_GROUP(3, 0)
-#undef LSTM_MFMA_GROUP
-#undef LSTM_MFMA_PAIR
-    const f32x4 pre = (a0 + a1) + (a2 + a3);
-    const float ig = fast_sigmoid(pre[0]), fg = fast_sigmoid(pre[1]);
-    const float cg = 2.0f * fast_sigmoid(2.0f * pre[2]) - 1.0f, og = fast_sigmoid(pre[3]);
-    c = fg * c + ig * cg;
-    float h = og * (2.0f * fast_sigmoid(2.0f * c) - 1.0f);
-    asm volatile("" : "+v"(h));                                // the fp32 h is formed first: LDS gets (_Float16) of the value stored
-    const uint32_t hb = (uint32_t)__builtin_bit_cast(unsigned short, (_Float16)h);
-    asm volatile("ds_write_b16 %0, %1" ::"v"(hslot + (uint32_t)((par ^ 1) * BUF)), "v"(hb) : "memory");
-    if (live) {
-      if constexpr (OUT == LSTM_OUT_F32) ob[s * ostep] = h;
-      else if constexpr (OUT == SFM_DT_F16) ob[s * ostep] = (u16)hb;
-      else ob[s * ostep] = BF16::from_f32(h);
-    }
-    // LDS-only barrier: the xg loads in flight and the store of h are not waited for
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  };
-  int s0 = 0;
-  for (; s0 + PF <= T; s0 += PF) {                             // PF is even: the parity of step s0 + i is that of i
-    step(xr[0], s0, 0);
-    step(xr[1], s0 + 1, 1);
-    step(xr[2], s0 + 2, 0);
-    step(xr[3], s0 + 3, 1);
-  }
-  if (s0 < T) step(xr[0], s0, 0);                              // the T % PF steps left
-  if (s0 + 1 < T) step(xr[1], s0 + 1, 1);
-  if (s0 + 2 < T) step(xr[2], s0 + 2, 0);
-}
+#define LSTM_VARLEN 0
+#include "lstm_mfma_kernel.h"                                // bilstm_layer16_mfma_kernel: the dense form
+#undef LSTM_VARLEN
+#define LSTM_VARLEN 1
+#include "lstm_mfma_kernel.h"                                // bilstm_layer16_mfma_varlen_kernel: a length per chain from a table
+#undef LSTM_VARLEN
 
 // ---------------------------------------------------------------------------
 // BPTT of one BiLSTM layer (training of agents/cpea.py:43-50): same workgroup = chain mapping as the forward.
@@ -484,6 +383,22 @@ extern "C" int sfm_bilstm_layer_rows16(const float* xg, const float* whh, void* 
   const dim3 grid(2, (B + LSTM_MFMA_CHAINS - 1) / LSTM_MFMA_CHAINS);
   if (dtype == SFM_DT_F16) SFM_LAUNCH((bilstm_layer16_mfma_kernel<SFM_DT_F16>), grid, dim3(512), 0, st, xg, whh, out16, ld16, B, T);
   else SFM_LAUNCH((bilstm_layer16_mfma_kernel<SFM_DT_BF16>), grid, dim3(512), 0, st, xg, whh, out16, ld16, B, T);
+  return SFM_OK;
+}
+
+// sfm_bilstm_layer_rows16 on ragged rows: xg [B, T, 2, 4H] and out16 [B * T, ld16] keep the row stride T of the longest chain,
+// chain b has ttab[b] <= T steps (int32 [B], device).  Rows of xg from ttab[b] on are never read; rows of out16 from ttab[b] on
+// are written as zeros (their 2H columns).  A chain's rows are the bits sfm_bilstm_layer_rows16 gives for it alone (B = 1,
+// T = ttab[b]): the columns of the 4x4x4 products are independent.  H 128 with w16 != 0 only (else SFM_ERR_SHAPE).
+extern "C" int sfm_bilstm_layer_rows16_varlen(const float* xg, const float* whh, void* out16, long long ld16, const int* ttab, int B,
+                                              int T, int H, int w16, int dtype, void* stream) {
+  if (!xg || !whh || !out16 || !ttab || (dtype != SFM_DT_F16 && dtype != SFM_DT_BF16)) return SFM_ERR_ARG;
+  if (B <= 0 || T <= 0 || H != 128 || !w16 || ld16 < 2 * H) return SFM_ERR_SHAPE;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(2, (B + LSTM_MFMA_CHAINS - 1) / LSTM_MFMA_CHAINS);
+  if (dtype == SFM_DT_F16)
+    SFM_LAUNCH((bilstm_layer16_mfma_varlen_kernel<SFM_DT_F16>), grid, dim3(512), 0, st, xg, whh, out16, ld16, B, T, ttab);
+  else SFM_LAUNCH((bilstm_layer16_mfma_varlen_kernel<SFM_DT_BF16>), grid, dim3(512), 0, st, xg, whh, out16, ld16, B, T, ttab);
   return SFM_OK;
 }
 

@@ -468,13 +468,14 @@ def pack_complex_conformer(sd, num_blocks, num_heads=4):
             "blocks": [pack_block(sub(sd, "blocks.%d" % i), num_heads, i) for i in range(num_blocks)], "nf2": nf2}
 
 
-def complex_conformer_core(x16, pk, B, T, H, out_dtype=None):
-    """x16: [M, ld>=round32(2*n_freq)] 16-bit operand of input_proj -> output_proj result [M, 2*n_freq]."""
+def complex_conformer_core(x16, pk, B, T, H, out_dtype=None, seg=None):
+    """x16: [M, ld>=round32(2*n_freq)] 16-bit operand of input_proj -> output_proj result [M, 2*n_freq].
+    seg: a PackedSegments - the rows are its utterances back to back (B, T unused), as block_forward takes them."""
     with ops.stage("front"):
         x = ops.linear16(x16, pk["in"], out_dtype=torch.float32)
     skip = x
     for bp in pk["blocks"]:
-        x = block_forward(x, bp, B, T, H)
+        x = block_forward(x, bp, B, T, H, seg=seg)
     with ops.stage("tail"):
         y16 = add_to16(x, skip, x.shape[1])
         return ops.linear16(y16, pk["out"], out_dtype=out_dtype or ops.compute_dtype())
@@ -545,11 +546,18 @@ def _conv_gn(x16, pw, B, Lin, stride, pad, groups, raw_dtype):
     return raw, part, P, Lout
 
 
-def perception_forward(wave, pk, keep_sinc=False, latents=True, pool_to=None):
+def perception_forward(wave, pk, keep_sinc=False, latents=True, pool_to=None, lengths=None):
     """wave [B, L] fp32 -> zcat [B, T_pa, 2D] fp32 (z_real | z_imag, channels-last), sigma [B, T_pa] fp32.
     latents=False: zcat = (raw head outputs [B, T_pa, 2D] 16-bit, scale, shift [B, 2D]) - the caller only pools the latents, and the
     GroupNorm behind the heads is affine per (utterance, channel); with pool_to = T (the STFT frame count) the heads and the pooling
-    are one launch (ops.headpool) and the first element is already the POOLED raw output [B, T, 2D]."""
+    are one launch (ops.headpool) and the first element is already the POOLED raw output [B, T, 2D].
+    lengths: the valid samples of every row of a zero-padded batch (a sequence of ints or a RaggedPlan): the ragged front end
+    (perception_forward_ragged below), which takes latents=False with the pooling fused and ignores pool_to."""
+    if lengths is not None:
+        if latents or keep_sinc:
+            raise NotImplementedError("perception_forward(lengths=...): the ragged front end returns the pooled raw latents "
+                                      "(latents=False); full-rate latents have no ragged form")
+        return perception_forward_ragged(wave, pk, lengths)
     with ops.stage("pa"):
         return _perception_forward(wave, pk, keep_sinc, latents, pool_to)
 
@@ -706,20 +714,31 @@ def _pack_cpea(sd, num_layers):
     return pk
 
 
-def cpea_forward(z16, pk, B, T, out=None):
+def cpea_forward(z16, pk, B, T, out=None, lengths=None):
     """z16: [B*T, ld] 16-bit rows whose first input_dim columns are the latent ->
-    [B*T, 4*oc] (rho_s | rho_n | phi1 | phi2); `out` may be a strided 16-bit/fp32 view."""
+    [B*T, 4*oc] (rho_s | rho_n | phi1 | phi2); `out` may be a strided 16-bit/fp32 view.
+    lengths: the frames of every utterance of a zero-padded batch (a sequence of B ints <= T, or a frame_table): both chains of
+    utterance b run over its own lengths[b] frames (sfm_bilstm_layer_rows16_varlen); the rows beyond them are row-wise filler."""
+    if lengths is not None:
+        if pk["H"] != 128 or not ops.lstm_w16():
+            raise NotImplementedError("cpea_forward(lengths=...): the ragged BiLSTM is built for hidden_size 128 with fp16 "
+                                      "recurrent operands (lstm_w16); got H %d, lstm_w16 %s" % (pk["H"], ops.lstm_w16()))
+        if not isinstance(lengths, FrameTable):
+            lengths = frame_table(lengths, z16.device, T)
     with ops.stage("front"):
-        return _cpea_forward(z16, pk, B, T, out)
+        return _cpea_forward(z16, pk, B, T, out, lengths)
 
 
-def _cpea_forward(z16, pk, B, T, out):
+def _cpea_forward(z16, pk, B, T, out, lengths=None):
     H = pk["H"]
     M = B * T
     dt = ops.compute_dtype()
     x16 = z16
     for lp in pk["layers"]:
         xg = ops.linear16(x16, lp["wih"], out_dtype=torch.float32)                  # [M, 8H] = [B,T,2,4H]
+        if lengths is not None:                                                    # (H 128 on fp16 operands: cpea_forward checked)
+            x16 = ops.bilstm_layer_rows16_varlen(xg, lp["whh"], lengths.dev, B, T, H, lengths.total)
+            continue
         if H == 128 and ops.lstm_w16():                                            # the kernel writes the next GEMM's rows itself
             x16 = ops.bilstm_layer_rows16(xg, lp["whh"], B, T, H)                   # [M, 2H] 16-bit
             continue
@@ -762,16 +781,17 @@ def pack_msa(sd, num_blocks, num_heads=4):
     return pk
 
 
-def msa_logits(fused16, pk, B, T, H):
+def msa_logits(fused16, pk, B, T, H, seg=None):
     """fused16 [M, FUSE_LD] 16-bit (the 8-way concat of agents/msa.py:140, zero padded)
-    -> magnitude / phase logits [M, 129] fp32 each."""
+    -> magnitude / phase logits [M, 129] fp32 each.  seg: a PackedSegments - packed rows (B, T unused); everything but the
+    Conformer blocks is row-wise."""
     D = pk["d_model"]
     with ops.stage("front"):
         h = ops.linear16(fused16, pk["f0"], out_dtype=torch.float32)
         h16 = _ln16(h, pk["f1w"], pk["f1b"], act=1)
         h = ops.linear16(h16, pk["f3"], out_dtype=torch.float32)
         hf16 = _ln16(h, pk["f4w"], pk["f4b"])
-    y16 = complex_conformer_core(hf16, pk["conf"], B, T, H)   # [M, D]: mask_r | mask_i, 16-bit in the tail's format
+    y16 = complex_conformer_core(hf16, pk["conf"], B, T, H, seg=seg)   # [M, D]: mask_r | mask_i, 16-bit in the tail's format
     half = D // 2
     with ops.stage("tail"):
         gr = ops.linear16(y16[:, :half], pk["r0"], epi=ops.EPI_GELU)
@@ -869,6 +889,308 @@ def enhance_path(wave, packs, H=4, use_memory=False, want=("mask", "wave")):
         out["zcat"] = zcat
     if "wave" in want:
         out["enhanced"] = (istft_from_packed_split16 if FUSED_STFT_SPLIT16 else istft_from_packed)(spec, B, T, L)
+    return out
+
+
+# ---------------------------------------------------------------------------
+# The same composition on utterances of different lengths in one pass ("The ragged EnhancementPath")
+#   front end (PerceptionAgent, pooling, CPEA): zero-padded batch, one row per utterance, row stride of the longest, a length
+#     per row from an int32 table - the dense kernels' own tiles, anchored at the row start;
+#   hand-over: one row gather (ops.rows_gather32) of the pooled latents | CPEA columns, BEFORE the fusion linears;
+#   back half (STFT, fusion, ComplexConformer, mask tail, polar mask, iSTFT): packed rows with a PackedSegments.
+# ---------------------------------------------------------------------------
+PA_CONV_CHAIN = ((7, 2, 3), (7, 2, 3), (7, 2, 3), (5, 2, 2))   # (kernel, stride, padding) of the three blocks' strided convs and the
+#                                                                down-sampling conv (agents/perception.py:160-171): the length chain
+RAGGED_MIN_SAMPLES = N_FFT // 2 + 1        # the STFT's reflection needs more than n_fft / 2 samples; every conv has output there
+
+
+def ragged_length_chain(lengths, hop=HOP):
+    """L_b -> the row counts of utterance b at every layer of the path, with the dense path's integer formulas (_convp's Lout,
+    enhance_path's T): {"rows": [L, L1, L2, L3] (input of the sinc layer and output of each residual block), "Tpa": the
+    down-sampling conv's output, "T": the STFT frames}, int64 arrays [B].  Pure host arithmetic."""
+    L = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    rows = [L]
+    for k, s, p in PA_CONV_CHAIN:
+        rows.append((rows[-1] + 2 * p - k) // s + 1)
+    return {"rows": rows[:4], "Tpa": rows[4], "T": 1 + L // hop}
+
+
+class FrameTable:
+    """a length-per-row operand: `dev` int32 [B] on the device, `host` the same as a tuple, `total` their sum (for the costs)"""
+
+    def __init__(self, dev, host):
+        self.dev, self.host, self.total = dev, tuple(int(x) for x in host), int(sum(host))
+
+
+_FRAME_TABLES = {}
+_RAGGED_PLANS = {}
+RAGGED_CACHE = 64                          # lengths tuples kept (plans and frame tables); the oldest goes first
+
+
+def _cache_put(cache, key, value):
+    if len(cache) >= RAGGED_CACHE:
+        cache.pop(next(iter(cache)))
+    cache[key] = value
+    return value
+
+
+def frame_table(counts, device, T=None):
+    """FrameTable of a sequence of row counts, uploaded once per (device, counts) and cached: a repeated set of lengths makes no
+    copy.  T: the row stride they must fit."""
+    host = tuple(int(x) for x in counts)
+    if not host or min(host) < 1 or (T is not None and max(host) > T):
+        raise ValueError("frame_table: %d row counts in [%s, %s], row stride %s" % (len(host), min(host, default=None),
+                                                                                   max(host, default=None), T))
+    key = (str(device), host)
+    t = _FRAME_TABLES.get(key)
+    if t is None:
+        t = _cache_put(_FRAME_TABLES, key, FrameTable(torch.tensor(host, dtype=torch.int32).to(device), host))
+    return t
+
+
+class RaggedPlan:
+    """Host description of one ragged pass over utterances of `lengths` samples: the length chain (ragged_length_chain), the
+    number of GroupNorm partial slots each utterance fills at every layer, the headpool table, the PackedSegments of the back
+    half.  tables(device) uploads all of it in ONE copy and caches it; ragged_plan() caches the plan by its lengths."""
+
+    def __init__(self, lengths):
+        L = [int(x) for x in lengths]
+        if not L:
+            raise ValueError("a ragged pass needs at least one utterance")
+        for i, n in enumerate(L):
+            if n < RAGGED_MIN_SAMPLES:
+                raise ValueError("utterance %d has %d samples: the ragged path needs at least %d (the STFT reflects n_fft / 2 = %d "
+                                 "samples at either end)" % (i, n, RAGGED_MIN_SAMPLES, N_FFT // 2))
+        self.lengths = tuple(L)
+        self.B = len(L)
+        ch = ragged_length_chain(L)
+        self.rows, self.Tpa, self.T = ch["rows"], ch["Tpa"], ch["T"]
+        self.max_rows = [int(r.max()) for r in self.rows]
+        self.Tpa_max, self.T_max = int(self.Tpa.max()), int(self.T.max())
+        self.seg = PackedSegments(self.T, L)
+        lib = ops._lib.load()
+        conv_slots = lambda n: 2 * ((n + 127) // 128)
+        # partial slots per utterance: what the dense launch on that utterance alone fills (sfm_sinc_fir16_tiles, 2 per 128 rows)
+        self.slots = {"sinc": np.asarray([lib.sfm_sinc_fir16_tiles(n) for n in L], dtype=np.int64),
+                      "b0": conv_slots(self.rows[1]), "b1": conv_slots(self.rows[2]), "b2": conv_slots(self.rows[3]),
+                      "down": conv_slots(self.Tpa)}
+        self.headpool = ops.headpool_tab(self.Tpa, self.T)              # int32 [B, 4], or None: pair unsupported / fusion off
+        if self.headpool is not None:
+            self.slots["heads"] = self.headpool[:, 3].astype(np.int64)
+        self.tpa_offsets = np.concatenate([[0], np.cumsum(self.Tpa)])
+        self.sum_Tpa = int(self.tpa_offsets[-1])
+        self._tables = {}
+
+    def tables(self, device):
+        """{"rows": [4 FrameTables], "Tpa", "T": FrameTables, "slots": {layer: int32 [B]}, "headpool": int32 [B, 4] | None,
+        "tpa_off": int32 [B + 1]} on `device`: one upload, cached"""
+        t = self._tables.get(str(device))
+        if t is None:
+            names = sorted(self.slots)
+            parts = list(self.rows) + [self.Tpa, self.T] + [self.slots[k] for k in names]
+            parts += [self.tpa_offsets] + ([self.headpool.reshape(-1)] if self.headpool is not None else [])
+            flat = torch.from_numpy(np.concatenate([np.asarray(p, dtype=np.int32) for p in parts])).to(device)
+            B = self.B
+            cut = lambda i: flat[i * B:(i + 1) * B]
+            t = {"rows": [FrameTable(cut(i), self.rows[i]) for i in range(4)], "Tpa": FrameTable(cut(4), self.Tpa),
+                 "T": FrameTable(cut(5), self.T), "slots": {k: cut(6 + i) for i, k in enumerate(names)}}
+            o = (6 + len(names)) * B
+            t["tpa_off"] = flat[o:o + B + 1]
+            t["headpool"] = flat[o + B + 1:].view(B, 4) if self.headpool is not None else None
+            self._tables[str(device)] = t
+        return t
+
+
+def ragged_plan(lengths):
+    """the RaggedPlan of a lengths sequence, cached by the lengths (a plan passes through)"""
+    if isinstance(lengths, RaggedPlan):
+        return lengths
+    key = tuple(int(x) for x in (lengths.tolist() if hasattr(lengths, "tolist") else lengths))
+    plan = _RAGGED_PLANS.get(key)
+    if plan is None:
+        plan = _cache_put(_RAGGED_PLANS, key, RaggedPlan(key))
+    return plan
+
+
+def _ragged_empty(*shape, device, dtype):
+    """every intermediate buffer of the ragged path is allocated here (the tests fill them with NaN through this name)"""
+    return torch.empty(*shape, device=device, dtype=dtype)
+
+
+def _ragged_refuse_front(pk, wave):
+    """the front end's refusals, before any launch (no device needed)"""
+    if torch.is_grad_enabled() and wave.requires_grad:
+        raise RuntimeError("the ragged path is inference only: the waveform requires grad (training takes rectangular batches)")
+    if not _patch_conv_ok(pk):
+        raise NotImplementedError("the ragged front end needs the fused convs (sfm_conv16p): PATCH_CONV off or layer shapes "
+                                  "outside conv16p_supported")
+    if ops.stage_dtype("pa") is not torch.float16:
+        raise NotImplementedError("the ragged front end is built for fp16 operands (the resident-tap sinc FIR and conv16p's "
+                                  "ragged forms); the 'pa' stage is %s" % ops.stage_dtype("pa"))
+    if not (pk["C0"] == 64 and pk["K"] + 7 <= 272 and SINC_ON_16BIT_MFMA):
+        raise NotImplementedError("the ragged front end needs the 16-bit sinc FIR (64 channels, at most 265 taps)")
+    D = pk["D"]
+    if not (D == 256 and pk["zproj"].Npad == 2 * D and pk["zproj"].ksize == 1):
+        raise NotImplementedError("the ragged front end needs the fused heads + pooling kernel (encoder width 256)")
+
+
+def _convp_ragged(inp, pw, B, Lin, stride, pad, groups, dt, lin, lout, skip_pw=None):
+    """_convp with a length per row: lin / lout = FrameTables of the input / output rows; the partials start from zeros"""
+    dev = inp[0].device
+    k, N = pw.ksize, pw.N
+    Lout = (Lin + 2 * pad - k) // stride + 1
+    P = 2 * ((Lout + 127) // 128)
+    raw = _ragged_empty(B, Lout, N, device=dev, dtype=dt)
+    part = torch.zeros(B, P, groups, 2, device=dev, dtype=torch.float32)
+    raw_s = part_s = None
+    if skip_pw is not None:
+        raw_s = _ragged_empty(B, Lout, N, device=dev, dtype=dt)
+        part_s = torch.zeros(B, P, groups, 2, device=dev, dtype=torch.float32)
+    x2, sc2, sh2 = (inp[3], inp[4], inp[5]) if len(inp) == 6 else (None, None, None)
+    ops.conv16p_varlen(inp[0], inp[1], inp[2], pw, raw, lin.dev, lout.dev, B=B, Lin=Lin, stride=stride, pad=pad, n_out=lout.total,
+                       x2=x2, sc2=sc2, sh2=sh2, gn_partial=part, gn_group=N // groups, skip_pw=skip_pw, out_s=raw_s,
+                       gn_partial_s=part_s)
+    return raw, part, P, Lout, raw_s, part_s
+
+
+def perception_forward_ragged(wave, pk, lengths):
+    """wave [B, Lmax] fp32, row b holding lengths[b] valid samples (what follows them is never read) ->
+    (pooled raw heads [B, Tmax, 2D] 16-bit with zeros from T_b on, scale, shift [B, 2D]), sigma [B, Tpa_max] fp32: per utterance
+    the bits perception_forward(wave[b:b+1, :L_b], latents=False, pool_to=T_b) gives.  sigma's columns from Tpa_b on are filler."""
+    _ragged_refuse_front(pk, wave)
+    plan = ragged_plan(lengths)
+    if plan.headpool is None:
+        raise NotImplementedError("the ragged front end needs the fused heads + pooling kernel (sfm_headpool) for every utterance")
+    if wave.dim() != 2 or wave.shape[0] != plan.B or wave.shape[1] < plan.max_rows[0]:
+        raise ValueError("perception_forward_ragged: wave %s for %d utterances of up to %d samples" % (tuple(wave.shape), plan.B,
+                                                                                                      plan.max_rows[0]))
+    with ops.stage("pa"):
+        return _perception_forward_ragged(wave.contiguous(), pk, plan)
+
+
+def _perception_forward_ragged(wave, pk, plan):
+    dt = ops.compute_dtype()
+    B, Lrow = wave.shape
+    C0, K, D = pk["C0"], pk["K"], pk["D"]
+    dev = wave.device
+    tb = plan.tables(dev)
+    rows, slots = tb["rows"], tb["slots"]
+    # the buffers' row counts: the chain of the row stride (>= the longest utterance's, equal unless the caller padded further)
+    ch = ragged_length_chain([Lrow])
+    Ls, Tpa_s, T_s = [int(r[0]) for r in ch["rows"]], int(ch["Tpa"][0]), plan.T_max
+    filt, _ = ops.sinc_filters(pk["low_hz_"], pk["band_hz_"], pk["window"], pk["n_"], C0, K, pk["fs"], 50.0, 50.0, want_filt=True)
+    raw = _ragged_empty(B, Lrow, C0, device=dev, dtype=dt)
+    part, P0 = ops.sinc_fir16_varlen(wave, rows[0].dev, filt, raw, C0, K, rows[0].total)
+    sc, sh = ops.gn_finalize_varlen(part, pk["sn_w"], pk["sn_b"], rows[0].dev, slots["sinc"], B, P0, 8, C0)
+    inp = (raw, sc, sh)
+    for i, bp in enumerate(pk["blocks"]):
+        G, C = bp["groups"], bp["cout"]
+        lin, lout, sl = rows[i], rows[i + 1], slots["b%d" % i]
+        if C == 128:
+            r1, p1, P1, L1, rs, ps = _convp_ragged(inp, bp["c1"], B, Ls[i], 2, 3, G, dt, lin, lout, skip_pw=bp["cs"])
+        else:
+            r1, p1, P1, L1, _, _ = _convp_ragged(inp, bp["c1"], B, Ls[i], 2, 3, G, dt, lin, lout)
+            rs, ps, _, _, _, _ = _convp_ragged(inp, bp["cs"], B, Ls[i], 2, 0, G, dt, lin, lout)
+        s1, h1 = ops.gn_finalize_varlen(p1, bp["g1w"], bp["g1b"], lout.dev, sl, B, P1, G, C)
+        ss, hs = ops.gn_finalize_varlen(ps, bp["gsw"], bp["gsb"], lout.dev, sl, B, P1, G, C)
+        r2, p2, P2, _, _, _ = _convp_ragged((r1, s1, h1), bp["c2"], B, L1, 1, 1, G, dt, lout, lout)
+        s2, h2 = ops.gn_finalize_varlen(p2, bp["g2w"], bp["g2b"], lout.dev, sl, B, P2, G, C)
+        inp = (r2, s2, h2, rs, ss, hs)
+    tpa = tb["Tpa"]
+    rd, pd, Pd, Tpa_rows, _, _ = _convp_ragged(inp, pk["down"], B, Ls[3], 2, 2, 16, dt, rows[3], tpa)
+    sd_, hd_ = ops.gn_finalize_varlen(pd, pk["dn_w"], pk["dn_b"], tpa.dev, slots["down"], B, Pd, 16, D)
+    # GroupNorm + GELU of the down-sampled rows, zeros from Tpa_b on: a zero row is the k 3 uncertainty conv's own zero edge
+    xd = _ragged_empty(B, Tpa_rows, D, device=dev, dtype=dt)
+    ops.gn_apply_varlen(rd, sd_, hd_, xd, tpa.dev, B, Tpa_rows, D, tpa.total)
+    PS = int(plan.slots["heads"].max())
+    rz = _ragged_empty(B, T_s, 2 * D, device=dev, dtype=dt)
+    pz = torch.zeros(B, PS, 32, 2, device=dev, dtype=torch.float32)
+    ops.headpool_varlen(xd, pk["zproj"], rz, pz, tb["headpool"], B, Tpa_rows, T_s, PS, tpa.total, tb["T"].total, gcols=(2 * D) // 32)
+    sz, hz = ops.gn_finalize_varlen(pz, pk["z_w"], pk["z_b"], tpa.dev, slots["heads"], B, PS, 32, 2 * D)
+    # uncertainty head: the dense implicit GEMM per row of the batch; beyond Tpa_b it reads the zeros above and writes filler
+    u = _ragged_empty(B, Tpa_rows, pk["u0"].N, device=dev, dtype=dt)
+    ops.gemm16(xd, pk["u0"], u, B=B, Lout=Tpa_rows, Lin=Tpa_rows, a_batch_stride=Tpa_rows * D, ldo=pk["u0"].N,
+               o_batch_stride=Tpa_rows * pk["u0"].N, stride=1, pad=1, epi=ops.EPI_GELU)
+    sigma = _ragged_empty(B * Tpa_rows, 1, device=dev, dtype=torch.float32)
+    ops.linear16(u.reshape(B * Tpa_rows, -1), pk["u2"], epi=ops.EPI_SIGMA, out=sigma)
+    return (rz, sz, hz), sigma.reshape(B, Tpa_rows)
+
+
+def istft_from_packed_varlen(spec, seg, n_fft=N_FFT, hop=HOP, win=WIN, split16=False):
+    """spec [sum_T, ld >= 2F] fp32 rows (real | imag | zero pad) of the utterances of `seg` -> packed samples [sum_L].  The
+    irfft x window product is row-wise (the dense path's launch: split16 as istft_from_packed_split16, else the exact fp32
+    one); the overlap-add runs per utterance."""
+    F = n_fft // 2 + 1
+    c = _stft_consts(n_fft, win, spec.device)
+    tb = seg.tables(spec.device)
+    ld, M = spec.stride(0), spec.shape[0]
+    frames = torch.empty(M, win, device=spec.device, dtype=torch.float32)
+    if split16:
+        if "inv16" not in c:
+            c["inv16"] = ops.pack_split16_matrix(c["inv"][:2 * F, :win].contiguous())
+        ops.framed_gemm_split16(spec, c["inv16"], frames, B=1, M=M, Ls=M * ld, sig_batch_stride=0, hop=ld, padl=0,
+                                o_batch_stride=0, ldm=win, mode=0)
+    else:
+        ops.framed_gemm(spec, c["inv"], frames, B=1, M=M, Ls=M * ld, sig_batch_stride=0, hop=ld, padl=0, K=2 * F, N=win,
+                        o_batch_stride=0, ldm=win, ldn=1, mode=0)
+    out = torch.empty(seg.sum_L, device=spec.device, dtype=torch.float32)
+    ops.istft_ola_varlen(frames, c["win2"], out, tb["frame_off"], tb["samp_off"], seg.B, n_fft, hop, win, win)
+    return out
+
+
+def enhance_path_ragged(wave, lengths, packs, H=4, use_memory=False, want=("mask", "wave")):
+    """enhance_path on utterances of different lengths in one pass.  wave [B, Lmax] fp32: row b holds lengths[b] samples, what
+    follows them is never read.  Returns PACKED results, every utterance as if it were alone: mask_real / mask_imag
+    [sum_T, 129], sigma [sum_Tpa], noisy_real / noisy_imag, spec, enhanced [sum_L] (with "wave" in want), seg (the
+    PackedSegments: frame_offsets, sample_offsets) and plan (tpa_offsets).  Inference only; at least RAGGED_MIN_SAMPLES
+    samples per utterance."""
+    if use_memory or "memory" in packs:
+        raise NotImplementedError("the ragged path has no episodic memory: its key is a mean over frames, which would need a "
+                                  "ragged form of its own")
+    if "latents" in want:
+        raise NotImplementedError("the ragged path does not return full-rate latents (want contains 'latents')")
+    pa = packs["pa"]
+    _ragged_refuse_front(pa, wave)
+    if packs["cpea"]["H"] != 128 or not ops.lstm_w16():
+        raise NotImplementedError("the ragged CPEA is built for hidden_size 128 with fp16 recurrent operands (lstm_w16)")
+    plan = ragged_plan(lengths)
+    seg = plan.seg
+    dt = ops.stage_dtype("front")
+    wave = wave.contiguous()
+    B, Lrow = wave.shape
+    dev = wave.device
+    D = pa["D"]
+    (rz, zsc, zsh), sigma_rows = perception_forward(wave, pa, latents=False, lengths=plan)
+    tb, st = plan.tables(dev), seg.tables(dev)
+    T_s, Tpa_s = rz.shape[1], sigma_rows.shape[1]
+    oc4 = 4 * packs["cpea"]["oc"]
+    wf = 2 * D + oc4                                                    # pooled z_real | z_imag | rho_s | rho_n | phi1 | phi2
+    front = _ragged_empty(B * T_s, wf, device=dev, dtype=dt)
+    with ops.stage("front"):
+        ops.pool_time(rz, front, None, B, T_s, T_s, 2 * D, 2 * D, wf, scale=zsc, shift=zsh)       # G1: row-wise (Tin == Tout)
+    cpea_forward(front, packs["cpea"], B, T_s, out=front[:, 2 * D:], lengths=tb["T"])
+    # hand-over: the valid rows of the front end's columns -> packed rows of the fusion operand; the spectrum columns are
+    # written there directly from the packed STFT
+    fused = _ragged_empty(seg.sum_T, FUSE_LD, device=dev, dtype=dt)
+    ops.rows_gather32(front, fused, tb["T"].dev, st["frame_off"], B, T_s, wf, seg.sum_T)
+    wpk = torch.empty(seg.sum_L, 1, device=dev, dtype=torch.float32)
+    ops.rows_gather32(wave.view(-1, 1), wpk, tb["rows"][0].dev, st["samp_off"], B, Lrow, 1, seg.sum_L)
+    nr, ni = stft_packed(wpk.view(-1), seg, split16=FUSED_STFT_SPLIT16)
+    M = seg.sum_T
+    with ops.stage("front"):
+        ops.stft_lognorm_pack(nr, ni, fused[:, wf:], M, N_FREQ, FUSE_LD - wf - 2 * N_FREQ, FUSE_LD)
+    lm, lp = msa_logits(fused, packs["msa"], None, None, H, seg=seg)
+    mr = torch.empty(M, N_FREQ, device=dev, dtype=torch.float32)
+    mi = torch.empty(M, N_FREQ, device=dev, dtype=torch.float32)
+    ld = ops.round_up(2 * N_FREQ, 8)
+    spec = torch.zeros(M, ld, device=dev, dtype=torch.float32)
+    ops.polar_mask(lm, lp, 1, M, N_FREQ, PHASE_SCALE_MSA, lm.stride(0), nr=nr, ni=ni, mr=mr, mi=mi, er=spec, ei=spec[:, N_FREQ:],
+                   ld_enh=ld)
+    sigma = torch.empty(plan.sum_Tpa, 1, device=dev, dtype=torch.float32)
+    ops.rows_gather32(sigma_rows.reshape(-1, 1), sigma, tb["Tpa"].dev, tb["tpa_off"], B, Tpa_s, 1, plan.sum_Tpa)
+    out = dict(mask_real=mr, mask_imag=mi, sigma=sigma.view(-1), noisy_real=nr, noisy_imag=ni, spec=spec, seg=seg, plan=plan)
+    if "wave" in want:
+        out["enhanced"] = istft_from_packed_varlen(spec, seg, split16=FUSED_STFT_SPLIT16)
     return out
 
 

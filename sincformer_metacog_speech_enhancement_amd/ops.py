@@ -977,6 +977,149 @@ def istft_ola_varlen(frames, win2, out, frame_off, samp_off, B, n_fft, hop, win,
     return out
 
 
+# ---------------------------------------------------------------------------
+# The ragged front end: the dense front-end kernels with a length per row.  Buffers have the dense layout of
+# the LONGEST row; the tables are int32 device tensors that functional.ragged_plan builds once per lengths tuple.  Costs are
+# stated over the valid rows (`n_*` = their sums over the batch, host integers of the plan), as the dense wrappers state theirs.
+# ---------------------------------------------------------------------------
+def _ragged_check(name, ok):
+    """the ragged wrappers' refusal: the one predicate's verdict `ok`, answered like every checking wrapper (_refuse)"""
+    if not ok:
+        _refuse(name)
+
+
+def sinc_fir16_varlen(wave, lengths, filt, out, C, K, n_valid, passes=0):
+    """sinc_fir16 (one pass, resident taps) on wave [B, Lrow] with lengths[b] valid samples per row -> out [B, Lrow, C] rows below
+    lengths[b], and the zero-filled GroupNorm partials [B, P, 8, 2] whose slots past a row's last tile stay zero."""
+    _need_dev(wave, lengths, filt, out)
+    Lb = _lib.load()
+    _ragged_check("sinc_fir16_varlen", _is(wave, _F32, ndim=2, least=1) and wave.shape[0] <= 65535 and
+                  _lengths_ok(lengths, wave.shape[0]) and lengths is not None and _is(filt, _F32, (C, K)) and
+                  _is(out, None, (wave.shape[0], wave.shape[1], C)) and out.dtype in (_state["dtype"], _F32))
+    B, Lrow = wave.shape
+    wsh = torch.empty(_K["SINC_FIR16_WS_WORDS"], device=wave.device, dtype=torch.int16)
+    P = Lb.sfm_sinc_fir16_tiles(Lrow)
+    part = torch.zeros(B, P, 8, 2, device=wave.device, dtype=torch.float32)
+    out_f32 = 1 if out.dtype == torch.float32 else 0
+    _call("sinc_fir16", Lb.sfm_sinc_fir16_varlen, (_p(wave), _p(lengths), _p(filt), _p(wsh), _p(out), _p(part), B, Lrow, C, K, out_f32,
+                                                   _dt(), int(passes), _stream()),
+          2.0 * n_valid * C * K, n_valid * 4 + n_valid * C * (4 if out_f32 else 2))
+    return part, P
+
+
+def conv16p_varlen(x1, sc1, sh1, pw, out, lin_tab, lout_tab, *, B, Lin, stride, pad, n_out, x2=None, sc2=None, sh2=None,
+                   gn_partial=None, gn_group=0, skip_pw=None, out_s=None, gn_partial_s=None):
+    """conv16p with lin_tab[b] input rows and lout_tab[b] output rows per utterance inside buffers of row counts Lin / Lout;
+    gn_partial (_s) zero-filled by the caller.  n_out: the sum of lout_tab (host), for the cost."""
+    _need_dev(x1, out, lin_tab, lout_tab)
+    L = _lib.load()
+    cin, N, ks = pw.cin, pw.N, pw.ksize
+    dt = _state["dtype"]
+    Lout = (Lin + 2 * pad - ks) // stride + 1
+    _ragged_check("conv16p_varlen", _is(x1, dt, (B, Lin, cin)) and _is(x2, dt, (B, Lin, cin), opt=True) and pw.w.dtype is dt and
+                  _each(_F32, B * cin, sc1, sh1) and (x2 is None or _each(_F32, B * cin, sc2, sh2)) and
+                  _lengths_ok(lin_tab, B) and _lengths_ok(lout_tab, B) and lin_tab is not None and lout_tab is not None and
+                  _is(out, None, (B, Lout, N)) and _is(out_s, out.dtype, (B, Lout, N), opt=True) and
+                  pw.Npad == N and pw.Kpad == ks * cin and (skip_pw is None or (skip_pw.Npad == N and skip_pw.Kpad == cin)))
+    out_f32 = 1 if out.dtype == torch.float32 else (0 if out.dtype == dt else 2)
+    nin = 2 if x2 is not None else 1
+    n_in = n_out * stride
+    flops = 2.0 * n_out * N * (ks * cin + (cin if skip_pw is not None else 0))
+    nbytes = n_in * cin * 2.0 * nin + n_out * N * out.element_size() * (2 if skip_pw is not None else 1) + N * ks * cin * 2.0
+    _call("conv16p", L.sfm_conv16p_varlen,
+          (_p(x1), _p(sc1), _p(sh1), _p(x2), _p(sc2), _p(sh2), _p(pw.w), _p(pw.bias), _p(out), _p(gn_partial),
+           _p(skip_pw.w if skip_pw is not None else None), _p(skip_pw.bias if skip_pw is not None else None), _p(out_s),
+           _p(gn_partial_s), _p(lin_tab), _p(lout_tab), B, Lin, cin, N, ks, stride, pad, out_f32, gn_group, _dt(), _stream()),
+          flops, nbytes, tag="Lout%d Cin%d N%d k%d s%d in%d%s varlen" % (n_out, cin, N, ks, stride, nin,
+                                                                       " +skip" if skip_pw is not None else ""))
+    return out
+
+
+def gn_finalize_varlen(partial, w, b, rows_tab, p_tab, Bn, Pmax, G, C, eps=1e-5):
+    """gn_finalize with rows_tab[b] rows and p_tab[b] partial slots per utterance (partial [Bn, Pmax, G, 2]) -> scale, shift [Bn, C]"""
+    _need_dev(partial, w, b, rows_tab, p_tab)
+    L = _lib.load()
+    _ragged_check("gn_finalize_varlen", _is(partial, _F32, Bn * Pmax * G * 2) and _each(_F32, C, w, b) and G > 0 and C % G == 0 and
+                  _lengths_ok(rows_tab, Bn) and _lengths_ok(p_tab, Bn) and rows_tab is not None and p_tab is not None)
+    scale = torch.empty(Bn, C, device=w.device, dtype=torch.float32)
+    shift = torch.empty(Bn, C, device=w.device, dtype=torch.float32)
+    _call("gn_finalize", L.sfm_gn_finalize_varlen, (_p(partial), _p(w), _p(b), _p(scale), _p(shift), _p(rows_tab), _p(p_tab), Bn, Pmax,
+                                                    G, C, eps, _stream()), 0.0, 8.0 * Bn * C)
+    return scale, shift
+
+
+def gn_apply_varlen(x1, sc1, sh1, out, rows_tab, Bn, rows, C, n_valid):
+    """gn_apply(act=1) on 16-bit rows x1 [Bn, rows, C] -> out of the same shape and format: the rows below rows_tab[b] as gn_apply,
+    zeros from there on (never read)"""
+    _need_dev(x1, out, rows_tab)
+    L = _lib.load()
+    dt = _state["dtype"]
+    _ragged_check("gn_apply_varlen", _is(x1, dt, (Bn, rows, C)) and _is(out, dt, (Bn, rows, C)) and _each(_F32, Bn * C, sc1, sh1) and
+                  _lengths_ok(rows_tab, Bn) and rows_tab is not None and 64 <= C <= 2048 and C & (C - 1) == 0)
+    _call("gn_apply", L.sfm_gn_apply_varlen, (_p(x1), _p(sc1), _p(sh1), _p(out), _p(rows_tab), Bn, rows, C, _dt(), _stream()),
+          10.0 * n_valid * C, n_valid * C * 2 + Bn * rows * C * 2)
+    return out
+
+
+def headpool_tab(Tin, Tout):
+    """host table of sfm_headpool_varlen: int32 [B, 4] = (Tin_b, Tout_b, frames per tile, tiles), by sfm_headpool_frames_per_tile;
+    None when a pair is not supported or the fusion is switched off"""
+    rows = []
+    for ti, to in zip(Tin, Tout):
+        t = headpool_tiles(int(ti), int(to))
+        if t is None:
+            return None
+        rows.append((int(ti), int(to), t[0], t[1]))
+    return np.asarray(rows, dtype=np.int32).reshape(-1, 4)
+
+
+def headpool_varlen(xd16, pw, pooled16, part, tab, B, TinS, ToutS, PS, n_in, n_out, gcols=16):
+    """headpool with tab[b] = (Tin_b, Tout_b, frames per tile, tiles): xd16 [B, TinS, 256] -> pooled16 [B, ToutS, N] (zeros from
+    Tout_b on), part [B, PS, N / gcols, 2] zero-filled by the caller.  n_in / n_out: the sums of Tin_b / Tout_b, for the cost."""
+    _need_dev(xd16, pooled16, part, tab)
+    L = _lib.load()
+    dt = _state["dtype"]
+    _ragged_check("headpool_varlen", _is(xd16, dt, (B, TinS, None)) and _is(pooled16, dt, (B, ToutS, None)) and pw.w.dtype is dt and
+                  pooled16.shape[2] >= pw.Npad and _is(part, _F32, B * PS * (pw.Npad // gcols) * 2) and _is(tab, _I32, (B, 4)))
+    _call("gemm16", L.sfm_headpool_varlen, (_p(xd16), _p(pw.w), _p(pw.bias), _p(pooled16), _p(part), _p(tab), B, TinS, ToutS, PS, pw.Npad,
+                                            xd16.stride(1), pooled16.stride(1), gcols, _dt(), _stream()),
+          2.0 * n_in * pw.Npad * 256, n_in * 512.0 + pw.Npad * 512.0 + B * ToutS * pw.Npad * 2.0,
+          tag="M%d N%d K256 headpool->T%d varlen" % (n_in, pw.Npad, n_out))
+
+
+def bilstm_layer_rows16_varlen(xg, whh, ttab, B, T, H, n_steps, out16=None):
+    """bilstm_layer_rows16 with ttab[b] steps per chain inside rows of stride T; the rows from ttab[b] on are written as zeros.
+    H 128 on fp16 recurrent operands only (the caller refuses the rest).  n_steps: the sum of ttab, for the cost."""
+    _need_dev(xg, whh, ttab, out16)
+    L = _lib.load()
+    _ragged_check("bilstm_layer_rows16_varlen", H == 128 and _is(xg, _F32, B * T * 8 * H) and _is(whh, _F32, (2, 4 * H, H)) and
+                  _lengths_ok(ttab, B) and ttab is not None and
+                  _is(out16, _state["dtype"], (B * T, None), opt=True, contig="last"))
+    if out16 is None:
+        out16 = torch.empty(B * T, 2 * H, device=xg.device, dtype=compute_dtype())
+    flops, nbytes = 2.0 * n_steps * 2 * 4 * H * H, n_steps * 8 * H * 4 + B * T * 2 * H * 2
+    _call("bilstm_layer", L.sfm_bilstm_layer_rows16_varlen, (_p(xg), _p(whh), _p(out16), out16.stride(0), _p(ttab), B, T, H, 1, _dt(),
+                                                             _stream()), flops, nbytes)
+    return out16
+
+
+def rows_gather32(src, dst, rows_tab, dst_off, B, src_rows, width, n_rows):
+    """the hand-over from the padded to the packed layout: the first `width` elements of row r < rows_tab[b] of src [B * src_rows, ld]
+    -> row dst_off[b] + r of dst [n_rows, ld'].  src and dst hold the same element type (4 bytes, or 2 with an even width)."""
+    _need_dev(src, dst, rows_tab, dst_off)
+    L = _lib.load()
+    per = 4 // src.element_size() if src is not None and src.element_size() in (2, 4) else 0
+    ok = (per > 0 and _is(src, dst.dtype if dst is not None else None, contig="last", ndim=2, rows=B * src_rows) and
+          _is(dst, src.dtype, (n_rows, None), contig="last") and width % per == 0 and src.stride(0) % per == 0 and
+          dst.stride(0) % per == 0 and 0 < width <= min(src.shape[1], dst.shape[1]) and
+          _lengths_ok(rows_tab, B) and rows_tab is not None and _is(dst_off, _I32, least=B))
+    _ragged_check("rows_gather32", ok)
+    _call("rows_gather", L.sfm_rows_gather32, (_p(src), _p(dst), _p(rows_tab), _p(dst_off), B, src_rows, width // per,
+                                               src.stride(0) // per, dst.stride(0) // per, _stream()),
+          0.0, 2.0 * n_rows * width * src.element_size())
+    return dst
+
+
 def pack_spec(re, im, dst, M, F, ld, ld_src):
     L = _lib.load()
     _call("pack_spec", L.sfm_pack_spec, (_p(re), _p(im), _p(dst), M, F, ld, ld_src, _stream()))

@@ -586,6 +586,48 @@ class EnhancementPath(HipModule):
         return Fn.enhance_path(waveform.float(), packs, H=self.msa.conformer.num_heads,
                                use_memory=self.memory is not None, want=want)
 
+    def _refuse_ragged(self, waveform, want):
+        """what forward_ragged does not take, said before anything is packed or launched (and so without a device)"""
+        if self.training or self._wants_autograd(waveform):
+            raise RuntimeError("EnhancementPath.forward_ragged is an inference path: call eval() and pass a waveform that does "
+                               "not require grad (training takes rectangular batches through forward())")
+        if self.memory is not None:
+            raise NotImplementedError("EnhancementPath.forward_ragged: use_memory=True has no ragged form (the memory key is a "
+                                      "mean over frames)")
+        if "latents" in want:
+            raise NotImplementedError("EnhancementPath.forward_ragged does not return full-rate latents")
+
+    def forward_ragged(self, waveform, lengths, want=("mask", "wave")):
+        """forward() on utterances of different lengths in ONE pass: waveform [B, Lmax] zero-padded (what follows lengths[b]
+        samples in row b is never read), lengths a sequence of B ints >= functional.RAGGED_MIN_SAMPLES.  Returns packed results
+        (functional.enhance_path_ragged): mask_real / mask_imag [sum_T, 129], sigma [sum_Tpa], enhanced [sum_L], seg, plan -
+        every utterance as forward() gives it alone.  eval() only, no memory, no latents."""
+        self._refuse_ragged(waveform, want)
+        plan = Fn.ragged_plan(lengths)                             # (a short utterance: ValueError, before the device check)
+        self._require_device(waveform)
+        packs = self._packed(self._pack)
+        return Fn.enhance_path_ragged(waveform.float(), plan, packs, H=self.msa.conformer.num_heads, want=want)
+
+    @torch.no_grad()
+    def enhance_batch(self, signals):
+        """forward_ragged for a list of 1-D signals (numpy arrays or tensors) of different lengths: one page-locked upload of the
+        zero-padded batch, one pass, one download of the packed result; returns a list of numpy arrays of the input lengths.
+        Splitting a large set into passes is the caller's."""
+        sigs = [np.ascontiguousarray(s.detach().cpu().numpy() if torch.is_tensor(s) else s, dtype=np.float32).reshape(-1)
+                for s in signals]
+        if not sigs:
+            return []
+        self._refuse_ragged(torch.empty(0), ("wave",))
+        plan = Fn.ragged_plan([s.size for s in sigs])
+        dev = next(self.parameters()).device
+        stage = torch.zeros(len(sigs), plan.max_rows[0], dtype=torch.float32, pin_memory=True)
+        host = stage.numpy()
+        for b, s in enumerate(sigs):
+            host[b, :s.size] = s
+        out = self.forward_ragged(stage.to(dev, non_blocking=True), plan, want=("wave",))
+        y = out["enhanced"].cpu().numpy()
+        return np.split(y, plan.seg.sample_offsets[1:-1])
+
 
 class ConformerPipeline:
     """training/conformer_pipeline.py:308-685 without its file search and audio loading: train (:403) on two WaveformSets, the
