@@ -546,6 +546,24 @@ int sfm_attention_fwd_train(const void* qkv, void* out, float* lse, int B, int T
 int sfm_attention_bwd(const void* qkv, const void* O, const void* dO, const float* lse, float* delta, void* dqkv,
                       int B, int T, int H, int hd, int ldqkv, int ldo, int koff, int voff, float p_drop,
                       unsigned int seed, int dtype, void* stream);
+/* The three training launches that see (B, T), on packed rows (utterance u = rows [frame_off[u], frame_off[u + 1]), int32[B + 1] on
+ * the device).  Attention, head_dim 64 only: items = sfm_attention_fwd_varlen's table, one workgroup of each kernel per entry
+ * (forward: 128 queries; backward: 128 queries for dQ, 128 keys for dK / dV); lse and the workspace delta are fp32 [H, sum_T]
+ * (entry h * sum_T + packed row, log2 domain); the dropout hash row of (u, h, q) is H * frame_off[u] + h * T_u + q, which is the
+ * dense launches' (b * H + h) * T + q when all lengths are equal. */
+int sfm_attention_fwd_train_varlen(const void* qkv, void* out, float* lse, const int* frame_off, const int* items, int n_items,
+                                   int B, int max_T, int sum_T, int H, int hd, int ldqkv, int ldo, int koff, int voff,
+                                   float scale, float p_drop, unsigned int seed, int dtype, void* stream);
+int sfm_attention_bwd_varlen(const void* qkv, const void* O, const void* dO, const float* lse, float* delta, void* dqkv,
+                             const int* frame_off, const int* items, int n_items, int B, int max_T, int sum_T, int H, int hd,
+                             int ldqkv, int ldo, int koff, int voff, float p_drop, unsigned int seed, int dtype, void* stream);
+/* sfm_dwconv_wgrad on packed rows: spans = int32[n_spans][3] (utterance, first frame, frame count), every frame of every
+ * utterance in exactly one span, no span across an utterance; the x window is zero outside the span's own utterance.  One
+ * partial per span in scratch (sfm_dwconv_wgrad_varlen_scratch_floats floats; SFM_ERR_SHAPE when that count passes 2^31 - 1),
+ * folded in table order into dw [C, KS] / db [C] (accumulated). */
+int sfm_dwconv_wgrad_varlen_scratch_floats(int n_spans, int C, int KS);
+int sfm_dwconv_wgrad_varlen(const void* x, const float* dy, float* dw, float* db, float* scratch, const int* frame_off,
+                            const int* spans, int n_spans, int B, int sum_T, int C, int KS, int dtype, void* stream);
 /* Linear layer with K = 256 inputs and a 16-bit result, one 8-wave workgroup per 128 rows for ALL output columns (A tile resident in
    registers, W streamed through an LDS-DMA ring, epilogue of a 64-row W chunk under the next chunk's MFMAs; csrc/lin256.hip):
      glu == 0: out[M, NW]     = A[M, 256] W^T + b                       (models/conformer.py:57-59, the Q | K | V projection)

@@ -40,6 +40,9 @@ __device__ __forceinline__ float sfm_max3_raw(float a, float b, float c) { retur
 // frame_off[u + 1])); a workgroup is one entry (utterance, head, query tile) of the item table the host built from the lengths
 // (ops.attention_items: only the tiles that exist, longest key range first).  Query tiles start at the utterance's first row and
 // keys run over that utterance alone, so an utterance's result is the dense kernel's on that utterance by itself.
+// The training form (lse_out given, DROP) hands the packed row count sum_T in through `Tlen`: LSE is [H, sum_T], entry
+// h * sum_T + packed row, and the dropout hash row is H * frame_off[u] + h * T_u + q - unique over the pack, and the dense
+// kernel's own (b * H + h) * T + q when every utterance has T rows.
 template <class T, bool DROP, bool VARLEN = false>
 __global__ __launch_bounds__(256) void attn_fwd_hd64_kernel(const u16* __restrict__ qkv, u16* __restrict__ out,
                                                             int Tlen, int ldqkv, int ldo, int koff, int voff,
@@ -56,12 +59,14 @@ __global__ __launch_bounds__(256) void attn_fwd_hd64_kernel(const u16* __restric
   // run of (batch, head, q-tile) ids: the q-tiles that share one (batch, head)'s K/V then share an L2.
   int id = blockIdx.x;
   int qt, h, b;
+  int row0 = 0;
+  const int sum_T = Tlen;                                           // (VARLEN only)
   if (VARLEN) {
     // (the host has dealt the table over the XCDs already: ops.attention_items)
     const int u = __builtin_amdgcn_readfirstlane(items[4 * id]);
     h = __builtin_amdgcn_readfirstlane(items[4 * id + 1]);
     qt = __builtin_amdgcn_readfirstlane(items[4 * id + 2]);
-    const int row0 = __builtin_amdgcn_readfirstlane(frame_off[u]);
+    row0 = __builtin_amdgcn_readfirstlane(frame_off[u]);
     Tlen = __builtin_amdgcn_readfirstlane(frame_off[u + 1]) - row0;
     b = 0;
     qkv += (long long)row0 * ldqkv;
@@ -118,7 +123,9 @@ __global__ __launch_bounds__(256) void attn_fwd_hd64_kernel(const u16* __restric
   for (int r = 0; r < 16; ++r) lacc[r] = 0.f;
   float m_run = 0.f;                                                // value currently subtracted by the MFMA
   // attention dropout (training): the lane's probability row is fixed, so its row hash is computed once
-  const uint32_t drop_rowh = DROP ? sfm_hash(seed, ((unsigned long long)b * nheads + h) * Tlen + (q0 + l31 < Tlen ? q0 + l31 : 0)) : 0u;
+  const unsigned long long drop_row0 = VARLEN ? (unsigned long long)nheads * row0 + (unsigned long long)h * Tlen
+                                             : ((unsigned long long)b * nheads + h) * Tlen;
+  const uint32_t drop_rowh = DROP ? sfm_hash(seed, drop_row0 + (q0 + l31 < Tlen ? q0 + l31 : 0)) : 0u;
   const uint32_t drop_thr = DROP ? sfm_keep_threshold(p_drop) : 0u;
   const float drop_ik = DROP ? 1.0f / (1.0f - p_drop) : 1.0f;
 
@@ -270,7 +277,8 @@ __global__ __launch_bounds__(256) void attn_fwd_hd64_kernel(const u16* __restric
   // ---- epilogue: normalise, transpose through LDS, coalesced stores ----
   const float inv = 1.0f / lacc[0];
   if (lse_out && hl == 0 && q0 + l31 < Tlen)             // log2-domain log-sum-exp of the scaled scores (for the backward)
-    lse_out[((long long)b * nheads + h) * Tlen + q0 + l31] = m_run + __builtin_amdgcn_logf(lacc[0]);
+    lse_out[(VARLEN ? (long long)h * sum_T + row0 : ((long long)b * nheads + h) * Tlen) + q0 + l31] =
+        m_run + __builtin_amdgcn_logf(lacc[0]);
   u16* Os = smem + wave * (32 * OS_ROW);
 #pragma unroll
   for (int dj = 0; dj < 2; ++dj)
@@ -824,6 +832,30 @@ extern "C" int sfm_attention_fwd_varlen(const void* qkv, void* out, const int* f
   else
     SFM_LAUNCH((attn_fwd_generic_kernel<BF16, true>), grid, block, 0, st, (const u16*)qkv, (u16*)out, sum_T, hd, ldqkv, ldo, koff,
                voff, 0LL, 0LL, scale, (float*)nullptr, 0.f, 0u, frame_off, B);
+  return SFM_OK;
+}
+
+// training-mode forward on packed rows (head_dim 64 only): sfm_attention_fwd_varlen that also writes lse [H, sum_T] (log2
+// domain, entry h * sum_T + packed row) and applies attention dropout under the packed row index (see attn_fwd_hd64_kernel)
+extern "C" int sfm_attention_fwd_train_varlen(const void* qkv, void* out, float* lse, const int* frame_off, const int* items,
+                                              int n_items, int B, int max_T, int sum_T, int H, int hd, int ldqkv, int ldo,
+                                              int koff, int voff, float scale, float p_drop, unsigned int seed, int dtype,
+                                              void* stream) {
+  if (!qkv || !out || !lse || !frame_off || !items) return SFM_ERR_ARG;
+  if (B <= 0 || max_T <= 0 || sum_T < max_T || H <= 0 || hd != 64 || p_drop < 0.f || p_drop >= 1.f) return SFM_ERR_SHAPE;
+  if (ldqkv < H * hd || ldo < H * hd || (ldqkv % 8) || (ldo % 8) || (koff % 8) || (voff % 8)) return SFM_ERR_SHAPE;
+  if (n_items < B * H || (long long)n_items > (long long)B * H * ((max_T + SFM_ATTN_QTILE - 1) / SFM_ATTN_QTILE))
+    return SFM_ERR_SHAPE;
+  if (dtype != SFM_DT_BF16 && dtype != SFM_DT_F16) return SFM_ERR_ARG;
+  const float sl2 = (scale > 0.f) ? scale * 1.44269504088896340736f : 1.0f;
+  hipStream_t st = (hipStream_t)stream;
+  dim3 grid(n_items), block(256);
+#define ATTN_GO(TT, DD)                                                                                                  \
+  SFM_LAUNCH((attn_fwd_hd64_kernel<TT, DD, true>), grid, block, 0, st, (const u16*)qkv, (u16*)out, sum_T, ldqkv, ldo, koff, voff, \
+             0LL, 0LL, sl2, 1, H, lse, p_drop, seed, 0, frame_off, items)
+  if (dtype == SFM_DT_F16) { if (p_drop > 0.f) ATTN_GO(F16, true); else ATTN_GO(F16, false); }
+  else { if (p_drop > 0.f) ATTN_GO(BF16, true); else ATTN_GO(BF16, false); }
+#undef ATTN_GO
   return SFM_OK;
 }
 

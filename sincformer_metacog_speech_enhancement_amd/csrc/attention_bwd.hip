@@ -53,11 +53,19 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const u16* __restrict__
 }
 
 // ----------------------------------------------------------------------------------------------------
-template <class T>
+// VARLEN (both kernels below): the packed form, as attn_fwd_hd64_kernel's.  qkv / dO / dqkv hold the rows of all utterances back
+// to back; a workgroup is one entry (utterance, head, 128-row tile) of the forward's item table (ops.attention_items: both
+// kernels tile by SFM_ATTN_QTILE rows, queries here, keys in attn_bwd_dkv), the operand pointers are advanced to the
+// utterance's first row and the loops run over that utterance alone.  `Tlen` hands in the packed row count sum_T: lse / delta
+// are [H, sum_T], entry h * sum_T + packed row; the dropout hash row is H * frame_off[u] + h * T_u + q, as the forward's.
+template <class T, bool VARLEN = false>
 __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const u16* __restrict__ qkv, const u16* __restrict__ dO,
                                                           const float* __restrict__ lse, const float* __restrict__ delta,
                                                           u16* __restrict__ dqkv, int Tlen, int H, int ldqkv, int ldo,
-                                                          int koff, int voff, int nqt, float p_drop, uint32_t seed) {
+                                                          int koff, int voff, int nqt, float p_drop, uint32_t seed,
+                                                          const int* __restrict__ frame_off = nullptr,
+                                                          const int* __restrict__ items = nullptr) {
+  static_assert(SFM_ATTN_QTILE == 128, "the item table's tile is this kernel's 4 waves x 32 queries");
   __shared__ __attribute__((aligned(16))) u16 smem[64 * RS_ROW * 2 + 64 * TS_ROW];
   u16* Kr = smem;                       // K rows     (S^T  = K Q^T)
   u16* Vr = smem + 64 * RS_ROW;         // V rows     (dP^T = V dO^T)
@@ -65,7 +73,20 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const u16* __restrict_
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l31 = lane & 31, hl = lane >> 5;
   const int id = blockIdx.x;
-  const int qt = id % nqt, h = (id / nqt) % H, b = id / (nqt * H);
+  int qt = id % nqt, h = (id / nqt) % H, b = id / (nqt * H);
+  int row0 = 0;
+  const int sum_T = Tlen;                                            // (VARLEN only)
+  if (VARLEN) {
+    const int u = __builtin_amdgcn_readfirstlane(items[4 * id]);
+    h = __builtin_amdgcn_readfirstlane(items[4 * id + 1]);
+    qt = __builtin_amdgcn_readfirstlane(items[4 * id + 2]);
+    row0 = __builtin_amdgcn_readfirstlane(frame_off[u]);
+    Tlen = __builtin_amdgcn_readfirstlane(frame_off[u + 1]) - row0;
+    b = 0;
+    qkv += (long long)row0 * ldqkv;
+    dO += (long long)row0 * ldo;
+    dqkv += (long long)row0 * ldqkv;
+  }
   const int q0 = qt * 128 + wave * 32;
   const int q = q0 + l31;
   const u16* base = qkv + (long long)b * Tlen * ldqkv + h * 64;
@@ -82,10 +103,12 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const u16* __restrict_
     qf[ks] = a;
     dof[ks] = c;
   }
-  const long long rowid = ((long long)b * H + h) * Tlen + (q < Tlen ? q : 0);
+  const long long rowid = (VARLEN ? (long long)h * sum_T + row0 : ((long long)b * H + h) * Tlen) + (q < Tlen ? q : 0);
   const float lse_q = (q < Tlen) ? lse[rowid] : 1e30f;
   const float dl_q = (q < Tlen) ? delta[rowid] : 0.f;
-  const uint32_t drop_rowh = sfm_hash(seed, (unsigned long long)rowid);   // the lane's probability row is fixed
+  // the lane's probability row is fixed
+  const uint32_t drop_rowh = sfm_hash(seed, VARLEN ? (unsigned long long)H * row0 + (unsigned long long)h * Tlen + (q < Tlen ? q : 0)
+                                                   : (unsigned long long)rowid);
   const uint32_t drop_thr = sfm_keep_threshold(p_drop);
 
   f32x16 dq[2];
@@ -190,11 +213,14 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const u16* __restrict_
 }
 
 // ----------------------------------------------------------------------------------------------------
-template <class T, bool DROP>
+template <class T, bool DROP, bool VARLEN = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const u16* __restrict__ qkv, const u16* __restrict__ dO,
                                                            const float* __restrict__ lse, const float* __restrict__ delta,
                                                            u16* __restrict__ dqkv, int Tlen, int H, int ldqkv, int ldo,
-                                                           int koff, int voff, int nkt, float p_drop, uint32_t seed) {
+                                                           int koff, int voff, int nkt, float p_drop, uint32_t seed,
+                                                           const int* __restrict__ frame_off = nullptr,
+                                                           const int* __restrict__ items = nullptr) {
+  static_assert(SFM_ATTN_QTILE == 128, "the item table's tile is this kernel's 4 waves x 32 keys");
   __shared__ __attribute__((aligned(16))) u16 smem[2 * 64 * RS_ROW + 2 * 64 * TS_ROW];
   __shared__ float sl[64], sd[64];
   __shared__ uint32_t srh[64];                         // row hashes of the staged query tile (attention dropout)
@@ -205,7 +231,20 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const u16* __restr
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l31 = lane & 31, hl = lane >> 5;
   const int id = blockIdx.x;
-  const int ktile = id % nkt, h = (id / nkt) % H, b = id / (nkt * H);
+  int ktile = id % nkt, h = (id / nkt) % H, b = id / (nkt * H);
+  int row0 = 0;
+  const int sum_T = Tlen;                                            // (VARLEN only)
+  if (VARLEN) {
+    const int u = __builtin_amdgcn_readfirstlane(items[4 * id]);
+    h = __builtin_amdgcn_readfirstlane(items[4 * id + 1]);
+    ktile = __builtin_amdgcn_readfirstlane(items[4 * id + 2]);
+    row0 = __builtin_amdgcn_readfirstlane(frame_off[u]);
+    Tlen = __builtin_amdgcn_readfirstlane(frame_off[u + 1]) - row0;
+    b = 0;
+    qkv += (long long)row0 * ldqkv;
+    dO += (long long)row0 * ldo;
+    dqkv += (long long)row0 * ldqkv;
+  }
   const int key0 = ktile * 128 + wave * 32;
   const int key = key0 + l31;
   const u16* base = qkv + (long long)b * Tlen * ldqkv + h * 64;
@@ -256,9 +295,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const u16* __restr
     }
     if (tid < 64) {
       const int q = qt * 64 + tid;
-      rl = (q < Tlen) ? lse[bh * Tlen + q] : 1e30f;             // rows past T get P = 0
-      rdl = (q < Tlen) ? delta[bh * Tlen + q] : 0.f;
-      if (DROP) rrh = sfm_hash(seed, (unsigned long long)(bh * Tlen + (q < Tlen ? q : 0)));
+      rl = (q < Tlen) ? lse[(VARLEN ? (long long)h * sum_T + row0 : bh * Tlen) + q] : 1e30f;             // rows past T get P = 0
+      rdl = (q < Tlen) ? delta[(VARLEN ? (long long)h * sum_T + row0 : bh * Tlen) + q] : 0.f;
+      if (DROP) rrh = sfm_hash(seed, (unsigned long long)((VARLEN ? (long long)H * row0 + (long long)h * Tlen : bh * Tlen) + (q < Tlen ? q : 0)));
     }
   };
   load_tile(0);
@@ -483,5 +522,38 @@ extern "C" int sfm_attention_bwd(const void* qkv, const void* O, const void* dO,
       SFM_LAUNCH((attn_bwd_dkv_kernel<BF16, false>), g2, blk, 0, st, (const u16*)qkv, (const u16*)dO, lse, delta, (u16*)dqkv,
                  T, H, ldqkv, ldo, koff, voff, nq, p_drop, seed);
   }
+  return SFM_OK;
+}
+
+// sfm_attention_bwd on packed rows (head_dim 64): qkv / dqkv [sum_T, ldqkv], O / dO [sum_T, ldo], utterance u = rows
+// [frame_off[u], frame_off[u + 1]); lse (from sfm_attention_fwd_train_varlen) and the workspace delta are [H, sum_T]; one
+// workgroup of each kernel per entry of the forward's item table (every 128-row tile of every (utterance, head) once).
+extern "C" int sfm_attention_bwd_varlen(const void* qkv, const void* O, const void* dO, const float* lse, float* delta, void* dqkv,
+                                        const int* frame_off, const int* items, int n_items, int B, int max_T, int sum_T, int H,
+                                        int hd, int ldqkv, int ldo, int koff, int voff, float p_drop, unsigned int seed, int dtype,
+                                        void* stream) {
+  if (!qkv || !O || !dO || !lse || !delta || !dqkv || !frame_off || !items) return SFM_ERR_ARG;
+  if (B <= 0 || max_T <= 0 || sum_T < max_T || H <= 0 || hd != 64 || (ldqkv % 8) || (ldo % 8) || (koff % 8) || (voff % 8) ||
+      ldqkv < H * hd || ldo < H * hd || p_drop < 0.f || p_drop >= 1.f)
+    return SFM_ERR_SHAPE;
+  if (n_items < B * H || (long long)n_items > (long long)B * H * ((max_T + SFM_ATTN_QTILE - 1) / SFM_ATTN_QTILE))
+    return SFM_ERR_SHAPE;
+  if (dtype != SFM_DT_BF16 && dtype != SFM_DT_F16) return SFM_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const long long total = (long long)H * sum_T;                     // delta: the dense kernel on one "utterance" of sum_T rows
+  dim3 g1((unsigned)((total + 255) / 256)), g2(n_items), blk(256);
+#define BWD_ARGS (const u16*)qkv, (const u16*)dO, lse, delta, (u16*)dqkv, sum_T, H, ldqkv, ldo, koff, voff, 1, p_drop, seed, frame_off, items
+  if (dtype == SFM_DT_F16) {
+    SFM_LAUNCH((attn_delta_kernel<F16>), g1, blk, 0, st, (const u16*)dO, (const u16*)O, delta, sum_T, H, ldo, total);
+    SFM_LAUNCH((attn_bwd_dq_kernel<F16, true>), g2, blk, 0, st, BWD_ARGS);
+    if (p_drop > 0.f) SFM_LAUNCH((attn_bwd_dkv_kernel<F16, true, true>), g2, blk, 0, st, BWD_ARGS);
+    else SFM_LAUNCH((attn_bwd_dkv_kernel<F16, false, true>), g2, blk, 0, st, BWD_ARGS);
+  } else {
+    SFM_LAUNCH((attn_delta_kernel<BF16>), g1, blk, 0, st, (const u16*)dO, (const u16*)O, delta, sum_T, H, ldo, total);
+    SFM_LAUNCH((attn_bwd_dq_kernel<BF16, true>), g2, blk, 0, st, BWD_ARGS);
+    if (p_drop > 0.f) SFM_LAUNCH((attn_bwd_dkv_kernel<BF16, true, true>), g2, blk, 0, st, BWD_ARGS);
+    else SFM_LAUNCH((attn_bwd_dkv_kernel<BF16, false, true>), g2, blk, 0, st, BWD_ARGS);
+  }
+#undef BWD_ARGS
   return SFM_OK;
 }

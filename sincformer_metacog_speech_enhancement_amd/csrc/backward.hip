@@ -816,19 +816,38 @@ extern "C" int sfm_bn_swish_bwd(const void* g, const float* y, const float* mean
 // ---------------------------------------------------------------------------
 // Depthwise conv weight gradient: dW[c][k] += sum_{b,t} dY[b,t,c] * X[b, t+k-pad, c]   (X 16-bit, dY fp32)
 // one thread per channel, KS accumulators, a block covers a span of frames of one utterance
+// VARLEN (both kernels): the packed form.  x / dy [sum_T, C] hold the utterances back to back (utterance u = rows
+// [frame_off[u], frame_off[u + 1])); workgroup row y handles entry y of the host's span table (ops.dwconv_wgrad_spans:
+// int32 [n][3] = utterance, first frame, frame count; a span lies inside one utterance) and the x window is zero outside
+// [0, T_u) of that utterance.  `span` hands in the number of utterances.  Same partial layout: partial y.
 // ---------------------------------------------------------------------------
-template <class T, int KS>
+template <class T, int KS, bool VARLEN = false>
 __global__ __launch_bounds__(128) void dwconv_wgrad_kernel(const u16* __restrict__ x, const float* __restrict__ dy,
-                                                           float* __restrict__ part, int Tlen, int C, int span) {
+                                                           float* __restrict__ part, int Tlen, int C, int span,
+                                                           const int* __restrict__ frame_off = nullptr,
+                                                           const int* __restrict__ spans = nullptr) {
   // two adjacent channels per thread (one 4-byte load of x, one 8-byte load of dy per frame); the KS-frame window of x
   // lives in registers and is indexed with compile-time (j + k) % KS, so sliding it costs no moves
   const int c = (blockIdx.x * 128 + threadIdx.x) * 2;
   if (c >= C) return;
   const int b = blockIdx.z;
-  const int t0 = blockIdx.y * span, t1 = min(Tlen, t0 + span);
+  int t0 = blockIdx.y * span, t1 = min(Tlen, t0 + span);
+  long long row0 = (long long)b * Tlen;
+  if (VARLEN) {
+    // `span` carries the number of utterances and `Tlen` nothing (the launcher passes B and 0): the length comes from the table.
+    // The three table words are wave-uniform: read once into scalars.  The clamps keep a table that breaks its contract
+    // (sfm_dwconv_wgrad_varlen: spans inside their utterance) inside the operands; they do not make its result right.
+    const int nutt = span;
+    const int u = min(max(__builtin_amdgcn_readfirstlane(spans[3 * blockIdx.y]), 0), nutt - 1);
+    const int first = __builtin_amdgcn_readfirstlane(frame_off[u]);
+    row0 = first;
+    Tlen = __builtin_amdgcn_readfirstlane(frame_off[u + 1]) - first;
+    t0 = max(__builtin_amdgcn_readfirstlane(spans[3 * blockIdx.y + 1]), 0);
+    t1 = min(Tlen, t0 + __builtin_amdgcn_readfirstlane(spans[3 * blockIdx.y + 2]));
+  }
   constexpr int pad = (KS - 1) / 2;
-  const u16* xb = x + (long long)b * Tlen * C + c;
-  const float* gb = dy + (long long)b * Tlen * C + c;
+  const u16* xb = x + row0 * C + c;
+  const float* gb = dy + row0 * C + c;
   float acc0[KS], acc1[KS], w0[KS], w1[KS];
   auto load_x = [&](int tt, float& a, float& bb) {
     if (tt >= 0 && tt < Tlen) {
@@ -893,18 +912,33 @@ __global__ __launch_bounds__(128) void dwconv_wgrad_kernel(const u16* __restrict
 // x rows of a 31-frame chunk go through LDS, the NEXT chunk's 12 x 16-byte loads per thread are in flight while the current
 // one is multiplied (the kernel above prefetches one frame = 12 bytes per thread ahead and waits out a full memory round trip per
 // frame: 0.33 ms per launch at [205 056, 256] against 0.05 ms of FMA issue; tools/train_profile.py).  Same partial layout.
-template <class T>
+template <class T, bool VARLEN = false>
 __global__ __launch_bounds__(256) void dwconv_wgrad31_lds_kernel(const u16* __restrict__ x, const float* __restrict__ dy,
-                                                                 float* __restrict__ part, int Tlen, int C, int span) {
+                                                                 float* __restrict__ part, int Tlen, int C, int span,
+                                                                 const int* __restrict__ frame_off = nullptr,
+                                                                 const int* __restrict__ spans = nullptr) {
   constexpr int KS = 31, pad = 15;
   __shared__ __attribute__((aligned(16))) float gL[KS][256];
   __shared__ __attribute__((aligned(16))) u16 xL[KS][256];
   const int tid = threadIdx.x;
   const int cb = blockIdx.x * 256, c = cb + tid;
   const int b = blockIdx.z;
-  const int t0 = blockIdx.y * span, t1 = min(Tlen, t0 + span);
-  const u16* xb = x + (long long)b * Tlen * C + cb;
-  const float* gb = dy + (long long)b * Tlen * C + cb;
+  int t0 = blockIdx.y * span, t1 = min(Tlen, t0 + span);
+  long long row0 = (long long)b * Tlen;
+  if (VARLEN) {
+    // `span` carries the number of utterances and `Tlen` nothing (the launcher passes B and 0): the length comes from the table.
+    // The three table words are wave-uniform: read once into scalars.  The clamps keep a table that breaks its contract
+    // (sfm_dwconv_wgrad_varlen: spans inside their utterance) inside the operands; they do not make its result right.
+    const int nutt = span;
+    const int u = min(max(__builtin_amdgcn_readfirstlane(spans[3 * blockIdx.y]), 0), nutt - 1);
+    const int first = __builtin_amdgcn_readfirstlane(frame_off[u]);
+    row0 = first;
+    Tlen = __builtin_amdgcn_readfirstlane(frame_off[u + 1]) - first;
+    t0 = max(__builtin_amdgcn_readfirstlane(spans[3 * blockIdx.y + 1]), 0);
+    t1 = min(Tlen, t0 + __builtin_amdgcn_readfirstlane(spans[3 * blockIdx.y + 2]));
+  }
+  const u16* xb = x + row0 * C + cb;
+  const float* gb = dy + row0 * C + cb;
   float acc[KS], w[KS];
 #pragma unroll
   for (int k = 0; k < KS; ++k) {
@@ -988,6 +1022,21 @@ __global__ __launch_bounds__(256) void dwconv_wgrad_reduce_kernel(float* __restr
   else db[c] += s;
 }
 
+// the ordered fold of nparts partials [KS + 1][C] in `scratch` into dw / db (accumulated): chunks of 32 until one chunk is left
+static int dwconv_wgrad_fold(float* scratch, float* dw, float* db, int nparts, int C, int KS, hipStream_t st) {
+  const int ppb = 32;
+  long long stride = (long long)(KS + 1) * C;
+  while (true) {
+    const int final = nparts <= ppb;
+    dim3 g2(((KS + 1) * C + 255) / 256, final ? 1 : (nparts + ppb - 1) / ppb);
+    SFM_LAUNCH(dwconv_wgrad_reduce_kernel, g2, dim3(256), 0, st, scratch, dw, db, nparts, C, KS, ppb, stride, final);
+    if (final) break;
+    nparts = (int)g2.y;
+    stride *= ppb;
+  }
+  return SFM_OK;
+}
+
 extern "C" long long sfm_dwconv_wgrad_scratch_floats(int B, int T, int C, int KS) {
   int nspan = (2048 + B - 1) / B;
   if (nspan > (T + 31) / 32) nspan = (T + 31) / 32;
@@ -1017,16 +1066,37 @@ extern "C" int sfm_dwconv_wgrad(const void* x, const float* dy, float* dw, float
     else { if (KS == 31) GO(BF16, 31); else GO(BF16, 7); }
 #undef GO
   }
-  int nparts = B * ny;
-  const int ppb = 32;
-  long long stride = (long long)(KS + 1) * C;
-  while (true) {
-    const int final = nparts <= ppb;
-    dim3 g2(((KS + 1) * C + 255) / 256, final ? 1 : (nparts + ppb - 1) / ppb);
-    SFM_LAUNCH(dwconv_wgrad_reduce_kernel, g2, dim3(256), 0, st, scratch, dw, db, nparts, C, KS, ppb, stride, final);
-    if (final) break;
-    nparts = (int)g2.y;
-    stride *= ppb;
+  return dwconv_wgrad_fold(scratch, dw, db, B * ny, C, KS, st);
+}
+
+// Packed (variable-length) form of sfm_dwconv_wgrad: x / dy [sum_T, C] hold B utterances back to back, utterance u = rows
+// [frame_off[u], frame_off[u + 1]) (int32[B + 1] on the device); spans = int32[n_spans][3] (utterance, first frame, frame count)
+// covers every frame of every utterance once, no span across an utterance (ops.dwconv_wgrad_spans).  One partial per span in
+// `scratch` (sfm_dwconv_wgrad_varlen_scratch_floats floats), folded in the table's order: the same bits on every run.
+extern "C" int sfm_dwconv_wgrad_varlen_scratch_floats(int n_spans, int C, int KS) {
+  const long long n = (long long)n_spans * (KS + 1) * C;
+  return (n_spans <= 0 || C <= 0 || KS <= 0 || n > 0x7fffffffLL) ? SFM_ERR_SHAPE : (int)n;
+}
+
+extern "C" int sfm_dwconv_wgrad_varlen(const void* x, const float* dy, float* dw, float* db, float* scratch, const int* frame_off,
+                                       const int* spans, int n_spans, int B, int sum_T, int C, int KS, int dtype, void* stream) {
+  if (!x || !dy || !dw || !db || !scratch || !frame_off || !spans) return SFM_ERR_ARG;
+  if (B <= 0 || sum_T < B || C <= 0 || (C & 1) || (KS != 31 && KS != 7)) return SFM_ERR_SHAPE;
+  if (n_spans < B || n_spans > 65535 || n_spans > sum_T || sfm_dwconv_wgrad_varlen_scratch_floats(n_spans, C, KS) < 0)
+    return SFM_ERR_SHAPE;
+  if (dtype != SFM_DT_BF16 && dtype != SFM_DT_F16) return SFM_ERR_ARG;
+  dim3 grid((C + 255) / 256, n_spans, 1), block(128);
+  hipStream_t st = (hipStream_t)stream;
+  if (KS == 31 && C % 256 == 0 && (((uintptr_t)x | (uintptr_t)dy) % 16) == 0) {
+    if (dtype == SFM_DT_F16)
+      SFM_LAUNCH((dwconv_wgrad31_lds_kernel<F16, true>), grid, dim3(256), 0, st, (const u16*)x, dy, scratch, 0, C, B, frame_off, spans);
+    else
+      SFM_LAUNCH((dwconv_wgrad31_lds_kernel<BF16, true>), grid, dim3(256), 0, st, (const u16*)x, dy, scratch, 0, C, B, frame_off, spans);
+  } else {
+#define GO(TT, KK) SFM_LAUNCH((dwconv_wgrad_kernel<TT, KK, true>), grid, block, 0, st, (const u16*)x, dy, scratch, 0, C, B, frame_off, spans)
+    if (dtype == SFM_DT_F16) { if (KS == 31) GO(F16, 31); else GO(F16, 7); }
+    else { if (KS == 31) GO(BF16, 31); else GO(BF16, 7); }
+#undef GO
   }
-  return SFM_OK;
+  return dwconv_wgrad_fold(scratch, dw, db, n_spans, C, KS, st);
 }

@@ -179,17 +179,20 @@ class PackedSegments:
         self._tables = {}
 
     def tables(self, device, H=None):
-        """device int32 tensors: frame_off [B + 1], samp_off [B + 1] (None without lengths), conv_tiles [n, 2] - one upload - and,
-        when H is given, attn_items [n, 4] for H heads (a second one, the first time that H is asked for)"""
+        """device int32 tensors: frame_off [B + 1], samp_off [B + 1] (None without lengths), conv_tiles [n, 2], wgrad_spans [n, 3]
+        (the training step's depthwise weight gradient) - one upload - and, when H is given, attn_items [n, 4] for H heads (a
+        second one, the first time that H is asked for)"""
         t = self._tables.get(str(device))
         if t is None:
-            parts = [self.frame_offsets.astype(np.int32), ops.dwconv_tiles(self.frame_counts).reshape(-1)]
+            parts = [self.frame_offsets.astype(np.int32), ops.dwconv_tiles(self.frame_counts).reshape(-1),
+                     ops.dwconv_wgrad_spans(self.frame_counts).reshape(-1)]
             if self.sample_offsets is not None:
                 parts.append(self.sample_offsets.astype(np.int32))
             flat = torch.from_numpy(np.concatenate(parts)).to(device)
-            n0, n1 = parts[0].size, parts[1].size
+            n0, n1, n2 = parts[0].size, parts[1].size, parts[2].size
             t = self._tables[str(device)] = {"frame_off": flat[:n0], "conv_tiles": flat[n0:n0 + n1].view(-1, 2),
-                                             "samp_off": flat[n0 + n1:] if self.sample_offsets is not None else None}
+                                             "wgrad_spans": flat[n0 + n1:n0 + n1 + n2].view(-1, 3),
+                                             "samp_off": flat[n0 + n1 + n2:] if self.sample_offsets is not None else None}
         if H is not None and ("attn_items", H) not in t:
             t["attn_items", H] = torch.from_numpy(ops.attention_items(self.frame_counts, H)).to(device)
         return t
@@ -1010,6 +1013,21 @@ def ragged_plan(lengths):
     if plan is None:
         plan = _cache_put(_RAGGED_PLANS, key, RaggedPlan(key))
     return plan
+
+
+_FRAME_SEGMENTS = {}
+
+
+def packed_frames(frame_counts):
+    """the PackedSegments of a sequence of frame counts, cached by the counts (a PackedSegments passes through): a repeated
+    set of lengths finds its device tables uploaded, so a training step on it makes no host-device copy"""
+    if isinstance(frame_counts, PackedSegments):
+        return frame_counts
+    key = tuple(int(x) for x in (frame_counts.tolist() if hasattr(frame_counts, "tolist") else frame_counts))
+    seg = _FRAME_SEGMENTS.get(key)
+    if seg is None:
+        seg = _cache_put(_FRAME_SEGMENTS, key, PackedSegments(key))
+    return seg
 
 
 def _ragged_empty(*shape, device, dtype):

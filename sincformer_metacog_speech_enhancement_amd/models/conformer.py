@@ -115,12 +115,31 @@ class ConformerBlock(HipModule):
         y = Fn.block_forward(x.float().reshape(B * T, D).contiguous(), pk, B, T, self.num_heads)
         return y.reshape(B, T, D)
 
+    def forward_packed(self, x, frame_counts):
+        """forward() on packed rows: x [sum_T, D] holds utterances of different lengths back to back, `frame_counts` their frame
+        counts (a sequence, or the functional.PackedSegments of the pass) -> [sum_T, D].  Every utterance attends to and is
+        convolved over its own rows only.  eval() without autograd: the inference kernels; train() (or eval() under autograd):
+        the training node on packed rows, whose BatchNorm batch statistics run over the sum_T real frames."""
+        self._require_device(x)
+        seg = Fn.packed_frames(frame_counts)
+        if x.dim() != 2 or x.shape[0] != seg.sum_T:
+            raise RuntimeError("ConformerBlock.forward_packed: x %s, expected [%d, d_model] (the sum of the frame counts)" % (
+                tuple(x.shape), seg.sum_T))
+        if self.training or self._wants_autograd(x):
+            return self._train_forward(x, seg=seg)
+        pk = self._packed(lambda sd: Fn.pack_block(sd, self.num_heads))
+        return Fn.block_forward(x.float().contiguous(), pk, None, None, self.num_heads, seg=seg)
 
-    def _train_forward(self, x):
+    def _train_forward(self, x, seg=None):
         """Training mode (dropout active, BatchNorm batch statistics + running-stat update): one autograd node
         whose forward and backward run on the HIP kernels (train.ConformerBlockFunction).  The dropout seed is
-        drawn from torch's default CPU generator, so torch.manual_seed() makes a step reproducible."""
+        drawn from torch's default CPU generator, so torch.manual_seed() makes a step reproducible.
+        seg: x is [sum_T, D], the packed rows of that functional.PackedSegments."""
         from .. import train
+        if seg is not None:
+            # (before the seed is drawn and before the first launch)
+            train.check_packed_train(x.shape[-1], self.num_heads, {"conv.depthwise.weight": self.conv.depthwise.weight},
+                                     who="ConformerBlock.forward_packed")
         named = dict(self.named_parameters())
         params = [named[k] for k in train.PARAM_NAMES]
         bn = self.conv.batch_norm
@@ -130,6 +149,8 @@ class ConformerBlock(HipModule):
         p = float(self.ff1.dropout.p) if self.training else 0.0
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if p > 0 else 0
         meta = (self.num_heads, p, seed, buffers, float(bn.momentum or 0.1), float(bn.eps), not self.training)
+        if seg is not None:
+            meta += (seg,)
         return train.ConformerBlockFunction.apply(x, meta, *params)
 
 

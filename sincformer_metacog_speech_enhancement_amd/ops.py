@@ -967,6 +967,97 @@ def dwconv_folded_varlen(x16, wT, sc, sh, frame_off, tiles, B, max_T, sum_T, C, 
     return out
 
 
+# ---- training on packed rows: the three launches of a Conformer block's training step that see (B, T) -------------------------
+WGRAD_PARTIALS, WGRAD_MIN_SPAN = 2048, 32      # sfm_dwconv_wgrad's own aim: ~2048 partials, no span under 32 frames
+
+
+def dwconv_wgrad_spans(frame_counts):
+    """work table of sfm_dwconv_wgrad_varlen: int32 [n, 3] = (utterance, first frame, frame count), in utterance order.  Every
+    frame of every utterance lies in exactly one span and no span crosses an utterance.  Spans are cut for about WGRAD_PARTIALS
+    partials over the pack and at least WGRAD_MIN_SPAN frames each (an utterance's frames split evenly over its spans), which
+    on equal lengths is the dense launcher's own cut; n <= WGRAD_PARTIALS + B."""
+    T = np.asarray(frame_counts, dtype=np.int64).reshape(-1)
+    if T.size == 0 or int(T.min()) < 1:
+        raise ValueError("dwconv_wgrad_spans: at least one utterance and one frame per utterance")
+    span = max(WGRAD_MIN_SPAN, -(-int(T.sum()) // WGRAD_PARTIALS))
+    per = -(-T // (-(-T // span)))                                   # frames per span of each utterance: an even split
+    n = -(-T // per)
+    utt = np.repeat(np.arange(T.size), n)
+    k = np.arange(int(n.sum())) - np.repeat(np.cumsum(n) - n, n)
+    first = k * per[utt]
+    count = np.minimum(per[utt], T[utt] - first)
+    return np.ascontiguousarray(np.stack([utt, first, count], axis=1), dtype=np.int32)
+
+
+def _packed_attention_ok(qkv16, frame_off, items, B, max_T, sum_T, H, hd):
+    """the operands the packed training attention launches share: 16-bit rows [sum_T, >= 3 H hd] in the stage's format, the
+    offsets and the head_dim-64 item table"""
+    return (hd == 64 and H > 0 and 0 < B and 0 < max_T <= sum_T and
+            _is(qkv16, _state["dtype"], (sum_T, None), contig="last") and qkv16.shape[1] >= 3 * H * hd and
+            _is(frame_off, _I32, B + 1) and _is(items, _I32, (None, 4)))
+
+
+def attention_train_varlen(qkv16, frame_off, items, B, max_T, sum_T, H, hd, p_drop=0.0, seed=0, sum_T2=None, lse=None):
+    """attention_train() on packed rows (q pre-scaled, head_dim 64): qkv16 [sum_T, 3 H hd] -> O [sum_T, H hd] 16-bit and LSE
+    [H, sum_T] fp32 (log2 domain; `lse`: a buffer of at least that many elements to write it into).  items: device copy of
+    attention_items(frame_counts, H).  Dropout hashes row H * frame_off[u] + h * T_u + q: an equal-length pack is the dense
+    launch bit for bit.  sum_T2 = sum of T_u^2, for the stated cost."""
+    _need_dev(qkv16, frame_off, items, lse)
+    L = _lib.load()
+    D = H * hd
+    _ragged_check("attention_train_varlen", _packed_attention_ok(qkv16, frame_off, items, B, max_T, sum_T, H, hd) and
+                  0.0 <= p_drop < 1.0 and _is(lse, _F32, least=H * sum_T, opt=True))
+    out = torch.empty(sum_T, D, device=qkv16.device, dtype=qkv16.dtype)
+    lse = torch.empty(H, sum_T, device=qkv16.device, dtype=torch.float32) if lse is None else lse
+    _call("attention_fwd_varlen", L.sfm_attention_fwd_train_varlen,
+          (_p(qkv16), _p(out), _p(lse), _p(frame_off), _p(items), items.shape[0], B, max_T, sum_T, H, hd, qkv16.stride(0),
+           out.stride(0), D, 2 * D, -1.0, float(p_drop), int(seed) & 0xffffffff, _dt(), _stream()),
+          4.0 * H * hd * float(sum_T2 if sum_T2 is not None else 0), 4.0 * sum_T * D * 2)
+    return out, lse
+
+
+def attention_bwd_varlen(qkv16, O16, dO16, lse, frame_off, items, B, max_T, sum_T, H, hd, p_drop=0.0, seed=0, sum_T2=None,
+                         delta=None):
+    """attention_bwd() on packed rows (head_dim 64): -> dqkv like qkv16.  lse [H, sum_T] from attention_train_varlen, same
+    p_drop and seed; delta: the [H, sum_T] fp32 workspace (a buffer of at least that many elements), fresh when None."""
+    _need_dev(qkv16, O16, dO16, lse, frame_off, items, delta)
+    L = _lib.load()
+    D = H * hd
+    dt = _state["dtype"]
+    _ragged_check("attention_bwd_varlen", _packed_attention_ok(qkv16, frame_off, items, B, max_T, sum_T, H, hd) and
+                  0.0 <= p_drop < 1.0 and _is(O16, dt, (sum_T, None), contig="last") and O16.shape[1] >= D and
+                  _is(dO16, dt, (sum_T, None), contig="last") and dO16.shape[1] >= D and O16.stride(0) == dO16.stride(0) and
+                  _is(lse, _F32, least=H * sum_T) and _is(delta, _F32, least=H * sum_T, opt=True))
+    dqkv = torch.empty_like(qkv16)
+    delta = torch.empty(H, sum_T, device=qkv16.device, dtype=torch.float32) if delta is None else delta
+    _call("attention_bwd_varlen", L.sfm_attention_bwd_varlen,
+          (_p(qkv16), _p(O16), _p(dO16), _p(lse), _p(delta), _p(dqkv), _p(frame_off), _p(items), items.shape[0], B, max_T, sum_T,
+           H, hd, qkv16.stride(0), O16.stride(0), D, 2 * D, float(p_drop), int(seed) & 0xffffffff, _dt(), _stream()),
+          10.0 * H * hd * float(sum_T2 if sum_T2 is not None else 0), 8.0 * sum_T * D * 2)
+    return dqkv
+
+
+def dwconv_wgrad_varlen(x16, dy32, frame_off, spans, B, sum_T, C, KS, dw=None, db=None):
+    """dwconv_wgrad() on packed rows x16 / dy32 [sum_T, C]: -> dw [C, KS], db [C] (accumulated into dw / db when given), each
+    utterance's window zero outside its own frames.  spans: device copy of dwconv_wgrad_spans(frame_counts)."""
+    _need_dev(x16, dy32, frame_off, spans, dw, db)
+    L = _lib.load()
+    _ragged_check("dwconv_wgrad_varlen", KS in (7, 31) and C > 0 and C % 2 == 0 and 0 < B <= sum_T and
+                  _is(x16, _state["dtype"], (sum_T, C)) and _is(dy32, _F32, (sum_T, C)) and _is(frame_off, _I32, B + 1) and
+                  _is(spans, _I32, (None, 3)) and B <= spans.shape[0] <= min(sum_T, 65535) and
+                  _is(dw, _F32, (C, KS), opt=True) and _is(db, _F32, (C,), opt=True))
+    n = spans.shape[0]
+    dw = torch.zeros(C, KS, device=x16.device, dtype=torch.float32) if dw is None else dw
+    db = torch.zeros(C, device=x16.device, dtype=torch.float32) if db is None else db
+    floats = int(L.sfm_dwconv_wgrad_varlen_scratch_floats(n, C, KS))       # (a negative count is the launcher's status)
+    _lib.check(min(floats, 0), "dwconv_wgrad_varlen")
+    scratch = torch.empty(floats, device=x16.device, dtype=torch.float32)
+    _call("dwconv_wgrad_varlen", L.sfm_dwconv_wgrad_varlen,
+          (_p(x16), _p(dy32), _p(dw), _p(db), _p(scratch), _p(frame_off), _p(spans), n, B, sum_T, C, KS, _dt(), _stream()),
+          2.0 * sum_T * C * (KS + 1), sum_T * C * 6.0 + n * (KS + 1) * C * 8.0)
+    return dw, db
+
+
 def istft_ola_varlen(frames, win2, out, frame_off, samp_off, B, n_fft, hop, win, ld_frames):
     """istft_ola() on packed frames [sum_T, ld_frames] -> packed samples out [sum_L]"""
     _need_dev(frames, out, frame_off, samp_off)

@@ -150,7 +150,9 @@ def _ffn_bwd(dy, c, G, pre, do=None, nxt=None):
 # ---------------------------------------------------------------------------
 # MultiHeadSelfAttention (models/conformer.py:66-71)
 # ---------------------------------------------------------------------------
-def _mhsa_fwd(x, P, B, T, H, p, seeds):
+def _mhsa_fwd(x, P, B, T, H, p, seeds, seg=None):
+    """seg: a functional.PackedSegments - x holds its utterances back to back (B, T unused) and every utterance attends to its
+    own rows (ops.attention_train_varlen); None: B rows of T frames"""
     M, D = x.shape
     hd = D // H
     lw, lb = _f32(P["mhsa.layer_norm.weight"]), _f32(P["mhsa.layer_norm.bias"])
@@ -163,9 +165,15 @@ def _mhsa_fwd(x, P, B, T, H, p, seeds):
     h16 = _ln16(x, lw, lb)
     qkv = ops.linear16(h16, fin)
     sa, sd = seeds.next(), seeds.next()
-    O, lse = ops.attention_train(qkv, B, T, H, hd, p_drop=p, seed=sa)
+    if seg is None:
+        O, lse = ops.attention_train(qkv, B, T, H, hd, p_drop=p, seed=sa)
+    else:
+        tb = seg.tables(x.device, H)
+        O, lse = ops.attention_train_varlen(qkv, tb["frame_off"], tb["attn_items", H], seg.B, seg.max_T, seg.sum_T, H, hd,
+                                            p_drop=p, seed=sa, sum_T2=seg.sum_T2)
     y = _resid_gemm(O, fout, x, 1.0, p, sd)
-    return y, dict(x=x, lw=lw, h16=h16, qkv=qkv, O=O, lse=lse, bin=bin_, bout=bout, sa=sa, sd=sd, p=p, qs=qs, B=B, T=T, H=H)
+    return y, dict(x=x, lw=lw, h16=h16, qkv=qkv, O=O, lse=lse, bin=bin_, bout=bout, sa=sa, sd=sd, p=p, qs=qs, B=B, T=T, H=H,
+                   seg=seg)
 
 
 def _mhsa_bwd(dy, c, G, do=None, nxt=None):
@@ -174,7 +182,14 @@ def _mhsa_bwd(dy, c, G, do=None, nxt=None):
     do = _branch_grad(dy, do, 1.0, c["p"], c["sd"])
     ops.gemm16_tn(do, c["O"], G["mhsa.attention.out_proj.weight"], G["mhsa.attention.out_proj.bias"])
     dO = ops.linear16(do, c["bout"])                                         # 16-bit [M, D]
-    dqkv = ops.attention_bwd(c["qkv"], c["O"], dO, c["lse"], c["B"], c["T"], c["H"], D // c["H"], p_drop=c["p"], seed=c["sa"])
+    seg = c["seg"]
+    if seg is None:
+        dqkv = ops.attention_bwd(c["qkv"], c["O"], dO, c["lse"], c["B"], c["T"], c["H"], D // c["H"], p_drop=c["p"], seed=c["sa"])
+    else:
+        tb = seg.tables(dy.device, c["H"])
+        dqkv = ops.attention_bwd_varlen(c["qkv"], c["O"], dO, c["lse"], tb["frame_off"], tb["attn_items", c["H"]], seg.B,
+                                        seg.max_T, seg.sum_T, c["H"], D // c["H"], p_drop=c["p"], seed=c["sa"],
+                                        sum_T2=seg.sum_T2)
     gw, gb = G["mhsa.attention.in_proj_weight"], G["mhsa.attention.in_proj_bias"]
     # the Q rows of W were multiplied by qs in the forward: accumulate into scratch, then scale those rows
     tw = torch.zeros_like(gw)
@@ -195,12 +210,18 @@ def _mhsa_bwd(dy, c, G, do=None, nxt=None):
 TRAIN_DWCONV_KS = (7, 31)      # depthwise kernel sizes whose weight gradient sfm_dwconv_wgrad computes
 
 
-def _conv_fwd(x, P, B, T, p, seeds, bn_buffers, momentum=0.1, eps=1e-5, bn_eval=False):
+def _check_train_ks(P):
     KS = P["conv.depthwise.weight"].shape[-1]
     if KS not in TRAIN_DWCONV_KS:
         # refused here, before any launch and before the BatchNorm running statistics move, not in the backward
         raise NotImplementedError("ConvolutionModule training: depthwise kernel_size %d is not supported (the weight-gradient "
                                   "kernel takes kernel_size 7 or 31; eval() takes any odd kernel_size)" % KS)
+
+
+def _conv_fwd(x, P, B, T, p, seeds, bn_buffers, momentum=0.1, eps=1e-5, bn_eval=False, seg=None):
+    """seg: a functional.PackedSegments - x holds its utterances back to back (B, T unused): the depthwise conv has a zero edge
+    at every utterance's own ends and the BatchNorm batch statistics run over the M = sum_T real frames; None: B rows of T frames"""
+    _check_train_ks(P)
     dt = ops.compute_dtype()
     M, D = x.shape
     lw, lb = _f32(P["conv.layer_norm.weight"]), _f32(P["conv.layer_norm.bias"])
@@ -216,7 +237,12 @@ def _conv_fwd(x, P, B, T, p, seeds, bn_buffers, momentum=0.1, eps=1e-5, bn_eval=
     ops.ew_train(ops.EW_GLU_FWD, g16, z=pre)
     ones = torch.ones(D, device=x.device)
     yc = torch.empty(M, D, device=x.device, dtype=torch.float32)
-    ops.dwconv_folded(g16, wdw.t().contiguous(), ones, bdw, B, T, D, out=yc, act=0)   # conv + bias, fp32
+    if seg is None:
+        ops.dwconv_folded(g16, wdw.t().contiguous(), ones, bdw, B, T, D, out=yc, act=0)   # conv + bias, fp32
+    else:
+        tb = seg.tables(x.device)
+        ops.dwconv_folded_varlen(g16, wdw.t().contiguous(), ones, bdw, tb["frame_off"], tb["conv_tiles"], seg.B, seg.max_T,
+                                 seg.sum_T, D, out=yc, act=0)
     # statistics -> mean, rstd, folded affine and the running-statistics update (unbiased var, momentum) in one launch
     rm, rv = (bn_buffers[0], bn_buffers[1]) if bn_buffers is not None else (None, None)
     fp32_buffers = rm is not None and rm.dtype == torch.float32 and rv.dtype == torch.float32
@@ -235,7 +261,7 @@ def _conv_fwd(x, P, B, T, p, seeds, bn_buffers, momentum=0.1, eps=1e-5, bn_eval=
     sd = seeds.next()
     y = _resid_gemm(s16, f2, x, 1.0, p, sd)
     return y, dict(x=x, lw=lw, h16=h16, pre=pre, g16=g16, yc=yc, mean=mean, rstd=rstd, gam=gam, bet=bet, s16=s16, b1=b1, b2=b2,
-                   wdw=wdw, KS=KS, sd=sd, p=p, B=B, T=T, bn_eval=bn_eval)
+                   wdw=wdw, KS=KS, sd=sd, p=p, B=B, T=T, bn_eval=bn_eval, seg=seg)
 
 
 def _conv_bwd(dy, c, G, do=None, nxt=None):
@@ -248,7 +274,12 @@ def _conv_bwd(dy, c, G, do=None, nxt=None):
     dyc, dgam, dbet = ops.bn_swish_bwd(ds, c["yc"], c["mean"], c["rstd"], c["gam"], c["bet"], eval_mode=c["bn_eval"])
     G["conv.batch_norm.weight"] += dgam
     G["conv.batch_norm.bias"] += dbet
-    dw, db = ops.dwconv_wgrad(c["g16"], dyc, B, T, D, KS)
+    seg = c["seg"]
+    tb = None if seg is None else seg.tables(dy.device)
+    if seg is None:
+        dw, db = ops.dwconv_wgrad(c["g16"], dyc, B, T, D, KS)
+    else:
+        dw, db = ops.dwconv_wgrad_varlen(c["g16"], dyc, tb["frame_off"], tb["wgrad_spans"], seg.B, seg.sum_T, D, KS)
     G["conv.depthwise.weight"] += dw.view_as(G["conv.depthwise.weight"])
     G["conv.depthwise.bias"] += db
     # input gradient of the depthwise conv = correlation with the flipped taps
@@ -256,7 +287,11 @@ def _conv_bwd(dy, c, G, do=None, nxt=None):
     ops.convert_rows(dyc, dyc16, M, D, D, D, D)
     wflipT = torch.flip(c["wdw"], dims=[1]).t().contiguous()
     ones, zeros = torch.ones(D, device=dy.device), torch.zeros(D, device=dy.device)
-    dg = ops.dwconv_folded(dyc16, wflipT, ones, zeros, B, T, D, act=0)
+    if seg is None:
+        dg = ops.dwconv_folded(dyc16, wflipT, ones, zeros, B, T, D, act=0)
+    else:
+        dg = ops.dwconv_folded_varlen(dyc16, wflipT, ones, zeros, tb["frame_off"], tb["conv_tiles"], seg.B, seg.max_T, seg.sum_T, D,
+                                      act=0)
     dpre = torch.empty(M, 2 * D, device=dy.device, dtype=dt)
     ops.ew_train(ops.EW_GLU_BWD, dpre, z=c["pre"], g=dg, N=D)
     ops.gemm16_tn(dpre, c["h16"], G["conv.pointwise1.weight"].view(2 * D, D), G["conv.pointwise1.bias"])
@@ -267,11 +302,28 @@ def _conv_bwd(dy, c, G, do=None, nxt=None):
 # ---------------------------------------------------------------------------
 # whole block
 # ---------------------------------------------------------------------------
-def block_train_forward(x32, P, B, T, H, p, seed, bn_buffers=None, momentum=0.1, eps=1e-5, bn_eval=False):
+def check_packed_train(D, H, P=None, n_rows=None, seg=None, who="training on packed rows"):
+    """what a packed training step refuses, before its first launch: head_dim != 64 (the packed attention backward is the
+    head_dim-64 kernels'), a depthwise kernel size without a weight-gradient kernel, rows that are not the pack's sum_T"""
+    if D % H != 0 or D // H != 64:
+        raise NotImplementedError("%s: d_model %d with %d heads is head_dim %s; the packed attention kernels of the training "
+                                  "path take head_dim 64 only (rectangular batches train at any head_dim <= 256)" % (
+                                      who, D, H, D // H if D % H == 0 else "%.3g" % (D / H)))
+    if P is not None:
+        _check_train_ks(P)
+    if seg is not None and n_rows != seg.sum_T:
+        raise RuntimeError("%s: %d rows, expected sum_T = %d (the sum of the frame counts)" % (who, n_rows, seg.sum_T))
+
+
+def block_train_forward(x32, P, B, T, H, p, seed, bn_buffers=None, momentum=0.1, eps=1e-5, bn_eval=False, seg=None):
+    """seg: a functional.PackedSegments - x32 [sum_T, D] holds its utterances back to back and B, T are unused (None).  The four
+    launches that see (B, T) take their packed forms; every other launch is the same call on M = sum_T rows."""
+    if seg is not None:
+        check_packed_train(x32.shape[1], H, P, x32.shape[0], seg)
     seeds = _Seeds(seed)
     x1, c1 = _ffn_fwd(x32, P, "ff1.", p, seeds)
-    x2, c2 = _mhsa_fwd(x1, P, B, T, H, p, seeds)
-    x3, c3 = _conv_fwd(x2, P, B, T, p, seeds, bn_buffers, momentum, eps, bn_eval)
+    x2, c2 = _mhsa_fwd(x1, P, B, T, H, p, seeds, seg=seg)
+    x3, c3 = _conv_fwd(x2, P, B, T, p, seeds, bn_buffers, momentum, eps, bn_eval, seg=seg)
     x4, c4 = _ffn_fwd(x3, P, "ff2.", p, seeds)
     fw, fb = _f32(P["final_norm.weight"]), _f32(P["final_norm.bias"])
     y = torch.empty_like(x4)
@@ -301,26 +353,35 @@ def block_train_backward(dy32, ctx, P):
 
 
 class ConformerBlockFunction(torch.autograd.Function):
-    """y = ConformerBlock(x) in training mode; saved state lives on ctx as plain tensors (no autograd graph inside)."""
+    """y = ConformerBlock(x) in training mode; saved state lives on ctx as plain tensors (no autograd graph inside).
+    meta = (H, p, seed, bn_buffers, momentum, eps, bn_eval[, seg]): with seg, a functional.PackedSegments, x is [sum_T, D], the
+    utterances of the pack back to back, and so is y; without it (or seg None) x is [B, T, D]."""
 
     @staticmethod
     def forward(ctx, x, meta, *params):
-        B, T, D = x.shape
-        H, p, seed, bn_buffers, momentum, eps, bn_eval = meta
+        H, p, seed, bn_buffers, momentum, eps, bn_eval = meta[:7]
+        seg = meta[7] if len(meta) > 7 else None
         P = dict(zip(PARAM_NAMES, params))
-        x32 = x.detach().float().reshape(B * T, D).contiguous()
-        y, saved = block_train_forward(x32, P, B, T, H, p, seed, bn_buffers, momentum, eps, bn_eval)
-        ctx.saved, ctx.P, ctx.in_dtype, ctx.shape = saved, P, x.dtype, (B, T, D)
+        if seg is None:
+            B, T, D = x.shape
+        else:
+            if x.dim() != 2:
+                raise RuntimeError("ConformerBlockFunction on packed rows: x %s, expected [sum_T, D]" % (tuple(x.shape),))
+            (B, T), D = (None, None), x.shape[1]
+        M = x.numel() // D
+        x32 = x.detach().float().reshape(M, D).contiguous()
+        y, saved = block_train_forward(x32, P, B, T, H, p, seed, bn_buffers, momentum, eps, bn_eval, seg=seg)
+        ctx.saved, ctx.P, ctx.in_dtype, ctx.shape = saved, P, x.dtype, tuple(x.shape)
         ctx.param_dtypes = [t.dtype for t in params]
-        return y.reshape(B, T, D).to(x.dtype)
+        return y.reshape(ctx.shape).to(x.dtype)
 
     @staticmethod
     def backward(ctx, dy):
-        B, T, D = ctx.shape
-        dx, G = block_train_backward(dy.detach().float().reshape(B * T, D).contiguous(), ctx.saved, ctx.P)
+        D = ctx.shape[-1]
+        dx, G = block_train_backward(dy.detach().float().reshape(-1, D).contiguous(), ctx.saved, ctx.P)
         grads = [G[k].to(dt_) for k, dt_ in zip(PARAM_NAMES, ctx.param_dtypes)]
         ctx.saved = None
-        return (dx.reshape(B, T, D).to(ctx.in_dtype), None) + tuple(grads)
+        return (dx.reshape(ctx.shape).to(ctx.in_dtype), None) + tuple(grads)
 
 
 # ---------------------------------------------------------------------------

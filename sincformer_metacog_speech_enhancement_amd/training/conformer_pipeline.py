@@ -473,6 +473,38 @@ class SpeechEnhancer(HipModule):
         ops.polar_mask(logits, logits[:, F:], 1, M, F, math.pi / 6, logits.stride(0), nr=nr, ni=ni, er=er, ei=ei, mmag=mm, ld_enh=F)
         return er, ei, mm
 
+    def forward_packed_train(self, noisy_real, noisy_imag, frame_counts):
+        """The trainable door to packed batches: _train_forward with the blocks on packed rows.  noisy_real / noisy_imag
+        [sum_T, F] hold the spectra of utterances of different lengths back to back, `frame_counts` their frame counts (a
+        sequence, or the functional.PackedSegments of the pass).  Returns (enh_real, enh_imag, mask_mag), each [sum_T, F], through
+        the same chain of autograd nodes as forward() in train(): LNLinearFunction -> blocks -> LNLinearFunction ->
+        PolarMaskFunction.  Attention and the depthwise conv stay inside an utterance; BatchNorm's batch statistics run over
+        the sum_T real frames.  In eval() the nodes run without dropout and on the running statistics.  head_dim 64 only."""
+        from .. import train
+        self._require_device(noisy_real, noisy_imag)
+        seg = Fn.packed_frames(frame_counts)
+        if noisy_real.dim() != 2 or noisy_real.shape != noisy_imag.shape or noisy_real.shape[0] != seg.sum_T or \
+                noisy_real.shape[1] != self.n_freq:
+            raise RuntimeError("forward_packed_train: spectra %s / %s, expected [%d, %d] (sum of the frame counts x n_freq)" % (
+                tuple(noisy_real.shape), tuple(noisy_imag.shape), seg.sum_T, self.n_freq))
+        for block in self.blocks:                         # every refusal before the first launch
+            train.check_packed_train(self.input_proj.out_features, self.num_heads,
+                                     {"conv.depthwise.weight": block.conv.depthwise.weight}, who="forward_packed_train")
+        nr, ni = noisy_real.float().contiguous(), noisy_imag.float().contiguous()
+        M, F = nr.shape
+        ldc = ops.round_up(2 * F, 8)
+        cat = torch.empty(M, ldc, device=nr.device, dtype=torch.float32)
+        ops.pack_spec(nr, ni, cat, M, F, ldc, F)
+        x = train.LNLinearFunction.apply(cat, self.input_norm.weight, self.input_norm.bias, self.input_proj.weight,
+                                         self.input_proj.bias)
+        for block in self.blocks:
+            x = block._train_forward(x, seg=seg)
+        heads_w = torch.cat([self.mag_head.weight, self.phase_head.weight], dim=0)
+        heads_b = torch.cat([self.mag_head.bias, self.phase_head.bias], dim=0)
+        logits = train.LNLinearFunction.apply(x, self.output_norm.weight, self.output_norm.bias, heads_w, heads_b)
+        er, ei, mm = train.PolarMaskFunction.apply(logits, nr.unsqueeze(0), ni.unsqueeze(0), math.pi / 6)
+        return er.squeeze(0), ei.squeeze(0), mm.squeeze(0)
+
     # LayerNorm over 2F needs D passed explicitly: ops.layernorm infers D from x32.shape[1]
     # (cat has ldc >= 2F columns), so view the valid columns.
 
